@@ -16,13 +16,26 @@ mels, hop 80) per GPU; utterances shard across GPUs with no data-path collective
 The timed loop replays a HIP graph of the forward (pwv_amd/graph.py; --no-graph enqueues every launch from the
 host); the logistic sampler is a node of that graph and draws a fresh counter range on every replay.
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus
+A plain run does only what the headline figure needs: set up, warm up, time --steps steps, write the outputs of the last
+timed step if --dump-outputs DIR is given, print the result line.  It prints ONE JSON line (rank 0) with the driver's
+contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step, ...) and the whole-model `model` figures
+(arithmetic on `value`, no runs of their own).
+
+--dump-outputs DIR: what the timed path computed in its last timed step -- the waveform [utterances, samples, 1] a caller
+receives -- as DIR/waveform.npy (float32; with N > 1 ranks, rank r > 0 writes waveform_rank<r>.npy).  The inputs (mel, weights,
+noise stream) are seeded, so the same arguments give the same inputs on every run.  An output beyond 64 MB is written as
+a fixed, seeded sample of its elements (<name>_sample.npy).
+
+--full adds everything else the benchmark measures, each in runs of its own after the timed steps:
+  f32_exact     -- the same workload in exact fp32 MFMA, timed the same way
+  job           -- (N > 1, or PWV_BENCH_FORCE_DIST=1) the sharded job: mels on rank 0 -> scatter -> forward -> gather
   roofline      -- the dominant kernel (fused gated-residual layer): algorithmic bytes (512 B per sample, net and
                    layer) per launch x concurrent launches / its mean launch duration, measured live with HIP events
                    the library records on the launch streams around each chain's run of residual-layer launches
                    (pwv_stack_args.ev_begin / ev_end, production launch path) against 8 TB/s; `traffic` = HBM bytes per
                    launch from the committed PMC passes (profiles/); the matrix-pipe view is beside it as roofline_mfma
                    (with --precision f32 the roles swap: fp32 MFMA roofline, HBM view beside it)
+  range_guard   -- (f16x3) limit / observed maximum per fp16 operand class of this workload
   short_input   -- (N=1, default workload) the same model on ONE utterance of 16000 samples under graph replay: the latency-bound end of the
                    path, where the persistent launch takes its short-input instantiation; reported beside `value`, never part of it
   cpu_baseline  -- the oracle's torch-CPU fp32 port of the same model timed on this host's cores on a bounded sample
@@ -63,11 +76,19 @@ LIMITER_K1P = ('neither nominal roof binds: by arithmetic intensity (3 x 80 = 24
                '256 MB Infinity Cache (C4, C5) run the unit at the same rate as C3, so HBM residency is not the limit either')
 
 
+DUMP_LIMIT_BYTES = 64 << 20       # --dump-outputs: all files together
+
+
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=20)
-    ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--steps', type=int, default=20, help='timed steps')
+    ap.add_argument('--warmup', type=int, default=3, help='untimed steps before them')
+    ap.add_argument('--full', action='store_true',
+                    help='beside the headline figure, also measure f32_exact, the sharded job (N > 1), the live kernel timing / '
+                         'roofline, range_guard, short_input and cpu_baseline (each in runs of its own, after the timed steps)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the timed path computed in its last timed step as DIR/<name>.npy (float32)')
     ap.add_argument('--case', default='bench/c3', help='hparams case (bench/c1..c5, default, test/tran ...)')
     ap.add_argument('--length', type=int, default=0, help='override samples per utterance')
     ap.add_argument('--utts', type=int, default=0, help='override utterances per GPU')
@@ -83,7 +104,23 @@ def parse_args():
     ap.add_argument('--cpu-seconds', type=float, default=15.0, help='target CPU time of the cpu_baseline sample')
     ap.add_argument('--no-f32-exact', action='store_true', help="skip the second timing of the same workload in exact fp32 ('f32_exact')")
     ap.add_argument('--cpu-baseline-child', action='store_true', help=argparse.SUPPRESS)      # (internal: the cpu_baseline leg in a clean process)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    return args
+
+
+def dump_outputs(directory, arrays, budget):
+    """--dump-outputs: every array as DIR/<name>.npy in float32.  One that is larger than its share of `budget` is written as a
+    fixed, seeded sample of its elements instead (DIR/<name>_sample.npy: flat, in index order, the same indices on every run)."""
+    os.makedirs(directory, exist_ok=True)
+    share = budget // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a, name = a.reshape(-1)[idx], name + '_sample'
+        np.save(os.path.join(directory, name + '.npy'), a)
 
 
 def spawn_ranks(n):
@@ -392,9 +429,10 @@ def main():
         model0 = IAFVocoder(batch_size=utts, length=length, store=store, precision=args.precision)
         model0.noise_seed = 1 + (0 if time_shard else rank)
         model0(None, mel, is_training=False, verify=False)            # creates the variables
+        gb = torch.Generator(device=dev).manual_seed(3)               # seeded: the same biases on every run (--dump-outputs)
         for name in list(store.vars):
             if store.vars[name].dim() == 1:
-                store.vars[name].normal_(0, 0.1, generator=None)
+                store.vars[name].normal_(0, 0.1, generator=gb)
         store.version += 1
         engine.clear_plan_cache()
 
@@ -492,10 +530,15 @@ def main():
 
     (step, eager_step, graphed), elapsed, out = timed_verified(args.precision, args.warmup, args.steps)
     assert torch.isfinite(out).all(), 'non-finite output'
+    if args.dump_outputs:
+        # `out` is the timed path's own result of its last step (a graph replay returns its output buffer): copy it out before
+        # anything else runs
+        dump_outputs(args.dump_outputs, {'waveform' if rank == 0 else 'waveform_rank%d' % rank: out.detach().float().cpu().numpy()},
+                     DUMP_LIMIT_BYTES // world)
 
     # ---- the same workload in the reference's own arithmetic (exact fp32 MFMA), timed the same way ------------------
     f32_exact = None
-    if args.precision == 'f16x3' and not args.no_f32_exact and not control:
+    if args.full and args.precision == 'f16x3' and not args.no_f32_exact and not control:
         n32 = max(3, min(args.steps, 10))
         (step32, _, graphed32), e32, out32 = timed_verified('f32', 2, n32)
         assert torch.isfinite(out32).all()
@@ -544,7 +587,7 @@ def main():
             times = [float(v) for v in t.tolist()]
         return w_, sorted(times)[len(times) // 2], times
 
-    if dist is not None and time_shard is not None:
+    if args.full and dist is not None and time_shard is not None:
         from pwv_amd.distributed import generate_time_sharded_ranks
         coll_dev = torch.device('cpu') if dryrun else dev
         jt = 1 + job_length // hop
@@ -570,7 +613,7 @@ def main():
                 utts, job_length, time_shard['shards'], time_shard['halo'])
             job = {'what': 'distributed.generate_time_sharded_ranks: mel on rank 0 -> slices to the ranks -> verified forward per rank -> waveform gathered on rank 0',
                    'samples': job_samples}
-    elif dist is not None:
+    elif args.full and dist is not None:
         from pwv_amd.distributed import generate_sharded
         total = utts * world
         coll_dev = torch.device('cpu') if dryrun else dev        # gloo (test hooks) scatters / gathers host tensors only
@@ -601,7 +644,7 @@ def main():
 
     # ---- live kernel timing of the dominant kernel (HIP events on the launch streams) --------------------------------
     timing = None
-    if not control:
+    if args.full and not control:
         for attempt in (0, 1):
             engine.EVENT_LOG = []
             ref = torch.cuda.Event(enable_timing=True)
@@ -811,7 +854,7 @@ def main():
                 'value': v32, 'unit': 'samples/s', 'ms_per_step': e32 / n32 * 1e3, 'steps': n32,
                 'alg_TFLOPs': mf * v32 / n_gpus / 1e12, 'mfma_frac': mf * v32 / n_gpus / 1e12 / PEAK_F32_MFMA_TFLOPS,
                 'launch': 'HIP graph replay' if g32 else 'host-enqueued launches'}
-        if not control and args.precision == 'f16x3':
+        if args.full and not control and args.precision == 'f16x3':
             # how far this workload stays from the range guard of the split-fp16 arithmetic (untimed, one eager forward with the
             # run-time maxima read back): limit / observed per operand class, `range_margin` = the smallest (engine.range_report)
             try:
@@ -824,7 +867,7 @@ def main():
                                                  'would be rerun in exact fp32 (f32_exact is that path)'}
             except Exception as e:
                 sys.stderr.write('range report failed (%s: %s)\n' % (type(e).__name__, e))
-        if n_gpus == 1 and not control and not dryrun and args.precision == 'f16x3' and not args.no_f32_exact and length > 16000 and not args.length:
+        if args.full and n_gpus == 1 and not control and not dryrun and args.precision == 'f16x3' and not args.no_f32_exact and length > 16000 and not args.length:
             # the SAME model on one SHORT utterance (16000 samples: the latency-bound end of the path, where the persistent launch takes its
             # short-input instantiation -- csrc/pwv_stack_persist.hip, DESIGN.md section 4 "Short inputs"), untimed by the contract, reported beside it
             try:
@@ -851,7 +894,7 @@ def main():
                                          'hbm_frac_of_8TBs': mb * ls / es / 1e9 / PEAK_HBM_GBS}
             except Exception as e:
                 sys.stderr.write('short-input leg failed (%s: %s)\n' % (type(e).__name__, e))
-        if n_gpus == 1 and not args.no_cpu_baseline and not control:
+        if args.full and n_gpus == 1 and not args.no_cpu_baseline and not control:
             from oracle.iaf_oracle import ModelConfig          # the oracle is only ever the CPU leg, never the timed path
             result['cpu_baseline'] = cpu_baseline(args.case, ModelConfig.from_hparam(hp), args.cpu_seconds)
     if dist is not None:

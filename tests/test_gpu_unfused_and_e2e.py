@@ -442,7 +442,7 @@ def test_bench_multi_rank_control_flow_on_one_gpu():
     env = dict(os.environ, PWV_BENCH_DRYRUN_ONE_GPU='1')
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT'):
         env.pop(k, None)
-    tail = [os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--case', 'bench/c1', '--no-cpu-baseline']
+    tail = [os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--case', 'bench/c1', '--no-cpu-baseline', '--full']
     launcher = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
                 '--master-port', str(port)]
     for cmd in (launcher + tail, [sys.executable] + tail):
@@ -470,7 +470,7 @@ def test_bench_takes_every_rccl_branch_at_world_size_one(extra, want):
     env = dict(os.environ, PWV_BENCH_FORCE_DIST='1')
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT', 'PWV_BENCH_DRYRUN', 'PWV_BENCH_DRYRUN_ONE_GPU'):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--no-cpu-baseline', '--no-f32-exact'] + extra
+    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--no-cpu-baseline', '--no-f32-exact', '--full'] + extra
     res = subprocess.run(cmd, env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith('{')]
@@ -481,6 +481,29 @@ def test_bench_takes_every_rccl_branch_at_world_size_one(extra, want):
     # ... and the job-level number next to the forward-only `value`: rank 0's inputs -> RCCL scatter -> verified forward -> gather
     job = j['job']
     assert job['calls'] == 5 and job['job_samples_per_s'] > 0 and job['job_samples_per_s'] < 1.05 * j['value']
+
+
+def test_bench_dumped_outputs_repeat_from_run_to_run(gpu, tmp_path):
+    """`bench.py --dump-outputs DIR` twice with the same arguments, each in a fresh process: the seeded inputs (mel, weights,
+    biases, noise stream) make the last timed step's waveform bit-identical, so two builds can be compared output for output."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT', 'PWV_BENCH_DRYRUN', 'PWV_BENCH_DRYRUN_ONE_GPU', 'PWV_BENCH_FORCE_DIST'):
+        env.pop(k, None)
+    got = []
+    for k in range(2):
+        d = str(tmp_path / ('run%d' % k))
+        cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '4', '--warmup', '1', '--case', 'bench/c1', '--dump-outputs', d]
+        res = subprocess.run(cmd, env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        assert res.returncode == 0, res.stderr[-3000:]
+        j = json.loads([l for l in res.stdout.splitlines() if l.startswith('{')][-1])
+        assert j['steps'] == 4 and j['ms_per_step'] > 0
+        got.append(np.load(os.path.join(d, 'waveform.npy')))
+    assert got[0].shape == (1, 16000, 1) and got[0].dtype == np.float32 and np.isfinite(got[0]).all()
+    assert np.array_equal(got[0], got[1])
 
 
 def test_device_mel_frontend_matches_numpy_restatement(gpu):

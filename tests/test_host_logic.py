@@ -163,7 +163,7 @@ def test_bench_spawns_its_own_ranks_when_started_without_a_launcher():
     env = dict(os.environ, PWV_BENCH_DRYRUN='control')
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT'):
         env.pop(k, None)
-    res = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1'],
+    res = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--full'],
                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith('{')]
@@ -189,7 +189,7 @@ def test_bench_time_sharded_mode_is_strong_scaling():
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT'):
         env.pop(k, None)
     res = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--case', 'bench/c5', '--gpus', '2', '--shard', 'time',
-                          '--steps', '2', '--warmup', '1'], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, timeout=600)
+                          '--steps', '2', '--warmup', '1', '--full'], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     out = json.loads([l for l in res.stdout.splitlines() if l.startswith('{')][0])
     assert out['n_gpus'] == 2 and out['scaling'] == 'strong'
@@ -197,6 +197,47 @@ def test_bench_time_sharded_mode_is_strong_scaling():
     assert 'cut into 2 time shards' in out['sharded_generate']
     assert out['job']['samples'] == 960000 and 'generate_time_sharded_ranks' in out['job']['what'] and out['job']['job_samples_per_s'] > 0
     assert abs(out['value'] * out['ms_per_step'] * 1e-3 - 960000) < 1.0          # the job's samples, counted once per step
+
+
+def test_bench_plain_run_times_only_the_steps_and_dumps_the_last_one(tmp_path):
+    """`python bench.py --gpus 1 --steps N --warmup W --dump-outputs DIR` without --full: the contract fields, N timed steps,
+    none of the extra legs, and the last timed step's waveform as DIR/waveform.npy.  Control-flow dry run (no kernels)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, PWV_BENCH_DRYRUN='control')
+    for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_PORT', 'PWV_BENCH_FORCE_DIST'):
+        env.pop(k, None)
+    res = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
+                          '--dump-outputs', str(tmp_path / 'out')], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, timeout=600)
+    assert res.returncode == 0, res.stderr[-2000:]
+    lines = [l for l in res.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1, res.stdout
+    out = json.loads(lines[0])
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+        assert k in out, k
+    assert out['steps'] == 3 and out['warmup'] == 1 and out['unit'] == 'samples/s' and out['higher_is_better'] is True
+    assert abs(out['value'] * out['ms_per_step'] * 1e-3 - 160000) < 1.0
+    for k in ('f32_exact', 'roofline', 'range_guard', 'short_input', 'cpu_baseline', 'job'):
+        assert k not in out, k
+    assert sorted(os.listdir(tmp_path / 'out')) == ['waveform.npy']
+    w = np.load(tmp_path / 'out' / 'waveform.npy')
+    assert w.shape == (1, 160000, 1) and w.dtype == np.float32
+
+
+def test_bench_dump_outputs_samples_what_exceeds_the_budget(tmp_path):
+    """An output larger than its share of the --dump-outputs budget is written as a fixed, seeded sample of its elements."""
+    import bench
+    a = np.arange(3000, dtype=np.float64).reshape(3, 1000)
+    small = np.ones((2, 5), dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / 'x'), {'big': a, 'small': small}, budget=2 * 4 * 500)
+    bench.dump_outputs(str(tmp_path / 'y'), {'big': a, 'small': small}, budget=2 * 4 * 500)
+    assert sorted(os.listdir(tmp_path / 'x')) == ['big_sample.npy', 'small.npy']
+    s = np.load(tmp_path / 'x' / 'big_sample.npy')
+    assert s.dtype == np.float32 and s.shape == (500,) and np.all(np.diff(s) > 0) and np.isin(s, a).all()
+    assert np.array_equal(s, np.load(tmp_path / 'y' / 'big_sample.npy'))
+    assert np.array_equal(np.load(tmp_path / 'x' / 'small.npy'), small)
 
 
 @pytest.mark.parametrize('case,precision,name', [('bench/c3', 'f16x3', 'c3'), ('bench/c4', 'f16x3', 'c4'), ('bench/c5', 'f16x3', 'c5'), ('bench/c5', 'f16', 'c5_f16')])

@@ -4,7 +4,7 @@
 echo "| config (per GPU) | precision | samples/s | x real-time @22.05 kHz | ms/step | K1 roofline frac | whole-model frac of 8 TB/s |"
 echo "|---|---|---|---|---|---|---|"
 run() {
-python bench.py --no-cpu-baseline --no-f32-exact "$@" 2>/dev/null < /dev/null | python -c "
+python bench.py --full --no-cpu-baseline --no-f32-exact "$@" 2>/dev/null < /dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

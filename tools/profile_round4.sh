@@ -11,14 +11,14 @@ tag=${1:-r04_x}
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/${tag}_profiles
 mkdir -p $O
-B="python $R/bench.py --no-cpu-baseline --no-f32-exact"
+B="python $R/bench.py --full --no-cpu-baseline --no-f32-exact"
 SQ="SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_SALU GRBM_GUI_ACTIVE"
 run_stats() {   # name, env..., -- bench args
     local name=$1; shift; local envs=(); while [ "$1" != "--" ]; do envs+=("$1"); shift; done; shift
     cd /tmp; env "${envs[@]}" timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p4_$name -- $B --steps 10 --warmup 2 "$@" > /tmp/p4_${name}_stats.log 2>&1 < /dev/null
     cd $R; cp "$(find /tmp/p4_$name -name '*kernel_stats.csv' | head -1)" /tmp/p4_${name}_stats.csv
     python tools/summarize_rocprof.py /tmp/p4_${name}_stats.csv $O/${tag}_${name}_kernel_stats.md \
-        "rocprofv3 --kernel-trace --stats -- ${envs[*]} python bench.py --no-cpu-baseline --no-f32-exact --steps 10 --warmup 2 $*"
+        "rocprofv3 --kernel-trace --stats -- ${envs[*]} python bench.py --full --no-cpu-baseline --no-f32-exact --steps 10 --warmup 2 $*"
     rm -rf /tmp/p4_$name
 }
 run_pmc() {     # name, "counters", -- bench args   -> /tmp/p4_<name>.csv
@@ -37,7 +37,7 @@ done
 run_stats c3_perlayer PWV_PERSIST=0 -- --case bench/c3
 run_stats c3_f32 -- --case bench/c3 --precision f32
 cd $R; PWV_PERSIST=0 $B --steps 20 --warmup 3 > $O/${tag}_c3_perlayer_bench.json 2> /dev/null < /dev/null
-python bench.py > $O/${tag}_bench_default.json 2> /tmp/p4_bench_default.err < /dev/null
+python bench.py --full > $O/${tag}_bench_default.json 2> /tmp/p4_bench_default.err < /dev/null
 python tools/profile_round4_summarize.py $O /tmp $tag > $O/${tag}_configs.md
 STEPS=9000 tools/power_sample.sh > $O/${tag}_power_clock.txt 2>&1
 ls -la $O
