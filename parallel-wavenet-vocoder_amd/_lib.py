@@ -8,6 +8,7 @@ through a CPU implementation.
 from __future__ import annotations
 
 import ctypes
+import hashlib
 import os
 import subprocess
 from ctypes import POINTER, Structure, c_char_p, c_int, c_int64, c_size_t, c_uint64, c_void_p
@@ -178,47 +179,86 @@ for _e in os.environ.get('PWV_EXTRA_SRC', '').split():
     EXTRA_FLAGS[os.path.basename(_src)] = [f for f in _fl.split(',') if f]
 
 
+OBJ_DIR = os.path.join(_PKG_DIR, 'csrc', '_obj')
+
+
+def _digest(parts) -> str:
+    return hashlib.sha256('\0'.join(parts).encode()).hexdigest()[:16]
+
+
 def build_library(force: bool = False, verbose: bool = False) -> str:
-    """Compile the HIP sources for gfx950 into the in-tree shared library (one object per source, compiled in parallel and
-    reused while the source and the headers are older than it)."""
+    """Compile the HIP sources for gfx950 into the in-tree shared library: one object per source, compiled in parallel.
+
+    An object is named after a hash of its whole compile command (HIPCC, flags, EXTRA_FLAGS, PWV_CXXFLAGS) and reused while it is
+    newer than its source and the headers; the library is rebuilt unless the hash of its link command, kept next to the objects,
+    matches.  Objects and the library are written under temporary names and renamed into place, and builders in different
+    processes take turns on a lock file, so no process links or loads a half-written file."""
+    import fcntl
     from concurrent.futures import ThreadPoolExecutor
-    hdrs = [os.path.join(_PKG_DIR, 'csrc', h) for h in ('pwv_common.h', 'pwv_layer_common.h', 'pwv_f16x3.h')] + [os.path.join(_REPO_ROOT, 'include', 'pwv_hip.h')]
     if os.environ.get('PWV_LIB'):
         return LIB_PATH            # an explicitly chosen library is never rebuilt
-    if not force and os.path.exists(LIB_PATH):
-        if all(os.path.getmtime(LIB_PATH) >= os.path.getmtime(s) for s in CSRC + hdrs):
-            return LIB_PATH
+    hdrs = [os.path.join(_PKG_DIR, 'csrc', h) for h in ('pwv_common.h', 'pwv_layer_common.h', 'pwv_f16x3.h')] + [os.path.join(_REPO_ROOT, 'include', 'pwv_hip.h')]
+    hdr_time = max(os.path.getmtime(h) for h in hdrs + [os.path.abspath(__file__)])
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-    objdir = os.path.join(_PKG_DIR, 'csrc', '_obj')
-    os.makedirs(objdir, exist_ok=True)
     # ONE gfx950 code object for the XNACK mode an MI355X runs in by default (xnack-): code built for a known mode instead of
     # 'either' is 0.5 % faster on the bench step; xnack+ objects (XNACK-on runs) are not available on the GPU pool
     base = [hipcc, '--offload-arch=gfx950:xnack-', '-O3', '-std=c++17', '-fPIC',
             '-I' + os.path.join(_REPO_ROOT, 'include'), '-I' + os.path.join(_PKG_DIR, 'csrc')]
     extra = os.environ.get('PWV_CXXFLAGS', '').split()
-    hdr_time = max(os.path.getmtime(h) for h in hdrs + [os.path.abspath(__file__)])
+    compiles = []                  # (source, object, command without the output)
+    for src in CSRC:
+        cmd = base + EXTRA_FLAGS.get(os.path.basename(src), []) + extra + ['-c', src]
+        compiles.append((src, os.path.join(OBJ_DIR, '%s.%s.o' % (os.path.basename(src), _digest(cmd))), cmd))
+    link = [hipcc, '--offload-arch=gfx950:xnack-', '-shared', '-fPIC'] + [o for _, o, _ in compiles]
+    link_hash = _digest(link)
+    stamp = os.path.join(OBJ_DIR, os.path.basename(LIB_PATH) + '.inputs')
+    newest = max([hdr_time] + [os.path.getmtime(s) for s in CSRC])
 
-    def compile_one(src):
-        obj = os.path.join(objdir, os.path.basename(src) + ('.' + '_'.join(extra).replace('/', '_') if extra else '') + '.o')
-        if not force and os.path.exists(obj) and os.path.getmtime(obj) >= max(os.path.getmtime(src), hdr_time):
-            return obj, None
-        cmd = base + EXTRA_FLAGS.get(os.path.basename(src), []) + extra + ['-c', src, '-o', obj]
-        if verbose:
-            print(' '.join(cmd))
-        res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        return obj, (res.stdout if res.returncode != 0 else None)
+    def fresh():
+        try:
+            with open(stamp) as f:
+                return f.read().strip() == link_hash and os.path.getmtime(LIB_PATH) >= newest
+        except OSError:
+            return False
 
-    with ThreadPoolExecutor(max_workers=min(len(CSRC), os.cpu_count() or 4)) as ex:
-        results = list(ex.map(compile_one, CSRC))
-    for obj, err in results:
+    if not force and fresh():
+        return LIB_PATH
+    os.makedirs(OBJ_DIR, exist_ok=True)
+    with open(os.path.join(OBJ_DIR, '.lock'), 'w') as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)          # one builder at a time; the others then find its result fresh
+        if not force and fresh():
+            return LIB_PATH
+
+        def run(cmd, out):
+            tmp = '%s.tmp%d' % (out, os.getpid())
+            if verbose:
+                print(' '.join(cmd + ['-o', out]))
+            res = subprocess.run(cmd + ['-o', tmp], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+            if res.returncode != 0:
+                if os.path.exists(tmp):
+                    os.remove(tmp)
+                return res.stdout
+            os.replace(tmp, out)
+            return None
+
+        def compile_one(job):
+            src, obj, cmd = job
+            if not force and os.path.exists(obj) and os.path.getmtime(obj) >= max(os.path.getmtime(src), hdr_time):
+                return None
+            return run(cmd, obj)
+
+        # the GPU hosts show the whole machine's CPUs; a build gets 16 of them at most
+        jobs = min(len(compiles), 16, int(os.environ.get('MAX_JOBS') or 16), os.cpu_count() or 4)
+        with ThreadPoolExecutor(max_workers=max(jobs, 1)) as ex:
+            errors = [e for e in ex.map(compile_one, compiles) if e is not None]
+        if errors:
+            raise PwvError('hipcc failed:\n' + errors[0])
+        err = run(link, LIB_PATH)
         if err is not None:
-            raise PwvError('hipcc failed:\n' + err)
-    cmd = [hipcc, '--offload-arch=gfx950:xnack-', '-shared', '-fPIC', '-o', LIB_PATH] + [o for o, _ in results]
-    if verbose:
-        print(' '.join(cmd))
-    res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    if res.returncode != 0:
-        raise PwvError('hipcc (link) failed:\n' + res.stdout)
+            raise PwvError('hipcc (link) failed:\n' + err)
+        with open(stamp + '.tmp', 'w') as f:
+            f.write(link_hash + '\n')
+        os.replace(stamp + '.tmp', stamp)
     return LIB_PATH
 
 

@@ -61,12 +61,11 @@ __device__ __forceinline__ void load_skip_row(const LayerParams& p, int net, int
     }
 }
 
-// SK_NOW = false: the skip-sum row is NOT loaded with the tile (8-wave kernels request it in front of GEMM2 / the gating instead:
-// its 64 registers next to x[t-d], x[t], P and the per-sample condition at the top of the unit were the 27-35 spilled VGPRs of the
-// SKIP + COND variants)
-template <bool SKIP, bool COND, bool FIRST = false, bool SK_NOW = true>
-__device__ __forceinline__ void load_tile(const LayerParams& p, int net, int unit, int lane,
-                                          TileRegs<SKIP, COND>& r, bool skip_load) {
+// The skip-sum row is NOT loaded with the tile (the kernel requests it in front of GEMM2 / the gating instead: its 64 registers
+// next to x[t-d], x[t], P and the per-sample condition at the top of the unit were the 27-35 spilled VGPRs of the SKIP + COND
+// variants)
+template <bool SKIP, bool COND, bool FIRST>
+__device__ __forceinline__ void load_tile(const LayerParams& p, int net, int unit, int lane, TileRegs<SKIP, COND>& r) {
     const int h = lane >> 5;
     const int rows = p.N * p.T;
     const int row = unit * 32 + (lane & 31);
@@ -95,31 +94,27 @@ __device__ __forceinline__ void load_tile(const LayerParams& p, int net, int uni
     if (p.cond_hop > 0) prow = n * p.cond_frames + fast_div(t + p.cond_offset, p.hop_magic, p.hop_shift);
     load_contig<16>(p.proj[net] + (size_t)prow * p.proj_row_stride + h * 64, r.pj);
     if constexpr (COND) load_tiled<10, kCondC>(p.cond, rc, h, true, r.cd);
-    if constexpr (SKIP && SK_NOW) load_skip_row<SKIP, COND>(p, net, lane, r, skip_load);
 }
 
 // Work is handed out in 32-row units (one MFMA column tile = one wave's worth of samples).
-// WAVES = 4: one wave per SIMD with up to 512 registers; units are strided statically and the next
-//            unit's operands are prefetched into registers under the current unit's GEMM2.
-// WAVES = 8: two waves per SIMD (<= 256 registers each).  Waves pull units from a per-workgroup
-//            LDS counter and waves 4..7 (the second wave of each SIMD) run at raised priority, so
-//            the two waves of a SIMD drift out of phase: one wave's MFMAs cover the other's loads,
-//            gating, address arithmetic and stores (identical streams at equal priority stay in
-//            lockstep and hit their VALU sections together, leaving the matrix pipe idle).
-// FIRST (layer 0 of a scalar-input net, 8 waves): the causal layer's output is not read but rebuilt from the flow input
+// 8 waves, two per SIMD (<= 256 registers each).  Waves pull units from a per-workgroup
+// LDS counter and waves 4..7 (the second wave of each SIMD) run at raised priority, so
+// the two waves of a SIMD drift out of phase: one wave's MFMAs cover the other's loads,
+// gating, address arithmetic and stores (identical streams at equal priority stay in
+// lockstep and hit their VALU sections together, leaving the matrix pipe idle).
+// FIRST (layer 0 of a scalar-input net): the causal layer's output is not read but rebuilt from the flow input
 //   with the front kernel's own two fp32 operations per channel (bit-identical to pwv_iaf_front_f32 + this kernel).
-// HEAD  (plain gated last layer, 8 waves): head_f32_kernel<true>'s arithmetic runs behind the gate on the registers the
+// HEAD  (plain gated last layer): head_f32_kernel<true>'s arithmetic runs behind the gate on the registers the
 //   gated output was accumulated in; LDS holds exactly filter|gate + skip + postprocess1 = 160 KB, so the small vectors
 //   come from global memory and units are handed out statically (no room for the counter).
 // FOLD (with FIRST): layer 0's filter|gate convolution on the four scalars x[t-d-1], x[t-d], x[t-1], x[t] themselves
 //   (pwv_pack_first_fold_f32; see layer_f16x3_kernel): two fp32 MFMA k-steps per row tile instead of 64.
-template <int WAVES, bool SKIP, bool COND, bool GATED, bool FIRST = false, bool HEAD = false, bool FOLD = false>
-__global__ __launch_bounds__(64 * WAVES) void layer_f32_kernel(const LayerParams p) {
+template <bool SKIP, bool COND, bool GATED, bool FIRST = false, bool HEAD = false, bool FOLD = false>
+__global__ __launch_bounds__(512) void layer_f32_kernel(const LayerParams p) {
     static_assert(!FOLD || FIRST, "FOLD: layer 0 of a scalar-input net only");
-    static_assert(!(FIRST || HEAD) || WAVES == 8, "FIRST / HEAD: 8-wave kernels only");
     static_assert(!HEAD || (GATED && !SKIP && !COND && !FIRST), "HEAD: plain last layer only");
     static_assert(!FIRST || !SKIP, "FIRST: no skip accumulation");
-    constexpr bool PREFETCH = WAVES == 4;
+    constexpr int WAVES = 8;
     constexpr int kLds = HEAD ? kA1Size + kASSize + kHA1Size : layer_floats(SKIP, COND);
     constexpr int kCF = kLds + 4;           // FIRST: the causal filter [2][64] behind the unit counter
     constexpr int kHS = kA1Size;            // HEAD: skip weights, then postprocess1
@@ -162,28 +157,21 @@ __global__ __launch_bounds__(64 * WAVES) void layer_f32_kernel(const LayerParams
     const int u_begin = wg * per_wg;
     const int u_end = (u_begin + per_wg < units) ? u_begin + per_wg : units;
 
-    auto grab = [&]() -> int {   // next unit for this wave (WAVES == 8)
+    auto grab = [&]() -> int {   // next unit for this wave
         int v = 0;
         if (lane == 0) v = __hip_atomic_fetch_add(unit_counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         return u_begin + __builtin_amdgcn_readfirstlane(v);
     };
 
-    int unit;
     TileRegs<SKIP, COND> cur;
-    if constexpr (PREFETCH) {
-        unit = u_begin + wave;
-        load_tile<SKIP, COND>(p, net, unit, lane, cur, skip_load);
-    } else {
-        if (wave >= WAVES / 2) __builtin_amdgcn_s_setprio(1);
-        unit = HEAD ? u_begin + wave : grab();
-    }
+    if (wave >= WAVES / 2) __builtin_amdgcn_s_setprio(1);
+    int unit = HEAD ? u_begin + wave : grab();
 
     auto no_extra = [](int) {};
     const __amdgpu_buffer_rsrc_t out_rs = units_rsrc(p.x_out[net], u_begin, u_end, 32 * 64 * 4);      // unused with HEAD
 
     while (unit < u_end) {
-        const int next = PREFETCH ? unit + WAVES : 0;
-        if constexpr (!PREFETCH) load_tile<SKIP, COND, FIRST, false>(p, net, unit, lane, cur, skip_load);
+        load_tile<SKIP, COND, FIRST>(p, net, unit, lane, cur);
         float first_x0 = 0.f, first_x1 = 0.f;      // FIRST: x[t], x[t-1]
         float fold_b0 = 0.f, fold_b1 = 0.f;        // FOLD: the B values of the two k-steps
         (void)first_x0;
@@ -299,13 +287,6 @@ __global__ __launch_bounds__(64 * WAVES) void layer_f32_kernel(const LayerParams
             });
         }
 
-        // next tile's operands: in flight during GEMM2 / skip GEMM / stores
-        TileRegs<SKIP, COND> nx;   // rows past the end are clamped inside load_tile
-        if constexpr (PREFETCH) {
-            load_tile<SKIP, COND>(p, net, next, lane, nx, skip_load);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-
         const int ooff = units_off(cur.row, h, 64, u_begin);      // (rows past the end are never stored: `valid`)
         if constexpr (GATED && HEAD) {
             // ---- fused head: o (registers) -> skip -> relu -> postprocess1 -> relu -> postprocess2, the operations
@@ -357,7 +338,7 @@ __global__ __launch_bounds__(64 * WAVES) void layer_f32_kernel(const LayerParams
                 if (cur.valid && h == 0) p.head_out[net][(size_t)cur.row * Q + q] = part;
             }
         } else if constexpr (GATED) {
-            if constexpr (SKIP && !PREFETCH) load_skip_row<SKIP, COND>(p, net, lane, cur, skip_load);      // in flight under the gating
+            if constexpr (SKIP) load_skip_row<SKIP, COND>(p, net, lane, cur, skip_load);      // in flight under the gating
 #pragma unroll
             for (int r = 0; r < 16; ++r) o[16 + r] = gate_act(acc[1][r], acc[3][r]);
             if (cur.valid) {
@@ -388,7 +369,7 @@ __global__ __launch_bounds__(64 * WAVES) void layer_f32_kernel(const LayerParams
                     }
                 }
             }
-            if constexpr (SKIP && !PREFETCH) load_skip_row<SKIP, COND>(p, net, lane, cur, skip_load);      // in flight under GEMM2
+            if constexpr (SKIP) load_skip_row<SKIP, COND>(p, net, lane, cur, skip_load);      // in flight under GEMM2
             // k-steps 0..15 use o tile 0 (ready); pair 1 is gated under those MFMAs
             gemm_groups<8, 2, 0, 1>(
                 lds, kA2, lane, acc2, a, [&](int ks) -> float { return o[ks]; },
@@ -443,12 +424,7 @@ __global__ __launch_bounds__(64 * WAVES) void layer_f32_kernel(const LayerParams
             }
         }
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (PREFETCH) {
-            cur = nx;
-            unit = next;
-        } else {
-            unit = HEAD ? unit + WAVES : grab();
-        }
+        unit = HEAD ? unit + WAVES : grab();
     }
 }
 
@@ -651,31 +627,9 @@ __global__ void pack_head_kernel(const float* skip, const float* skip_bias, cons
     out[idx] = v;
 }
 
-// waves per workgroup of the layer kernel: 8 (two per SIMD) unless PWV_LAYER_WAVES=4
-static int layer_waves() {
-    static int w = 0;
-    if (w == 0) {
-        const char* e = getenv("PWV_LAYER_WAVES");
-        w = (e && atoi(e) == 4) ? 4 : 8;
-    }
-    return w;
-}
-
-template <bool SKIP, bool COND, bool GATED>
-static int launch_layer(const LayerParams& lp, int per_net4, int per_net8, hipStream_t s) {
-    if (layer_waves() == 4)
-        hipLaunchKernelGGL((layer_f32_kernel<4, SKIP, COND, GATED>), dim3(per_net4 * lp.G), dim3(256), 0, s, lp);
-    else
-        hipLaunchKernelGGL((layer_f32_kernel<8, SKIP, COND, GATED>), dim3(per_net8 * lp.G), dim3(512), 0, s, lp);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(PWV_EHIP, "layer kernel launch failed: %s", hipGetErrorString(e));
-    return PWV_OK;
-}
-
-// the two buffer-removing variants (always 8 waves)
-template <bool COND, bool GATED, bool FIRST, bool HEAD, bool FOLD = false>
-static int launch_layer_fused(const LayerParams& lp, int per_net8, hipStream_t s) {
-    hipLaunchKernelGGL((layer_f32_kernel<8, false, COND, GATED, FIRST, HEAD, FOLD>), dim3(per_net8 * lp.G), dim3(512), 0, s, lp);
+template <bool SKIP, bool COND, bool GATED, bool FIRST = false, bool HEAD = false, bool FOLD = false>
+static int launch_layer(const LayerParams& lp, int per_net, hipStream_t s) {
+    hipLaunchKernelGGL((layer_f32_kernel<SKIP, COND, GATED, FIRST, HEAD, FOLD>), dim3(per_net * lp.G), dim3(512), 0, s, lp);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return set_error(PWV_EHIP, "layer kernel launch failed: %s", hipGetErrorString(e));
     return PWV_OK;
@@ -818,15 +772,12 @@ int pwv_wavenet_layer_f32(const pwv_layer_args* a, pwv_stream_t stream) {
     int per_net = (a->max_workgroups > 0 ? a->max_workgroups : cus) / a->G;
     if (per_net < 1) per_net = 1;
     const int nt4 = (int)((rows + 127) / 128), nt8 = (int)((rows + 255) / 256);   // >= 1 unit per wave
-    const int g4 = per_net < nt4 ? per_net : nt4, g8 = per_net < nt8 ? per_net : nt8;
+    const int g8 = per_net < nt8 ? per_net : nt8;
     // the write-through stores address a workgroup's own units with 32-bit byte offsets (units_rsrc / units_off): 16 KB per
     // unit of the widest buffer (skip accumulators) must stay below 2 GB per workgroup
-    {
-        const int gmin = g4 < g8 ? g4 : g8;
-        PWV_CHECK_ARG(((rows + 31) / 32 + gmin - 1) / gmin < (1 << 17),
-                      "pwv_wavenet_layer_f32: %lld rows on %d workgroups per net: more than 131071 units per workgroup (raise max_workgroups)",
-                      rows, gmin);
-    }
+    PWV_CHECK_ARG(((rows + 31) / 32 + g8 - 1) / g8 < (1 << 17),
+                  "pwv_wavenet_layer_f32: %lld rows on %d workgroups per net: more than 131071 units per workgroup (raise max_workgroups)",
+                  rows, g8);
     hipStream_t s = (hipStream_t)stream;
     const bool cond = a->cond != nullptr, gated = a->out_mode == PWV_OUT_GATED;
     PWV_CHECK_ARG(a->out_mode == PWV_OUT_GATED || a->out_mode == PWV_OUT_RESIDUAL, "pwv_wavenet_layer_f32: bad out_mode");
@@ -838,21 +789,21 @@ int pwv_wavenet_layer_f32(const pwv_layer_args* a, pwv_stream_t stream) {
         const int want = per_net * (cond ? 2 : 3);
         return launch_layer_h16(lp, cond, gated, want < nt4 ? want : nt4, s);
     }
-    if (lp.packed_head[0]) return launch_layer_fused<false, true, false, true>(lp, g8, s);
+    if (lp.packed_head[0]) return launch_layer<false, false, true, false, true>(lp, g8, s);
     if (lp.x_first && lp.fold0[0]) {
-        if (cond) return gated ? launch_layer_fused<true, true, true, false, true>(lp, g8, s) : launch_layer_fused<true, false, true, false, true>(lp, g8, s);
-        return gated ? launch_layer_fused<false, true, true, false, true>(lp, g8, s) : launch_layer_fused<false, false, true, false, true>(lp, g8, s);
+        if (cond) return gated ? launch_layer<false, true, true, true, false, true>(lp, g8, s) : launch_layer<false, true, false, true, false, true>(lp, g8, s);
+        return gated ? launch_layer<false, false, true, true, false, true>(lp, g8, s) : launch_layer<false, false, false, true, false, true>(lp, g8, s);
     }
     if (lp.x_first) {
-        if (cond) return gated ? launch_layer_fused<true, true, true, false>(lp, g8, s) : launch_layer_fused<true, false, true, false>(lp, g8, s);
-        return gated ? launch_layer_fused<false, true, true, false>(lp, g8, s) : launch_layer_fused<false, false, true, false>(lp, g8, s);
+        if (cond) return gated ? launch_layer<false, true, true, true>(lp, g8, s) : launch_layer<false, true, false, true>(lp, g8, s);
+        return gated ? launch_layer<false, false, true, true>(lp, g8, s) : launch_layer<false, false, false, true>(lp, g8, s);
     }
     if (any_skip) {
-        if (cond) return gated ? launch_layer<true, true, true>(lp, g4, g8, s) : launch_layer<true, true, false>(lp, g4, g8, s);
-        return gated ? launch_layer<true, false, true>(lp, g4, g8, s) : launch_layer<true, false, false>(lp, g4, g8, s);
+        if (cond) return gated ? launch_layer<true, true, true>(lp, g8, s) : launch_layer<true, true, false>(lp, g8, s);
+        return gated ? launch_layer<true, false, true>(lp, g8, s) : launch_layer<true, false, false>(lp, g8, s);
     }
-    if (cond) return gated ? launch_layer<false, true, true>(lp, g4, g8, s) : launch_layer<false, true, false>(lp, g4, g8, s);
-    return gated ? launch_layer<false, false, true>(lp, g4, g8, s) : launch_layer<false, false, false>(lp, g4, g8, s);
+    if (cond) return gated ? launch_layer<false, true, true>(lp, g8, s) : launch_layer<false, true, false>(lp, g8, s);
+    return gated ? launch_layer<false, false, true>(lp, g8, s) : launch_layer<false, false, false>(lp, g8, s);
 }
 
 int pwv_wavenet_head_f32(const pwv_head_args* a, pwv_stream_t stream) {

@@ -132,9 +132,6 @@ __device__ __forceinline__ void stage_head_h16(f16x8* hl, float* fl, const float
     for (int i = tid; i < 2 * Q * 64 + 4; i += waves * 64) fl[256 + i] = packed[kHW2 + i];
 }
 
-#ifndef PWV_H16_MINWAVES
-#define PWV_H16_MINWAVES 2
-#endif
 // FIRST: layer 0 of a scalar-input net rebuilds the causal layer's fp16 rows from four scalars per row with the operations of
 // iaf_front_h16_kernel (fp32 fma, then ONE rounding to fp16): no front launch, no [rows, 64] fp16 buffer written and read twice.
 // HEAD: the LAST layer with the head behind it -- the gated output's fp16 fragments are the B operand of the skip GEMM, exactly
@@ -142,7 +139,7 @@ __device__ __forceinline__ void stage_head_h16(f16x8* hl, float* fl, const float
 // FOLD (with FIRST): layer 0's filter|gate convolution on the four scalars themselves (the `hi` fragments of
 //   pwv_pack_first_fold_f16x3; see layer_f16x3_kernel): one MFMA k-step instead of eight.
 template <bool COND, bool GATED, bool FIRST = false, bool HEAD = false, bool FOLD = false>
-__global__ __launch_bounds__(HEAD ? 512 : 256, HEAD ? 1 : PWV_H16_MINWAVES) void layer_h16_kernel(const LayerParams p) {
+__global__ __launch_bounds__(HEAD ? 512 : 256, HEAD ? 1 : 2) void layer_h16_kernel(const LayerParams p) {
     static_assert(!FOLD || FIRST, "FOLD: layer 0 of a scalar-input net only");
     static_assert(!HEAD || GATED, "HEAD: the last layer only");
     constexpr int WAVES = HEAD ? 8 : 4;

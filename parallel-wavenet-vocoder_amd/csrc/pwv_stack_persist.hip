@@ -38,12 +38,9 @@
 #include <cstdlib>
 #include <cstring>
 
-// cache policy of the stores of units no other workgroup reads (0 = plain: produced and consumed through one CU's L2)
-#ifndef PWV_PERSIST_STORE_AUX
-#define PWV_PERSIST_STORE_AUX 0
-#endif
-
 namespace pwv {
+
+constexpr int kStoreAuxLocal = 0;              // cache policy of the stores of units no other workgroup reads (plain: produced and consumed through one CU's L2)
 
 constexpr int kSlotFull = kA1Size + kA2Size;   // floats of a layer's matrices: filter|gate (hi+lo) + dense (hi+lo) = 81,920 B
 constexpr int kSlot = kSlotFull - 256;         // held in LDS: everything but the last 1 KB fragment of the dense matrix
@@ -56,17 +53,13 @@ constexpr int kLeftN = 32;                                 // unit mode (short i
 constexpr int kLeftB = (kCfF + 128) * 4;                   // ... in front of the own units' bytes, so one linear address serves both
 constexpr int kDoneB = kLeftB + kLeftN;                    // byte offset of the per-unit "layers completed" bytes
 constexpr int kMaxUnitsWg = kLdsFloats * 4 - kDoneB;       // 832 units per workgroup
-#ifndef PWV_SHORT_MAX_UNITS
-#define PWV_SHORT_MAX_UNITS 7      // (wave 7 is the loader.  Against the general kernel: 4 units per workgroup -17 %, 5: -8 %, 6: -11.5 %, 7: -11 %; profiles/r06_ab_experiments.md, r06_z2)
-#endif
-constexpr int kUnitModeMaxPerWg = PWV_SHORT_MAX_UNITS;
+// unit mode up to this many units per workgroup and layer (wave 7 is the loader.  Against the general kernel: 4 units per workgroup -17 %,
+// 5: -8 %, 6: -11.5 %, 7: -11 %; profiles/r06_ab_experiments.md, r06_z2)
+constexpr int kUnitModeMaxPerWg = 7;
 static_assert(kUnitModeMaxPerWg <= 7, "the short-input instantiation keeps wave 7 as its loader");
-#ifndef PWV_MEDIUM_MAX_UNITS
-#define PWV_MEDIUM_MAX_UNITS 0
-#endif
-constexpr int kMediumMaxPerWg = PWV_MEDIUM_MAX_UNITS;
-constexpr int kMediumMode = (PWV_MEDIUM_MAX_UNITS) > 0 ? 1 : 0;      // (0: no such instantiation is built)
-                      // unit mode up to this many units per workgroup and layer
+// unit mode reads the left neighbours' unit words with lanes 1 / 2 and the right neighbours' workgroup words with lanes 32..63 of one
+// instruction (poll_units): the look-back stays within 32 units, and persist_plan grants it only with at most 32 right neighbours
+static_assert(kLeftN <= 32, "unit mode: the right neighbours are polled by lanes 32..63 alone");
 constexpr int kUnitStride = 32;                            // ints between two units' words (own 128-byte lines: a poll asks for exactly the unit it waits for)
 constexpr int kFlagB = (kCtlF + 2) * 4;        // flag bytes: +0 seenL, +1 seenR, +2 / +3 newest layer in LDS slot 0 / 1, +4 always 255
 constexpr int kSeenLB = kFlagB, kSeenRB = kFlagB + 1, kWreadyB = kFlagB + 2, kTrueB = kFlagB + 4;
@@ -201,11 +194,9 @@ __device__ __forceinline__ void gemm_groups_dense(FR&& fr, f32x16 (&acc)[2], f32
 // SHORT (round 6): the instantiation for short inputs (at most kUnitModeMaxPerWg units per workgroup and layer: progress words per unit, stationary
 // units, a loader wave) -- a template parameter, not a run-time mode: as run-time branches in the general task loop the additions cost the long-input
 // launch 2.7 % of its step (SGPR spills reloaded per unit, profiles/r06_ab_experiments.md r06_r)
-// MODE 1 (medium inputs, 8 ... PWV_MEDIUM_MAX_UNITS units per workgroup): the general kernel with the progress words per unit only.
 template <bool F32, int MODE>
 __global__ __launch_bounds__(512) void stack_persist_kernel(const PersistParams p) {
-    constexpr bool SHORT = MODE == 2;      // stationary units, loader wave, ... (everything below that says SHORT)
-    constexpr bool UNITW = MODE >= 1;      // progress words per unit
+    constexpr bool SHORT = MODE == 2;      // progress words per unit, stationary units, loader wave, ... (everything below that says SHORT)
     __shared__ __attribute__((aligned(16))) float lds[kLdsFloats];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -275,9 +266,7 @@ __global__ __launch_bounds__(512) void stack_persist_kernel(const PersistParams 
     fill_slot(0, 0, wave, 8);
     if (L > 1) fill_slot(1, 1, wave, 8);
     __syncthreads();
-#ifndef PWV_PERSIST_NOPRIO
     if (wave >= 4) __builtin_amdgcn_s_setprio(1);
-#endif
 
     // ONE buffer descriptor for the three ring buffers (they are one allocation); the buffer of a layer is selected by the
     // scalar offset operand of the load / store.  sc1 loads: L2-served, never the CU's L1.
@@ -385,7 +374,7 @@ __global__ __launch_bounds__(512) void stack_persist_kernel(const PersistParams 
     auto dep_addr = [&](int j, int u) -> int {
         const int v = u + (int)(short)vpack;
         int a = kDoneB - u_begin + v;
-        a = (v < u_begin && !UNITW) ? kSeenLB : a;      // (unit mode: the byte of that very unit, kLeftN bytes in front of the own ones)
+        a = (v < u_begin && !SHORT) ? kSeenLB : a;      // (unit mode: the byte of that very unit, kLeftN bytes in front of the own ones)
         a = v >= u_end ? kSeenRB : a;
         a = (v < 0 || v >= p.units) ? kTrueB : a;
         a = lane == 3 ? kWreadyB + (j & 1) : a;
@@ -408,7 +397,7 @@ __global__ __launch_bounds__(512) void stack_persist_kernel(const PersistParams 
         int lo = lane;
         asm volatile("" : "+v"(lo));      // (address made here, not hoisted out of the task loop into a spilled register pair)
         if (lo < cnt) v = __hip_atomic_load(prog_n + (size_t)(w0 + lo) * kProgStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if constexpr (UNITW) {
+        if constexpr (SHORT) {
             const int m = wave_min(v);
             if (m >= need) lb[side ? kSeenRB : kSeenLB] = (unsigned char)m;
         } else {
@@ -446,7 +435,7 @@ __global__ __launch_bounds__(512) void stack_persist_kernel(const PersistParams 
     auto publish = [&]() {               // (all lanes store the same byte: no exec juggling)
         if (prev_addr >= 0) {
             lb[prev_addr] = (unsigned char)(prev_j + 1);
-            if (UNITW && lane == 0) __hip_atomic_store(uprog_n + (size_t)(prev_addr - kDoneB + u_begin) * kUnitStride, prev_j + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (SHORT && lane == 0) __hip_atomic_store(uprog_n + (size_t)(prev_addr - kDoneB + u_begin) * kUnitStride, prev_j + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             prev_addr = -1;
         }
         if (dma_pending >= 0) { lb[kWreadyB + (dma_pending & 1)] = (unsigned char)dma_pending; dma_pending = -1; }
@@ -507,7 +496,7 @@ __global__ __launch_bounds__(512) void stack_persist_kernel(const PersistParams 
             if (__builtin_amdgcn_readfirstlane(*(__attribute__((address_space(3))) volatile int*)&ctl[1])) break;
             if ((k & 63) == 63 && (__builtin_amdgcn_readfirstlane(__hip_atomic_load(p.abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) ||
                                    __builtin_amdgcn_s_memrealtime() - t0 > kWaitTicks)) break;
-            if constexpr (UNITW) {
+            if constexpr (SHORT) {
                 if ((bad & 0x6u) && __ballot((lane == 1 || lane == 2) && addr < kDoneB && addr >= kLeftB)) poll_units(addr, j);
             } else if ((bad & 0x6u) && __ballot(addr == kSeenLB && (lane == 1 || lane == 2))) poll_side(0, j);
             if ((bad & 0x30u) && __ballot(addr == kSeenRB && (lane == 4 || lane == 5))) poll_side(1, j - 1);
@@ -726,7 +715,7 @@ __global__ __launch_bounds__(512) void stack_persist_kernel(const PersistParams 
                         for (int g = 0; g < 8; ++g) {
                             const int it = g >> 2, q = g & 3;
                             const f32x4 v = {acc2[it][q * 4], acc2[it][q * 4 + 1], acc2[it][q * 4 + 2], acc2[it][q * 4 + 3]};
-                            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ring_rs, oo + g * 1024, so, PWV_PERSIST_STORE_AUX);
+                            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ring_rs, oo + g * 1024, so, kStoreAuxLocal);
                         }
                     }
                 }
@@ -1047,7 +1036,7 @@ __global__ __launch_bounds__(512) void stack_persist_kernel(const PersistParams 
             // (that verdict is a task old: look again before the machinery of a wait -- drain, leave, poll -- is set in motion; 1 us per unit on
             //  short inputs, where every unit's verdict is stale, profiles/r06_short_timeline.md)
             unsigned badw = kWarMask;
-            if constexpr (UNITW) {
+            if constexpr (SHORT) {
                 if (lv_j != j) layer_vectors(j);
                 badw = eval(dep_addr(j, u)) & kWarMask;
                 if (lv_j != j) layer_vectors(lv_j);
@@ -1078,7 +1067,7 @@ __global__ __launch_bounds__(512) void stack_persist_kernel(const PersistParams 
                     for (int g = 0; g < 8; ++g) {
                         const int it = g >> 2, q = g & 3;
                         const f32x4 v = {acc2[it][q * 4], acc2[it][q * 4 + 1], acc2[it][q * 4 + 2], acc2[it][q * 4 + 3]};
-                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ring_rs, oo + g * 1024, so, PWV_PERSIST_STORE_AUX);
+                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ring_rs, oo + g * 1024, so, kStoreAuxLocal);
                     }
                 }
             }
@@ -1227,7 +1216,7 @@ __global__ __launch_bounds__(512) void stack_persist_kernel(const PersistParams 
                     }
                     f32x16 acc1[4];      // postprocess1's accumulators: what both arithmetics hand to the postprocess2 dot below
                     if constexpr (F32) {
-                        // ---- exact fp32 (round 6): the operations of layer_f32_kernel<8, ..., GATED, HEAD> in the same order ----------
+                        // ---- exact fp32 (round 6): the operations of layer_f32_kernel<..., GATED, HEAD> in the same order ----------
                         auto bx = [&](int ks) -> float { return ks < 32 ? txb[ks] : txc[ks - 32]; };
                         float o[32];
                         f32x4 a[4];
@@ -1411,7 +1400,7 @@ __global__ __launch_bounds__(512) void stack_persist_kernel(const PersistParams 
                 if (lane == 0) done = __hip_atomic_fetch_add(p.exited, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 if (__builtin_amdgcn_readfirstlane(done) == p.active_wgs - 1) {
                     for (int k = lane; k < p.G * p.nwg; k += 64) __hip_atomic_store(p.prog + (size_t)k * kProgStride, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (UNITW) for (int k = lane; k < p.G * p.units; k += 64) __hip_atomic_store(p.uprog + (size_t)k * kUnitStride, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (SHORT) for (int k = lane; k < p.G * p.units; k += 64) __hip_atomic_store(p.uprog + (size_t)k * kUnitStride, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     if (lane == 0) {
                         __hip_atomic_store(p.abort, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         __hip_atomic_store(p.exited, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1432,7 +1421,7 @@ __global__ __launch_bounds__(512) void stack_persist_kernel(const PersistParams 
             if (lane == 0) done = __hip_atomic_fetch_add(p.exited, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (__builtin_amdgcn_readfirstlane(done) == p.active_wgs - 1) {
                 for (int k = lane; k < p.G * p.nwg; k += 64) __hip_atomic_store(p.prog + (size_t)k * kProgStride, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (UNITW) for (int k = lane; k < p.G * p.units; k += 64) __hip_atomic_store(p.uprog + (size_t)k * kUnitStride, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (SHORT) for (int k = lane; k < p.G * p.units; k += 64) __hip_atomic_store(p.uprog + (size_t)k * kUnitStride, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 if (lane == 0) {
                     __hip_atomic_store(p.abort, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     __hip_atomic_store(p.exited, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1510,12 +1499,11 @@ static int persist_plan(int G, long long rows, int n_layers, const int* dil, int
     // Short inputs (a handful of units per workgroup and layer: every layer is ONE unit's latency per SIMD): progress per UNIT instead of per
     // workgroup.  A range's bottom unit waits for the left neighbour's TOP units, which that workgroup computes FIRST; its workgroup word
     // appears only when its slowest unit -- its own bottom one, which waited for ITS left neighbour -- is through: with workgroup words every
-    // layer of the chain costs a cross-workgroup hop (profiles/r06_short_timeline.md).  PWV_PERSIST_UNITWORDS=0 keeps the workgroup words (A/B).
-    static const int unit_words_env = [] { const char* e = getenv("PWV_PERSIST_UNITWORDS"); return e ? atoi(e) : 1; }();
-    pl.unit_mode = 0;      // 2: the short-input instantiation, 1: the general kernel with unit words (medium inputs)
-    if (unit_words_env && reach <= kLeftN && pl.nwg > 1) {
-        if (pl.per_wg <= kUnitModeMaxPerWg) pl.unit_mode = 2;      // (the launcher: and a folded layer 0, if the run starts there)
-        else if (pl.per_wg <= kMediumMaxPerWg) pl.unit_mode = 1;
+    // layer of the chain costs a cross-workgroup hop (profiles/r06_short_timeline.md).
+    pl.unit_mode = 0;      // 2: the short-input instantiation (the launcher: and a folded layer 0, if the run starts there)
+    if (reach <= kLeftN && pl.nwg > 1 && pl.per_wg <= kUnitModeMaxPerWg) {
+        pl.unit_mode = 2;
+        PWV_CHECK_ARG(pl.reach_wgs <= 32, "persistent stack: unit mode polls at most 32 right neighbours (reach %d workgroups)", pl.reach_wgs);
     }
     // the tail's layer looks back too (a stack whose LAST dilation is its largest passed the probe and failed at the launch)
     pl.tail_reach_wgs = 0;
@@ -1533,11 +1521,10 @@ static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 // the short-input instantiation: the plan's verdict (units per workgroup, look-back reach), and a folded layer 0 if the run starts with one (it has
 // no unfolded form), and the P rows inside the 2 GB its buffer descriptor's 32-bit offsets reach.  (The workspace is sized by the plan alone.)
 static int short_input_mode(const pwv_persist_args* a, const PersistPlan& pl) {
-    if (pl.unit_mode != 2) return pl.unit_mode;
-    const int fallback = kMediumMaxPerWg > 0 ? 1 : 0;
-    if (a->x_first && !a->first_fold[0]) return fallback;
+    if (pl.unit_mode != 2) return 0;
+    if (a->x_first && !a->first_fold[0]) return 0;
     const long long p_rows = a->cond_hop > 0 ? (long long)a->N * a->cond_frames : 1;
-    if (p_rows * a->proj_row_stride * 4 >= (1ll << 31)) return fallback;
+    if (p_rows * a->proj_row_stride * 4 >= (1ll << 31)) return 0;
     return 2;
 }
 
@@ -1684,11 +1671,9 @@ int pwv_wavenet_stack_persist_f32(const pwv_persist_args* args, pwv_stream_t str
     const dim3 grid(a->G * pl.nwg), block(512);
     if (a->precision == PWV_PREC_F32) {
         if (pl.unit_mode == 2) hipLaunchKernelGGL((stack_persist_kernel<true, 2>), grid, block, 0, s, p);
-        else if (pl.unit_mode == 1 && kMediumMaxPerWg > 0) hipLaunchKernelGGL((stack_persist_kernel<true, kMediumMode>), grid, block, 0, s, p);
         else hipLaunchKernelGGL((stack_persist_kernel<true, 0>), grid, block, 0, s, p);
     } else {
         if (pl.unit_mode == 2) hipLaunchKernelGGL((stack_persist_kernel<false, 2>), grid, block, 0, s, p);
-        else if (pl.unit_mode == 1 && kMediumMaxPerWg > 0) hipLaunchKernelGGL((stack_persist_kernel<false, kMediumMode>), grid, block, 0, s, p);
         else hipLaunchKernelGGL((stack_persist_kernel<false, 0>), grid, block, 0, s, p);
     }
     hipError_t e = hipGetLastError();

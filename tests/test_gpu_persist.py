@@ -100,7 +100,7 @@ def test_tail_and_affine_inside_the_launch_are_bit_identical_to_the_separate_lau
     launch (pwv_persist_args.tail_*: a flow is one launch instead of three).  Same operations in the same order as
     layer_f16x3_kernel<..., HEAD> and the affine kernel: the nets' outputs and the flow's output agree bit for bit with the
     separate launches (FUSE_TAIL off) and with the per-layer path -- three times in a row on one workspace (the pair counters
-    and progress words are left clean), eager.  Round 6: in the exact-fp32 arithmetic too (the operations of layer_f32_kernel<8, ..., HEAD>):
+    and progress words are left clean), eager.  Round 6: in the exact-fp32 arithmetic too (the operations of layer_f32_kernel<..., HEAD>):
     the path a range flag reruns on is one launch per flow as well."""
     import torch
     from pwv_amd.modules import WaveNet

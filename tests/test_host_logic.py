@@ -315,7 +315,7 @@ def test_variable_scopes_are_per_thread():
 
 def test_no_vgpr_spills_in_the_layer_kernels():
     """`use_skip_connection: True` (modules.py:147) used to run kernels with 19-37 VGPRs spilled to scratch
-    (layer_f16x3_kernel<SKIP = true, ...>: all four variants; layer_f32_kernel<8, SKIP, COND>: 27-35).  The compiler's own resource
+    (layer_f16x3_kernel<SKIP = true, ...>: all four variants; layer_f32_kernel<SKIP, COND>: 27-35).  The compiler's own resource
     remarks (`-Rpass-analysis=kernel-resource-usage`, gfx950 device code, no GPU needed) must show no spilled VGPR in any kernel of the
     layer / persistent sources -- except the two variants pinned below, which no default or benchmarked configuration reaches."""
     import re
