@@ -20,7 +20,7 @@ import os
 import threading
 import weakref
 from ctypes import c_void_p
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -41,8 +41,9 @@ DEFAULT_PRECISION = os.environ.get('PWV_PRECISION', 'f16x3')
 # launch stream and appends (tag, start_event, end_event): bench.py's live kernel timing.
 EVENT_LOG = None
 
-# Environment knobs (six, all read once at import): PWV_PRECISION (above), PWV_PERSIST, PWV_TWO_STREAMS, PWV_FOLD_FIRST, PWV_FUSE_TAIL,
-# PWV_ASYNC.  Everything else below is a module attribute that tests / tools set directly.
+# Environment knobs (seven, all read once at import into the module attributes a forward reads): PWV_PRECISION (above), PWV_PERSIST,
+# PWV_TWO_STREAMS, PWV_FOLD_FIRST, PWV_FUSE_TAIL, PWV_ASYNC, PWV_FUSE_PROLOGUE.  Everything else below is a module attribute that
+# tests / tools set directly.  launch_knobs() lists every attribute that decides which launches a forward enqueues.
 #
 # The scalar and shifter nets of a flow are independent dependency chains.  On the per-layer path (PWV_PERSIST=0, or a shape
 # the persistent launch does not cover) TWO_STREAMS gives each chain its own HIP stream and half of the CUs per launch
@@ -85,25 +86,27 @@ _side_streams = {}
 # own words, and its verification reads only those, so two threads serving two streams cannot consume or clear each other's
 # flags.  (A captured graph keeps reporting into the words of the thread that captured it: graph.GraphedVocoder remembers them.)
 _tls = threading.local()      # .words: {device index: StatusWords};  .depth: nesting of reference-shaped calls (verified_call)
-_verify = _tls
 
 
-_free_words: List[int] = []      # pinned pairs whose owners (threads, graphs) are gone: handed out again instead of allocated
-_free_words_lock = threading.Lock()
+# pinned pairs whose owners (threads, graphs) are gone: handed out again instead of allocated.  No lock: list.pop() / append are
+# atomic under the GIL, and a lock would deadlock when the GC collects a StatusWords (__del__) inside another's __init__.
+_free_words: List[int] = []
 
 
 class StatusWords(object):
     """One pinned, mapped pair {give-up word, range word}.  Pairs are POOLED: a serving process that spawns short-lived worker
     threads would otherwise leave one page-granular pinned allocation behind per thread.  A pair goes back to the
     pool when its last owner is collected -- the thread's table (a thread-local) and every GraphedVocoder that captured launches
-    carrying it hold references -- and is cleared when it is handed out again.  (A launch the dead thread left in flight can
-    still raise such a pair: the next owner then sees one spurious give-up, i.e. one rerun -- never a wrong result.)"""
+    carrying it hold references -- and is cleared when it is handed out again.  A launch the dead owner left in flight can still
+    write into the recycled pair after that: a stale give-up word costs the next owner one rerun on per-layer launches, a stale
+    range word one rerun in exact fp32 -- or, for a caller that does not verify (verify=False, PWV_ASYNC=1), a PwvPersistError /
+    PwvRangeError from verify_enqueued().  Never a wrong result."""
     __slots__ = ('addr', '__weakref__')
 
     def __init__(self):
-        with _free_words_lock:
-            addr = _free_words.pop() if _free_words else None
-        if addr is None:
+        try:
+            addr = _free_words.pop()
+        except IndexError:
             p = c_void_p()
             check(_lib.lib().pwv_status_words_alloc(ctypes.byref(p)), 'pwv_status_words_alloc')
             addr = p.value
@@ -113,8 +116,7 @@ class StatusWords(object):
 
     def __del__(self):
         try:
-            with _free_words_lock:
-                _free_words.append(self.addr)
+            _free_words.append(self.addr)
         except Exception:      # interpreter shutdown
             pass
 
@@ -234,16 +236,16 @@ def verified_call(run, verify: Optional[bool] = None):
     global _persist_backoff
     if verify is None:
         verify = not ASYNC
-    depth = getattr(_verify, 'depth', 0)
+    depth = getattr(_tls, 'depth', 0)
     if depth == 0:
         note_forward()
     if depth > 0 or not verify or torch.cuda.is_current_stream_capturing():
-        _verify.depth = depth + 1
+        _tls.depth = depth + 1
         try:
             return run(None)
         finally:
-            _verify.depth = depth
-    _verify.depth = 1
+            _tls.depth = depth
+    _tls.depth = 1
     try:
         out = run(None)
         torch.cuda.current_stream().synchronize()
@@ -271,7 +273,7 @@ def verified_call(run, verify: Optional[bool] = None):
             raise_if_range_flag("its rerun in precision 'f32'")
         return out
     finally:
-        _verify.depth = 0
+        _tls.depth = 0
 
 
 def _persist_runs(L: int, first: int = 1) -> List[Tuple[int, int]]:
@@ -289,28 +291,48 @@ def _persist_runs(L: int, first: int = 1) -> List[Tuple[int, int]]:
     return runs
 
 
-def _use_persist(G: int, n: int, t: int, dilations, first: int = 1, tail_q: int = 0) -> bool:
-    """Can layers first .. L-2 (and, with tail_q > 0, the last layer + head behind the last run) run as persistent launches?"""
+def _persist_launches(G: int, n: int, t: int, dilations, first: int = 1, tail_q: int = 0, prec: int = 0, layer_stride: int = 0,
+                      cond_geom=(0, 0, 0)) -> Optional[List[Tuple[int, _lib.PersistArgs]]]:
+    """(first layer, pwv_persist_args) of the persistent launches that run layers first .. L-2 (with tail_q > 0: and the last layer +
+    head behind the last run), one per run of _persist_runs, with every field but the buffers filled in, workspace_bytes included --
+    or None (per-layer launches) where the policy or the library (0 bytes for some run) refuses.  The launch only adds the buffers."""
     L = len(dilations)
     if PERSIST is False or _persist_cooldown > 0 or L < 4:
-        return False
+        return None
     if PERSIST == 'auto' and n * t > PERSIST_AUTO_MAX_ROWS:
-        return False
+        return None
     lib = _lib.lib()
-    runs = _persist_runs(L, first)
-    for j0, cnt in runs:    # 0 bytes = the library cannot run this shape persistently: per-layer launches
+    runs, out, rot = _persist_runs(L, first), [], 0
+    for j0, cnt in runs:
         pa = _lib.PersistArgs()
         pa.G, pa.n_layers, pa.N, pa.T = G, cnt, n, t
         pa.dilations = (ctypes.c_int * cnt)(*[int(d) for d in dilations[j0:j0 + cnt]])
-        pa.min_units_per_workgroup = PERSIST_MIN_UNITS
+        pa.min_units_per_workgroup, pa.precision, pa.packed_layer_stride = PERSIST_MIN_UNITS, prec, layer_stride
+        pa.cond_hop, pa.cond_offset, pa.cond_frames = cond_geom
+        pa.ring_rotation = rot              # input in buffer (2 + rot) % 3, output in buffer (cnt - 1 + rot) % 3
+        rot = (cnt + rot) % 3               # the next run reads this run's output: (2 + rot') % 3 == (cnt - 1 + rot) % 3
         if tail_q > 0 and (j0, cnt) == runs[-1]:      # the tail's own look-back (the LAST dilation) is part of the answer
             pa.tail_q, pa.tail_dilation = tail_q, int(dilations[L - 1])
-        if lib.pwv_persist_workspace_bytes(ctypes.byref(pa)) == 0:
-            return False
-    return True
+        pa.workspace_bytes = lib.pwv_persist_workspace_bytes(ctypes.byref(pa))
+        if pa.workspace_bytes == 0:         # the library cannot run this shape persistently
+            return None
+        out.append((j0, pa))
+    return out
+
+
+def _use_persist(G: int, n: int, t: int, dilations, first: int = 1, tail_q: int = 0) -> bool:
+    """Can layers first .. L-2 (and, with tail_q > 0, the last layer + head behind the last run) run as persistent launches?"""
+    return _persist_launches(G, n, t, dilations, first, tail_q) is not None
 
 
 PERSIST_ARGS_HOOK = None      # tests: called with the filled-in pwv_persist_args right before every persistent launch
+
+
+def launch_knobs() -> tuple:
+    """Every module attribute that decides WHICH launches a forward enqueues (read by _choose_path, get_plan, the launch helpers and
+    the prologue): a graph captured under other values is stale (graph.GraphedVocoder._launch_mode).  A new such knob goes here."""
+    return (PERSIST, persist_suspended(), TWO_STREAMS, FOLD_FIRST, FUSE_FIRST, FUSE_HEAD, FUSE_TAIL, HOIST_P, PERSIST_MAX_LAYERS,
+            PERSIST_MIN_UNITS, DEFAULT_PRECISION, FUSE_PROLOGUE, FUSE_PROLOGUE_MAX_OUTPUTS, PERSIST_AUTO_MAX_ROWS)
 
 
 def _net_streams(device):
@@ -701,84 +723,105 @@ def tail_fusable(prec: int) -> bool:
     return bool(FUSE_TAIL and FUSE_HEAD and prec in (_lib.PREC_F16X3, _lib.PREC_F32))      # (round 6: the exact-fp32 kernel has the tail too)
 
 
-def _run_stack_persist(lib, nets, plans, projs, bufs, outs, x_first, x_limit, row_stride, cond_geom, n, t, s, prec, affine=None, tail=None):
-    """Layers 0 .. L-2 as ONE persistent launch (layer 0 a launch of its own when it cannot rebuild the causal layer itself), with
-    layer L-1 + the head behind it -- and, given `affine` = (x, out), the flow's affine out = x*s + b -- INSIDE that launch on the
-    split-fp16 and exact-fp32 paths (FUSE_TAIL; otherwise one more launch for them); all nets of the flow in every launch, all on the current
+def head_fusable(prec: int) -> bool:
+    """Persistent launches without the tail: does the head run inside the last layer's launch (else in a launch of its own)?"""
+    return prec == _lib.PREC_F16X3 or (prec == _lib.PREC_F32 and FUSE_HEAD)
+
+
+class _Path(NamedTuple):
+    """Which launches one forward enqueues (_choose_path): decided once, read by the launch helpers."""
+    runs: Optional[List[Tuple[int, _lib.PersistArgs]]]    # the persistent launches (_persist_launches); None: per-layer launches
+    tail: bool              # layer L-1 + head (+ the flow's affine) run inside the last persistent launch
+    first_fused: bool       # layer 0 rebuilds the causal layer from the scalar input (x_first): no causal-layer launch
+    two: bool               # per-layer launches of G = 2 nets: each net's chain on a side stream of its own (TWO_STREAMS)
+
+    persist = property(lambda self: self.runs is not None)     # (else per-layer launches)
+
+
+def _choose_path(net0, plans, mode: str, n: int, t: int, max_workgroups: int, cond_geom) -> _Path:
+    """The launch path of a forward of the nets behind `plans` (one structure, one arithmetic, conditioning `mode`) on N x T rows."""
+    G, prec = len(plans), plans[0].precision
+    use_skip = bool(net0.use_skip_connection)
+    first_fused = bool(FUSE_FIRST and prec in (_lib.PREC_F16X3, _lib.PREC_F32, _lib.PREC_F16) and net0.in_channels == 1
+                       and net0.filter_width == 2 and net0.residual_channels == 64 and not use_skip and plans[0].causal_bias is None)
+    runs, tail = None, False
+    if (prec == _lib.PREC_F32 or (prec == _lib.PREC_F16X3 and FUSE_HEAD)) and mode != 'samples' and not use_skip and max_workgroups == 0:
+        def launches(tail_q):
+            return _persist_launches(G, n, t, net0.dilations, 0 if first_fused else 1, tail_q, prec, plans[0].layer_floats, cond_geom)
+        # the tail (last layer + head inside the launch) has a look-back of its own -- the stack's LAST dilation: ask for the launch
+        # that will be made, and keep the persistent layers with the tail as a launch of its own where only the tail does not fit
+        tail = tail_fusable(prec)
+        runs = launches(net0.out_channels if tail else 0)
+        if runs is None and tail:
+            tail, runs = False, launches(0)
+    two = G == 2 and TWO_STREAMS and max_workgroups == 0 and runs is None
+    return _Path(runs, tail, first_fused, two)
+
+
+def _set_x_first(a, plans, x: torch.Tensor, x_limit: float) -> None:
+    """pwv_stack_args / pwv_persist_args: layer 0 rebuilds the causal layer from the scalar input x (range-checked against x_limit)."""
+    a.x_first, a.x_limit, a.range_flag = _ptr(x), x_limit, range_flag_ptr()
+    for g, p in enumerate(plans):
+        a.causal_filter[g] = p.causal_filter.data_ptr()
+    if FOLD_FIRST and all(p.first_fold is not None for p in plans):
+        for g, p in enumerate(plans):
+            a.first_fold[g] = p.first_fold.data_ptr()
+
+
+def _layer_args(net0, plans, projs, row_stride: int, cond_geom, bufs, j: int, src: int, dst: int, x: torch.Tensor) -> _lib.LayerArgs:
+    """pwv_layer_args of layer j of the nets behind `plans`: reads bufs[g][src], writes bufs[g][dst]."""
+    la = _lib.LayerArgs()
+    la.G, la.precision, la.skip_init = len(plans), plans[0].precision, 1
+    for g, p in enumerate(plans):
+        la.x_in[g], la.x_out[g] = bufs[g][src].data_ptr(), bufs[g][dst].data_ptr()
+        la.packed[g] = p.packed_layers.data_ptr() + 4 * p.layer_floats * j
+        la.proj[g] = projs[g].data_ptr() + 4 * 128 * j
+    la.proj_row_stride = row_stride
+    la.N, la.T, la.dilation = x.shape[0], x.shape[1], int(net0.dilations[j])
+    la.cond_hop, la.cond_offset, la.cond_frames = cond_geom
+    return la
+
+
+def _run_stack_persist(path: _Path, nets, plans, projs, bufs, outs, x, x_limit, row_stride, cond_geom, affine=None):
+    """Layers 0 .. L-2 as the persistent launches of `path` (layer 0 a launch of its own when it cannot rebuild the causal layer
+    itself), with layer L-1 + the head behind them -- and, given `affine` = (x, out), the flow's affine out = x*s + b -- INSIDE the
+    last launch where `path.tail` (otherwise one more launch for them); all nets of the flow in every launch, all on the current
     stream.  `bufs[g]` holds THREE tile32 buffers: the persistent launch rotates through them (include/pwv_hip.h,
     pwv_persist_args.x_ring).  Returns True when the affine was evaluated by the launch."""
-    G, L = len(nets), plans[0].n_layers
+    lib, s = _lib.lib(), _stream()
+    G, L, prec = len(nets), plans[0].n_layers, plans[0].precision
     net0 = nets[0]
-    hop, offset, frames = cond_geom
     stride = plans[0].layer_floats
 
-    def layer_args(j, src, dst):
-        la = _lib.LayerArgs()
-        la.G = G
-        for g in range(G):
-            la.x_in[g], la.x_out[g] = bufs[g][src].data_ptr(), bufs[g][dst].data_ptr()
-            la.packed[g] = plans[g].packed_layers.data_ptr() + 4 * stride * j
-            la.proj[g] = projs[g].data_ptr() + 4 * 128 * j
-        la.proj_row_stride = row_stride
-        la.skip_init = 1
-        la.N, la.T, la.dilation = n, t, int(net0.dilations[j])
-        la.cond_hop, la.cond_offset, la.cond_frames = hop, offset, frames
-        la.precision = prec
-        return la
-
-    if x_first is None:                     # layer 0 on the causal layer's buffer (bufs[g][0]) as a launch of its own
-        la = layer_args(0, 0, 2)
+    if not path.first_fused:                # layer 0 on the causal layer's buffer (bufs[g][0]) as a launch of its own
+        la = _layer_args(net0, plans, projs, row_stride, cond_geom, bufs, 0, 0, 2, x)
         la.out_mode = _lib.OUT_RESIDUAL
         check(lib.pwv_wavenet_layer_f32(ctypes.byref(la), s), 'pwv_wavenet_layer_f32')
 
     # the residual layers (0 or) 1 .. L-2 as persistent launches of at most PERSIST_MAX_LAYERS layers each, handing the ring on
-    rot, out_slot = 0, 2
-    runs = _persist_runs(L, 1 if x_first is None else 0)
     Q = net0.out_channels
-    if tail is None:
-        tail = tail_fusable(prec)
-    affine_fused = bool(tail and affine is not None and ((G == 2 and Q == 1) or (G == 1 and Q == 2)))
-    for j0, cnt in runs:
-        pa = _lib.PersistArgs()
-        pa.G, pa.n_layers = G, cnt
-        dil = (ctypes.c_int * cnt)(*[int(d) for d in net0.dilations[j0:j0 + cnt]])
-        pa.dilations = dil
+    affine_fused = bool(path.tail and affine is not None and ((G == 2 and Q == 1) or (G == 1 and Q == 2)))
+    for j0, pa in path.runs:
         for g in range(G):
             pa.x_ring[g] = bufs[g][0].data_ptr()
             pa.packed_layers[g] = plans[g].packed_layers.data_ptr() + 4 * stride * j0
             pa.proj[g] = projs[g].data_ptr() + 4 * 128 * j0
-        pa.ring_stride = bufs[0][0].numel()
-        pa.ring_rotation = rot
-        pa.min_units_per_workgroup = PERSIST_MIN_UNITS
-        if j0 == 0:                          # the net's layer 0 rebuilds the causal layer from the scalar input
-            pa.x_first, pa.x_limit, pa.range_flag = _ptr(x_first), x_limit, range_flag_ptr()
-            for g in range(G):
-                pa.causal_filter[g] = plans[g].causal_filter.data_ptr()
-            if FOLD_FIRST and all(p.first_fold is not None for p in plans):
-                for g in range(G):
-                    pa.first_fold[g] = plans[g].first_fold.data_ptr()
-        pa.packed_layer_stride = stride
-        pa.proj_row_stride = row_stride
-        pa.N, pa.T = n, t
-        pa.precision = prec
-        pa.cond_hop, pa.cond_offset, pa.cond_frames = hop, offset, frames
-        nbytes = lib.pwv_persist_workspace_bytes(ctypes.byref(pa))
-        if nbytes == 0:
-            raise _lib.PwvError('pwv_persist_workspace_bytes: %s' % lib.pwv_last_error().decode())
+        pa.ring_stride, pa.proj_row_stride = bufs[0][0].numel(), row_stride
+        if j0 == 0:
+            _set_x_first(pa, plans, x, x_limit)
         # one zero-initialised workspace per (device, stream), kept: a launch leaves it clean, so none needs a zeroing kernel
         wkey = (bufs[0][0].device, torch.cuda.current_stream().cuda_stream)
         ws = _persist_ws.get(wkey)
-        if ws is None or ws.numel() < nbytes:
-            ws = _persist_ws[wkey] = torch.zeros((max(nbytes, 1 << 16),), dtype=torch.uint8, device=bufs[0][0].device)
-        pa.workspace, pa.workspace_bytes, pa.workspace_clean = ws.data_ptr(), nbytes, 1
+        if ws is None or ws.numel() < pa.workspace_bytes:
+            ws = _persist_ws[wkey] = torch.zeros((max(pa.workspace_bytes, 1 << 16),), dtype=torch.uint8, device=bufs[0][0].device)
+        pa.workspace, pa.workspace_clean = ws.data_ptr(), 1
         pa.status = persist_status_ptr()
-        last_run = (j0, cnt) == runs[-1]
-        if tail and last_run:             # layer L-1 + head (+ affine) behind this run's layers, inside the launch
+        tail_here = path.tail and pa is path.runs[-1][1]
+        if tail_here:                        # layer L-1 + head (+ affine) behind this run's layers, inside the launch
             for g in range(G):
                 pa.tail_layer[g] = plans[g].packed_layers.data_ptr() + 4 * stride * (L - 1)
                 pa.tail_head[g] = plans[g].packed_head.data_ptr()
                 pa.tail_out[g] = outs[g].data_ptr()
-            pa.tail_q, pa.tail_dilation = Q, int(net0.dilations[L - 1])
             if affine_fused:
                 pa.affine_x, pa.affine_out = affine[0].data_ptr(), affine[1].data_ptr()
         ev = None
@@ -790,29 +833,28 @@ def _run_stack_persist(lib, nets, plans, projs, bufs, outs, x_first, x_limit, ro
         check(lib.pwv_wavenet_stack_persist_f32(ctypes.byref(pa), s), 'pwv_wavenet_stack_persist_f32')
         if ev is not None:
             ev[1].record()
-            EVENT_LOG.append(('persist', ev[0], ev[1], G, cnt, 1 if j0 == 0 else 0, 1 if (tail and last_run) else 0,
+            EVENT_LOG.append(('persist', ev[0], ev[1], G, pa.n_layers, 1 if j0 == 0 else 0, 1 if tail_here else 0,
                               int(lib.pwv_persist_short_input(ctypes.byref(pa)))))      # [7]: the short-input instantiation (round 6)
-        out_slot = (cnt - 1 + rot) % 3      # where this run left its last layer
-        rot = (out_slot + 1) % 3            # the next run's input buffer is (2 + rot') % 3 == out_slot
-    if tail:
+    if path.tail:
         return affine_fused
+    last = path.runs[-1][1]
+    out_slot = (last.n_layers - 1 + last.ring_rotation) % 3      # where the last run left layer L-2
     spare = (out_slot + 1) % 3
 
-    la = layer_args(L - 1, out_slot, spare)
+    la = _layer_args(net0, plans, projs, row_stride, cond_geom, bufs, L - 1, out_slot, spare, x)
     la.out_mode = _lib.OUT_GATED
-    fuse_head = prec == _lib.PREC_F16X3 or (prec == _lib.PREC_F32 and FUSE_HEAD)
+    fuse_head = head_fusable(prec)
     if fuse_head:                        # the head runs inside the last layer's launch
         for g in range(G):
             la.head_packed[g] = plans[g].packed_head.data_ptr()
             la.head_out[g] = outs[g].data_ptr()
-        la.head_q = net0.out_channels
+        la.head_q = Q
     check(lib.pwv_wavenet_layer_f32(ctypes.byref(la), s), 'pwv_wavenet_layer_f32')
     if not fuse_head:
         ha = _lib.HeadArgs()
-        ha.G = G
+        ha.G, ha.N, ha.T, ha.Q = G, x.shape[0], x.shape[1], Q
         for g in range(G):
             ha.in_[g], ha.packed[g], ha.out[g] = bufs[g][spare].data_ptr(), plans[g].packed_head.data_ptr(), outs[g].data_ptr()
-        ha.N, ha.T, ha.Q = n, t, net0.out_channels
         ha.in_mode, ha.precision = _lib.HEAD_IN_GATED, prec
         check(lib.pwv_wavenet_head_f32(ctypes.byref(ha), s), 'pwv_wavenet_head_f32')
     return False
@@ -948,14 +990,12 @@ def run_flow(nets: Sequence, x: torch.Tensor, cond, precision: Optional[str] = N
 
 def _run_nets(nets: Sequence, x: torch.Tensor, cond, precision: Optional[str], max_workgroups: int, affine_out: Optional[torch.Tensor]):
     """run_nets / run_flow: ([one [N, T, Q] tensor per net], whether `affine_out` = x*s + b was written by the launches)."""
-    lib = _lib.lib()
     prec = PRECISIONS[precision or DEFAULT_PRECISION]
     x = _require_cuda_f32(x, 'input_batch')
     if x.dim() != 3:
         raise ValueError('input_batch must be [N, T, C], got %s' % (tuple(x.shape),))
     n, t, qin = x.shape
-    G = len(nets)
-    assert 1 <= G <= _lib.PWV_MAX_NETS
+    assert 1 <= len(nets) <= _lib.PWV_MAX_NETS
     net0 = nets[0]
     for other in nets[1:]:
         assert _same_structure(net0, other)
@@ -963,29 +1003,8 @@ def _run_nets(nets: Sequence, x: torch.Tensor, cond, precision: Optional[str], m
         raise ValueError('input has %d channels, net expects %d' % (qin, net0.in_channels))
     if n * t == 0:
         return [torch.empty((n, t, net0.out_channels), dtype=torch.float32, device=x.device) for _ in nets], False
-    dev = x.device
-    s = _stream()
-
-    # ---- conditioning mode ------------------------------------------------------------------
-    cond_t = None
-    hop = offset = frames_per_utt = 0
-    if cond is None:
-        mode = 'none'
-    elif isinstance(cond, RepeatedCondition):
-        mode = 'frames'
-        if cond.length != t or cond.frames.shape[0] != n:
-            raise ValueError('condition %s does not match input %s' % (cond.shape, tuple(x.shape)))
-        if cond.frames.shape[2] != net0.condition_channels:
-            raise ValueError('condition has %d channels, net expects %d' % (cond.frames.shape[2], net0.condition_channels))
-        hop, offset, frames_per_utt = cond.hop, cond.offset, cond.frames.shape[1]
-    else:
-        mode = 'samples'
-        cond_t = _require_cuda_f32(cond, 'condition_batch')
-        if tuple(cond_t.shape) != (n, t, net0.condition_channels):
-            raise ValueError('condition_batch %s does not match input %s / %d channels'
-                             % (tuple(cond_t.shape), tuple(x.shape), net0.condition_channels))
-    half = prec == _lib.PREC_F16
-    if half and (qin != 1 or net0.use_skip_connection):
+    mode, cond_geom, cond_t = _check_condition(net0, cond, x)
+    if prec == _lib.PREC_F16 and (qin != 1 or net0.use_skip_connection):
         raise _lib.PwvError("precision 'f16' supports scalar-input nets without skip accumulation only")
     plans = [get_plan(net, mode, prec) for net in nets]
     if prec == _lib.PREC_F16X3 and not all(p.f16x3_ok and p.x_limit > 0 for p in plans):
@@ -999,90 +1018,106 @@ def _run_nets(nets: Sequence, x: torch.Tensor, cond, precision: Optional[str], m
     x_limit = min(p.x_limit for p in plans)
     if prec == _lib.PREC_F16X3:
         _log_range('flow_input', x, x_limit, [p.range_bounds for p in plans])
-    L = plans[0].n_layers
     for net, plan in zip(nets, plans):
         assert plan.n_layers == len(net.dilations) and plan.with_skip == bool(net.use_skip_connection)
-    rows = n * t
-
-    def tile_buf(channels, dtype=torch.float32):
-        return torch.empty((lib.pwv_tile32_floats(rows, channels),), dtype=dtype, device=dev)
-
     if cond_t is not None:
-        # per-sample condition -> the form the kernels of this precision read: fp32 tile32 ('f32'), pre-split fp16
-        # hi / lo planes ('f16x3': split once per forward instead of once per net-layer), fp16 blocks ('f16').
-        # Every flow of a forward pass is handed the same tensor: convert it once (the entry is valid while that
-        # very tensor object is alive and has not been written to)
-        global _cond_cache
-        hit = _cond_cache
-        if (hit is not None and hit[0]() is cond_t and hit[1] == cond_t._version and hit[2] == prec
-                and hit[4] == torch.cuda.current_stream()):
-            cond_t = hit[3]
-        else:
-            cc = cond_t.shape[2]
-            if prec == _lib.PREC_F32:
-                ct = tile_buf(cc)
-                check(lib.pwv_rows_to_tile32_f32(_ptr(cond_t), _ptr(ct), rows, cc, s), 'pwv_rows_to_tile32_f32')
-            elif prec == _lib.PREC_F16X3:
-                ct = torch.empty((2 * lib.pwv_tile32_floats(rows, cc),), dtype=torch.float16, device=dev)
-                check(lib.pwv_cond_split_f16(_ptr(cond_t), _ptr(ct), n, t, cc, s), 'pwv_cond_split_f16')
-            else:
-                ct = tile_buf(cc, torch.float16)
-                check(lib.pwv_cond_to_f16(_ptr(cond_t), _ptr(ct), n, t, cc, s), 'pwv_cond_to_f16')
-            _cond_cache = (weakref.ref(cond_t), cond_t._version, prec, ct, torch.cuda.current_stream())
-            cond_t = ct
+        cond_t = _cond_operand(cond_t, prec)
+    path = _choose_path(net0, plans, mode, n, t, max_workgroups, cond_geom)
+    side = _net_streams(x.device) if path.two else None
+    projs = _projections(cond, mode, plans, precision, side)
+    row_stride = projs[0].stride(0)      # (all nets' columns where project_all's one GEMM made them, else 128 * L)
+    bufs = _causal_front(x, net0, plans, path, x_limit)
+    outs = [torch.empty((n, t, net0.out_channels), dtype=torch.float32, device=x.device) for _ in nets]
+    if path.persist:
+        aff = (x, affine_out) if (affine_out is not None and qin == 1) else None
+        return outs, _run_stack_persist(path, nets, plans, projs, bufs, outs, x, x_limit, row_stride, cond_geom, aff)
+    _run_stack_layers(path, nets, plans, projs, bufs, outs, x, x_limit, cond_t, row_stride, cond_geom, max_workgroups, side)
+    return outs, False
 
-    # ---- frame-rate projection P (or bias-only row) -------------------------------------------
-    main = torch.cuda.current_stream()
-    use_skip = bool(net0.use_skip_connection)
-    # layer 0 rebuilds the causal layer's output from the scalar input itself (pwv_layer_args.x_first), so the [rows, 64]
-    # front buffer is neither written nor read
-    first_fused = (FUSE_FIRST and prec in (_lib.PREC_F16X3, _lib.PREC_F32, _lib.PREC_F16) and qin == 1 and net0.filter_width == 2
-                   and net0.residual_channels == 64 and not net0.use_skip_connection and plans[0].causal_bias is None)
-    persist_able = ((prec == _lib.PREC_F32 or (prec == _lib.PREC_F16X3 and FUSE_HEAD)) and mode != 'samples' and not use_skip
-                    and max_workgroups == 0)
-    # the tail (last layer + head inside the launch) has a look-back of its own -- the stack's LAST dilation: ask for the launch that
-    # will be made, and keep the persistent layers with the tail as a launch of its own where only the tail does not fit
-    tail = bool(persist_able and tail_fusable(prec))
-    persist = persist_able and _use_persist(G, n, t, net0.dilations, 0 if first_fused else 1, net0.out_channels if tail else 0)
-    if persist_able and tail and not persist:
-        tail = False
-        persist = _use_persist(G, n, t, net0.dilations, 0 if first_fused else 1, 0)
-    two = G == 2 and TWO_STREAMS and max_workgroups == 0 and not persist
-    side = _net_streams(dev) if two else None
-    row_stride = 128 * L
-    bank = getattr(cond, 'proj_bank', None) if mode == 'frames' else None
+
+def _check_condition(net0, cond, x: torch.Tensor):
+    """(conditioning mode, (hop, offset, frames per utterance) of a frame-rate condition, the per-sample condition or None)."""
+    n, t = x.shape[0], x.shape[1]
+    if cond is None:
+        return 'none', (0, 0, 0), None
+    if isinstance(cond, RepeatedCondition):
+        if cond.length != t or cond.frames.shape[0] != n:
+            raise ValueError('condition %s does not match input %s' % (cond.shape, tuple(x.shape)))
+        if cond.frames.shape[2] != net0.condition_channels:
+            raise ValueError('condition has %d channels, net expects %d' % (cond.frames.shape[2], net0.condition_channels))
+        return 'frames', (cond.hop, cond.offset, cond.frames.shape[1]), None
+    cond_t = _require_cuda_f32(cond, 'condition_batch')
+    if tuple(cond_t.shape) != (n, t, net0.condition_channels):
+        raise ValueError('condition_batch %s does not match input %s / %d channels'
+                         % (tuple(cond_t.shape), tuple(x.shape), net0.condition_channels))
+    return 'samples', (0, 0, 0), cond_t
+
+
+def _cond_operand(cond_t: torch.Tensor, prec: int) -> torch.Tensor:
+    """The per-sample condition in the form the kernels of this precision read: fp32 tile32 ('f32'), pre-split fp16 hi / lo planes
+    ('f16x3': split once per forward instead of once per net-layer), fp16 blocks ('f16').  Every flow of a forward pass is handed the
+    same tensor: convert it once (the entry is valid while that very tensor object is alive and has not been written to)."""
+    global _cond_cache
+    hit = _cond_cache
+    if (hit is not None and hit[0]() is cond_t and hit[1] == cond_t._version and hit[2] == prec
+            and hit[4] == torch.cuda.current_stream()):
+        return hit[3]
+    lib, s = _lib.lib(), _stream()
+    n, t, cc = cond_t.shape
+    floats = lib.pwv_tile32_floats(n * t, cc)
+    if prec == _lib.PREC_F32:
+        ct = torch.empty((floats,), dtype=torch.float32, device=cond_t.device)
+        check(lib.pwv_rows_to_tile32_f32(_ptr(cond_t), _ptr(ct), n * t, cc, s), 'pwv_rows_to_tile32_f32')
+    elif prec == _lib.PREC_F16X3:
+        ct = torch.empty((2 * floats,), dtype=torch.float16, device=cond_t.device)
+        check(lib.pwv_cond_split_f16(_ptr(cond_t), _ptr(ct), n, t, cc, s), 'pwv_cond_split_f16')
+    else:
+        ct = torch.empty((floats,), dtype=torch.float16, device=cond_t.device)
+        check(lib.pwv_cond_to_f16(_ptr(cond_t), _ptr(ct), n, t, cc, s), 'pwv_cond_to_f16')
+    _cond_cache = (weakref.ref(cond_t), cond_t._version, prec, ct, torch.cuda.current_stream())
+    return ct
+
+
+def _projections(cond, mode: str, plans, precision: Optional[str], side) -> List[torch.Tensor]:
+    """P of each net: its column block of the forward's one projection GEMM (project_all), else a frame-rate GEMM of its own, or
+    the bias-only row without a frame-rate condition."""
+    if mode != 'frames':
+        return [p.proj_b.reshape(1, -1) for p in plans]
+    bank = getattr(cond, 'proj_bank', None)
     if bank is not None and all(id(p) in bank for p in plans):
-        projs = [bank[id(p)] for p in plans]          # column blocks of the forward's one projection GEMM (project_all)
-        row_stride = projs[0].stride(0)
-    elif mode == 'frames':
-        f2d = _require_cuda_f32(cond.frames, 'frames').reshape(n * frames_per_utt, -1)
-        if two:
-            # net 0's P on the main stream, net 1's on its own stream: its chain then starts one small GEMM
-            # later than net 0's, which keeps the two chains out of phase (they would otherwise run in
-            # lockstep and hit their launch gaps / tails together)
-            pname = precision or DEFAULT_PRECISION
-            projs = [linear_op(f2d, plans[0].proj_w, plans[0].proj_b, relu=False, precision=pname), None]
-            side[1].wait_stream(main)
-            with torch.cuda.stream(side[1]):
-                projs[1] = linear_op(f2d, plans[1].proj_w, plans[1].proj_b, relu=False, precision=pname)
-        else:
-            projs = [linear_op(f2d, p.proj_w, p.proj_b, relu=False, precision=precision or DEFAULT_PRECISION) for p in plans]
-    else:
-        projs = [p.proj_b.reshape(1, -1) for p in plans]
+        return [bank[id(p)] for p in plans]
+    pname = precision or DEFAULT_PRECISION
+    n, frames, _ = cond.frames.shape
+    f2d = _require_cuda_f32(cond.frames, 'frames').reshape(n * frames, -1)
+    if side is None:
+        return [linear_op(f2d, p.proj_w, p.proj_b, relu=False, precision=pname) for p in plans]
+    # two streams: net 0's P on the main stream, net 1's on its own stream: its chain then starts one small GEMM later than
+    # net 0's, which keeps the two chains out of phase (they would otherwise run in lockstep and hit their launch gaps / tails together)
+    projs = [linear_op(f2d, plans[0].proj_w, plans[0].proj_b, relu=False, precision=pname), None]
+    side[1].wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side[1]):
+        projs[1] = linear_op(f2d, plans[1].proj_w, plans[1].proj_b, relu=False, precision=pname)
+    return projs
 
-    # ---- causal layer (modules.py:174-183) ----------------------------------------------------
-    R = net0.residual_channels
-    if persist:      # the persistent launch rotates through three buffers of one allocation (pwv_persist_args.x_ring)
-        bufs = [list(torch.empty((3, lib.pwv_tile32_floats(rows, R)), dtype=torch.float32, device=dev).unbind(0)) for _ in nets]
+
+def _causal_front(x: torch.Tensor, net0, plans, path: _Path, x_limit: float) -> List[List[torch.Tensor]]:
+    """Each net's residual buffers -- the persistent launch's ring of three (pwv_persist_args.x_ring) or the per-layer path's
+    ping-pong pair -- with the causal layer's output (modules.py:174-183) in buffer 0.  Where layer 0 rebuilds that output from
+    the scalar input itself (path.first_fused, pwv_layer_args.x_first) the [rows, 64] front buffer is neither written nor read."""
+    lib, s = _lib.lib(), _stream()
+    n, t, qin = x.shape
+    rows, R, G, prec = n * t, net0.residual_channels, len(plans), plans[0].precision
+    half = prec == _lib.PREC_F16
+    if path.persist:
+        bufs = [list(torch.empty((3, lib.pwv_tile32_floats(rows, R)), dtype=torch.float32, device=x.device).unbind(0)) for _ in plans]
     else:
-        bufs = [[tile_buf(R, torch.float16 if half else torch.float32) for _ in range(2)] for _ in nets]
-    # split-fp16 and fp32 kernels: layer 0 rebuilds the causal layer's output from the scalar input itself
-    # (pwv_layer_args.x_first), so the [rows, 64] front buffer is neither written nor read
-    if prec == _lib.PREC_F16X3 and not first_fused:
+        bufs = [[torch.empty((lib.pwv_tile32_floats(rows, R),), dtype=torch.float16 if half else torch.float32, device=x.device)
+                 for _ in range(2)] for _ in plans]
+    if path.first_fused:
+        return bufs
+    if prec == _lib.PREC_F16X3:
         range_check_op(x, x_limit, kind=None)          # (layer 0 checks its scalar input itself when it rebuilds the causal layer)
-    if first_fused:
-        pass
-    elif qin == 1:
+    if qin == 1:
         filt = (c_void_p * G)(*[p.causal_filter.data_ptr() for p in plans])
         hout = (c_void_p * G)(*[b[0].data_ptr() for b in bufs])
         front = lib.pwv_iaf_front_f16 if half else lib.pwv_iaf_front_f32
@@ -1094,29 +1129,29 @@ def _run_nets(nets: Sequence, x: torch.Tensor, cond, precision: Optional[str], m
                 channel_affine_op(bufs[g][0], None, p.causal_bias, tile32_rows=rows, channels=R, out=bufs[g][0])
     else:
         for g, p in enumerate(plans):      # multi-channel input: generic causal conv, then into tile32
-            hrows = torch.empty((n, t, R), dtype=torch.float32, device=dev)
+            hrows = torch.empty((n, t, R), dtype=torch.float32, device=x.device)
             check(lib.pwv_causal_conv_f32(_ptr(x), _ptr(p.causal_filter), _ptr(hrows), n, t, qin, R,
                                           net0.filter_width, 1, s), 'pwv_causal_conv_f32')
             check(lib.pwv_rows_to_tile32_f32(_ptr(hrows), _ptr(bufs[g][0]), rows, R, s), 'pwv_rows_to_tile32_f32')
+    return bufs
 
 
-    skips = [tile_buf(net0.skip_channels) for _ in nets] if use_skip else None
-    Q = net0.out_channels
-    outs = [torch.empty((n, t, Q), dtype=torch.float32, device=dev) for _ in nets]
-
-    if persist:
-        aff = (x, affine_out) if (affine_out is not None and qin == 1) else None
-        done = _run_stack_persist(lib, nets, plans, projs, bufs, outs, x if first_fused else None, x_limit, row_stride,
-                                  (hop, offset, frames_per_utt) if mode == 'frames' else (0, 0, 0), n, t, s, prec, aff, tail)
-        return outs, done
-    if two:
+def _run_stack_layers(path: _Path, nets, plans, projs, bufs, outs, x, x_limit, cond_t, row_stride, cond_geom, max_workgroups, side):
+    """The whole stack + head as per-layer launches in ONE C call (pwv_wavenet_stack_f32; over two side streams where path.two)."""
+    lib, s = _lib.lib(), _stream()
+    G, L, prec = len(nets), plans[0].n_layers, plans[0].precision
+    net0 = nets[0]
+    n, t = x.shape[0], x.shape[1]
+    use_skip = bool(net0.use_skip_connection)
+    skips = [torch.empty((lib.pwv_tile32_floats(n * t, net0.skip_channels),), dtype=torch.float32, device=x.device)
+             for _ in nets] if use_skip else None
+    main = torch.cuda.current_stream()
+    if path.two:
         for g in range(2):
             side[g].wait_stream(main)
-    # the whole stack + head in ONE C call (launches interleaved over the two streams)
     sa = StackArgs()
-    sa.G, sa.n_layers = G, L
-    dil = (ctypes.c_int * L)(*[int(d) for d in net0.dilations])
-    sa.dilations = dil
+    sa.G, sa.n_layers, sa.Q, sa.N, sa.T = G, L, net0.out_channels, n, t
+    sa.dilations = (ctypes.c_int * L)(*[int(d) for d in net0.dilations])
     for g in range(G):
         sa.buf0[g], sa.buf1[g] = bufs[g][0].data_ptr(), bufs[g][1].data_ptr()
         sa.packed_layers[g] = plans[g].packed_layers.data_ptr()
@@ -1124,30 +1159,18 @@ def _run_nets(nets: Sequence, x: torch.Tensor, cond, precision: Optional[str], m
         sa.skip[g] = skips[g].data_ptr() if use_skip else None
         sa.packed_head[g] = plans[g].packed_head.data_ptr()
         sa.out[g] = outs[g].data_ptr()
-    sa.packed_layer_stride = plans[0].layer_floats
-    sa.proj_row_stride = row_stride
-    sa.cond = _ptr(cond_t)
-    sa.cond_channels = net0.condition_channels if mode == 'samples' else 0
-    sa.Q, sa.N, sa.T = Q, n, t
-    sa.cond_hop, sa.cond_offset, sa.cond_frames = (hop, offset, frames_per_utt) if mode == 'frames' else (0, 0, 0)
-    sa.precision = prec
-    sa.max_workgroups = max_workgroups
-    sa.separate_head = 0 if FUSE_HEAD else 1
-    if first_fused:
-        sa.x_first = _ptr(x)
-        sa.x_limit = x_limit
-        sa.range_flag = range_flag_ptr()
-        for g in range(G):
-            sa.causal_filter[g] = plans[g].causal_filter.data_ptr()
-        if FOLD_FIRST and all(p.first_fold is not None for p in plans):
-            for g in range(G):
-                sa.first_fold[g] = plans[g].first_fold.data_ptr()
-    streams = (c_void_p * 2)(side[0].cuda_stream if two else s.value, side[1].cuda_stream if two else None)
+    sa.packed_layer_stride, sa.proj_row_stride = plans[0].layer_floats, row_stride
+    sa.cond, sa.cond_channels = _ptr(cond_t), (net0.condition_channels if cond_t is not None else 0)
+    sa.cond_hop, sa.cond_offset, sa.cond_frames = cond_geom
+    sa.precision, sa.max_workgroups, sa.separate_head = prec, max_workgroups, 0 if FUSE_HEAD else 1
+    if path.first_fused:
+        _set_x_first(sa, plans, x, x_limit)
+    streams = (c_void_p * 2)(side[0].cuda_stream if path.two else s.value, side[1].cuda_stream if path.two else None)
     evs = []
     if EVENT_LOG is not None and L > 1:
         # bench.py's live kernel timing: the library records one event pair per chain around its run of residual-layer
         # launches (pwv_stack_args.ev_begin / ev_end) -- the production launch path plus two event records
-        for c, so in enumerate(side[:2] if two else [main]):
+        for c, so in enumerate(side[:2] if path.two else [main]):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(so)       # materialises the hipEvent_t handles; the library re-records them
             e1.record(so)
@@ -1155,8 +1178,7 @@ def _run_nets(nets: Sequence, x: torch.Tensor, cond, precision: Optional[str], m
             evs.append((e0, e1))
     check(lib.pwv_wavenet_stack_f32(ctypes.byref(sa), streams), 'pwv_wavenet_stack_f32')
     for e0, e1 in evs:
-        EVENT_LOG.append(('layer_residual', e0, e1, 1 if two else G, L - 1))
-    if two:
+        EVENT_LOG.append(('layer_residual', e0, e1, 1 if path.two else G, L - 1))
+    if path.two:
         for g in range(2):
             main.wait_stream(side[g])
-    return outs, False

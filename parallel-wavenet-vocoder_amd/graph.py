@@ -73,8 +73,7 @@ class GraphedVocoder(object):
     @staticmethod
     def _launch_mode():
         """what decides WHICH launches a forward enqueues, besides the weights: a graph captured under another value is stale"""
-        return (engine.PERSIST, engine.persist_suspended(), engine.TWO_STREAMS, engine.FOLD_FIRST, engine.FUSE_FIRST, engine.FUSE_HEAD,
-                engine.FUSE_TAIL, engine.HOIST_P, engine.PERSIST_MAX_LAYERS, engine.PERSIST_MIN_UNITS, engine.DEFAULT_PRECISION)
+        return engine.launch_knobs()
 
     def verify(self):
         """Replays only enqueue: wait for them and raise like IAFVocoder.verify().  After a PwvPersistError the engine has

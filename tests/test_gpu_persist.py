@@ -18,13 +18,13 @@ pytestmark = pytest.mark.gpu
 D10 = [1, 2, 4, 8, 16, 32, 64, 128, 256, 512]
 
 
-def _nets(gpu, L, G, seed=3, cond_channels=80):
+def _nets(gpu, L, G, seed=3, cond_channels=80, dilations=None):
     import torch
     from pwv_amd import engine
     from pwv_amd.modules import WaveNet
     from pwv_amd.variables import VariableStore
     store = VariableStore(device=gpu, seed=seed)
-    kw = dict(batch_size=1, dilations=(D10 * 3)[:L], filter_width=2, residual_channels=64, dilation_channels=64, skip_channels=128,
+    kw = dict(batch_size=1, dilations=dilations or (D10 * 3)[:L], filter_width=2, residual_channels=64, dilation_channels=64, skip_channels=128,
               quantization_channels=1, use_biases=True, condition_channels=cond_channels, use_skip_connection=False, is_training=False, store=store)
     nets = [WaveNet(name='n%d' % g, **kw) for g in range(G)]
     return store, nets
@@ -326,6 +326,53 @@ def test_a_tail_that_reaches_too_far_runs_as_its_own_launch(gpu, persist_knobs):
     assert engine.persist_status() == 0 and [e[0] for e in log] == ['persist'] and log[0][6] == 0      # persistent layers, no tail in the launch
     for a, b in zip(ref, got):
         assert torch.equal(a, b)
+
+
+@pytest.mark.parametrize('case', ['tail', 'tail_does_not_fit', 'several_runs', 'per_layer_above_auto_rows'])
+def test_every_launched_struct_is_the_one_the_path_choice_sized(gpu, persist_knobs, monkeypatch, case):
+    """One builder (engine._persist_launches) answers whether a stack runs persistently AND fills in the arguments of its launches: every
+    struct a flow launches is one that _choose_path recorded, in order, and the library sizes its workspace exactly as it did when the path
+    was chosen (the ADVICE r05 bug was a probe that asked about another launch than the one made).  Per-layer forwards launch none."""
+    import torch
+    from pwv_amd import _lib
+    engine = persist_knobs
+    engine.PERSIST = 'auto'
+    t, L, dilations = 16000, 10, None
+    if case == 'tail_does_not_fit':          # the LAST dilation reaches over 64 workgroups: the layers stay persistent, the tail does not
+        t, L, dilations = 4000, 6, [1, 2, 4, 8, 16, 2048]
+        engine.PERSIST_MIN_UNITS = 1
+    elif case == 'several_runs':             # 12 residual layers as runs of 4 + 4 + 4
+        L, engine.PERSIST_MAX_LAYERS = 13, 4
+    elif case == 'per_layer_above_auto_rows':
+        monkeypatch.setattr(engine, 'PERSIST_AUTO_MAX_ROWS', 8000)
+    store, nets = _nets(gpu, L, 2, dilations=dilations)
+    g = torch.Generator().manual_seed(11)
+    x = torch.randn((1, t, 1), generator=g).to(gpu)
+    cond = engine.RepeatedCondition(torch.rand((1, t // 80 + 1, 80), generator=g).to(gpu), 80, 40, t)
+    engine.run_flow(nets, x, cond)       # creates the variables
+    torch.cuda.synchronize()
+    lib, chosen, launched = _lib.lib(), [], []
+    choose = engine._choose_path
+
+    def spy(*a, **k):
+        path = choose(*a, **k)
+        chosen.append((path, [pa.workspace_bytes for _, pa in path.runs or ()]))
+        return path
+    monkeypatch.setattr(engine, '_choose_path', spy)
+    engine.PERSIST_ARGS_HOOK = lambda pa: launched.append((pa, lib.pwv_persist_workspace_bytes(ctypes.byref(pa))))
+    try:
+        engine.run_flow(nets, x, cond)
+        torch.cuda.synchronize()
+    finally:
+        engine.PERSIST_ARGS_HOOK = None
+    assert engine.persist_status() == 0 and len(chosen) == 1
+    path, recorded = chosen[0]
+    if case == 'per_layer_above_auto_rows':
+        assert not path.persist and not launched
+        return
+    assert path.persist and path.tail == (case != 'tail_does_not_fit') and len(path.runs) == (3 if case == 'several_runs' else 1)
+    assert [id(pa) for pa, _ in launched] == [id(pa) for _, pa in path.runs]
+    assert [nbytes for _, nbytes in launched] == recorded and all(recorded)
 
 
 def test_random_shapes_through_the_persistent_launch_under_load(gpu):

@@ -104,6 +104,25 @@ def test_repeated_condition_validation():
         RepeatedCondition(frames, 80, 40, 400)          # needs 6 frames
 
 
+@pytest.mark.parametrize('knob', ['PERSIST', '_persist_cooldown', 'TWO_STREAMS', 'FOLD_FIRST', 'FUSE_FIRST', 'FUSE_HEAD', 'FUSE_TAIL',
+                                  'HOIST_P', 'PERSIST_MAX_LAYERS', 'PERSIST_MIN_UNITS', 'DEFAULT_PRECISION', 'FUSE_PROLOGUE',
+                                  'FUSE_PROLOGUE_MAX_OUTPUTS', 'PERSIST_AUTO_MAX_ROWS'])
+def test_every_launch_knob_outdates_a_captured_graph(monkeypatch, knob):
+    """A graph captured under one value of a knob that decides which launches a forward enqueues is stale under another
+    (_persist_cooldown: a suspension of the persistent launches)."""
+    from pwv_amd import engine
+    from pwv_amd.graph import GraphedVocoder
+    key = GraphedVocoder._launch_mode()
+    saved = getattr(engine, knob)
+    other = {'PERSIST': False if saved is not False else 'auto', 'DEFAULT_PRECISION': 'f32' if saved != 'f32' else 'f16x3'}.get(knob)
+    if other is None:
+        other = (not saved) if isinstance(saved, bool) else saved + 1
+    monkeypatch.setattr(engine, knob, other)
+    assert GraphedVocoder._launch_mode() != key
+    monkeypatch.setattr(engine, knob, saved)
+    assert GraphedVocoder._launch_mode() == key
+
+
 def test_fused_supported_matrix():
     from pwv_amd.engine import RepeatedCondition
     from pwv_amd.modules import WaveNet
