@@ -52,7 +52,9 @@ typedef void* pwv_stream_t;
 const char* pwv_last_error(void);
 /* PWV_HIP_VERSION of the library that was loaded: major * 100 + minor.  A change of the major number changes the layout of an
  * argument struct: 3xx = pwv_persist_args begins with `struct_size`.  A client compiled against this header checks
- * pwv_version() / 100 == PWV_HIP_VERSION / 100 once after loading the library. */
+ * pwv_version() / 100 == PWV_HIP_VERSION / 100 once after loading the library.  Fields appended to pwv_persist_args behind
+ * `struct_size` (the packed-batch fields cu_rows ... varlen_rows among them) leave the number as it is: a shorter caller's
+ * struct reads as zeros behind its end, i.e. as the behaviour it was compiled for. */
 #define PWV_HIP_VERSION 301
 int pwv_version(void);
 /* number of compute units of the current device (grid sizing); <0 on error */
@@ -468,7 +470,29 @@ typedef struct pwv_persist_args {
     int tail_dilation;
     const float* affine_x;
     float* affine_out;
+    /* optional PACKED ("varlen") batch: N utterances of different lengths, concatenated.  Utterance i has len_i >= 32 rows (a multiple of
+     * cond_hop with a frame-rate condition) and t_mel_i = len_i / cond_hop + 1 frames; its sample t is row cu_rows[i] + t of every [R, .]
+     * buffer (x_ring in tile32 blocks of the R rows, x_first, tail_out, affine_x / affine_out), its P row for sample t is
+     * cu_frames[i] + (t + cond_offset) / cond_hop, and its look-back x[t-d] is zero for t < d.  T and cond_frames are ignored.
+     *   cu_rows    device int32 [N+1], cu_rows[0] = 0, cu_rows[N] = R
+     *   cu_frames  device int32 [N+1], cu_frames[0] = 0 (required with cond_hop > 0)
+     *   unit_map   device int32 [ceil(R/32)][PWV_VARLEN_REC_INTS]: pwv_varlen_unit_map(cu_rows, cu_frames, ...) -- built once per batch,
+     *              shared by every launch of the forward
+     *   varlen_rows  HOST copy of R (the plan and the grid are sized on the host; nothing is read back)
+     * All NULL / 0: the uniform batch of N x T rows.  Any of them set without the others (or R < 32 N) is PWV_EINVAL; read by
+     * pwv_persist_workspace_bytes and pwv_persist_short_input too.  A batch with a shorter utterance has no persistent form (the engine
+     * pads it).  Results are bit-identical to each utterance's own uniform launch. */
+    const int* cu_rows;
+    const int* cu_frames;
+    const int* unit_map;
+    long long varlen_rows;
 } pwv_persist_args;
+
+/* PWV_VARLEN_REC_INTS ints per 32-row unit of a packed batch: {n, cu_rows[n], cu_frames[n], cu_rows[n+1], cu_frames[n+1], 0, 0, 0}
+ * with n the utterance that holds the unit's first row (cu_frames NULL: the frame entries are 0).  Enqueued on `stream`; no host
+ * synchronisation, so lengths that are already on the device need no round trip.  units = ceil(R / 32). */
+#define PWV_VARLEN_REC_INTS 8
+int pwv_varlen_unit_map(const int* cu_rows, const int* cu_frames, int n_utt, int units, int* out, pwv_stream_t stream);
 
 size_t pwv_persist_workspace_bytes(const pwv_persist_args* args);
 /* 1 if pwv_wavenet_stack_persist_f32 takes its SHORT-INPUT instantiation for `args` (round 6; at most 7 units of 32 rows per workgroup and layer, i.e. up to

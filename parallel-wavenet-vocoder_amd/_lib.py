@@ -21,6 +21,8 @@ CSRC = [os.path.join(_PKG_DIR, 'csrc', f) for f in ('pwv_layer.hip', 'pwv_layer_
 
 HEADER_VERSION = 301          # PWV_HIP_VERSION of include/pwv_hip.h these ctypes mirrors were written against
 FIRST_FOLD_FLOATS = 2048      # PWV_FIRST_FOLD_FLOATS
+VARLEN_REC_INTS = 8           # PWV_VARLEN_REC_INTS: int32 per 32-row unit of a packed batch (pwv_varlen_unit_map)
+VARLEN_MIN_ROWS = 32          # the persistent launch of a packed batch needs every utterance this long
 PWV_MAX_NETS = 2
 PREC_F32, PREC_F16X3, PREC_F16 = 0, 1, 2
 OUT_RESIDUAL, OUT_GATED = 0, 1
@@ -34,7 +36,7 @@ EXPORTED_SYMBOLS = (
     'pwv_head_packed_floats', 'pwv_pack_head_f32', 'pwv_wavenet_head_f32', 'pwv_wavenet_stack_f32',
     'pwv_iaf_front_f16', 'pwv_cond_to_f16', 'pwv_tile32_floats', 'pwv_rows_to_tile32_f32', 'pwv_tile32_to_rows_f32',
     'pwv_linear_split_f32', 'pwv_cond_project_f32', 'pwv_pack_first_fold_f16x3', 'pwv_pack_first_fold_f32', 'pwv_cond_split_f16', 'pwv_range_flag', 'pwv_status_words_alloc', 'pwv_status_words_free', 'pwv_range_check_f32', 'pwv_range_stats_f32',
-    'pwv_persist_workspace_bytes', 'pwv_persist_short_input', 'pwv_persist_status', 'pwv_wavenet_stack_persist_f32',
+    'pwv_persist_workspace_bytes', 'pwv_persist_short_input', 'pwv_persist_status', 'pwv_wavenet_stack_persist_f32', 'pwv_varlen_unit_map',
     'pwv_wav_to_mel_db_f32', 'pwv_pack_proj_f32', 'pwv_instance_norm_workspace_bytes', 'pwv_instance_norm_f32', 'pwv_channel_affine_f32', 'pwv_add_f32', 'pwv_gate_f32',
 )
 
@@ -161,6 +163,11 @@ class PersistArgs(Structure):
         ('tail_dilation', c_int),
         ('affine_x', c_void_p),
         ('affine_out', c_void_p),
+        # a packed ("varlen") batch: device int32 prefix sums, the unit records of pwv_varlen_unit_map, R on the host
+        ('cu_rows', c_void_p),
+        ('cu_frames', c_void_p),
+        ('unit_map', c_void_p),
+        ('varlen_rows', ctypes.c_longlong),
     ]
 
     def __init__(self, *args, **kw):
@@ -312,6 +319,7 @@ def _declare(lib):
     lib.pwv_persist_short_input.argtypes = [POINTER(PersistArgs)]
     lib.pwv_persist_status.argtypes = [POINTER(c_void_p)]
     lib.pwv_wavenet_stack_persist_f32.argtypes = [POINTER(PersistArgs), c_void_p]
+    lib.pwv_varlen_unit_map.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]
     lib.pwv_range_stats_f32.argtypes = [f32p] * 8 + [c_int, f32p, c_void_p]
     lib.pwv_range_flag.argtypes = [POINTER(c_void_p)]
     lib.pwv_logistic_noise_stream_f32.argtypes = [f32p, c_int64, c_void_p, c_void_p]

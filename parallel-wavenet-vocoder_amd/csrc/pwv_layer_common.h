@@ -89,6 +89,30 @@ __device__ __forceinline__ void unit_rows(int unit, int lane, int rows, int N, i
     }
 }
 
+// ---- packed ("varlen") batches (include/pwv_hip.h, pwv_persist_args.cu_rows) ---------------------------------------
+// Utterance i holds the rows cu_rows[i] .. cu_rows[i+1]-1 (sample t = row cu_rows[i] + t) and the condition frames from
+// cu_frames[i] on.  Unit u (rows 32u .. 32u+31) is described by one record of kVarlenRec ints (pwv_varlen_unit_map):
+//     {n, cu_rows[n], cu_frames[n], cu_rows[n+1], cu_frames[n+1], 0, 0, 0},   n = the utterance that holds row 32u.
+// Every utterance has at least 32 rows, so a unit spans at most the two utterances n and n + 1.
+constexpr int kVarlenRec = PWV_VARLEN_REC_INTS;
+constexpr int kVarlenMinRows = 32;
+
+// unit_rows for a packed batch: `fb` = the first condition frame of the lane's utterance (its index is not needed).  The record
+// is read with scalar loads (the unit is wave-uniform); a unit past the last one (a clamped prefetch) reads the last record.
+__device__ __forceinline__ void unit_rows_varlen(const int* unit_map, int unit, int lane, int rows,
+                                                 int& row, bool& valid, int& rc, int& fb, int& t) {
+    typedef const __attribute__((address_space(4))) int* const_ints_t;      // constant address space: s_load
+    row = unit * 32 + (lane & 31);
+    valid = row < rows;
+    rc = valid ? row : rows - 1;
+    const int last = (rows - 1) >> 5;
+    const const_ints_t rec = (const_ints_t)(unit_map + (size_t)(unit < last ? unit : last) * kVarlenRec);
+    const int r0 = rec[1], f0 = rec[2], r1 = rec[3], f1 = rec[4];
+    const bool second = rc >= r1;
+    t = rc - (second ? r1 : r0);
+    fb = second ? f1 : f0;
+}
+
 // -DPWV_TRACE: waves of workgroup 0 record s_memtime at phase boundaries (tools/trace_layer.py)
 #ifdef PWV_TRACE
 #define PWV_STAMP(slot)                                                                   \

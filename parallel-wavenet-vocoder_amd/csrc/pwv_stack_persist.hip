@@ -103,6 +103,8 @@ struct PersistParams {
     const float* affine_x;                 // != NULL: out = fma(x, s, b) (modules.py:59) for the workgroup's rows, by whichever of the
     float* affine_out;                     // two nets' workgroups of a range finishes second (G = 2, Q = 1), or in place (G = 1, Q = 2)
     int* pair;                             // [nwg] arrival counters of the two nets' workgroups of a range (zero on entry and on exit)
+    // VARLEN instantiations: a packed batch (N = 1, T = R rows here); [units][kVarlenRec] records of pwv_varlen_unit_map (pwv_layer_common.h)
+    const int* unit_map;
 };
 
 // -DPWV_PTRACE: every wave accumulates s_memtime cycles: [0] whole loop, [1] drain at the top, [2] RAW spins, [3] WAR spins,
@@ -194,7 +196,10 @@ __device__ __forceinline__ void gemm_groups_dense(FR&& fr, f32x16 (&acc)[2], f32
 // SHORT (round 6): the instantiation for short inputs (at most kUnitModeMaxPerWg units per workgroup and layer: progress words per unit, stationary
 // units, a loader wave) -- a template parameter, not a run-time mode: as run-time branches in the general task loop the additions cost the long-input
 // launch 2.7 % of its step (SGPR spills reloaded per unit, profiles/r06_ab_experiments.md r06_r)
-template <bool F32, int MODE>
+// VARLEN: a packed batch of utterances of different lengths (pwv_persist_args.cu_rows): a lane's (utterance, time) and P row come from
+// its unit's record (unit_rows_varlen) instead of row / T.  Nothing else differs: the plan, ring, progress words and workspace are
+// defined on rows and units.  The instantiations without it compile to the instruction stream they had before it existed.
+template <bool F32, int MODE, bool VARLEN>
 __global__ __launch_bounds__(512) void stack_persist_kernel(const PersistParams p) {
     constexpr bool SHORT = MODE == 2;      // progress words per unit, stationary units, loader wave, ... (everything below that says SHORT)
     __shared__ __attribute__((aligned(16))) float lds[kLdsFloats];
@@ -215,6 +220,16 @@ __global__ __launch_bounds__(512) void stack_persist_kernel(const PersistParams 
         w = blockIdx.x / p.G;
     }
     const int rows = p.N * p.T;
+    // (row, utterance, time) of this lane's row of `unit` -- with VARLEN `nn` is the first condition frame of the lane's utterance, so
+    // that p_base(nn) is the first P row of the utterance either way
+    auto rows_of = [&](int unit, int& row, bool& valid, int& rc, int& nn, int& t) {
+        if constexpr (VARLEN) unit_rows_varlen(p.unit_map, unit, lane, rows, row, valid, rc, nn, t);
+        else unit_rows(unit, lane, rows, p.N, p.T, p.T_magic, p.T_shift, row, valid, rc, nn, t);
+    };
+    auto p_base = [&](int nn) -> int {
+        if constexpr (VARLEN) return nn;
+        else return nn * p.cond_frames;
+    };
     const int u_begin = w * p.per_wg;
     const int u_end = u_begin + p.per_wg < p.units ? u_begin + p.per_wg : p.units;
     const int n = u_end - u_begin;
@@ -291,7 +306,7 @@ __global__ __launch_bounds__(512) void stack_persist_kernel(const PersistParams 
     auto load_x = [&](int j, int unit, float (&xb)[32], float (&xc)[32]) {
         int row, rc, nn, t;
         bool valid;
-        unit_rows(unit, lane, rows, p.N, p.T, p.T_magic, p.T_shift, row, valid, rc, nn, t);
+        rows_of(unit, row, valid, rc, nn, t);
         const int d = dil_of(j);
         const bool has_prev = t >= d;
         if (p.x_first && j == 0) {
@@ -330,7 +345,7 @@ __global__ __launch_bounds__(512) void stack_persist_kernel(const PersistParams 
     auto load_xc = [&](int j, int unit, float (&xc)[32]) {
         int row, rc, nn, t;
         bool valid;
-        unit_rows(unit, lane, rows, p.N, p.T, p.T_magic, p.T_shift, row, valid, rc, nn, t);
+        rows_of(unit, row, valid, rc, nn, t);
         const int so = in_soff(j);
         const int oc = toff(rc);
 #pragma unroll
@@ -344,7 +359,7 @@ __global__ __launch_bounds__(512) void stack_persist_kernel(const PersistParams 
     auto load_xb = [&](int j, int unit, float (&xb)[32]) {
         int row, rc, nn, t;
         bool valid;
-        unit_rows(unit, lane, rows, p.N, p.T, p.T_magic, p.T_shift, row, valid, rc, nn, t);
+        rows_of(unit, row, valid, rc, nn, t);
         const int d = dil_of(j);
         const bool has_prev = t >= d;
         const int so = in_soff(j);
@@ -609,7 +624,7 @@ __global__ __launch_bounds__(512) void stack_persist_kernel(const PersistParams 
         while (u >= 0 && j == 0) {
             int row, rc, nn, t;
             bool valid;
-            unit_rows(u, lane, rows, p.N, p.T, p.T_magic, p.T_shift, row, valid, rc, nn, t);
+            rows_of(u, row, valid, rc, nn, t);
             // the four scalars (zero left of the utterance start) and the P row
             const float* x1 = p.x_first;
             const bool has_prev = t >= d;
@@ -620,7 +635,7 @@ __global__ __launch_bounds__(512) void stack_persist_kernel(const PersistParams 
             f32x16 acc[4];
             {
                 int prow = 0;
-                if (p.cond_hop > 0) prow = nn * p.cond_frames + fast_div(t + p.cond_offset, p.hop_magic, p.hop_shift);
+                if (p.cond_hop > 0) prow = p_base(nn) + fast_div(t + p.cond_offset, p.hop_magic, p.hop_shift);
                 const float* pr = proj_n + (size_t)prow * p.proj_row_stride + h * 64;
 #pragma unroll
                 for (int it = 0; it < 4; ++it)
@@ -754,7 +769,7 @@ __global__ __launch_bounds__(512) void stack_persist_kernel(const PersistParams 
         // ---- TOP: P row requested; the rows of this unit were requested during the previous one ---------------------------
         int row, rc, nn, t;
         bool valid;
-        unit_rows(u, lane, rows, p.N, p.T, p.T_magic, p.T_shift, row, valid, rc, nn, t);
+        rows_of(u, row, valid, rc, nn, t);
         if constexpr (SHORT) {
             flush_owed();
             PT_EV(3, j, u);
@@ -765,7 +780,7 @@ __global__ __launch_bounds__(512) void stack_persist_kernel(const PersistParams 
             // (buffer loads, like the rows: the compiler's scoreboard takes "all but the last 8 loads have landed" for the P row only if both are the
             //  same kind of vector-memory instruction; the launcher keeps the P rows of a short launch inside a descriptor's 4 GB)
             int prow = 0;
-            if (p.cond_hop > 0) prow = nn * p.cond_frames + fast_div(t + p.cond_offset, p.hop_magic, p.hop_shift);
+            if (p.cond_hop > 0) prow = p_base(nn) + fast_div(t + p.cond_offset, p.hop_magic, p.hop_shift);
             const int po = (prow * p.proj_row_stride + j * 128 + h * 64) * 4;
 #pragma unroll
             for (int it = 0; it < 4; ++it)
@@ -777,7 +792,7 @@ __global__ __launch_bounds__(512) void stack_persist_kernel(const PersistParams 
                 }
         } else {
             int prow = 0;
-            if (p.cond_hop > 0) prow = nn * p.cond_frames + fast_div(t + p.cond_offset, p.hop_magic, p.hop_shift);
+            if (p.cond_hop > 0) prow = p_base(nn) + fast_div(t + p.cond_offset, p.hop_magic, p.hop_shift);
             const float* pr = proj_n + (size_t)prow * p.proj_row_stride + j * 128 + h * 64;
 #pragma unroll
             for (int it = 0; it < 4; ++it)
@@ -1171,7 +1186,7 @@ __global__ __launch_bounds__(512) void stack_persist_kernel(const PersistParams 
                 auto load_tail = [&](int unit, float (&xb)[32], float (&xc)[32]) {
                     int row, rc, nn, t;
                     bool valid;
-                    unit_rows(unit, lane, rows, p.N, p.T, p.T_magic, p.T_shift, row, valid, rc, nn, t);
+                    rows_of(unit, row, valid, rc, nn, t);
                     const bool has_prev = t >= td;
                     const int oc = toff(rc), ob = toff(has_prev ? rc - td : rc);
 #pragma unroll
@@ -1199,11 +1214,11 @@ __global__ __launch_bounds__(512) void stack_persist_kernel(const PersistParams 
                     const int next = unit + 8;
                     int row, rc, nn, t;
                     bool valid;
-                    unit_rows(unit, lane, rows, p.N, p.T, p.T_magic, p.T_shift, row, valid, rc, nn, t);
+                    rows_of(unit, row, valid, rc, nn, t);
                     f32x16 acc[4];
                     {
                         int prow = 0;
-                        if (p.cond_hop > 0) prow = nn * p.cond_frames + fast_div(t + p.cond_offset, p.hop_magic, p.hop_shift);
+                        if (p.cond_hop > 0) prow = p_base(nn) + fast_div(t + p.cond_offset, p.hop_magic, p.hop_shift);
                         const float* pr = proj_n + (size_t)prow * p.proj_row_stride + L * 128 + h * 64;
 #pragma unroll
                         for (int it = 0; it < 4; ++it)
@@ -1448,6 +1463,22 @@ __global__ void persist_zero_kernel(int4* p, size_t n16) {
     if (i < n16) p[i] = int4{0, 0, 0, 0};
 }
 
+// one thread per unit of a packed batch: the record unit_rows_varlen reads (pwv_layer_common.h)
+__global__ void varlen_unit_map_kernel(const int* __restrict__ cu_rows, const int* __restrict__ cu_frames, int n_utt, int units, int* __restrict__ out) {
+    const int u = blockIdx.x * blockDim.x + threadIdx.x;
+    if (u >= units) return;
+    const int r = u * 32;
+    int lo = 0, hi = n_utt - 1;          // the last utterance that starts at or before row r
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (cu_rows[mid] <= r) lo = mid;
+        else hi = mid - 1;
+    }
+    int4* o = reinterpret_cast<int4*>(out + (size_t)u * kVarlenRec);
+    o[0] = int4{lo, cu_rows[lo], cu_frames ? cu_frames[lo] : 0, cu_rows[lo + 1]};
+    o[1] = int4{cu_frames ? cu_frames[lo + 1] : 0, 0, 0, 0};
+}
+
 }  // namespace pwv
 
 using namespace pwv;
@@ -1518,12 +1549,27 @@ static int persist_plan(int G, long long rows, int n_layers, const int* dil, int
 
 static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
+static bool is_varlen(const pwv_persist_args* a) { return a->cu_rows || a->cu_frames || a->unit_map || a->varlen_rows != 0; }
+// the rows a launch covers: N*T, or R of a packed batch
+static long long launch_rows(const pwv_persist_args* a) { return is_varlen(a) ? a->varlen_rows : (long long)a->N * a->T; }
+
+// the packed-batch fields are all set or all NULL / 0 (include/pwv_hip.h); checked before the plan, which needs a device
+static int varlen_check(const pwv_persist_args* a, const char* who) {
+    if (!is_varlen(a)) return PWV_OK;
+    PWV_CHECK_ARG(a->cu_rows && a->unit_map && a->varlen_rows > 0, "%s: a packed batch needs cu_rows, unit_map and varlen_rows (R) together", who);
+    PWV_CHECK_ARG(a->cond_hop <= 0 || a->cu_frames, "%s: a packed batch with a frame-rate condition (cond_hop > 0) needs cu_frames", who);
+    PWV_CHECK_ARG(a->N >= 1 && a->varlen_rows >= (long long)kVarlenMinRows * a->N,
+                  "%s: packed batch of %d utterances in %lld rows: every utterance needs at least %d rows", who, a->N, a->varlen_rows, kVarlenMinRows);
+    return PWV_OK;
+}
+
 // the short-input instantiation: the plan's verdict (units per workgroup, look-back reach), and a folded layer 0 if the run starts with one (it has
 // no unfolded form), and the P rows inside the 2 GB its buffer descriptor's 32-bit offsets reach.  (The workspace is sized by the plan alone.)
 static int short_input_mode(const pwv_persist_args* a, const PersistPlan& pl) {
     if (pl.unit_mode != 2) return 0;
     if (a->x_first && !a->first_fold[0]) return 0;
-    const long long p_rows = a->cond_hop > 0 ? (long long)a->N * a->cond_frames : 1;
+    // (a packed batch: R / hop + N frames, the layout's t_mel_i = len_i / hop + 1)
+    const long long p_rows = a->cond_hop > 0 ? (is_varlen(a) ? a->varlen_rows / a->cond_hop + a->N : (long long)a->N * a->cond_frames) : 1;
     if (p_rows * a->proj_row_stride * 4 >= (1ll << 31)) return 0;
     return 2;
 }
@@ -1547,7 +1593,8 @@ size_t pwv_persist_workspace_bytes(const pwv_persist_args* args) {
     pwv_persist_args copy;
     if (persist_args_copy(args, copy, "pwv_persist_workspace_bytes") != PWV_OK) return 0;
     const pwv_persist_args* a = &copy;
-    if (persist_plan(a->G, (long long)a->N * a->T, a->n_layers, a->dilations, cus, a->max_workgroups, a->min_units_per_workgroup, a->tail_q, a->tail_dilation, pl) != PWV_OK) return 0;
+    if (varlen_check(a, "pwv_persist_workspace_bytes") != PWV_OK) return 0;
+    if (persist_plan(a->G, launch_rows(a), a->n_layers, a->dilations, cus, a->max_workgroups, a->min_units_per_workgroup, a->tail_q, a->tail_dilation, pl) != PWV_OK) return 0;
     // progress words + the abort word + the exit counter (one 256-byte line) + one arrival counter per range (the tail's affine)
     // (+ in unit mode one word per unit and net)
     return align256((size_t)a->G * pl.nwg * kProgStride * 4 + 256) + align256((size_t)pl.nwg * 4) + (pl.unit_mode ? align256((size_t)a->G * pl.units * kUnitStride * 4) : 0);
@@ -1558,7 +1605,8 @@ int pwv_persist_short_input(const pwv_persist_args* args) {
     pwv_persist_args copy;
     if (persist_args_copy(args, copy, "pwv_persist_short_input") != PWV_OK) return -1;
     const pwv_persist_args* a = &copy;
-    if (persist_plan(a->G, (long long)a->N * a->T, a->n_layers, a->dilations, device_cus(), a->max_workgroups, a->min_units_per_workgroup, a->tail_q, a->tail_dilation, pl) != PWV_OK) return -1;
+    if (varlen_check(a, "pwv_persist_short_input") != PWV_OK) return -1;
+    if (persist_plan(a->G, launch_rows(a), a->n_layers, a->dilations, device_cus(), a->max_workgroups, a->min_units_per_workgroup, a->tail_q, a->tail_dilation, pl) != PWV_OK) return -1;
     return short_input_mode(a, pl) == 2 ? 1 : 0;
 }
 
@@ -1567,13 +1615,15 @@ int pwv_wavenet_stack_persist_f32(const pwv_persist_args* args, pwv_stream_t str
     if (int rc0 = persist_args_copy(args, copy, "pwv_wavenet_stack_persist_f32")) return rc0;
     const pwv_persist_args* a = &copy;
     PWV_CHECK_ARG(a->workspace, "pwv_wavenet_stack_persist_f32: NULL workspace");
+    if (int rc1 = varlen_check(a, "pwv_wavenet_stack_persist_f32")) return rc1;
+    const bool varlen = is_varlen(a);
     const int cus = device_cus();
     if (cus <= 0) return set_error(PWV_EHIP, "no HIP device");
     PersistParams p{};
     PersistPlan pl;
-    int rc = persist_plan(a->G, (long long)a->N * a->T, a->n_layers, a->dilations, cus, a->max_workgroups, a->min_units_per_workgroup, a->tail_q, a->tail_dilation, pl);
+    int rc = persist_plan(a->G, launch_rows(a), a->n_layers, a->dilations, cus, a->max_workgroups, a->min_units_per_workgroup, a->tail_q, a->tail_dilation, pl);
     if (rc != PWV_OK) return rc;
-    PWV_CHECK_ARG(a->N >= 1 && a->T >= 1, "pwv_wavenet_stack_persist_f32: bad N/T");
+    PWV_CHECK_ARG(a->N >= 1 && (varlen || a->T >= 1), "pwv_wavenet_stack_persist_f32: bad N/T");
     PWV_CHECK_ARG(a->precision == PWV_PREC_F16X3 || a->precision == PWV_PREC_F32, "pwv_wavenet_stack_persist_f32: precision must be PWV_PREC_F16X3 or PWV_PREC_F32");
     PWV_CHECK_ARG(a->proj_row_stride % 4 == 0 && a->cond_hop >= 0, "pwv_wavenet_stack_persist_f32: bad projection arguments");
     PWV_CHECK_ARG(a->workspace_bytes >= pwv_persist_workspace_bytes(a), "pwv_wavenet_stack_persist_f32: workspace too small");
@@ -1600,8 +1650,9 @@ int pwv_wavenet_stack_persist_f32(const pwv_persist_args* args, pwv_stream_t str
     p.packed_stride = (long long)a->packed_layer_stride;
     p.proj_row_stride = a->proj_row_stride;
     p.G = a->G;
-    p.N = a->N;
-    p.T = a->T;
+    p.N = varlen ? 1 : a->N;                   // (a packed batch is one run of R rows to everything but unit_rows_varlen)
+    p.T = varlen ? (int)a->varlen_rows : a->T;
+    p.unit_map = varlen ? a->unit_map : nullptr;
     p.n_layers = a->n_layers;
     p.units = pl.units;
     p.per_wg = pl.per_wg;
@@ -1614,13 +1665,13 @@ int pwv_wavenet_stack_persist_f32(const pwv_persist_args* args, pwv_stream_t str
     // dirty when the launch ends (dead data: the ring is scratch) is written back between this launch and the next one: all
     // write-through measures -0.8 % / -0.2 % on C3 on two boxes (82 MB per layer), -0.2 % on C4, but +5 % on C1 and level at 16000 rows
     // (4 - 8 MB per layer) (profiles/r05_ab_experiments.md, r05_h / r05_i).  Same bits either way.
-    p.all_wt = (long long)a->N * a->T * a->G * 256 > (32ll << 20) ? 1 : 0;
+    p.all_wt = launch_rows(a) * a->G * 256 > (32ll << 20) ? 1 : 0;
     PWV_CHECK_ARG(a->ring_rotation >= 0 && a->ring_rotation < 3, "pwv_wavenet_stack_persist_f32: ring_rotation must be 0, 1 or 2");
     p.rot = a->ring_rotation;
     p.cond_hop = a->cond_hop;
     p.cond_offset = a->cond_offset;
     p.cond_frames = a->cond_frames;
-    make_magic((unsigned)a->T, p.T_magic, p.T_shift);
+    make_magic((unsigned)p.T, p.T_magic, p.T_shift);
     make_magic((unsigned)(a->cond_hop > 0 ? a->cond_hop : 1), p.hop_magic, p.hop_shift);
     for (int j = 0; j < a->n_layers; ++j) p.dil[j] = a->dilations[j];
     p.x_first = a->x_first;
@@ -1669,15 +1720,33 @@ int pwv_wavenet_stack_persist_f32(const pwv_persist_args* args, pwv_stream_t str
     if (!a->workspace_clean)
         hipLaunchKernelGGL(persist_zero_kernel, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, s, (int4*)a->workspace, n16);
     const dim3 grid(a->G * pl.nwg), block(512);
-    if (a->precision == PWV_PREC_F32) {
-        if (pl.unit_mode == 2) hipLaunchKernelGGL((stack_persist_kernel<true, 2>), grid, block, 0, s, p);
-        else hipLaunchKernelGGL((stack_persist_kernel<true, 0>), grid, block, 0, s, p);
+    if (varlen) {
+        if (a->precision == PWV_PREC_F32) {
+            if (pl.unit_mode == 2) hipLaunchKernelGGL((stack_persist_kernel<true, 2, true>), grid, block, 0, s, p);
+            else hipLaunchKernelGGL((stack_persist_kernel<true, 0, true>), grid, block, 0, s, p);
+        } else {
+            if (pl.unit_mode == 2) hipLaunchKernelGGL((stack_persist_kernel<false, 2, true>), grid, block, 0, s, p);
+            else hipLaunchKernelGGL((stack_persist_kernel<false, 0, true>), grid, block, 0, s, p);
+        }
+    } else if (a->precision == PWV_PREC_F32) {
+        if (pl.unit_mode == 2) hipLaunchKernelGGL((stack_persist_kernel<true, 2, false>), grid, block, 0, s, p);
+        else hipLaunchKernelGGL((stack_persist_kernel<true, 0, false>), grid, block, 0, s, p);
     } else {
-        if (pl.unit_mode == 2) hipLaunchKernelGGL((stack_persist_kernel<false, 2>), grid, block, 0, s, p);
-        else hipLaunchKernelGGL((stack_persist_kernel<false, 0>), grid, block, 0, s, p);
+        if (pl.unit_mode == 2) hipLaunchKernelGGL((stack_persist_kernel<false, 2, false>), grid, block, 0, s, p);
+        else hipLaunchKernelGGL((stack_persist_kernel<false, 0, false>), grid, block, 0, s, p);
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return set_error(PWV_EHIP, "persistent stack kernel launch failed: %s", hipGetErrorString(e));
+    return PWV_OK;
+}
+
+int pwv_varlen_unit_map(const int* cu_rows, const int* cu_frames, int n_utt, int units, int* out, pwv_stream_t stream) {
+    PWV_CHECK_ARG(cu_rows && out, "pwv_varlen_unit_map: NULL argument");
+    PWV_CHECK_ARG(n_utt >= 1 && units >= 1, "pwv_varlen_unit_map: n_utt = %d, units = %d", n_utt, units);
+    PWV_CHECK_ARG(((uintptr_t)out & 15) == 0, "pwv_varlen_unit_map: out must be 16-byte aligned");
+    hipLaunchKernelGGL(varlen_unit_map_kernel, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, (hipStream_t)stream, cu_rows, cu_frames, n_utt, units, out);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return set_error(PWV_EHIP, "pwv_varlen_unit_map launch failed: %s", hipGetErrorString(e));
     return PWV_OK;
 }
 

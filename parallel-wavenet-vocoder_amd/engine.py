@@ -782,12 +782,13 @@ def _layer_args(net0, plans, projs, row_stride: int, cond_geom, bufs, j: int, sr
     return la
 
 
-def _run_stack_persist(path: _Path, nets, plans, projs, bufs, outs, x, x_limit, row_stride, cond_geom, affine=None):
+def _run_stack_persist(path: _Path, nets, plans, projs, bufs, outs, x, x_limit, row_stride, cond_geom, affine=None, geom=None):
     """Layers 0 .. L-2 as the persistent launches of `path` (layer 0 a launch of its own when it cannot rebuild the causal layer
     itself), with layer L-1 + the head behind them -- and, given `affine` = (x, out), the flow's affine out = x*s + b -- INSIDE the
     last launch where `path.tail` (otherwise one more launch for them); all nets of the flow in every launch, all on the current
     stream.  `bufs[g]` holds THREE tile32 buffers: the persistent launch rotates through them (include/pwv_hip.h,
-    pwv_persist_args.x_ring).  Returns True when the affine was evaluated by the launch."""
+    pwv_persist_args.x_ring).  With `geom` (a VarlenGeometry; x is then its [1, R, 1]) every launch carries the packed batch's
+    fields.  Returns True when the affine was evaluated by the launch."""
     lib, s = _lib.lib(), _stream()
     G, L, prec = len(nets), plans[0].n_layers, plans[0].precision
     net0 = nets[0]
@@ -809,6 +810,8 @@ def _run_stack_persist(path: _Path, nets, plans, projs, bufs, outs, x, x_limit, 
         pa.ring_stride, pa.proj_row_stride = bufs[0][0].numel(), row_stride
         if j0 == 0:
             _set_x_first(pa, plans, x, x_limit)
+        if geom is not None:
+            geom.set_args(pa)
         # one zero-initialised workspace per (device, stream), kept: a launch leaves it clean, so none needs a zeroing kernel
         wkey = (bufs[0][0].device, torch.cuda.current_stream().cuda_stream)
         ws = _persist_ws.get(wkey)
@@ -988,8 +991,182 @@ def run_flow(nets: Sequence, x: torch.Tensor, cond, precision: Optional[str] = N
     return iaf_affine_op(x, flat, flat[1:], 2)
 
 
-def _run_nets(nets: Sequence, x: torch.Tensor, cond, precision: Optional[str], max_workgroups: int, affine_out: Optional[torch.Tensor]):
-    """run_nets / run_flow: ([one [N, T, Q] tensor per net], whether `affine_out` = x*s + b was written by the launches)."""
+# ---- packed ("varlen") batches: utterances of different lengths in one forward (include/pwv_hip.h, pwv_persist_args.cu_rows) ------------
+VARLEN_PADDED = 0        # flows of packed batches that took the padded fallback (tests / tools read it)
+
+
+class VarlenGeometry:
+    """The layout of a packed batch: utterance i has lengths[i] samples, rows cu_rows[i] .. cu_rows[i+1]-1 of
+    every [R, C] tensor, and t_mel_i = lengths[i] / hop + 1 condition frames, rows cu_frames[i] .. of every [F, C] tensor.  Sample t
+    of utterance i is conditioned on frame cu_frames[i] + (t + hop/2) // hop and looks back at zeros for t < d.  Holds the host
+    prefix sums (the launches are sized on the host), their device copies and, made on first use, the per-unit records of the
+    persistent launches and the index maps of the padded fallback."""
+
+    def __init__(self, lengths: Sequence[int], hop: int, device):
+        self.lengths = [int(v) for v in lengths]
+        self.hop = int(hop)
+        if not self.lengths:
+            raise ValueError('a packed batch needs at least one utterance')
+        for v in self.lengths:
+            if v <= 0 or v % self.hop:
+                raise ValueError('utterance lengths must be positive multiples of hop_length (%d), got %d' % (self.hop, v))
+        self.frames = [v // self.hop + 1 for v in self.lengths]
+        self.cu_rows_host, self.cu_frames_host = [0], [0]
+        for v, f in zip(self.lengths, self.frames):
+            self.cu_rows_host.append(self.cu_rows_host[-1] + v)
+            self.cu_frames_host.append(self.cu_frames_host[-1] + f)
+        self.n, self.rows, self.total_frames = len(self.lengths), self.cu_rows_host[-1], self.cu_frames_host[-1]
+        self.max_len, self.max_frames = max(self.lengths), max(self.frames)
+        self.device = device
+        both = self._upload([self.cu_rows_host, self.cu_frames_host], torch.int32)
+        self.cu_rows, self.cu_frames = both[0], both[1]
+        self._unit_map = None
+        self._pad_rows = self._pad_frames = None
+        self._cond_cache = None
+
+    def _upload(self, table, dtype) -> torch.Tensor:
+        """A small host table on the device WITHOUT a synchronisation: a copy from pageable memory makes the host wait until the stream
+        has drained (the previous forward), which leaves the GPU idle while this forward's launches are enqueued.  Staged in pinned
+        memory instead (torch keeps the staging buffer alive until the copy has run)."""
+        t = torch.tensor(table, dtype=dtype)
+        if torch.device(self.device).type != 'cuda':
+            return t
+        return t.pin_memory().to(self.device, non_blocking=True)
+
+    def persistent_ok(self) -> bool:
+        """Every utterance long enough for the persistent launch's packed form (a unit spans at most two utterances)."""
+        return min(self.lengths) >= _lib.VARLEN_MIN_ROWS
+
+    def unit_map(self) -> torch.Tensor:
+        if self._unit_map is None:
+            units = (self.rows + 31) // 32
+            m = torch.empty((units * _lib.VARLEN_REC_INTS,), dtype=torch.int32, device=self.device)
+            check(_lib.lib().pwv_varlen_unit_map(_ptr(self.cu_rows), _ptr(self.cu_frames), self.n, units, _ptr(m), _stream()),
+                  'pwv_varlen_unit_map')
+            self._unit_map = m
+        return self._unit_map
+
+    def set_args(self, pa) -> None:
+        """The packed-batch fields of one pwv_persist_args (the plan was made on N = 1, T = R: the same rows and units)."""
+        pa.N, pa.T = self.n, 0
+        pa.cu_rows, pa.cu_frames = _ptr(self.cu_rows), _ptr(self.cu_frames)
+        pa.unit_map, pa.varlen_rows = _ptr(self.unit_map()), self.rows
+
+    # -- the padded fallback: [R, C] <-> zero-padded [N, max_len, C] (rows past an utterance's end are zero, and by causality they
+    #    influence nothing before them: the padded batch computes every real row exactly as the packed one)
+    def _index(self, cu, counts, stride):
+        """The padded position i * stride + t of packed row cu[i] + t, for every row, made on the device: row r of utterance i moves
+        by i * stride - cu[i], so the map is arange(size) plus that shift repeated counts[i] times -- per utterance, not per row, on
+        the host (one copy of 2N ints, no synchronisation)."""
+        per_utt = self._upload([counts, [i * stride - c for i, c in enumerate(cu[:-1])]], torch.int64)
+        size = cu[-1]
+        return torch.arange(size, dtype=torch.int64, device=self.device) + torch.repeat_interleave(per_utt[1], per_utt[0], output_size=size)
+
+    def pad_rows(self, x: torch.Tensor) -> torch.Tensor:
+        if self._pad_rows is None:
+            self._pad_rows = self._index(self.cu_rows_host, self.lengths, self.max_len)
+        c = x.shape[-1]
+        out = torch.zeros((self.n * self.max_len, c), dtype=x.dtype, device=x.device)
+        out.index_copy_(0, self._pad_rows, x.reshape(self.rows, c))
+        return out.reshape(self.n, self.max_len, c)
+
+    def unpad_rows(self, y: torch.Tensor) -> torch.Tensor:
+        c = y.shape[-1]
+        return y.reshape(self.n * self.max_len, c).index_select(0, self._pad_rows)
+
+    def pad_frames(self, f: torch.Tensor) -> torch.Tensor:
+        if self._pad_frames is None:
+            self._pad_frames = self._index(self.cu_frames_host, self.frames, self.max_frames)
+        c = f.shape[-1]
+        out = torch.zeros((self.n * self.max_frames, c), dtype=f.dtype, device=f.device)
+        out.index_copy_(0, self._pad_frames, f.reshape(self.total_frames, c))
+        return out.reshape(self.n, self.max_frames, c)
+
+    def pad_condition(self, cond):
+        """The packed condition (a RepeatedCondition over [1, F, C] frames with its projection bank, a per-sample [1, R, C] tensor, or
+        None) in the padded batch's form; made once per condition object (every flow of a forward shares it)."""
+        if cond is None:
+            return None
+        hit = self._cond_cache
+        if hit is not None and hit[0]() is cond:
+            return hit[1]
+        if isinstance(cond, RepeatedCondition):
+            padded = RepeatedCondition(self.pad_frames(cond.frames), cond.hop, cond.offset, self.max_len)
+            bank = getattr(cond, 'proj_bank', None)
+            if bank is not None:
+                # the bank's column blocks are views of one [F, cols] GEMM output: pad that once, keep the column offsets
+                base = next(iter(bank.values()))
+                full = base.as_strided((self.total_frames, base.stride(0)), (base.stride(0), 1), 0)
+                fp = self.pad_frames(full).reshape(self.n * self.max_frames, base.stride(0))
+                padded.proj_bank = {k: fp[:, v.storage_offset() - full.storage_offset():][:, :v.shape[1]] for k, v in bank.items()}
+        else:
+            padded = self.pad_rows(cond)
+        self._cond_cache = (weakref.ref(cond), padded)
+        return padded
+
+
+def varlen_fallback_reason(nets, cond, geom: VarlenGeometry, precision: Optional[str] = None) -> Optional[str]:
+    """Why a flow (its nets) of a packed batch takes the padded fallback -- or None: the persistent launches of the packed form, where
+    the library plans the R rows persistently with layer 0 and the tail inside the launches (what a uniform batch of R rows would take)."""
+    net0 = nets[0]
+    if not geom.persistent_ok():
+        return 'an utterance shorter than %d samples' % _lib.VARLEN_MIN_ROWS
+    if PERSIST is False:
+        return 'PWV_PERSIST=0'
+    if persist_suspended():
+        return 'persistent launches suspended after a give-up'
+    if PERSIST == 'auto' and geom.rows > PERSIST_AUTO_MAX_ROWS:
+        return 'more than PERSIST_AUTO_MAX_ROWS rows'
+    if cond is not None and not isinstance(cond, RepeatedCondition):
+        return 'per-sample conditioning'
+    if net0.use_skip_connection:
+        return 'skip accumulation'
+    if (precision or net0.precision or DEFAULT_PRECISION) == 'f16':
+        return "precision 'f16'"
+    if not (all(n.fused_supported(cond) for n in nets) and all(_same_structure(net0, n) for n in nets)
+            and all(n.precision == net0.precision for n in nets) and net0.in_channels == 1
+            and ((len(nets) == 2 and net0.out_channels == 1) or (len(nets) == 1 and net0.out_channels == 2))):
+        return 'the flow has no fused form'
+    return None
+
+
+def run_flow_varlen(flow, x: torch.Tensor, cond, geom: VarlenGeometry, precision: Optional[str] = None) -> torch.Tensor:
+    """One IAF flow (LinearIAFLayer / SharedIAFLayer) over a packed batch: x [R, 1] -> [R, 1], `cond` over the packed frames [1, F, C]
+    (length R) or None.  The path is chosen once: the persistent launches of the packed form (pwv_persist_args.cu_rows) wherever a
+    uniform batch of R rows would run the flow as persistent launches with layer 0 and the tail inside them; otherwise
+    (varlen_fallback_reason) the PADDED fallback: the flow's ordinary path on the zero-padded [N, max_len, 1] batch, gathered back.
+    Both give the same bits: every stage of such a flow is causal and row-local in the batch, so the zero rows behind an utterance
+    change nothing in front of them.  Instance normalisation ('in') is not row-local -- its statistics span the time axis, padding
+    included -- so nets that use it are refused here (IAFVocoder.generate_varlen runs them utterance by utterance).  Only enqueues,
+    like run_flow."""
+    global VARLEN_PADDED
+    nets = list(flow.nets())
+    if any(getattr(n, 'normalize', None) == 'in' for n in nets):
+        raise _lib.PwvError("run_flow_varlen: nets with instance normalisation ('in') have no packed or padded form (its statistics "
+                            "span the time axis); run the utterances one by one")
+    x = _require_cuda_f32(x, 'input')
+    if x.dim() != 2 or tuple(x.shape) != (geom.rows, 1):
+        raise ValueError('input must be the packed batch [%d, 1], got %s' % (geom.rows, tuple(x.shape)))
+    if varlen_fallback_reason(nets, cond, geom, precision) is None:
+        x3 = x.reshape(1, geom.rows, 1)
+        out = torch.empty_like(x3)
+        res = _run_nets(nets, x3, cond, precision or nets[0].precision, 0, out, geom)
+        if res is not None:
+            outs, done = res
+            if not done:
+                out = (iaf_affine_op(x3, outs[0], outs[1], 1) if len(outs) == 2
+                       else iaf_affine_op(x3, outs[0].reshape(-1), outs[0].reshape(-1)[1:], 2))
+            return out.reshape(geom.rows, 1)
+    VARLEN_PADDED += 1
+    y = flow(geom.pad_rows(x), geom.pad_condition(cond))        # (nested in the caller's verified_call: only enqueues)
+    return geom.unpad_rows(y)
+
+
+def _run_nets(nets: Sequence, x: torch.Tensor, cond, precision: Optional[str], max_workgroups: int, affine_out: Optional[torch.Tensor],
+              geom=None):
+    """run_nets / run_flow: ([one [N, T, Q] tensor per net], whether `affine_out` = x*s + b was written by the launches).
+    With `geom` (run_flow_varlen: x = the packed batch as [1, R, 1]) only the persistent path with layer 0 and the tail inside its
+    launches is taken; where that path is not the one a uniform batch of R rows would take, nothing is enqueued and None returned."""
     prec = PRECISIONS[precision or DEFAULT_PRECISION]
     x = _require_cuda_f32(x, 'input_batch')
     if x.dim() != 3:
@@ -1014,7 +1191,7 @@ def _run_nets(nets: Sequence, x: torch.Tensor, cond, precision: Optional[str], m
             _range_warned.add(key)
             import warnings
             warnings.warn("pwv: weights of %s exceed the range of the split-fp16 arithmetic; using precision 'f32' for it" % (key,))
-        return _run_nets(nets, x, cond, 'f32', max_workgroups, affine_out)
+        return _run_nets(nets, x, cond, 'f32', max_workgroups, affine_out, geom)
     x_limit = min(p.x_limit for p in plans)
     if prec == _lib.PREC_F16X3:
         _log_range('flow_input', x, x_limit, [p.range_bounds for p in plans])
@@ -1023,6 +1200,8 @@ def _run_nets(nets: Sequence, x: torch.Tensor, cond, precision: Optional[str], m
     if cond_t is not None:
         cond_t = _cond_operand(cond_t, prec)
     path = _choose_path(net0, plans, mode, n, t, max_workgroups, cond_geom)
+    if geom is not None and not (path.persist and path.tail and path.first_fused):
+        return None         # (the per-layer kernels and the causal-layer launch have no packed form)
     side = _net_streams(x.device) if path.two else None
     projs = _projections(cond, mode, plans, precision, side)
     row_stride = projs[0].stride(0)      # (all nets' columns where project_all's one GEMM made them, else 128 * L)
@@ -1030,7 +1209,7 @@ def _run_nets(nets: Sequence, x: torch.Tensor, cond, precision: Optional[str], m
     outs = [torch.empty((n, t, net0.out_channels), dtype=torch.float32, device=x.device) for _ in nets]
     if path.persist:
         aff = (x, affine_out) if (affine_out is not None and qin == 1) else None
-        return outs, _run_stack_persist(path, nets, plans, projs, bufs, outs, x, x_limit, row_stride, cond_geom, aff)
+        return outs, _run_stack_persist(path, nets, plans, projs, bufs, outs, x, x_limit, row_stride, cond_geom, aff, geom)
     _run_stack_layers(path, nets, plans, projs, bufs, outs, x, x_limit, cond_t, row_stride, cond_geom, max_workgroups, side)
     return outs, False
 

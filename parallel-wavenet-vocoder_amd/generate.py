@@ -109,11 +109,43 @@ def forward_over_ranks(mel, batch_size, length, device, make_model, noise_window
                                        mel, n_mels, length, hop, halo, device, group=group)
 
 
-def generate(case='default', ckpt=None, debug=False):
+def _load_mels_varlen(data_path, batch_size, device):
+    """--varlen: one [t_mel_i, n_mels] mel per input at the input's OWN length -- a .npy mel as stored (at least 2 frames), a wav
+    trimmed (data_load.py:42-44) and cut down to a multiple of hop_length, its mel computed on the device.  'synthetic' has no lengths
+    of its own: every utterance is generate.length long."""
+    hop = hp.signal.hop_length
+    if data_path == 'synthetic':
+        return list(_load_mels(data_path, batch_size, hp.generate.length, device)[1].unbind(0))
+    files = sorted(glob.glob(data_path))
+    if not files:
+        raise FileNotFoundError('no input files match data_path %r (use data_path: synthetic for seeded noise mel)' % data_path)
+    split = int(len(files) * hp.train.dataset_ratio)
+    files = (files[split:] or files)[:batch_size]
+    mels = []
+    for f in files:
+        if f.endswith('.npy'):
+            m = np.load(f).astype(np.float32)
+            if m.ndim != 2 or m.shape[0] < 2:
+                raise ValueError('%s: a mel needs at least 2 frames, got shape %s' % (f, m.shape))
+            mels.append(torch.from_numpy(m).to(device))
+        else:
+            from .audio_frontend import read_wav, trim_wav, wav_to_mel_device
+            wav = trim_wav(read_wav(f, hp.signal.sr))
+            wav = wav[:len(wav) // hop * hop].astype(np.float32)
+            if len(wav) == 0:
+                raise ValueError('%s: shorter than one hop (%d samples) after trimming' % (f, hop))
+            mels.append(wav_to_mel_device(torch.from_numpy(wav[None]).to(device))[0])
+    print('dataset size is {}'.format(len(mels)))
+    return mels
+
+
+def generate(case='default', ckpt=None, debug=False, varlen=False):
     '''
     :param case: experiment case name
     :param ckpt: checkpoint to load model
     :param debug: print per-stage timing (the reference hooks tfdbg here).
+    :param varlen: vocode every input at its own length in ONE packed forward (IAFVocoder.generate_varlen) instead of every
+        utterance at hp.generate.length; writes pred_i.wav at each length.
     '''
     hp.set_hparam_yaml(case)
     if not torch.cuda.is_available():
@@ -127,10 +159,16 @@ def generate(case='default', ckpt=None, debug=False):
     batch_size, length = hp.generate.batch_size, hp.generate.length
     world, rank = int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('RANK', '0'))
     if world > 1:
+        if varlen:
+            raise ValueError('--varlen runs on one GPU (a packed batch is not sharded over ranks)')
         # one process per GPU (torchrun): utterances -- or, for a batch smaller than the world, time slices -- shard over
         # the ranks; rank 0 reads the inputs and writes the outputs
         return _generate_over_ranks(store, batch_size, length, device, logdir, ckpt, debug)
-    gt_wav, melspec = _load_mels(hp.data_path, batch_size, length, device)
+    if varlen:
+        gt_wav, melspec = None, _load_mels_varlen(hp.data_path, batch_size, device)
+        batch_size, length = 1, sum(int(m.shape[0] - 1) * hp.signal.hop_length for m in melspec)     # (the timing line: all samples)
+    else:
+        gt_wav, melspec = _load_mels(hp.data_path, batch_size, length, device)
 
     model = IAFVocoder(batch_size=batch_size, length=length, store=store)
 
@@ -149,7 +187,7 @@ def generate(case='default', ckpt=None, debug=False):
     # launches, a forward that left the range of the split-fp16 arithmetic in exact fp32 -- on the same noise
     # (engine.verified_call); what comes back is what the reference's fp32 sess.run would have produced, or an exception.
     # verify=True is EXPLICIT: it outranks PWV_ASYNC=1 (whose default is enqueue-only) -- nothing unverified is written to disk
-    pred = model(gt_wav, melspec, is_training=False, verify=True)
+    pred = model.generate_varlen(melspec, verify=True) if varlen else model(gt_wav, melspec, is_training=False, verify=True)
     if ckpt:
         # tf.train.Saver.restore fails on a variable the checkpoint lacks (generate.py:59-63); here variables are
         # created lazily by the forward, so the coverage check comes after it
@@ -169,6 +207,11 @@ def generate(case='default', ckpt=None, debug=False):
         torch.cuda.synchronize()
         ms = e0.elapsed_time(e1)
         print('forward: %.2f ms, %.3g samples/s (first call includes weight packing)' % (ms, batch_size * length / ms * 1e3))
+    if varlen:
+        pred_wav = [p.cpu().numpy() for p in pred]
+        _write_outputs_varlen(pred_wav, logdir)
+        print('Done.')
+        return pred_wav
     pred_wav = pred.cpu().numpy()
     _write_outputs(pred_wav, logdir)
     print('Done.')
@@ -183,6 +226,19 @@ def _write_outputs(pred_wav, logdir):
             wavfile.write(os.path.join(logdir, 'pred_%d.wav' % i), hp.signal.sr, np.clip(pred_wav[i, :, 0], -1, 1))
         np.save(os.path.join(logdir, 'pred_wav.npy'), pred_wav)
         print('wrote %d waveform(s) to %s' % (pred_wav.shape[0], logdir))
+    except OSError as e:
+        print('could not write outputs to %s: %s' % (logdir, e))
+
+
+def _write_outputs_varlen(pred_wavs, logdir):
+    """--varlen: pred_i.wav at utterance i's own length, and every waveform in pred_wav_varlen.npz (as pred_i)."""
+    try:
+        os.makedirs(logdir, exist_ok=True)
+        from scipy.io import wavfile
+        for i, w in enumerate(pred_wavs):
+            wavfile.write(os.path.join(logdir, 'pred_%d.wav' % i), hp.signal.sr, np.clip(w[:, 0], -1, 1))
+        np.savez(os.path.join(logdir, 'pred_wav_varlen.npz'), **{'pred_%d' % i: w for i, w in enumerate(pred_wavs)})
+        print('wrote %d waveform(s) of %s samples to %s' % (len(pred_wavs), [len(w) for w in pred_wavs], logdir))
     except OSError as e:
         print('could not write outputs to %s: %s' % (logdir, e))
 

@@ -10,12 +10,28 @@ from __future__ import annotations
 from typing import Optional
 
 import numpy as np
+import torch
 
 from . import engine
 from .engine import RepeatedCondition
 from .hparam import hparam as hp
 from .modules import LinearIAFLayer, SharedIAFLayer, WaveNet, normalize
 from .variables import VariableStore, get_default_store, get_variable, variable_scope
+
+
+def torch_cat(parts):
+    return parts[0] if len(parts) == 1 else torch.cat(parts)
+
+
+class VarlenOutput(list):
+    """What IAFVocoder.generate_varlen returns: the [len_i, 1] results of the utterances (views), with the packed [R, 1] result as
+    `.packed` and the batch's layout (engine.VarlenGeometry: lengths, cu_rows, cu_frames) as `.geometry`."""
+
+    def __init__(self, packed, geometry):
+        r = geometry.cu_rows_host
+        super().__init__(packed[a:b] for a, b in zip(r, r[1:]))
+        self.packed = packed
+        self.geometry = geometry
 
 
 class IAFVocoder(object):
@@ -74,8 +90,9 @@ class IAFVocoder(object):
                 raise ValueError('z must be [%d, %d, 1], got %s' % (n, self.length, tuple(noise.shape)))
         return engine.verified_call(lambda prec: self._forward(store, melspec, noise, is_training, name, prec or self.precision), verify)
 
-    def _forward(self, store, melspec, input, is_training, name, precision):
-        """models.py:23-78: condition, then the flows; only enqueues."""
+    def _forward(self, store, melspec, input, is_training, name, precision, length=None, geom=None):
+        """models.py:23-78: condition, then the flows; only enqueues.  `length` overrides the constructor's (the padded form of a
+        packed batch); with `geom` (an engine.VarlenGeometry) `melspec` is the packed [1, F, n_mels] and `input` the packed [R, 1]."""
         shared = bool(hp.model.get('shared_nets', False))
         with variable_scope(name):
             flows = []
@@ -107,7 +124,8 @@ class IAFVocoder(object):
             with variable_scope('cond'):
                 # (the flows are set up first -- that opens no variable scope of theirs, models.py:26-29 stays ahead of :36-67 in the
                 # variable order -- so that the one-launch prologue can project for all of them)
-                condition = self._condition(melspec, is_training, strides=[4, 4, 5], store=store, precision=precision, nets=all_nets)   # (n, t, h)
+                condition = self._condition(melspec, is_training, strides=[4, 4, 5], store=store, precision=precision, nets=all_nets,
+                                            length=length)   # (n, t, h)
                 if hp.model.normalize_cond and condition is not None:
                     if isinstance(condition, RepeatedCondition):
                         condition = condition.materialize()
@@ -116,10 +134,79 @@ class IAFVocoder(object):
             # the frame-rate projections of every net depend on the mel only: one GEMM for all flows, ahead of the first
             engine.project_all(all_nets, condition, precision=precision)
             for i, iaf in enumerate(flows):
-                input = iaf(input, condition)  # (n, t, h)
+                if geom is not None:
+                    input = engine.run_flow_varlen(iaf, input, condition, geom, precision)      # (R, 1)
+                else:
+                    input = iaf(input, condition)  # (n, t, h)
                 # normalization (identity at the default hparams), models.py:70
                 input = normalize(input, is_training, hp.model.normalize, name='normalize{}'.format(i), store=store)
         return input
+
+    # -- mixed-length batches ("Packed batches") -----------------------------------------------------
+    def generate_varlen(self, melspecs, z=None, verify=None):
+        """One forward over utterances of DIFFERENT lengths, without padding them to the longest.  `melspecs`: a list of
+        [t_mel_i, n_mels] float32 tensors on the GPU (t_mel_i >= 2); utterance i yields len_i = (t_mel_i - 1) * hop samples.
+        Returns a list (VarlenOutput) of [len_i, 1] tensors, views of ONE packed [R, 1] result (R = sum of len_i), which is
+        `.packed` of the list.  ``z`` (optional): the noise, packed [R, 1] or a list of [len_i, 1]; by default one draw of R
+        counters that continues this model's stream (row r of the packed batch is counter noise_offset + r).  The constructor's
+        `batch_size` and `length` are not used here.  ``verify`` as for __call__."""
+        if not isinstance(melspecs, (list, tuple)) or not melspecs:
+            raise ValueError('melspecs must be a non-empty list of [t_mel, n_mels] tensors')
+        for i, m in enumerate(melspecs):
+            if not hasattr(m, 'dim') or m.dim() != 2 or m.shape[1] != hp.signal.n_mels or m.shape[0] < 2:
+                raise ValueError('melspecs[%d] must be [t_mel >= 2, %d], got %s' % (i, hp.signal.n_mels, tuple(getattr(m, 'shape', ()))))
+        if isinstance(z, (list, tuple)):      # (each piece against its own utterance: a split that only adds up to R would misassign)
+            if len(z) != len(melspecs):
+                raise ValueError('z holds %d utterances, melspecs %d' % (len(z), len(melspecs)))
+            for i, (v, m) in enumerate(zip(z, melspecs)):
+                want = ((m.shape[0] - 1) * hp.signal.hop_length, 1)
+                if tuple(getattr(v, 'shape', ())) != want:
+                    raise ValueError('z[%d] must be %s (utterance %d), got %s' % (i, want, i, tuple(getattr(v, 'shape', ()))))
+            z = torch_cat([engine._require_cuda_f32(v, 'z[%d]' % i) for i, v in enumerate(z)])
+        mels = [engine._require_cuda_f32(m, 'melspecs[%d]' % i) for i, m in enumerate(melspecs)]
+        cu_frames = [0]
+        for m in mels:
+            cu_frames.append(cu_frames[-1] + m.shape[0])
+        return self.forward_packed(torch_cat(mels), cu_frames, z=z, verify=verify)
+
+    def forward_packed(self, mel_packed, cu_frames, z=None, verify=None):
+        """generate_varlen on the packed form: `mel_packed` [F, n_mels] holds the utterances' frames one after the other and
+        `cu_frames` (host ints, F = cu_frames[-1]) their prefix sums; returns the VarlenOutput (packed result [R, 1] as `.packed`)."""
+        store = self.store or get_default_store()
+        engine.raise_if_range_flag('an earlier call')
+        engine.raise_if_persist_failed()
+        mel = engine._require_cuda_f32(mel_packed, 'mel_packed')
+        cu = [int(v) for v in (cu_frames.tolist() if hasattr(cu_frames, 'tolist') else cu_frames)]
+        if len(cu) < 2 or cu[0] != 0 or any(b - a < 2 for a, b in zip(cu, cu[1:])):
+            raise ValueError('cu_frames must start at 0 and give every utterance at least 2 frames, got %s' % (cu,))
+        if mel.dim() != 2 or mel.shape[1] != hp.signal.n_mels or mel.shape[0] != cu[-1]:
+            raise ValueError('mel_packed must be [%d, %d], got %s' % (cu[-1], hp.signal.n_mels, tuple(mel.shape)))
+        hop = hp.signal.hop_length
+        geom = engine.VarlenGeometry([(b - a - 1) * hop for a, b in zip(cu, cu[1:])], hop, mel.device)
+        if z is None:   # one draw of R counters, continuing the stream (a rerun sees the same noise)
+            noise = engine.logistic_noise_op((geom.rows, 1), mel.device, seed=self._seed(), offset=self.noise_offset)
+            self.noise_offset += geom.rows
+        else:
+            noise = engine._require_cuda_f32(z, 'z')
+            if tuple(noise.shape) != (geom.rows, 1):
+                raise ValueError('z must be [%d, 1], got %s' % (geom.rows, tuple(noise.shape)))
+        out = engine.verified_call(lambda prec: self._forward_varlen(store, mel, noise, geom, prec or self.precision), verify)
+        return VarlenOutput(out, geom)
+
+    def _forward_varlen(self, store, mel, noise, geom, precision):
+        """The packed forward: the prologue on the concatenated frames (per frame: nothing changes), then every flow as
+        engine.run_flow_varlen.  Configurations whose stages are not row-local on the packed batch run the model's ordinary forward on
+        the zero-padded batch (a materialised or normalised condition) or utterance by utterance (instance normalisation, whose
+        statistics span the whole time axis)."""
+        m = hp.model
+        if 'in' in (m.get('normalize'), m.get('normalize_cond'), m.get('normalize_wavenet')):
+            outs = [self._forward(store, mel[a:b].unsqueeze(0), noise[r0:r1].unsqueeze(0), False, 'iaf_vocoder', precision, length=r1 - r0)
+                    for a, b, r0, r1 in zip(geom.cu_frames_host, geom.cu_frames_host[1:], geom.cu_rows_host, geom.cu_rows_host[1:])]
+            return torch_cat([o.reshape(-1, 1) for o in outs])
+        if m.cond_upsample_method != 'repeat' or m.normalize_cond:
+            out = self._forward(store, geom.pad_frames(mel), geom.pad_rows(noise), False, 'iaf_vocoder', precision, length=geom.max_len)
+            return geom.unpad_rows(out)
+        return self._forward(store, mel.unsqueeze(0), noise, False, 'iaf_vocoder', precision, length=geom.rows, geom=geom)
 
     def verify(self):
         """For callers of the enqueue-only form (verify=False / PWV_ASYNC=1): wait for the enqueued forwards and raise
@@ -143,16 +230,17 @@ class IAFVocoder(object):
         return self._mel_limit_val
 
     # -- condition upsampling (models.py:105-136) ----------------------------------------------------
-    def _condition(self, melspec, is_training, strides, store, precision=None, nets=None):
+    def _condition(self, melspec, is_training, strides, store, precision=None, nets=None, length=None):
         """The condition in the form the kernels want: a lazy RepeatedCondition for 'repeat'
         (projected at frame rate inside the nets), a materialised [N, T, C] tensor for
-        'transposed_conv', None otherwise."""
+        'transposed_conv', None otherwise.  `length` overrides the constructor's."""
         precision = precision or self.precision
+        n_samples = self.length if length is None else length
         hop = hp.signal.hop_length
         assert (np.prod(np.array(strides)) == hop)                              # models.py:106
-        if self.length % hop != 0:
+        if n_samples % hop != 0:
             raise ValueError('length (%d) must be a multiple of hop_length (%d): the crop at models.py:124,133 '
-                             'yields (t_mel-1)*hop samples' % (self.length, hop))
+                             'yields (t_mel-1)*hop samples' % (n_samples, hop))
         method = hp.model.cond_upsample_method
         n, t_mel, n_mels = melspec.shape
         C = hp.model.condition_channels
@@ -187,7 +275,7 @@ class IAFVocoder(object):
             split = (precision or engine.DEFAULT_PRECISION) == 'f16x3'
             if nets and not hp.model.normalize_cond:
                 # range check + dense / relu + the projections of every net of the forward: ONE launch (bit-identical to the three)
-                fused = engine.repeat_condition_with_projections(nets, melspec, w[0], hop, self.length, precision,
+                fused = engine.repeat_condition_with_projections(nets, melspec, w[0], hop, n_samples, precision,
                                                                  self._mel_limit([w[0]], store) if split else None)
                 if fused is not None:
                     return fused
@@ -195,7 +283,7 @@ class IAFVocoder(object):
                 engine.range_check_op(melspec, self._mel_limit([w[0]], store))
             frames = engine.linear_op(melspec.reshape(n * t_mel, n_mels), w[0], None, relu=True,
                                       precision=precision)                              # models.py:128-130
-            return RepeatedCondition(frames.reshape(n, t_mel, C), hop, hop // 2, self.length)      # models.py:131-133
+            return RepeatedCondition(frames.reshape(n, t_mel, C), hop, hop // 2, n_samples)      # models.py:131-133
         return None
 
     def _upsample_cond(self, melspec, is_training, strides):
