@@ -118,6 +118,15 @@ int pwv_logistic_noise_f32(float* z, int64_t n, uint64_t seed, uint64_t offset, 
  * ONE launch per `state` in flight at a time: two launches that share a state must be ordered (one stream, or one graph replayed on
  * one stream) -- overlapping ones would share the ticket. */
 int pwv_logistic_noise_stream_f32(float* z, int64_t n, uint64_t* state, pwv_stream_t stream);
+/* The sampler of a PACKED batch (n utterances, rows = cu_rows[n] rows) with one counter stream per utterance, read from DEVICE memory:
+ *   cu_rows  device int32 [n+1], cu_rows[0] = 0, ascending, cu_rows[n] = rows (the prefix sums of pwv_persist_args.cu_rows)
+ *   streams  device uint64 [n][2] = {seed_i, offset_i}
+ * Row r of utterance i (cu_rows[i] <= r < cu_rows[i+1]) gets the sample of counter offset_i + (r - cu_rows[i]) under seed_i, so
+ * z[cu_rows[i] .. cu_rows[i+1]) is BIT-IDENTICAL to what pwv_logistic_noise_f32(z_i, len_i, seed_i, offset_i) writes: an utterance's noise
+ * depends on its own stream only, not on its companions or its position.  Nothing is read on the host, so a captured launch replays
+ * with whatever tables the caller wrote before the replay.  Any n (binary search per row); rows <= 2^31 - 1; vector stores only. */
+int pwv_logistic_noise_packed_f32(float* z, const int32_t* cu_rows, const uint64_t* streams, int32_t n, int64_t rows,
+                                  pwv_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * Range guard of the split-fp16 arithmetic (PWV_PREC_F16X3).  The reference computes in fp32 (models.py:81-82);

@@ -515,6 +515,25 @@ __global__ void logistic_noise_stream_kernel(float* __restrict__ z, long long n,
     }
 }
 
+// The sampler of a PACKED batch with one stream per utterance: row r of utterance u (cu_rows[u] <= r < cu_rows[u+1]) is the sample of
+// counter streams[u].offset + (r - cu_rows[u]) under streams[u].seed -- utterance u's slice is what pwv_logistic_noise_f32(seed_u,
+// offset_u) draws for it alone.  The tables are read from device memory, so a captured launch replays with whatever the caller wrote
+// there.  Each thread finds its utterance by binary search over cu_rows (a block's 256 rows span few utterances: the probes of its
+// threads hit the same lines); the search stays inside [0, n) whatever the table holds.
+__global__ __launch_bounds__(256) void logistic_noise_packed_kernel(float* __restrict__ z, const int* __restrict__ cu_rows,
+                                                                    const unsigned long long* __restrict__ streams, int n, long long rows) {
+    const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= rows) return;
+    int lo = 0, hi = n - 1;              // the last utterance that starts at or before r
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if ((long long)cu_rows[mid] <= r) lo = mid;
+        else hi = mid - 1;
+    }
+    const unsigned long long seed = streams[2 * lo], offset = streams[2 * lo + 1];
+    z[r] = logistic_of_counter(seed, offset + (unsigned long long)(r - (long long)cu_rows[lo]));
+}
+
 // modules.py:59 (x = z*s + b) fused with the next flow's causal layer (modules.py:179-180):
 // h_g[row, c] = sum_k x[t-(W-1-k)] * filt_g[k,0,c], written in the tile32 layout (pwv_layer_common.h).
 // One thread per (block of 32 rows, net, channel quad, row in block): consecutive threads write consecutive 16 B.
@@ -772,6 +791,18 @@ int pwv_logistic_noise_stream_f32(float* z, int64_t n, uint64_t* state, pwv_stre
     if (n == 0) return PWV_OK;
     hipLaunchKernelGGL(logistic_noise_stream_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, z, (long long)n,
                        (unsigned long long*)state);
+    PWV_CHECK_HIP(hipGetLastError());
+    return PWV_OK;
+}
+
+int pwv_logistic_noise_packed_f32(float* z, const int32_t* cu_rows, const uint64_t* streams, int32_t n, int64_t rows,
+                                  pwv_stream_t stream) {
+    PWV_CHECK_ARG(z && cu_rows && streams, "pwv_logistic_noise_packed_f32: NULL pointer");
+    PWV_CHECK_ARG(n >= 1 && rows >= 0 && rows <= 0x7fffffffLL, "pwv_logistic_noise_packed_f32: bad n=%d / rows=%lld (cu_rows is int32)",
+                  (int)n, (long long)rows);
+    if (rows == 0) return PWV_OK;
+    hipLaunchKernelGGL(logistic_noise_packed_kernel, dim3(blocks_for(rows, 256)), dim3(256), 0, (hipStream_t)stream, z,
+                       (const int*)cu_rows, (const unsigned long long*)streams, (int)n, (long long)rows);
     PWV_CHECK_HIP(hipGetLastError());
     return PWV_OK;
 }

@@ -514,6 +514,38 @@ def logistic_noise_stream_op(z: torch.Tensor, state: torch.Tensor) -> torch.Tens
     return z
 
 
+def as_int64_bits(v: int) -> int:
+    """A uint64 (a seed or a counter offset, 0 .. 2**64 - 1) as the int64 with the same bits: how a torch.int64 tensor carries it."""
+    v = int(v) & ((1 << 64) - 1)
+    return v - (1 << 64) if v >> 63 else v
+
+
+def logistic_noise_packed_op(cu_rows: torch.Tensor, streams: torch.Tensor, rows: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[rows, 1] Logistic(0,1) noise of a packed batch with one counter stream per utterance (pwv_logistic_noise_packed_f32): `cu_rows`
+    int32 [n+1] on the GPU (the batch's prefix sums, cu_rows[n] = rows), `streams` int64 [n, 2] on the GPU = {seed_i, offset_i} (uint64
+    bits, as_int64_bits).  Rows cu_rows[i] .. cu_rows[i+1]-1 equal logistic_noise_op((len_i, 1), seed=seed_i, offset=offset_i) bit for bit.
+    The tables are read on the device: a captured launch replays with what they hold then."""
+    for t, what, dt in ((cu_rows, 'cu_rows', torch.int32), (streams, 'streams', torch.int64)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or not t.is_contiguous():
+            raise ValueError('%s must be a contiguous %s tensor' % (what, dt))
+    for t, what in ((cu_rows, 'cu_rows'), (streams, 'streams')):
+        if not t.is_cuda:
+            raise _lib.PwvError('%s must live on the GPU (cuda device); there is no CPU path' % what)
+    n = cu_rows.numel() - 1
+    if cu_rows.dim() != 1 or n < 1 or tuple(streams.shape) != (n, 2):
+        raise ValueError('cu_rows must be [n+1] (n >= 1) and streams [n, 2], got %s and %s' % (tuple(cu_rows.shape), tuple(streams.shape)))
+    rows = int(rows)
+    if not 0 <= rows < (1 << 31):
+        raise ValueError('rows must be in [0, 2**31), got %d' % rows)
+    if streams.device != cu_rows.device:
+        raise ValueError('cu_rows and streams must be on one device')
+    z = out if out is not None else torch.empty((rows, 1), dtype=torch.float32, device=cu_rows.device)
+    if out is not None and (tuple(out.shape) != (rows, 1) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != cu_rows.device):
+        raise ValueError('out must be a contiguous float32 [%d, 1] tensor on %s' % (rows, cu_rows.device))
+    check(_lib.lib().pwv_logistic_noise_packed_f32(_ptr(z), _ptr(cu_rows), _ptr(streams), n, rows, _stream()), 'pwv_logistic_noise_packed_f32')
+    return z
+
+
 def logistic_noise_window(n: int, total_length: int, first_sample: int, window: int, device, seed: int, first_item: int = 0) -> torch.Tensor:
     """[n, window, 1] Logistic(0,1) noise for the samples [first_sample, first_sample + window) of the utterances
     first_item .. first_item + n - 1 of ONE counter-based stream in which utterance i, sample t is counter
@@ -993,6 +1025,7 @@ def run_flow(nets: Sequence, x: torch.Tensor, cond, precision: Optional[str] = N
 
 # ---- packed ("varlen") batches: utterances of different lengths in one forward (include/pwv_hip.h, pwv_persist_args.cu_rows) ------------
 VARLEN_PADDED = 0        # flows of packed batches that took the padded fallback (tests / tools read it)
+VARLEN_PADDED_WHY = None  # ... and why the last of them did (graph.GraphedPackedVocoder refuses with it)
 
 
 class VarlenGeometry:
@@ -1002,7 +1035,11 @@ class VarlenGeometry:
     prefix sums (the launches are sized on the host), their device copies and, made on first use, the per-unit records of the
     persistent launches and the index maps of the padded fallback."""
 
-    def __init__(self, lengths: Sequence[int], hop: int, device):
+    def __init__(self, lengths: Sequence[int], hop: int, device, tables=None):
+        """`tables` (optional): caller-owned device buffers (cu_rows int32 [N+1], cu_frames int32 [N+1], unit map int32
+        [ceil(R/32) * VARLEN_REC_INTS]) that the caller keeps filled; nothing is uploaded, and unit_map() hands out the buffer as it is
+        (the caller rebuilds it, build_unit_map(), ahead of every forward: graph.GraphedPackedVocoder rewrites the tables between
+        replays of one capture)."""
         self.lengths = [int(v) for v in lengths]
         self.hop = int(hop)
         if not self.lengths:
@@ -1018,9 +1055,14 @@ class VarlenGeometry:
         self.n, self.rows, self.total_frames = len(self.lengths), self.cu_rows_host[-1], self.cu_frames_host[-1]
         self.max_len, self.max_frames = max(self.lengths), max(self.frames)
         self.device = device
-        both = self._upload([self.cu_rows_host, self.cu_frames_host], torch.int32)
-        self.cu_rows, self.cu_frames = both[0], both[1]
-        self._unit_map = None
+        if tables is None:
+            both = self._upload([self.cu_rows_host, self.cu_frames_host], torch.int32)
+            self.cu_rows, self.cu_frames = both[0], both[1]
+            self._unit_map = None
+        else:
+            self.cu_rows, self.cu_frames, self._unit_map = tables
+            if self._unit_map.numel() != (self.rows + 31) // 32 * _lib.VARLEN_REC_INTS or self.cu_rows.numel() != self.n + 1:
+                raise ValueError('tables do not match %d utterances of %d rows' % (self.n, self.rows))
         self._pad_rows = self._pad_frames = None
         self._cond_cache = None
 
@@ -1033,6 +1075,10 @@ class VarlenGeometry:
             return t
         return t.pin_memory().to(self.device, non_blocking=True)
 
+    def stream_table(self, streams: Sequence[Tuple[int, int]]) -> torch.Tensor:
+        """The int64 [N, 2] table {seed_i, offset_i} (uint64 bits) of logistic_noise_packed_op on the device, staged like the prefix sums."""
+        return self._upload([[as_int64_bits(a), as_int64_bits(b)] for a, b in streams], torch.int64)
+
     def persistent_ok(self) -> bool:
         """Every utterance long enough for the persistent launch's packed form (a unit spans at most two utterances)."""
         return min(self.lengths) >= _lib.VARLEN_MIN_ROWS
@@ -1040,11 +1086,14 @@ class VarlenGeometry:
     def unit_map(self) -> torch.Tensor:
         if self._unit_map is None:
             units = (self.rows + 31) // 32
-            m = torch.empty((units * _lib.VARLEN_REC_INTS,), dtype=torch.int32, device=self.device)
-            check(_lib.lib().pwv_varlen_unit_map(_ptr(self.cu_rows), _ptr(self.cu_frames), self.n, units, _ptr(m), _stream()),
-                  'pwv_varlen_unit_map')
-            self._unit_map = m
+            self._unit_map = torch.empty((units * _lib.VARLEN_REC_INTS,), dtype=torch.int32, device=self.device)
+            self.build_unit_map()
         return self._unit_map
+
+    def build_unit_map(self) -> None:
+        """Enqueue pwv_varlen_unit_map: the unit records from the device tables, into the unit map's buffer."""
+        check(_lib.lib().pwv_varlen_unit_map(_ptr(self.cu_rows), _ptr(self.cu_frames), self.n, (self.rows + 31) // 32, _ptr(self._unit_map),
+                                             _stream()), 'pwv_varlen_unit_map')
 
     def set_args(self, pa) -> None:
         """The packed-batch fields of one pwv_persist_args (the plan was made on N = 1, T = R: the same rows and units)."""
@@ -1139,7 +1188,7 @@ def run_flow_varlen(flow, x: torch.Tensor, cond, geom: VarlenGeometry, precision
     change nothing in front of them.  Instance normalisation ('in') is not row-local -- its statistics span the time axis, padding
     included -- so nets that use it are refused here (IAFVocoder.generate_varlen runs them utterance by utterance).  Only enqueues,
     like run_flow."""
-    global VARLEN_PADDED
+    global VARLEN_PADDED, VARLEN_PADDED_WHY
     nets = list(flow.nets())
     if any(getattr(n, 'normalize', None) == 'in' for n in nets):
         raise _lib.PwvError("run_flow_varlen: nets with instance normalisation ('in') have no packed or padded form (its statistics "
@@ -1147,7 +1196,8 @@ def run_flow_varlen(flow, x: torch.Tensor, cond, geom: VarlenGeometry, precision
     x = _require_cuda_f32(x, 'input')
     if x.dim() != 2 or tuple(x.shape) != (geom.rows, 1):
         raise ValueError('input must be the packed batch [%d, 1], got %s' % (geom.rows, tuple(x.shape)))
-    if varlen_fallback_reason(nets, cond, geom, precision) is None:
+    why = varlen_fallback_reason(nets, cond, geom, precision)
+    if why is None:
         x3 = x.reshape(1, geom.rows, 1)
         out = torch.empty_like(x3)
         res = _run_nets(nets, x3, cond, precision or nets[0].precision, 0, out, geom)
@@ -1157,7 +1207,9 @@ def run_flow_varlen(flow, x: torch.Tensor, cond, geom: VarlenGeometry, precision
                 out = (iaf_affine_op(x3, outs[0], outs[1], 1) if len(outs) == 2
                        else iaf_affine_op(x3, outs[0].reshape(-1), outs[0].reshape(-1)[1:], 2))
             return out.reshape(geom.rows, 1)
+        why = 'the library plans this stack at %d rows per layer' % geom.rows
     VARLEN_PADDED += 1
+    VARLEN_PADDED_WHY = why
     y = flow(geom.pad_rows(x), geom.pad_condition(cond))        # (nested in the caller's verified_call: only enqueues)
     return geom.unpad_rows(y)
 

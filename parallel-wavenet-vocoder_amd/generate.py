@@ -12,7 +12,7 @@ follow from the platform, not from the math:
     TensorBoard audio summaries, generate.py:71-73);
   * `data_path: 'synthetic'` (bench cases) or a glob of .npy mel files replaces the wav dataset;
     wav input uses the torch STFT front-end in audio_frontend.py.
-CLI (python-fire style, fire itself is not installed):  python -m pwv_amd.generate <case> [--ckpt=..] [--debug]
+CLI (python-fire style, fire itself is not installed):  python -m pwv_amd.generate <case> [--ckpt=..] [--debug] [--varlen [--seed=S]]
 """
 from __future__ import absolute_import, division, print_function
 
@@ -139,14 +139,22 @@ def _load_mels_varlen(data_path, batch_size, device):
     return mels
 
 
-def generate(case='default', ckpt=None, debug=False, varlen=False):
+def generate(case='default', ckpt=None, debug=False, varlen=False, seed=None):
     '''
     :param case: experiment case name
     :param ckpt: checkpoint to load model
     :param debug: print per-stage timing (the reference hooks tfdbg here).
     :param varlen: vocode every input at its own length in ONE packed forward (IAFVocoder.generate_varlen) instead of every
         utterance at hp.generate.length; writes pred_i.wav at each length.
+    :param seed: (with varlen) every utterance draws its noise from stream `seed` at counter 0, so a file's audio depends only on
+        its mel and the seed -- not on the other files of the run or their order.
     '''
+    if seed is not None:
+        if not varlen:
+            raise ValueError('--seed applies to --varlen (one noise stream per utterance)')
+        seed = int(seed)
+        if not 0 <= seed < (1 << 64):
+            raise ValueError('--seed must be in [0, 2**64), got %d' % seed)
     hp.set_hparam_yaml(case)
     if not torch.cuda.is_available():
         raise RuntimeError('generate() needs an MI355X: the HIP path has no CPU fallback')
@@ -187,7 +195,10 @@ def generate(case='default', ckpt=None, debug=False, varlen=False):
     # launches, a forward that left the range of the split-fp16 arithmetic in exact fp32 -- on the same noise
     # (engine.verified_call); what comes back is what the reference's fp32 sess.run would have produced, or an exception.
     # verify=True is EXPLICIT: it outranks PWV_ASYNC=1 (whose default is enqueue-only) -- nothing unverified is written to disk
-    pred = model.generate_varlen(melspec, verify=True) if varlen else model(gt_wav, melspec, is_training=False, verify=True)
+    if varlen:
+        pred = model.generate_varlen(melspec, verify=True, seeds=None if seed is None else [seed] * len(melspec))
+    else:
+        pred = model(gt_wav, melspec, is_training=False, verify=True)
     if ckpt:
         # tf.train.Saver.restore fails on a variable the checkpoint lacks (generate.py:59-63); here variables are
         # created lazily by the forward, so the coverage check comes after it

@@ -12,16 +12,21 @@ graph-private pool handed out during capture.  Shapes are fixed at capture (batc
 are copied into static input tensors before each replay (or written there by the caller: `graphed.mel`), and the noise is
 sampled by a node of the graph whose counter range lives in device memory (pwv_logistic_noise_stream_f32: a sampler with its
 range passed by value would replay the same noise).
+
+GraphedPackedVocoder does the same for packed batches of utterances of different lengths (IAFVocoder.generate_varlen with one noise
+stream per utterance): captured once at a capacity of `slots` utterances and `rows` samples, replayed for any lengths that fit, the
+layout and the streams rewritten in device tables before each replay and the free slots taken by filler utterances.
 """
 from __future__ import annotations
 
 from typing import Optional
 
+import numpy as np
 import torch
 
-from . import engine
+from . import _lib, engine
 from .hparam import hparam as hp
-from .models import IAFVocoder
+from .models import IAFVocoder, VarlenOutput, noise_streams
 
 
 class GraphedVocoder(object):
@@ -131,3 +136,215 @@ class GraphedVocoder(object):
             wrap = lambda v: (int(v) & ((1 << 64) - 1)) - (1 << 64) if (int(v) & (1 << 63)) else int(v) & ((1 << 64) - 1)  # noqa: E731
             self.noise_state.copy_(torch.tensor([wrap(want[0]), wrap(want[1]), 0, want[2]], dtype=torch.int64), non_blocking=False)
             self._noise_mirror = want
+
+
+class GraphedPackedVocoder(object):
+    """The packed forward of IAFVocoder.generate_varlen with one noise stream per utterance (seeds=), captured once at a capacity
+    of `slots` utterances and `rows` samples and replayed for ANY lengths that fit it ("Graph replay of packed
+    batches").  On the packed persistent route no launch argument depends on the individual lengths: the plan is made on N = 1,
+    T = rows, the mel has rows / hop + slots frames, and the layout reaches the kernels only through the device tables cu_rows,
+    cu_frames and the unit map.  So the graph holds the packed sampler (reading {seed_i, offset_i} from `streams`), the unit-map
+    build, the prologue and the packed persistent flows, and a call rewrites the tables in place before the replay.
+
+    A call with n < slots utterances adds slots - n FILLER utterances behind them: the first slots - n - 1 of `filler` rows (one hop,
+    or the smallest multiple of hop of at least _lib.VARLEN_MIN_ROWS), the last one the remaining rows; zero mel, seed
+    FILLER_SEED.  Every utterance's result depends on its own mel and stream only, so the fillers change no bit of the real ones.
+
+    The model must take the packed persistent route on every flow at this capacity: anything else (a flow that would take the padded
+    fallback, engine.varlen_fallback_reason, or that the library plans per layer; utterance-by-utterance instance normalisation;
+    a materialised or normalised condition) is refused at construction with PwvError, since its launches depend on the lengths."""
+
+    FILLER_SEED = 0
+
+    def __init__(self, model: IAFVocoder, slots: int, rows: int, warmup: int = 2, device=None):
+        self.model = model
+        store = model.store
+        if store is None:
+            from .variables import get_default_store
+            store = get_default_store()
+        self.store = store
+        self.device = torch.device(device) if device is not None else store.device
+        if self.device.type != 'cuda':
+            raise _lib.PwvError('GraphedPackedVocoder needs a GPU (cuda device); there is no CPU path')
+        self.hop = hop = int(hp.signal.hop_length)
+        self.filler = hop * -(-max(hop, _lib.VARLEN_MIN_ROWS) // hop)
+        self.slots, self.rows = int(slots), int(rows)
+        if self.slots < 1 or self.rows % hop or self.rows < self.slots * self.filler:
+            raise ValueError('a capacity of %d slots needs rows a multiple of %d and at least %d, got %d'
+                             % (self.slots, hop, self.slots * self.filler, self.rows))
+        m = hp.model
+        if 'in' in (m.get('normalize'), m.get('normalize_cond'), m.get('normalize_wavenet')):
+            raise _lib.PwvError("GraphedPackedVocoder: instance normalisation ('in') runs packed batches utterance by utterance")
+        if m.cond_upsample_method != 'repeat' or m.normalize_cond:
+            raise _lib.PwvError('GraphedPackedVocoder: %r conditioning%s runs packed batches on the padded batch'
+                                % (m.cond_upsample_method, ' with normalize_cond' if m.normalize_cond else ''))
+        self.frames = self.rows // hop + self.slots
+        self.mel = torch.zeros((self.frames, int(hp.signal.n_mels)), dtype=torch.float32, device=self.device)
+        self.z = torch.zeros((self.rows, 1), dtype=torch.float32, device=self.device)
+        # the three tables in ONE device buffer, written from one pinned staging copy per call: cu_rows, cu_frames (int32 [slots+1]
+        # each), streams (int64 [slots, 2] = {seed_i, offset_i}, uint64 bits); two staging buffers, so that a call does not wait for
+        # the copy of the previous one
+        nt = 8 * (self.slots + 1) + 16 * self.slots
+        self._tables = torch.zeros((nt,), dtype=torch.uint8, device=self.device)
+        self.cu_rows = self._tables[:4 * (self.slots + 1)].view(torch.int32)
+        self.cu_frames = self._tables[4 * (self.slots + 1):8 * (self.slots + 1)].view(torch.int32)
+        self.streams = self._tables[8 * (self.slots + 1):].view(torch.int64).view(self.slots, 2)
+        self._unit_map = torch.zeros(((self.rows + 31) // 32 * _lib.VARLEN_REC_INTS,), dtype=torch.int32, device=self.device)
+        self._staging = [torch.zeros((nt,), dtype=torch.uint8).pin_memory() for _ in range(2)]
+        self._staged = [None, None]
+        self._flip = 0
+        self._warmup = max(1, int(warmup))
+        self._stream = None
+        self._words = None
+        self.graph = None
+        self.captures = 0          # graphs captured so far (a weight or launch-knob change, or the end of a suspension, captures again)
+        self.eager_calls = 0       # calls that ran the eager packed forward instead (a suspension, a layout that does not fit)
+        self._capture()
+
+    # -- layout ------------------------------------------------------------------------------------------------------------------
+    def _layout(self, lengths):
+        """The lengths of all `slots` utterances of a replay: the real ones, then the fillers; ValueError if they do not fit."""
+        lengths = [int(v) for v in lengths]
+        n = len(lengths)
+        if not 1 <= n <= self.slots:
+            raise ValueError('%d utterances for %d slots' % (n, self.slots))
+        for v in lengths:
+            if v < _lib.VARLEN_MIN_ROWS or v % self.hop:
+                raise ValueError('utterance lengths must be multiples of hop_length (%d) of at least %d samples, got %d'
+                                 % (self.hop, _lib.VARLEN_MIN_ROWS, v))
+        k, left = self.slots - n, self.rows - sum(lengths)
+        if k == 0:
+            if left != 0:
+                raise ValueError('%d utterances in all %d slots must fill the %d rows exactly, they hold %d' % (n, n, self.rows, self.rows - left))
+            return lengths
+        if left < k * self.filler:
+            raise ValueError('%d rows and %d filler utterances of at least %d rows exceed the %d rows' % (self.rows - left, k, self.filler, self.rows))
+        return lengths + [self.filler] * (k - 1) + [left - (k - 1) * self.filler]
+
+    def fits(self, lengths) -> bool:
+        """Can utterances of these lengths (samples) be replayed by this capture?"""
+        try:
+            self._layout(lengths)
+        except ValueError:
+            return False
+        return True
+
+    def _write_tables(self, lengths, streams):
+        """cu_rows, cu_frames and streams of the layout `lengths` (fillers included) into the device tables: one copy from pinned
+        staging, enqueued on the current stream."""
+        k = self._flip
+        self._flip ^= 1
+        if self._staged[k] is not None:
+            self._staged[k].synchronize()          # (the copy that last read this staging buffer has run)
+        cu_rows, cu_frames = [0], [0]
+        for v in lengths:
+            cu_rows.append(cu_rows[-1] + v)
+            cu_frames.append(cu_frames[-1] + v // self.hop + 1)
+        pairs = list(streams) + [(self.FILLER_SEED, 0)] * (len(lengths) - len(streams))
+        buf = self._staging[k].numpy()
+        a = 4 * (self.slots + 1)
+        buf[:a] = np.asarray(cu_rows, np.int32).view(np.uint8)
+        buf[a:2 * a] = np.asarray(cu_frames, np.int32).view(np.uint8)
+        buf[2 * a:] = np.asarray([engine.as_int64_bits(v) for p in pairs for v in p], np.int64).view(np.uint8)
+        self._tables.copy_(self._staging[k], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self._staged[k] = ev
+
+    # -- capture -----------------------------------------------------------------------------------------------------------------
+    def _enqueue(self):
+        """The forward the graph holds: sampler, unit map, prologue, packed persistent flows (only enqueues)."""
+        engine.logistic_noise_packed_op(self.cu_rows, self.streams, self.rows, out=self.z)
+        self._geom.build_unit_map()
+        m = self.model
+        return engine.verified_call(lambda prec: m._forward_varlen(self.store, self.mel, self.z, self._geom, prec or m.precision),
+                                    verify=False)
+
+    def _capture(self):
+        self.graph = None
+        if engine.persist_suspended():
+            return           # (no packed persistent route now: calls run eagerly until the suspension ends, then capture)
+        if self._stream is None:
+            self._stream = torch.cuda.Stream(device=self.device)
+        side = self._stream
+        layout = self._layout([self.filler])          # capture on an all-filler layout: any layout replays the same launches
+        self._write_tables(layout, [])
+        self._geom = engine.VarlenGeometry(layout, self.hop, self.device, tables=(self.cu_rows, self.cu_frames, self._unit_map))
+        self.mel.zero_()
+        # warm up on the capture stream (plans packed, allocator primed, that stream's persistent workspace created), as GraphedVocoder
+        padded = engine.VARLEN_PADDED
+        side.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(side):
+            for _ in range(self._warmup):
+                self._enqueue()
+        torch.cuda.current_stream(self.device).wait_stream(side)
+        if engine.VARLEN_PADDED != padded:
+            raise _lib.PwvError('GraphedPackedVocoder: a flow takes the padded fallback at %d slots / %d rows (%s): its launches depend on '
+                                'the lengths, there is nothing to capture' % (self.slots, self.rows, engine.VARLEN_PADDED_WHY))
+        engine.verify_enqueued('the warm-up of a packed graph')
+        graph = torch.cuda.CUDAGraph()
+        self._words = engine.current_words(self.device)
+        with torch.cuda.graph(graph, stream=side, capture_error_mode='thread_local'):
+            self.out = self._enqueue()
+        self.graph = graph
+        self._version = self.store.version
+        self._mode = engine.launch_knobs()
+        self.captures += 1
+
+    # -- calls -------------------------------------------------------------------------------------------------------------------
+    def __call__(self, melspecs, seeds, offsets=None):
+        """Vocode n <= slots utterances (a list of [t_mel_i, n_mels] float32 mels on the GPU, len_i = (t_mel_i - 1) * hop samples)
+        with noise streams (seeds[i], offsets[i]) -- the contract of IAFVocoder.generate_varlen(seeds=...): the same bits.  Returns
+        a VarlenOutput of [len_i, 1] views of the graph's output buffer: valid until the next call (clone to keep).  Enqueue-only:
+        call verify() before reading.  A layout that does not fit, or a call while the persistent launches are suspended, runs the
+        eager generate_varlen(verify=False) instead and returns its result."""
+        if not isinstance(melspecs, (list, tuple)) or not melspecs:
+            raise ValueError('melspecs must be a non-empty list of [t_mel, n_mels] tensors')
+        n_mels = int(hp.signal.n_mels)
+        for i, m in enumerate(melspecs):
+            if not hasattr(m, 'dim') or m.dim() != 2 or m.shape[1] != n_mels or m.shape[0] < 2:
+                raise ValueError('melspecs[%d] must be [t_mel >= 2, %d], got %s' % (i, n_mels, tuple(getattr(m, 'shape', ()))))
+        streams = noise_streams(seeds, offsets, len(melspecs))
+        if streams is None:
+            raise ValueError('a packed graph draws its noise from seeds: pass one per utterance')
+        lengths = [(int(m.shape[0]) - 1) * self.hop for m in melspecs]
+        if engine.persist_suspended():
+            self.graph = None       # (the suspension retired the workspace the captured launches point at)
+        if engine.persist_suspended() or not self.fits(lengths):
+            self.eager_calls += 1
+            return self.model.generate_varlen(list(melspecs), seeds=[s for s, _ in streams], offsets=[o for _, o in streams], verify=False)
+        if self.graph is None or self.store.version != self._version or self._mode != engine.launch_knobs():
+            self._capture()         # first call after a suspension, new weights (the launches point at stale packs), other launch knobs
+        engine.note_forward()
+        layout = self._layout(lengths)
+        real_frames = sum(int(m.shape[0]) for m in melspecs)
+        torch.cat([engine._require_cuda_f32(m, 'melspecs[%d]' % i) for i, m in enumerate(melspecs)], out=self.mel[:real_frames])
+        self.mel[real_frames:].zero_()
+        self._write_tables(layout, streams)
+        self.graph.replay()
+        geom = _Layout(lengths, self.hop)
+        return VarlenOutput(self.out[:geom.rows], geom)
+
+    def verify(self):
+        """Wait for the enqueued calls and raise like IAFVocoder.verify(): PwvPersistError if a persistent launch gave up (the engine
+        suspends the persistent launches; calls run eagerly meanwhile and the graph is captured again once the suspension ends),
+        PwvRangeError if one left the range of the split-fp16 arithmetic.  The caller reruns with the same seeds: the same noise."""
+        try:
+            engine.verify_enqueued()
+            if self._words is not None and self._words is not engine.current_words(self.device):
+                engine.verify_enqueued(words=self._words)       # (a graph captured by another thread reports into that thread's words)
+        except _lib.PwvPersistError:
+            self.graph = None
+            raise
+
+
+class _Layout(object):
+    """The layout of a replay's real utterances, in the shape VarlenOutput.geometry has (lengths, cu_rows_host, cu_frames_host)."""
+
+    def __init__(self, lengths, hop):
+        self.lengths, self.hop = list(lengths), hop
+        self.cu_rows_host, self.cu_frames_host = [0], [0]
+        for v in self.lengths:
+            self.cu_rows_host.append(self.cu_rows_host[-1] + v)
+            self.cu_frames_host.append(self.cu_frames_host[-1] + v // hop + 1)
+        self.n, self.rows = len(self.lengths), self.cu_rows_host[-1]

@@ -34,6 +34,27 @@ class VarlenOutput(list):
         self.geometry = geometry
 
 
+def noise_streams(seeds, offsets, n, z=None):
+    """[(seed_i, offset_i)] of a packed batch of n utterances with one noise stream each (IAFVocoder.generate_varlen), or None when
+    `seeds` is None (then `offsets` must be too).  Every value is an integer in [0, 2**64): the sampler's uint64."""
+    if seeds is None:
+        if offsets is not None:
+            raise ValueError('offsets need seeds')
+        return None
+    if z is not None:
+        raise ValueError('seeds and z exclude each other: seeds draw the noise, z is the noise')
+
+    def ints(vals, what):
+        vals = list(vals.tolist() if hasattr(vals, 'tolist') else vals)
+        if len(vals) != n:
+            raise ValueError('%s holds %d values for %d utterances' % (what, len(vals), n))
+        for i, v in enumerate(vals):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < (1 << 64):
+                raise ValueError('%s[%d] must be an integer in [0, 2**64), got %r' % (what, i, v))
+        return [int(v) for v in vals]
+    return list(zip(ints(seeds, 'seeds'), ints([0] * n if offsets is None else offsets, 'offsets')))
+
+
 class IAFVocoder(object):
 
     def __init__(self, batch_size, length, store: Optional[VariableStore] = None, precision: Optional[str] = None):
@@ -143,18 +164,23 @@ class IAFVocoder(object):
         return input
 
     # -- mixed-length batches ("Packed batches") -----------------------------------------------------
-    def generate_varlen(self, melspecs, z=None, verify=None):
+    def generate_varlen(self, melspecs, z=None, verify=None, seeds=None, offsets=None):
         """One forward over utterances of DIFFERENT lengths, without padding them to the longest.  `melspecs`: a list of
         [t_mel_i, n_mels] float32 tensors on the GPU (t_mel_i >= 2); utterance i yields len_i = (t_mel_i - 1) * hop samples.
         Returns a list (VarlenOutput) of [len_i, 1] tensors, views of ONE packed [R, 1] result (R = sum of len_i), which is
         `.packed` of the list.  ``z`` (optional): the noise, packed [R, 1] or a list of [len_i, 1]; by default one draw of R
         counters that continues this model's stream (row r of the packed batch is counter noise_offset + r).  The constructor's
-        `batch_size` and `length` are not used here.  ``verify`` as for __call__."""
+        `batch_size` and `length` are not used here.  ``verify`` as for __call__.
+        ``seeds`` (optional, one integer in [0, 2**64) per utterance) gives every utterance a noise stream of its own, starting at
+        counter ``offsets[i]`` (default 0): piece i is then exactly what IAFVocoder(1, len_i) with noise_seed = seeds[i] and
+        noise_offset = offsets[i] returns for mel i alone, whatever its companions and its position; this model's noise_offset does
+        not move.  Not together with ``z``."""
         if not isinstance(melspecs, (list, tuple)) or not melspecs:
             raise ValueError('melspecs must be a non-empty list of [t_mel, n_mels] tensors')
         for i, m in enumerate(melspecs):
             if not hasattr(m, 'dim') or m.dim() != 2 or m.shape[1] != hp.signal.n_mels or m.shape[0] < 2:
                 raise ValueError('melspecs[%d] must be [t_mel >= 2, %d], got %s' % (i, hp.signal.n_mels, tuple(getattr(m, 'shape', ()))))
+        noise_streams(seeds, offsets, len(melspecs), z)      # (checked before anything touches the device)
         if isinstance(z, (list, tuple)):      # (each piece against its own utterance: a split that only adds up to R would misassign)
             if len(z) != len(melspecs):
                 raise ValueError('z holds %d utterances, melspecs %d' % (len(z), len(melspecs)))
@@ -167,23 +193,27 @@ class IAFVocoder(object):
         cu_frames = [0]
         for m in mels:
             cu_frames.append(cu_frames[-1] + m.shape[0])
-        return self.forward_packed(torch_cat(mels), cu_frames, z=z, verify=verify)
+        return self.forward_packed(torch_cat(mels), cu_frames, z=z, verify=verify, seeds=seeds, offsets=offsets)
 
-    def forward_packed(self, mel_packed, cu_frames, z=None, verify=None):
+    def forward_packed(self, mel_packed, cu_frames, z=None, verify=None, seeds=None, offsets=None):
         """generate_varlen on the packed form: `mel_packed` [F, n_mels] holds the utterances' frames one after the other and
-        `cu_frames` (host ints, F = cu_frames[-1]) their prefix sums; returns the VarlenOutput (packed result [R, 1] as `.packed`)."""
+        `cu_frames` (host ints, F = cu_frames[-1]) their prefix sums; returns the VarlenOutput (packed result [R, 1] as `.packed`).
+        ``seeds`` / ``offsets`` as for generate_varlen."""
+        cu = [int(v) for v in (cu_frames.tolist() if hasattr(cu_frames, 'tolist') else cu_frames)]
+        streams = noise_streams(seeds, offsets, len(cu) - 1, z)
         store = self.store or get_default_store()
         engine.raise_if_range_flag('an earlier call')
         engine.raise_if_persist_failed()
         mel = engine._require_cuda_f32(mel_packed, 'mel_packed')
-        cu = [int(v) for v in (cu_frames.tolist() if hasattr(cu_frames, 'tolist') else cu_frames)]
         if len(cu) < 2 or cu[0] != 0 or any(b - a < 2 for a, b in zip(cu, cu[1:])):
             raise ValueError('cu_frames must start at 0 and give every utterance at least 2 frames, got %s' % (cu,))
         if mel.dim() != 2 or mel.shape[1] != hp.signal.n_mels or mel.shape[0] != cu[-1]:
             raise ValueError('mel_packed must be [%d, %d], got %s' % (cu[-1], hp.signal.n_mels, tuple(mel.shape)))
         hop = hp.signal.hop_length
         geom = engine.VarlenGeometry([(b - a - 1) * hop for a, b in zip(cu, cu[1:])], hop, mel.device)
-        if z is None:   # one draw of R counters, continuing the stream (a rerun sees the same noise)
+        if streams is not None:     # one stream per utterance, drawn before the route is chosen: every route sees the same noise
+            noise = engine.logistic_noise_packed_op(geom.cu_rows, geom.stream_table(streams), geom.rows)
+        elif z is None:   # one draw of R counters, continuing the stream (a rerun sees the same noise)
             noise = engine.logistic_noise_op((geom.rows, 1), mel.device, seed=self._seed(), offset=self.noise_offset)
             self.noise_offset += geom.rows
         else:
