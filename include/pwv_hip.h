@@ -284,6 +284,54 @@ typedef struct pwv_layer_args {
 int pwv_wavenet_layer_f32(const pwv_layer_args* args, pwv_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
+ * STREAMING: the same layer on a CHUNK of a longer utterance                        modules.py:185-259 (the reference has no
+ * chunked form: models.py:23-78 generates a whole utterance per sess.run; the call sites replaced are the layer's own)
+ *
+ * A launch of N x T rows continues N SESSIONS: utterance n's rows are the T samples that follow what the session has seen.  The
+ * look-back x[t-d] of a row with t < d is not zero but the session's HISTORY of this layer's input, and the last d input rows of
+ * the chunk are stored as the next history.  Every row then runs the instructions of pwv_wavenet_layer_f32 in their order: the
+ * chunks of a session, concatenated, equal the one-shot launch BIT FOR BIT, whatever the chunk lengths (T < d included).  A history
+ * of zeros is the one-shot left edge (a fresh session).
+ *
+ * History layout.  `hist_rd` / `hist_wr` point at arrays of BLOCKS, `block_stride` floats apart (a multiple of 4; the two may be one
+ * array).  A block is one session's state in one generation; the caller chooses what goes where inside it:
+ *   row history of a layer (dilation d, one per net): a tile32 buffer of round32(d) rows x 64 channels at float offset row_off[g]
+ *       (a multiple of 4); row k (k < d) is the layer's input at chunk time k - d, i.e. row t < d of a chunk looks back at row t;
+ *   scalar history of layer 0 (x_first; dilation d): d + 1 floats at float offset scalar_off; element k is x_first at chunk
+ *       time k - (d + 1).
+ * slot_tab  device int32 [N][2]: utterance n READS block slot_tab[2n] of hist_rd and WRITES block slot_tab[2n+1] of hist_wr.  The
+ *       two must differ (a chunk with T < d reads rows a lane of the same launch would overwrite): keep two generations per session
+ *       and flip after the chunk is accepted -- which also makes a chunk a transaction: until the flip, the chunk can be run again
+ *       from the same state (the range-guard rerun in PWV_PREC_F32).
+ * A chunk with T >= d rewrites all d rows of the written block.  With T < d the launch writes rows d-T .. d-1 only; rows 0 .. d-T-1
+ * are the read block's rows T .. d-1 and are moved by pwv_stream_carry_f32 -- ONE launch per chunk for all layers of the model:
+ *   carry_tab  device int32 [n_carry][4] = {float offset inside a block, rows, floats per row (64: a tile32 row history, 1: a
+ *       scalar history), 0}: every history of the model; entries with rows <= T are left alone (the layer launches rewrite them).
+ * The carry launch and the layer launches of a chunk write disjoint rows and read only `hist_rd` blocks: any order.
+ *
+ * Supported: PWV_PREC_F32 / PWV_PREC_F16X3; no skip accumulation, no per-sample condition (PWV_EINVAL otherwise); three forms:
+ *   layer 0 with x_first AND first_fold (out_mode PWV_OUT_RESIDUAL; uses scalar_off),
+ *   a plain layer (out_mode PWV_OUT_RESIDUAL; uses row_off),
+ *   the last layer with head_packed / head_out (out_mode PWV_OUT_GATED; uses row_off).
+ * A frame-rate condition is indexed as in pwv_layer_args, relative to the chunk: a chunk that starts at a multiple of cond_hop brings
+ * the T / cond_hop + 1 frames from its first sample's frame on.
+ * ------------------------------------------------------------------------------------- */
+typedef struct pwv_stream_args {
+    size_t struct_size;                    /* = sizeof(pwv_stream_args) as the caller was compiled (as in pwv_persist_args) */
+    const float* hist_rd;                  /* blocks the launch reads */
+    float* hist_wr;                        /* blocks the launch writes */
+    size_t block_stride;                   /* floats between two blocks */
+    const int32_t* slot_tab;               /* device int32 [N][2] = {block read, block written} */
+    size_t row_off[PWV_MAX_NETS];          /* this layer's row history, per net of the launch */
+    size_t scalar_off;                     /* x_first: the scalar history */
+    const int32_t* carry_tab;              /* pwv_stream_carry_f32 only */
+    int32_t n_carry;
+} pwv_stream_args;
+
+int pwv_wavenet_layer_stream_f32(const pwv_layer_args* args, const pwv_stream_args* hist, pwv_stream_t stream);
+int pwv_stream_carry_f32(const pwv_stream_args* hist, int N, int T, pwv_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
  * WaveNet post-processing head                                         modules.py:145-165
  *   total = o @ skip_w + skip_bias   (in_mode PWV_HEAD_IN_GATED: use_skip_connection False,
  *                                     only the last layer's skip is live, modules.py:147)

@@ -38,6 +38,7 @@ EXPORTED_SYMBOLS = (
     'pwv_iaf_front_f16', 'pwv_cond_to_f16', 'pwv_tile32_floats', 'pwv_rows_to_tile32_f32', 'pwv_tile32_to_rows_f32',
     'pwv_linear_split_f32', 'pwv_cond_project_f32', 'pwv_pack_first_fold_f16x3', 'pwv_pack_first_fold_f32', 'pwv_cond_split_f16', 'pwv_range_flag', 'pwv_status_words_alloc', 'pwv_status_words_free', 'pwv_range_check_f32', 'pwv_range_stats_f32',
     'pwv_persist_workspace_bytes', 'pwv_persist_short_input', 'pwv_persist_status', 'pwv_wavenet_stack_persist_f32', 'pwv_varlen_unit_map',
+    'pwv_wavenet_layer_stream_f32', 'pwv_stream_carry_f32',
     'pwv_wav_to_mel_db_f32', 'pwv_pack_proj_f32', 'pwv_instance_norm_workspace_bytes', 'pwv_instance_norm_f32', 'pwv_channel_affine_f32', 'pwv_add_f32', 'pwv_gate_f32',
 )
 
@@ -175,6 +176,23 @@ class PersistArgs(Structure):
         super().__init__(*args, **kw)
         self.struct_size = ctypes.sizeof(PersistArgs)
 
+class StreamArgs(Structure):
+    """pwv_stream_args: where a streaming layer launch finds its sessions' histories (include/pwv_hip.h, "STREAMING")."""
+    _fields_ = [
+        ('struct_size', c_size_t),      # set by __init__
+        ('hist_rd', c_void_p),
+        ('hist_wr', c_void_p),
+        ('block_stride', c_size_t),
+        ('slot_tab', c_void_p),
+        ('row_off', c_size_t * PWV_MAX_NETS),
+        ('scalar_off', c_size_t),
+        ('carry_tab', c_void_p),
+        ('n_carry', ctypes.c_int32),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = ctypes.sizeof(StreamArgs)
 
 
 # per-source extra flags (none in the product; tools/probes/regw/README.md: the register-stationary probe kernel needs
@@ -205,7 +223,8 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
     from concurrent.futures import ThreadPoolExecutor
     if os.environ.get('PWV_LIB'):
         return LIB_PATH            # an explicitly chosen library is never rebuilt
-    hdrs = [os.path.join(_PKG_DIR, 'csrc', h) for h in ('pwv_common.h', 'pwv_layer_common.h', 'pwv_f16x3.h')] + [os.path.join(_REPO_ROOT, 'include', 'pwv_hip.h')]
+    hdrs = [os.path.join(_PKG_DIR, 'csrc', h) for h in ('pwv_common.h', 'pwv_layer_common.h', 'pwv_f16x3.h', 'pwv_layer_f16x3_body.inc',
+                                                         'pwv_layer_f32_body.inc')] + [os.path.join(_REPO_ROOT, 'include', 'pwv_hip.h')]
     hdr_time = max(os.path.getmtime(h) for h in hdrs + [os.path.abspath(__file__)])
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
     # ONE gfx950 code object for the XNACK mode an MI355X runs in by default (xnack-): code built for a known mode instead of
@@ -299,6 +318,8 @@ def _declare(lib):
     lib.pwv_pack_layer_f32.argtypes = [f32p] * 8 + [c_int, c_int, c_int, f32p, c_void_p]
     lib.pwv_proj_column_map.argtypes = [POINTER(c_int)]
     lib.pwv_wavenet_layer_f32.argtypes = [POINTER(LayerArgs), c_void_p]
+    lib.pwv_wavenet_layer_stream_f32.argtypes = [POINTER(LayerArgs), POINTER(StreamArgs), c_void_p]
+    lib.pwv_stream_carry_f32.argtypes = [POINTER(StreamArgs), c_int, c_int, c_void_p]
     lib.pwv_head_packed_floats.restype = c_size_t
     lib.pwv_head_packed_floats.argtypes = [c_int]
     lib.pwv_pack_head_f32.argtypes = [f32p] * 6 + [c_int, c_int, f32p, c_void_p]

@@ -21,7 +21,9 @@
 //   * fp32 arithmetic: v_mfma_f32_32x32x2_f32 (exact fp32 fma chains, 157 TFLOP/s peak).
 #include "pwv_layer_common.h"
 
+#include <cstddef>
 #include <cstdlib>
+#include <cstring>
 
 namespace pwv {
 
@@ -64,8 +66,10 @@ __device__ __forceinline__ void load_skip_row(const LayerParams& p, int net, int
 // The skip-sum row is NOT loaded with the tile (the kernel requests it in front of GEMM2 / the gating instead: its 64 registers
 // next to x[t-d], x[t], P and the per-sample condition at the top of the unit were the 27-35 spilled VGPRs of the SKIP + COND
 // variants)
-template <bool SKIP, bool COND, bool FIRST>
-__device__ __forceinline__ void load_tile(const LayerParams& p, int net, int unit, int lane, TileRegs<SKIP, COND>& r) {
+// STREAM (layer_f32_stream_kernel): rows left of the chunk come from the session's history block instead of zeros (StreamParams,
+// pwv_layer_common.h; every address a valid one, selected rather than predicated); `wr` = the block the lane's utterance writes.
+template <bool SKIP, bool COND, bool FIRST, bool STREAM>
+__device__ __forceinline__ void load_tile(const LayerParams& p, const StreamParams& st, int net, int unit, int lane, TileRegs<SKIP, COND>& r, int& wr) {
     const int h = lane >> 5;
     const int rows = p.N * p.T;
     const int row = unit * 32 + (lane & 31);
@@ -77,7 +81,23 @@ __device__ __forceinline__ void load_tile(const LayerParams& p, int net, int uni
     const int t = rc - n * p.T;
     const bool has_prev = t >= p.dilation;            // x[t-d] = 0 left of the utterance start
     r.t = t;
-    if constexpr (FIRST) {
+    if constexpr (STREAM) {
+        const int2 blk = reinterpret_cast<const int2*>(st.slot_tab)[n];
+        wr = blk.y;
+        const float* hist = st.hist_rd + (long long)blk.x * st.block_stride;
+        if constexpr (FIRST) {
+            const float* x1 = p.x_first + rc;
+            const float* hx = hist + st.scalar_off;      // x[-(d + 1)] .. x[-1]: time r < 0 is hx[d + 1 + r]
+            const int d = p.dilation;
+            r.xc[0] = *x1;
+            r.xc[1] = *(t >= 1 ? x1 - 1 : hx + d);
+            r.xb[0] = *(has_prev ? x1 - d : hx + t + 1);
+            r.xb[1] = *(t >= d + 1 ? x1 - d - 1 : hx + t);
+        } else {
+            load_tiled<8, 64>(p.x_in[net], rc, h, true, r.xc);
+            load_tiled<8, 64>(has_prev ? p.x_in[net] : hist + st.row_off[net], has_prev ? rc - p.dilation : t, h, true, r.xb);
+        }
+    } else if constexpr (FIRST) {
         // the four scalars the two rows are functions of: x[t], x[t-1], x[t-d], x[t-d-1] (zero left of the start);
         // rebuild_first() turns them into the rows
         const float* x1 = p.x_first;
@@ -109,322 +129,43 @@ __device__ __forceinline__ void load_tile(const LayerParams& p, int net, int uni
 //   come from global memory and units are handed out statically (no room for the counter).
 // FOLD (with FIRST): layer 0's filter|gate convolution on the four scalars x[t-d-1], x[t-d], x[t-1], x[t] themselves
 //   (pwv_pack_first_fold_f32; see layer_f16x3_kernel): two fp32 MFMA k-steps per row tile instead of 64.
+// STREAM: see layer_f16x3_kernel (pwv_layer_f16.hip) -- history look-back instead of zeros, the chunk's last rows stored as the
+//   next history.  The body is text included into both kernels (pwv_layer_f32_body.inc): the non-streaming instantiations keep
+//   their names and their instruction streams.
 template <bool SKIP, bool COND, bool GATED, bool FIRST = false, bool HEAD = false, bool FOLD = false>
 __global__ __launch_bounds__(512) void layer_f32_kernel(const LayerParams p) {
-    static_assert(!FOLD || FIRST, "FOLD: layer 0 of a scalar-input net only");
-    static_assert(!HEAD || (GATED && !SKIP && !COND && !FIRST), "HEAD: plain last layer only");
-    static_assert(!FIRST || !SKIP, "FIRST: no skip accumulation");
-    constexpr int WAVES = 8;
-    constexpr int kLds = HEAD ? kA1Size + kASSize + kHA1Size : layer_floats(SKIP, COND);
-    constexpr int kCF = kLds + 4;           // FIRST: the causal filter [2][64] behind the unit counter
-    constexpr int kHS = kA1Size;            // HEAD: skip weights, then postprocess1
-    constexpr int kH1 = kA1Size + kASSize;
-    __shared__ __attribute__((aligned(16))) float lds[kLds + (HEAD ? 0 : 4) + (FIRST ? 128 : 0)];   // +4: the unit counter
+    constexpr bool STREAM = false;
+    const StreamParams st{};      // (not read)
+#include "pwv_layer_f32_body.inc"
+}
 
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int h = lane >> 5;
-    const int net = blockIdx.x % p.G;
-    const int wg = blockIdx.x / p.G;
-    const int nwg = gridDim.x / p.G;
-    int* unit_counter = reinterpret_cast<int*>(&lds[HEAD ? 0 : kLds]);      // unused with HEAD
+// the streaming forms: layer 0 folded (FIRST), the last layer + head (HEAD), else a plain residual layer
+template <bool FIRST, bool HEAD>
+__global__ __launch_bounds__(512) void layer_f32_stream_kernel(const LayerParams p, const StreamParams st) {
+    constexpr bool STREAM = true, SKIP = false, COND = false, GATED = HEAD, FOLD = FIRST;
+#include "pwv_layer_f32_body.inc"
+}
 
-    if constexpr (HEAD) {
-        fill_lds_dma<kA1Size / 4, WAVES>(lds, p.packed[net] + kA1, wave, lane);
-        fill_lds_dma<kASSize / 4, WAVES>(lds + kHS, p.packed_head[net] + kHAS, wave, lane);
-        fill_lds_dma<kHA1Size / 4, WAVES>(lds + kH1, p.packed_head[net] + kHA1, wave, lane);
-    } else {
-        fill_lds_dma<kLds / 4, WAVES>(lds, p.packed[net], wave, lane);
-        if (tid == 0) *unit_counter = 0;
-        if constexpr (FIRST) {
-            if (tid < 128) lds[kCF + tid] = p.cfilt[net][tid];
-        }
+// pwv_stream_carry_f32: the rows of the read blocks that a chunk of T rows does not push out, moved to the written blocks
+// (new[k] = old[k + T], k < len - T), for every history of the model in one launch: block (entry, utterance); `tab` holds
+// {float offset in a block, rows, floats per row (64: tile32 rows, 1: scalars), 0} per entry.
+__global__ __launch_bounds__(256) void stream_carry_kernel(const StreamParams st, const int* __restrict__ tab, int T) {
+    const int e = blockIdx.x, n = blockIdx.y;
+    const int off = tab[4 * e], len = tab[4 * e + 1], width = tab[4 * e + 2];
+    const int keep = len - T;
+    if (keep <= 0) return;
+    const int2 blk = reinterpret_cast<const int2*>(st.slot_tab)[n];
+    const float* src = st.hist_rd + (long long)blk.x * st.block_stride + off;
+    float* dst = st.hist_wr + (long long)blk.y * st.block_stride + off;
+    if (width == 1) {
+        for (int k = threadIdx.x; k < keep; k += blockDim.x) dst[k] = src[k + T];
+        return;
     }
-    __syncthreads();
-
-    constexpr int kAS = kLayerBase;
-    constexpr int kBS = kAS + kASSize;
-    constexpr int kAC = kLayerBase + (SKIP ? kASSize + kBSSize : 0);
-    constexpr int NC8 = kCondC / 8;
-
-    const int rows = p.N * p.T;
-    const int units = (rows + 31) / 32;
-    const bool skip_load = SKIP && !p.skip_init;
-
-    // this workgroup's contiguous share of the units
-    const int per_wg = (units + nwg - 1) / nwg;
-    const int u_begin = wg * per_wg;
-    const int u_end = (u_begin + per_wg < units) ? u_begin + per_wg : units;
-
-    auto grab = [&]() -> int {   // next unit for this wave
-        int v = 0;
-        if (lane == 0) v = __hip_atomic_fetch_add(unit_counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        return u_begin + __builtin_amdgcn_readfirstlane(v);
-    };
-
-    TileRegs<SKIP, COND> cur;
-    if (wave >= WAVES / 2) __builtin_amdgcn_s_setprio(1);
-    int unit = HEAD ? u_begin + wave : grab();
-
-    auto no_extra = [](int) {};
-    const __amdgpu_buffer_rsrc_t out_rs = units_rsrc(p.x_out[net], u_begin, u_end, 32 * 64 * 4);      // unused with HEAD
-
-    while (unit < u_end) {
-        load_tile<SKIP, COND, FIRST>(p, net, unit, lane, cur);
-        float first_x0 = 0.f, first_x1 = 0.f;      // FIRST: x[t], x[t-1]
-        float fold_b0 = 0.f, fold_b1 = 0.f;        // FOLD: the B values of the two k-steps
-        (void)first_x0;
-        (void)first_x1;
-        (void)fold_b0;
-        (void)fold_b1;
-        if constexpr (FIRST) {
-            // this lane's 32 channels (8g + 4h + e) of h[t] and h[t-d] from the scalars; same operation order as
-            // iaf_front_kernel: round(x[t-1] w0), then fma(x[t], w1, .)
-            const float x0 = cur.xc[0], x1v = cur.xc[1], xd0 = cur.xb[0], xd1 = cur.xb[1];
-            first_x0 = x0;
-            first_x1 = x1v;
-            const bool has_prev = cur.t >= p.dilation;
-            if constexpr (FOLD) {      // (x[t-d], x[t-d-1] are already zero left of the start)
-                fold_b0 = h ? xd0 : xd1;      // k = 0, 1
-                fold_b1 = h ? x0 : x1v;       // k = 2, 3
-            }
-#pragma unroll
-            for (int g = 0; g < (FOLD ? 0 : 8); ++g) {
-                const f32x4 w0 = *reinterpret_cast<const f32x4*>(&lds[kCF + 8 * g + 4 * h]);
-                const f32x4 w1 = *reinterpret_cast<const f32x4*>(&lds[kCF + 64 + 8 * g + 4 * h]);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    cur.xc[4 * g + e] = fmaf(x0, w1[e], x1v * w0[e]);
-                    const float vb = fmaf(xd0, w1[e], xd1 * w0[e]);
-                    cur.xb[4 * g + e] = has_prev ? vb : 0.f;
-                }
-                __builtin_amdgcn_sched_barrier(0);      // one filter quad at a time: the scheduler otherwise front-loads all 16 reads
-            }
-        }
-        // ---- GEMM1: [F;G][128 x 32t] = W1^T[128 x K] * [x[t-d]; x[t]; (cond[t])] -------------
-        // accumulators start at P[frame(t)] (conditioning projection + filter/gate bias)
-        f32x16 acc[4];
-#pragma unroll
-        for (int it = 0; it < 4; ++it)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[it][r] = cur.pj[it * 16 + r];
-        float o[32];
-        f32x4 a[4];
-        auto bx = [&](int ks) -> float { return ks < 32 ? cur.xb[ks] : cur.xc[ks - 32]; };
-        auto bc = [&](int ks) -> float { return cur.cd[COND ? ks : 0]; };
-        // pair 0 = row tiles (0: F[0:32], 2: G[0:32]); pair 1 = (1: F[32:64], 3: G[32:64]).
-        // pair 0 is gated on the VALU while pair 1's MFMAs run.
-        if constexpr (FOLD) {
-            // ---- layer 0, folded: the per-sample condition's GEMM (if any), then two k-steps on the scalars ------------------
-            if constexpr (COND) {
-                a[0] = frag(lds, kAC, 0, NC8, 0, lane);
-                a[1] = frag(lds, kAC, 2, NC8, 0, lane);
-                gemm_groups<NC8, 2, 0, 2>(lds, kAC, lane, acc, a, bc, no_extra, [&](f32x4(&n)[4]) {
-                    n[0] = frag(lds, kAC, 1, NC8, 0, lane);
-                    n[1] = frag(lds, kAC, 3, NC8, 0, lane);
-                });
-                gemm_groups<NC8, 2, 1, 2>(lds, kAC, lane, acc, a, bc, no_extra, [](f32x4(&)[4]) {});
-            }
-            const f32x4* F0 = reinterpret_cast<const f32x4*>(p.fold0[net]);
-            f32x4 ff[4];
-#pragma unroll
-            for (int it = 0; it < 4; ++it) ff[it] = F0[it * 64 + lane];
-#pragma unroll
-            for (int it = 0; it < 4; ++it) acc[it] = __builtin_amdgcn_mfma_f32_32x32x2f32(ff[it][0], fold_b0, acc[it], 0, 0, 0);
-#pragma unroll
-            for (int it = 0; it < 4; ++it) acc[it] = __builtin_amdgcn_mfma_f32_32x32x2f32(ff[it][1], fold_b1, acc[it], 0, 0, 0);
-            if constexpr (!GATED) {
-                a[0] = frag(lds, kA2, 0, 8, 0, lane);
-                a[1] = frag(lds, kA2, 1, 8, 0, lane);
-            }
-#pragma unroll
-            for (int g = 0; g < 16; ++g) o[g] = gate_act(acc[0][g], acc[2][g]);
-        } else {
-        if constexpr (COND) {
-            a[0] = frag(lds, kAC, 0, NC8, 0, lane);
-            a[1] = frag(lds, kAC, 2, NC8, 0, lane);
-            gemm_groups<NC8, 2, 0, 2>(lds, kAC, lane, acc, a, bc, no_extra, [&](f32x4(&n)[4]) {
-                n[0] = frag(lds, kA1, 0, 16, 0, lane);
-                n[1] = frag(lds, kA1, 2, 16, 0, lane);
-            });
-        } else {
-            a[0] = frag(lds, kA1, 0, 16, 0, lane);
-            a[1] = frag(lds, kA1, 2, 16, 0, lane);
-        }
-        gemm_groups<16, 2, 0, 2>(lds, kA1, lane, acc, a, bx, no_extra, [&](f32x4(&n)[4]) {
-            if constexpr (COND) {
-                n[0] = frag(lds, kAC, 1, NC8, 0, lane);
-                n[1] = frag(lds, kAC, 3, NC8, 0, lane);
-            } else {
-                n[0] = frag(lds, kA1, 1, 16, 0, lane);
-                n[1] = frag(lds, kA1, 3, 16, 0, lane);
-            }
-        });
-        if constexpr (COND) {
-            gemm_groups<NC8, 2, 1, 2>(lds, kAC, lane, acc, a, bc, no_extra, [&](f32x4(&n)[4]) {
-                n[0] = frag(lds, kA1, 1, 16, 0, lane);
-                n[1] = frag(lds, kA1, 3, 16, 0, lane);
-            });
-        }
-        gemm_groups<16, 2, 1, 2>(
-            lds, kA1, lane, acc, a, bx,
-            [&](int g) {
-                o[g] = gate_act(acc[0][g], acc[2][g]);
-                asm volatile("" : "+v"(o[g]));   // keep the gating inside this MFMA group (no sinking)
-            },
-            [&](f32x4(&n)[4]) {
-                if constexpr (!GATED) {
-                    n[0] = frag(lds, kA2, 0, 8, 0, lane);
-                    n[1] = frag(lds, kA2, 1, 8, 0, lane);
-                } else if constexpr (SKIP) {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) n[i] = frag(lds, kAS, i, 8, 0, lane);
-                } else if constexpr (HEAD) {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) n[i] = frag(lds, kHS, i, 8, 0, lane);
-                }
-            });
-        }
-
-        const int ooff = units_off(cur.row, h, 64, u_begin);      // (rows past the end are never stored: `valid`)
-        if constexpr (GATED && HEAD) {
-            // ---- fused head: o (registers) -> skip -> relu -> postprocess1 -> relu -> postprocess2, the operations
-            //      (and bits) of head_f32_kernel<true> ------------------------------------------------------------
-            const float* hb = p.packed_head[net];
-            f32x16 accs[4];
-#pragma unroll
-            for (int it = 0; it < 4; ++it)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const f32x4 v = *reinterpret_cast<const f32x4*>(hb + kHBS + h * 64 + it * 16 + q * 4);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) accs[it][q * 4 + e] = v[e];
-                }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[16 + r] = gate_act(acc[1][r], acc[3][r]);
-            gemm_groups<8, 4, 0, 1>(lds, kHS, lane, accs, a, [&](int ks) -> float { return o[ks]; }, no_extra,
-                                    [&](f32x4(&n)[4]) {
-#pragma unroll
-                                        for (int i = 0; i < 4; ++i) n[i] = frag(lds, kH1, i, 16, 0, lane);
-                                    });
-            f32x16 acc1[4];
-#pragma unroll
-            for (int it = 0; it < 4; ++it)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const f32x4 v = *reinterpret_cast<const f32x4*>(hb + kHB1 + h * 64 + it * 16 + q * 4);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) acc1[it][q * 4 + e] = v[e];
-                }
-            gemm_groups<16, 4, 0, 1>(
-                lds, kH1, lane, acc1, a, [&](int ks) -> float { return fmaxf(accs[ks >> 4][ks & 15], 0.f); }, no_extra,
-                [](f32x4(&)[4]) {});
-            const int Q = p.head_q;
-            for (int q = 0; q < Q; ++q) {
-                float part = 0.f;
-                const float* w2 = hb + kHW2 + (h * Q + q) * 64;
-#pragma unroll
-                for (int i4 = 0; i4 < 16; ++i4) {
-                    const f32x4 w = *reinterpret_cast<const f32x4*>(w2 + 4 * i4);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const int i = 4 * i4 + e;
-                        part = fmaf(fmaxf(acc1[i >> 4][i & 15], 0.f), w[e], part);
-                    }
-                }
-                part += __shfl_xor(part, 32);
-                part += hb[kHW2 + 2 * Q * 64 + q];
-                if (cur.valid && h == 0) p.head_out[net][(size_t)cur.row * Q + q] = part;
-            }
-        } else if constexpr (GATED) {
-            if constexpr (SKIP) load_skip_row<SKIP, COND>(p, net, lane, cur, skip_load);      // in flight under the gating
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[16 + r] = gate_act(acc[1][r], acc[3][r]);
-            if (cur.valid) {
-#pragma unroll
-                for (int g = 0; g < 8; ++g) {
-                    f32x4 v = {o[4 * g], o[4 * g + 1], o[4 * g + 2], o[4 * g + 3]};
-                    store_wt(out_rs, ooff + g * 1024, v);
-                }
-            }
-        } else {
-            // ---- GEMM2: dense 64 -> 64, accumulator starts at x[t] + dense_bias ---------------
-            f32x16 acc2[2];
-#pragma unroll
-            for (int it = 0; it < 2; ++it) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const f32x4 bd = *reinterpret_cast<const f32x4*>(&lds[kBD + h * 32 + it * 16 + q * 4]);
-                    if constexpr (FIRST) {
-                        // x[t] row evaluated again from the two scalars (same operations, same bits) rather than kept live
-                        const int g = it * 4 + q;
-                        const f32x4 w0 = *reinterpret_cast<const f32x4*>(&lds[kCF + 8 * g + 4 * h]);
-                        const f32x4 w1 = *reinterpret_cast<const f32x4*>(&lds[kCF + 64 + 8 * g + 4 * h]);
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) acc2[it][q * 4 + e] = fmaf(first_x0, w1[e], first_x1 * w0[e]) + bd[e];
-                    } else {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) acc2[it][q * 4 + e] = cur.xc[it * 16 + q * 4 + e] + bd[e];
-                    }
-                }
-            }
-            if constexpr (SKIP) load_skip_row<SKIP, COND>(p, net, lane, cur, skip_load);      // in flight under GEMM2
-            // k-steps 0..15 use o tile 0 (ready); pair 1 is gated under those MFMAs
-            gemm_groups<8, 2, 0, 1>(
-                lds, kA2, lane, acc2, a, [&](int ks) -> float { return o[ks]; },
-                [&](int g) {
-                    if (g < 4) {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            o[16 + 4 * g + e] = gate_act(acc[1][4 * g + e], acc[3][4 * g + e]);
-                            asm volatile("" : "+v"(o[16 + 4 * g + e]));
-                        }
-                    }
-                },
-                [&](f32x4(&n)[4]) {
-                    if constexpr (SKIP) {
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) n[i] = frag(lds, kAS, i, 8, 0, lane);
-                    }
-                });
-            if (cur.valid) {
-#pragma unroll
-                for (int g = 0; g < 8; ++g) {
-                    const int it = g >> 2, q = g & 3;
-                    f32x4 v = {acc2[it][q * 4], acc2[it][q * 4 + 1], acc2[it][q * 4 + 2], acc2[it][q * 4 + 3]};
-                    store_wt(out_rs, ooff + g * 1024, v);
-                }
-            }
-        }
-
-        if constexpr (SKIP) {
-            // ---- skip 64 -> 128, accumulated across layers (modules.py:243-250, :147) ----------
-            f32x16 accs[4];
-#pragma unroll
-            for (int it = 0; it < 4; ++it)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const f32x4 bs = *reinterpret_cast<const f32x4*>(&lds[kBS + h * 64 + it * 16 + q * 4]);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) accs[it][q * 4 + e] = cur.sk[it * 16 + q * 4 + e] + bs[e];
-                }
-            gemm_groups<8, 4, 0, 1>(lds, kAS, lane, accs, a, [&](int ks) -> float { return o[ks]; }, no_extra,
-                                    [](f32x4(&)[4]) {});
-            if (cur.valid) {
-                const __amdgpu_buffer_rsrc_t skip_rs = units_rsrc(p.skip[net], u_begin, u_end, 32 * 128 * 4);
-                const int soff = units_off(cur.row, h, 128, u_begin);
-#pragma unroll
-                for (int it = 0; it < 4; ++it)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        f32x4 v = {accs[it][q * 4], accs[it][q * 4 + 1], accs[it][q * 4 + 2], accs[it][q * 4 + 3]};
-                        store_wt(skip_rs, soff + (8 * it + 2 * q) * 512, v);
-                    }
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        unit = HEAD ? unit + WAVES : grab();
+    // 32 consecutive rows of one channel quad per 32 threads: 512 B contiguous on the written side
+    const int total = ((keep + 31) >> 5) * 512;
+    for (int i = threadIdx.x; i < total; i += blockDim.x) {
+        const int k = (i >> 9) * 32 + (i & 31), q = (i >> 5) & 15;
+        if (k < keep) *reinterpret_cast<f32x4*>(dst + tile_off(k, q, 64)) = *reinterpret_cast<const f32x4*>(src + tile_off(k + T, q, 64));
     }
 }
 
@@ -706,7 +447,10 @@ int pwv_pack_head_f32(const float* skip, const float* skip_bias, const float* po
     return PWV_OK;
 }
 
-int pwv_wavenet_layer_f32(const pwv_layer_args* a, pwv_stream_t stream) {
+}  // extern "C"
+
+// pwv_wavenet_layer_f32 (st == NULL) and pwv_wavenet_layer_stream_f32: checks, kernel parameters, grid, instantiation
+static int layer_call(const pwv_layer_args* a, const StreamParams* st, pwv_stream_t stream) {
     PWV_CHECK_ARG(a, "pwv_wavenet_layer_f32: args is NULL");
     PWV_CHECK_ARG(a->G >= 1 && a->G <= PWV_MAX_NETS, "pwv_wavenet_layer_f32: G=%d out of range", a->G);
     PWV_CHECK_ARG(a->N >= 1 && a->T >= 1 && a->dilation >= 1, "pwv_wavenet_layer_f32: bad N/T/dilation");
@@ -781,6 +525,15 @@ int pwv_wavenet_layer_f32(const pwv_layer_args* a, pwv_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
     const bool cond = a->cond != nullptr, gated = a->out_mode == PWV_OUT_GATED;
     PWV_CHECK_ARG(a->out_mode == PWV_OUT_GATED || a->out_mode == PWV_OUT_RESIDUAL, "pwv_wavenet_layer_f32: bad out_mode");
+    if (st) {      // (pwv_wavenet_layer_stream_f32 has checked that the layer is one of the three streaming forms)
+        if (a->precision == PWV_PREC_F16X3) return launch_layer_f16x3_stream(lp, *st, g8, s);
+        const dim3 grid(g8 * lp.G);
+        if (lp.packed_head[0]) hipLaunchKernelGGL((layer_f32_stream_kernel<false, true>), grid, dim3(512), 0, s, lp, *st);
+        else if (lp.x_first) hipLaunchKernelGGL((layer_f32_stream_kernel<true, false>), grid, dim3(512), 0, s, lp, *st);
+        else hipLaunchKernelGGL((layer_f32_stream_kernel<false, false>), grid, dim3(512), 0, s, lp, *st);
+        PWV_CHECK_HIP(hipGetLastError());
+        return PWV_OK;
+    }
     if (a->precision == PWV_PREC_F16X3) return launch_layer_f16x3(lp, any_skip, cond, gated, g8, s);
     if (a->precision == PWV_PREC_F16) {
         PWV_CHECK_ARG(!any_skip, "pwv_wavenet_layer_f32: PWV_PREC_F16 does not support skip accumulation");
@@ -804,6 +557,67 @@ int pwv_wavenet_layer_f32(const pwv_layer_args* a, pwv_stream_t stream) {
     }
     if (cond) return gated ? launch_layer<false, true, true>(lp, g8, s) : launch_layer<false, true, false>(lp, g8, s);
     return gated ? launch_layer<false, false, true>(lp, g8, s) : launch_layer<false, false, false>(lp, g8, s);
+}
+
+// pwv_stream_args as far as the caller's struct_size reaches (the rest zero) and the kernels' view of it; returns why not, or NULL
+static const char* stream_args(const pwv_stream_args* sa, pwv_stream_args& out, StreamParams& st) {
+    if (!sa) return "args is NULL";
+    if (sa->struct_size < offsetof(pwv_stream_args, carry_tab) || sa->struct_size > 4096) return "struct_size does not cover the history fields";
+    out = pwv_stream_args{};
+    memcpy(&out, sa, sa->struct_size < sizeof(out) ? sa->struct_size : sizeof(out));
+    if (!out.hist_rd || !out.hist_wr || !out.slot_tab) return "NULL history / slot table";
+    if (out.block_stride == 0 || out.block_stride % 4) return "block_stride must be a positive multiple of 4 floats";
+    st.hist_rd = out.hist_rd;
+    st.hist_wr = out.hist_wr;
+    st.slot_tab = out.slot_tab;
+    st.block_stride = (long long)out.block_stride;
+    for (int g = 0; g < PWV_MAX_NETS; ++g) st.row_off[g] = (long long)out.row_off[g];
+    st.scalar_off = (long long)out.scalar_off;
+    return nullptr;
+}
+
+extern "C" {
+
+int pwv_wavenet_layer_f32(const pwv_layer_args* a, pwv_stream_t stream) { return layer_call(a, nullptr, stream); }
+
+int pwv_wavenet_layer_stream_f32(const pwv_layer_args* a, const pwv_stream_args* sa, pwv_stream_t stream) {
+    PWV_CHECK_ARG(a, "pwv_wavenet_layer_stream_f32: args is NULL");
+    pwv_stream_args v;
+    StreamParams st{};
+    const char* why = stream_args(sa, v, st);
+    PWV_CHECK_ARG(!why, "pwv_wavenet_layer_stream_f32: %s", why);
+    PWV_CHECK_ARG(a->precision == PWV_PREC_F32 || a->precision == PWV_PREC_F16X3,
+                  "pwv_wavenet_layer_stream_f32: PWV_PREC_F32 / PWV_PREC_F16X3 only (the fp16 storage mode has no streaming form)");
+    PWV_CHECK_ARG(a->G >= 1 && a->G <= PWV_MAX_NETS && a->dilation >= 1 && a->T >= 1, "pwv_wavenet_layer_stream_f32: bad G / dilation / T");
+    PWV_CHECK_ARG(!a->cond && a->cond_channels == 0, "pwv_wavenet_layer_stream_f32: per-sample conditioning has no streaming form");
+    const long long hist_rows = ((long long)a->dilation + 31) / 32 * 32;
+    for (int g = 0; g < a->G; ++g) {
+        PWV_CHECK_ARG(!a->skip[g], "pwv_wavenet_layer_stream_f32: skip accumulation has no streaming form");
+        PWV_CHECK_ARG(!a->x_first || a->first_fold[g], "pwv_wavenet_layer_stream_f32: layer 0 streams in its folded form only (first_fold)");
+        PWV_CHECK_ARG(a->x_first || (v.row_off[g] % 4 == 0 && v.row_off[g] + (size_t)hist_rows * 64 <= v.block_stride),
+                      "pwv_wavenet_layer_stream_f32: row_off[%d] + round32(dilation) rows leave the history block", g);
+        for (int o = 0; o < g && !a->x_first; ++o)
+            PWV_CHECK_ARG(v.row_off[o] + (size_t)hist_rows * 64 <= v.row_off[g] || v.row_off[g] + (size_t)hist_rows * 64 <= v.row_off[o],
+                          "pwv_wavenet_layer_stream_f32: the nets' row histories overlap");
+    }
+    PWV_CHECK_ARG(!a->x_first || v.scalar_off + (size_t)a->dilation + 1 <= v.block_stride,
+                  "pwv_wavenet_layer_stream_f32: scalar_off + dilation + 1 scalars leave the history block");
+    if (a->head_packed[0]) PWV_CHECK_ARG(a->out_mode == PWV_OUT_GATED && !a->x_first, "pwv_wavenet_layer_stream_f32: a fused head needs out_mode PWV_OUT_GATED");
+    else PWV_CHECK_ARG(a->out_mode == PWV_OUT_RESIDUAL, "pwv_wavenet_layer_stream_f32: without a fused head the streaming layer is out_mode PWV_OUT_RESIDUAL");
+    return layer_call(a, &st, stream);
+}
+
+int pwv_stream_carry_f32(const pwv_stream_args* sa, int N, int T, pwv_stream_t stream) {
+    pwv_stream_args v;
+    StreamParams st{};
+    const char* why = stream_args(sa, v, st);
+    PWV_CHECK_ARG(!why, "pwv_stream_carry_f32: %s", why);
+    PWV_CHECK_ARG(sa->struct_size >= sizeof(pwv_stream_args) && v.carry_tab && v.n_carry >= 1 && v.n_carry <= 65535,
+                  "pwv_stream_carry_f32: carry_tab / n_carry missing");
+    PWV_CHECK_ARG(N >= 1 && N <= 65535 && T >= 1, "pwv_stream_carry_f32: bad N / T");
+    hipLaunchKernelGGL(stream_carry_kernel, dim3(v.n_carry, N), dim3(256), 0, (hipStream_t)stream, st, v.carry_tab, T);
+    PWV_CHECK_HIP(hipGetLastError());
+    return PWV_OK;
 }
 
 int pwv_wavenet_head_f32(const pwv_head_args* a, pwv_stream_t stream) {

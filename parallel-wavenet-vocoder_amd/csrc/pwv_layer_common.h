@@ -57,6 +57,22 @@ struct LayerParams {
     int* range_flag;                        // ... else *range_flag = 1 (pinned host memory); NULL = no check
 };
 
+// ---- streaming (include/pwv_hip.h, pwv_stream_args) ------------------------------------------------------------------
+// A chunk of T rows per utterance continues a session: rows with t < dilation read their look-back from the session's HISTORY of
+// this layer's input instead of zeros, and the chunk's last rows become the next history.  A history block (one session, one
+// generation) holds, per layer with a row input, a tile32 buffer of round32(d) rows x 64 (row k = the input at chunk time k - d) at
+// float offset row_off[net], and per flow the d0 + 1 scalars x[-(d0 + 1)] .. x[-1] of layer 0's input at scalar_off.
+// Utterance n of the launch reads block slot_tab[2n] and writes block slot_tab[2n + 1] (never the same: a chunk shorter than the
+// dilation would race; the rows of the old block that survive are moved by stream_carry_kernel).
+struct StreamParams {
+    const float* hist_rd;
+    float* hist_wr;
+    const int* slot_tab;
+    long long block_stride;                 // floats between two blocks
+    long long row_off[PWV_MAX_NETS];
+    long long scalar_off;
+};
+
 // exact n / d for n < 2^31 (Granlund-Montgomery): l = ceil(log2 d), magic = ceil(2^(31+l) / d), shift = l - 1
 inline void make_magic(unsigned d, unsigned& magic, unsigned& shift) {
     if (d <= 1) { magic = 0; shift = 0; return; }
@@ -309,6 +325,8 @@ __device__ __forceinline__ void gemm_groups(const float* lds, int base, int lane
 
 // launchers of the split-fp16 variants (pwv_layer_f16.hip)
 int launch_layer_f16x3(const LayerParams& lp, bool skip, bool cond, bool gated, int per_net, hipStream_t s);
+// ... and of their streaming forms: layer 0 folded (lp.x_first), the last layer + head (lp.packed_head), else a plain residual layer
+int launch_layer_f16x3_stream(const LayerParams& lp, const StreamParams& st, int per_net, hipStream_t s);
 int launch_head_f16x3(const HeadParams& hp, bool from_gated, int grid, hipStream_t s);
 int launch_pack_layer_f16x3(const float* filter, const float* gate, const float* dense, const float* dense_bias,
                             const float* skip, const float* skip_bias, const float* gc_filter, const float* gc_gate,

@@ -1413,3 +1413,73 @@ def _run_stack_layers(path: _Path, nets, plans, projs, bufs, outs, x, x_limit, c
     if path.two:
         for g in range(2):
             main.wait_stream(side[g])
+
+
+# ---- streaming: a flow on one CHUNK of N sessions (include/pwv_hip.h "STREAMING"; stream.StreamingVocoder owns the sessions) ---------
+def stream_refusal(nets, cond, precision: Optional[str] = None) -> Optional[str]:
+    """Why a flow (its nets) has no streaming form -- or None.  The per-layer kernels stream in three forms only: layer 0 folded onto
+    its scalar input, a plain residual layer, the last layer with the head fused behind it."""
+    net0 = nets[0]
+    if any(getattr(n, 'normalize', None) == 'in' for n in nets):
+        return "instance normalisation ('in'): its statistics span the whole time axis"
+    if cond is not None and not isinstance(cond, RepeatedCondition):
+        return 'per-sample (transposed-conv) conditioning'
+    if net0.use_skip_connection:
+        return 'skip accumulation (use_skip_connection)'
+    if (precision or net0.precision or DEFAULT_PRECISION) == 'f16':
+        return "precision 'f16' (the fp16 storage mode)"
+    if not (len(nets) == 2 and net0.out_channels == 1 and net0.in_channels == 1 and not net0.normalize and len(net0.dilations) >= 2
+            and all(n.fused_supported(cond) for n in nets) and all(_same_structure(net0, n) for n in nets)
+            and all(n.precision == net0.precision for n in nets)):
+        return 'a net outside the fused shape (two scalar-input nets per flow, W = 2, R = D = 64, S = 128, no normaliser, at least 2 layers)'
+    if not (FOLD_FIRST and FUSE_FIRST and FUSE_HEAD):
+        return 'PWV_FOLD_FIRST=0 / FUSE_FIRST / FUSE_HEAD off: layer 0 streams folded and the head fused only'
+    return None
+
+
+def run_flow_stream(nets: Sequence, x: torch.Tensor, cond, precision: Optional[str], hist: _lib.StreamArgs, scalar_off: int,
+                    row_off) -> torch.Tensor:
+    """One IAF flow on a chunk: x [N, T, 1] = the T samples that follow what each of the N sessions has seen, `cond` the chunk's own
+    frames (a RepeatedCondition of T / hop + 1 frames per session).  L streaming layer launches of both nets (G = 2) on the current
+    stream, then the affine.  `hist` carries the history blocks and the slot table of the call (read / written block per session);
+    `scalar_off` and `row_off[g][j]` (j >= 1) say where this flow's histories lie in a block.  Only enqueues, like run_flow; the
+    written blocks become the sessions' state when the caller flips their generation."""
+    why = stream_refusal(nets, cond, precision)
+    if why is not None:
+        raise _lib.PwvError('run_flow_stream: no streaming form: ' + why)
+    prec = PRECISIONS[precision or DEFAULT_PRECISION]
+    x = _require_cuda_f32(x, 'input')
+    net0 = nets[0]
+    n, t, _ = x.shape
+    mode, cond_geom, _ = _check_condition(net0, cond, x)
+    plans = [get_plan(net, mode, prec) for net in nets]
+    if prec == _lib.PREC_F16X3 and not all(p.f16x3_ok and p.x_limit > 0 for p in plans):
+        key = tuple(net.full_scope for net in nets)      # (as _run_nets: weights beyond fp16's range run in exact fp32)
+        if key not in _range_warned:
+            _range_warned.add(key)
+            import warnings
+            warnings.warn("pwv: weights of %s exceed the range of the split-fp16 arithmetic; using precision 'f32' for it" % (key,))
+        return run_flow_stream(nets, x, cond, 'f32', hist, scalar_off, row_off)
+    if any(p.first_fold is None for p in plans):
+        raise _lib.PwvError('run_flow_stream: no streaming form: layer 0 has no folded form for these weights')
+    x_limit = min(p.x_limit for p in plans)
+    projs = _projections(cond, mode, plans, precision, None)
+    lib, s = _lib.lib(), _stream()
+    G, L = len(plans), plans[0].n_layers
+    bufs = [[torch.empty((lib.pwv_tile32_floats(n * t, 64),), dtype=torch.float32, device=x.device) for _ in range(2)] for _ in plans]
+    outs = [torch.empty((n, t, 1), dtype=torch.float32, device=x.device) for _ in plans]
+    for j in range(L):
+        la = _layer_args(net0, plans, projs, projs[0].stride(0), cond_geom, bufs, j, (j + 1) & 1, j & 1, x)
+        la.out_mode = _lib.OUT_GATED if j == L - 1 else _lib.OUT_RESIDUAL
+        if j == 0:
+            _set_x_first(la, plans, x, x_limit)
+            hist.scalar_off = scalar_off
+        else:
+            for g in range(G):
+                hist.row_off[g] = row_off[g][j]
+        if j == L - 1:
+            for g in range(G):
+                la.head_packed[g], la.head_out[g] = plans[g].packed_head.data_ptr(), outs[g].data_ptr()
+            la.head_q = 1
+        check(lib.pwv_wavenet_layer_stream_f32(ctypes.byref(la), ctypes.byref(hist), s), 'pwv_wavenet_layer_stream_f32')
+    return iaf_affine_op(x, outs[0], outs[1], 1)

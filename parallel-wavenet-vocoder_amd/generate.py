@@ -12,7 +12,7 @@ follow from the platform, not from the math:
     TensorBoard audio summaries, generate.py:71-73);
   * `data_path: 'synthetic'` (bench cases) or a glob of .npy mel files replaces the wav dataset;
     wav input uses the torch STFT front-end in audio_frontend.py.
-CLI (python-fire style, fire itself is not installed):  python -m pwv_amd.generate <case> [--ckpt=..] [--debug] [--varlen [--seed=S]]
+CLI (python-fire style, fire itself is not installed):  python -m pwv_amd.generate <case> [--ckpt=..] [--debug] [--varlen [--seed=S]] [--stream=FRAMES]
 """
 from __future__ import absolute_import, division, print_function
 
@@ -139,7 +139,7 @@ def _load_mels_varlen(data_path, batch_size, device):
     return mels
 
 
-def generate(case='default', ckpt=None, debug=False, varlen=False, seed=None):
+def generate(case='default', ckpt=None, debug=False, varlen=False, seed=None, stream=None):
     '''
     :param case: experiment case name
     :param ckpt: checkpoint to load model
@@ -148,7 +148,15 @@ def generate(case='default', ckpt=None, debug=False, varlen=False, seed=None):
         utterance at hp.generate.length; writes pred_i.wav at each length.
     :param seed: (with varlen) every utterance draws its noise from stream `seed` at counter 0, so a file's audio depends only on
         its mel and the seed -- not on the other files of the run or their order.
+    :param stream: vocode every input at its own length as a STREAM (IAFVocoder.open_stream): one session per input, fed in pushes
+        of `stream` mel frames; writes the files --varlen writes.
     '''
+    if stream is not None:
+        stream = int(stream)
+        if stream < 1:
+            raise ValueError('--stream must be a number of frames >= 1, got %d' % stream)
+        if varlen or seed is not None:
+            raise ValueError('--stream excludes --varlen / --seed')
     if seed is not None:
         if not varlen:
             raise ValueError('--seed applies to --varlen (one noise stream per utterance)')
@@ -167,12 +175,12 @@ def generate(case='default', ckpt=None, debug=False, varlen=False, seed=None):
     batch_size, length = hp.generate.batch_size, hp.generate.length
     world, rank = int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('RANK', '0'))
     if world > 1:
-        if varlen:
-            raise ValueError('--varlen runs on one GPU (a packed batch is not sharded over ranks)')
+        if varlen or stream:
+            raise ValueError('--varlen / --stream run on one GPU (a packed batch or a set of sessions is not sharded over ranks)')
         # one process per GPU (torchrun): utterances -- or, for a batch smaller than the world, time slices -- shard over
         # the ranks; rank 0 reads the inputs and writes the outputs
         return _generate_over_ranks(store, batch_size, length, device, logdir, ckpt, debug)
-    if varlen:
+    if varlen or stream:
         gt_wav, melspec = None, _load_mels_varlen(hp.data_path, batch_size, device)
         batch_size, length = 1, sum(int(m.shape[0] - 1) * hp.signal.hop_length for m in melspec)     # (the timing line: all samples)
     else:
@@ -195,7 +203,9 @@ def generate(case='default', ckpt=None, debug=False, varlen=False, seed=None):
     # launches, a forward that left the range of the split-fp16 arithmetic in exact fp32 -- on the same noise
     # (engine.verified_call); what comes back is what the reference's fp32 sess.run would have produced, or an exception.
     # verify=True is EXPLICIT: it outranks PWV_ASYNC=1 (whose default is enqueue-only) -- nothing unverified is written to disk
-    if varlen:
+    if stream:
+        pred = _generate_stream(model, melspec, stream)
+    elif varlen:
         pred = model.generate_varlen(melspec, verify=True, seeds=None if seed is None else [seed] * len(melspec))
     else:
         pred = model(gt_wav, melspec, is_training=False, verify=True)
@@ -218,7 +228,7 @@ def generate(case='default', ckpt=None, debug=False, varlen=False, seed=None):
         torch.cuda.synchronize()
         ms = e0.elapsed_time(e1)
         print('forward: %.2f ms, %.3g samples/s (first call includes weight packing)' % (ms, batch_size * length / ms * 1e3))
-    if varlen:
+    if varlen or stream:
         pred_wav = [p.cpu().numpy() for p in pred]
         _write_outputs_varlen(pred_wav, logdir)
         print('Done.')
@@ -227,6 +237,26 @@ def generate(case='default', ckpt=None, debug=False, varlen=False, seed=None):
     _write_outputs(pred_wav, logdir)
     print('Done.')
     return pred_wav
+
+
+def _generate_stream(model, mels, frames):
+    """--stream: input i is session i of one StreamingVocoder; every tick gives each unfinished session its next `frames` frames (the
+    rest at its end).  Sessions that get the same number of frames in the same state share a push (verify=True: explicit, as above).
+    Returns the [len_i, 1] waveforms."""
+    s = model.open_stream(slots=len(mels))
+    pos, outs = [0] * len(mels), [[] for _ in mels]
+    while any(p < m.shape[0] for p, m in zip(pos, mels)):
+        groups = {}
+        for i, m in enumerate(mels):
+            f = min(frames, m.shape[0] - pos[i])
+            if f > 0:
+                groups.setdefault((f, pos[i] == 0), []).append(i)
+        for (f, _), slots in sorted(groups.items()):
+            got = s.push(torch.stack([mels[i][pos[i]:pos[i] + f] for i in slots]), slots=slots, verify=True)
+            for k, i in enumerate(slots):
+                outs[i].append(got[k])
+                pos[i] += f
+    return [torch.cat(o) for o in outs]
 
 
 def _write_outputs(pred_wav, logdir):

@@ -111,36 +111,41 @@ class IAFVocoder(object):
                 raise ValueError('z must be [%d, %d, 1], got %s' % (n, self.length, tuple(noise.shape)))
         return engine.verified_call(lambda prec: self._forward(store, melspec, noise, is_training, name, prec or self.precision), verify)
 
+    def _flows(self, store, is_training, precision):
+        """The IAF flows of the model (models.py:36-67), set up inside the caller's variable scope (that opens no scope of theirs)."""
+        shared = bool(hp.model.get('shared_nets', False))
+        flows = []
+        for i in range(hp.model.n_iaf):
+            with variable_scope('iaf{}'.format(i)):
+                kwargs = dict(
+                    batch_size=self.batch_size,
+                    dilations=hp.model.dilations[i],
+                    filter_width=hp.model.filter_width,
+                    residual_channels=hp.model.residual_channels,
+                    dilation_channels=hp.model.dilation_channels,
+                    skip_channels=hp.model.skip_channels,
+                    use_biases=hp.model.use_biases,
+                    condition_channels=hp.model.condition_channels,
+                    use_skip_connection=hp.model.use_skip_connection,
+                    is_training=is_training,
+                    normalize=hp.model.normalize_wavenet,
+                    store=store, precision=precision)
+                if shared:   # build extension: BASELINE.json configs[1]
+                    net = WaveNet(quantization_channels=2, input_channels=1, name='shared', **kwargs)
+                    iaf = SharedIAFLayer(batch_size=hp.train.batch_size, net=net)
+                else:
+                    # quantization_channels=1: the output is a real value, models.py:42,57
+                    scaler = WaveNet(quantization_channels=1, name='scalar', **kwargs)
+                    shifter = WaveNet(quantization_channels=1, name='shifter', **kwargs)
+                    iaf = LinearIAFLayer(batch_size=hp.train.batch_size, scaler=scaler, shifter=shifter)
+                flows.append(iaf)
+        return flows
+
     def _forward(self, store, melspec, input, is_training, name, precision, length=None, geom=None):
         """models.py:23-78: condition, then the flows; only enqueues.  `length` overrides the constructor's (the padded form of a
         packed batch); with `geom` (an engine.VarlenGeometry) `melspec` is the packed [1, F, n_mels] and `input` the packed [R, 1]."""
-        shared = bool(hp.model.get('shared_nets', False))
         with variable_scope(name):
-            flows = []
-            for i in range(hp.model.n_iaf):
-                with variable_scope('iaf{}'.format(i)):
-                    kwargs = dict(
-                        batch_size=self.batch_size,
-                        dilations=hp.model.dilations[i],
-                        filter_width=hp.model.filter_width,
-                        residual_channels=hp.model.residual_channels,
-                        dilation_channels=hp.model.dilation_channels,
-                        skip_channels=hp.model.skip_channels,
-                        use_biases=hp.model.use_biases,
-                        condition_channels=hp.model.condition_channels,
-                        use_skip_connection=hp.model.use_skip_connection,
-                        is_training=is_training,
-                        normalize=hp.model.normalize_wavenet,
-                        store=store, precision=precision)
-                    if shared:   # build extension: BASELINE.json configs[1]
-                        net = WaveNet(quantization_channels=2, input_channels=1, name='shared', **kwargs)
-                        iaf = SharedIAFLayer(batch_size=hp.train.batch_size, net=net)
-                    else:
-                        # quantization_channels=1: the output is a real value, models.py:42,57
-                        scaler = WaveNet(quantization_channels=1, name='scalar', **kwargs)
-                        shifter = WaveNet(quantization_channels=1, name='shifter', **kwargs)
-                        iaf = LinearIAFLayer(batch_size=hp.train.batch_size, scaler=scaler, shifter=shifter)
-                    flows.append(iaf)
+            flows = self._flows(store, is_training, precision)
             all_nets = [net for iaf in flows for net in iaf.nets()]
             with variable_scope('cond'):
                 # (the flows are set up first -- that opens no variable scope of theirs, models.py:26-29 stays ahead of :36-67 in the
@@ -237,6 +242,20 @@ class IAFVocoder(object):
             out = self._forward(store, geom.pad_frames(mel), geom.pad_rows(noise), False, 'iaf_vocoder', precision, length=geom.max_len)
             return geom.unpad_rows(out)
         return self._forward(store, mel.unsqueeze(0), noise, False, 'iaf_vocoder', precision, length=geom.rows, geom=geom)
+
+    # -- streaming ("Streaming") ---------------------------------------------------------------------
+    def open_stream(self, slots=1, hist_alloc=None):
+        """A stream.StreamingVocoder over this model's weights: `slots` independent sessions that take their mel frames in pushes
+        and return each push's samples -- bit for bit the samples the one-shot forward gives for the whole utterance, at the cost
+        of the pushed rows alone (every layer keeps the last `dilation` rows of its input per session).  The constructor's
+        `batch_size` and `length` are not used.  Pays when many sessions advance per call (32 sessions x 1600 samples: 2.57x faster
+        than overlap-and-discard).  One session (measured at chunks of 800 .. 8000 samples), two, or four with chunks under 1600
+        samples: overlap-and-discard through __call__ (timeshard.chain_halo samples recomputed per chunk, one persistent launch per
+        flow) is quicker than the ~65 launches of a push, which the host's enqueue bounds at ~0.7 ms; the crossover is at four
+        sessions x 1600 samples -- DESIGN.md section 9 "Streaming" has the measured table.  `hist_alloc` (tests):
+        called with a float count, returns the zero-filled float32 buffer the histories live in."""
+        from .stream import StreamingVocoder
+        return StreamingVocoder(self, slots, hist_alloc=hist_alloc)
 
     def verify(self):
         """For callers of the enqueue-only form (verify=False / PWV_ASYNC=1): wait for the enqueued forwards and raise

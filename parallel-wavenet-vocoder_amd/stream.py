@@ -1,0 +1,298 @@
+"""Streaming generation: audio out while the mel frames are still coming in ("Streaming").
+
+The model is a chain of causal FIR layers: a layer with dilation d needs, besides the chunk it is given, only the last d rows of
+its own input from before the chunk.  A StreamingVocoder keeps those rows per layer and session (the HISTORY; layout in
+include/pwv_hip.h, "STREAMING"), so a push costs exactly its own rows, and -- every row going through the instructions of the
+one-shot per-layer kernels in their order -- the pushes of a session concatenate to ``IAFVocoder(1, L)(None, mel, z=z)`` bit for bit.
+
+State per session: two GENERATIONS of the history block (a push reads one and writes the other; the flip is the commit), the last
+mel frame it was given (the first frame of the next chunk: sample t is conditioned on frame (t + hop/2) // hop), its noise seed
+and the number of samples emitted.  Its size does not depend on the chunk length.
+"""
+from __future__ import annotations
+
+import ctypes
+import os
+from typing import List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib, engine
+from .hparam import hparam as hp
+from .variables import get_default_store, variable_scope
+
+
+def round32(d: int) -> int:
+    return (int(d) + 31) // 32 * 32
+
+
+class HistoryLayout:
+    """Where every history of the model lies inside a block (float offsets): per flow the d0 + 1 scalars of layer 0's input
+    (padded to 64 floats), then per net and layer j >= 1 a tile32 buffer of round32(d_j) rows x 64 channels.  `carry` lists every
+    history as (offset, rows, floats per row): the table of pwv_stream_carry_f32."""
+
+    def __init__(self, dilations: Sequence[Sequence[int]], nets_per_flow: int = 2):
+        self.scalar_off: List[int] = []
+        self.row_off: List[List[List[int]]] = []       # [flow][net][layer] (layer 0: unused, -1)
+        self.carry: List[tuple] = []
+        off = 0
+        for dil in dilations:
+            self.scalar_off.append(off)
+            self.carry.append((off, int(dil[0]) + 1, 1))
+            off += (int(dil[0]) + 1 + 63) // 64 * 64
+            per_net = []
+            for _ in range(nets_per_flow):
+                offs = [-1]
+                for d in dil[1:]:
+                    offs.append(off)
+                    self.carry.append((off, int(d), 64))
+                    off += round32(d) * 64
+                per_net.append(offs)
+            self.row_off.append(per_net)
+        self.block_floats = off
+        self.max_rows = max(rows for _, rows, _ in self.carry)
+
+
+def advance_history(old: np.ndarray, chunk: np.ndarray) -> np.ndarray:
+    """(numpy restatement, tests) The history of a layer after a chunk: the last len(old) rows of old ++ chunk."""
+    return np.concatenate([old, chunk])[len(chunk):]
+
+
+def history_sources(length: int, T: int):
+    """(numpy restatement of the kernels' index arithmetic, tests) For a history of `length` rows and a chunk of T rows: where every
+    row k of the NEXT history comes from -- ('carry', k + T) = row k + T of the old history (moved by the carry launch, k < length - T)
+    or ('chunk', t) = the chunk's row t, stored by the layer launch at k = t + length - T (t >= T - length)."""
+    src = {}
+    for k in range(max(length - T, 0)):
+        src[k] = ('carry', k + T)
+    for t in range(T):
+        k = t + length - T
+        if k >= 0:
+            assert k not in src
+            src[k] = ('chunk', t)
+    return [src[k] for k in range(length)]
+
+
+def push_samples(frames: int, fresh: bool, hop: int) -> int:
+    """Samples a push of `frames` frames yields: a fresh session keeps its last frame back ((f - 1) * hop), a running one has the
+    kept frame in front (f * hop)."""
+    return (frames - (1 if fresh else 0)) * hop
+
+
+class StreamingVocoder(object):
+    """IAFVocoder.open_stream(slots): `slots` independent sessions over the model's weights.
+
+        wav = s.push(mel, slots=[0, 3])      # mel [n, f, n_mels] -> wav [n, samples, 1]
+        s.reset(3); s.emitted(0); st = s.state(0); s.load_state(1, st)
+
+    New weights in the store (store.version) re-plan the kernels' packed weights at the next push; open sessions KEEP their
+    history -- it is activations, not weights (what they then produce is the new weights' continuation of the old context).
+
+    Refused with a PwvError that names the reason (nothing is launched): per-sample (transposed-conv) conditioning, skip
+    accumulation, precision 'f16', any normaliser -- instance normalisation's statistics span the whole time axis --, shared nets,
+    nets outside the fused shape."""
+
+    def __init__(self, model, slots: int, hist_alloc=None):
+        m = hp.model
+        why = None
+        if 'in' in (m.get('normalize'), m.get('normalize_cond'), m.get('normalize_wavenet')):
+            why = "instance normalisation ('in'): its statistics span the whole time axis, a chunk does not have them"
+        elif m.cond_upsample_method != 'repeat':
+            why = "per-sample (transposed-conv) conditioning: only 'repeat' conditioning streams (frames enter at frame rate)"
+        elif m.use_skip_connection:
+            why = 'skip accumulation (use_skip_connection: True): the per-layer kernels stream without skip sums only'
+        elif (model.precision or engine.DEFAULT_PRECISION) == 'f16':
+            why = "precision 'f16': the fp16 storage mode has no streaming kernels ('f16x3' and 'f32' have)"
+        elif m.get('normalize') or m.get('normalize_cond') or m.get('normalize_wavenet'):
+            why = 'a normaliser (normalize / normalize_cond / normalize_wavenet): outside the fused shape that streams'
+        elif m.get('shared_nets', False):
+            why = 'shared nets: outside the fused shape that streams (two scalar-input nets per flow)'
+        elif not (m.filter_width == 2 and m.residual_channels == 64 and m.dilation_channels == 64 and m.skip_channels == 128
+                  and all(len(d) >= 2 for d in m.dilations[:m.n_iaf])):
+            why = 'nets outside the fused shape (W = 2, R = D = 64, S = 128, at least 2 layers per net)'
+        if why is not None:
+            raise _lib.PwvError('open_stream: this model has no streaming form: ' + why)
+        if int(slots) < 1:
+            raise ValueError('slots must be >= 1, got %r' % (slots,))
+        self.model = model
+        self.n_slots = int(slots)
+        self.hop = int(hp.signal.hop_length)
+        self.n_mels = int(hp.signal.n_mels)
+        self.layout = HistoryLayout([list(d) for d in m.dilations[:m.n_iaf]])
+        store = model.store or get_default_store()
+        self.device = store.device
+        floats = 2 * self.n_slots * self.layout.block_floats
+        self._hist = (hist_alloc(floats) if hist_alloc is not None
+                      else torch.zeros((floats,), dtype=torch.float32, device=self.device)).view(2 * self.n_slots, self.layout.block_floats)
+        self._carry_tab = torch.tensor([[o, r, w, 0] for o, r, w in self.layout.carry], dtype=torch.int32).to(self.device)
+        self._kept = torch.zeros((self.n_slots, self.n_mels), dtype=torch.float32, device=self.device)
+        self._gen = [0] * self.n_slots              # the generation a push READS
+        self._running = [False] * self.n_slots      # a frame is kept (the slot has been pushed to since its last reset)
+        self._emitted = [0] * self.n_slots
+        self._seed: List[Optional[int]] = [None] * self.n_slots
+        self._pending = None                        # the commit of an un-verified push (verify=False / PWV_ASYNC=1)
+
+    # -- bookkeeping -----------------------------------------------------------------------------------------------------
+    def _slot(self, slot) -> int:
+        s = int(slot)
+        if not 0 <= s < self.n_slots:
+            raise ValueError('slot %r out of range (0 .. %d)' % (slot, self.n_slots - 1))
+        return s
+
+    def _settled(self, what: str) -> None:
+        if self._pending is not None:
+            raise _lib.PwvError('%s: the previous push was only enqueued (verify=False / PWV_ASYNC=1): call verify() first' % what)
+
+    def emitted(self, slot) -> int:
+        """Samples produced so far by `slot` since its last reset."""
+        return self._emitted[self._slot(slot)]
+
+    def state_bytes(self, slot=0) -> int:
+        """Bytes of device memory one session holds: two generations of the history block and the kept frame."""
+        self._slot(slot)
+        return 2 * self.layout.block_floats * 4 + self.n_mels * 4
+
+    def reset(self, slot, seed: Optional[int] = None) -> None:
+        """`slot` starts a new utterance: zero history (the one-shot left edge), no kept frame, emitted = 0.  `seed`: the noise
+        stream of the new utterance (else given at its first push, else drawn from the OS)."""
+        self._settled('reset')
+        s = self._slot(slot)
+        self._hist[2 * s:2 * s + 2].zero_()
+        self._gen[s], self._running[s], self._emitted[s] = 0, False, 0
+        self._seed[s] = None if seed is None else self._check_seed(seed)
+
+    @staticmethod
+    def _check_seed(v) -> int:
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < (1 << 64):
+            raise ValueError('a seed must be an integer in [0, 2**64), got %r' % (v,))
+        return int(v)
+
+    def state(self, slot) -> dict:
+        """A copy of the session in `slot` (to park it, or to bring another stream to the same point): load_state takes it."""
+        self._settled('state')
+        s = self._slot(slot)
+        return {'hist': self._hist[2 * s + self._gen[s]].clone(), 'kept': self._kept[s].clone(), 'running': self._running[s],
+                'emitted': self._emitted[s], 'seed': self._seed[s], 'block_floats': self.layout.block_floats}
+
+    def load_state(self, slot, st: dict) -> None:
+        self._settled('load_state')
+        s = self._slot(slot)
+        if st['block_floats'] != self.layout.block_floats or st['kept'].numel() != self.n_mels:
+            raise ValueError('the state was taken from a model of another shape')
+        self._hist[2 * s + self._gen[s]].copy_(st['hist'])
+        self._kept[s].copy_(st['kept'])
+        self._running[s], self._emitted[s], self._seed[s] = bool(st['running']), int(st['emitted']), st['seed']
+
+    def verify(self) -> None:
+        """For pushes that only enqueued (verify=False / PWV_ASYNC=1): wait, raise PwvRangeError if the chunk left the range of the
+        split-fp16 arithmetic (the sessions then stand where they stood before the push: push the chunk again on a precision='f32'
+        stream of the same state), else advance the sessions."""
+        commit, self._pending = self._pending, None
+        engine.verify_enqueued('a streaming push')
+        if commit is not None:
+            commit()
+
+    # -- a push ----------------------------------------------------------------------------------------------------------
+    def push(self, mel, slots=None, z=None, seeds=None, verify=None):
+        """Give the sessions in `slots` (default: all) their next `f` mel frames, mel [n, f, n_mels]; returns their next samples
+        [n, samples, 1]: (f - 1) * hop for fresh sessions (the last frame is kept back: the samples around it need the frame after
+        it), f * hop afterwards.  All slots of a call get the same f and are in the same state (all fresh or all running).
+        ``z`` [n, samples, 1] is the chunk's noise; without it slot i draws from its own counter stream: ``seeds[i]`` (first push
+        after a reset; default: from the OS) at counter = samples emitted so far -- what IAFVocoder(1, L) with noise_seed = seeds[i],
+        noise_offset = 0 draws.  The model's own noise_offset does not move.
+
+        A push is a transaction and, by default, a verified call (engine.verified_call): the sessions advance only after the chunk
+        has completed in range; a chunk that trips the range guard of the split-fp16 arithmetic is rerun in exact fp32 from the same
+        pre-chunk state on the same noise (with the usual `pwv:` warning).  verify=False / PWV_ASYNC=1 only enqueue: call verify()
+        before the next push."""
+        self._settled('push')
+        slots = list(range(self.n_slots)) if slots is None else [self._slot(v) for v in slots]
+        n = len(slots)
+        if n == 0 or len(set(slots)) != n:
+            raise ValueError('slots must be a non-empty list of distinct slots, got %r' % (slots,))
+        mel = engine._require_cuda_f32(mel, 'mel')
+        if mel.dim() != 3 or mel.shape[0] != n or mel.shape[1] < 1 or mel.shape[2] != self.n_mels:
+            raise ValueError('mel must be [%d, f >= 1, %d], got %s' % (n, self.n_mels, tuple(mel.shape)))
+        running = [self._running[s] for s in slots]
+        if any(running) != all(running):
+            raise ValueError('the slots of one push must be in one state: all fresh or all running (got %r)' % (dict(zip(slots, running)),))
+        fresh = not running[0]
+        T = push_samples(mel.shape[1], fresh, self.hop)
+        if seeds is not None:
+            if z is not None:
+                raise ValueError('seeds and z exclude each other: seeds draw the noise, z is the noise')
+            if not fresh:
+                raise ValueError('seeds are given at a slot\'s first push (or reset): these slots are running')
+            seeds = [self._check_seed(v) for v in (seeds.tolist() if hasattr(seeds, 'tolist') else seeds)]
+            if len(seeds) != n:
+                raise ValueError('seeds holds %d values for %d slots' % (len(seeds), n))
+        if z is not None:
+            z = engine._require_cuda_f32(z, 'z')
+            if tuple(z.shape) != (n, T, 1):
+                raise ValueError('z must be [%d, %d, 1], got %s' % (n, T, tuple(z.shape)))
+        engine.raise_if_range_flag('an earlier call')
+        idx = torch.tensor(slots, dtype=torch.int64).to(self.device) if n != self.n_slots or slots != list(range(n)) else None
+        new_seeds = None
+        if z is None:
+            new_seeds = [self._seed[s] if self._seed[s] is not None else int.from_bytes(os.urandom(7), 'little') for s in slots]
+            if seeds is not None:
+                new_seeds = seeds
+        last = mel[:, -1]
+
+        def commit():
+            for i, s in enumerate(slots):
+                self._gen[s] ^= 1
+                self._running[s] = True
+                self._emitted[s] += T
+                if new_seeds is not None:
+                    self._seed[s] = new_seeds[i]
+            if idx is None:
+                self._kept.copy_(last)
+            else:
+                self._kept.index_copy_(0, idx, last)
+
+        if T == 0:            # one frame to a fresh slot: nothing to generate yet
+            commit()
+            return torch.empty((n, 0, 1), dtype=torch.float32, device=self.device)
+        kept = self._kept if idx is None else self._kept.index_select(0, idx)
+        frames = mel if fresh else torch.cat([kept[:, None], mel], dim=1)
+        if z is None:
+            cu = torch.arange(0, (n + 1) * T, T, dtype=torch.int32).pin_memory().to(self.device, non_blocking=True)
+            table = torch.tensor([[engine.as_int64_bits(sd), engine.as_int64_bits(self._emitted[s])] for sd, s in zip(new_seeds, slots)],
+                                 dtype=torch.int64).pin_memory().to(self.device, non_blocking=True)
+            z = engine.logistic_noise_packed_op(cu, table, n * T).view(n, T, 1)
+        # utterance i of the launches reads block 2 s + gen, writes block 2 s + 1 - gen
+        tab = torch.tensor([[2 * s + self._gen[s], 2 * s + 1 - self._gen[s]] for s in slots],
+                           dtype=torch.int32).pin_memory().to(self.device, non_blocking=True)
+        out = engine.verified_call(lambda prec: self._enqueue(prec or self.model.precision, frames, z, tab, T), verify)
+        verified = ((not engine.ASYNC) if verify is None else bool(verify)) and getattr(engine._tls, 'depth', 0) == 0
+        if verified and not torch.cuda.is_current_stream_capturing():
+            commit()
+        else:
+            self._pending = commit
+        return out
+
+    def _enqueue(self, precision, frames, z, tab, T):
+        """The chunk's launches on the current stream: the prologue on the chunk's frames, the carry-over of the histories the chunk
+        does not push out (one launch, only when T is below the largest history), then per flow L streaming layer launches and the
+        affine.  Reads the sessions' current generation, writes the other one: may be enqueued again from the same state."""
+        model = self.model
+        store = model.store or get_default_store()
+        lay = self.layout
+        sa = _lib.StreamArgs()
+        sa.hist_rd = sa.hist_wr = self._hist.data_ptr()
+        sa.block_stride, sa.slot_tab = lay.block_floats, tab.data_ptr()
+        sa.carry_tab, sa.n_carry = self._carry_tab.data_ptr(), len(lay.carry)
+        with variable_scope('iaf_vocoder'):
+            flows = model._flows(store, False, precision)
+            nets = [net for iaf in flows for net in iaf.nets()]
+            with variable_scope('cond'):
+                cond = model._condition(frames, False, strides=[4, 4, 5], store=store, precision=precision, nets=nets, length=T)
+            engine.project_all(nets, cond, precision=precision)
+            if T < lay.max_rows:
+                _lib.check(_lib.lib().pwv_stream_carry_f32(ctypes.byref(sa), frames.shape[0], T, engine._stream()), 'pwv_stream_carry_f32')
+            x = z
+            for i, iaf in enumerate(flows):
+                x = engine.run_flow_stream(iaf.nets(), x, cond, precision, sa, lay.scalar_off[i], lay.row_off[i])
+        return x

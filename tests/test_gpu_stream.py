@@ -1,0 +1,301 @@
+"""GPU: streaming generation (IAFVocoder.open_stream -> stream.StreamingVocoder, pwv_wavenet_layer_stream_f32).  The contract: for
+any schedule of chunk lengths (multiples of hop) the pushes of a session, concatenated, are torch.equal to the one-shot forward
+IAFVocoder(1, L)(None, mel, z=z) on its default route; a session's audio does not depend on its companions; a push is a transaction."""
+import numpy as np
+import pytest
+import torch
+
+from oracle import iaf_oracle as O
+from tests.util import TOL_F32, set_hparams, small_cfg
+
+pytestmark = pytest.mark.gpu
+
+
+def _small():
+    return small_cfg(dilations=[[1, 2, 4, 8], [1, 2, 4, 8, 16, 32]])
+
+
+def _model(gpu, cfg, precision=None, seed=2):
+    from pwv_amd.models import IAFVocoder
+    from pwv_amd.variables import VariableStore
+    set_hparams(cfg)
+    w = O.init_weights(cfg, seed=seed)
+    store = VariableStore(device=gpu)
+    store.load_dict(w)
+    return IAFVocoder(batch_size=1, length=80, store=store, precision=precision), w
+
+
+def _inputs(cfg, L, gpu, seed=0):
+    rng = np.random.default_rng(seed)
+    mel = rng.uniform(-1, 1, (L // cfg.hop_length + 1, cfg.n_mels)).astype(np.float32)
+    z = np.clip(rng.logistic(0, 1, (L, 1)), -20, 20).astype(np.float32)
+    return mel, z, torch.from_numpy(mel).to(gpu), torch.from_numpy(z).to(gpu)
+
+
+def _one_shot(model, mel_t, z_t=None, precision=None, seed=None):
+    from pwv_amd.models import IAFVocoder
+    L = (mel_t.shape[0] - 1) * 80
+    one = IAFVocoder(batch_size=1, length=L, store=model.store, precision=precision or model.precision)
+    if seed is not None:
+        one.noise_seed, one.noise_offset = seed, 0
+    return one(None, mel_t[None], is_training=False, z=None if z_t is None else z_t[None])[0]
+
+
+class _Feeder:
+    """Per slot: an utterance (mel, z) and a cursor; adv(slots, T) pushes the next T samples' worth of frames of those slots."""
+
+    def __init__(self, s, hop=80):
+        self.s, self.hop, self.utt, self.pos, self.out = s, hop, {}, {}, {}
+
+    def start(self, slot, mel_t, z_t=None):
+        self.utt[slot], self.pos[slot], self.out[slot] = (mel_t, z_t), 0, []
+
+    def adv(self, slots, T, **kw):
+        mels, zs = [], []
+        for sl in slots:
+            mel, z = self.utt[sl]
+            c = self.pos[sl]
+            f0 = 0 if c == 0 and not self.out[sl] else c // self.hop + 1
+            mels.append(mel[f0:(c + T) // self.hop + 1])
+            if z is not None:
+                zs.append(z[c:c + T])
+        got = self.s.push(torch.stack(mels), slots=slots, z=torch.stack(zs) if zs else None, **kw)
+        assert tuple(got.shape) == (len(slots), T, 1)
+        for i, sl in enumerate(slots):
+            self.out[sl].append(got[i])
+            self.pos[sl] += T
+        return got
+
+    def result(self, slot):
+        return torch.cat(self.out[slot])
+
+
+_RAGGED = [80, 2400, 560, 7200, 160, 4000, 80, 1600, 400, 7520]
+_ONE_SHOT = {}
+
+
+@pytest.mark.parametrize('schedule', [[1600] * 15, [4000] * 6, [400] * 60, _RAGGED], ids=['1600x15', '4000x6', '400x60', 'ragged'])
+@pytest.mark.parametrize('precision', ['f16x3', 'f32'])
+def test_chunks_equal_the_one_shot_forward_default_model(gpu, precision, schedule):
+    """Default model (max dilation 512), L = 24000, explicit z: chunks above every dilation, below the largest, ragged."""
+    cfg = O.ModelConfig()
+    L = 24000
+    assert sum(schedule) == L
+    model, _ = _model(gpu, cfg, precision)
+    _, _, mel_t, z_t = _inputs(cfg, L, gpu)
+    if precision not in _ONE_SHOT:
+        _ONE_SHOT[precision] = _one_shot(model, mel_t, z_t).clone()
+    s = model.open_stream(slots=1)
+    fd = _Feeder(s)
+    fd.start(0, mel_t, z_t)
+    for T in schedule:
+        fd.adv([0], T)
+    assert s.emitted(0) == L
+    got, want = fd.result(0), _ONE_SHOT[precision]
+    assert torch.equal(got, want), float((got - want).abs().max())
+
+
+def _small_wide():
+    # most dilations above the 80-sample chunk (every push carries most histories over), two that are no multiple of 32
+    return small_cfg(dilations=[[1, 96, 128, 256], [2, 64, 200, 512, 3, 160]])
+
+
+@pytest.mark.parametrize('config', [_small, _small_wide], ids=['small', 'small_wide'])
+@pytest.mark.parametrize('precision', ['f16x3', 'f32'])
+def test_one_frame_pushes_small_model(gpu, precision, config):
+    """Small configs, 80-sample chunks throughout (one-frame pushes): the one of tests/test_gpu_varlen.py, and one whose dilations
+    are mostly longer than the chunk (and whose first layers have dilations 1 and 2)."""
+    cfg = config()
+    L = 1600
+    model, _ = _model(gpu, cfg, precision)
+    _, _, mel_t, z_t = _inputs(cfg, L, gpu, seed=1)
+    s = model.open_stream(slots=1)
+    assert tuple(s.push(mel_t[None, :1], z=z_t[None, :0]).shape) == (1, 0, 1) and s.emitted(0) == 0      # one frame: stored only
+    outs = [s.push(mel_t[None, k:k + 1], z=z_t[None, 80 * (k - 1):80 * k]) for k in range(1, L // 80 + 1)]
+    got = torch.cat([o[0] for o in outs])
+    want = _one_shot(model, mel_t, z_t)
+    assert torch.equal(got, want), float((got - want).abs().max())
+
+
+@pytest.mark.parametrize('precision', ['f16x3', 'f32'])
+def test_stream_matches_oracle(gpu, precision):
+    """Two sessions against the fp64 oracle, the fp32 bar of every parity test (enqueue-only + verify(): no self-repair)."""
+    cfg = _small()
+    L = 800
+    model, w = _model(gpu, cfg, precision)
+    s = model.open_stream(slots=2)
+    fd = _Feeder(s)
+    ins = [_inputs(cfg, L, gpu, seed=10 + i) for i in range(2)]
+    for i in range(2):
+        fd.start(i, ins[i][2], ins[i][3])
+    for T in [160, 80, 400, 160]:
+        fd.adv([0, 1], T, verify=False)
+        s.verify()
+    for i in range(2):
+        want = O.iaf_vocoder_forward(w, ins[i][0][None], ins[i][1][None], cfg)[0]
+        err = float(np.abs(fd.result(i).cpu().numpy() - want).max())
+        print('stream vs oracle, %s, slot %d: %.3g' % (precision, i, err))
+        assert err <= TOL_F32, err
+
+
+def test_slots_are_independent(gpu):
+    """3 slots, different mels, advanced in different subsets per call, slot 2 reset half-way and restarted on another mel: every
+    finished utterance equals its own one-shot forward (and the abandoned one the prefix of its one-shot forward)."""
+    cfg = _small()
+    model, _ = _model(gpu, cfg)
+    s = model.open_stream(slots=3)
+    fd = _Feeder(s)
+    a, b, c, d = (_inputs(cfg, L, gpu, seed=20 + i) for i, L in enumerate([960, 960, 960, 480]))
+    fd.start(0, a[2], a[3]), fd.start(1, b[2], b[3]), fd.start(2, c[2], c[3])
+    fd.adv([0, 1, 2], 160)
+    fd.adv([2, 0], 80)
+    fd.adv([1], 240)
+    fd.adv([0, 1], 160)
+    part_c = fd.result(2)
+    s.reset(2)
+    assert s.emitted(2) == 0
+    fd.start(2, d[2], d[3])
+    fd.adv([2], 240)
+    fd.adv([0, 1, 2], 80)
+    fd.adv([2, 1], 160)          # d done (480)
+    fd.adv([0], 480)             # a done (960)
+    fd.adv([1], 160)             # b done (960)
+    assert [s.emitted(i) for i in range(3)] == [960, 960, 480]
+    for slot, u in ((0, a), (1, b), (2, d)):
+        want = _one_shot(model, u[2], u[3])
+        assert torch.equal(fd.result(slot), want), slot
+    assert torch.equal(part_c, _one_shot(model, c[2], c[3])[:240])
+
+
+def test_noise_contract(gpu):
+    """No z, seeds=[s_i]: slot i equals IAFVocoder(1, L) with noise_seed = s_i, noise_offset = 0; the model's own offset stays."""
+    cfg = _small()
+    L = 640
+    model, _ = _model(gpu, cfg)
+    model.noise_seed, model.noise_offset = 3, 17
+    s = model.open_stream(slots=2)
+    fd = _Feeder(s)
+    ins = [_inputs(cfg, L, gpu, seed=30 + i) for i in range(2)]
+    seeds = [5, (1 << 63) + 9]
+    for i in range(2):
+        fd.start(i, ins[i][2])
+    fd.adv([0, 1], 160, seeds=seeds)
+    for T in [80, 320, 80]:
+        fd.adv([0, 1], T)
+    assert model.noise_offset == 17
+    for i in range(2):
+        assert torch.equal(fd.result(i), _one_shot(model, ins[i][2], seed=seeds[i])), i
+
+
+def test_range_rerun_is_transactional(gpu):
+    """A stream whose middle chunk has mel * 1e5 (its last frame, the one kept for the next chunk, excepted): the chunk before it
+    is an undisturbed stream's; the tripped chunk warns and equals the same chunk pushed by a precision='f32' stream brought to the
+    same state; the stream goes on from the state the rerun left."""
+    cfg = _small()
+    model, _ = _model(gpu, cfg)
+    from pwv_amd.models import IAFVocoder
+    m32 = IAFVocoder(batch_size=1, length=80, store=model.store, precision='f32')
+    L = 720
+    _, _, mel_t, z_t = _inputs(cfg, L, gpu, seed=40)
+    mel_t = mel_t.clone()
+    mel_t[4:6] *= 1e5                      # frames 4, 5 of the chunk that brings frames 4, 5, 6
+    s = model.open_stream(slots=1)
+    first = s.push(mel_t[None, :4], z=z_t[None, :240])
+    assert torch.equal(first[0], _one_shot(model, mel_t[:4], z_t[:240]))
+    before = s.state(0)
+    with pytest.warns(UserWarning, match='rerun in exact fp32'):
+        tripped = s.push(mel_t[None, 4:7], z=z_t[None, 240:480])
+    assert s.emitted(0) == 480 and bool(torch.isfinite(tripped).all())
+    s32 = m32.open_stream(slots=1)
+    s32.load_state(0, before)
+    want = s32.push(mel_t[None, 4:7], z=z_t[None, 240:480])
+    assert torch.equal(tripped, want)
+    # ... and goes on: from the very state the fp32 rerun left
+    s2 = model.open_stream(slots=1)
+    s2.load_state(0, s32.state(0))
+    after = s.push(mel_t[None, 7:], z=z_t[None, 480:])
+    assert torch.equal(after, s2.push(mel_t[None, 7:], z=z_t[None, 480:])) and s.emitted(0) == L
+
+
+@pytest.mark.parametrize('precision', ['f16x3', 'f32'])
+def test_guard_bands_around_the_histories(gpu, precision):
+    """The histories allocated inside a NaN-filled buffer: after a ragged schedule with chunks of 80 and of 4000 samples on the
+    default model the bands are untouched, the blocks of a slot that was never pushed are still zero, the pushed slots equal their
+    one-shot forwards; and a session's state stays within 2 * sum round32(d_j) * 256 B + 64 KB (j over every layer of every net)."""
+    cfg = O.ModelConfig()
+    model, _ = _model(gpu, cfg, precision)
+    guard, keep = 1 << 16, []
+
+    def alloc(floats):
+        buf = torch.full((floats + 2 * guard,), float('nan'), device=gpu)
+        buf[guard:guard + floats].zero_()
+        keep.append((buf, floats))
+        return buf[guard:guard + floats]
+
+    s = model.open_stream(slots=3, hist_alloc=alloc)
+    L = 8800
+    fd = _Feeder(s)
+    ins = [_inputs(cfg, L, gpu, seed=50 + i) for i in range(2)]
+    fd.start(0, ins[0][2], ins[0][3]), fd.start(2, ins[1][2], ins[1][3])
+    for T in [80, 4000, 80, 80, 4000, 560]:
+        fd.adv([0, 2], T)
+    torch.cuda.synchronize()
+    buf, floats = keep[0]
+    assert bool(torch.isnan(buf[:guard]).all()) and bool(torch.isnan(buf[guard + floats:]).all())
+    blocks = buf[guard:guard + floats].view(6, -1)
+    assert not bool(torch.isnan(blocks).any()) and not bool(blocks[2:4].any())
+    for slot, u in ((0, ins[0]), (2, ins[1])):
+        assert torch.equal(fd.result(slot), _one_shot(model, u[2], u[3])), slot
+    layers = [d for dl in cfg.dilations for d in dl] * 2          # every layer of every net: two nets per flow
+    bound = 2 * sum((d + 31) // 32 * 32 for d in layers) * 256 + (64 << 10)
+    assert s.state_bytes(0) <= bound, (s.state_bytes(0), bound)
+
+
+@pytest.mark.parametrize('case', ['transposed_conv', 'skip', 'f16', 'in'])
+def test_refusals(gpu, case):
+    from pwv_amd._lib import PwvError
+    from pwv_amd.models import IAFVocoder
+    from pwv_amd.variables import VariableStore
+    kw, precision, reason = {}, None, None
+    if case == 'transposed_conv':
+        kw, reason = dict(cond_upsample_method='transposed_conv'), 'transposed-conv'
+    elif case == 'skip':
+        kw, reason = dict(use_skip_connection=True), 'skip accumulation'
+    elif case == 'f16':
+        precision, reason = 'f16', "precision 'f16'"
+    else:
+        kw, reason = dict(normalize='in'), 'instance normalisation'
+    set_hparams(small_cfg(**kw))
+    store = VariableStore(device=gpu)
+    model = IAFVocoder(batch_size=1, length=80, store=store, precision=precision)
+    with pytest.raises(PwvError, match=reason):
+        model.open_stream(slots=2)
+    assert len(store.vars) == 0          # nothing planned, packed or launched
+
+
+def test_generate_cli_stream(gpu, tmp_path, monkeypatch):
+    """`generate default --stream=5` on three .npy mels writes the sample counts `--varlen` writes."""
+    from scipy.io import wavfile
+    from pwv_amd.generate import _fire, generate
+    from pwv_amd.hparam import hparam as hp
+    rng = np.random.default_rng(4)
+    frames = [3, 21, 9]
+    for i, f in enumerate(frames):
+        np.save(str(tmp_path / ('m%d.npy' % i)), rng.uniform(-1, 1, (f, 80)).astype(np.float32))
+    logdir = tmp_path / 'out'
+    monkeypatch.setenv('PWV_LOGDIR', str(logdir))
+    orig = type(hp).set_hparam_yaml
+
+    def patched(self, case, *a, **k):          # what a user's hparams.yaml case would override
+        r = orig(self, case, *a, **k)
+        self.data_path = str(tmp_path / '*.npy')
+        self.train.dataset_ratio, self.generate.batch_size = 0.0, 3
+        self.model.n_iaf, self.model.dilations = 1, [[1, 2, 4, 8]]
+        return r
+
+    monkeypatch.setattr(type(hp), 'set_hparam_yaml', patched)
+    pred = _fire(generate, ['default', '--stream=5'])
+    assert [p.shape for p in pred] == [((f - 1) * 80, 1) for f in frames]
+    for i, f in enumerate(frames):
+        rate, data = wavfile.read(str(logdir / ('pred_%d.wav' % i)))
+        assert data.shape == ((f - 1) * 80,)

@@ -1,0 +1,103 @@
+"""Streaming against overlap-and-discard ("Streaming"): what one TICK of a server costs that advances
+`sessions` sessions by `chunk` samples each, default model, random weights, one GPU, steady state (every session has emitted more
+than timeshard.chain_halo samples).
+
+Legs of a cell (sessions x chunk):
+  stream    StreamingVocoder.push of all slots: sessions x chunk rows through the streaming per-layer kernels
+  overlap   the same new samples through the one-shot API only: one uniform forward IAFVocoder(sessions, chunk + chain_halo), the
+            first chain_halo samples discarded (timeshard.py: exact) -- code that runs unchanged without the streaming feature
+  rows      sessions x chunk rows as a plain uniform forward IAFVocoder(sessions, chunk): what the kept rows alone cost (the floor;
+            its audio is the one-shot left edge, not a continuation)
+A tick = the leg's launches enqueued (verify=False, explicit z) and ONE synchronisation; `ms` is the median over --steps ticks after
+--warmup ticks, `enqueue_ms` the median host time up to the synchronisation.  The three legs of a cell run one after the other in the
+same process, the whole round twice ('ms' holds both medians: their difference is the spread).  Prints one JSON line.
+
+    python tools/stream_bench.py [--steps 20] [--warmup 5] [--precision f16x3] [--sessions 1,8,32] [--chunks 800,1600,8000]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--steps', type=int, default=20)
+    ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--precision', default='f16x3', choices=['f16x3', 'f32'])
+    ap.add_argument('--sessions', default='1,8,32')
+    ap.add_argument('--chunks', default='800,1600,8000')
+    args = ap.parse_args()
+
+    import numpy as np
+    import torch
+    from oracle import iaf_oracle as O
+    from pwv_amd import engine
+    from pwv_amd.models import IAFVocoder
+    from pwv_amd.timeshard import chain_halo
+    from pwv_amd.variables import VariableStore
+    from tests.util import set_hparams
+
+    dev = torch.device('cuda', 0)
+    cfg = O.ModelConfig()
+    set_hparams(cfg)
+    store = VariableStore(device=dev)
+    store.load_dict(O.init_weights(cfg, seed=2))
+    hop = cfg.hop_length
+    halo = chain_halo(cfg.dilations, cfg.filter_width, cfg.n_iaf, hop)
+    rng = np.random.default_rng(0)
+
+    def rand(*shape):
+        return torch.from_numpy(rng.uniform(-1, 1, shape).astype(np.float32)).to(dev)
+
+    def timed(fn, sync):
+        host, total = [], []
+        for k in range(args.warmup + args.steps):
+            t0 = time.perf_counter()
+            fn()
+            t1 = time.perf_counter()
+            sync()
+            t2 = time.perf_counter()
+            if k >= args.warmup:
+                host.append((t1 - t0) * 1e3)
+                total.append((t2 - t0) * 1e3)
+        return statistics.median(total), statistics.median(host)
+
+    out = {'precision': args.precision, 'steps': args.steps, 'warmup': args.warmup, 'chain_halo': halo, 'cells': []}
+    for S in [int(v) for v in args.sessions.split(',')]:
+        for chunk in [int(v) for v in args.chunks.split(',')]:
+            model = IAFVocoder(batch_size=S, length=chunk, store=store, precision=args.precision)
+            stream = model.open_stream(slots=S)
+            warm = -(-(halo + hop) // hop) * hop
+            stream.push(rand(S, warm // hop + 1, cfg.n_mels), z=rand(S, warm, 1))        # steady state: emitted > chain_halo
+            mel_s, z_s = rand(S, chunk // hop, cfg.n_mels), rand(S, chunk, 1)
+            over = IAFVocoder(batch_size=S, length=chunk + halo, store=store, precision=args.precision)
+            mel_o, z_o = rand(S, (chunk + halo) // hop + 1, cfg.n_mels), rand(S, chunk + halo, 1)
+            mel_r, z_r = rand(S, chunk // hop + 1, cfg.n_mels), rand(S, chunk, 1)
+            legs = {
+                'stream': (lambda: stream.push(mel_s, z=z_s, verify=False), stream.verify),
+                'overlap': (lambda: over(None, mel_o, z=z_o, verify=False)[:, halo:], lambda: engine.verify_enqueued('overlap')),
+                'rows': (lambda: model(None, mel_r, z=z_r, verify=False), lambda: engine.verify_enqueued('rows')),
+            }
+            cell = {'sessions': S, 'chunk': chunk, 'stream_rows': S * chunk, 'overlap_rows': S * (chunk + halo)}
+            for name in legs:
+                cell[name] = {'ms': [], 'enqueue_ms': []}
+            for _ in range(2):
+                for name, (fn, sync) in legs.items():
+                    ms, host = timed(fn, sync)
+                    cell[name]['ms'].append(round(ms, 3))
+                    cell[name]['enqueue_ms'].append(round(host, 3))
+            assert stream.emitted(0) == warm + 2 * (args.warmup + args.steps) * chunk
+            cell['overlap_over_stream'] = [round(o / s, 3) for o, s in zip(cell['overlap']['ms'], cell['stream']['ms'])]
+            out['cells'].append(cell)
+            print('# %s' % json.dumps(cell), file=sys.stderr)
+    print(json.dumps(out))
+
+
+if __name__ == '__main__':
+    main()
