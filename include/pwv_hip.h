@@ -543,6 +543,23 @@ typedef struct pwv_persist_args {
     const int* cu_frames;
     const int* unit_map;
     long long varlen_rows;
+    /* optional STREAMING (see "STREAMING" above pwv_stream_args): the launch continues N sessions -- its N x T rows are the T samples that
+     * follow what each session has seen.  The two changes pwv_wavenet_layer_stream_f32 makes against pwv_wavenet_layer_f32, for every layer
+     * of the launch and the tail's: the look-back x[t-d] of a row with t < d is the session's history of that layer's input (a run that
+     * starts at x_first: the scalar history at hist->scalar_off), and the last d input rows of the chunk are stored as the next history.
+     * Results are bit-identical to the L calls of pwv_wavenet_layer_stream_f32 plus the affine that the launch replaces -- outputs and
+     * every written history row; a history of zeros gives the one-shot launch's bits.  With T < d the launch writes rows d-T .. d-1 of a
+     * history only: pwv_stream_carry_f32 moves the rest, as for the per-layer launches.
+     *   hist          NULL: the one-shot launch.  Read: struct_size, hist_rd, hist_wr, block_stride, slot_tab, scalar_off (row_off is not:
+     *                 a launch has many layers)
+     *   hist_row_off  per net a HOST array [n_layers + (tail_q > 0 ? 1 : 0)]: the float offset (a multiple of 4) of the row history of the
+     *                 run's layer j inside a block -- entry 0 is not read when the run starts at x_first --; the last entry is the tail's layer
+     * PWV_EINVAL (before a device is needed, pwv_last_error names the field): hist with cu_rows (a packed batch has no streaming form), with
+     * a precision other than PWV_PREC_F16X3 / PWV_PREC_F32, with x_first but no first_fold, without hist_row_off[g] for a net of the launch,
+     * hist->struct_size == 0, hist->slot_tab == NULL.  pwv_persist_workspace_bytes and pwv_persist_short_input do not read these fields:
+     * the plan is on rows. */
+    const pwv_stream_args* hist;
+    const size_t* hist_row_off[PWV_MAX_NETS];
 } pwv_persist_args;
 
 /* PWV_VARLEN_REC_INTS ints per 32-row unit of a packed batch: {n, cu_rows[n], cu_frames[n], cu_rows[n+1], cu_frames[n+1], 0, 0, 0}

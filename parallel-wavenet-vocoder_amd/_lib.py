@@ -170,6 +170,9 @@ class PersistArgs(Structure):
         ('cu_frames', c_void_p),
         ('unit_map', c_void_p),
         ('varlen_rows', ctypes.c_longlong),
+        # streaming: a pwv_stream_args (its histories and slot table), per net the HOST array of the row-history offsets of the launch's layers
+        ('hist', c_void_p),
+        ('hist_row_off', POINTER(c_size_t) * PWV_MAX_NETS),
     ]
 
     def __init__(self, *args, **kw):

@@ -105,6 +105,15 @@ struct PersistParams {
     int* pair;                             // [nwg] arrival counters of the two nets' workgroups of a range (zero on entry and on exit)
     // VARLEN instantiations: a packed batch (N = 1, T = R rows here); [units][kVarlenRec] records of pwv_varlen_unit_map (pwv_layer_common.h)
     const int* unit_map;
+    // STREAM instantiations (pwv_persist_args.hist): the launch continues N sessions.  Session n reads block slot_tab[2n] of hist_rd and writes
+    // block slot_tab[2n+1] of hist_wr (StreamParams, pwv_layer_common.h); hist_off[net][j] = float offset of the row history of the launch's
+    // layer j inside a block ([n_layers]: the tail's layer), hist_scalar_off = the scalar history of a run that starts at x_first
+    const float* hist_rd;
+    float* hist_wr;
+    const int* slot_tab;
+    long long hist_block_stride;
+    long long hist_scalar_off;
+    long long hist_off[PWV_MAX_NETS][kMaxPLayers + 1];
 };
 
 // -DPWV_PTRACE: every wave accumulates s_memtime cycles: [0] whole loop, [1] drain at the top, [2] RAW spins, [3] WAR spins,
@@ -199,8 +208,18 @@ __device__ __forceinline__ void gemm_groups_dense(FR&& fr, f32x16 (&acc)[2], f32
 // VARLEN: a packed batch of utterances of different lengths (pwv_persist_args.cu_rows): a lane's (utterance, time) and P row come from
 // its unit's record (unit_rows_varlen) instead of row / T.  Nothing else differs: the plan, ring, progress words and workspace are
 // defined on rows and units.  The instantiations without it compile to the instruction stream they had before it existed.
-template <bool F32, int MODE, bool VARLEN>
+// STREAM: the uniform [N, T] launch continues N sessions (pwv_persist_args.hist) -- the two changes layer_*_stream_kernel makes against
+// layer_*_kernel.  A lane whose row has t < d takes its look-back x[t-d] from the session's history of that layer's input (row t of the
+// layer's tile32 row history in the block the session reads; layer 0 folded: the scalar history) instead of zero, and the lanes with
+// t >= T - d store their layer-input row -- in registers anyway -- to row t + d - T of the block the session writes.  All but
+// ceil(d/32) + 1 units per session and layer have __all(t >= d) and none of the stored rows: they run the one-shot instruction
+// sequence; the history addresses are made under wave-uniform branches for the boundary units only and not kept.  Plan, ring, progress
+// words and waits are the one-shot kernel's (the waits are defined on units: merely conservative for lanes that read the history; a
+// push reads one generation and writes the other, so the history adds no dependency inside a launch).  Plain stores: the next
+// reader of hist_wr is a later launch.  The instantiations without it compile to the instruction stream they had before it existed.
+template <bool F32, int MODE, bool VARLEN, bool STREAM = false>
 __global__ __launch_bounds__(512) void stack_persist_kernel(const PersistParams p) {
+    static_assert(!(VARLEN && STREAM), "streaming of packed batches is not built");
     constexpr bool SHORT = MODE == 2;      // progress words per unit, stationary units, loader wave, ... (everything below that says SHORT)
     __shared__ __attribute__((aligned(16))) float lds[kLdsFloats];
     const int tid = threadIdx.x;
@@ -301,6 +320,39 @@ __global__ __launch_bounds__(512) void stack_persist_kernel(const PersistParams 
     auto in_soff = [&](int j) -> int { return ((j + 2 + p.rot) % 3) * slot_bytes; };
     auto out_soff = [&](int j) -> int { return ((j + p.rot) % 3) * slot_bytes; };
     auto toff = [&](int row) -> int { return ((row >> 5) * 2048 + h * 128 + (row & 31) * 4) * 4; };
+    // STREAM, boundary units only (64-bit global addresses: the histories are another allocation, and slots x 2 blocks pass 4 GB)
+    // look-back from the history: lanes with t < d overwrite xb with row t of layer `jh`'s row history in the block their session reads
+    auto hist_lookback = [&](int jh, int d, int nn, int t, float (&xb)[32]) {
+        if constexpr (STREAM) {
+            if (!__all(t >= d)) {
+                if (t < d) {
+                    const float* hr = p.hist_rd + (long long)p.slot_tab[2 * nn] * p.hist_block_stride + p.hist_off[net][jh] + tile_off(t, h, 64);
+#pragma unroll
+                    for (int g = 0; g < 8; ++g) {
+                        const f32x4 v = *reinterpret_cast<const f32x4*>(hr + g * 256);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) xb[4 * g + e] = v[e];
+                    }
+                }
+            }
+        }
+    };
+    // history store: lanes with t >= T - d store their row of layer `jh`'s input to row t + d - T of the block their session writes
+    auto hist_store = [&](int jh, int d, int nn, int t, bool valid, const float (&xr)[32]) {
+        if constexpr (STREAM) {
+            const int k = t + d - p.T;
+            if (__any(valid && k >= 0)) {
+                if (valid && k >= 0) {
+                    float* hw = p.hist_wr + (long long)p.slot_tab[2 * nn + 1] * p.hist_block_stride + p.hist_off[net][jh] + tile_off(k, h, 64);
+#pragma unroll
+                    for (int g = 0; g < 8; ++g) {
+                        const f32x4 v = {xr[4 * g], xr[4 * g + 1], xr[4 * g + 2], xr[4 * g + 3]};
+                        *reinterpret_cast<f32x4*>(hw + g * 256) = v;
+                    }
+                }
+            }
+        }
+    };
 
     // x[t-d] / x[t] rows of one unit -> registers
     auto load_x = [&](int j, int unit, float (&xb)[32], float (&xc)[32]) {
@@ -339,6 +391,7 @@ __global__ __launch_bounds__(512) void stack_persist_kernel(const PersistParams 
         };
         if (__all(has_prev)) load_b(true);      // wave-uniform fast path: no select behind the loads, they stay in flight
         else load_b(has_prev);
+        hist_lookback(j, d, nn, t, xb);
     };
 
     // the unit's own rows alone (stationary units: once, in front of the task loop)
@@ -372,6 +425,7 @@ __global__ __launch_bounds__(512) void stack_persist_kernel(const PersistParams 
 #pragma unroll
             for (int e = 0; e < 4; ++e) xb[4 * g + e] = v[e];
         }
+        hist_lookback(j, d, nn, t, xb);      // (STREAM: rows left of the chunk are the history's -- and are not zeroed where the row is used)
     };
 
     // ---- dependencies: lane k < 6 of a wave looks at ONE byte of LDS ------------------------------------------------------
@@ -629,9 +683,21 @@ __global__ __launch_bounds__(512) void stack_persist_kernel(const PersistParams 
             const float* x1 = p.x_first;
             const bool has_prev = t >= d;
             const float x0 = x1[rc];
-            const float x1v = t >= 1 ? x1[rc - (t >= 1 ? 1 : 0)] : 0.f;
-            const float xd0 = has_prev ? x1[rc - (has_prev ? d : 0)] : 0.f;
-            const float xd1 = t >= d + 1 ? x1[rc - (t >= d + 1 ? d + 1 : 0)] : 0.f;
+            float x1v, xd0, xd1;
+            if constexpr (STREAM) {
+                // x[t-1], x[t-d], x[t-d-1] with a negative time come from the session's scalar history: time r < 0 is element d + 1 + r
+                // (every address a valid one, selected: layer_*_stream_kernel's FIRST form); the chunk's last d + 1 scalars are the next history
+                const float* hx = p.hist_rd + (long long)p.slot_tab[2 * nn] * p.hist_block_stride + p.hist_scalar_off;
+                x1v = *(t >= 1 ? x1 + rc - 1 : hx + d);
+                xd0 = *(has_prev ? x1 + rc - d : hx + t + 1);
+                xd1 = *(t >= d + 1 ? x1 + rc - d - 1 : hx + t);
+                const int k = t + d + 1 - p.T;
+                if (valid && h == 0 && k >= 0) p.hist_wr[(long long)p.slot_tab[2 * nn + 1] * p.hist_block_stride + p.hist_scalar_off + k] = x0;
+            } else {
+                x1v = t >= 1 ? x1[rc - (t >= 1 ? 1 : 0)] : 0.f;
+                xd0 = has_prev ? x1[rc - (has_prev ? d : 0)] : 0.f;
+                xd1 = t >= d + 1 ? x1[rc - (t >= d + 1 ? d + 1 : 0)] : 0.f;
+            }
             f32x16 acc[4];
             {
                 int prow = 0;
@@ -906,7 +972,7 @@ __global__ __launch_bounds__(512) void stack_persist_kernel(const PersistParams 
             float xc[32], xb[32];
 #pragma unroll
             for (int k = 0; k < 32; ++k) { xc[k] = rxc[k]; xb[k] = rxb[k]; }
-            if constexpr (SHORT) {      // (SHORT: the look-back row arrives unselected, see load_xb; rows left of the utterance start are zero, modules.py:24-28)
+            if constexpr (SHORT && !STREAM) {      // (SHORT: the look-back row arrives unselected, see load_xb; rows left of the utterance start are zero, modules.py:24-28)
                 if (!__all(t >= dil_of(j))) {
                     const bool hp = t >= dil_of(j);
 #pragma unroll
@@ -914,6 +980,7 @@ __global__ __launch_bounds__(512) void stack_persist_kernel(const PersistParams 
                 }
             }
             settle_top();
+            hist_store(j, dil_of(j), nn, t, valid, xc);
             const float* Af = lds + (j & 1) * kSlot;                 // [kA1 | kA2 minus its last fragment]
             f32x4 a[4];
             f32x4 lf = {0.f, 0.f, 0.f, 0.f};
@@ -970,6 +1037,7 @@ __global__ __launch_bounds__(512) void stack_persist_kernel(const PersistParams 
             split8<16>(xc, bh[6], bl[6]);
             split8<24>(xc, bh[7], bl[7]);
             settle_top();
+            hist_store(j, dil_of(j), nn, t, valid, xc);
             auto bxh = [&](int s) -> f16x8 { return bh[s ^ 4]; };
             auto bxl = [&](int s) -> f16x8 { return bl[s ^ 4]; };
             f16x8 oh[4], ol[4];
@@ -985,10 +1053,12 @@ __global__ __launch_bounds__(512) void stack_persist_kernel(const PersistParams 
                     if constexpr (SHORT) {      // the look-back row (no select behind its loads, see load_xb) is zeroed left of the utterance start and split HERE, in one piece
                         if (s == 3) {
                             PT_EV(14, j, u);
-                            if (!__all(t >= dil_of(j))) {      // (rows left of the utterance start: zero, modules.py:24-28)
-                                const bool hp = t >= dil_of(j);
+                            if constexpr (!STREAM) {      // (STREAM: load_xb has put the history's rows there)
+                                if (!__all(t >= dil_of(j))) {      // (rows left of the utterance start: zero, modules.py:24-28)
+                                    const bool hp = t >= dil_of(j);
 #pragma unroll
-                                for (int k = 0; k < 32; ++k) rxb[k] = hp ? rxb[k] : 0.f;
+                                    for (int k = 0; k < 32; ++k) rxb[k] = hp ? rxb[k] : 0.f;
+                                }
                             }
                             split8<0>(rxb, bh[0], bl[0]);
                             split8<8>(rxb, bh[1], bl[1]);
@@ -1201,6 +1271,7 @@ __global__ __launch_bounds__(512) void stack_persist_kernel(const PersistParams 
 #pragma unroll
                         for (int e = 0; e < 4; ++e) xb[4 * g + e] = has_prev ? v[e] : 0.f;
                     }
+                    hist_lookback(L, td, nn, t, xb);
                 };
                 auto no_extra = [](int) {};
                 int unit = u_begin + wave;
@@ -1215,6 +1286,7 @@ __global__ __launch_bounds__(512) void stack_persist_kernel(const PersistParams 
                     int row, rc, nn, t;
                     bool valid;
                     rows_of(unit, row, valid, rc, nn, t);
+                    hist_store(L, td, nn, t, valid, txc);
                     f32x16 acc[4];
                     {
                         int prow = 0;
@@ -1563,6 +1635,28 @@ static int varlen_check(const pwv_persist_args* a, const char* who) {
     return PWV_OK;
 }
 
+// STREAMING (pwv_persist_args.hist): what can be refused without a device, each with the field's name; `sa` receives the caller's
+// pwv_stream_args as far as its struct_size reaches
+static int stream_check(const pwv_persist_args* a, pwv_stream_args& sa, const char* who) {
+    if (!a->hist) return PWV_OK;
+    PWV_CHECK_ARG(!is_varlen(a), "%s: hist together with cu_rows: a packed batch has no streaming form", who);
+    PWV_CHECK_ARG(a->precision == PWV_PREC_F16X3 || a->precision == PWV_PREC_F32, "%s: hist needs precision PWV_PREC_F16X3 or PWV_PREC_F32", who);
+    PWV_CHECK_ARG(a->G >= 1 && a->G <= PWV_MAX_NETS, "%s: G=%d out of range", who, a->G);
+    for (int g = 0; g < a->G; ++g) {
+        PWV_CHECK_ARG(!a->x_first || a->first_fold[g], "%s: hist with x_first needs first_fold: layer 0 streams in its folded form only", who);
+        PWV_CHECK_ARG(a->hist_row_off[g], "%s: hist without hist_row_off[%d]", who, g);
+    }
+    PWV_CHECK_ARG(a->hist->struct_size != 0, "%s: hist->struct_size is 0 (set it to sizeof(pwv_stream_args))", who);
+    PWV_CHECK_ARG(a->hist->struct_size >= offsetof(pwv_stream_args, carry_tab) && a->hist->struct_size <= 4096,
+                  "%s: hist->struct_size does not cover the history fields", who);
+    sa = pwv_stream_args{};
+    memcpy(&sa, a->hist, a->hist->struct_size < sizeof(sa) ? a->hist->struct_size : sizeof(sa));
+    PWV_CHECK_ARG(sa.slot_tab, "%s: hist->slot_tab is NULL", who);
+    PWV_CHECK_ARG(sa.hist_rd && sa.hist_wr, "%s: hist->hist_rd / hist->hist_wr is NULL", who);
+    PWV_CHECK_ARG(sa.block_stride > 0 && sa.block_stride % 4 == 0, "%s: hist->block_stride must be a positive multiple of 4 floats", who);
+    return PWV_OK;
+}
+
 // the short-input instantiation: the plan's verdict (units per workgroup, look-back reach), and a folded layer 0 if the run starts with one (it has
 // no unfolded form), and the P rows inside the 2 GB its buffer descriptor's 32-bit offsets reach.  (The workspace is sized by the plan alone.)
 static int short_input_mode(const pwv_persist_args* a, const PersistPlan& pl) {
@@ -1616,7 +1710,10 @@ int pwv_wavenet_stack_persist_f32(const pwv_persist_args* args, pwv_stream_t str
     const pwv_persist_args* a = &copy;
     PWV_CHECK_ARG(a->workspace, "pwv_wavenet_stack_persist_f32: NULL workspace");
     if (int rc1 = varlen_check(a, "pwv_wavenet_stack_persist_f32")) return rc1;
+    pwv_stream_args sa{};
+    if (int rc2 = stream_check(a, sa, "pwv_wavenet_stack_persist_f32")) return rc2;
     const bool varlen = is_varlen(a);
+    const bool streaming = a->hist != nullptr;
     const int cus = device_cus();
     if (cus <= 0) return set_error(PWV_EHIP, "no HIP device");
     PersistParams p{};
@@ -1709,6 +1806,25 @@ int pwv_wavenet_stack_persist_f32(const pwv_persist_args* args, pwv_stream_t str
         PWV_CHECK_ARG(!a->affine_x, "pwv_wavenet_stack_persist_f32: affine_x without a tail");
     }
     (void)pair_words;
+    // the sessions' histories: every history of the launch inside a block (the layers' dilations are the plan's, checked above)
+    if (streaming) {
+        p.hist_rd = sa.hist_rd;
+        p.hist_wr = sa.hist_wr;
+        p.slot_tab = sa.slot_tab;
+        p.hist_block_stride = (long long)sa.block_stride;
+        p.hist_scalar_off = (long long)sa.scalar_off;
+        PWV_CHECK_ARG(!a->x_first || sa.scalar_off + (size_t)a->dilations[0] + 1 <= sa.block_stride,
+                      "pwv_wavenet_stack_persist_f32: hist->scalar_off + dilation + 1 scalars leave the history block");
+        const int n_hist = a->n_layers + (a->tail_q > 0 ? 1 : 0);
+        for (int g = 0; g < a->G; ++g)
+            for (int j = a->x_first ? 1 : 0; j < n_hist; ++j) {
+                const size_t off = a->hist_row_off[g][j];
+                const size_t hist_rows = ((size_t)(j < a->n_layers ? a->dilations[j] : a->tail_dilation) + 31) / 32 * 32;
+                PWV_CHECK_ARG(off % 4 == 0 && off + hist_rows * 64 <= sa.block_stride,
+                              "pwv_wavenet_stack_persist_f32: hist_row_off[%d][%d] + round32(dilation) rows leave the history block", g, j);
+                p.hist_off[g][j] = (long long)off;
+            }
+    }
     p.trace = nullptr;
 #ifdef PWV_PTRACE
     { const char* e = getenv("PWV_PTRACE_PTR"); if (e) p.trace = (long long*)strtoull(e, nullptr, 0); }
@@ -1720,7 +1836,15 @@ int pwv_wavenet_stack_persist_f32(const pwv_persist_args* args, pwv_stream_t str
     if (!a->workspace_clean)
         hipLaunchKernelGGL(persist_zero_kernel, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, s, (int4*)a->workspace, n16);
     const dim3 grid(a->G * pl.nwg), block(512);
-    if (varlen) {
+    if (streaming) {
+        if (a->precision == PWV_PREC_F32) {
+            if (pl.unit_mode == 2) hipLaunchKernelGGL((stack_persist_kernel<true, 2, false, true>), grid, block, 0, s, p);
+            else hipLaunchKernelGGL((stack_persist_kernel<true, 0, false, true>), grid, block, 0, s, p);
+        } else {
+            if (pl.unit_mode == 2) hipLaunchKernelGGL((stack_persist_kernel<false, 2, false, true>), grid, block, 0, s, p);
+            else hipLaunchKernelGGL((stack_persist_kernel<false, 0, false, true>), grid, block, 0, s, p);
+        }
+    } else if (varlen) {
         if (a->precision == PWV_PREC_F32) {
             if (pl.unit_mode == 2) hipLaunchKernelGGL((stack_persist_kernel<true, 2, true>), grid, block, 0, s, p);
             else hipLaunchKernelGGL((stack_persist_kernel<true, 0, true>), grid, block, 0, s, p);

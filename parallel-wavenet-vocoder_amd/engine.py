@@ -814,13 +814,15 @@ def _layer_args(net0, plans, projs, row_stride: int, cond_geom, bufs, j: int, sr
     return la
 
 
-def _run_stack_persist(path: _Path, nets, plans, projs, bufs, outs, x, x_limit, row_stride, cond_geom, affine=None, geom=None):
+def _run_stack_persist(path: _Path, nets, plans, projs, bufs, outs, x, x_limit, row_stride, cond_geom, affine=None, geom=None, stream_hist=None):
     """Layers 0 .. L-2 as the persistent launches of `path` (layer 0 a launch of its own when it cannot rebuild the causal layer
     itself), with layer L-1 + the head behind them -- and, given `affine` = (x, out), the flow's affine out = x*s + b -- INSIDE the
     last launch where `path.tail` (otherwise one more launch for them); all nets of the flow in every launch, all on the current
     stream.  `bufs[g]` holds THREE tile32 buffers: the persistent launch rotates through them (include/pwv_hip.h,
     pwv_persist_args.x_ring).  With `geom` (a VarlenGeometry; x is then its [1, R, 1]) every launch carries the packed batch's
-    fields.  Returns True when the affine was evaluated by the launch."""
+    fields.  With `stream_hist` = (pwv_stream_args, row_off[g][layer]) the launches are the STREAMING ones (run_flow_stream): every
+    run is told where its own layers' row histories -- and the tail's -- lie in a block.  Returns True when the affine was evaluated
+    by the launch."""
     lib, s = _lib.lib(), _stream()
     G, L, prec = len(nets), plans[0].n_layers, plans[0].precision
     net0 = nets[0]
@@ -844,6 +846,14 @@ def _run_stack_persist(path: _Path, nets, plans, projs, bufs, outs, x, x_limit, 
             _set_x_first(pa, plans, x, x_limit)
         if geom is not None:
             geom.set_args(pa)
+        tail_here = path.tail and pa is path.runs[-1][1]
+        if stream_hist is not None:
+            sa, row_off = stream_hist
+            layers = list(range(j0, j0 + pa.n_layers)) + ([L - 1] if tail_here else [])
+            hist_offs = [(ctypes.c_size_t * len(layers))(*[max(int(row_off[g][j]), 0) for j in layers]) for g in range(G)]      # (layer 0: unused)
+            pa.hist = ctypes.addressof(sa)
+            for g in range(G):
+                pa.hist_row_off[g] = hist_offs[g]
         # one zero-initialised workspace per (device, stream), kept: a launch leaves it clean, so none needs a zeroing kernel
         wkey = (bufs[0][0].device, torch.cuda.current_stream().cuda_stream)
         ws = _persist_ws.get(wkey)
@@ -851,7 +861,6 @@ def _run_stack_persist(path: _Path, nets, plans, projs, bufs, outs, x, x_limit, 
             ws = _persist_ws[wkey] = torch.zeros((max(pa.workspace_bytes, 1 << 16),), dtype=torch.uint8, device=bufs[0][0].device)
         pa.workspace, pa.workspace_clean = ws.data_ptr(), 1
         pa.status = persist_status_ptr()
-        tail_here = path.tail and pa is path.runs[-1][1]
         if tail_here:                        # layer L-1 + head (+ affine) behind this run's layers, inside the launch
             for g in range(G):
                 pa.tail_layer[g] = plans[g].packed_layers.data_ptr() + 4 * stride * (L - 1)
@@ -869,7 +878,8 @@ def _run_stack_persist(path: _Path, nets, plans, projs, bufs, outs, x, x_limit, 
         if ev is not None:
             ev[1].record()
             EVENT_LOG.append(('persist', ev[0], ev[1], G, pa.n_layers, 1 if j0 == 0 else 0, 1 if tail_here else 0,
-                              int(lib.pwv_persist_short_input(ctypes.byref(pa)))))      # [7]: the short-input instantiation (round 6)
+                              int(lib.pwv_persist_short_input(ctypes.byref(pa))),      # [7]: the short-input instantiation (round 6)
+                              1 if stream_hist is not None else 0))                    # [8]: a STREAMING launch (pwv_persist_args.hist)
     if path.tail:
         return affine_fused
     last = path.runs[-1][1]
@@ -1440,10 +1450,16 @@ def stream_refusal(nets, cond, precision: Optional[str] = None) -> Optional[str]
 def run_flow_stream(nets: Sequence, x: torch.Tensor, cond, precision: Optional[str], hist: _lib.StreamArgs, scalar_off: int,
                     row_off) -> torch.Tensor:
     """One IAF flow on a chunk: x [N, T, 1] = the T samples that follow what each of the N sessions has seen, `cond` the chunk's own
-    frames (a RepeatedCondition of T / hop + 1 frames per session).  L streaming layer launches of both nets (G = 2) on the current
-    stream, then the affine.  `hist` carries the history blocks and the slot table of the call (read / written block per session);
-    `scalar_off` and `row_off[g][j]` (j >= 1) say where this flow's histories lie in a block.  Only enqueues, like run_flow; the
-    written blocks become the sessions' state when the caller flips their generation."""
+    frames (a RepeatedCondition of T / hop + 1 frames per session).  `hist` carries the history blocks and the slot table of the call
+    (read / written block per session); `scalar_off` and `row_off[g][j]` (j >= 1) say where this flow's histories lie in a block.
+    The launches, chosen once per flow, all on the current stream:
+      * the persistent STREAMING launches (pwv_persist_args.hist; the affine inside the last one: one launch per run of
+        _persist_runs, one for a stack of up to PERSIST_MAX_LAYERS + 1 layers) where _choose_path gives an [N, T] forward persistent
+        runs with the tail and the fused, folded layer 0 -- PERSIST not False, not suspended, rows <= PERSIST_AUTO_MAX_ROWS, L >= 4;
+      * else L streaming layer launches of both nets (G = 2), then the affine (PWV_PERSIST=0 keeps this route in use and tested).
+    Same bits, same written history rows either way.  Only enqueues, like run_flow; the written blocks become the sessions' state
+    when the caller flips their generation -- so a push whose persistent launch gave up is rerun by verified_call on the per-layer
+    launches (persist_suspended()) from the same generation."""
     why = stream_refusal(nets, cond, precision)
     if why is not None:
         raise _lib.PwvError('run_flow_stream: no streaming form: ' + why)
@@ -1466,8 +1482,18 @@ def run_flow_stream(nets: Sequence, x: torch.Tensor, cond, precision: Optional[s
     projs = _projections(cond, mode, plans, precision, None)
     lib, s = _lib.lib(), _stream()
     G, L = len(plans), plans[0].n_layers
-    bufs = [[torch.empty((lib.pwv_tile32_floats(n * t, 64),), dtype=torch.float32, device=x.device) for _ in range(2)] for _ in plans]
     outs = [torch.empty((n, t, 1), dtype=torch.float32, device=x.device) for _ in plans]
+    path = _choose_path(net0, plans, mode, n, t, 0, cond_geom)
+    if path.persist and path.tail and path.first_fused:
+        hist.scalar_off = scalar_off
+        bufs = _causal_front(x, net0, plans, path, x_limit)       # (the ring of three; layer 0 is inside the launch: nothing is enqueued)
+        out = torch.empty_like(x)
+        if _run_stack_persist(path, nets, plans, projs, bufs, outs, x, x_limit, projs[0].stride(0), cond_geom, (x, out), None, (hist, row_off)):
+            return out
+        return iaf_affine_op(x, outs[0], outs[1], 1)
+    if EVENT_LOG is not None:
+        EVENT_LOG.append(('layer_stream', None, None, G, L))      # L calls of pwv_wavenet_layer_stream_f32 + the affine
+    bufs = [[torch.empty((lib.pwv_tile32_floats(n * t, 64),), dtype=torch.float32, device=x.device) for _ in range(2)] for _ in plans]
     for j in range(L):
         la = _layer_args(net0, plans, projs, projs[0].stride(0), cond_geom, bufs, j, (j + 1) & 1, j & 1, x)
         la.out_mode = _lib.OUT_GATED if j == L - 1 else _lib.OUT_RESIDUAL

@@ -275,8 +275,10 @@ class StreamingVocoder(object):
 
     def _enqueue(self, precision, frames, z, tab, T):
         """The chunk's launches on the current stream: the prologue on the chunk's frames, the carry-over of the histories the chunk
-        does not push out (one launch, only when T is below the largest history), then per flow L streaming layer launches and the
-        affine.  Reads the sessions' current generation, writes the other one: may be enqueued again from the same state."""
+        does not push out (one launch, only when T is below the largest history), then per flow ONE persistent streaming launch
+        (engine.run_flow_stream; PWV_PERSIST=0, a suspended persistent launch or a stack below 4 layers: L streaming layer launches and
+        the affine -- same bits).  Reads the sessions' current generation, writes the other one: may be enqueued again from the same
+        state, on either route."""
         model = self.model
         store = model.store or get_default_store()
         lay = self.layout

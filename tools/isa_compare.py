@@ -6,6 +6,8 @@
 
 Prints, per kernel present in both files, the number of instructions and whether the two streams are equal (comments dropped, the
 per-function numbering of local labels normalised), then the kernels only one side has.  Exit status 1 if a common kernel differs.
+A kernel template that has gained a trailing template parameter is matched to its earlier self where the new argument is `false`
+(stack_persist_kernel<F32, MODE, VARLEN> is stack_persist_kernel<F32, MODE, VARLEN, false> of a tree with STREAM).
 """
 import re
 import subprocess
@@ -34,6 +36,11 @@ def kernels(path):
 
 def main(old, new):
     a, b = kernels(old), kernels(new)
+    # (Itanium mangling: a trailing `false` template argument is `Lb0E` in front of the `E`s that close the argument list and the name)
+    for n in sorted(set(b) - set(a)):
+        m = re.match(r'^(.*)Lb0E(E+v.*)$', n)
+        if m and m.group(1) + m.group(2) in a and m.group(1) + m.group(2) not in b:
+            b[m.group(1) + m.group(2)] = b.pop(n)
     names = sorted(set(a) & set(b))
     pretty = subprocess.run(['c++filt'] + names, stdout=subprocess.PIPE, text=True).stdout.split('\n') if names else []
     bad = 0

@@ -3,14 +3,18 @@
 than timeshard.chain_halo samples).
 
 Legs of a cell (sessions x chunk):
-  stream    StreamingVocoder.push of all slots: sessions x chunk rows through the streaming per-layer kernels
+  stream    StreamingVocoder.push of all slots: sessions x chunk rows, one persistent streaming launch per flow (engine.run_flow_stream's
+            default route; the cell's `launches` says what an untimed push enqueued)
+  stream_layers  the same push with engine.PERSIST = False: the streaming per-layer kernels, L launches per flow + the affine
   overlap   the same new samples through the one-shot API only: one uniform forward IAFVocoder(sessions, chunk + chain_halo), the
             first chain_halo samples discarded (timeshard.py: exact) -- code that runs unchanged without the streaming feature
   rows      sessions x chunk rows as a plain uniform forward IAFVocoder(sessions, chunk): what the kept rows alone cost (the floor;
             its audio is the one-shot left edge, not a continuation)
 A tick = the leg's launches enqueued (verify=False, explicit z) and ONE synchronisation; `ms` is the median over --steps ticks after
---warmup ticks, `enqueue_ms` the median host time up to the synchronisation.  The three legs of a cell run one after the other in the
-same process, the whole round twice ('ms' holds both medians: their difference is the spread).  Prints one JSON line.
+--warmup ticks, `enqueue_ms` the median host time up to the synchronisation.  The legs of a cell run one after the other in the
+same process, the whole round twice ('ms' holds both medians: their difference is the spread).  Per cell, from engine.EVENT_LOG and a
+count of the library's launch calls in one untimed push per streaming leg: `launches` = {leg: {calls, per-flow routes, short-input
+instantiation per persistent launch}}.  Prints one JSON line.
 
     python tools/stream_bench.py [--steps 20] [--warmup 5] [--precision f16x3] [--sessions 1,8,32] [--chunks 800,1600,8000]
 """
@@ -37,7 +41,7 @@ def main():
     import numpy as np
     import torch
     from oracle import iaf_oracle as O
-    from pwv_amd import engine
+    from pwv_amd import _lib, engine
     from pwv_amd.models import IAFVocoder
     from pwv_amd.timeshard import chain_halo
     from pwv_amd.variables import VariableStore
@@ -68,6 +72,26 @@ def main():
                 total.append((t2 - t0) * 1e3)
         return statistics.median(total), statistics.median(host)
 
+    persist_default, real_lib = engine.PERSIST, _lib.lib
+    # library calls that enqueue nothing (sizes, plans, error text)
+    NOT_LAUNCHES = ('pwv_persist_workspace_bytes', 'pwv_persist_short_input', 'pwv_tile32_floats', 'pwv_last_error', 'pwv_version',
+                    'pwv_layer_packed_floats', 'pwv_head_packed_floats', 'pwv_persist_status', 'pwv_status_words_alloc')
+
+    def counting(calls):
+        lib = real_lib()
+
+        class Counting(object):
+            def __getattr__(self, name):
+                fn = getattr(lib, name)
+                if not name.startswith('pwv_'):
+                    return fn
+
+                def wrapped(*a):
+                    calls.append(name)
+                    return fn(*a)
+                return wrapped
+        return Counting()
+
     out = {'precision': args.precision, 'steps': args.steps, 'warmup': args.warmup, 'chain_halo': halo, 'cells': []}
     for S in [int(v) for v in args.sessions.split(',')]:
         for chunk in [int(v) for v in args.chunks.split(',')]:
@@ -79,12 +103,31 @@ def main():
             over = IAFVocoder(batch_size=S, length=chunk + halo, store=store, precision=args.precision)
             mel_o, z_o = rand(S, (chunk + halo) // hop + 1, cfg.n_mels), rand(S, chunk + halo, 1)
             mel_r, z_r = rand(S, chunk // hop + 1, cfg.n_mels), rand(S, chunk, 1)
+            def push_layers():
+                engine.PERSIST = False
+                try:
+                    return stream.push(mel_s, z=z_s, verify=False)
+                finally:
+                    engine.PERSIST = persist_default
+
             legs = {
                 'stream': (lambda: stream.push(mel_s, z=z_s, verify=False), stream.verify),
+                'stream_layers': (push_layers, stream.verify),
                 'overlap': (lambda: over(None, mel_o, z=z_o, verify=False)[:, halo:], lambda: engine.verify_enqueued('overlap')),
                 'rows': (lambda: model(None, mel_r, z=z_r, verify=False), lambda: engine.verify_enqueued('rows')),
             }
-            cell = {'sessions': S, 'chunk': chunk, 'stream_rows': S * chunk, 'overlap_rows': S * (chunk + halo)}
+            cell = {'sessions': S, 'chunk': chunk, 'stream_rows': S * chunk, 'overlap_rows': S * (chunk + halo), 'launches': {}}
+            for name in ('stream', 'stream_layers'):        # one untimed push per streaming leg: what it enqueues
+                log, calls = [], []
+                engine.EVENT_LOG, _lib.lib = log, (lambda: counting(calls))
+                try:
+                    legs[name][0]()
+                    legs[name][1]()
+                finally:
+                    engine.EVENT_LOG, _lib.lib = None, real_lib
+                cell['launches'][name] = {'calls': len([c for c in calls if c not in NOT_LAUNCHES]),
+                                          'flows': [e[0] + ('_stream' if len(e) > 8 and e[8] else '') for e in log],
+                                          'short_input': [e[7] for e in log if e[0] == 'persist']}
             for name in legs:
                 cell[name] = {'ms': [], 'enqueue_ms': []}
             for _ in range(2):
@@ -92,8 +135,10 @@ def main():
                     ms, host = timed(fn, sync)
                     cell[name]['ms'].append(round(ms, 3))
                     cell[name]['enqueue_ms'].append(round(host, 3))
-            assert stream.emitted(0) == warm + 2 * (args.warmup + args.steps) * chunk
+            assert stream.emitted(0) == warm + (4 * (args.warmup + args.steps) + 2) * chunk
             cell['overlap_over_stream'] = [round(o / s, 3) for o, s in zip(cell['overlap']['ms'], cell['stream']['ms'])]
+            cell['stream_over_stream_layers'] = [round(a / b, 3) for a, b in zip(cell['stream']['ms'], cell['stream_layers']['ms'])]
+            cell['stream_over_rows'] = [round(a / b, 3) for a, b in zip(cell['stream']['ms'], cell['rows']['ms'])]
             out['cells'].append(cell)
             print('# %s' % json.dumps(cell), file=sys.stderr)
     print(json.dumps(out))
