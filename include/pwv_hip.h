@@ -309,6 +309,14 @@ int pwv_wavenet_layer_f32(const pwv_layer_args* args, pwv_stream_t stream);
  *       scalar history), 0}: every history of the model; entries with rows <= T are left alone (the layer launches rewrite them).
  * The carry launch and the layer launches of a chunk write disjoint rows and read only `hist_rd` blocks: any order.
  *
+ * The PACKED (ragged) form: sessions of DIFFERENT chunk lengths in one launch.  `cu_rows` (device int32 [N+1], prefix sums) gives session
+ * n the rows cu_rows[n] .. cu_rows[n+1]-1 of a packed launch and T_n = cu_rows[n+1] - cu_rows[n] >= 32 samples.  Everywhere above, T is
+ * then the session's OWN T_n: rows with t >= T_n - d store to row t + d - T_n of the written block, a chunk with T_n < d writes rows
+ * d-T_n .. d-1, and the carry moves that session's rows T_n .. d-1.  Taken by pwv_wavenet_stack_persist_f32 (pwv_persist_args.hist
+ * together with pwv_persist_args.cu_rows) and by pwv_stream_carry_f32 (its `T` argument is then not read; entries with rows <= T_n are
+ * left alone for that session); pwv_wavenet_layer_stream_f32 returns PWV_EINVAL and names hist->cu_rows: the per-layer kernels have
+ * no packed form.
+ *
  * Supported: PWV_PREC_F32 / PWV_PREC_F16X3; no skip accumulation, no per-sample condition (PWV_EINVAL otherwise); three forms:
  *   layer 0 with x_first AND first_fold (out_mode PWV_OUT_RESIDUAL; uses scalar_off),
  *   a plain layer (out_mode PWV_OUT_RESIDUAL; uses row_off),
@@ -326,6 +334,8 @@ typedef struct pwv_stream_args {
     size_t scalar_off;                     /* x_first: the scalar history */
     const int32_t* carry_tab;              /* pwv_stream_carry_f32 only */
     int32_t n_carry;
+    const int32_t* cu_rows;                /* NULL: the uniform [N, T] chunk.  Else device int32 [N+1]: session n's chunk is rows cu_rows[n] .. cu_rows[n+1]-1
+                                              of the packed launch (T_n = their difference) */
 } pwv_stream_args;
 
 int pwv_wavenet_layer_stream_f32(const pwv_layer_args* args, const pwv_stream_args* hist, pwv_stream_t stream);
@@ -550,11 +560,18 @@ typedef struct pwv_persist_args {
      * Results are bit-identical to the L calls of pwv_wavenet_layer_stream_f32 plus the affine that the launch replaces -- outputs and
      * every written history row; a history of zeros gives the one-shot launch's bits.  With T < d the launch writes rows d-T .. d-1 of a
      * history only: pwv_stream_carry_f32 moves the rest, as for the per-layer launches.
+     * The PACKED (ragged) form: with cu_rows / cu_frames / unit_map / varlen_rows set AND hist->cu_rows == cu_rows (the same device
+     * table) the launch continues N sessions of different chunk lengths T_n = cu_rows[n+1] - cu_rows[n] (each >= 32): rows map to
+     * (session, time, condition frame) as in a packed batch, slot_tab is indexed by the session, and T in "rows with t >= T - d store to
+     * row t + d - T" is the session's own T_n.  Bit-identical, outputs and written history rows, to the uniform streaming launches of the
+     * sessions grouped by length.
      *   hist          NULL: the one-shot launch.  Read: struct_size, hist_rd, hist_wr, block_stride, slot_tab, scalar_off (row_off is not:
      *                 a launch has many layers)
      *   hist_row_off  per net a HOST array [n_layers + (tail_q > 0 ? 1 : 0)]: the float offset (a multiple of 4) of the row history of the
      *                 run's layer j inside a block -- entry 0 is not read when the run starts at x_first --; the last entry is the tail's layer
-     * PWV_EINVAL (before a device is needed, pwv_last_error names the field): hist with cu_rows (a packed batch has no streaming form), with
+     * PWV_EINVAL (before a device is needed, pwv_last_error names the field): hist together with cu_rows (any packed field) while
+     * hist->cu_rows is NULL -- a caller whose pwv_stream_args describes a uniform chunk never gets a packed launch by accident --,
+     * hist->cu_rows set while the launch is not packed, hist->cu_rows different from cu_rows; hist with
      * a precision other than PWV_PREC_F16X3 / PWV_PREC_F32, with x_first but no first_fold, without hist_row_off[g] for a net of the launch,
      * hist->struct_size == 0, hist->slot_tab == NULL.  pwv_persist_workspace_bytes and pwv_persist_short_input do not read these fields:
      * the plan is on rows. */

@@ -191,6 +191,7 @@ class StreamArgs(Structure):
         ('scalar_off', c_size_t),
         ('carry_tab', c_void_p),
         ('n_carry', ctypes.c_int32),
+        ('cu_rows', c_void_p),          # NULL: the uniform [N, T] chunk; else device int32 [N + 1]: sessions of different chunk lengths (the ragged launch)
     ]
 
     def __init__(self, *args, **kw):
@@ -227,7 +228,7 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
     if os.environ.get('PWV_LIB'):
         return LIB_PATH            # an explicitly chosen library is never rebuilt
     hdrs = [os.path.join(_PKG_DIR, 'csrc', h) for h in ('pwv_common.h', 'pwv_layer_common.h', 'pwv_f16x3.h', 'pwv_layer_f16x3_body.inc',
-                                                         'pwv_layer_f32_body.inc')] + [os.path.join(_REPO_ROOT, 'include', 'pwv_hip.h')]
+                                                         'pwv_layer_f32_body.inc', 'pwv_stack_persist_body.inc')] + [os.path.join(_REPO_ROOT, 'include', 'pwv_hip.h')]
     hdr_time = max(os.path.getmtime(h) for h in hdrs + [os.path.abspath(__file__)])
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
     # ONE gfx950 code object for the XNACK mode an MI355X runs in by default (xnack-): code built for a known mode instead of

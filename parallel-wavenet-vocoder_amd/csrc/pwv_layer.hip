@@ -586,6 +586,7 @@ int pwv_wavenet_layer_stream_f32(const pwv_layer_args* a, const pwv_stream_args*
     StreamParams st{};
     const char* why = stream_args(sa, v, st);
     PWV_CHECK_ARG(!why, "pwv_wavenet_layer_stream_f32: %s", why);
+    PWV_CHECK_ARG(!v.cu_rows, "pwv_wavenet_layer_stream_f32: hist->cu_rows is set: the per-layer kernels have no packed form (the persistent launch has)");
     PWV_CHECK_ARG(a->precision == PWV_PREC_F32 || a->precision == PWV_PREC_F16X3,
                   "pwv_wavenet_layer_stream_f32: PWV_PREC_F32 / PWV_PREC_F16X3 only (the fp16 storage mode has no streaming form)");
     PWV_CHECK_ARG(a->G >= 1 && a->G <= PWV_MAX_NETS && a->dilation >= 1 && a->T >= 1, "pwv_wavenet_layer_stream_f32: bad G / dilation / T");
@@ -612,10 +613,13 @@ int pwv_stream_carry_f32(const pwv_stream_args* sa, int N, int T, pwv_stream_t s
     StreamParams st{};
     const char* why = stream_args(sa, v, st);
     PWV_CHECK_ARG(!why, "pwv_stream_carry_f32: %s", why);
-    PWV_CHECK_ARG(sa->struct_size >= sizeof(pwv_stream_args) && v.carry_tab && v.n_carry >= 1 && v.n_carry <= 65535,
+    PWV_CHECK_ARG(sa->struct_size >= offsetof(pwv_stream_args, n_carry) + sizeof(int32_t) && v.carry_tab && v.n_carry >= 1 && v.n_carry <= 65535,
                   "pwv_stream_carry_f32: carry_tab / n_carry missing");
-    PWV_CHECK_ARG(N >= 1 && N <= 65535 && T >= 1, "pwv_stream_carry_f32: bad N / T");
-    hipLaunchKernelGGL(stream_carry_kernel, dim3(v.n_carry, N), dim3(256), 0, (hipStream_t)stream, st, v.carry_tab, T);
+    PWV_CHECK_ARG(N >= 1 && N <= 65535 && (v.cu_rows || T >= 1), "pwv_stream_carry_f32: bad N / T");
+    if (v.cu_rows)      // the packed form: T is not read, session n's own T_n = cu_rows[n+1] - cu_rows[n]
+        return launch_stream_carry_ragged(st, v.carry_tab, v.n_carry, v.cu_rows, N, (hipStream_t)stream);      // (pwv_stack_persist.hip, next to the ragged flow kernel)
+    else
+        hipLaunchKernelGGL(stream_carry_kernel, dim3(v.n_carry, N), dim3(256), 0, (hipStream_t)stream, st, v.carry_tab, T);
     PWV_CHECK_HIP(hipGetLastError());
     return PWV_OK;
 }

@@ -323,6 +323,9 @@ __device__ __forceinline__ void gemm_groups(const float* lds, int base, int lane
 }
 
 
+// the carry-over of a ragged chunk (pwv_stream_carry_f32 with pwv_stream_args.cu_rows; pwv_stack_persist.hip)
+int launch_stream_carry_ragged(const StreamParams& st, const int* tab, int n_carry, const int* cu_rows, int N, hipStream_t s);
+
 // launchers of the split-fp16 variants (pwv_layer_f16.hip)
 int launch_layer_f16x3(const LayerParams& lp, bool skip, bool cond, bool gated, int per_net, hipStream_t s);
 // ... and of their streaming forms: layer 0 folded (lp.x_first), the last layer + head (lp.packed_head), else a plain residual layer

@@ -1447,8 +1447,120 @@ def stream_refusal(nets, cond, precision: Optional[str] = None) -> Optional[str]
     return None
 
 
+# the exact-fp32 instantiations of the ragged kernel (stack_persist_ragged_kernel<true, MODE>) are built: they are spill-free at 256 VGPRs
+# (tests/test_stream_varlen_host.py reads the compiler's remarks); False would route f32 ragged pushes to the grouped route
+RAGGED_F32 = True
+
+
+class _StreamGroup(object):
+    """The sessions of a ragged push that share one chunk length (the grouped route of run_flow_stream): their rows and frames in the
+    packed tensors (device index vectors) and their rows of the slot table."""
+
+    def __init__(self, geom, tab: torch.Tensor, t: int, members: Sequence[int]):
+        import numpy as np
+        fr = t // geom.hop + 1
+        self.t, self.n, self.frames = t, len(members), fr
+        self.rows_idx = geom._upload(np.concatenate([np.arange(geom.cu_rows_host[i], geom.cu_rows_host[i] + t) for i in members]), torch.int64)
+        self.frames_idx = geom._upload(np.concatenate([np.arange(geom.cu_frames_host[i], geom.cu_frames_host[i] + fr) for i in members]), torch.int64)
+        self.tab = tab.index_select(0, geom._upload(list(members), torch.int64)).contiguous()
+        self._cond = None
+
+    def condition(self, cond, geom):
+        """The group's [n, t / hop + 1, C] frames of the packed condition, with their rows of its projection bank (the prologue is per
+        frame: a gathered row holds the bits the group's own prologue would compute); made once per condition object."""
+        if cond is None:
+            return None
+        if self._cond is not None and self._cond[0]() is cond:
+            return self._cond[1]
+        c = cond.frames.shape[2]
+        out = RepeatedCondition(cond.frames.reshape(geom.total_frames, c).index_select(0, self.frames_idx).reshape(self.n, self.frames, c),
+                                cond.hop, cond.offset, self.t)
+        bank = getattr(cond, 'proj_bank', None)
+        if bank is not None:      # (the bank's column blocks are views of one [F, cols] GEMM output: gather that once, as pad_condition pads it)
+            base = next(iter(bank.values()))
+            full = base.as_strided((geom.total_frames, base.stride(0)), (base.stride(0), 1), 0)
+            fg = full.index_select(0, self.frames_idx)
+            out.proj_bank = {k: fg[:, v.storage_offset() - full.storage_offset():][:, :v.shape[1]] for k, v in bank.items()}
+        self._cond = (weakref.ref(cond), out)
+        return out
+
+
+def stream_groups(geom: 'VarlenGeometry', tab: torch.Tensor) -> List[_StreamGroup]:
+    """The groups of equal chunk length of a ragged push (first appearance first), made once per push and kept on its geometry."""
+    groups = getattr(geom, '_stream_groups', None)
+    if groups is None:
+        by_t = {}
+        for i, t in enumerate(geom.lengths):
+            by_t.setdefault(t, []).append(i)
+        groups = geom._stream_groups = [_StreamGroup(geom, tab, t, members) for t, members in by_t.items()]
+    return groups
+
+
+def _run_flow_stream_ragged(nets, x, cond, precision, hist, scalar_off, row_off, geom, slot_tab):
+    """run_flow_stream on a ragged chunk (geom: session i has geom.lengths[i] rows of the packed x [R, 1]).  The route, chosen once per flow:
+      * the PACKED streaming persistent launches (pwv_persist_args.cu_rows with hist->cu_rows, stack_persist_ragged_kernel) where a uniform
+        forward of R rows takes persistent runs with the tail and the fused, folded layer 0 and every session has >= 32 rows
+        (varlen_fallback_reason);
+      * else the GROUPED route: the sessions grouped by chunk length, each group the uniform streaming flow (persistent or per layer, as
+        run_flow_stream decides for it) on its own rows of x, its own frames and its own rows of the slot table, scattered back.
+    Same bits: a session's rows do not depend on which sessions were advanced with it.  EVENT_LOG gets ('stream_ragged', None, None,
+    'packed' | 'grouped', why, groups) ahead of the route's own entries."""
+    x = _require_cuda_f32(x, 'input')
+    if x.dim() != 2 or tuple(x.shape) != (geom.rows, 1):
+        raise ValueError('input must be the packed chunk [%d, 1], got %s' % (geom.rows, tuple(x.shape)))
+    net0 = nets[0]
+    name = precision or DEFAULT_PRECISION
+    prec = PRECISIONS[name]
+    why = varlen_fallback_reason(nets, cond, geom, precision)
+    if why is None:
+        x3 = x.reshape(1, geom.rows, 1)
+        mode, cond_geom, _ = _check_condition(net0, cond, x3)
+        plans = [get_plan(net, mode, prec) for net in nets]
+        if prec == _lib.PREC_F16X3 and not all(p.f16x3_ok and p.x_limit > 0 for p in plans):
+            key = tuple(net.full_scope for net in nets)      # (as run_flow_stream: weights beyond fp16's range run in exact fp32)
+            if key not in _range_warned:
+                _range_warned.add(key)
+                import warnings
+                warnings.warn("pwv: weights of %s exceed the range of the split-fp16 arithmetic; using precision 'f32' for it" % (key,))
+            return _run_flow_stream_ragged(nets, x, cond, 'f32', hist, scalar_off, row_off, geom, slot_tab)
+        if any(p.first_fold is None for p in plans):
+            raise _lib.PwvError('run_flow_stream: no streaming form: layer 0 has no folded form for these weights')
+        if prec == _lib.PREC_F32 and not RAGGED_F32:
+            why = "the ragged kernel is not built for precision 'f32'"
+        else:
+            path = _choose_path(net0, plans, mode, 1, geom.rows, 0, cond_geom)
+            if path.persist and path.tail and path.first_fused:
+                if EVENT_LOG is not None:
+                    EVENT_LOG.append(('stream_ragged', None, None, 'packed', None, 1))
+                x_limit = min(p.x_limit for p in plans)
+                projs = _projections(cond, mode, plans, precision, None)
+                outs = [torch.empty((1, geom.rows, 1), dtype=torch.float32, device=x.device) for _ in plans]
+                bufs = _causal_front(x3, net0, plans, path, x_limit)
+                out = torch.empty_like(x3)
+                hist.scalar_off, hist.cu_rows = scalar_off, _ptr(geom.cu_rows)
+                try:
+                    done = _run_stack_persist(path, nets, plans, projs, bufs, outs, x3, x_limit, projs[0].stride(0), cond_geom, (x3, out), geom,
+                                              (hist, row_off))
+                finally:
+                    hist.cu_rows = None
+                return (out if done else iaf_affine_op(x3, outs[0], outs[1], 1)).reshape(geom.rows, 1)
+            why = 'the library plans this stack per layer at %d rows' % geom.rows
+    groups = stream_groups(geom, slot_tab)
+    if EVENT_LOG is not None:
+        EVENT_LOG.append(('stream_ragged', None, None, 'grouped', why, len(groups)))
+    out = torch.empty_like(x)
+    for grp in groups:
+        hg = _lib.StreamArgs()
+        ctypes.memmove(ctypes.addressof(hg), ctypes.addressof(hist), ctypes.sizeof(_lib.StreamArgs))
+        hg.slot_tab, hg.cu_rows = grp.tab.data_ptr(), None
+        yg = run_flow_stream(nets, x.index_select(0, grp.rows_idx).reshape(grp.n, grp.t, 1), grp.condition(cond, geom), precision, hg,
+                             scalar_off, row_off)
+        out.index_copy_(0, grp.rows_idx, yg.reshape(grp.n * grp.t, 1))
+    return out
+
+
 def run_flow_stream(nets: Sequence, x: torch.Tensor, cond, precision: Optional[str], hist: _lib.StreamArgs, scalar_off: int,
-                    row_off) -> torch.Tensor:
+                    row_off, geom=None, slot_tab: Optional[torch.Tensor] = None) -> torch.Tensor:
     """One IAF flow on a chunk: x [N, T, 1] = the T samples that follow what each of the N sessions has seen, `cond` the chunk's own
     frames (a RepeatedCondition of T / hop + 1 frames per session).  `hist` carries the history blocks and the slot table of the call
     (read / written block per session); `scalar_off` and `row_off[g][j]` (j >= 1) say where this flow's histories lie in a block.
@@ -1459,10 +1571,15 @@ def run_flow_stream(nets: Sequence, x: torch.Tensor, cond, precision: Optional[s
       * else L streaming layer launches of both nets (G = 2), then the affine (PWV_PERSIST=0 keeps this route in use and tested).
     Same bits, same written history rows either way.  Only enqueues, like run_flow; the written blocks become the sessions' state
     when the caller flips their generation -- so a push whose persistent launch gave up is rerun by verified_call on the per-layer
-    launches (persist_suspended()) from the same generation."""
+    launches (persist_suspended()) from the same generation.
+    With `geom` (a VarlenGeometry) the chunk is RAGGED: session i brings geom.lengths[i] rows, x is the packed [R, 1], `cond` spans the
+    packed frames (geom.frames[i] per session) and `slot_tab` is the device int32 [N, 2] table hist.slot_tab points at
+    (_run_flow_stream_ragged: packed persistent launches, else the sessions grouped by length on the routes above)."""
     why = stream_refusal(nets, cond, precision)
     if why is not None:
         raise _lib.PwvError('run_flow_stream: no streaming form: ' + why)
+    if geom is not None:
+        return _run_flow_stream_ragged(nets, x, cond, precision, hist, scalar_off, row_off, geom, slot_tab)
     prec = PRECISIONS[precision or DEFAULT_PRECISION]
     x = _require_cuda_f32(x, 'input')
     net0 = nets[0]

@@ -241,21 +241,17 @@ def generate(case='default', ckpt=None, debug=False, varlen=False, seed=None, st
 
 def _generate_stream(model, mels, frames):
     """--stream: input i is session i of one StreamingVocoder; every tick gives each unfinished session its next `frames` frames (the
-    rest at its end).  Sessions that get the same number of frames in the same state share a push (verify=True: explicit, as above).
-    Returns the [len_i, 1] waveforms."""
+    rest at its end) in ONE ragged push (push_varlen: fresh and running sessions and short last chunks share the launch; verify=True:
+    explicit, as above).  Returns the [len_i, 1] waveforms."""
     s = model.open_stream(slots=len(mels))
     pos, outs = [0] * len(mels), [[] for _ in mels]
     while any(p < m.shape[0] for p, m in zip(pos, mels)):
-        groups = {}
-        for i, m in enumerate(mels):
-            f = min(frames, m.shape[0] - pos[i])
-            if f > 0:
-                groups.setdefault((f, pos[i] == 0), []).append(i)
-        for (f, _), slots in sorted(groups.items()):
-            got = s.push(torch.stack([mels[i][pos[i]:pos[i] + f] for i in slots]), slots=slots, verify=True)
-            for k, i in enumerate(slots):
-                outs[i].append(got[k])
-                pos[i] += f
+        slots = [i for i, m in enumerate(mels) if pos[i] < m.shape[0]]
+        counts = [min(frames, mels[i].shape[0] - pos[i]) for i in slots]
+        got = s.push_varlen([mels[i][pos[i]:pos[i] + f] for i, f in zip(slots, counts)], slots=slots, verify=True)
+        for k, (i, f) in enumerate(zip(slots, counts)):
+            outs[i].append(got[k])
+            pos[i] += f
     return [torch.cat(o) for o in outs]
 
 

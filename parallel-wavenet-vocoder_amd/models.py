@@ -252,7 +252,10 @@ class IAFVocoder(object):
         than overlap-and-discard).  One session (measured at chunks of 800 .. 8000 samples), two, or four with chunks under 1600
         samples: overlap-and-discard through __call__ (timeshard.chain_halo samples recomputed per chunk, one persistent launch per
         flow) is quicker than the ~65 launches of a push, which the host's enqueue bounds at ~0.7 ms; the crossover is at four
-        sessions x 1600 samples -- DESIGN.md section 9 "Streaming" has the measured table.  `hist_alloc` (tests):
+        sessions x 1600 samples -- DESIGN.md section 9 "Streaming" has the measured table.  A RAGGED tick -- sessions that got different
+        numbers of frames, new sessions next to running ones, a short last chunk -- is one call too: ``s.push_varlen([mel_i [f_i,
+        n_mels], ...], slots=[...])`` returns the [T_i, 1] pieces (views of one packed tensor, `.packed`) from ONE packed launch per flow
+        instead of one push per (frame count, fresh or running) group; same bits, same transaction rule.  `hist_alloc` (tests):
         called with a float count, returns the zero-filled float32 buffer the histories live in."""
         from .stream import StreamingVocoder
         return StreamingVocoder(self, slots, hist_alloc=hist_alloc)

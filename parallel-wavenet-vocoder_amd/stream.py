@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from typing import List, Optional, Sequence
+from typing import List, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -80,10 +80,51 @@ def push_samples(frames: int, fresh: bool, hop: int) -> int:
     return (frames - (1 if fresh else 0)) * hop
 
 
+class RaggedPlan(NamedTuple):
+    """ragged_plan: the bookkeeping of one push_varlen that needs no device."""
+    samples: List[int]       # T_i per session of the call
+    launch: List[int]        # the sessions (indices into the call) that take part in the launches: T_i > 0, in call order
+    cu_rows: List[int]       # prefix sums of T_i over `launch` (len(launch) + 1 entries): session launch[k] holds rows cu_rows[k] .. cu_rows[k+1]-1
+    cu_frames: List[int]     # ... and of its T_i / hop + 1 frames in the packed mel (a running session: the kept frame + its f_i, a fresh one: its f_i)
+
+
+def ragged_plan(frames: Sequence[int], fresh: Sequence[bool], hop: int) -> RaggedPlan:
+    """What a push of frames[i] >= 1 mel frames to session i (fresh[i]: no frame kept yet) comes to: T_i = push_samples(frames[i],
+    fresh[i], hop) samples each; the sessions with T_i > 0 form the packed launch, session k of it with T / hop + 1 frames -- the
+    packed layout's t_mel = len / hop + 1.  A fresh session given one frame has T = 0: it is committed (its frame kept) and launches
+    nothing."""
+    if len(frames) != len(fresh):
+        raise ValueError('%d frame counts for %d sessions' % (len(frames), len(fresh)))
+    for f in frames:
+        if int(f) < 1:
+            raise ValueError('every session of a push needs at least one frame, got %r' % (f,))
+    samples = [push_samples(int(f), bool(fr), hop) for f, fr in zip(frames, fresh)]
+    launch = [i for i, t in enumerate(samples) if t > 0]
+    cu_rows, cu_frames = [0], [0]
+    for i in launch:
+        cu_rows.append(cu_rows[-1] + samples[i])
+        cu_frames.append(cu_frames[-1] + samples[i] // hop + 1)
+    return RaggedPlan(samples, launch, cu_rows, cu_frames)
+
+
+class RaggedOutput(list):
+    """What StreamingVocoder.push_varlen returns: the [T_i, 1] pieces of the call's sessions (views; empty for a fresh session given one
+    frame), with the packed [sum T_i, 1] result as `.packed` (as models.VarlenOutput)."""
+
+    def __init__(self, packed, samples):
+        pieces, r = [], 0
+        for t in samples:
+            pieces.append(packed[r:r + t])
+            r += t
+        super().__init__(pieces)
+        self.packed = packed
+
+
 class StreamingVocoder(object):
     """IAFVocoder.open_stream(slots): `slots` independent sessions over the model's weights.
 
         wav = s.push(mel, slots=[0, 3])      # mel [n, f, n_mels] -> wav [n, samples, 1]
+        wavs = s.push_varlen([mel_a, mel_b], slots=[1, 2])      # a RAGGED tick: [f_i, n_mels] each, fresh and running mixed -> [T_i, 1] each
         s.reset(3); s.emitted(0); st = s.state(0); s.load_state(1, st)
 
     New weights in the store (store.version) re-plan the kernels' packed weights at the next push; open sessions KEEP their
@@ -297,4 +338,121 @@ class StreamingVocoder(object):
             x = z
             for i, iaf in enumerate(flows):
                 x = engine.run_flow_stream(iaf.nets(), x, cond, precision, sa, lay.scalar_off[i], lay.row_off[i])
+        return x
+
+    # -- a ragged push ---------------------------------------------------------------------------------------------------
+    def push_varlen(self, mels, slots=None, z=None, seeds=None, verify=None):
+        """A RAGGED tick: session slots[i] (default: all slots, in order) gets the f_i >= 1 frames mels[i] [f_i, n_mels] -- every session
+        its own count, fresh and running sessions mixed freely -- in ONE launch per flow.  Session i yields T_i = push_samples(f_i,
+        fresh_i, hop) samples; returns a RaggedOutput: the list of [T_i, 1] pieces, views of one packed [sum T_i, 1] tensor (`.packed`).  A
+        fresh session given one frame yields an empty piece: its frame is kept, it is running afterwards, and it takes part in no launch.
+        ``z``: the noise, packed [sum T_i, 1] or a list of [T_i, 1].  ``seeds``: one entry per slot, an integer for a fresh slot (its
+        noise stream; None: the seed given at reset, else drawn from the OS), None for a running one (an integer there is a ValueError,
+        as in push).  Without ``z`` slot i draws from its own stream at counter emitted(i).
+        Everything push promises holds: a transaction (reads generation g, writes 1 - g, the flip after verification), the range guard's
+        rerun in exact fp32 from the same state on the same noise, the rerun of a give-up on the fallback route, verify=False /
+        PWV_ASYNC=1 with verify().  A session may be advanced by push and push_varlen alternately: same bits either way."""
+        self._settled('push_varlen')
+        if not isinstance(mels, (list, tuple)) or not mels:
+            raise ValueError('mels must be a non-empty list of [f, n_mels] tensors')
+        slots = list(range(self.n_slots)) if slots is None else [self._slot(v) for v in slots]
+        n = len(slots)
+        if n != len(mels) or len(set(slots)) != n:
+            raise ValueError('slots must be distinct, one per mel (%d mels), got %r' % (len(mels), slots))
+        for i, m in enumerate(mels):
+            if not hasattr(m, 'dim') or m.dim() != 2 or m.shape[0] < 1 or m.shape[1] != self.n_mels:
+                raise ValueError('mels[%d] must be [f >= 1, %d], got %s' % (i, self.n_mels, tuple(getattr(m, 'shape', ()))))
+        fresh = [not self._running[s] for s in slots]
+        plan = ragged_plan([m.shape[0] for m in mels], fresh, self.hop)
+        total = plan.cu_rows[-1]
+        if seeds is not None:
+            if z is not None:
+                raise ValueError('seeds and z exclude each other: seeds draw the noise, z is the noise')
+            seeds = list(seeds.tolist() if hasattr(seeds, 'tolist') else seeds)
+            if len(seeds) != n:
+                raise ValueError('seeds holds %d values for %d slots' % (len(seeds), n))
+            for i, v in enumerate(seeds):
+                if v is not None and not fresh[i]:
+                    raise ValueError('seeds[%d]: a seed is given at a slot\'s first push (or reset): slot %d is running' % (i, slots[i]))
+            seeds = [None if v is None else self._check_seed(v) for v in seeds]
+        if isinstance(z, (list, tuple)):      # (each piece against its own session: a split that only adds up would misassign)
+            if len(z) != n:
+                raise ValueError('z holds %d pieces for %d sessions' % (len(z), n))
+            for i, v in enumerate(z):
+                if tuple(getattr(v, 'shape', ())) != (plan.samples[i], 1):
+                    raise ValueError('z[%d] must be %s, got %s' % (i, (plan.samples[i], 1), tuple(getattr(v, 'shape', ()))))
+            parts = [engine._require_cuda_f32(z[i], 'z[%d]' % i) for i in plan.launch]
+            z = (parts[0] if len(parts) == 1 else torch.cat(parts)) if parts else torch.empty((0, 1), dtype=torch.float32, device=self.device)
+        elif z is not None:
+            z = engine._require_cuda_f32(z, 'z')
+            if tuple(z.shape) != (total, 1):
+                raise ValueError('z must be the packed [%d, 1], got %s' % (total, tuple(z.shape)))
+        mels = [engine._require_cuda_f32(m, 'mels[%d]' % i) for i, m in enumerate(mels)]
+        engine.raise_if_range_flag('an earlier call')
+        new_seeds = None
+        if z is None:
+            new_seeds = [seeds[i] if (seeds is not None and seeds[i] is not None) else
+                         (self._seed[s] if self._seed[s] is not None else int.from_bytes(os.urandom(7), 'little')) for i, s in enumerate(slots)]
+        idx = torch.tensor(slots, dtype=torch.int64).pin_memory().to(self.device, non_blocking=True)
+        last = torch.stack([m[-1] for m in mels])
+
+        def commit():
+            for i, s in enumerate(slots):
+                self._gen[s] ^= 1
+                self._running[s] = True
+                self._emitted[s] += plan.samples[i]
+                if new_seeds is not None:
+                    self._seed[s] = new_seeds[i]
+            self._kept.index_copy_(0, idx, last)
+
+        if not plan.launch:            # one frame each to fresh slots: nothing to generate yet
+            commit()
+            return RaggedOutput(torch.empty((0, 1), dtype=torch.float32, device=self.device), plan.samples)
+        geom = engine.VarlenGeometry([plan.samples[i] for i in plan.launch], self.hop, self.device)
+        assert geom.cu_rows_host == plan.cu_rows and geom.cu_frames_host == plan.cu_frames
+        # the packed mel: a running session brings its kept frame in front of its frames, a fresh one does not
+        pieces = []
+        for i in plan.launch:
+            if not fresh[i]:
+                pieces.append(self._kept[slots[i]:slots[i] + 1])
+            pieces.append(mels[i])
+        mel = pieces[0] if len(pieces) == 1 else torch.cat(pieces)
+        if z is None:
+            z = engine.logistic_noise_packed_op(geom.cu_rows, geom.stream_table([(new_seeds[i], self._emitted[slots[i]]) for i in plan.launch]),
+                                                geom.rows)
+        # session k of the launches reads block 2 s + gen, writes block 2 s + 1 - gen
+        tab = geom._upload([[2 * slots[i] + self._gen[slots[i]], 2 * slots[i] + 1 - self._gen[slots[i]]] for i in plan.launch], torch.int32)
+        out = engine.verified_call(lambda prec: self._enqueue_varlen(prec or self.model.precision, mel, z, tab, geom), verify)
+        verified = ((not engine.ASYNC) if verify is None else bool(verify)) and getattr(engine._tls, 'depth', 0) == 0
+        if verified and not torch.cuda.is_current_stream_capturing():
+            commit()
+        else:
+            self._pending = commit
+        return RaggedOutput(out, plan.samples)
+
+    def _enqueue_varlen(self, precision, mel, z, tab, geom):
+        """The ragged chunk's launches on the current stream: the prologue on the packed frames (per frame: as in the packed one-shot
+        forward), the carry-over in its packed form (one launch; session n's own T_n decides what it moves; skipped when every T_n
+        reaches the largest history), then per flow engine.run_flow_stream with the geometry: ONE packed persistent streaming launch,
+        or the sessions grouped by length on the uniform routes.  Reads the sessions' current generation, writes the other one."""
+        model = self.model
+        store = model.store or get_default_store()
+        lay = self.layout
+        sa = _lib.StreamArgs()
+        sa.hist_rd = sa.hist_wr = self._hist.data_ptr()
+        sa.block_stride, sa.slot_tab = lay.block_floats, tab.data_ptr()
+        sa.carry_tab, sa.n_carry = self._carry_tab.data_ptr(), len(lay.carry)
+        with variable_scope('iaf_vocoder'):
+            flows = model._flows(store, False, precision)
+            nets = [net for iaf in flows for net in iaf.nets()]
+            with variable_scope('cond'):
+                cond = model._condition(mel.unsqueeze(0), False, strides=[4, 4, 5], store=store, precision=precision, nets=nets, length=geom.rows)
+            engine.project_all(nets, cond, precision=precision)
+            if min(geom.lengths) < lay.max_rows:
+                sa.cu_rows = geom.cu_rows.data_ptr()
+                _lib.check(_lib.lib().pwv_stream_carry_f32(ctypes.byref(sa), geom.n, 0, engine._stream()), 'pwv_stream_carry_f32')
+                sa.cu_rows = None
+            x = z
+            for i, iaf in enumerate(flows):
+                x = engine.run_flow_stream(iaf.nets(), x, cond, precision, sa, lay.scalar_off[i], lay.row_off[i], geom=geom, slot_tab=tab)
         return x

@@ -17,6 +17,18 @@ count of the library's launch calls in one untimed push per streaming leg: `laun
 instantiation per persistent launch}}.  Prints one JSON line.
 
     python tools/stream_bench.py [--steps 20] [--warmup 5] [--precision f16x3] [--sessions 1,8,32] [--chunks 800,1600,8000]
+
+--ragged ("Ragged pushes"): a tick whose sessions get DIFFERENT numbers of frames.  Cells: S = 8 and 32 running
+sessions, session i given 800 * (1 + i % 4) samples (four distinct lengths, R = 2000 S rows), and one "utterance ends" cell: 31 x 1600
+and 1 x 80.  Legs, same protocol (verify=False, one synchronisation at the end of the tick, median of --steps after --warmup, the round
+twice):
+  ragged    ONE push_varlen of all sessions
+  grouped   what a caller did before push_varlen: one push per distinct length (the API settles a push before the next: verify=False
+            and verify() per group; the last verify() is the tick's synchronisation)
+  uniform   one push of S sessions x the mean length (rounded up to a frame): about the same rows without raggedness, the floor
+`ragged_over_grouped` / `ragged_over_uniform` per round, and `spread` = the largest difference between the two medians of a leg.
+
+    python tools/stream_bench.py --ragged [--steps 20] [--warmup 5] [--precision f16x3]
 """
 import argparse
 import json
@@ -36,6 +48,7 @@ def main():
     ap.add_argument('--precision', default='f16x3', choices=['f16x3', 'f32'])
     ap.add_argument('--sessions', default='1,8,32')
     ap.add_argument('--chunks', default='800,1600,8000')
+    ap.add_argument('--ragged', action='store_true', help='the ragged-tick cells (push_varlen against grouped pushes) instead of the default legs')
     args = ap.parse_args()
 
     import numpy as np
@@ -91,6 +104,63 @@ def main():
                     return fn(*a)
                 return wrapped
         return Counting()
+
+    if args.ragged:
+        out = {'mode': 'ragged', 'precision': args.precision, 'steps': args.steps, 'warmup': args.warmup, 'cells': []}
+        cells = [('mixed_%d' % S, [800 * (1 + i % 4) for i in range(S)]) for S in (8, 32)] + [('utterance_ends', [1600] * 31 + [80])]
+        for name, lens in cells:
+            S = len(lens)
+            model = IAFVocoder(batch_size=S, length=hop, store=store, precision=args.precision)
+            stream = model.open_stream(slots=S)
+            warm = -(-(halo + hop) // hop) * hop
+            stream.push(rand(S, warm // hop + 1, cfg.n_mels), z=rand(S, warm, 1))        # steady state: every session running
+            mels, zs = [rand(T // hop, cfg.n_mels) for T in lens], [rand(T, 1) for T in lens]
+            groups = {}
+            for i, T in enumerate(lens):
+                groups.setdefault(T, []).append(i)
+            grouped = [(members, torch.stack([mels[i] for i in members]), torch.stack([zs[i] for i in members])) for members in groups.values()]
+            mean = -(-sum(lens) // (S * hop)) * hop
+            mel_u, z_u = rand(S, mean // hop, cfg.n_mels), rand(S, mean, 1)
+
+            def push_grouped():
+                for k, (members, mel_g, z_g) in enumerate(grouped):
+                    if k:
+                        stream.verify()
+                    stream.push(mel_g, slots=members, z=z_g, verify=False)
+
+            legs = {
+                'ragged': (lambda: stream.push_varlen(mels, z=zs, verify=False), stream.verify),
+                'grouped': (push_grouped, stream.verify),
+                'uniform': (lambda: stream.push(mel_u, z=z_u, verify=False), stream.verify),
+            }
+            cell = {'cell': name, 'sessions': S, 'lengths': sorted(groups), 'rows': sum(lens), 'uniform_rows': S * mean, 'groups': len(groups),
+                    'launches': {}}
+            for leg in legs:        # one untimed tick per leg: what it enqueues
+                log, calls = [], []
+                engine.EVENT_LOG, _lib.lib = log, (lambda: counting(calls))
+                try:
+                    legs[leg][0]()
+                    legs[leg][1]()
+                finally:
+                    engine.EVENT_LOG, _lib.lib = None, real_lib
+                cell['launches'][leg] = {'calls': len([c for c in calls if c not in NOT_LAUNCHES]),
+                                         'flows': [e[0] + ('_' + e[3] if e[0] == 'stream_ragged' else '_stream' if len(e) > 8 and e[8] else '') for e in log],
+                                         'short_input': [e[7] for e in log if e[0] == 'persist']}
+            for leg in legs:
+                cell[leg] = {'ms': [], 'enqueue_ms': []}
+            for _ in range(2):
+                for leg, (fn, sync) in legs.items():
+                    ms, host = timed(fn, sync)
+                    cell[leg]['ms'].append(round(ms, 3))
+                    cell[leg]['enqueue_ms'].append(round(host, 3))
+            cell['spread'] = round(max(abs(cell[leg]['ms'][0] - cell[leg]['ms'][1]) for leg in legs), 3)
+            cell['ragged_over_grouped'] = [round(a / b, 3) for a, b in zip(cell['ragged']['ms'], cell['grouped']['ms'])]
+            cell['ragged_over_uniform'] = [round(a / b, 3) for a, b in zip(cell['ragged']['ms'], cell['uniform']['ms'])]
+            cell['ragged_not_slower_than_grouped'] = all(a <= b + cell['spread'] for a, b in zip(cell['ragged']['ms'], cell['grouped']['ms']))
+            out['cells'].append(cell)
+            print('# %s' % json.dumps(cell), file=sys.stderr)
+        print(json.dumps(out))
+        return
 
     out = {'precision': args.precision, 'steps': args.steps, 'warmup': args.warmup, 'chain_halo': halo, 'cells': []}
     for S in [int(v) for v in args.sessions.split(',')]:
