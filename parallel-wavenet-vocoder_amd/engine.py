@@ -768,6 +768,8 @@ class _Path(NamedTuple):
     two: bool               # per-layer launches of G = 2 nets: each net's chain on a side stream of its own (TWO_STREAMS)
 
     persist = property(lambda self: self.runs is not None)     # (else per-layer launches)
+    # the WHOLE flow inside the persistent launches -- layer 0 and the tail included: the only form the packed and the streaming launches have
+    whole_flow = property(lambda self: self.runs is not None and self.tail and self.first_fused)
 
 
 def _choose_path(net0, plans, mode: str, n: int, t: int, max_workgroups: int, cond_geom) -> _Path:
@@ -820,7 +822,7 @@ def _run_stack_persist(path: _Path, nets, plans, projs, bufs, outs, x, x_limit, 
     last launch where `path.tail` (otherwise one more launch for them); all nets of the flow in every launch, all on the current
     stream.  `bufs[g]` holds THREE tile32 buffers: the persistent launch rotates through them (include/pwv_hip.h,
     pwv_persist_args.x_ring).  With `geom` (a VarlenGeometry; x is then its [1, R, 1]) every launch carries the packed batch's
-    fields.  With `stream_hist` = (pwv_stream_args, row_off[g][layer]) the launches are the STREAMING ones (run_flow_stream): every
+    fields.  With `stream_hist` = (pwv_stream_args, row_off[g][layer]) the launches are the STREAMING ones: every
     run is told where its own layers' row histories -- and the tail's -- lie in a block.  Returns True when the affine was evaluated
     by the launch."""
     lib, s = _lib.lib(), _stream()
@@ -1020,13 +1022,18 @@ def run_nets(nets: Sequence, x: torch.Tensor, cond, precision: Optional[str] = N
 
 def run_flow(nets: Sequence, x: torch.Tensor, cond, precision: Optional[str] = None) -> torch.Tensor:
     """One IAF flow (modules.py:53-60): out = x * scale + shift with (scale, shift) = the outputs of two scalar-input nets, or
-    the two outputs of one shared net.  On the default path the whole flow is ONE persistent launch (the affine is evaluated
-    inside it, pwv_persist_args.affine_x); otherwise the nets' launches are followed by the affine kernel."""
+    the two outputs of one shared net (route 1 of DESIGN.md section 9 "Routes", which lists all four).  On the default path the
+    whole flow is ONE persistent launch (the affine is evaluated inside it, pwv_persist_args.affine_x); otherwise the nets' launches
+    are followed by the affine kernel."""
     x = _require_cuda_f32(x, 'input')
     out = torch.empty_like(x)
     outs, done = _run_nets(nets, x, cond, precision, 0, out)
-    if done:
-        return out
+    return out if done else _flow_affine(x, outs)
+
+
+def _flow_affine(x: torch.Tensor, outs: List[torch.Tensor]) -> torch.Tensor:
+    """The flow's affine x * scale + shift as a launch of its own (where the persistent launch did not evaluate it): (scale, shift) =
+    the outputs of the flow's two nets, or the two interleaved outputs of its one shared net."""
     if len(outs) == 2:
         return iaf_affine_op(x, outs[0], outs[1], 1)
     flat = outs[0].reshape(-1)
@@ -1036,6 +1043,16 @@ def run_flow(nets: Sequence, x: torch.Tensor, cond, precision: Optional[str] = N
 # ---- packed ("varlen") batches: utterances of different lengths in one forward (include/pwv_hip.h, pwv_persist_args.cu_rows) ------------
 VARLEN_PADDED = 0        # flows of packed batches that took the padded fallback (tests / tools read it)
 VARLEN_PADDED_WHY = None  # ... and why the last of them did (graph.GraphedPackedVocoder refuses with it)
+
+
+def _remap_bank(bank: dict, total_frames: int, remap) -> dict:
+    """A projection bank (RepeatedCondition.proj_bank) over other frame rows: the bank's column blocks are views of ONE [F, cols] GEMM
+    output, so `remap` (rows in, rows out: a padding, a gather) is applied to that once and the blocks keep their column offsets.  The
+    prologue is per frame: a remapped row holds the bits a prologue over the remapped frames would compute."""
+    base = next(iter(bank.values()))
+    full = base.as_strided((total_frames, base.stride(0)), (base.stride(0), 1), 0)
+    rows = remap(full)
+    return {k: rows[:, v.storage_offset() - full.storage_offset():][:, :v.shape[1]] for k, v in bank.items()}
 
 
 class VarlenGeometry:
@@ -1153,21 +1170,45 @@ class VarlenGeometry:
             padded = RepeatedCondition(self.pad_frames(cond.frames), cond.hop, cond.offset, self.max_len)
             bank = getattr(cond, 'proj_bank', None)
             if bank is not None:
-                # the bank's column blocks are views of one [F, cols] GEMM output: pad that once, keep the column offsets
-                base = next(iter(bank.values()))
-                full = base.as_strided((self.total_frames, base.stride(0)), (base.stride(0), 1), 0)
-                fp = self.pad_frames(full).reshape(self.n * self.max_frames, base.stride(0))
-                padded.proj_bank = {k: fp[:, v.storage_offset() - full.storage_offset():][:, :v.shape[1]] for k, v in bank.items()}
+                padded.proj_bank = _remap_bank(bank, self.total_frames, lambda full: self.pad_frames(full).reshape(self.n * self.max_frames, -1))
         else:
             padded = self.pad_rows(cond)
         self._cond_cache = (weakref.ref(cond), padded)
         return padded
 
 
+def _instance_norm(nets) -> bool:
+    """Instance normalisation ('in') inside a net: its statistics span the whole time axis, so neither a packed or padded batch nor a
+    chunk of a stream computes them (run_flow_varlen and stream_refusal refuse it)."""
+    return any(getattr(n, 'normalize', None) == 'in' for n in nets)
+
+
+def _flow_structure(nets, cond, precision: Optional[str] = None) -> Optional[str]:
+    """Which structural property keeps a flow (its nets) off the forms that run it whole inside the fused launches -- the packed batch's
+    and the streaming ones -- as a key, or None: 'samples' (per-sample conditioning), 'skip' (skip accumulation), 'f16' (the fp16
+    storage mode), 'shape' (not two scalar-in / scalar-out nets or one shared net of two outputs, all fused-capable, of one structure
+    and one precision).  varlen_fallback_reason and stream_refusal word them."""
+    net0 = nets[0]
+    if cond is not None and not isinstance(cond, RepeatedCondition):
+        return 'samples'
+    if net0.use_skip_connection:
+        return 'skip'
+    if (precision or net0.precision or DEFAULT_PRECISION) == 'f16':
+        return 'f16'
+    if not (all(n.fused_supported(cond) for n in nets) and all(_same_structure(net0, n) for n in nets)
+            and all(n.precision == net0.precision for n in nets) and net0.in_channels == 1
+            and ((len(nets) == 2 and net0.out_channels == 1) or (len(nets) == 1 and net0.out_channels == 2))):
+        return 'shape'
+    return None
+
+
+_VARLEN_STRUCTURE_WHY = {'samples': 'per-sample conditioning', 'skip': 'skip accumulation', 'f16': "precision 'f16'",
+                         'shape': 'the flow has no fused form'}
+
+
 def varlen_fallback_reason(nets, cond, geom: VarlenGeometry, precision: Optional[str] = None) -> Optional[str]:
     """Why a flow (its nets) of a packed batch takes the padded fallback -- or None: the persistent launches of the packed form, where
     the library plans the R rows persistently with layer 0 and the tail inside the launches (what a uniform batch of R rows would take)."""
-    net0 = nets[0]
     if not geom.persistent_ok():
         return 'an utterance shorter than %d samples' % _lib.VARLEN_MIN_ROWS
     if PERSIST is False:
@@ -1176,23 +1217,13 @@ def varlen_fallback_reason(nets, cond, geom: VarlenGeometry, precision: Optional
         return 'persistent launches suspended after a give-up'
     if PERSIST == 'auto' and geom.rows > PERSIST_AUTO_MAX_ROWS:
         return 'more than PERSIST_AUTO_MAX_ROWS rows'
-    if cond is not None and not isinstance(cond, RepeatedCondition):
-        return 'per-sample conditioning'
-    if net0.use_skip_connection:
-        return 'skip accumulation'
-    if (precision or net0.precision or DEFAULT_PRECISION) == 'f16':
-        return "precision 'f16'"
-    if not (all(n.fused_supported(cond) for n in nets) and all(_same_structure(net0, n) for n in nets)
-            and all(n.precision == net0.precision for n in nets) and net0.in_channels == 1
-            and ((len(nets) == 2 and net0.out_channels == 1) or (len(nets) == 1 and net0.out_channels == 2))):
-        return 'the flow has no fused form'
-    return None
+    return _VARLEN_STRUCTURE_WHY.get(_flow_structure(nets, cond, precision))
 
 
 def run_flow_varlen(flow, x: torch.Tensor, cond, geom: VarlenGeometry, precision: Optional[str] = None) -> torch.Tensor:
     """One IAF flow (LinearIAFLayer / SharedIAFLayer) over a packed batch: x [R, 1] -> [R, 1], `cond` over the packed frames [1, F, C]
-    (length R) or None.  The path is chosen once: the persistent launches of the packed form (pwv_persist_args.cu_rows) wherever a
-    uniform batch of R rows would run the flow as persistent launches with layer 0 and the tail inside them; otherwise
+    (length R) or None (route 2 of DESIGN.md section 9 "Routes").  The path is chosen once: the persistent launches of the packed
+    form (pwv_persist_args.cu_rows) wherever a uniform batch of R rows would run the flow whole inside its persistent launches; otherwise
     (varlen_fallback_reason) the PADDED fallback: the flow's ordinary path on the zero-padded [N, max_len, 1] batch, gathered back.
     Both give the same bits: every stage of such a flow is causal and row-local in the batch, so the zero rows behind an utterance
     change nothing in front of them.  Instance normalisation ('in') is not row-local -- its statistics span the time axis, padding
@@ -1200,7 +1231,7 @@ def run_flow_varlen(flow, x: torch.Tensor, cond, geom: VarlenGeometry, precision
     like run_flow."""
     global VARLEN_PADDED, VARLEN_PADDED_WHY
     nets = list(flow.nets())
-    if any(getattr(n, 'normalize', None) == 'in' for n in nets):
+    if _instance_norm(nets):
         raise _lib.PwvError("run_flow_varlen: nets with instance normalisation ('in') have no packed or padded form (its statistics "
                             "span the time axis); run the utterances one by one")
     x = _require_cuda_f32(x, 'input')
@@ -1213,10 +1244,7 @@ def run_flow_varlen(flow, x: torch.Tensor, cond, geom: VarlenGeometry, precision
         res = _run_nets(nets, x3, cond, precision or nets[0].precision, 0, out, geom)
         if res is not None:
             outs, done = res
-            if not done:
-                out = (iaf_affine_op(x3, outs[0], outs[1], 1) if len(outs) == 2
-                       else iaf_affine_op(x3, outs[0].reshape(-1), outs[0].reshape(-1)[1:], 2))
-            return out.reshape(geom.rows, 1)
+            return (out if done else _flow_affine(x3, outs)).reshape(geom.rows, 1)
         why = 'the library plans this stack at %d rows per layer' % geom.rows
     VARLEN_PADDED += 1
     VARLEN_PADDED_WHY = why
@@ -1224,12 +1252,64 @@ def run_flow_varlen(flow, x: torch.Tensor, cond, geom: VarlenGeometry, precision
     return geom.unpad_rows(y)
 
 
+class _FlowPrep(NamedTuple):
+    """What every route of a flow ("Routes") settles before it enqueues (_prepare_flow)."""
+    precision: str          # the arithmetic's name AFTER the pack-time demotion ('f16x3' whose weights leave fp16's range runs as 'f32')
+    mode: str               # conditioning: 'none' | 'frames' | 'samples'
+    cond_geom: tuple        # (hop, offset, frames per utterance) of a frame-rate condition
+    cond_t: Optional[torch.Tensor]      # the per-sample condition in the form the kernels of this precision read (_cond_operand)
+    plans: List[NetPlan]
+    x_limit: float          # the run-time bound on the flow's input (the smallest of the plans')
+    path: _Path
+
+
+def _prepare_flow(nets: Sequence, x: torch.Tensor, cond, precision: Optional[str], max_workgroups: int = 0) -> _FlowPrep:
+    """The preparation of a forward of `nets` (one structure) on x [N, T, C], N * T > 0: the condition checked, the plans fetched --
+    in exact fp32 instead where the split-fp16 plans' pack-time bounds fail --, the launch path chosen.  Enqueues at most the
+    conversion of a per-sample condition."""
+    name = precision or DEFAULT_PRECISION
+    prec = PRECISIONS[name]
+    net0 = nets[0]
+    mode, cond_geom, cond_t = _check_condition(net0, cond, x)
+    if prec == _lib.PREC_F16 and (x.shape[2] != 1 or net0.use_skip_connection):
+        raise _lib.PwvError("precision 'f16' supports scalar-input nets without skip accumulation only")
+    plans = [get_plan(net, mode, prec) for net in nets]
+    if prec == _lib.PREC_F16X3 and not all(p.f16x3_ok and p.x_limit > 0 for p in plans):
+        # some weight / bound leaves fp16's exponent range: this net runs in the exact fp32 arithmetic instead
+        key = tuple(net.full_scope for net in nets)
+        if key not in _range_warned:
+            _range_warned.add(key)
+            import warnings
+            warnings.warn("pwv: weights of %s exceed the range of the split-fp16 arithmetic; using precision 'f32' for it" % (key,))
+        return _prepare_flow(nets, x, cond, 'f32', max_workgroups)
+    x_limit = min(p.x_limit for p in plans)
+    if prec == _lib.PREC_F16X3:
+        _log_range('flow_input', x, x_limit, [p.range_bounds for p in plans])
+    for net, plan in zip(nets, plans):
+        assert plan.n_layers == len(net.dilations) and plan.with_skip == bool(net.use_skip_connection)
+    if cond_t is not None:
+        cond_t = _cond_operand(cond_t, prec)
+    path = _choose_path(net0, plans, mode, x.shape[0], x.shape[1], max_workgroups, cond_geom)
+    return _FlowPrep(name, mode, cond_geom, cond_t, plans, x_limit, path)
+
+
+def _run_flow_persist(prep: _FlowPrep, nets, x: torch.Tensor, cond, affine_out: Optional[torch.Tensor], geom=None, stream_hist=None):
+    """The whole stack of `nets` as the persistent launches of prep.path on the current stream: ([one [N, T, Q] tensor per net], whether
+    `affine_out` = x*s + b was written by the launches).  `geom` and `stream_hist` as _run_stack_persist takes them."""
+    plans, path = prep.plans, prep.path
+    projs = _projections(cond, prep.mode, plans, prep.precision, None)
+    row_stride = projs[0].stride(0)      # (all nets' columns where project_all's one GEMM made them, else 128 * L)
+    bufs = _causal_front(x, nets[0], plans, path, prep.x_limit)
+    outs = [torch.empty((x.shape[0], x.shape[1], nets[0].out_channels), dtype=torch.float32, device=x.device) for _ in nets]
+    aff = (x, affine_out) if (affine_out is not None and x.shape[2] == 1) else None
+    return outs, _run_stack_persist(path, nets, plans, projs, bufs, outs, x, prep.x_limit, row_stride, prep.cond_geom, aff, geom, stream_hist)
+
+
 def _run_nets(nets: Sequence, x: torch.Tensor, cond, precision: Optional[str], max_workgroups: int, affine_out: Optional[torch.Tensor],
               geom=None):
     """run_nets / run_flow: ([one [N, T, Q] tensor per net], whether `affine_out` = x*s + b was written by the launches).
     With `geom` (run_flow_varlen: x = the packed batch as [1, R, 1]) only the persistent path with layer 0 and the tail inside its
     launches is taken; where that path is not the one a uniform batch of R rows would take, nothing is enqueued and None returned."""
-    prec = PRECISIONS[precision or DEFAULT_PRECISION]
     x = _require_cuda_f32(x, 'input_batch')
     if x.dim() != 3:
         raise ValueError('input_batch must be [N, T, C], got %s' % (tuple(x.shape),))
@@ -1242,37 +1322,17 @@ def _run_nets(nets: Sequence, x: torch.Tensor, cond, precision: Optional[str], m
         raise ValueError('input has %d channels, net expects %d' % (qin, net0.in_channels))
     if n * t == 0:
         return [torch.empty((n, t, net0.out_channels), dtype=torch.float32, device=x.device) for _ in nets], False
-    mode, cond_geom, cond_t = _check_condition(net0, cond, x)
-    if prec == _lib.PREC_F16 and (qin != 1 or net0.use_skip_connection):
-        raise _lib.PwvError("precision 'f16' supports scalar-input nets without skip accumulation only")
-    plans = [get_plan(net, mode, prec) for net in nets]
-    if prec == _lib.PREC_F16X3 and not all(p.f16x3_ok and p.x_limit > 0 for p in plans):
-        # some weight / bound leaves fp16's exponent range: this net runs in the exact fp32 arithmetic instead
-        key = tuple(net.full_scope for net in nets)
-        if key not in _range_warned:
-            _range_warned.add(key)
-            import warnings
-            warnings.warn("pwv: weights of %s exceed the range of the split-fp16 arithmetic; using precision 'f32' for it" % (key,))
-        return _run_nets(nets, x, cond, 'f32', max_workgroups, affine_out, geom)
-    x_limit = min(p.x_limit for p in plans)
-    if prec == _lib.PREC_F16X3:
-        _log_range('flow_input', x, x_limit, [p.range_bounds for p in plans])
-    for net, plan in zip(nets, plans):
-        assert plan.n_layers == len(net.dilations) and plan.with_skip == bool(net.use_skip_connection)
-    if cond_t is not None:
-        cond_t = _cond_operand(cond_t, prec)
-    path = _choose_path(net0, plans, mode, n, t, max_workgroups, cond_geom)
-    if geom is not None and not (path.persist and path.tail and path.first_fused):
+    prep = _prepare_flow(nets, x, cond, precision, max_workgroups)
+    path, plans = prep.path, prep.plans
+    if geom is not None and not path.whole_flow:
         return None         # (the per-layer kernels and the causal-layer launch have no packed form)
-    side = _net_streams(x.device) if path.two else None
-    projs = _projections(cond, mode, plans, precision, side)
-    row_stride = projs[0].stride(0)      # (all nets' columns where project_all's one GEMM made them, else 128 * L)
-    bufs = _causal_front(x, net0, plans, path, x_limit)
-    outs = [torch.empty((n, t, net0.out_channels), dtype=torch.float32, device=x.device) for _ in nets]
     if path.persist:
-        aff = (x, affine_out) if (affine_out is not None and qin == 1) else None
-        return outs, _run_stack_persist(path, nets, plans, projs, bufs, outs, x, x_limit, row_stride, cond_geom, aff, geom)
-    _run_stack_layers(path, nets, plans, projs, bufs, outs, x, x_limit, cond_t, row_stride, cond_geom, max_workgroups, side)
+        return _run_flow_persist(prep, nets, x, cond, affine_out, geom)
+    side = _net_streams(x.device) if path.two else None
+    projs = _projections(cond, prep.mode, plans, prep.precision, side)
+    bufs = _causal_front(x, net0, plans, path, prep.x_limit)
+    outs = [torch.empty((n, t, net0.out_channels), dtype=torch.float32, device=x.device) for _ in nets]
+    _run_stack_layers(path, nets, plans, projs, bufs, outs, x, prep.x_limit, prep.cond_t, projs[0].stride(0), prep.cond_geom, max_workgroups, side)
     return outs, False
 
 
@@ -1426,25 +1486,33 @@ def _run_stack_layers(path: _Path, nets, plans, projs, bufs, outs, x, x_limit, c
 
 
 # ---- streaming: a flow on one CHUNK of N sessions (include/pwv_hip.h "STREAMING"; stream.StreamingVocoder owns the sessions) ---------
+_STREAM_STRUCTURE_WHY = {'samples': 'per-sample (transposed-conv) conditioning', 'skip': 'skip accumulation (use_skip_connection)',
+                         'f16': "precision 'f16' (the fp16 storage mode)",
+                         'shape': 'a net outside the fused shape (two scalar-input nets per flow, W = 2, R = D = 64, S = 128, no normaliser, at least 2 layers)'}
+
+
 def stream_refusal(nets, cond, precision: Optional[str] = None) -> Optional[str]:
     """Why a flow (its nets) has no streaming form -- or None.  The per-layer kernels stream in three forms only: layer 0 folded onto
     its scalar input, a plain residual layer, the last layer with the head fused behind it."""
     net0 = nets[0]
-    if any(getattr(n, 'normalize', None) == 'in' for n in nets):
+    if _instance_norm(nets):
         return "instance normalisation ('in'): its statistics span the whole time axis"
-    if cond is not None and not isinstance(cond, RepeatedCondition):
-        return 'per-sample (transposed-conv) conditioning'
-    if net0.use_skip_connection:
-        return 'skip accumulation (use_skip_connection)'
-    if (precision or net0.precision or DEFAULT_PRECISION) == 'f16':
-        return "precision 'f16' (the fp16 storage mode)"
-    if not (len(nets) == 2 and net0.out_channels == 1 and net0.in_channels == 1 and not net0.normalize and len(net0.dilations) >= 2
-            and all(n.fused_supported(cond) for n in nets) and all(_same_structure(net0, n) for n in nets)
-            and all(n.precision == net0.precision for n in nets)):
-        return 'a net outside the fused shape (two scalar-input nets per flow, W = 2, R = D = 64, S = 128, no normaliser, at least 2 layers)'
+    key = _flow_structure(nets, cond, precision)
+    if key is None and not (len(nets) == 2 and not net0.normalize and len(net0.dilations) >= 2):       # (no shared net, no normaliser)
+        key = 'shape'
+    if key is not None:
+        return _STREAM_STRUCTURE_WHY[key]
     if not (FOLD_FIRST and FUSE_FIRST and FUSE_HEAD):
         return 'PWV_FOLD_FIRST=0 / FUSE_FIRST / FUSE_HEAD off: layer 0 streams folded and the head fused only'
     return None
+
+
+def _prepare_flow_stream(nets, x: torch.Tensor, cond, precision: Optional[str]) -> _FlowPrep:
+    """_prepare_flow for a streaming flow: layer 0 streams in its folded form only."""
+    prep = _prepare_flow(nets, x, cond, precision)
+    if any(p.first_fold is None for p in prep.plans):
+        raise _lib.PwvError('run_flow_stream: no streaming form: layer 0 has no folded form for these weights')
+    return prep
 
 
 # the exact-fp32 instantiations of the ragged kernel (stack_persist_ragged_kernel<true, MODE>) are built: they are spill-free at 256 VGPRs
@@ -1476,11 +1544,8 @@ class _StreamGroup(object):
         out = RepeatedCondition(cond.frames.reshape(geom.total_frames, c).index_select(0, self.frames_idx).reshape(self.n, self.frames, c),
                                 cond.hop, cond.offset, self.t)
         bank = getattr(cond, 'proj_bank', None)
-        if bank is not None:      # (the bank's column blocks are views of one [F, cols] GEMM output: gather that once, as pad_condition pads it)
-            base = next(iter(bank.values()))
-            full = base.as_strided((geom.total_frames, base.stride(0)), (base.stride(0), 1), 0)
-            fg = full.index_select(0, self.frames_idx)
-            out.proj_bank = {k: fg[:, v.storage_offset() - full.storage_offset():][:, :v.shape[1]] for k, v in bank.items()}
+        if bank is not None:
+            out.proj_bank = _remap_bank(bank, geom.total_frames, lambda full: full.index_select(0, self.frames_idx))
         self._cond = (weakref.ref(cond), out)
         return out
 
@@ -1497,7 +1562,8 @@ def stream_groups(geom: 'VarlenGeometry', tab: torch.Tensor) -> List[_StreamGrou
 
 
 def _run_flow_stream_ragged(nets, x, cond, precision, hist, scalar_off, row_off, geom, slot_tab):
-    """run_flow_stream on a ragged chunk (geom: session i has geom.lengths[i] rows of the packed x [R, 1]).  The route, chosen once per flow:
+    """run_flow_stream on a ragged chunk (geom: session i has geom.lengths[i] rows of the packed x [R, 1]; route 4 of DESIGN.md section 9
+    "Routes").  The launches, chosen once per flow:
       * the PACKED streaming persistent launches (pwv_persist_args.cu_rows with hist->cu_rows, stack_persist_ragged_kernel) where a uniform
         forward of R rows takes persistent runs with the tail and the fused, folded layer 0 and every session has >= 32 rows
         (varlen_fallback_reason);
@@ -1508,42 +1574,23 @@ def _run_flow_stream_ragged(nets, x, cond, precision, hist, scalar_off, row_off,
     x = _require_cuda_f32(x, 'input')
     if x.dim() != 2 or tuple(x.shape) != (geom.rows, 1):
         raise ValueError('input must be the packed chunk [%d, 1], got %s' % (geom.rows, tuple(x.shape)))
-    net0 = nets[0]
-    name = precision or DEFAULT_PRECISION
-    prec = PRECISIONS[name]
     why = varlen_fallback_reason(nets, cond, geom, precision)
     if why is None:
         x3 = x.reshape(1, geom.rows, 1)
-        mode, cond_geom, _ = _check_condition(net0, cond, x3)
-        plans = [get_plan(net, mode, prec) for net in nets]
-        if prec == _lib.PREC_F16X3 and not all(p.f16x3_ok and p.x_limit > 0 for p in plans):
-            key = tuple(net.full_scope for net in nets)      # (as run_flow_stream: weights beyond fp16's range run in exact fp32)
-            if key not in _range_warned:
-                _range_warned.add(key)
-                import warnings
-                warnings.warn("pwv: weights of %s exceed the range of the split-fp16 arithmetic; using precision 'f32' for it" % (key,))
-            return _run_flow_stream_ragged(nets, x, cond, 'f32', hist, scalar_off, row_off, geom, slot_tab)
-        if any(p.first_fold is None for p in plans):
-            raise _lib.PwvError('run_flow_stream: no streaming form: layer 0 has no folded form for these weights')
-        if prec == _lib.PREC_F32 and not RAGGED_F32:
+        prep = _prepare_flow_stream(nets, x3, cond, precision)
+        if prep.precision == 'f32' and not RAGGED_F32:
             why = "the ragged kernel is not built for precision 'f32'"
+        elif prep.path.whole_flow:
+            if EVENT_LOG is not None:
+                EVENT_LOG.append(('stream_ragged', None, None, 'packed', None, 1))
+            out = torch.empty_like(x3)
+            hist.scalar_off, hist.cu_rows = scalar_off, _ptr(geom.cu_rows)
+            try:
+                outs, done = _run_flow_persist(prep, nets, x3, cond, out, geom, (hist, row_off))
+            finally:
+                hist.cu_rows = None
+            return (out if done else _flow_affine(x3, outs)).reshape(geom.rows, 1)
         else:
-            path = _choose_path(net0, plans, mode, 1, geom.rows, 0, cond_geom)
-            if path.persist and path.tail and path.first_fused:
-                if EVENT_LOG is not None:
-                    EVENT_LOG.append(('stream_ragged', None, None, 'packed', None, 1))
-                x_limit = min(p.x_limit for p in plans)
-                projs = _projections(cond, mode, plans, precision, None)
-                outs = [torch.empty((1, geom.rows, 1), dtype=torch.float32, device=x.device) for _ in plans]
-                bufs = _causal_front(x3, net0, plans, path, x_limit)
-                out = torch.empty_like(x3)
-                hist.scalar_off, hist.cu_rows = scalar_off, _ptr(geom.cu_rows)
-                try:
-                    done = _run_stack_persist(path, nets, plans, projs, bufs, outs, x3, x_limit, projs[0].stride(0), cond_geom, (x3, out), geom,
-                                              (hist, row_off))
-                finally:
-                    hist.cu_rows = None
-                return (out if done else iaf_affine_op(x3, outs[0], outs[1], 1)).reshape(geom.rows, 1)
             why = 'the library plans this stack per layer at %d rows' % geom.rows
     groups = stream_groups(geom, slot_tab)
     if EVENT_LOG is not None:
@@ -1564,7 +1611,7 @@ def run_flow_stream(nets: Sequence, x: torch.Tensor, cond, precision: Optional[s
     """One IAF flow on a chunk: x [N, T, 1] = the T samples that follow what each of the N sessions has seen, `cond` the chunk's own
     frames (a RepeatedCondition of T / hop + 1 frames per session).  `hist` carries the history blocks and the slot table of the call
     (read / written block per session); `scalar_off` and `row_off[g][j]` (j >= 1) say where this flow's histories lie in a block.
-    The launches, chosen once per flow, all on the current stream:
+    The launches (route 3 of DESIGN.md section 9 "Routes"), chosen once per flow, all on the current stream:
       * the persistent STREAMING launches (pwv_persist_args.hist; the affine inside the last one: one launch per run of
         _persist_runs, one for a stack of up to PERSIST_MAX_LAYERS + 1 layers) where _choose_path gives an [N, T] forward persistent
         runs with the tail and the fused, folded layer 0 -- PERSIST not False, not suspended, rows <= PERSIST_AUTO_MAX_ROWS, L >= 4;
@@ -1580,42 +1627,27 @@ def run_flow_stream(nets: Sequence, x: torch.Tensor, cond, precision: Optional[s
         raise _lib.PwvError('run_flow_stream: no streaming form: ' + why)
     if geom is not None:
         return _run_flow_stream_ragged(nets, x, cond, precision, hist, scalar_off, row_off, geom, slot_tab)
-    prec = PRECISIONS[precision or DEFAULT_PRECISION]
     x = _require_cuda_f32(x, 'input')
-    net0 = nets[0]
-    n, t, _ = x.shape
-    mode, cond_geom, _ = _check_condition(net0, cond, x)
-    plans = [get_plan(net, mode, prec) for net in nets]
-    if prec == _lib.PREC_F16X3 and not all(p.f16x3_ok and p.x_limit > 0 for p in plans):
-        key = tuple(net.full_scope for net in nets)      # (as _run_nets: weights beyond fp16's range run in exact fp32)
-        if key not in _range_warned:
-            _range_warned.add(key)
-            import warnings
-            warnings.warn("pwv: weights of %s exceed the range of the split-fp16 arithmetic; using precision 'f32' for it" % (key,))
-        return run_flow_stream(nets, x, cond, 'f32', hist, scalar_off, row_off)
-    if any(p.first_fold is None for p in plans):
-        raise _lib.PwvError('run_flow_stream: no streaming form: layer 0 has no folded form for these weights')
-    x_limit = min(p.x_limit for p in plans)
-    projs = _projections(cond, mode, plans, precision, None)
-    lib, s = _lib.lib(), _stream()
-    G, L = len(plans), plans[0].n_layers
-    outs = [torch.empty((n, t, 1), dtype=torch.float32, device=x.device) for _ in plans]
-    path = _choose_path(net0, plans, mode, n, t, 0, cond_geom)
-    if path.persist and path.tail and path.first_fused:
+    prep = _prepare_flow_stream(nets, x, cond, precision)
+    if prep.path.whole_flow:
         hist.scalar_off = scalar_off
-        bufs = _causal_front(x, net0, plans, path, x_limit)       # (the ring of three; layer 0 is inside the launch: nothing is enqueued)
         out = torch.empty_like(x)
-        if _run_stack_persist(path, nets, plans, projs, bufs, outs, x, x_limit, projs[0].stride(0), cond_geom, (x, out), None, (hist, row_off)):
-            return out
-        return iaf_affine_op(x, outs[0], outs[1], 1)
+        outs, done = _run_flow_persist(prep, nets, x, cond, out, None, (hist, row_off))
+        return out if done else _flow_affine(x, outs)
+    lib, s = _lib.lib(), _stream()
+    net0, plans = nets[0], prep.plans
+    n, t, _ = x.shape
+    G, L = len(plans), plans[0].n_layers
     if EVENT_LOG is not None:
         EVENT_LOG.append(('layer_stream', None, None, G, L))      # L calls of pwv_wavenet_layer_stream_f32 + the affine
+    projs = _projections(cond, prep.mode, plans, prep.precision, None)
+    outs = [torch.empty((n, t, 1), dtype=torch.float32, device=x.device) for _ in plans]
     bufs = [[torch.empty((lib.pwv_tile32_floats(n * t, 64),), dtype=torch.float32, device=x.device) for _ in range(2)] for _ in plans]
     for j in range(L):
-        la = _layer_args(net0, plans, projs, projs[0].stride(0), cond_geom, bufs, j, (j + 1) & 1, j & 1, x)
+        la = _layer_args(net0, plans, projs, projs[0].stride(0), prep.cond_geom, bufs, j, (j + 1) & 1, j & 1, x)
         la.out_mode = _lib.OUT_GATED if j == L - 1 else _lib.OUT_RESIDUAL
         if j == 0:
-            _set_x_first(la, plans, x, x_limit)
+            _set_x_first(la, plans, x, prep.x_limit)
             hist.scalar_off = scalar_off
         else:
             for g in range(G):
@@ -1625,4 +1657,4 @@ def run_flow_stream(nets: Sequence, x: torch.Tensor, cond, precision: Optional[s
                 la.head_packed[g], la.head_out[g] = plans[g].packed_head.data_ptr(), outs[g].data_ptr()
             la.head_q = 1
         check(lib.pwv_wavenet_layer_stream_f32(ctypes.byref(la), ctypes.byref(hist), s), 'pwv_wavenet_layer_stream_f32')
-    return iaf_affine_op(x, outs[0], outs[1], 1)
+    return _flow_affine(x, outs)

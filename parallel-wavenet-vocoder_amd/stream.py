@@ -235,6 +235,42 @@ class StreamingVocoder(object):
             commit()
 
     # -- a push ----------------------------------------------------------------------------------------------------------
+    def _slots(self, slots) -> List[int]:
+        return list(range(self.n_slots)) if slots is None else [self._slot(v) for v in slots]
+
+    def _noise_seeds(self, slots, given=None) -> List[int]:
+        """The noise seed of every slot of a push that draws its own noise: given[i] where the call brings one, else the one kept
+        from the slot's reset or first push, else drawn from the OS."""
+        return [given[i] if (given is not None and given[i] is not None) else
+                (self._seed[s] if self._seed[s] is not None else int.from_bytes(os.urandom(7), 'little')) for i, s in enumerate(slots)]
+
+    def _commit(self, slots, samples, new_seeds, idx, last):
+        """The commit of a push that gave slots[i] samples[i] samples: the generation flip, running, emitted, the seeds (where the
+        push drew its own noise) and the kept frames `last` [n, n_mels] (idx: the slots as a device index vector, None = all in order)."""
+        def commit():
+            for i, s in enumerate(slots):
+                self._gen[s] ^= 1
+                self._running[s] = True
+                self._emitted[s] += samples[i]
+                if new_seeds is not None:
+                    self._seed[s] = new_seeds[i]
+            if idx is None:
+                self._kept.copy_(last)
+            else:
+                self._kept.index_copy_(0, idx, last)
+        return commit
+
+    def _transact(self, enqueue, commit, verify):
+        """The ending of a push: `enqueue(precision)` as a verified call (engine.verified_call), then the commit -- now, or left in
+        _pending for verify() where the call only enqueued."""
+        out = engine.verified_call(lambda prec: enqueue(prec or self.model.precision), verify)
+        verified = ((not engine.ASYNC) if verify is None else bool(verify)) and getattr(engine._tls, 'depth', 0) == 0
+        if verified and not torch.cuda.is_current_stream_capturing():
+            commit()
+        else:
+            self._pending = commit
+        return out
+
     def push(self, mel, slots=None, z=None, seeds=None, verify=None):
         """Give the sessions in `slots` (default: all) their next `f` mel frames, mel [n, f, n_mels]; returns their next samples
         [n, samples, 1]: (f - 1) * hop for fresh sessions (the last frame is kept back: the samples around it need the frame after
@@ -248,7 +284,7 @@ class StreamingVocoder(object):
         pre-chunk state on the same noise (with the usual `pwv:` warning).  verify=False / PWV_ASYNC=1 only enqueue: call verify()
         before the next push."""
         self._settled('push')
-        slots = list(range(self.n_slots)) if slots is None else [self._slot(v) for v in slots]
+        slots = self._slots(slots)
         n = len(slots)
         if n == 0 or len(set(slots)) != n:
             raise ValueError('slots must be a non-empty list of distinct slots, got %r' % (slots,))
@@ -274,25 +310,8 @@ class StreamingVocoder(object):
                 raise ValueError('z must be [%d, %d, 1], got %s' % (n, T, tuple(z.shape)))
         engine.raise_if_range_flag('an earlier call')
         idx = torch.tensor(slots, dtype=torch.int64).to(self.device) if n != self.n_slots or slots != list(range(n)) else None
-        new_seeds = None
-        if z is None:
-            new_seeds = [self._seed[s] if self._seed[s] is not None else int.from_bytes(os.urandom(7), 'little') for s in slots]
-            if seeds is not None:
-                new_seeds = seeds
-        last = mel[:, -1]
-
-        def commit():
-            for i, s in enumerate(slots):
-                self._gen[s] ^= 1
-                self._running[s] = True
-                self._emitted[s] += T
-                if new_seeds is not None:
-                    self._seed[s] = new_seeds[i]
-            if idx is None:
-                self._kept.copy_(last)
-            else:
-                self._kept.index_copy_(0, idx, last)
-
+        new_seeds = self._noise_seeds(slots, seeds) if z is None else None
+        commit = self._commit(slots, [T] * n, new_seeds, idx, mel[:, -1])
         if T == 0:            # one frame to a fresh slot: nothing to generate yet
             commit()
             return torch.empty((n, 0, 1), dtype=torch.float32, device=self.device)
@@ -306,23 +325,20 @@ class StreamingVocoder(object):
         # utterance i of the launches reads block 2 s + gen, writes block 2 s + 1 - gen
         tab = torch.tensor([[2 * s + self._gen[s], 2 * s + 1 - self._gen[s]] for s in slots],
                            dtype=torch.int32).pin_memory().to(self.device, non_blocking=True)
-        out = engine.verified_call(lambda prec: self._enqueue(prec or self.model.precision, frames, z, tab, T), verify)
-        verified = ((not engine.ASYNC) if verify is None else bool(verify)) and getattr(engine._tls, 'depth', 0) == 0
-        if verified and not torch.cuda.is_current_stream_capturing():
-            commit()
-        else:
-            self._pending = commit
-        return out
+        return self._transact(lambda prec: self._enqueue(prec, frames, z, tab, T), commit, verify)
 
-    def _enqueue(self, precision, frames, z, tab, T):
-        """The chunk's launches on the current stream: the prologue on the chunk's frames, the carry-over of the histories the chunk
-        does not push out (one launch, only when T is below the largest history), then per flow ONE persistent streaming launch
-        (engine.run_flow_stream; PWV_PERSIST=0, a suspended persistent launch or a stack below 4 layers: L streaming layer launches and
-        the affine -- same bits).  Reads the sessions' current generation, writes the other one: may be enqueued again from the same
-        state, on either route."""
+    def _enqueue(self, precision, frames, z, tab, T, geom=None):
+        """The chunk's launches on the current stream: the prologue on the chunk's frames [n, f, n_mels], the carry-over of the histories
+        the chunk does not push out (one launch, only when T is below the largest history), then per flow engine.run_flow_stream, which
+        picks the flow's route ("Routes"): by default ONE persistent streaming launch.  With `geom` the chunk is
+        RAGGED: `frames` is the packed mel [1, F, n_mels] (the prologue is per frame, as in the packed one-shot forward), the carry-over
+        runs in its packed form (session n's own T_n decides what it moves; skipped when every T_n reaches the largest history) and
+        every flow gets the geometry.  Reads the sessions' current generation, writes the other one: may be enqueued again from the
+        same state, on any route."""
         model = self.model
         store = model.store or get_default_store()
         lay = self.layout
+        rows, shortest = (T, T) if geom is None else (geom.rows, min(geom.lengths))
         sa = _lib.StreamArgs()
         sa.hist_rd = sa.hist_wr = self._hist.data_ptr()
         sa.block_stride, sa.slot_tab = lay.block_floats, tab.data_ptr()
@@ -331,13 +347,15 @@ class StreamingVocoder(object):
             flows = model._flows(store, False, precision)
             nets = [net for iaf in flows for net in iaf.nets()]
             with variable_scope('cond'):
-                cond = model._condition(frames, False, strides=[4, 4, 5], store=store, precision=precision, nets=nets, length=T)
+                cond = model._condition(frames, False, strides=[4, 4, 5], store=store, precision=precision, nets=nets, length=rows)
             engine.project_all(nets, cond, precision=precision)
-            if T < lay.max_rows:
-                _lib.check(_lib.lib().pwv_stream_carry_f32(ctypes.byref(sa), frames.shape[0], T, engine._stream()), 'pwv_stream_carry_f32')
+            if shortest < lay.max_rows:
+                sa.cu_rows = None if geom is None else geom.cu_rows.data_ptr()      # (packed form: T = 0, every session's own length)
+                _lib.check(_lib.lib().pwv_stream_carry_f32(ctypes.byref(sa), tab.shape[0], T, engine._stream()), 'pwv_stream_carry_f32')
+                sa.cu_rows = None
             x = z
             for i, iaf in enumerate(flows):
-                x = engine.run_flow_stream(iaf.nets(), x, cond, precision, sa, lay.scalar_off[i], lay.row_off[i])
+                x = engine.run_flow_stream(iaf.nets(), x, cond, precision, sa, lay.scalar_off[i], lay.row_off[i], geom=geom, slot_tab=tab)
         return x
 
     # -- a ragged push ---------------------------------------------------------------------------------------------------
@@ -355,7 +373,7 @@ class StreamingVocoder(object):
         self._settled('push_varlen')
         if not isinstance(mels, (list, tuple)) or not mels:
             raise ValueError('mels must be a non-empty list of [f, n_mels] tensors')
-        slots = list(range(self.n_slots)) if slots is None else [self._slot(v) for v in slots]
+        slots = self._slots(slots)
         n = len(slots)
         if n != len(mels) or len(set(slots)) != n:
             raise ValueError('slots must be distinct, one per mel (%d mels), got %r' % (len(mels), slots))
@@ -389,22 +407,9 @@ class StreamingVocoder(object):
                 raise ValueError('z must be the packed [%d, 1], got %s' % (total, tuple(z.shape)))
         mels = [engine._require_cuda_f32(m, 'mels[%d]' % i) for i, m in enumerate(mels)]
         engine.raise_if_range_flag('an earlier call')
-        new_seeds = None
-        if z is None:
-            new_seeds = [seeds[i] if (seeds is not None and seeds[i] is not None) else
-                         (self._seed[s] if self._seed[s] is not None else int.from_bytes(os.urandom(7), 'little')) for i, s in enumerate(slots)]
+        new_seeds = self._noise_seeds(slots, seeds) if z is None else None
         idx = torch.tensor(slots, dtype=torch.int64).pin_memory().to(self.device, non_blocking=True)
-        last = torch.stack([m[-1] for m in mels])
-
-        def commit():
-            for i, s in enumerate(slots):
-                self._gen[s] ^= 1
-                self._running[s] = True
-                self._emitted[s] += plan.samples[i]
-                if new_seeds is not None:
-                    self._seed[s] = new_seeds[i]
-            self._kept.index_copy_(0, idx, last)
-
+        commit = self._commit(slots, plan.samples, new_seeds, idx, torch.stack([m[-1] for m in mels]))
         if not plan.launch:            # one frame each to fresh slots: nothing to generate yet
             commit()
             return RaggedOutput(torch.empty((0, 1), dtype=torch.float32, device=self.device), plan.samples)
@@ -416,43 +421,10 @@ class StreamingVocoder(object):
             if not fresh[i]:
                 pieces.append(self._kept[slots[i]:slots[i] + 1])
             pieces.append(mels[i])
-        mel = pieces[0] if len(pieces) == 1 else torch.cat(pieces)
+        mel = (pieces[0] if len(pieces) == 1 else torch.cat(pieces)).unsqueeze(0)
         if z is None:
             z = engine.logistic_noise_packed_op(geom.cu_rows, geom.stream_table([(new_seeds[i], self._emitted[slots[i]]) for i in plan.launch]),
                                                 geom.rows)
         # session k of the launches reads block 2 s + gen, writes block 2 s + 1 - gen
         tab = geom._upload([[2 * slots[i] + self._gen[slots[i]], 2 * slots[i] + 1 - self._gen[slots[i]]] for i in plan.launch], torch.int32)
-        out = engine.verified_call(lambda prec: self._enqueue_varlen(prec or self.model.precision, mel, z, tab, geom), verify)
-        verified = ((not engine.ASYNC) if verify is None else bool(verify)) and getattr(engine._tls, 'depth', 0) == 0
-        if verified and not torch.cuda.is_current_stream_capturing():
-            commit()
-        else:
-            self._pending = commit
-        return RaggedOutput(out, plan.samples)
-
-    def _enqueue_varlen(self, precision, mel, z, tab, geom):
-        """The ragged chunk's launches on the current stream: the prologue on the packed frames (per frame: as in the packed one-shot
-        forward), the carry-over in its packed form (one launch; session n's own T_n decides what it moves; skipped when every T_n
-        reaches the largest history), then per flow engine.run_flow_stream with the geometry: ONE packed persistent streaming launch,
-        or the sessions grouped by length on the uniform routes.  Reads the sessions' current generation, writes the other one."""
-        model = self.model
-        store = model.store or get_default_store()
-        lay = self.layout
-        sa = _lib.StreamArgs()
-        sa.hist_rd = sa.hist_wr = self._hist.data_ptr()
-        sa.block_stride, sa.slot_tab = lay.block_floats, tab.data_ptr()
-        sa.carry_tab, sa.n_carry = self._carry_tab.data_ptr(), len(lay.carry)
-        with variable_scope('iaf_vocoder'):
-            flows = model._flows(store, False, precision)
-            nets = [net for iaf in flows for net in iaf.nets()]
-            with variable_scope('cond'):
-                cond = model._condition(mel.unsqueeze(0), False, strides=[4, 4, 5], store=store, precision=precision, nets=nets, length=geom.rows)
-            engine.project_all(nets, cond, precision=precision)
-            if min(geom.lengths) < lay.max_rows:
-                sa.cu_rows = geom.cu_rows.data_ptr()
-                _lib.check(_lib.lib().pwv_stream_carry_f32(ctypes.byref(sa), geom.n, 0, engine._stream()), 'pwv_stream_carry_f32')
-                sa.cu_rows = None
-            x = z
-            for i, iaf in enumerate(flows):
-                x = engine.run_flow_stream(iaf.nets(), x, cond, precision, sa, lay.scalar_off[i], lay.row_off[i], geom=geom, slot_tab=tab)
-        return x
+        return RaggedOutput(self._transact(lambda prec: self._enqueue(prec, mel, z, tab, 0, geom), commit, verify), plan.samples)

@@ -579,3 +579,58 @@ def test_generate_cli_stream_pushes_once_per_tick(gpu, tmp_path, monkeypatch):
     for i, f in enumerate(frames):
         rate, data = wavfile.read(str(logdir / ('pred_%d.wav' % i)))
         assert data.shape == ((f - 1) * 80,)
+
+
+def test_pack_time_demotion_is_the_same_on_every_route(gpu, knobs):
+    """Weights whose PACK-TIME bound fails (NetPlan._range_analysis: ||skip||_1 of the last layer, the bound on the head's operand, passes
+    65000; every value an ordinary finite fp32, and nothing behind the skip product saturates) send that flow -- and only it -- to the exact-fp32 kernels on every route: the one-shot forward, generate_varlen, uniform pushes
+    and a ragged schedule (a fresh session next to running ones, 80-row chunks: units that span two sessions) give the same bits on the
+    same mel and noise, every persistent launch of the demoted flow carries PREC_F32, and the warning is raised once for its pair of nets."""
+    import warnings
+    from pwv_amd import _lib
+    from pwv_amd.variables import variable_scope
+    from tests.test_gpu_stream import _Feeder
+    engine = knobs
+    cfg = _small()
+    model, w = _model(gpu, cfg, 'f16x3')
+    name = 'iaf_vocoder/iaf1/scalar/dilated_stack/layer%d/skip' % (len(cfg.dilations[1]) - 1)
+    model.store.assign(name, w[name] * 2.0e4)              # ||skip||_1 >= 64 * 0.088 * 2e4 = 1.1e5 (glorot: mean |w| = 0.088); max |w| = 3.5e3
+    with variable_scope('iaf_vocoder'):
+        flows = model._flows(model.store, False, 'f16x3')
+    ok = [[engine.get_plan(net, 'frames', _lib.PREC_F16X3).f16x3_ok for net in iaf.nets()] for iaf in flows]
+    assert ok[0] == [True, True] and sorted(ok[1]) == [False, True], ok      # (flow 1's scaler alone fails; its pair is demoted with it)
+    key = tuple(net.full_scope for net in flows[1].nets())
+    engine._range_warned.discard(key)
+    layers = [len(d) - 1 for d in cfg.dilations[:cfg.n_iaf]]      # layers per persistent launch (the tail rides in it): tells the flows apart
+    assert layers[0] != layers[1]
+    seen = []
+    schedule = {0: [4, 1, 5], 1: [None, 9, 7], 2: [None, None, 6]}       # 720, 1200 and 400 samples; sessions 1 and 2 start beside running ones
+    engine.PERSIST_ARGS_HOOK = lambda pa: seen.append((int(pa.n_layers), int(pa.precision)))
+    try:
+        with warnings.catch_warnings(record=True) as caught:
+            warnings.simplefilter('always')
+            s, fd, ins, rows = _run_schedule(model, cfg, gpu, schedule, 80)
+            ragged, seen[:] = list(seen), []
+            want = [_one_shot(model, ins[sl][2], ins[sl][3]) for sl in schedule]
+            one_shot, seen[:] = list(seen), []
+            packed = model.generate_varlen([ins[sl][2] for sl in schedule], z=[ins[sl][3] for sl in schedule])
+            varlen, seen[:] = list(seen), []
+            u = model.open_stream(slots=3)
+            uf = _Feeder(u)
+            for sl, chunks in ((0, [240, 80, 400]), (1, [640, 560]), (2, [400])):
+                uf.start(sl, ins[sl][2], ins[sl][3])
+                for T in chunks:
+                    uf.adv([sl], T)
+            uniform = list(seen)
+    finally:
+        engine.PERSIST_ARGS_HOOK = None
+    assert rows == [240, 80 + 640, 400 + 560 + 400]
+    for sl in schedule:
+        for route, got in (('generate_varlen', packed[sl]), ('push', uf.result(sl)), ('push_varlen', fd.result(sl))):
+            assert torch.equal(got, want[sl]), (route, sl, float((got - want[sl]).abs().max()))
+    for route, launches in (('one-shot', one_shot), ('generate_varlen', varlen), ('push', uniform), ('push_varlen', ragged)):
+        demoted = [p for n, p in launches if n == layers[1]]
+        assert demoted and all(p == _lib.PREC_F32 for p in demoted), (route, launches)
+        assert [p for n, p in launches if n == layers[0]] == [_lib.PREC_F16X3] * len(demoted), (route, launches)
+    told = [str(c.message) for c in caught if 'exceed the range' in str(c.message)]
+    assert len(told) == 1 and key[0] in told[0], told
