@@ -594,6 +594,50 @@ int pwv_persist_short_input(const pwv_persist_args* args);
 int pwv_persist_status(int** status);
 int pwv_wavenet_stack_persist_f32(const pwv_persist_args* args, pwv_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * A streaming TICK with its session state on the device (graph replay of a push: nothing of a tick is decided on the host).
+ *
+ * State (device memory, owned by the caller, one row per session slot):
+ *   sess  int64 [n_slots][4] = {generation a chunk READS (0 / 1), samples emitted, noise seed (uint64 bits), 0}
+ *   kept  float [n_slots][n_mels]: the last mel frame the session was given (the first frame of its next chunk)
+ * Per tick the caller writes `entries` (int32 [N][2] = {slot, live}; distinct slots) and the chunk's mel [N][frames][n_mels].
+ *
+ * pwv_stream_tick_begin, for entry i with slot s and g = sess[s][0]:
+ *   slot_tab[i]  = {2s + g, 2s + 1 - g}                       (pwv_stream_args.slot_tab: block read, block written)
+ *   streams[i]   = {sess[s][2], sess[s][1]},  cu_rows[i] = i * T, cu_rows[N] = N * T      (the tables of pwv_logistic_noise_packed_f32;
+ *                                                                                           both NULL: the noise is the caller's)
+ *   chunk[i][0]  = kept[s],  chunk[i][1 .. frames] = mel[i]   (chunk: float [N][frames + 1][n_mels], what the prologue conditions on)
+ * pwv_stream_tick_commit, the LAST launch of a tick: reads words[0] (give-up) and words[1] (range) of a pwv_status_words_alloc pair with
+ * system-scope atomic loads.  Both zero: every entry with live != 0 is COMMITTED -- sess[s][0] ^= 1, sess[s][1] += T, kept[s] =
+ * mel[i][frames - 1] -- and counters[0] += 1.  Otherwise nothing changes and counters[1] += 1: the words are sticky, so once a tick is
+ * refused every later one is, and the committed ticks are a prefix of the enqueued ones.  An entry with live == 0 (a FILLER) is never
+ * committed: it read generation g and wrote generation 1 - g, which is scratch until a flip.
+ * A slot outside 0 .. n_slots-1 is read as a filler of slot 0, so that no address leaves the arrays (the caller keeps slots in range).
+ * One launch each, nothing read on the host: a captured pair replays with whatever the tables hold then.
+ * PWV_EINVAL before a device is needed (pwv_last_error names the field): a NULL pointer, N < 1, frames < 1, n_mels < 1, T < 1,
+ * n_slots < 1, streams without cu_rows or the reverse, struct_size short of the fields the call reads.
+ * ------------------------------------------------------------------------------------- */
+typedef struct pwv_stream_tick_args {
+    size_t struct_size;                    /* = sizeof(pwv_stream_tick_args) as the caller was compiled */
+    int64_t* sess;                         /* device int64 [n_slots][4] */
+    float* kept;                           /* device float [n_slots][n_mels] */
+    const int32_t* entries;                /* device int32 [N][2] = {slot, live} */
+    const float* mel;                      /* device float [N][frames][n_mels] */
+    int32_t n_slots, N, frames, n_mels;
+    int32_t T;                             /* samples of the tick per session (frames * hop) */
+    /* pwv_stream_tick_begin writes: */
+    int32_t* slot_tab;                     /* device int32 [N][2] */
+    uint64_t* streams;                     /* device uint64 [N][2], or NULL together with cu_rows */
+    int32_t* cu_rows;                      /* device int32 [N + 1] */
+    float* chunk;                          /* device float [N][frames + 1][n_mels] */
+    /* pwv_stream_tick_commit reads / advances: */
+    const int* words;                      /* the sticky pair (mapped host memory) the tick's launches report into */
+    int64_t* counters;                     /* device int64 [2] = {ticks committed, ticks refused} */
+} pwv_stream_tick_args;
+
+int pwv_stream_tick_begin(const pwv_stream_tick_args* args, pwv_stream_t stream);
+int pwv_stream_tick_commit(const pwv_stream_tick_args* args, pwv_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

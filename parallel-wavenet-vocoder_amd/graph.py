@@ -16,9 +16,16 @@ range passed by value would replay the same noise).
 GraphedPackedVocoder does the same for packed batches of utterances of different lengths (IAFVocoder.generate_varlen with one noise
 stream per utterance): captured once at a capacity of `slots` utterances and `rows` samples, replayed for any lengths that fit, the
 layout and the streams rewritten in device tables before each replay and the free slots taken by filler utterances.
+
+GraphedStream does it for a streaming tick (StreamingVocoder.push of n running sessions x f frames): the session state -- generation,
+samples emitted, seed, kept frame -- lives on the device, a kernel at the head of the graph turns it into the tick's launch tables and a
+kernel at its end commits the tick iff the sticky words are clean, so ticks are enqueued back to back without a host round trip.
 """
 from __future__ import annotations
 
+import collections
+import ctypes
+import os
 from typing import Optional
 
 import numpy as np
@@ -336,6 +343,310 @@ class GraphedPackedVocoder(object):
         except _lib.PwvPersistError:
             self.graph = None
             raise
+
+
+class GraphedStream(object):
+    """ONE tick of a StreamingVocoder -- `n` running sessions x `frames` mel frames, T = frames * hop samples each -- captured into a HIP
+    graph with the commit on the device ("Graph replay of a streaming tick"; StreamingVocoder.graphed):
+
+        begin kernel (session table -> slot table, noise streams, the chunk's frames)  ->  packed sampler (sample=True)  ->
+        StreamingVocoder._enqueue (prologue, carry, one persistent streaming launch per flow)  ->  commit kernel
+
+    tick(mel [k, frames, n_mels], slots, z=None) replays it for 1 <= k <= n distinct RUNNING slots and only enqueues; the other n - k
+    entries are FILLERS on other slots of the stream (live = 0: they read their slot's generation g and write generation 1 - g, which
+    is scratch until a flip, and are never committed).  Ticks may follow each other with no synchronisation: the commit kernel flips a
+    session only if both sticky words are clean, and the words are sticky, so the committed ticks are a PREFIX of the enqueued ones.
+    verify() waits, makes the host's view of the sessions equal to the device table and returns the number of ticks committed; it
+    raises PwvRangeError / PwvPersistError (with that number as `.committed`) where a tick was refused: push the failed chunk again
+    with the eager push and carry on.  While ticks are in flight the stream is pending: push / reset / state refuse until verify().
+
+    Refused at construction (PwvError) wherever a flow of an [n, T] push is not the whole-flow persistent streaming launch."""
+
+    def __init__(self, stream, n: int, frames: int, sample: bool = True, depth: int = 4, warmup: int = 2):
+        st = self.stream = stream
+        self.model = st.model
+        store = st.model.store
+        if store is None:
+            from .variables import get_default_store
+            store = get_default_store()
+        self.store = store
+        self.device = st.device
+        if self.device.type != 'cuda':
+            raise _lib.PwvError('GraphedStream needs a GPU (cuda device); there is no CPU path')
+        self.n, self.frames = int(n), int(frames)
+        if self.n < 1 or self.frames < 1:
+            raise ValueError('a graphed tick needs n >= 1 sessions and frames >= 1, got %r / %r' % (n, frames))
+        if self.n > st.n_slots:
+            raise ValueError('a graph for %d sessions needs a stream of at least %d slots (this one has %d): the entries a tick does not '
+                             'use are fillers on OTHER slots of the stream' % (self.n, self.n, st.n_slots))
+        self.T = self.frames * st.hop
+        self.sample, self.depth = bool(sample), max(1, int(depth))
+        why = self._refusal()
+        if why is not None:
+            raise _lib.PwvError('GraphedStream: a flow of a %d x %d push is not one persistent streaming launch: %s' % (self.n, self.T, why))
+        dev, n = self.device, self.n
+        self.mel = torch.zeros((n, self.frames, st.n_mels), dtype=torch.float32, device=dev)
+        self.z = torch.zeros((n, self.T, 1), dtype=torch.float32, device=dev)
+        self._chunk = torch.zeros((n, self.frames + 1, st.n_mels), dtype=torch.float32, device=dev)
+        self._tab = torch.zeros((n, 2), dtype=torch.int32, device=dev)
+        self._entries = torch.zeros((n, 2), dtype=torch.int32, device=dev)
+        self._streams = torch.zeros((n, 2), dtype=torch.int64, device=dev) if self.sample else None
+        self._cu_rows = torch.zeros((n + 1,), dtype=torch.int32, device=dev) if self.sample else None
+        self._counters = torch.zeros((2,), dtype=torch.int64, device=dev)      # {ticks committed, ticks refused}
+        # pinned staging of the entries and of rewritten session rows: one pair per tick that may be in flight
+        self._entries_host = [torch.zeros((n, 2), dtype=torch.int32).pin_memory() for _ in range(self.depth)]
+        self._rows_host = [torch.zeros((n, 4), dtype=torch.int64).pin_memory() for _ in range(self.depth)]
+        self._entries_dev = None                # the entries the device table holds: (slots, live of the called ones)
+        self._counters_host = torch.zeros((2,), dtype=torch.int64).pin_memory()
+        self._sess_back = torch.zeros((st.n_slots, 4), dtype=torch.int64).pin_memory()
+        self._events = collections.deque()      # the end events of the ticks in flight (at most `depth`)
+        self._inflight = set()                  # the slots ticks in flight were called with
+        self._ticks = 0
+        self._seen = [0, 0]                     # the counters at the last verify()
+        self._carry = 0                         # eager ticks settled on the way (counted by the next verify())
+        self._dirty_rows = 0                    # rows of mel / z that may hold a previous tick's values
+        self._warmup = max(1, int(warmup))
+        self._stream = None
+        self._words = None
+        self.graph = None
+        self.captures = 0          # graphs captured so far (new weights, other launch knobs or the end of a suspension capture again)
+        self.eager_calls = 0       # ticks that ran the eager push instead (a suspension, a tick that does not fit the capture)
+        self._capture()
+
+    # -- capture -----------------------------------------------------------------------------------------------------------------
+    def _refusal(self) -> Optional[str]:
+        m = hp.model
+        if engine.PERSIST is False:
+            return 'PWV_PERSIST=0 (engine.PERSIST False): pushes run on per-layer streaming launches'
+        for i, d in enumerate(m.dilations[:m.n_iaf]):
+            if len(d) < 4:
+                return 'flow %d has %d layers (L < 4): the library plans it per layer' % (i, len(d))
+        if engine.PERSIST == 'auto' and self.n * self.T > engine.PERSIST_AUTO_MAX_ROWS:
+            return '%d rows are above PERSIST_AUTO_MAX_ROWS (%d)' % (self.n * self.T, engine.PERSIST_AUTO_MAX_ROWS)
+        return None
+
+    def _tick_args(self) -> _lib.StreamTickArgs:
+        st, ta = self.stream, _lib.StreamTickArgs()
+        ta.sess, ta.kept, ta.entries, ta.mel = st._sess.data_ptr(), st._kept.data_ptr(), self._entries.data_ptr(), self.mel.data_ptr()
+        ta.n_slots, ta.N, ta.frames, ta.n_mels, ta.T = st.n_slots, self.n, self.frames, st.n_mels, self.T
+        ta.slot_tab, ta.chunk = self._tab.data_ptr(), self._chunk.data_ptr()
+        if self.sample:
+            ta.streams, ta.cu_rows = self._streams.data_ptr(), self._cu_rows.data_ptr()
+        ta.words, ta.counters = self._words.addr, self._counters.data_ptr()
+        return ta
+
+    def _enqueue(self):
+        """The tick the graph holds (only enqueues): begin, sampler, the push's own launches, commit."""
+        st, lib, ta = self.stream, _lib.lib(), self._tick_args()
+        _lib.check(lib.pwv_stream_tick_begin(ctypes.byref(ta), engine._stream()), 'pwv_stream_tick_begin')
+        if self.sample:
+            engine.logistic_noise_packed_op(self._cu_rows, self._streams, self.n * self.T, out=self.z.view(self.n * self.T, 1))
+        out = engine.verified_call(lambda prec: st._enqueue(prec or self.model.precision, self._chunk, self.z, self._tab, self.T), verify=False)
+        _lib.check(lib.pwv_stream_tick_commit(ctypes.byref(ta), engine._stream()), 'pwv_stream_tick_commit')
+        return out
+
+    def _write_entries(self, k: int, called, live: int):
+        """The tick's entry table through pinned staging `k`: the called slots with `live`, then fillers -- other slots of the stream,
+        running ones first -- with live = 0."""
+        st = self.stream
+        others = sorted((s for s in range(st.n_slots) if s not in called), key=lambda s: not st._running[s])[:self.n - len(called)]
+        for s in others:
+            if not st._running[s]:
+                st._scratch_dirty[s] = True       # (a fresh slot's other generation is zeros no longer: StreamingVocoder._commit)
+        table = (tuple(called) + tuple(others), live)
+        if table == self._entries_dev:
+            return others                         # (the device table holds these entries already: the previous tick's)
+        buf = self._entries_host[k].numpy()
+        buf[:, 0] = table[0]
+        buf[:, 1] = [live] * len(called) + [0] * len(others)
+        self._entries.copy_(self._entries_host[k], non_blocking=True)
+        self._entries_dev = table
+        return others
+
+    def _capture(self):
+        self.graph = None
+        if engine.persist_suspended():
+            return           # (no persistent streaming launch now: ticks run eagerly until the suspension ends, then capture)
+        why = self._refusal()
+        if why is not None:
+            raise _lib.PwvError('GraphedStream: a flow of a %d x %d push is not one persistent streaming launch: %s' % (self.n, self.T, why))
+        if self._stream is None:
+            self._stream = torch.cuda.Stream(device=self.device)
+        side = self._stream
+        self._words = engine.current_words(self.device)       # the captured launches report into THIS thread's words: verify() reads these
+        # warm up and capture on an all-filler table: no session is touched, any entries replay the same launches
+        self._sync_rows(0, [], self._write_entries(0, [], 0))
+        self.mel.zero_()
+        self.z.zero_()
+        self._dirty_rows = 0
+        log, own = engine.EVENT_LOG, engine.EVENT_LOG is None
+        if own:
+            log = engine.EVENT_LOG = []
+        mark = len(log)
+        try:
+            side.wait_stream(torch.cuda.current_stream(self.device))
+            with torch.cuda.stream(side):
+                for _ in range(self._warmup):
+                    self._enqueue()
+            torch.cuda.current_stream(self.device).wait_stream(side)
+        finally:
+            if own:
+                engine.EVENT_LOG = None
+        odd = [e[0] for e in log[mark:] if not (e[0] == 'persist' and e[8] == 1)]
+        flows = int(hp.model.n_iaf)
+        if odd or len(log) - mark != self._warmup * flows or not all(e[5] == 1 and e[6] == 1 for e in log[mark:]):
+            raise _lib.PwvError('GraphedStream: a flow of a %d x %d push is not one persistent streaming launch (the warm-up enqueued %s)'
+                                % (self.n, self.T, odd or '%d persistent launches for %d flows' % ((len(log) - mark) // self._warmup, flows)))
+        engine.verify_enqueued('the warm-up of a streaming graph')
+        self._counters.zero_()
+        self._seen = [0, 0]
+        graph = torch.cuda.CUDAGraph()
+        saved, engine.EVENT_LOG = engine.EVENT_LOG, None       # (the log brackets launches with timing events: not inside a capture)
+        try:
+            with torch.cuda.graph(graph, stream=side, capture_error_mode='thread_local'):
+                self.out = self._enqueue()
+        finally:
+            engine.EVENT_LOG = saved
+        self.graph = graph
+        self._version = self.store.version
+        self._mode = engine.launch_knobs()
+        self.captures += 1
+
+    # -- ticks -------------------------------------------------------------------------------------------------------------------
+    def tick(self, mel, slots, z=None):
+        """Give the RUNNING sessions in `slots` (1 <= k <= n distinct slots) their next `frames` mel frames, mel [k, frames, n_mels];
+        returns their next samples [k, T, 1] as views of the graph's output buffer, valid until the next tick (a caller that pipelines
+        ticks copies them out on the stream).  sample=False: z [k, T, 1] is the noise; sample=True: every slot draws from its own
+        counter stream (a slot without a seed gets one from the OS, as in push).  Enqueue-only; before tick j is enqueued the host
+        waits for the end of tick j - depth.  A tick of another frame count, or one while the persistent launches are suspended,
+        settles what is in flight (verify()) and runs the eager push(verify=False) instead."""
+        st = self.stream
+        slots = [st._slot(v) for v in slots]
+        k = len(slots)
+        if k == 0 or len(set(slots)) != k:
+            raise ValueError('slots must be a non-empty list of distinct slots, got %r' % (slots,))
+        mel = engine._require_cuda_f32(mel, 'mel')
+        if mel.dim() != 3 or mel.shape[0] != k or mel.shape[1] < 1 or mel.shape[2] != st.n_mels:
+            raise ValueError('mel must be [%d, f >= 1, %d], got %s' % (k, st.n_mels, tuple(mel.shape)))
+        for s in slots:
+            if not st._running[s]:
+                raise ValueError('slot %d is fresh: a session starts with the eager one-frame push (push(mel[:, :1], slots=[%d]) keeps the '
+                                 'frame and marks the slot running) and takes graphed ticks from then on' % (s, s))
+        if self.sample and z is not None:
+            raise ValueError('this graph samples its own noise (sample=True): z is not taken')
+        if not self.sample:
+            if z is None:
+                raise ValueError('this graph has no sampler (sample=False): z [%d, %d, 1] is required' % (k, mel.shape[1] * st.hop))
+            z = engine._require_cuda_f32(z, 'z')
+            if tuple(z.shape) != (k, mel.shape[1] * st.hop, 1):
+                raise ValueError('z must be [%d, %d, 1], got %s' % (k, mel.shape[1] * st.hop, tuple(z.shape)))
+        if engine.persist_suspended():
+            self.graph = None       # (the suspension retired the workspace the captured launches point at)
+        if engine.persist_suspended() or mel.shape[1] != self.frames or k > self.n:
+            if st._pending is not None:
+                self._carry = self.verify()        # (what it returns counts the carry in)
+            self.eager_calls += 1
+            return st.push(mel, slots=slots, z=z, verify=False)
+        if st._pending is not None and st._ticker is not self:
+            self._carry = self.verify()        # (what it returns counts the carry in)            # an eager push that only enqueued (or another graph's ticks): settled first
+        if self.graph is None or self.store.version != self._version or self._mode != engine.launch_knobs():
+            if st._pending is not None:
+                self._carry = self.verify()        # (what it returns counts the carry in)
+            self._capture()         # first tick after a suspension, new weights (the launches point at stale packs), other launch knobs
+        engine.note_forward()
+        if len(self._events) >= self.depth:
+            self._events.popleft().synchronize()       # bounds the work that can pile up behind a refused tick (and frees staging j)
+        j = self._ticks % self.depth
+        self._ticks += 1
+        self._sync_rows(j, slots, self._write_entries(j, slots, 1))
+        self.mel[:k].copy_(mel, non_blocking=True)
+        if z is not None:
+            self.z[:k].copy_(z, non_blocking=True)
+        if self._dirty_rows > k:
+            self.mel[k:self._dirty_rows].zero_()
+            self.z[k:self._dirty_rows].zero_()
+        self._dirty_rows = k
+        self.graph.replay()
+        ev = torch.cuda.Event()
+        ev.record()
+        self._events.append(ev)
+        self._inflight.update(slots)
+        st._pending, st._ticker = self.verify, self
+        return self.out[:k]
+
+    def _sync_rows(self, j: int, slots, fillers) -> None:
+        """The session rows of the tick's entries -- the called slots, then the fillers --, rewritten where the host's view says the device
+        row differs (first tick, an eager push, reset or load_state since).  A filler needs its row as much as a called slot: the
+        generation it WRITES must be the one the session does not stand on.  A slot with ticks in flight is the device's: its row is
+        what those ticks leave."""
+        st, rows = self.stream, self._rows_host[j]
+        for i, s in enumerate(list(slots) + list(fillers)):
+            if s in self._inflight:
+                continue
+            have, seed = st._sess_host[s], st._seed[s]
+            if i >= len(slots):
+                # a filler's noise is nobody's: only the generation and the counter have to be the session's
+                if have is not None and have[:2] == (st._gen[s], st._emitted[s]):
+                    continue
+                seed = seed if seed is not None else 0
+            elif seed is None:
+                seed = int.from_bytes(os.urandom(7), 'little') if self.sample else 0
+            want = (st._gen[s], st._emitted[s], engine.as_int64_bits(seed))
+            if have != want:
+                rows[i, 0], rows[i, 1], rows[i, 2], rows[i, 3] = want[0], want[1], want[2], 0
+                st._sess[s].copy_(rows[i], non_blocking=True)
+                st._sess_host[s] = want
+
+    def verify(self) -> int:
+        """Wait for the ticks in flight, make the host's view of their sessions (generation, emitted, seed, running) equal to the device
+        table and return the number of ticks committed since the last verify().  Raises PwvRangeError / PwvPersistError, with that
+        number as `.committed`, if a sticky word is raised: the committed ticks are the first `.committed` ones, the sessions stand
+        behind them.  After a PwvPersistError the graph is dropped: ticks run eagerly until the suspension ends, then capture again."""
+        st = self.stream
+        if st._ticker is not self:
+            if st._ticker is not None:
+                return st._ticker.verify()
+            had = st._pending is not None          # an eager tick (push(verify=False)) of ours
+            try:
+                st.verify()
+            except _lib.PwvError as e:
+                e.committed, self._carry = self._carry, 0
+                if isinstance(e, _lib.PwvPersistError):
+                    self.graph = None
+                raise
+            done, self._carry = self._carry + (1 if had else 0), 0
+            return done
+        if self._events:
+            torch.cuda.current_stream(self.device).wait_event(self._events[-1])      # (verify() from another stream than the ticks')
+        self._counters_host.copy_(self._counters, non_blocking=True)
+        self._sess_back.copy_(st._sess, non_blocking=True)
+        torch.cuda.synchronize()
+        counters = [int(v) for v in self._counters_host.tolist()]
+        committed, refused = counters[0] - self._seen[0], counters[1] - self._seen[1]
+        self._seen = counters
+        table = self._sess_back.tolist()
+        for s in self._inflight:
+            gen, emitted, seed = int(table[s][0]) & 1, int(table[s][1]), int(table[s][2])
+            st._gen[s], st._emitted[s], st._running[s] = gen, emitted, True
+            if self.sample:
+                st._seed[s] = seed & ((1 << 64) - 1)
+            st._sess_host[s] = (gen, emitted, seed)
+        self._inflight.clear()
+        self._events.clear()
+        st._pending, st._ticker = None, None
+        committed, self._carry = committed + self._carry, 0
+        try:
+            engine.verify_enqueued('a graphed streaming tick', words=self._words)
+            if self._words is not engine.current_words(self.device):
+                engine.verify_enqueued('a graphed streaming tick')
+            if refused:
+                raise _lib.PwvError('%d graphed ticks were refused by their commit (a sticky word was raised and has been cleared since)' % refused)
+        except _lib.PwvError as e:
+            e.committed = committed
+            if isinstance(e, _lib.PwvPersistError):
+                self.graph = None
+            raise
+        return committed
 
 
 class _Layout(object):

@@ -107,6 +107,41 @@ def ragged_plan(frames: Sequence[int], fresh: Sequence[bool], hop: int) -> Ragge
     return RaggedPlan(samples, launch, cu_rows, cu_frames)
 
 
+def tick_begin_tables(sess, kept, entries, mel, hop: int):
+    """(numpy restatement of stream_tick_begin_kernel, csrc/pwv_stream_tick.hip; tests, and the definition of the tables)  From the device
+    session table `sess` (int64 [n_slots, 4] = {generation read, samples emitted, seed bits, 0}), the kept frames `kept` [n_slots, n_mels],
+    the tick's `entries` (int32 [N, 2] = {slot, live}) and its mel [N, f, n_mels]: (slot_tab int32 [N, 2], streams int64 [N, 2] =
+    {seed, emitted}, cu_rows int32 [N + 1], frames float32 [N, f + 1, n_mels]) -- what push builds on the host for the same sessions.
+    `live` plays no part here: a filler reads and writes like any other entry."""
+    sess, kept, mel = np.asarray(sess, np.int64), np.asarray(kept, np.float32), np.asarray(mel, np.float32)
+    entries = np.asarray(entries, np.int32).reshape(-1, 2)
+    n, f = entries.shape[0], mel.shape[1]
+    T = f * int(hop)
+    slots = np.where((entries[:, 0] >= 0) & (entries[:, 0] < sess.shape[0]), entries[:, 0], 0)      # (out of range: a filler of slot 0)
+    g = sess[slots, 0] & 1
+    slot_tab = np.stack([2 * slots + g, 2 * slots + 1 - g], axis=1).astype(np.int32)
+    streams = np.stack([sess[slots, 2], sess[slots, 1]], axis=1).astype(np.int64)
+    cu_rows = (np.arange(n + 1, dtype=np.int64) * T).astype(np.int32)
+    frames = np.concatenate([kept[slots][:, None], mel], axis=1).astype(np.float32)
+    return slot_tab, streams, cu_rows, frames
+
+
+def tick_commit(sess, kept, entries, mel, T: int, words):
+    """(numpy restatement of stream_tick_commit_kernel)  (sess, kept, committed) after the tick's last node: with both sticky `words`
+    (give-up, range) zero every LIVE entry's session flips its generation, has emitted T more samples and keeps the chunk's last
+    frame; otherwise -- and for every filler -- nothing changes.  Returns copies."""
+    sess, kept = np.array(sess, np.int64), np.array(kept, np.float32)
+    mel = np.asarray(mel, np.float32)
+    if int(words[0]) != 0 or int(words[1]) != 0:
+        return sess, kept, False
+    for i, (slot, live) in enumerate(np.asarray(entries, np.int32).reshape(-1, 2)):
+        if live and 0 <= slot < sess.shape[0]:
+            sess[slot, 0] ^= 1
+            sess[slot, 1] += int(T)
+            kept[slot] = mel[i, -1]
+    return sess, kept, True
+
+
 class RaggedOutput(list):
     """What StreamingVocoder.push_varlen returns: the [T_i, 1] pieces of the call's sessions (views; empty for a fresh session given one
     frame), with the packed [sum T_i, 1] result as `.packed` (as models.VarlenOutput)."""
@@ -173,6 +208,13 @@ class StreamingVocoder(object):
         self._emitted = [0] * self.n_slots
         self._seed: List[Optional[int]] = [None] * self.n_slots
         self._pending = None                        # the commit of an un-verified push (verify=False / PWV_ASYNC=1)
+        # graph replay of a tick (graph.GraphedStream): the sessions as the device sees them -- int64 [n_slots, 4] = {generation read,
+        # samples emitted, seed bits, 0} --, per slot what that row is known to hold (None: never written), the graph whose ticks are
+        # in flight, and the fresh slots a FILLER entry has written generation 1 - g of (zeros no longer: see _commit)
+        self._sess = torch.zeros((self.n_slots, 4), dtype=torch.int64, device=self.device)
+        self._sess_host: List[Optional[tuple]] = [None] * self.n_slots
+        self._ticker = None
+        self._scratch_dirty = [False] * self.n_slots
 
     # -- bookkeeping -----------------------------------------------------------------------------------------------------
     def _slot(self, slot) -> int:
@@ -200,7 +242,7 @@ class StreamingVocoder(object):
         self._settled('reset')
         s = self._slot(slot)
         self._hist[2 * s:2 * s + 2].zero_()
-        self._gen[s], self._running[s], self._emitted[s] = 0, False, 0
+        self._gen[s], self._running[s], self._emitted[s], self._scratch_dirty[s] = 0, False, 0, False
         self._seed[s] = None if seed is None else self._check_seed(seed)
 
     @staticmethod
@@ -229,10 +271,18 @@ class StreamingVocoder(object):
         """For pushes that only enqueued (verify=False / PWV_ASYNC=1): wait, raise PwvRangeError if the chunk left the range of the
         split-fp16 arithmetic (the sessions then stand where they stood before the push: push the chunk again on a precision='f32'
         stream of the same state), else advance the sessions."""
+        if self._ticker is not None:          # graphed ticks are in flight: their graph settles them (and returns how many committed)
+            return self._ticker.verify()
         commit, self._pending = self._pending, None
         engine.verify_enqueued('a streaming push')
         if commit is not None:
             commit()
+
+    def graphed(self, n: int, frames: int, sample: bool = True, depth: int = 4, warmup: int = 2):
+        """One tick of `n` running sessions x `frames` frames captured into a HIP graph with the commit on the device
+        (graph.GraphedStream; DESIGN.md section 9, "Graph replay of a streaming tick")."""
+        from .graph import GraphedStream
+        return GraphedStream(self, n, frames, sample=sample, depth=depth, warmup=warmup)
 
     # -- a push ----------------------------------------------------------------------------------------------------------
     def _slots(self, slots) -> List[int]:
@@ -249,6 +299,11 @@ class StreamingVocoder(object):
         push drew its own noise) and the kept frames `last` [n, n_mels] (idx: the slots as a device index vector, None = all in order)."""
         def commit():
             for i, s in enumerate(slots):
+                if samples[i] == 0 and self._scratch_dirty[s]:
+                    # a fresh slot given one frame flips without having written the other generation, which counts on the zeros a
+                    # reset left there; a filler entry of a graphed tick has used that block as scratch since: zeros again first
+                    self._hist[2 * s + 1 - self._gen[s]].zero_()
+                self._scratch_dirty[s] = False
                 self._gen[s] ^= 1
                 self._running[s] = True
                 self._emitted[s] += samples[i]

@@ -1,0 +1,193 @@
+"""CPU: the host side of the graphed streaming tick (csrc/pwv_stream_tick.hip, graph.GraphedStream): the two new entry points of the
+C ABI and their ctypes mirror, their refusals (each names its field, none needs a device), the numpy restatement of the two kernels
+against what StreamingVocoder.push / _commit do on the host today, and the compiler's resource remarks for the two kernels."""
+import ctypes
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, 'parallel-wavenet-vocoder_amd', 'csrc')
+SYMBOLS = ('pwv_stream_tick_begin', 'pwv_stream_tick_commit')
+
+
+def test_abi_symbols_struct_and_version(built_lib, tmp_path):
+    """Both symbols are declared in the header, listed in EXPORTED_SYMBOLS and exported by the built library; the C compiler's size and
+    offsets of pwv_stream_tick_args equal the ctypes mirror's; no existing struct changed, so the version is still 301."""
+    from pwv_amd import _lib
+    header = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', 'pwv_hip.h')).read(), flags=re.S)
+    raw = ctypes.CDLL(_lib.LIB_PATH)
+    for name in SYMBOLS:
+        assert re.search(r'\bint %s\s*\(const pwv_stream_tick_args\*' % name, header), name
+        assert name in _lib.EXPORTED_SYMBOLS and hasattr(raw, name), name
+    assert os.path.join(CSRC, 'pwv_stream_tick.hip') in _lib.CSRC
+    fields = [f[0] for f in _lib.StreamTickArgs._fields_]
+    assert fields[0] == 'struct_size'
+    probe = ['sizeof(pwv_stream_tick_args)'] + ['offsetof(pwv_stream_tick_args, %s)' % f for f in fields]
+    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "pwv_hip.h"\nint main(void){ printf("%s %%d\\n", %s, PWV_HIP_VERSION); return 0; }\n'
+           % (' '.join(['%zu'] * len(probe)), ', '.join(probe)))
+    c, exe = str(tmp_path / 't.c'), str(tmp_path / 't')
+    with open(c, 'w') as f:
+        f.write(src)
+    subprocess.check_call(['gcc', '-std=c99', '-Wall', '-Wextra', '-pedantic', '-Werror', '-I' + os.path.join(ROOT, 'include'), c, '-o', exe])
+    got = [int(x) for x in subprocess.check_output([exe]).decode().split()]
+    S = _lib.StreamTickArgs
+    assert got == [ctypes.sizeof(S)] + [getattr(S, f).offset for f in fields] + [301]
+    assert S().struct_size == ctypes.sizeof(S)
+    assert built_lib.pwv_version() == _lib.HEADER_VERSION == 301
+
+
+def _args(**kw):
+    """A complete pwv_stream_tick_args on made-up addresses: nothing may be launched or dereferenced on the refused paths."""
+    from pwv_amd import _lib
+    ta = _lib.StreamTickArgs()
+    ta.sess, ta.kept, ta.entries, ta.mel = 0x10000, 0x20000, 0x30000, 0x40000
+    ta.n_slots, ta.N, ta.frames, ta.n_mels, ta.T = 4, 2, 10, 80, 800
+    ta.slot_tab, ta.streams, ta.cu_rows, ta.chunk = 0x50000, 0x60000, 0x70000, 0x80000
+    ta.words, ta.counters = 0x90000, 0xa0000
+    for k, v in kw.items():
+        setattr(ta, k, v)
+    return ta
+
+
+_BOTH = [('sess', None, b'sess'), ('kept', None, b'kept'), ('entries', None, b'entries'), ('mel', None, b'mel'), ('N', 0, b'N must'),
+         ('frames', 0, b'frames must'), ('n_mels', 0, b'n_mels'), ('T', 0, b'T must'), ('n_slots', 0, b'n_slots'),
+         ('struct_size', 0, b'struct_size'), ('struct_size', 16, b'struct_size')]
+
+
+@pytest.mark.parametrize('symbol', SYMBOLS)
+@pytest.mark.parametrize('field,value,named', _BOTH, ids=['%s=%r' % (f, v) for f, v, _ in _BOTH])
+def test_refusals_name_the_field(built_lib, symbol, field, value, named):
+    fn = getattr(built_lib, symbol)
+    assert fn(ctypes.byref(_args(**{field: value})), None) == -1
+    err = built_lib.pwv_last_error()
+    assert named in err and symbol.encode() in err, err
+
+
+def test_refusals_of_each_entry_point(built_lib):
+    lib = built_lib
+    assert lib.pwv_stream_tick_begin(None, None) == -1 and b'args is NULL' in lib.pwv_last_error()
+    assert lib.pwv_stream_tick_commit(None, None) == -1 and b'args is NULL' in lib.pwv_last_error()
+    for field in ('slot_tab', 'chunk'):
+        assert lib.pwv_stream_tick_begin(ctypes.byref(_args(**{field: None})), None) == -1
+        assert field.encode() in lib.pwv_last_error(), lib.pwv_last_error()
+    for field in ('streams', 'cu_rows'):          # the sampler's tables go together
+        assert lib.pwv_stream_tick_begin(ctypes.byref(_args(**{field: None})), None) == -1
+        assert b'streams and cu_rows' in lib.pwv_last_error(), lib.pwv_last_error()
+    for field in ('words', 'counters'):
+        assert lib.pwv_stream_tick_commit(ctypes.byref(_args(**{field: None})), None) == -1
+        assert field.encode() in lib.pwv_last_error(), lib.pwv_last_error()
+
+
+# ---- the restatement against the host code of push ------------------------------------------------------------------------------------
+class _HostStream(object):
+    """The host bookkeeping of StreamingVocoder, without a device: `push_tables` is what push() builds (stream.py: frames = cat(kept, mel),
+    the noise table {seed, emitted}, cu = arange * T, tab = {2s + gen, 2s + 1 - gen}), `commit` what _commit's closure does."""
+
+    def __init__(self, rng, n_slots, n_mels):
+        self.gen = [int(v) for v in rng.integers(0, 2, n_slots)]
+        self.emitted = [int(v) * 80 for v in rng.integers(0, 1000, n_slots)]
+        self.seed = [int(v) for v in rng.integers(0, 1 << 63, n_slots)]
+        self.seed[0] = (1 << 63) + 9          # a seed whose top bit is set: carried as the int64 with the same bits
+        self.kept = rng.uniform(-1, 1, (n_slots, n_mels)).astype(np.float32)
+
+    def sess(self):
+        from pwv_amd import engine
+        return np.array([[g, e, engine.as_int64_bits(sd), 0] for g, e, sd in zip(self.gen, self.emitted, self.seed)], np.int64)
+
+    def push_tables(self, slots, mel, hop):
+        from pwv_amd import engine
+        n, T = len(slots), mel.shape[1] * hop
+        frames = np.concatenate([self.kept[slots][:, None], mel], axis=1)
+        cu = np.arange(0, (n + 1) * T, T, dtype=np.int32)
+        table = np.array([[engine.as_int64_bits(self.seed[s]), engine.as_int64_bits(self.emitted[s])] for s in slots], np.int64)
+        tab = np.array([[2 * s + self.gen[s], 2 * s + 1 - self.gen[s]] for s in slots], np.int32)
+        return tab, table, cu, frames
+
+    def commit(self, slots, T, last):
+        for i, s in enumerate(slots):
+            self.gen[s] ^= 1
+            self.emitted[s] += T
+        self.kept[slots] = last
+
+
+@pytest.mark.parametrize('shape', [(1, [0], 1), (6, [4, 1], 10), (8, [5, 2, 7, 0], 3)], ids=['1x1', '2of6', '4of8'])
+def test_restatement_equals_what_push_builds(shape):
+    from pwv_amd import stream
+    n_slots, slots, f = shape
+    hop, n_mels = 80, 80
+    rng = np.random.default_rng(n_slots)
+    host = _HostStream(rng, n_slots, n_mels)
+    mel = rng.uniform(-1, 1, (len(slots), f, n_mels)).astype(np.float32)
+    entries = [[s, 1] for s in slots]
+    tab, streams, cu, frames = stream.tick_begin_tables(host.sess(), host.kept, entries, mel, hop)
+    want = host.push_tables(slots, mel, hop)
+    for got, w in zip((tab, streams, cu, frames), want):
+        assert got.dtype == w.dtype and np.array_equal(got, w)
+    # `live` plays no part in the tables: a filler reads generation g and writes generation 1 - g like any other entry
+    again = stream.tick_begin_tables(host.sess(), host.kept, [[s, 0] for s in slots], mel, hop)
+    assert all(np.array_equal(a, b) for a, b in zip(again, (tab, streams, cu, frames)))
+    # the commit with clean words is _commit's effect ...
+    sess0, kept0 = host.sess(), host.kept.copy()
+    sess1, kept1, done = stream.tick_commit(sess0, kept0, entries, mel, f * hop, (0, 0))
+    host.commit(slots, f * hop, mel[:, -1])
+    assert done and np.array_equal(sess1, host.sess()) and np.array_equal(kept1, host.kept)
+    assert np.array_equal(sess0[:, 2:], sess1[:, 2:])          # the seeds do not move
+    # ... with either word raised it changes nothing ...
+    for words in ((4, 0), (0, 1), (1, 1)):
+        s2, k2, done = stream.tick_commit(sess0, kept0, entries, mel, f * hop, words)
+        assert not done and np.array_equal(s2, sess0) and np.array_equal(k2, kept0)
+    # ... and a filler never changes the table or the kept frames
+    mixed = [[s, 1 if i == 0 else 0] for i, s in enumerate(slots)]
+    s3, k3, done = stream.tick_commit(sess0, kept0, mixed, mel, f * hop, (0, 0))
+    assert done
+    for i, s in enumerate(slots):
+        if i == 0:
+            assert s3[s, 0] == sess0[s, 0] ^ 1 and s3[s, 1] == sess0[s, 1] + f * hop and np.array_equal(k3[s], mel[0, -1])
+        else:
+            assert np.array_equal(s3[s], sess0[s]) and np.array_equal(k3[s], kept0[s])
+    s4, k4, _ = stream.tick_commit(sess0, kept0, [[s, 0] for s in slots], mel, f * hop, (0, 0))
+    assert np.array_equal(s4, sess0) and np.array_equal(k4, kept0)
+
+
+def test_ticks_chain_like_pushes():
+    """Three ticks through the restatement (begin tables of tick j from the table tick j - 1 committed) against three host pushes: the
+    device table alone carries the generation, the counter offset and the kept frame from tick to tick."""
+    from pwv_amd import stream
+    rng = np.random.default_rng(3)
+    host = _HostStream(rng, 3, 8)
+    sess, kept = host.sess(), host.kept.copy()
+    slots, hop = [2, 0], 80
+    for _ in range(3):
+        mel = rng.uniform(-1, 1, (2, 2, 8)).astype(np.float32)
+        got = stream.tick_begin_tables(sess, kept, [[s, 1] for s in slots], mel, hop)
+        assert all(np.array_equal(a, b) for a, b in zip(got, host.push_tables(slots, mel, hop)))
+        sess, kept, _ = stream.tick_commit(sess, kept, [[s, 1] for s in slots], mel, 2 * hop, (0, 0))
+        host.commit(slots, 2 * hop, mel[:, -1])
+    assert np.array_equal(sess, host.sess()) and np.array_equal(kept, host.kept)
+
+
+def test_the_two_tick_kernels_use_no_scratch():
+    """The compiler's resource remarks for pwv_stream_tick.hip (gfx950 device code, no GPU needed): both kernels with 0 bytes of scratch
+    and nothing spilled."""
+    out = subprocess.run(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950:xnack-', '-O3', '-std=c++17', '-c', '--cuda-device-only',
+                          '-Rpass-analysis=kernel-resource-usage', '-I' + os.path.join(ROOT, 'include'), '-I' + CSRC, '-o', os.devnull,
+                          os.path.join(CSRC, 'pwv_stream_tick.hip')], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True).stdout
+    names = re.findall(r'Function Name: (\S+)', out)
+    scratch = [int(x) for x in re.findall(r'ScratchSize \[bytes/lane\]: (\d+)', out)]
+    vspill = [int(x) for x in re.findall(r'VGPRs Spill: (\d+)', out)]
+    sspill = [int(x) for x in re.findall(r'SGPRs Spill: (\d+)', out)]
+    vgprs = [int(x) for x in re.findall(r' VGPRs: (\d+)', out)]
+    assert names and len(names) == len(scratch) == len(vspill) == len(sspill) == len(vgprs), out[-2000:]
+    seen = {}
+    for name, sc, vs, ss, vg in zip(names, scratch, vspill, sspill, vgprs):
+        for kernel in ('stream_tick_begin_kernel', 'stream_tick_commit_kernel'):
+            if kernel in name:
+                seen[kernel] = (sc, vs, ss, vg)
+    print('tick kernels (scratch, spilled VGPRs, spilled SGPRs, VGPRs):', seen)
+    assert sorted(seen) == ['stream_tick_begin_kernel', 'stream_tick_commit_kernel'], names
+    for kernel, (sc, vs, ss, vg) in seen.items():
+        assert sc == 0 and vs == 0 and ss == 0, (kernel, sc, vs, ss)

@@ -29,6 +29,19 @@ twice):
 `ragged_over_grouped` / `ragged_over_uniform` per round, and `spread` = the largest difference between the two medians of a leg.
 
     python tools/stream_bench.py --ragged [--steps 20] [--warmup 5] [--precision f16x3]
+
+--graph ("Graph replay of a streaming tick"): the tick as ONE graph replay with the commit on the device
+(StreamingVocoder.graphed).  Cells (sessions x chunk): 1 x 800, 1 x 1600, 2 x 800, 8 x 800, 32 x 1600.  Legs, same protocol (explicit z,
+one synchronisation per tick, median of --steps after --warmup, the legs of a cell one after the other in one process, the round twice):
+  stream           the eager push(verify=False) + verify(): the baseline, unchanged code
+  graph            one tick() + verify()
+  graph_pipelined  8 ticks enqueued back to back (no host synchronisation between them, the default depth of 4 ticks in flight), one
+                   verify(), divided by 8
+  overlap          overlap-and-discard, as above
+`spread` = the largest difference between the two medians of a leg; `graph_not_slower_than_stream`: graph <= stream + spread in both
+rounds.  `graph_over_stream`, `graph_pipelined_over_stream`, `overlap_over_graph` per round.
+
+    python tools/stream_bench.py --graph [--steps 20] [--warmup 5] [--precision f16x3]
 """
 import argparse
 import json
@@ -49,6 +62,7 @@ def main():
     ap.add_argument('--sessions', default='1,8,32')
     ap.add_argument('--chunks', default='800,1600,8000')
     ap.add_argument('--ragged', action='store_true', help='the ragged-tick cells (push_varlen against grouped pushes) instead of the default legs')
+    ap.add_argument('--graph', action='store_true', help='the graphed-tick cells (StreamingVocoder.graphed against the eager push) instead of the default legs')
     args = ap.parse_args()
 
     import numpy as np
@@ -157,6 +171,51 @@ def main():
             cell['ragged_over_grouped'] = [round(a / b, 3) for a, b in zip(cell['ragged']['ms'], cell['grouped']['ms'])]
             cell['ragged_over_uniform'] = [round(a / b, 3) for a, b in zip(cell['ragged']['ms'], cell['uniform']['ms'])]
             cell['ragged_not_slower_than_grouped'] = all(a <= b + cell['spread'] for a, b in zip(cell['ragged']['ms'], cell['grouped']['ms']))
+            out['cells'].append(cell)
+            print('# %s' % json.dumps(cell), file=sys.stderr)
+        print(json.dumps(out))
+        return
+
+    if args.graph:
+        out = {'mode': 'graph', 'precision': args.precision, 'steps': args.steps, 'warmup': args.warmup, 'chain_halo': halo, 'pipelined_ticks': 8,
+               'cells': []}
+        for S, chunk in ((1, 800), (1, 1600), (2, 800), (8, 800), (32, 1600)):
+            model = IAFVocoder(batch_size=S, length=chunk, store=store, precision=args.precision)
+            stream = model.open_stream(slots=S)
+            warm = -(-(halo + hop) // hop) * hop
+            stream.push(rand(S, warm // hop + 1, cfg.n_mels), z=rand(S, warm, 1))        # steady state: emitted > chain_halo
+            graphed = stream.graphed(S, chunk // hop, sample=False)
+            slots = list(range(S))
+            mel_s, z_s = rand(S, chunk // hop, cfg.n_mels), rand(S, chunk, 1)
+            over = IAFVocoder(batch_size=S, length=chunk + halo, store=store, precision=args.precision)
+            mel_o, z_o = rand(S, (chunk + halo) // hop + 1, cfg.n_mels), rand(S, chunk + halo, 1)
+
+            def pipelined():
+                for _ in range(8):
+                    graphed.tick(mel_s, slots, z=z_s)
+
+            legs = {
+                'stream': (lambda: stream.push(mel_s, z=z_s, verify=False), stream.verify, 1),
+                'graph': (lambda: graphed.tick(mel_s, slots, z=z_s), graphed.verify, 1),
+                'graph_pipelined': (pipelined, graphed.verify, 8),
+                'overlap': (lambda: over(None, mel_o, z=z_o, verify=False)[:, halo:], lambda: engine.verify_enqueued('overlap'), 1),
+            }
+            cell = {'sessions': S, 'chunk': chunk, 'stream_rows': S * chunk, 'overlap_rows': S * (chunk + halo)}
+            for name in legs:
+                cell[name] = {'ms': [], 'enqueue_ms': []}
+            for _ in range(2):
+                for name, (fn, sync, ticks) in legs.items():
+                    ms, host = timed(fn, sync)
+                    cell[name]['ms'].append(round(ms / ticks, 4))
+                    cell[name]['enqueue_ms'].append(round(host / ticks, 4))
+            assert graphed.captures == 1 and graphed.eager_calls == 0
+            assert stream.emitted(0) == warm + 2 * 10 * (args.warmup + args.steps) * chunk
+            cell['spread'] = round(max(abs(cell[name]['ms'][0] - cell[name]['ms'][1]) for name in legs), 4)
+            ratio = lambda a, b: [round(x / y, 3) for x, y in zip(cell[a]['ms'], cell[b]['ms'])]      # noqa: E731
+            cell['graph_over_stream'] = ratio('graph', 'stream')
+            cell['graph_pipelined_over_stream'] = ratio('graph_pipelined', 'stream')
+            cell['overlap_over_graph'] = ratio('overlap', 'graph')
+            cell['graph_not_slower_than_stream'] = all(g <= e + cell['spread'] for g, e in zip(cell['graph']['ms'], cell['stream']['ms']))
             out['cells'].append(cell)
             print('# %s' % json.dumps(cell), file=sys.stderr)
         print(json.dumps(out))
