@@ -145,6 +145,12 @@ class GraphedVocoder(object):
             self._noise_mirror = want
 
 
+def packed_filler_rows(hop: int) -> int:
+    """Rows of a filler utterance of GraphedPackedVocoder: one hop, or the smallest multiple of hop of at least _lib.VARLEN_MIN_ROWS."""
+    hop = int(hop)
+    return hop * -(-max(hop, _lib.VARLEN_MIN_ROWS) // hop)
+
+
 class GraphedPackedVocoder(object):
     """The packed forward of IAFVocoder.generate_varlen with one noise stream per utterance (seeds=), captured once at a capacity
     of `slots` utterances and `rows` samples and replayed for ANY lengths that fit it ("Graph replay of packed
@@ -174,7 +180,7 @@ class GraphedPackedVocoder(object):
         if self.device.type != 'cuda':
             raise _lib.PwvError('GraphedPackedVocoder needs a GPU (cuda device); there is no CPU path')
         self.hop = hop = int(hp.signal.hop_length)
-        self.filler = hop * -(-max(hop, _lib.VARLEN_MIN_ROWS) // hop)
+        self.filler = packed_filler_rows(hop)
         self.slots, self.rows = int(slots), int(rows)
         if self.slots < 1 or self.rows % hop or self.rows < self.slots * self.filler:
             raise ValueError('a capacity of %d slots needs rows a multiple of %d and at least %d, got %d'

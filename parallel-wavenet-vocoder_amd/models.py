@@ -289,11 +289,16 @@ class IAFVocoder(object):
         precision = precision or self.precision
         n_samples = self.length if length is None else length
         hop = hp.signal.hop_length
-        assert (np.prod(np.array(strides)) == hop)                              # models.py:106
+        method = hp.model.cond_upsample_method
+        # models.py:106 holds every method to prod(strides) == hop; only the transposed convolutions read the strides, so 'repeat' and no
+        # conditioning run at any even hop here (the oracle draws the same line)
+        assert method != 'transposed_conv' or np.prod(np.array(strides)) == hop
         if n_samples % hop != 0:
             raise ValueError('length (%d) must be a multiple of hop_length (%d): the crop at models.py:124,133 '
                              'yields (t_mel-1)*hop samples' % (n_samples, hop))
-        method = hp.model.cond_upsample_method
+        if hop < 2 or hop % 2:
+            raise ValueError('hop_length (%d) must be even and at least 2: the crop [hop//2 : -(hop//2)] at models.py:124,133 leaves '
+                             '(t_mel-1)*hop + 1 samples of an odd hop (and nothing of hop 1), so the reference has no answer there' % hop)
         n, t_mel, n_mels = melspec.shape
         C = hp.model.condition_channels
         if method == 'transposed_conv':

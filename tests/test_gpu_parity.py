@@ -58,7 +58,9 @@ def test_linear(gpu, M, K, Nout, relu, bias, precision):
 PRECS = ['f32', 'f16x3']
 
 
-def _wavenet_case(gpu, cond_mode, use_skip, use_biases, q_out, T=300, N=2, dil=(1, 2, 4, 8, 16), precision='f32'):
+def _wavenet_case(gpu, cond_mode, use_skip, use_biases, q_out, T=300, N=2, dil=(1, 2, 4, 8, 16), precision='f32', geom=(80, 40), spare=0):
+    """`geom` = (hop, offset) of the frame-rate condition: sample t reads frame (t + offset) // hop (any pair: only IAFVocoder ties the
+    offset to hop // 2); the frames hold exactly the rows that needs, plus `spare`."""
     import torch
     from pwv_amd.engine import RepeatedCondition
     from pwv_amd.modules import WaveNet
@@ -71,15 +73,14 @@ def _wavenet_case(gpu, cond_mode, use_skip, use_biases, q_out, T=300, N=2, dil=(
     net_name = 'shared' if q_out == 2 else 'scalar'
     scope = 'iaf_vocoder/iaf0/' + net_name
     x = rng.randn(N, T, 1).astype(np.float32)
-    hop = 80
+    hop, offset = geom
     cond_np = None
     cond_dev = None
     if cond_mode != 'none':
-        assert T % hop == 0
-        frames = np.maximum(rng.randn(N, T // hop + 1, 80), 0).astype(np.float32)
-        cond_np = np.repeat(frames, hop, axis=1)[:, hop // 2: -(hop // 2), :]
+        frames = np.maximum(rng.randn(N, (T - 1 + offset) // hop + 1 + spare, 80), 0).astype(np.float32)
+        cond_np = frames[:, (np.arange(T) + offset) // hop, :]
         if cond_mode == 'frames':
-            cond_dev = RepeatedCondition(_t(frames, gpu), hop, hop // 2, T)
+            cond_dev = RepeatedCondition(_t(frames, gpu), hop, offset, T)
         else:
             cond_dev = _t(cond_np, gpu)
     want = O.wavenet_forward(weights, scope, x, cond_np, dilations=list(dil), use_biases=use_biases,
@@ -296,8 +297,10 @@ def test_misuse_raises(gpu):
         IAFVocoder(2, 160, store=store)(None, torch.zeros(2, 3, 80, device=gpu), False, z=torch.zeros(2, 80, 1, device=gpu))
     with pytest.raises(ValueError):                       # filter Cin mismatch
         causal_conv(torch.zeros(1, 8, 4, device=gpu), torch.zeros(2, 5, 4, device=gpu), 1)
-    hp = set_hparams(cfg)
-    hp.signal.hop_length = 40                             # prod(strides) != hop  (assert at models.py:106)
+    # prod(strides) != hop (assert at models.py:106) where the strides are read: the transposed convolutions.  ('repeat' reads no
+    # strides and runs at any even hop: tests/test_gpu_hop_geometry.py.)
+    hp = set_hparams(small_cfg(cond_upsample_method='transposed_conv'))
+    hp.signal.hop_length = 40
     with pytest.raises(AssertionError):
         IAFVocoder(1, 80, store=store)(None, torch.zeros(1, 3, 80, device=gpu), False)
     set_hparams(cfg)

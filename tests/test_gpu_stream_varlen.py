@@ -3,8 +3,8 @@ mixed, in ONE packed persistent launch per flow (pwv_persist_args.cu_rows with h
 engine.run_flow_stream with a geometry).  The contract is push's: the pieces of a session concatenate to its own one-shot forward bit
 for bit, a session does not depend on its companions, a push is a transaction.  Every case that claims the new kernel first shows from
 engine.EVENT_LOG / PERSIST_ARGS_HOOK that it RAN (cu_rows, unit_map and hist all set, and in which instantiation).
-(No small configuration has hop < 32, so a session under 32 rows cannot be made: the grouped route is reached with PERSIST = False and
-through a suspension.)"""
+(Every configuration here runs hop 80, so a session under 32 rows cannot be made: the grouped route is reached with PERSIST = False and
+through a suspension.  tests/test_gpu_hop_geometry.py reaches it at hop 16 with PERSIST at its default: a one-frame session of 16 rows.)"""
 import ctypes
 
 import numpy as np

@@ -58,6 +58,21 @@ def small_cfg(**kw):
     return O.ModelConfig(**base)
 
 
+# Conditioning geometry at hops other than 80 (tests/test_gpu_hop_geometry.py, tests/test_hop_geometry_host.py).  2: offset 1, up to 17
+# P rows per 32-row unit; 16: below the unit; 32: a frame boundary at row 16 of every unit, power-of-two magic; 48: neither a power of two
+# nor a multiple of 32; 96: a multiple of 32 that is no power of two; 256: a power of two above every dilation of the small models.
+HOPS = (2, 16, 32, 48, 96, 256)
+# hop -> (utterances, samples each) of the one-shot cases: at least 3 frames per utterance, and a total row count that is no multiple of
+# 32 wherever the hop allows one (140, 144, 432 rows); 5 to 48 units of 32 rows, so both persistent instantiations can be asked for
+HOP_CASES = {2: (2, 70), 16: (3, 48), 32: (3, 96), 48: (3, 144), 96: (2, 288), 256: (2, 768)}
+
+
+def hop_cfg(hop, **kw):
+    """The small two-flow model of the streaming / packed tests (every flow at least 4 layers: shorter stacks have no persistent form)
+    at another hop."""
+    return small_cfg(dilations=[[1, 2, 4, 8], [1, 2, 4, 8, 16, 32]], hop_length=hop, **kw)
+
+
 def f16_storage_model(weights, cfg):
     """What the PWV_PREC_F16 build extension computes, restated for the fp64 oracle: the weights as its kernels
     hold them (fp16 after the exp2 scale folding of csrc/pwv_layer_common.h; dense / skip / postprocess1 plain
