@@ -121,12 +121,15 @@ struct PersistParams {
 // -DPWV_PTRACE: every wave accumulates s_memtime cycles: [0] whole loop, [1] drain at the top, [2] RAW spins, [3] WAR spins,
 // [4] settle (publish / leave / refill), [5] units, [6] tasks that were not prefetched, [7] first task at, [8] last task done at;
 // round 5, phases of a unit of the general loop (PT_PHASE: the time since the previous stamp goes to slot k): [9] top of the unit up
-// to the drain (P row requested, next task located, look-back row split), [10] GEMM1, [11] GEMM2, [12] stores + moving on
+// to the drain (P row requested, next task located, look-back row split), [10] GEMM1, [11] GEMM2, [12] stores + moving on;
+// inside [11] (PT_LAP: the time since PT_BEGIN or the previous lap goes to slot k): [13] prefetch_next (the next unit's rows requested -- and whatever
+// the wave waits for before it gets on), [14] GEMM2 proper
 #ifdef PWV_PTRACE
-#define PT_DECL long long pt_acc[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; long long pt_t = 0, pt_p = 0; (void)pt_t; (void)pt_p;
+#define PT_DECL long long pt_acc[15] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; long long pt_t = 0, pt_p = 0; (void)pt_t; (void)pt_p;
 #define PT_BEGIN() pt_t = __builtin_amdgcn_s_memtime()
 #define PT_END(k) pt_acc[k] += __builtin_amdgcn_s_memtime() - pt_t
 #define PT_ADD(k, v) pt_acc[k] += (v)
+#define PT_LAP(k) do { __builtin_amdgcn_sched_barrier(0); const long long pt_n = __builtin_amdgcn_s_memtime(); pt_acc[k] += pt_n - pt_t; pt_t = pt_n; __builtin_amdgcn_sched_barrier(0); } while (0)
 #define PT_MARK() do { __builtin_amdgcn_sched_barrier(0); pt_p = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } while (0)
 #define PT_PHASE(k) do { __builtin_amdgcn_sched_barrier(0); const long long pt_n = __builtin_amdgcn_s_memtime(); pt_acc[k] += pt_n - pt_p; pt_p = pt_n; __builtin_amdgcn_sched_barrier(0); } while (0)
 // event timeline (round 6, tools/persist_timeline.py): 1 unit computed, 2 stores issued, 3 own stores acknowledged (in front of a wait; 13 in front of a WAR wait), 4 dependencies
@@ -138,6 +141,7 @@ struct PersistParams {
 #define PT_BEGIN() do {} while (0)
 #define PT_END(k) do {} while (0)
 #define PT_ADD(k, v) do {} while (0)
+#define PT_LAP(k) do {} while (0)
 #define PT_MARK() do {} while (0)
 #define PT_PHASE(k) do {} while (0)
 #define PT_EV(code, jj, uu) do {} while (0)

@@ -224,16 +224,21 @@
 #pragma unroll
             for (int e = 0; e < 4; ++e) xc[4 * g + e] = v[e];
         }
-        auto load_b = [&](bool keep) {
+        // ONE load sequence for the look-back row; units at an utterance start (rare) zero their lanes IN PLACE behind it, under a wave-uniform
+        // branch.  (Two sequences -- a plain one for __all(has_prev), one with the select -- had the compiler share the first chunk's load between
+        // them and join the two results in another register than the one it is loaded into: `s_waitcnt vmcnt(7)` + a v_mov_b32 on the FAST path, i.e.
+        // every unit stalled in front of GEMM2 until its successor's own rows and that chunk had arrived; tests/test_persist_prefetch_isa.py.)
+        // The fast path has no instruction behind the loads: they stay in flight.
 #pragma unroll
-            for (int g = 0; g < 8; ++g) {
-                const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ring_rs, ob + g * 1024, so, 16));
+        for (int g = 0; g < 8; ++g) {
+            const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ring_rs, ob + g * 1024, so, 16));
 #pragma unroll
-                for (int e = 0; e < 4; ++e) xb[4 * g + e] = keep ? v[e] : 0.f;
-            }
-        };
-        if (__all(has_prev)) load_b(true);      // wave-uniform fast path: no select behind the loads, they stay in flight
-        else load_b(has_prev);
+            for (int e = 0; e < 4; ++e) xb[4 * g + e] = v[e];
+        }
+        if (!__all(has_prev)) {
+#pragma unroll
+            for (int k = 0; k < 32; ++k) xb[k] = has_prev ? xb[k] : 0.f;
+        }
         hist_lookback(j, d, nn, t, unit, rc, xb);
     };
 
@@ -795,12 +800,15 @@
             PT_MARK();
         };
         // the next task's rows: requested between GEMM1 and GEMM2, in flight under GEMM2 + gating + stores -- if their
-        // producers are done (normally they are a layer-sweep old); otherwise behind this unit's stores, after a wait
+        // producers are done (normally they are a layer-sweep old); otherwise behind this unit's stores, after a wait.
+        // ("In flight" is a property of the COMPILED loop, not of this source: no s_waitcnt vmcnt may stand between the loads and GEMM2's
+        //  first fragment reads on the wave-uniform path; see load_x and tests/test_persist_prefetch_isa.py.  -DPWV_PTRACE slot [13] times it.)
         // (stationary units) the word of a LEFT NEIGHBOUR's unit the next task waits for: asked for here, under GEMM2 -- a poll is a
         // 2 us round trip, and that unit, its workgroup's top one, is usually through by now; the answer goes into its byte before the wait
         int early_v = -1;
         auto prefetch_next = [&]() {
             PT_PHASE(10);
+            PT_BEGIN();
             if (u2 >= 0 && !(bad2 & kRawMask) && !stat) {
                 load_x(j2, u2, rxb, rxc);
             } else {      // (ends the old rows' live ranges: without it they would occupy 64 registers through both GEMMs)
@@ -820,6 +828,7 @@
                     early_v = __hip_atomic_load(prog_n + (size_t)(w + 1 + lo - 32) * kProgStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             __builtin_amdgcn_sched_barrier(0);
+            PT_LAP(13);
         };
         // the last fragment of the dense matrix (not in LDS): global memory, 16 bytes per lane
         const float* lastfrag = packed_n + (size_t)j * p.packed_stride + kSlot + lane * 4;
@@ -881,6 +890,7 @@
                         }
                     }
                 });
+            PT_LAP(14);
         } else {
             const f16x8* A1 = reinterpret_cast<const f16x8*>(lds + (j & 1) * kSlot);
             const f16x8* A2 = reinterpret_cast<const f16x8*>(lds + (j & 1) * kSlot + kA1Size);
@@ -969,6 +979,7 @@
                         asm volatile("" : "+v"(oh[2 + (s & 1)]), "+v"(ol[2 + (s & 1)]));
                     }
                 });
+            PT_LAP(14);
         }
         if (dead) break;
         PT_PHASE(11);
@@ -1378,7 +1389,7 @@
         pt_acc[8] = __builtin_amdgcn_s_memtime();
         pt_acc[0] = pt_acc[8] - pt_start;
         long long* tr = p.trace + ((size_t)blockIdx.x * 8 + wave) * 24;
-        for (int k = 0; k < 13; ++k) tr[k] = pt_acc[k];
+        for (int k = 0; k < 15; ++k) tr[k] = pt_acc[k];
         tr[16] = net; tr[17] = w; tr[18] = dead ? 1 : 0; tr[19] = __builtin_amdgcn_s_memrealtime(); tr[20] = pt_start_rt;
     }
 #endif

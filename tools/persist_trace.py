@@ -56,6 +56,10 @@ def main():
                     (10, 'GEMM1 (filter|gate, K = 128; gate of pair 0)'), (11, 'GEMM2 (dense; gate of pair 1; next rows requested)'),
                     (12, 'stores + moving on (incl. the waits for the next task)')):
         print('  phase %-68s %7.0f cycles per unit' % (name, (t[:, k] / t[:, 5]).mean()))
+    # inside the GEMM2 phase: the request for the next unit's rows (with whatever the wave waits for before it gets on) and GEMM2 proper
+    for k, name in ((13, 'prefetch_next (next rows requested; any wait behind the loads)'), (14, 'GEMM2 proper (24 MFMAs, gate + split of pair 1)')):
+        print('    of GEMM2: %-62s %7.0f cycles per unit (%.1f %% of a unit)'
+              % (name, (t[:, k] / t[:, 5]).mean(), 100 * (t[:, k] / tot).mean()))
     t0 = t[:, 20].min()
     st, en = (t[:, 20] - t0) / 100.0, (t[:, 19] - t0) / 100.0
     print('loop start %.1f .. %.1f us, loop end %.1f .. %.1f us (chip-wide 100 MHz clock)' % (st.min(), st.max(), en.min(), en.max()))
