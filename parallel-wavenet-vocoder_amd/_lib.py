@@ -8,6 +8,7 @@ through a CPU implementation.
 from __future__ import annotations
 
 import ctypes
+import glob
 import hashlib
 import os
 import subprocess
@@ -239,6 +240,19 @@ def _digest(parts) -> str:
     return hashlib.sha256('\0'.join(parts).encode()).hexdigest()[:16]
 
 
+def _hipcc() -> str:
+    return os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
+
+
+def device_compile_command(src: str) -> list:
+    """The shipped compile command of one source, without its mode (-c, -S, ...), input and output: build_library derives its own
+    from it, and the tests that look at resource remarks or assembly compile what ships."""
+    # ONE gfx950 code object for the XNACK mode an MI355X runs in by default (xnack-): code built for a known mode instead of
+    # 'either' is 0.5 % faster on the bench step; xnack+ objects (XNACK-on runs) are not available on the GPU pool
+    return ([_hipcc(), '--offload-arch=gfx950:xnack-', '-O3', '-std=c++17', '-I' + os.path.join(_REPO_ROOT, 'include'), '-I' + os.path.join(_PKG_DIR, 'csrc')]
+            + EXTRA_FLAGS.get(os.path.basename(src), []) + os.environ.get('PWV_CXXFLAGS', '').split())
+
+
 def build_library(force: bool = False, verbose: bool = False) -> str:
     """Compile the HIP sources for gfx950 into the in-tree shared library: one object per source, compiled in parallel.
 
@@ -250,20 +264,14 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
     from concurrent.futures import ThreadPoolExecutor
     if os.environ.get('PWV_LIB'):
         return LIB_PATH            # an explicitly chosen library is never rebuilt
-    hdrs = [os.path.join(_PKG_DIR, 'csrc', h) for h in ('pwv_common.h', 'pwv_layer_common.h', 'pwv_f16x3.h', 'pwv_layer_f16x3_body.inc',
-                                                         'pwv_layer_f32_body.inc', 'pwv_stack_persist_body.inc')] + [os.path.join(_REPO_ROOT, 'include', 'pwv_hip.h')]
+    # every header and body of csrc/, by pattern: a new part can never be missing from the staleness check
+    hdrs = glob.glob(os.path.join(_PKG_DIR, 'csrc', '*.h')) + glob.glob(os.path.join(_PKG_DIR, 'csrc', '*.inc')) + [os.path.join(_REPO_ROOT, 'include', 'pwv_hip.h')]
     hdr_time = max(os.path.getmtime(h) for h in hdrs + [os.path.abspath(__file__)])
-    hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
-    # ONE gfx950 code object for the XNACK mode an MI355X runs in by default (xnack-): code built for a known mode instead of
-    # 'either' is 0.5 % faster on the bench step; xnack+ objects (XNACK-on runs) are not available on the GPU pool
-    base = [hipcc, '--offload-arch=gfx950:xnack-', '-O3', '-std=c++17', '-fPIC',
-            '-I' + os.path.join(_REPO_ROOT, 'include'), '-I' + os.path.join(_PKG_DIR, 'csrc')]
-    extra = os.environ.get('PWV_CXXFLAGS', '').split()
     compiles = []                  # (source, object, command without the output)
     for src in CSRC:
-        cmd = base + EXTRA_FLAGS.get(os.path.basename(src), []) + extra + ['-c', src]
+        cmd = device_compile_command(src) + ['-fPIC', '-c', src]
         compiles.append((src, os.path.join(OBJ_DIR, '%s.%s.o' % (os.path.basename(src), _digest(cmd))), cmd))
-    link = [hipcc, '--offload-arch=gfx950:xnack-', '-shared', '-fPIC'] + [o for _, o, _ in compiles]
+    link = [_hipcc(), '--offload-arch=gfx950:xnack-', '-shared', '-fPIC'] + [o for _, o, _ in compiles]
     link_hash = _digest(link)
     stamp = os.path.join(OBJ_DIR, os.path.basename(LIB_PATH) + '.inputs')
     newest = max([hdr_time] + [os.path.getmtime(s) for s in CSRC])

@@ -1,6 +1,8 @@
 // The body of layer_f16x3_kernel and of its streaming form layer_f16x3_stream_kernel (pwv_layer_f16.hip), included into both: the kernel's parameter block
 // `p`, `constexpr bool STREAM` and `const StreamParams st` are in scope.  Text, not a function: the non-streaming kernels keep the very
 // instruction streams they had before the streaming form existed (tools/isa_compare.py).
+// The fused head of the HEAD variants is text of its own, pwv_head_f16x3.inc and pwv_head_pp2.inc, which the persistent kernel's tail (pwv_persist_tail.inc)
+// includes too: the two are bit-identical because they are one text.
     static_assert(!HEAD || (GATED && !SKIP && !COND && !FIRST), "HEAD: plain last layer only");
     static_assert(!FOLD || FIRST, "FOLD: layer 0 of a scalar-input net only");
     static_assert(!STREAM || (!SKIP && !COND && FOLD == FIRST && GATED == HEAD), "STREAM: folded layer 0, plain residual layer, last layer + head");
@@ -329,66 +331,14 @@
             const float* hb = p.packed_head[net];
             const f16x8* HS = reinterpret_cast<const f16x8*>(&lds[kHS]);
             const f16x8* H1 = reinterpret_cast<const f16x8*>(&lds[kH1]);
-            f32x16 accs[4];      // starts at the skip bias (requested now, lands while pair 1 is gated)
-#pragma unroll
-            for (int it = 0; it < 4; ++it)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const f32x4 v = *reinterpret_cast<const f32x4*>(hb + kHBS + h * 64 + it * 16 + q * 4);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) accs[it][q * 4 + e] = v[e];
-                }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[16 + r] = gate_act(acc[1][r], acc[3][r]);
-            split8<16>(o, oh[2], ol[2]);
-            split8<24>(o, oh[3], ol[3]);
-            first_frags<4, 4, 0, 1, 4>(HS, lane, ah, al);
-            gemm16<4, 4, 0, 1, 4>(HS, lane, accs, ah, al, [&](int s) -> f16x8 { return oh[s]; },
-                                  [&](int s) -> f16x8 { return ol[s]; }, no_extra,
-                                  [&](f16x8(&nh)[4], f16x8(&nl)[4]) { first_frags<8, 4, 0, 1, 4>(H1, lane, nh, nl); });
-            f32x16 acc1[4];      // starts at the postprocess1 bias
-#pragma unroll
-            for (int it = 0; it < 4; ++it)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const f32x4 v = *reinterpret_cast<const f32x4*>(hb + kHB1 + h * 64 + it * 16 + q * 4);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) acc1[it][q * 4 + e] = v[e];
-                }
-            f16x8 sh[8], sl[8];
-            {
-                float r[64];
-#pragma unroll
-                for (int i = 0; i < 64; ++i) r[i] = fmaxf(accs[i >> 4][i & 15], 0.f);
-                split8<0>(r, sh[0], sl[0]);
-                split8<8>(r, sh[1], sl[1]);
-                split8<16>(r, sh[2], sl[2]);
-                split8<24>(r, sh[3], sl[3]);
-                split8<32>(r, sh[4], sl[4]);
-                split8<40>(r, sh[5], sl[5]);
-                split8<48>(r, sh[6], sl[6]);
-                split8<56>(r, sh[7], sl[7]);
-            }
-            gemm16<8, 4, 0, 1, 4>(H1, lane, acc1, ah, al, [&](int s) -> f16x8 { return sh[s]; },
-                                  [&](int s) -> f16x8 { return sl[s]; }, no_extra, [](f16x8(&)[4], f16x8(&)[4]) {});
+            f32x16 acc1[4];
+#include "pwv_head_f16x3.inc"
             load_x(next, rxb, rxc);      // the next unit's rows: in flight under the postprocess2 dot
             const int Q = p.head_q;
-            for (int q = 0; q < Q; ++q) {
-                float part = 0.f;
-                const float* w2 = hb + kHW2 + (h * Q + q) * 64;
-#pragma unroll
-                for (int i4 = 0; i4 < 16; ++i4) {
-                    const f32x4 w = *reinterpret_cast<const f32x4*>(w2 + 4 * i4);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const int i = 4 * i4 + e;
-                        part = fmaf(fmaxf(acc1[i >> 4][i & 15], 0.f), w[e], part);
-                    }
-                }
-                part += __shfl_xor(part, 32);
-                part += hb[kHW2 + 2 * Q * 64 + q];
-                if (valid && h == 0) p.head_out[net][(size_t)row * Q + q] = part;
-            }
+            const int hq = h * Q;
+#define PWV_HEAD_STORE(q, part) if (valid && h == 0) p.head_out[net][(size_t)row * Q + (q)] = (part)
+#include "pwv_head_pp2.inc"
+#undef PWV_HEAD_STORE
         } else if constexpr (GATED) {
             if constexpr (!SKIP) load_x(next, rxb, rxc);      // (SKIP: requested in front of the skip GEMM, see below)
             __builtin_amdgcn_sched_barrier(0);

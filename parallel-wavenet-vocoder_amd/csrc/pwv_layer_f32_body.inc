@@ -1,6 +1,8 @@
 // The body of layer_f32_kernel and of its streaming form layer_f32_stream_kernel (pwv_layer.hip), included into both: the kernel's parameter block
 // `p`, `constexpr bool STREAM` and `const StreamParams st` are in scope.  Text, not a function: the non-streaming kernels keep the very
 // instruction streams they had before the streaming form existed (tools/isa_compare.py).
+// The fused head of the HEAD variants is text of its own, pwv_head_f32.inc and pwv_head_pp2.inc, which the persistent kernel's tail (pwv_persist_tail.inc)
+// includes too: the two are bit-identical because they are one text.
     static_assert(!FOLD || FIRST, "FOLD: layer 0 of a scalar-input net only");
     static_assert(!STREAM || (!SKIP && !COND && FOLD == FIRST && GATED == HEAD), "STREAM: folded layer 0, plain residual layer, last layer + head");
     static_assert(!HEAD || (GATED && !SKIP && !COND && !FIRST), "HEAD: plain last layer only");
@@ -202,51 +204,15 @@
             // ---- fused head: o (registers) -> skip -> relu -> postprocess1 -> relu -> postprocess2, the operations
             //      (and bits) of head_f32_kernel<true> ------------------------------------------------------------
             const float* hb = p.packed_head[net];
-            f32x16 accs[4];
-#pragma unroll
-            for (int it = 0; it < 4; ++it)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const f32x4 v = *reinterpret_cast<const f32x4*>(hb + kHBS + h * 64 + it * 16 + q * 4);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) accs[it][q * 4 + e] = v[e];
-                }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[16 + r] = gate_act(acc[1][r], acc[3][r]);
-            gemm_groups<8, 4, 0, 1>(lds, kHS, lane, accs, a, [&](int ks) -> float { return o[ks]; }, no_extra,
-                                    [&](f32x4(&n)[4]) {
-#pragma unroll
-                                        for (int i = 0; i < 4; ++i) n[i] = frag(lds, kH1, i, 16, 0, lane);
-                                    });
             f32x16 acc1[4];
-#pragma unroll
-            for (int it = 0; it < 4; ++it)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const f32x4 v = *reinterpret_cast<const f32x4*>(hb + kHB1 + h * 64 + it * 16 + q * 4);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) acc1[it][q * 4 + e] = v[e];
-                }
-            gemm_groups<16, 4, 0, 1>(
-                lds, kH1, lane, acc1, a, [&](int ks) -> float { return fmaxf(accs[ks >> 4][ks & 15], 0.f); }, no_extra,
-                [](f32x4(&)[4]) {});
+#define PWV_HEAD_FENCE() do {} while (0)
+#include "pwv_head_f32.inc"
+#undef PWV_HEAD_FENCE
             const int Q = p.head_q;
-            for (int q = 0; q < Q; ++q) {
-                float part = 0.f;
-                const float* w2 = hb + kHW2 + (h * Q + q) * 64;
-#pragma unroll
-                for (int i4 = 0; i4 < 16; ++i4) {
-                    const f32x4 w = *reinterpret_cast<const f32x4*>(w2 + 4 * i4);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const int i = 4 * i4 + e;
-                        part = fmaf(fmaxf(acc1[i >> 4][i & 15], 0.f), w[e], part);
-                    }
-                }
-                part += __shfl_xor(part, 32);
-                part += hb[kHW2 + 2 * Q * 64 + q];
-                if (cur.valid && h == 0) p.head_out[net][(size_t)cur.row * Q + q] = part;
-            }
+            const int hq = h * Q;
+#define PWV_HEAD_STORE(q, part) if (cur.valid && h == 0) p.head_out[net][(size_t)cur.row * Q + (q)] = (part)
+#include "pwv_head_pp2.inc"
+#undef PWV_HEAD_STORE
         } else if constexpr (GATED) {
             if constexpr (SKIP) load_skip_row<SKIP, COND>(p, net, lane, cur, skip_load);      // in flight under the gating
 #pragma unroll

@@ -32,7 +32,14 @@
 //  * Every wait is bounded (20 ms, or until any wave of the launch has given up) and reports through a sticky status word in pinned host memory; the host then reruns on the
 //    per-layer path.  All workgroups must be resident (grid <= CUs, one workgroup per CU by its LDS size).
 // Results are bit-identical to the per-layer launches (same per-unit arithmetic): tests/test_gpu_persist.py.
+//
+// Files: this one holds the constants of the LDS layout, PersistParams, the kernel templates and the launcher.  The kernels' body is
+// pwv_stack_persist_body.inc, which includes its parts in order -- pwv_persist_geometry.inc (row maps, descriptors, row loaders),
+// _protocol (dependency bytes, progress words, waits, task claiming), _loader, _fold0, _tasks (the unit's arithmetic in
+// pwv_persist_unit_f32.inc / pwv_persist_unit_f16x3.inc), _tail (the fused head: pwv_head_f32.inc / pwv_head_f16x3.inc / pwv_head_pp2.inc, the
+// very text of the per-layer HEAD kernels) and _exit.  The plan and the workspace layout need no device: pwv_persist_plan.h.
 #include "pwv_f16x3.h"
+#include "pwv_persist_plan.h"
 
 #include <cstddef>
 #include <cstdlib>
@@ -49,24 +56,17 @@ constexpr int kCtlF = kBiasF + 128;            // control ints: [0] task counter
 constexpr int kCtlInts = 40;
 constexpr int kLdsFloats = 40960;              // all 160 KB of the CU
 constexpr int kCfF = kCtlF + kCtlInts;       // causal filter [2][64] (a run that starts with the net's layer 0, see x_first)
-constexpr int kLeftN = 32;                                 // unit mode (short inputs): "layers completed" bytes of the 32 units LEFT of the range, as last seen
 constexpr int kLeftB = (kCfF + 128) * 4;                   // ... in front of the own units' bytes, so one linear address serves both
 constexpr int kDoneB = kLeftB + kLeftN;                    // byte offset of the per-unit "layers completed" bytes
-constexpr int kMaxUnitsWg = kLdsFloats * 4 - kDoneB;       // 832 units per workgroup
-// unit mode up to this many units per workgroup and layer (wave 7 is the loader.  Against the general kernel: 4 units per workgroup -17 %,
-// 5: -8 %, 6: -11.5 %, 7: -11 %; profiles/r06_ab_experiments.md, r06_z2)
-constexpr int kUnitModeMaxPerWg = 7;
+constexpr int kMaxUnitsWgLds = kLdsFloats * 4 - kDoneB;    // units per workgroup: one "layers completed" byte each
+static_assert(kMaxUnitsWg == kMaxUnitsWgLds && kPlanMaxQ == kMaxQ, "pwv_persist_plan.h restates the kernel's limits");
 static_assert(kUnitModeMaxPerWg <= 7, "the short-input instantiation keeps wave 7 as its loader");
 // unit mode reads the left neighbours' unit words with lanes 1 / 2 and the right neighbours' workgroup words with lanes 32..63 of one
 // instruction (poll_units): the look-back stays within 32 units, and persist_plan grants it only with at most 32 right neighbours
 static_assert(kLeftN <= 32, "unit mode: the right neighbours are polled by lanes 32..63 alone");
-constexpr int kUnitStride = 32;                            // ints between two units' words (own 128-byte lines: a poll asks for exactly the unit it waits for)
 constexpr int kFlagB = (kCtlF + 2) * 4;        // flag bytes: +0 seenL, +1 seenR, +2 / +3 newest layer in LDS slot 0 / 1, +4 always 255
 constexpr int kSeenLB = kFlagB, kSeenRB = kFlagB + 1, kWreadyB = kFlagB + 2, kTrueB = kFlagB + 4;
-constexpr int kMaxPLayers = 32;
 constexpr long long kWaitTicks = 2000000;      // a wave gives up after 20 ms of the chip-wide 100 MHz clock (normal waits: microseconds)
-constexpr int kProgStride = 32;                // ints between two workgroups' progress words (own 128-byte lines)
-constexpr int kMaxReachWgs = 60;               // neighbours polled by one wave instruction
 
 struct PersistParams {
     float* ring[PWV_MAX_NETS];             // three full-size tile32 buffers, `ring_stride` floats apart; layer j reads buffer (j + 2 + rot) % 3, writes (j + rot) % 3
@@ -314,58 +314,16 @@ int pwv_persist_status(int** status) {
 #define RAGGED_F32 1
 #endif
 
-struct PersistPlan { int units, nwg, per_wg, last_wg, reach_wgs, xcd_map, tail_reach_wgs, unit_mode; };
-
-static int persist_plan(int G, long long rows, int n_layers, const int* dil, int cus, int max_wgs, int min_units, int tail_q, int tail_dil, PersistPlan& pl) {
-    PWV_CHECK_ARG(G >= 1 && G <= PWV_MAX_NETS, "persistent stack: G=%d out of range", G);
-    PWV_CHECK_ARG(n_layers >= 2 && n_layers <= kMaxPLayers && dil, "persistent stack: 2..%d layers per launch, got %d", kMaxPLayers, n_layers);
-    PWV_CHECK_ARG(rows >= 1 && rows < (1ll << 31) - 256, "persistent stack: bad N*T");
-    PWV_CHECK_ARG(cus >= G, "persistent stack: %d CUs for %d nets", cus, G);
-    int dmax = 1;
-    for (int j = 0; j < n_layers; ++j) {
-        PWV_CHECK_ARG(dil[j] >= 1, "persistent stack: bad dilation");
-        dmax = dil[j] > dmax ? dil[j] : dmax;
-    }
-    pl.units = (int)((rows + 31) / 32);
-    PWV_CHECK_ARG((long long)pl.units * 8192 < (1ll << 32), "persistent stack: buffers beyond the 4 GB reach of a buffer descriptor");
-    int wgs = cus / G;                                  // every workgroup must be resident: one per CU (its LDS is the whole CU's)
-    if (max_wgs > 0 && max_wgs / G < wgs) wgs = max_wgs / G;
-    PWV_CHECK_ARG(wgs >= 1, "persistent stack: no workgroups");
-    // short inputs: at least `min_units` units per workgroup and layer: fewer workgroups instead of ranges of one or two units
-    // (default 4 = one per SIMD; measured at 16000 rows x 2 nets: 0.64 ms per forward with 4, 0.76 ms with 8)
-    if (min_units <= 0) min_units = 4;
-    int want = (pl.units + min_units - 1) / min_units;
-    if (want < 1) want = 1;
-    pl.nwg = wgs < want ? wgs : want;
-    pl.per_wg = (pl.units + pl.nwg - 1) / pl.nwg;
-    PWV_CHECK_ARG(pl.per_wg <= kMaxUnitsWg, "persistent stack: %d units per workgroup (max %d)", pl.per_wg, kMaxUnitsWg);
-    pl.last_wg = (pl.units - 1) / pl.per_wg;
-    const int reach = (dmax + 31) / 32;      // units a task looks back (RAW) / is looked back at from (WAR)
-    pl.reach_wgs = (reach + pl.per_wg - 1) / pl.per_wg;
-    PWV_CHECK_ARG(pl.reach_wgs <= kMaxReachWgs, "persistent stack: dilation %d reaches over %d workgroups (max %d)", dmax, pl.reach_wgs, kMaxReachWgs);
-    const int grid = G * pl.nwg;
-    pl.xcd_map = (pl.nwg % 8 == 0 && grid % 8 == 0) ? 1 : 0;
-    // Short inputs (a handful of units per workgroup and layer: every layer is ONE unit's latency per SIMD): progress per UNIT instead of per
-    // workgroup.  A range's bottom unit waits for the left neighbour's TOP units, which that workgroup computes FIRST; its workgroup word
-    // appears only when its slowest unit -- its own bottom one, which waited for ITS left neighbour -- is through: with workgroup words every
-    // layer of the chain costs a cross-workgroup hop (profiles/r06_short_timeline.md).
-    pl.unit_mode = 0;      // 2: the short-input instantiation (the launcher: and a folded layer 0, if the run starts there)
-    if (reach <= kLeftN && pl.nwg > 1 && pl.per_wg <= kUnitModeMaxPerWg) {
-        pl.unit_mode = 2;
-        PWV_CHECK_ARG(pl.reach_wgs <= 32, "persistent stack: unit mode polls at most 32 right neighbours (reach %d workgroups)", pl.reach_wgs);
-    }
-    // the tail's layer looks back too (a stack whose LAST dilation is its largest passed the probe and failed at the launch)
-    pl.tail_reach_wgs = 0;
-    if (tail_q > 0) {
-        PWV_CHECK_ARG(tail_q <= kMaxQ && tail_dil >= 1, "persistent stack: tail_q 1..%d, tail_dilation >= 1", kMaxQ);
-        PWV_CHECK_ARG(rows * tail_q * 4 < (1ll << 32), "persistent stack: tail_out beyond the 4 GB reach of a buffer descriptor");
-        pl.tail_reach_wgs = ((tail_dil + 31) / 32 + pl.per_wg - 1) / pl.per_wg;
-        PWV_CHECK_ARG(pl.tail_reach_wgs <= kMaxReachWgs, "persistent stack: tail dilation %d reaches over %d workgroups (max %d)", tail_dil, pl.tail_reach_wgs, kMaxReachWgs);
-    }
-    return PWV_OK;
-}
-
-static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+// the four kernel families, each [F32][MODE == 2]
+typedef void (*persist_kernel_t)(const PersistParams);
+#define PERSIST_FAMILY(K, ...) {{K<false, 0, ##__VA_ARGS__>, K<false, 2, ##__VA_ARGS__>}, {K<true, 0, ##__VA_ARGS__>, K<true, 2, ##__VA_ARGS__>}}
+static const persist_kernel_t kUniform[2][2] = PERSIST_FAMILY(stack_persist_kernel, false), kPacked[2][2] = PERSIST_FAMILY(stack_persist_kernel, true),
+                              kStreaming[2][2] = PERSIST_FAMILY(stack_persist_kernel, false, true);
+#if RAGGED_F32
+static const persist_kernel_t kRagged[2][2] = PERSIST_FAMILY(stack_persist_ragged_kernel);
+#else
+static const persist_kernel_t kRagged[2][2] = {{stack_persist_ragged_kernel<false, 0>, stack_persist_ragged_kernel<false, 2>}, {nullptr, nullptr}};
+#endif
 
 static bool is_varlen(const pwv_persist_args* a) { return a->cu_rows || a->cu_frames || a->unit_map || a->varlen_rows != 0; }
 // the rows a launch covers: N*T, or R of a packed batch
@@ -432,57 +390,63 @@ static int persist_args_copy(const pwv_persist_args* a, pwv_persist_args& out, c
     return PWV_OK;
 }
 
-size_t pwv_persist_workspace_bytes(const pwv_persist_args* args) {
+// One resolution of the caller's arguments for the three entry points: the struct copy, what can be refused without a device, the plan
+// and the workspace layout.  `launch`: the launcher's own refusals, in the places they have always had among the others.
+struct Resolved {
+    pwv_persist_args a;
+    pwv_stream_args sa;
     PersistPlan pl;
+    PersistLayout lay;
+};
+
+static int persist_resolve(const pwv_persist_args* args, const char* who, Resolved& r, bool launch = false) {
+    if (int rc = persist_args_copy(args, r.a, who)) return rc;
+    const pwv_persist_args* a = &r.a;
+    if (launch) PWV_CHECK_ARG(a->workspace, "%s: NULL workspace", who);
+    if (int rc = varlen_check(a, who)) return rc;
+    r.sa = pwv_stream_args{};
     const int cus = device_cus();
-    pwv_persist_args copy;
-    if (persist_args_copy(args, copy, "pwv_persist_workspace_bytes") != PWV_OK) return 0;
-    const pwv_persist_args* a = &copy;
-    if (varlen_check(a, "pwv_persist_workspace_bytes") != PWV_OK) return 0;
-    if (persist_plan(a->G, launch_rows(a), a->n_layers, a->dilations, cus, a->max_workgroups, a->min_units_per_workgroup, a->tail_q, a->tail_dilation, pl) != PWV_OK) return 0;
-    // progress words + the abort word + the exit counter (one 256-byte line) + one arrival counter per range (the tail's affine)
-    // (+ in unit mode one word per unit and net)
-    return align256((size_t)a->G * pl.nwg * kProgStride * 4 + 256) + align256((size_t)pl.nwg * 4) + (pl.unit_mode ? align256((size_t)a->G * pl.units * kUnitStride * 4) : 0);
+    if (launch) {
+        if (int rc = stream_check(a, r.sa, who)) return rc;
+        PWV_CHECK_ARG(!(a->hist && is_varlen(a)) || a->precision == PWV_PREC_F16X3 || RAGGED_F32, "%s: the ragged launch (hist->cu_rows) is built for PWV_PREC_F16X3 only", who);
+        if (cus <= 0) return set_error(PWV_EHIP, "no HIP device");
+    }
+    if (int rc = persist_plan(a->G, launch_rows(a), a->n_layers, a->dilations, cus, a->max_workgroups, a->min_units_per_workgroup, a->tail_q, a->tail_dilation, r.pl)) return rc;
+    r.lay = persist_layout(a->G, r.pl);
+    return PWV_OK;
+}
+
+size_t pwv_persist_workspace_bytes(const pwv_persist_args* args) {
+    Resolved r;
+    return persist_resolve(args, "pwv_persist_workspace_bytes", r) == PWV_OK ? r.lay.total : 0;
 }
 
 int pwv_persist_short_input(const pwv_persist_args* args) {
-    PersistPlan pl;
-    pwv_persist_args copy;
-    if (persist_args_copy(args, copy, "pwv_persist_short_input") != PWV_OK) return -1;
-    const pwv_persist_args* a = &copy;
-    if (varlen_check(a, "pwv_persist_short_input") != PWV_OK) return -1;
-    if (persist_plan(a->G, launch_rows(a), a->n_layers, a->dilations, device_cus(), a->max_workgroups, a->min_units_per_workgroup, a->tail_q, a->tail_dilation, pl) != PWV_OK) return -1;
-    return short_input_mode(a, pl) == 2 ? 1 : 0;
+    Resolved r;
+    if (persist_resolve(args, "pwv_persist_short_input", r) != PWV_OK) return -1;
+    return short_input_mode(&r.a, r.pl) == 2 ? 1 : 0;
 }
 
 int pwv_wavenet_stack_persist_f32(const pwv_persist_args* args, pwv_stream_t stream) {
-    pwv_persist_args copy;
-    if (int rc0 = persist_args_copy(args, copy, "pwv_wavenet_stack_persist_f32")) return rc0;
-    const pwv_persist_args* a = &copy;
-    PWV_CHECK_ARG(a->workspace, "pwv_wavenet_stack_persist_f32: NULL workspace");
-    if (int rc1 = varlen_check(a, "pwv_wavenet_stack_persist_f32")) return rc1;
-    pwv_stream_args sa{};
-    if (int rc2 = stream_check(a, sa, "pwv_wavenet_stack_persist_f32")) return rc2;
+    Resolved r;
+    if (int rc0 = persist_resolve(args, "pwv_wavenet_stack_persist_f32", r, true)) return rc0;
+    const pwv_persist_args* a = &r.a;
+    const pwv_stream_args& sa = r.sa;
+    PersistPlan& pl = r.pl;
     const bool varlen = is_varlen(a);
     const bool streaming = a->hist != nullptr;
     const bool ragged = streaming && varlen;      // (stream_check: then hist->cu_rows == cu_rows)
-    PWV_CHECK_ARG(!ragged || a->precision == PWV_PREC_F16X3 || RAGGED_F32, "pwv_wavenet_stack_persist_f32: the ragged launch (hist->cu_rows) is built for PWV_PREC_F16X3 only");
-    const int cus = device_cus();
-    if (cus <= 0) return set_error(PWV_EHIP, "no HIP device");
     PersistParams p{};
-    PersistPlan pl;
-    int rc = persist_plan(a->G, launch_rows(a), a->n_layers, a->dilations, cus, a->max_workgroups, a->min_units_per_workgroup, a->tail_q, a->tail_dilation, pl);
-    if (rc != PWV_OK) return rc;
     PWV_CHECK_ARG(a->N >= 1 && (varlen || a->T >= 1), "pwv_wavenet_stack_persist_f32: bad N/T");
     PWV_CHECK_ARG(a->precision == PWV_PREC_F16X3 || a->precision == PWV_PREC_F32, "pwv_wavenet_stack_persist_f32: precision must be PWV_PREC_F16X3 or PWV_PREC_F32");
     PWV_CHECK_ARG(a->proj_row_stride % 4 == 0 && a->cond_hop >= 0, "pwv_wavenet_stack_persist_f32: bad projection arguments");
-    PWV_CHECK_ARG(a->workspace_bytes >= pwv_persist_workspace_bytes(a), "pwv_wavenet_stack_persist_f32: workspace too small");
+    PWV_CHECK_ARG(a->workspace_bytes >= r.lay.total, "pwv_wavenet_stack_persist_f32: workspace too small");
     PWV_CHECK_ARG(((uintptr_t)a->workspace & 255) == 0, "pwv_wavenet_stack_persist_f32: workspace must be 256-byte aligned");
     p.prog = (int*)a->workspace;
-    p.abort = p.prog + (size_t)a->G * pl.nwg * kProgStride;
+    p.abort = (int*)((char*)a->workspace + r.lay.prog_bytes);
     p.exited = p.abort + 1;
-    int* const pair_words = (int*)((char*)a->workspace + align256((size_t)a->G * pl.nwg * kProgStride * 4 + 256));
-    p.uprog = (int*)((char*)pair_words + align256((size_t)pl.nwg * 4));
+    int* const pair_words = (int*)((char*)a->workspace + r.lay.pair_off);
+    p.uprog = (int*)((char*)a->workspace + r.lay.uprog_off);
     pl.unit_mode = short_input_mode(a, pl);
     p.unit_mode = pl.unit_mode;
     p.active_wgs = a->G * (pl.last_wg + 1);
@@ -586,43 +550,12 @@ int pwv_wavenet_stack_persist_f32(const pwv_persist_args* args, pwv_stream_t str
     { const char* e = getenv("PWV_PTRACE_EV_PTR"); if (e) p.trace_ev = (long long*)strtoull(e, nullptr, 0); }
 #endif
     hipStream_t s = (hipStream_t)stream;
-    const size_t n16 = pwv_persist_workspace_bytes(a) / 16;      // (progress words, abort / exit line, pair counters)
+    const size_t n16 = r.lay.total / 16;      // (progress words, abort / exit line, pair counters)
     if (!a->workspace_clean)
         hipLaunchKernelGGL(persist_zero_kernel, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, s, (int4*)a->workspace, n16);
     const dim3 grid(a->G * pl.nwg), block(512);
-    if (ragged) {
-        if (a->precision == PWV_PREC_F32) {
-#if RAGGED_F32
-            if (pl.unit_mode == 2) hipLaunchKernelGGL((stack_persist_ragged_kernel<true, 2>), grid, block, 0, s, p);
-            else hipLaunchKernelGGL((stack_persist_ragged_kernel<true, 0>), grid, block, 0, s, p);
-#endif
-        } else {
-            if (pl.unit_mode == 2) hipLaunchKernelGGL((stack_persist_ragged_kernel<false, 2>), grid, block, 0, s, p);
-            else hipLaunchKernelGGL((stack_persist_ragged_kernel<false, 0>), grid, block, 0, s, p);
-        }
-    } else if (streaming) {
-        if (a->precision == PWV_PREC_F32) {
-            if (pl.unit_mode == 2) hipLaunchKernelGGL((stack_persist_kernel<true, 2, false, true>), grid, block, 0, s, p);
-            else hipLaunchKernelGGL((stack_persist_kernel<true, 0, false, true>), grid, block, 0, s, p);
-        } else {
-            if (pl.unit_mode == 2) hipLaunchKernelGGL((stack_persist_kernel<false, 2, false, true>), grid, block, 0, s, p);
-            else hipLaunchKernelGGL((stack_persist_kernel<false, 0, false, true>), grid, block, 0, s, p);
-        }
-    } else if (varlen) {
-        if (a->precision == PWV_PREC_F32) {
-            if (pl.unit_mode == 2) hipLaunchKernelGGL((stack_persist_kernel<true, 2, true>), grid, block, 0, s, p);
-            else hipLaunchKernelGGL((stack_persist_kernel<true, 0, true>), grid, block, 0, s, p);
-        } else {
-            if (pl.unit_mode == 2) hipLaunchKernelGGL((stack_persist_kernel<false, 2, true>), grid, block, 0, s, p);
-            else hipLaunchKernelGGL((stack_persist_kernel<false, 0, true>), grid, block, 0, s, p);
-        }
-    } else if (a->precision == PWV_PREC_F32) {
-        if (pl.unit_mode == 2) hipLaunchKernelGGL((stack_persist_kernel<true, 2, false>), grid, block, 0, s, p);
-        else hipLaunchKernelGGL((stack_persist_kernel<true, 0, false>), grid, block, 0, s, p);
-    } else {
-        if (pl.unit_mode == 2) hipLaunchKernelGGL((stack_persist_kernel<false, 2, false>), grid, block, 0, s, p);
-        else hipLaunchKernelGGL((stack_persist_kernel<false, 0, false>), grid, block, 0, s, p);
-    }
+    const persist_kernel_t kernel = (ragged ? kRagged : streaming ? kStreaming : varlen ? kPacked : kUniform)[a->precision == PWV_PREC_F32][pl.unit_mode == 2];
+    hipLaunchKernelGGL(kernel, grid, block, 0, s, p);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return set_error(PWV_EHIP, "persistent stack kernel launch failed: %s", hipGetErrorString(e));
     return PWV_OK;

@@ -298,6 +298,25 @@ def test_a_shorter_callers_struct_is_not_read_past_its_end(gpu, persist_knobs):
         assert torch.equal(a, b)
 
 
+@pytest.mark.parametrize('G', [1, 2])
+def test_workspace_size_and_instantiation_equal_the_restated_plan(gpu, built_lib, G):
+    """No launch: pwv_persist_workspace_bytes and pwv_persist_short_input on this device's CU count against tests/util.persist_plan_restated
+    (which tests/test_persist_plan_host.py holds against csrc/pwv_persist_plan.h without a device)."""
+    from pwv_amd import _lib
+    from tests.util import persist_plan_restated
+    cus = built_lib.pwv_device_cus()
+    assert cus >= 8
+    for rows in (32, 1000, 16000, 28704, 160000):
+        for dmax in (1, 512):
+            for min_units in (0, 8):
+                dil = (ctypes.c_int * 2)(1, dmax)
+                pa = _lib.PersistArgs()
+                pa.G, pa.n_layers, pa.dilations, pa.N, pa.T, pa.min_units_per_workgroup = G, 2, dil, 1, rows, min_units
+                want = persist_plan_restated(cus, G, rows, dmax, min_units=min_units)
+                assert built_lib.pwv_persist_workspace_bytes(ctypes.byref(pa)) == want['total'], (rows, dmax, min_units, want)
+                assert built_lib.pwv_persist_short_input(ctypes.byref(pa)) == int(want['unit_mode'] == 2), (rows, dmax, min_units, want)
+
+
 def test_a_tail_that_reaches_too_far_runs_as_its_own_launch(gpu, persist_knobs):
     """the probe behind `_use_persist` asks about the launch that will be made, tail included.  A stack whose LAST dilation is
     its largest (2048 samples = 64 units, one unit per workgroup: 64 workgroups back, the poll reaches 60) keeps its persistent layers and

@@ -1,4 +1,4 @@
-"""-m gpu: the general loop of the persistent kernel (csrc/pwv_stack_persist_body.inc, MODE 0) on the smallest shapes that reach every
+"""-m gpu: the general loop of the persistent kernel (csrc/pwv_persist_tasks.inc, MODE 0) on the smallest shapes that reach every
 path of load_x() -- the loads of the next unit's rows, which tests/test_persist_prefetch_isa.py looks at in the assembly: the look-back
 inside the unit (d = 1, 2), on unit boundaries (32, 64), off them (48) and longer than a workgroup's range (512: the first 16 units have
 rows left of the utterance start, zeroed per lane), units that span two utterances (has_prev is not wave-uniform), the unfolded layer 0

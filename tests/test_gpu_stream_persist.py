@@ -9,6 +9,7 @@ import torch
 
 from oracle import iaf_oracle as O
 from tests.test_gpu_stream import _Feeder, _inputs, _model, _one_shot, _small, _small_wide
+from tests.util import persist_plan_restated
 
 pytestmark = pytest.mark.gpu
 
@@ -27,13 +28,9 @@ def knobs():
 
 
 def _short_expected(rows, dmax, gpu, G=2, min_units=4):
-    """persist_plan's arithmetic (csrc/pwv_stack_persist.hip): units of 32 rows, one workgroup per CU and net, at least `min_units`
-    units per workgroup; the short-input instantiation iff more than one workgroup, at most 7 units each, look-back within 32 units."""
+    """Whether the library takes the short-input instantiation for these rows on this device: tests/util.persist_plan_restated."""
     cus = torch.cuda.get_device_properties(gpu).multi_processor_count
-    units = -(-rows // 32)
-    nwg = min(cus // G, max(1, -(-units // min_units)))
-    per_wg = -(-units // nwg)
-    return 1 if (nwg > 1 and per_wg <= 7 and -(-dmax // 32) <= 32) else 0
+    return 1 if persist_plan_restated(cus, G, rows, dmax, min_units=min_units)['unit_mode'] == 2 else 0
 
 
 class _Log:

@@ -337,22 +337,12 @@ def test_no_vgpr_spills_in_the_layer_kernels():
     (layer_f16x3_kernel<SKIP = true, ...>: all four variants; layer_f32_kernel<SKIP, COND>: 27-35).  The compiler's own resource
     remarks (`-Rpass-analysis=kernel-resource-usage`, gfx950 device code, no GPU needed) must show no spilled VGPR in any kernel of the
     layer / persistent sources -- except the two variants pinned below, which no default or benchmarked configuration reaches."""
-    import re
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    csrc = os.path.join(root, 'parallel-wavenet-vocoder_amd', 'csrc')
+    from tests.util import kernel_resources
     allowed = {      # demangled-name fragment -> most spilled VGPRs tolerated
         'layer_f16x3_kernel<true, true, false, false, false, false>': 3,      # skip sums AND a per-sample condition (transposed conv), residual output
         'layer_f16x3_kernel<false, true, false, true, false, false>': 14,     # per-sample condition, layer 0 NOT folded (PWV_FOLD_FIRST=0 only)
     }
     for src in ('pwv_layer_f16.hip', 'pwv_layer.hip', 'pwv_layer_h16.hip', 'pwv_stack_persist.hip'):
-        out = subprocess.run(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950:xnack-', '-O3', '-std=c++17', '-c', '--cuda-device-only',
-                              '-Rpass-analysis=kernel-resource-usage', '-I' + os.path.join(root, 'include'), '-I' + csrc, '-o', os.devnull,
-                              os.path.join(csrc, src)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True).stdout
-        names = re.findall(r'Function Name: (\S+)', out)
-        spills = [int(x) for x in re.findall(r'VGPRs Spill: (\d+)', out)]
-        assert names and len(names) == len(spills), out[-2000:]
-        demangled = subprocess.run(['c++filt'] + names, stdout=subprocess.PIPE, text=True).stdout.split('\n')
-        for name, n in zip(demangled, spills):
+        for name, n in ((k, r['vgpr_spills']) for k, r in kernel_resources(src).items()):
             limit = max([v for k, v in allowed.items() if k in name] or [0])
             assert n <= limit, '%s: %d VGPRs spilled (%s)' % (name, n, src)

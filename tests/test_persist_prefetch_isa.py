@@ -1,4 +1,4 @@
-"""CPU: the persistent kernel's general loop (csrc/pwv_stack_persist_body.inc, MODE 0) requests the next unit's rows between GEMM1 and
+"""CPU: the persistent kernel's general loop (csrc/pwv_persist_tasks.inc, MODE 0) requests the next unit's rows between GEMM1 and
 GEMM2 and must leave them IN FLIGHT under GEMM2.  What broke that once was a register-allocator join copy: the look-back row's first
 chunk was loaded into one register and lived in another, so the wave-uniform fast path of load_x() ended in
 
@@ -10,12 +10,10 @@ compiler's own assembly (gfx950 device code, product flags, no GPU needed) must 
 instantiations; the predicate is checked against an excerpt of the assembly it was written for (tests/golden/)."""
 import os
 import re
-import subprocess
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'parallel-wavenet-vocoder_amd', 'csrc')
 EXCERPT = os.path.join(ROOT, 'tests', 'golden', 'persist_prefetch_parent_isa.txt')
 WINDOW = 24      # instructions executed before the wait in which the copied register was loaded
 
@@ -103,11 +101,8 @@ def join_copies(body, window=WINDOW):
 
 @pytest.fixture(scope='module')
 def assembly():
-    res = subprocess.run(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950:xnack-', '-O3', '-std=c++17', '--cuda-device-only', '-S',
-                          '-I' + os.path.join(ROOT, 'include'), '-I' + CSRC, '-o', '-', os.path.join(CSRC, 'pwv_stack_persist.hip')],
-                         stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
-    assert res.returncode == 0, res.stderr[-2000:]
-    return kernels(res.stdout)
+    from tests.util import kernel_assembly
+    return kernels(kernel_assembly('pwv_stack_persist.hip'))
 
 
 def test_predicate_finds_the_join_copy_in_the_excerpt_it_was_written_for():

@@ -173,21 +173,13 @@ def test_ticks_chain_like_pushes():
 def test_the_two_tick_kernels_use_no_scratch():
     """The compiler's resource remarks for pwv_stream_tick.hip (gfx950 device code, no GPU needed): both kernels with 0 bytes of scratch
     and nothing spilled."""
-    out = subprocess.run(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950:xnack-', '-O3', '-std=c++17', '-c', '--cuda-device-only',
-                          '-Rpass-analysis=kernel-resource-usage', '-I' + os.path.join(ROOT, 'include'), '-I' + CSRC, '-o', os.devnull,
-                          os.path.join(CSRC, 'pwv_stream_tick.hip')], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True).stdout
-    names = re.findall(r'Function Name: (\S+)', out)
-    scratch = [int(x) for x in re.findall(r'ScratchSize \[bytes/lane\]: (\d+)', out)]
-    vspill = [int(x) for x in re.findall(r'VGPRs Spill: (\d+)', out)]
-    sspill = [int(x) for x in re.findall(r'SGPRs Spill: (\d+)', out)]
-    vgprs = [int(x) for x in re.findall(r' VGPRs: (\d+)', out)]
-    assert names and len(names) == len(scratch) == len(vspill) == len(sspill) == len(vgprs), out[-2000:]
+    from tests.util import kernel_resources
     seen = {}
-    for name, sc, vs, ss, vg in zip(names, scratch, vspill, sspill, vgprs):
+    for name, r in kernel_resources('pwv_stream_tick.hip').items():
         for kernel in ('stream_tick_begin_kernel', 'stream_tick_commit_kernel'):
             if kernel in name:
-                seen[kernel] = (sc, vs, ss, vg)
+                seen[kernel] = (r['scratch'], r['vgpr_spills'], r['sgpr_spills'], r['vgprs'])
     print('tick kernels (scratch, spilled VGPRs, spilled SGPRs, VGPRs):', seen)
-    assert sorted(seen) == ['stream_tick_begin_kernel', 'stream_tick_commit_kernel'], names
+    assert sorted(seen) == ['stream_tick_begin_kernel', 'stream_tick_commit_kernel'], seen
     for kernel, (sc, vs, ss, vg) in seen.items():
         assert sc == 0 and vs == 0 and ss == 0, (kernel, sc, vs, ss)

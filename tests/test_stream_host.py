@@ -131,19 +131,13 @@ def test_history_layout_is_disjoint_and_bounded():
 def test_streaming_kernels_use_no_scratch():
     """The compiler's resource remarks (gfx950 device code, as tests/test_host_logic.py::test_no_vgpr_spills_in_the_layer_kernels reads
     them) for the streaming instantiations: no scratch, no spilled register -- three forms in each arithmetic, and the carry-over."""
-    csrc = os.path.join(ROOT, 'parallel-wavenet-vocoder_amd', 'csrc')
+    from tests.util import kernel_resources
     seen = []
     for src in ('pwv_layer_f16.hip', 'pwv_layer.hip'):
-        out = subprocess.run(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950:xnack-', '-O3', '-std=c++17', '-c', '--cuda-device-only',
-                              '-Rpass-analysis=kernel-resource-usage', '-I' + os.path.join(ROOT, 'include'), '-I' + csrc, '-o', os.devnull,
-                              os.path.join(csrc, src)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True).stdout
-        for block in out.split('Function Name: ')[1:]:
-            name = block.split()[0]
+        for name, r in kernel_resources(src).items():
             if 'stream' not in name:
                 continue
-            vals = {k: int(re.search(r'%s: (\d+)' % re.escape(k), block).group(1))
-                    for k in ('ScratchSize [bytes/lane]', 'VGPRs Spill', 'SGPRs Spill', 'VGPRs')}
             seen.append(name)
-            assert vals['ScratchSize [bytes/lane]'] == 0 and vals['VGPRs Spill'] == 0 and vals['SGPRs Spill'] == 0, (name, vals)
-            assert vals['VGPRs'] <= 256, (name, vals)
+            assert r['scratch'] == 0 and r['vgpr_spills'] == 0 and r['sgpr_spills'] == 0, (name, r)
+            assert r['vgprs'] <= 256, (name, r)
     assert len(seen) == 7 and sum('layer_f16x3_stream_kernel' in n for n in seen) == 3 and sum('layer_f32_stream_kernel' in n for n in seen) == 3, seen

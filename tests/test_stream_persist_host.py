@@ -7,7 +7,6 @@ import re
 import subprocess
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'parallel-wavenet-vocoder_amd', 'csrc')
 
 
 def test_header_and_binding_agree_on_the_new_fields(tmp_path):
@@ -107,17 +106,11 @@ def test_the_four_stream_instantiations_spill_nothing():
     """The compiler's resource remarks for pwv_stack_persist.hip (gfx950 device code, no GPU needed) list
     stack_persist_kernel<false|true, 0|2, false, true> -- both arithmetics: the fp32 escape of the issue was not needed -- each with
     0 bytes of scratch and 0 spilled VGPRs."""
-    out = subprocess.run(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950:xnack-', '-O3', '-std=c++17', '-c', '--cuda-device-only',
-                          '-Rpass-analysis=kernel-resource-usage', '-I' + os.path.join(ROOT, 'include'), '-I' + CSRC, '-o', os.devnull,
-                          os.path.join(CSRC, 'pwv_stack_persist.hip')], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True).stdout
-    names = re.findall(r'Function Name: (\S+)', out)
-    scratch = [int(x) for x in re.findall(r'ScratchSize \[bytes/lane\]: (\d+)', out)]
-    spills = [int(x) for x in re.findall(r'VGPRs Spill: (\d+)', out)]
-    vgprs = [int(x) for x in re.findall(r' VGPRs: (\d+)', out)]
-    assert names and len(names) == len(scratch) == len(spills) == len(vgprs), out[-2000:]
-    demangled = subprocess.run(['c++filt'] + names, stdout=subprocess.PIPE, text=True).stdout.split('\n')
+    from tests.util import kernel_resources
+    res = kernel_resources('pwv_stack_persist.hip')
+    demangled = list(res)
     seen = {}
-    for name, sc, sp, vg in zip(demangled, scratch, spills, vgprs):
+    for name, sc, sp, vg in ((k, r['scratch'], r['vgpr_spills'], r['vgprs']) for k, r in res.items()):
         m = re.search(r'stack_persist_kernel<(true|false), (\d), false, true>', name)
         if m:
             seen[(m.group(1), int(m.group(2)))] = (sc, sp, vg)

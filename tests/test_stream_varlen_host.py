@@ -3,13 +3,11 @@ the bookkeeping function, the field the C ABI gained and its ctypes mirror, the 
 resource remarks for the new kernels.  No GPU needed."""
 import ctypes
 import os
-import re
 import subprocess
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'parallel-wavenet-vocoder_amd', 'csrc')
 
 
 def test_ragged_plan_mixed_fresh_and_running():
@@ -116,16 +114,8 @@ def test_refusals_name_hist_cu_rows(built_lib):
 
 
 def _remarks(source):
-    out = subprocess.run(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950:xnack-', '-O3', '-std=c++17', '-c', '--cuda-device-only',
-                          '-Rpass-analysis=kernel-resource-usage', '-I' + os.path.join(ROOT, 'include'), '-I' + CSRC, '-o', os.devnull,
-                          os.path.join(CSRC, source)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True).stdout
-    names = re.findall(r'Function Name: (\S+)', out)
-    scratch = [int(x) for x in re.findall(r'ScratchSize \[bytes/lane\]: (\d+)', out)]
-    spills = [int(x) for x in re.findall(r'VGPRs Spill: (\d+)', out)]
-    vgprs = [int(x) for x in re.findall(r' VGPRs: (\d+)', out)]
-    assert names and len(names) == len(scratch) == len(spills) == len(vgprs), out[-2000:]
-    demangled = subprocess.run(['c++filt'] + names, stdout=subprocess.PIPE, text=True).stdout.split('\n')
-    return list(zip(demangled, scratch, spills, vgprs))
+    from tests.util import kernel_resources
+    return [(name, r['scratch'], r['vgpr_spills'], r['vgprs']) for name, r in kernel_resources(source).items()]
 
 
 def test_the_ragged_kernels_spill_nothing():

@@ -4,7 +4,6 @@ scratch).  No GPU needed."""
 import ctypes
 import os
 import re
-import subprocess
 
 import pytest
 import torch
@@ -123,12 +122,9 @@ def test_packed_sampler_is_declared_and_exported(built_lib):
 
 def test_packed_sampler_uses_no_scratch():
     """The compiler's resource remarks (gfx950 device code, no GPU needed): the packed sampler uses no scratch and spills nothing."""
-    csrc = os.path.join(ROOT, 'parallel-wavenet-vocoder_amd', 'csrc')
-    out = subprocess.run(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950:xnack-', '-O3', '-std=c++17', '-c', '--cuda-device-only',
-                          '-Rpass-analysis=kernel-resource-usage', '-I' + os.path.join(ROOT, 'include'), '-I' + csrc, '-o', os.devnull,
-                          os.path.join(csrc, 'pwv_misc.hip')], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True).stdout
-    blocks = re.split(r'remark: Function Name: ', out)
-    mine = [b for b in blocks if b.startswith('_ZN3pwv28logistic_noise_packed_kernel')]
-    assert len(mine) == 1, out[-2000:]
-    assert re.search(r'ScratchSize \[bytes/lane\]: 0\b', mine[0]) and re.search(r'VGPRs Spill: 0\b', mine[0]), mine[0]
-    assert re.search(r'Dynamic Stack: False', mine[0]), mine[0]
+    from tests.util import kernel_resources
+    res = kernel_resources('pwv_misc.hip')
+    mine = [r for name, r in res.items() if name.startswith('pwv::logistic_noise_packed_kernel(')]
+    assert len(mine) == 1, sorted(res)
+    assert mine[0]['scratch'] == 0 and mine[0]['vgpr_spills'] == 0, mine[0]
+    assert mine[0]['dynamic_stack'] is False, mine[0]

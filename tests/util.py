@@ -1,4 +1,6 @@
 """Shared helpers for the parity tests (oracle = checker, HIP path = thing under test)."""
+import functools
+
 import numpy as np
 
 from oracle import iaf_oracle as O
@@ -109,3 +111,81 @@ def build_c_abi_smoke(out_path):
            '-I' + os.path.join(root, 'include'), '-I/opt/rocm/include', '-L' + lib_dir, '-lpwv_hip', '-L/opt/rocm/lib',
            '-lamdhip64', '-lm', '-Wl,-rpath,' + lib_dir, '-Wl,-rpath,/opt/rocm/lib', '-o', out_path]
     return subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+
+
+def _device_compile(source_name, mode):
+    """Run the shipped compile command (_lib.device_compile_command) of csrc/<source_name> for the device side alone; returns the
+    CompletedProcess (text)."""
+    import os
+    import subprocess
+    from pwv_amd import _lib
+    src = os.path.join(os.path.dirname(_lib.__file__), 'csrc', source_name)
+    res = subprocess.run(_lib.device_compile_command(src) + ['--cuda-device-only'] + mode + [src], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+    assert res.returncode == 0, res.stderr[-2000:]
+    return res
+
+
+_REMARK_FIELDS = (('vgprs', 'VGPRs'), ('agprs', 'AGPRs'), ('sgprs', 'TotalSGPRs'), ('scratch', 'ScratchSize [bytes/lane]'),
+                  ('vgpr_spills', 'VGPRs Spill'), ('sgpr_spills', 'SGPRs Spill'), ('lds', 'LDS Size [bytes/block]'))
+
+
+@functools.lru_cache(maxsize=None)
+def kernel_resources(source_name):
+    """The compiler's resource remarks (`-Rpass-analysis=kernel-resource-usage`, gfx950 device code, no GPU needed) for every kernel of
+    csrc/<source_name> as the library is built: {demangled kernel name: {vgprs, agprs, sgprs, scratch, vgpr_spills, sgpr_spills, lds,
+    dynamic_stack}}.  One compile per process and source."""
+    import re
+    import subprocess
+    out = _device_compile(source_name, ['-c', '-Rpass-analysis=kernel-resource-usage', '-o', '/dev/null']).stderr
+    blocks = out.split('Function Name: ')[1:]
+    assert blocks, out[-2000:]
+    names = [b.split()[0] for b in blocks]
+    demangled = subprocess.run(['c++filt'] + names, stdout=subprocess.PIPE, text=True).stdout.split('\n')
+    res = {}
+    for name, block in zip(demangled, blocks):
+        vals = {key: int(re.search(r' %s: (\d+)' % re.escape(label), block).group(1)) for key, label in _REMARK_FIELDS}
+        vals['dynamic_stack'] = re.search(r'Dynamic Stack: (\w+)', block).group(1) != 'False'
+        assert name not in res, name
+        res[name] = vals
+    return res
+
+
+@functools.lru_cache(maxsize=None)
+def kernel_assembly(source_name):
+    """The assembly listing (`-S`) of the device code of csrc/<source_name> as the library is built.  One compile per process and source."""
+    return _device_compile(source_name, ['-S', '-o', '-']).stdout
+
+
+def persist_plan_restated(cus, G, rows, dmax, min_units=0, max_workgroups=0, tail_q=0, tail_dil=0):
+    """How a persistent launch deals its rows to workgroups and lays out its workspace, restated from the design (DESIGN.md section 4,
+    K1p) and not from csrc/pwv_persist_plan.h: units of 32 rows; one workgroup per CU and net, fewer if that leaves a workgroup
+    under `min_units` units (default 4) or `max_workgroups` caps the grid; the look-back reach in units and in workgroups; the
+    short-input instantiation (unit_mode 2) iff the reach stays within 32 units, there is more than one workgroup and none has more than
+    7 units; the workspace = a 128-byte progress word per workgroup and net + one 256-byte line, an arrival counter per range and, in
+    unit mode, a 128-byte word per unit and net, each part rounded up to 256 bytes.  Returns a dict -- or None where the library
+    refuses the launch: more than 832 units per workgroup, or a reach of more than 60 workgroups."""
+    def cdiv(a, b):
+        return -(-a // b)
+
+    def align256(v):
+        return cdiv(v, 256) * 256
+    units = cdiv(rows, 32)
+    wgs = cus // G
+    if max_workgroups > 0:
+        wgs = min(wgs, max_workgroups // G)
+    if min_units <= 0:
+        min_units = 4
+    nwg = min(wgs, max(1, cdiv(units, min_units)))
+    per_wg = cdiv(units, nwg)
+    reach = cdiv(dmax, 32)
+    plan = dict(units=units, nwg=nwg, per_wg=per_wg, last_wg=(units - 1) // per_wg, reach_wgs=cdiv(reach, per_wg),
+                xcd_map=int(nwg % 8 == 0 and (G * nwg) % 8 == 0),
+                tail_reach_wgs=cdiv(cdiv(tail_dil, 32), per_wg) if tail_q > 0 else 0,
+                unit_mode=2 if (reach <= 32 and nwg > 1 and per_wg <= 7) else 0)
+    if per_wg > 832 or plan['reach_wgs'] > 60 or plan['tail_reach_wgs'] > 60:
+        return None
+    plan['prog_bytes'] = G * nwg * 128
+    plan['pair_off'] = align256(plan['prog_bytes'] + 256)
+    plan['uprog_off'] = plan['pair_off'] + align256(4 * nwg)
+    plan['total'] = plan['uprog_off'] + (align256(G * units * 128) if plan['unit_mode'] else 0)
+    return plan
