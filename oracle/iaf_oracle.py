@@ -123,6 +123,10 @@ def _sigmoid(x):
     return 1.0 / (1.0 + np.exp(-x))
 
 
+# tests: a callable that is handed every layer's gate pre-activations (F, G) = (conv_filter, conv_gate) as the oracle computes them
+GATE_PROBE = None
+
+
 def wavenet_forward(weights: Weights, scope: str, input_batch: np.ndarray,
                     condition_batch: Optional[np.ndarray], dilations: Sequence[int],
                     use_biases: bool, use_skip_connection: bool,
@@ -161,7 +165,10 @@ def wavenet_forward(weights: Weights, scope: str, input_batch: np.ndarray,
         if normalize_method:                                              # :230-234
             conv_filter = normalize(conv_filter, normalize_method, W, scope + '/' + p + 'normalize_filter')
             conv_gate = normalize(conv_gate, normalize_method, W, scope + '/' + p + 'normalize_gate')
-        out = rnd(np.tanh(conv_filter) * _sigmoid(conv_gate))             # :236
+        if GATE_PROBE is not None:
+            GATE_PROBE(conv_filter, conv_gate)
+        with np.errstate(over='ignore'):      # exp(-G) = inf for G < -709: sigmoid = 0, as it should be
+            out = rnd(np.tanh(conv_filter) * _sigmoid(conv_gate))         # :236
         transformed = out @ g(p + 'dense')[0]                             # :239-240
         skip_output = out @ g(p + 'skip')[0]                              # :243-244
         if use_biases:                                                    # :246-250

@@ -12,7 +12,7 @@ import pytest
 
 from oracle import iaf_oracle as O
 from oracle.make_golden import VOCODER_CASES
-from tests.util import run_vocoder_hip, small_cfg
+from tests.util import run_vocoder_hip, small_cfg, untile_f16
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
@@ -85,16 +85,6 @@ def test_f16_layout_round_trip(gpu):
     assert torch.equal(out, want)
 
 
-def _untile_f16(buf, rows):
-    """fp16 tile32 (64 channels) -> [rows, 64] float64 in channel order (include/pwv_hip.h)."""
-    blocks = buf.numel() // 2048
-    perm = np.array([16 * s + 8 * (q >> 2) + 4 * h + (q & 3) for s in range(4) for h in range(2) for q in range(8)])
-    v = buf.cpu().numpy().astype(np.float64).reshape(blocks, 8, 32, 8).transpose(0, 2, 1, 3).reshape(blocks * 32, 64)[:rows]
-    out = np.zeros_like(v)
-    out[:, perm] = v
-    return out
-
-
 @pytest.mark.parametrize('dense_kind', ['identity', 'random'])
 def test_f16_residual_layer_matches_its_own_gated_output(gpu, dense_kind):
     """One residual layer through the C ABI: out = fp16(x + fp16(o) @ fp16(dense) + bias) must follow from the
@@ -141,7 +131,7 @@ def test_f16_residual_layer_matches_its_own_gated_output(gpu, dense_kind):
         a.x_out[0], a.out_mode = out.data_ptr(), mode
         check(lib.pwv_wavenet_layer_f32(ctypes.byref(a), s))
     torch.cuda.synchronize()
-    h0, h1, og = (_untile_f16(b, rows) for b in (b0, b1, b2))
+    h0, h1, og = (untile_f16(b, rows) for b in (b0, b1, b2))
     want = (h0 + og @ dense + bias).astype(np.float16).astype(np.float64)
     diff = np.abs(h1 - want)
     ulp = np.spacing(np.maximum(np.abs(want), 2.0 ** -14).astype(np.float16)).astype(np.float64)

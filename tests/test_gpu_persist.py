@@ -407,3 +407,17 @@ def test_random_shapes_through_the_persistent_launch_under_load(gpu):
                        stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:]
     assert ' 0 failed' in r.stdout
+
+
+def test_random_shapes_through_the_persistent_launch_with_saturated_gates(gpu):
+    """The same stress test with --saturate: the stacks' filter / gate biases redrawn as tests/util.saturating_weights draws them, so that a
+    third of the gates run beyond |F| = 20 and a tenth below G = -40 (gate_act's clamp) in every instantiation the 16 cases reach: both
+    arithmetics, the short-input and the general kernel, the tail, stacks cut into runs -- bit for bit against the per-layer launches."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, 'tools', 'persist_fuzz.py'), '--cases', '16', '--seed', '5', '--load', '--saturate'],
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:]
+    assert '16 cases, 0 failed' in r.stdout

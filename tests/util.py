@@ -100,6 +100,188 @@ def f16_storage_model(weights, cfg):
     return out, r16
 
 
+def untile_f16(buf, rows):
+    """fp16 tile32 (64 channels) -> [rows, 64] float64 in channel order (include/pwv_hip.h)."""
+    blocks = buf.numel() // 2048
+    perm = np.array([16 * s + 8 * (q >> 2) + 4 * h + (q & 3) for s in range(4) for h in range(2) for q in range(8)])
+    v = buf.cpu().numpy().astype(np.float64).reshape(blocks, 8, 32, 8).transpose(0, 2, 1, 3).reshape(blocks * 32, 64)[:rows]
+    out = np.zeros_like(v)
+    out[:, perm] = v
+    return out
+
+
+# ---- the fused gate, tanh(F) * sigmoid(G), over the whole (F, G) plane (tests/test_gate_formula_host.py, tests/test_gpu_gate_plane.py) ----
+K_F, K_G = np.float32(-2.8853900817779268), np.float32(-1.4426950408889634)      # kFScale, kGScale of csrc/pwv_layer_common.h
+GATE_MUTANTS = ('no_clamp', 'clamp_g_only', 'clamp_at_128', 'scales_swapped', 'one_plus_e1')
+
+
+def _push_ulp(v, ulps):
+    """`v` (fp32, finite and positive where it is moved) pushed by `ulps` units in the last place: the stated accuracy of v_exp_f32 / v_rcp_f32."""
+    out = v.copy()
+    move = np.isfinite(v) & (v > 0)
+    for _ in range(abs(int(ulps))):
+        out[move] = np.nextafter(out[move], np.float32(np.inf if ulps > 0 else 0))
+    return out
+
+
+def gate_emulated(F, G, exp_ulp=0, rcp_ulp=0, mutant=None):
+    """gate_act of csrc/pwv_layer_common.h restated in numpy, operation by operation in fp32: Fs = fp32(F * kF), Gs = fp32(G * kG) (what the
+    packers fold into the weights and P), the one-sided med3 clamp against (-3.0e38, 57.7), two correctly rounded exp2, t = 1 + e2, ONE fused
+    e1 * t + t, a correctly rounded reciprocal and the final product.  `exp_ulp` / `rcp_ulp` push both exp2 / the reciprocal by that many
+    units in the last place.  `mutant` (one of GATE_MUTANTS) restates a wrong gate instead -- what assert_gate_plane must reject."""
+    assert mutant is None or mutant in GATE_MUTANTS, mutant
+    f32 = np.float32
+    kf, kg = (K_G, K_F) if mutant == 'scales_swapped' else (K_F, K_G)
+    hi = f32(128.0) if mutant == 'clamp_at_128' else f32(57.7)
+    with np.errstate(all='ignore'):
+        fs = np.asarray(F, dtype=f32) * kf
+        gs = np.asarray(G, dtype=f32) * kg
+        if mutant not in ('no_clamp', 'clamp_g_only'):
+            fs = np.clip(fs, f32(-3.0e38), hi)
+        if mutant != 'no_clamp':
+            gs = np.clip(gs, f32(-3.0e38), hi)
+        e1 = _push_ulp(np.exp2(fs.astype(np.float64)).astype(f32), exp_ulp)
+        e2 = _push_ulp(np.exp2(gs.astype(np.float64)).astype(f32), exp_ulp)
+        t = f32(1) + e2
+        den = (e1.astype(np.float64) * t.astype(np.float64) + t.astype(np.float64)).astype(f32)      # (the product is exact in fp64: one rounding)
+        rcp = _push_ulp((1.0 / den.astype(np.float64)).astype(f32), rcp_ulp)
+        num = (f32(1) + e1) if mutant == 'one_plus_e1' else (f32(1) - e1)
+        return num * rcp
+
+
+_PLANE_FIXED = (2.0 ** -20, 1e-3, 0.1, 0.5, 1, 2, 3, 5, 8, 12, 16, 19, 19.99, 20, 20.01, 22.17, 22.2, 30, 39.99, 40, 40.01, 44.3, 44.4,
+                60, 88, 100, 1e4, 1e30)
+
+
+@functools.lru_cache(maxsize=None)
+def gate_plane():
+    """(F, G, perm): the fixed grid of 128 F values x 128 G values as two flat fp32 arrays of 16384 pairs, in the order of a fixed seeded
+    permutation `perm` of the row-major grid (so that every lane and register position of a kernel sees every regime).  Each axis: 0 and
+    both signs of _PLANE_FIXED -- the small arguments, both sides of Fs = 57.7 (|F| = 20), of Fs = 64 (22.18: e1 * t overflows without the
+    clamp), of Gs = 57.7 (|G| = 40), of Fs = 128 (44.36: e1 itself overflows), and far beyond --, the rest seeded uniform in (-25, 25)."""
+    rng = np.random.RandomState(20)
+    fixed = [0.0] + [s * v for v in _PLANE_FIXED for s in (1.0, -1.0)]
+    axes = [np.array(fixed + list(rng.uniform(-25, 25, 128 - len(fixed))), dtype=np.float32) for _ in range(2)]
+    f2, g2 = np.meshgrid(axes[0], axes[1], indexing='ij')
+    perm = rng.permutation(128 * 128)
+    F, G = f2.ravel()[perm], g2.ravel()[perm]
+    for a in (F, G, perm):
+        a.setflags(write=False)
+    return F, G, perm
+
+
+def gate_exact(F, G):
+    """tanh(F) / (1 + exp(-G)) in fp64."""
+    with np.errstate(over='ignore'):
+        return np.tanh(np.asarray(F, dtype=np.float64)) / (1.0 + np.exp(-np.asarray(G, dtype=np.float64)))
+
+
+def gate_errors(got, F, G):
+    """(max absolute error, max relative error where 0.5 <= |F| <= 19.5 and G >= -39.5) of `got` against gate_exact; inf if not finite."""
+    got, F, G = (np.asarray(a, dtype=np.float64).ravel() for a in (got, F, G))
+    if not np.isfinite(got).all():
+        return np.inf, np.inf
+    want = gate_exact(F, G)
+    err = np.abs(got - want)
+    rel = (np.abs(F) >= 0.5) & (np.abs(F) <= 19.5) & (G >= -39.5)
+    return float(err.max()), float((err[rel] / np.abs(want[rel])).max()) if rel.any() else 0.0
+
+
+@functools.lru_cache(maxsize=None)
+def gate_bounds():
+    """(A, R, worst absolute, worst relative): the bars of assert_gate_plane.  The worst errors of gate_emulated over gate_plane() for the
+    nine (exp_ulp, rcp_ulp) in {-1, 0, 1}^2 -- every answer a gate built from v_exp_f32 / v_rcp_f32 at their stated accuracy can give --
+    times 4: the factor covers the hardware's argument reduction and the compiler's freedom outside the contract(off) block.  They come
+    from the emulation, never from a kernel."""
+    F, G, _ = gate_plane()
+    errs = [gate_errors(gate_emulated(F, G, e, r), F, G) for e in (-1, 0, 1) for r in (-1, 0, 1)]
+    worst_abs, worst_rel = max(a for a, _ in errs), max(r for _, r in errs)
+    return 4 * worst_abs, 4 * worst_rel, worst_abs, worst_rel
+
+
+def assert_gate_plane(got, F, G, extra_abs=0):
+    """`got` = tanh(F) * sigmoid(G) as a kernel (or gate_emulated) computed it, against fp64, with A, R = gate_bounds(): everything finite;
+    absolute error <= A everywhere; relative error <= R where 0.5 <= |F| <= 19.5 and G >= -39.5; where G <= -40.01 (the gate's clamp holds
+    sigmoid at 2^-57.7): |got| <= 4.3e-18 and got is zero or has the sign of F; where |F| >= 20.01 and G >= -39.5 (tanh is +-1 in fp32): got =
+    +-sigmoid(G) to R.  `extra_abs` (a scalar or one value per point) is added to every bar: the rounding of an output stored as fp16.
+    Returns (max absolute error, max relative error) for the record."""
+    A, R = gate_bounds()[:2]
+    got, F, G = (np.asarray(a, dtype=np.float64).ravel() for a in (got, F, G))
+    extra = np.broadcast_to(np.asarray(extra_abs, dtype=np.float64).ravel(), got.shape)
+    assert got.shape == F.shape == G.shape
+    bad = ~np.isfinite(got)
+    assert not bad.any(), ('not finite', int(bad.sum()), F[bad][:8], G[bad][:8], got[bad][:8])
+    want = gate_exact(F, G)
+    err = np.abs(got - want)
+    bad = err > A + extra
+    assert not bad.any(), ('absolute error', int(bad.sum()), float(err.max()), A, F[bad][:8], G[bad][:8], got[bad][:8])
+    rel = (np.abs(F) >= 0.5) & (np.abs(F) <= 19.5) & (G >= -39.5)
+    bad = rel & (err > R * np.abs(want) + extra)
+    assert not bad.any(), ('relative error', int(bad.sum()), float((err[bad] / np.abs(want[bad])).max()), R, F[bad][:8], G[bad][:8], got[bad][:8])
+    low = G <= -40.01
+    bad = low & ((np.abs(got) > 4.3e-18 + extra) | ((got != 0) & (F != 0) & (np.sign(got) != np.sign(F))))      # (F = 0 has no sign: the bound alone)
+    assert not bad.any(), ('below the sigmoid clamp', int(bad.sum()), F[bad][:8], G[bad][:8], got[bad][:8])
+    sat = (np.abs(F) >= 20.01) & (G >= -39.5)
+    sig = np.sign(F) * gate_exact(np.full_like(G, 1e3), G)
+    bad = sat & (np.abs(got - sig) > R * np.abs(sig) + extra)
+    assert not bad.any(), ('saturated tanh', int(bad.sum()), F[bad][:8], G[bad][:8], got[bad][:8])
+    return float(err.max()), float((err[rel] / np.abs(want[rel])).max())
+
+
+def saturating_weights(cfg, seed):
+    """O.init_weights(cfg, seed) with every filter_bias and gate_bias of the dilated stacks redrawn per channel: with probability 1/2 from
+    U(-70, 70), else from N(0, 1), independently for filter and gate.  Nothing else is scaled: biases enter the projection P exactly, so
+    the model stays well conditioned while a third of its gates run beyond |F| = 20 and a tenth below G = -40 (where gate_act's clamp
+    works), next to gates in the ordinary range."""
+    w = O.init_weights(cfg, seed=seed)
+    rng = np.random.RandomState(7919 + seed)
+    for name in w:
+        if '/dilated_stack/' in name and name.rsplit('/', 1)[1] in ('filter_bias', 'gate_bias'):
+            n = w[name].shape[0]
+            wide = rng.uniform(size=n) < 0.5
+            w[name] = np.where(wide, rng.uniform(-70, 70, n), rng.randn(n)).astype(np.float32)
+    return w
+
+
+def gate_statistics(weights, mel, z, cfg):
+    """The fp64 oracle's forward with every gate pre-activation recorded: (y, share with |F| > 20, share with G < -40, share with |F| < 3 and
+    |G| < 3, largest |F|)."""
+    seen = []
+    O.GATE_PROBE = lambda f, g: seen.append((np.abs(f).ravel(), g.ravel()))
+    try:
+        y = O.iaf_vocoder_forward(weights, mel, z, cfg)
+    finally:
+        O.GATE_PROBE = None
+    af, g = np.concatenate([a for a, _ in seen]), np.concatenate([b for _, b in seen])
+    return y, float((af > 20).mean()), float((g < -40).mean()), float(((af < 3) & (np.abs(g) < 3)).mean()), float(af.max())
+
+
+DIL7 = [1, 2, 32, 64, 48, 512, 4]      # tests/test_gpu_persist_prefetch.py: every look-back path of the general persistent loop
+SATURATED_SEED = 6
+
+
+@functools.lru_cache(maxsize=None)
+def saturated_case(kind):
+    """The models of the saturated-gate route tests (tests/test_gpu_gate_plane.py; their shares of saturated gates are asserted in
+    tests/test_gate_formula_host.py): (cfg, weights, mel, z).  Shared between the tests, never written to."""
+    if kind == 'small':             # the two-flow model of the streaming / packed tests
+        cfg, n, length = hop_cfg(80), 2, 480
+    elif kind == 'dil7':            # one flow whose persistent launch is the general instantiation at PERSIST_MIN_UNITS = 16
+        cfg, n, length = small_cfg(dilations=[DIL7], n_iaf=1), 1, 2080
+    elif kind == 'shared':          # one two-output net per flow: the affine in place
+        cfg, n, length = hop_cfg(80, shared_nets=True), 2, 160
+    elif kind == 'transposed':      # the per-sample condition GEMM inside the layer kernels
+        cfg, n, length = hop_cfg(80, cond_upsample_method='transposed_conv'), 2, 240
+    else:
+        raise KeyError(kind)
+    w = saturating_weights(cfg, SATURATED_SEED)
+    mel, z = O.synthetic_inputs(n, length, cfg)
+    return cfg, w, mel, z
+
+
+SATURATED_KINDS = ('small', 'dil7', 'shared', 'transposed')
+
+
 def build_c_abi_smoke(out_path):
     """Compile examples/c_abi_smoke.c (a plain C99 client of the C ABI: raw hipMalloc pointers, no Python / torch)
     with gcc against the in-tree library.  Returns the command's CompletedProcess."""

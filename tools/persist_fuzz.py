@@ -1,11 +1,14 @@
 """GPU: random shapes through the persistent launch against the per-layer launches, bit for bit (the protocol's stress test).
 
-    python tools/persist_fuzz.py [--cases 200] [--seed 1] [--max-rows 40000] [--load]
+    python tools/persist_fuzz.py [--cases 200] [--seed 1] [--max-rows 40000] [--load] [--saturate]
 
 Every case: random (utterances, length, layers, nets, units per workgroup, layers per run, arithmetic) -- lengths that are no multiple of 32,
 utterance starts inside units, one to seven units per workgroup (the short-input instantiation) and a few beyond (the general one) -- the per-layer
 result once, then the persistent launch FOUR times on one workspace (the control words must be left clean), each compared with torch.equal.
 --load runs a second stream of unrelated memory traffic beside it (uneven load: hand-off bugs hide on an idle chip).
+--saturate redraws the stacks' filter_bias / gate_bias per channel from U(-70, 70) with probability 1/2, else from N(0, 1), in place of N(0, 0.1)
+(tests/util.saturating_weights): a third of the gates beyond |F| = 20 and a tenth below G = -40, where gate_act's clamp works -- an instantiation
+whose gate differed there would differ in bits.
 """
 import argparse
 import os
@@ -29,6 +32,7 @@ def main():
     ap.add_argument('--seed', type=int, default=1)
     ap.add_argument('--max-rows', type=int, default=40000)
     ap.add_argument('--load', action='store_true')
+    ap.add_argument('--saturate', action='store_true')
     a = ap.parse_args()
     rnd = random.Random(a.seed)
     dev = torch.device('cuda', 0)
@@ -60,8 +64,15 @@ def main():
         if not init:
             engine.run_nets(nets, x, cond, precision=prec)
             for name in list(store.vars):
-                if store.vars[name].dim() == 1:
-                    store.vars[name].normal_(0, 0.1)
+                v = store.vars[name]
+                if v.dim() != 1:
+                    continue
+                if a.saturate and '/dilated_stack/' in name and name.rsplit('/', 1)[1] in ('filter_bias', 'gate_bias'):
+                    wg = torch.Generator().manual_seed(rnd.randrange(1 << 30))
+                    wide = torch.rand(v.shape, generator=wg) < 0.5
+                    v.copy_(torch.where(wide, torch.rand(v.shape, generator=wg) * 140 - 70, torch.randn(v.shape, generator=wg)))
+                else:
+                    v.normal_(0, 0.1)
             store.version += 1
             nets_cache[key] = (store, nets, True)
         engine.PERSIST = False
