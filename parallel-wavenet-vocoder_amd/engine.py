@@ -16,6 +16,7 @@ Data layout in HBM (float32):
 from __future__ import annotations
 
 import ctypes
+import numbers
 import os
 import threading
 import weakref
@@ -171,7 +172,7 @@ _persist_backoff = PERSIST_RETRY_AFTER
 
 # NOTE the suspension below is PROCESS-wide (one counter for all threads) although the sticky words are per thread: a give-up means
 # the chip is shared with somebody, which concerns every thread's launches alike; the other threads' graphs are re-captured
-# on the per-layer path at their next call (graph.GraphedVocoder._launch_mode).
+# on the per-layer path at their next call (graph._Captured._stale).
 def persist_suspended() -> bool:
     return _persist_cooldown > 0
 
@@ -330,7 +331,7 @@ PERSIST_ARGS_HOOK = None      # tests: called with the filled-in pwv_persist_arg
 
 def launch_knobs() -> tuple:
     """Every module attribute that decides WHICH launches a forward enqueues (read by _choose_path, get_plan, the launch helpers and
-    the prologue): a graph captured under other values is stale (graph.GraphedVocoder._launch_mode).  A new such knob goes here."""
+    the prologue): a graph captured under other values is stale (graph._Captured._stale).  A new such knob goes here."""
     return (PERSIST, persist_suspended(), TWO_STREAMS, FOLD_FIRST, FUSE_FIRST, FUSE_HEAD, FUSE_TAIL, HOIST_P, PERSIST_MAX_LAYERS,
             PERSIST_MIN_UNITS, DEFAULT_PRECISION, FUSE_PROLOGUE, FUSE_PROLOGUE_MAX_OUTPUTS, PERSIST_AUTO_MAX_ROWS)
 
@@ -518,6 +519,23 @@ def as_int64_bits(v: int) -> int:
     """A uint64 (a seed or a counter offset, 0 .. 2**64 - 1) as the int64 with the same bits: how a torch.int64 tensor carries it."""
     v = int(v) & ((1 << 64) - 1)
     return v - (1 << 64) if v >> 63 else v
+
+
+def from_int64_bits(v: int) -> int:
+    """The inverse of as_int64_bits: the uint64 an int64 read back from a device table stands for."""
+    return int(v) & ((1 << 64) - 1)
+
+
+def check_u64(v, what: str) -> int:
+    """`v` as the sampler's uint64 -- an integer in [0, 2**64), not a bool -- or ValueError('<what> must be an integer in ...')."""
+    if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not 0 <= int(v) < (1 << 64):
+        raise ValueError('%s must be an integer in [0, 2**64), got %r' % (what, v))
+    return int(v)
+
+
+def os_seed() -> int:
+    """A noise seed from the OS: what a model, a session or a tool draws where the caller gave none."""
+    return int.from_bytes(os.urandom(7), 'little')
 
 
 def logistic_noise_packed_op(cu_rows: torch.Tensor, streams: torch.Tensor, rows: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1055,18 +1073,12 @@ def _remap_bank(bank: dict, total_frames: int, remap) -> dict:
     return {k: rows[:, v.storage_offset() - full.storage_offset():][:, :v.shape[1]] for k, v in bank.items()}
 
 
-class VarlenGeometry:
-    """The layout of a packed batch: utterance i has lengths[i] samples, rows cu_rows[i] .. cu_rows[i+1]-1 of
-    every [R, C] tensor, and t_mel_i = lengths[i] / hop + 1 condition frames, rows cu_frames[i] .. of every [F, C] tensor.  Sample t
-    of utterance i is conditioned on frame cu_frames[i] + (t + hop/2) // hop and looks back at zeros for t < d.  Holds the host
-    prefix sums (the launches are sized on the host), their device copies and, made on first use, the per-unit records of the
-    persistent launches and the index maps of the padded fallback."""
+class PackedLayout:
+    """The host side of a packed batch's layout: utterance i has lengths[i] samples, rows cu_rows_host[i] ..
+    cu_rows_host[i+1]-1 of every [R, C] tensor, and t_mel_i = lengths[i] / hop + 1 condition frames, rows cu_frames_host[i] .. of every
+    [F, C] tensor.  Plain integers: no device."""
 
-    def __init__(self, lengths: Sequence[int], hop: int, device, tables=None):
-        """`tables` (optional): caller-owned device buffers (cu_rows int32 [N+1], cu_frames int32 [N+1], unit map int32
-        [ceil(R/32) * VARLEN_REC_INTS]) that the caller keeps filled; nothing is uploaded, and unit_map() hands out the buffer as it is
-        (the caller rebuilds it, build_unit_map(), ahead of every forward: graph.GraphedPackedVocoder rewrites the tables between
-        replays of one capture)."""
+    def __init__(self, lengths: Sequence[int], hop: int):
         self.lengths = [int(v) for v in lengths]
         self.hop = int(hop)
         if not self.lengths:
@@ -1081,6 +1093,19 @@ class VarlenGeometry:
             self.cu_frames_host.append(self.cu_frames_host[-1] + f)
         self.n, self.rows, self.total_frames = len(self.lengths), self.cu_rows_host[-1], self.cu_frames_host[-1]
         self.max_len, self.max_frames = max(self.lengths), max(self.frames)
+
+
+class VarlenGeometry(PackedLayout):
+    """A PackedLayout on a device.  Sample t of utterance i is conditioned on frame cu_frames[i] + (t + hop/2) // hop and looks back
+    at zeros for t < d.  Holds the host prefix sums (the launches are sized on the host), their device copies and, made on first
+    use, the per-unit records of the persistent launches and the index maps of the padded fallback."""
+
+    def __init__(self, lengths: Sequence[int], hop: int, device, tables=None):
+        """`tables` (optional): caller-owned device buffers (cu_rows int32 [N+1], cu_frames int32 [N+1], unit map int32
+        [ceil(R/32) * VARLEN_REC_INTS]) that the caller keeps filled; nothing is uploaded, and unit_map() hands out the buffer as it is
+        (the caller rebuilds it, build_unit_map(), ahead of every forward: graph.GraphedPackedVocoder rewrites the tables between
+        replays of one capture)."""
+        super().__init__(lengths, hop)
         self.device = device
         if tables is None:
             both = self._upload([self.cu_rows_host, self.cu_frames_host], torch.int32)

@@ -296,7 +296,7 @@ def _generate_over_ranks(store, batch_size, length, device, logdir, ckpt, debug)
         store.load_checkpoint(ckpt, use_ema=bool(hp.train.use_ema))
     elif rank == 0:
         print('No checkpoint found at {}.'.format(logdir))
-    seed = torch.tensor([int(os.environ.get('PWV_NOISE_SEED') or int.from_bytes(os.urandom(7), 'little'))], dtype=torch.int64, device=device)
+    seed = torch.tensor([int(os.environ.get('PWV_NOISE_SEED') or engine.os_seed())], dtype=torch.int64, device=device)
     dist.broadcast(seed, src=0)                                         # one noise stream for the whole job
     seed = int(seed.item())
     halo = chain_halo(hp.model.dilations, hp.model.filter_width, hp.model.n_iaf, hop)

@@ -25,7 +25,6 @@ from __future__ import annotations
 
 import collections
 import ctypes
-import os
 from typing import Optional
 
 import numpy as np
@@ -33,21 +32,99 @@ import torch
 
 from . import _lib, engine
 from .hparam import hparam as hp
-from .models import IAFVocoder, VarlenOutput, noise_streams
+from .models import IAFVocoder, VarlenOutput, check_packed_mels, noise_streams
+from .variables import get_default_store
 
 
-class GraphedVocoder(object):
+class _Captured(object):
+    """The capture lifecycle the three wrappers share ("The capture lifecycle").  A subclass provides _enqueue()
+    -- the forward the graph holds, run `warmup` times and then captured, all on ONE side stream -- and, where it needs them, the
+    hooks _before_capture(), _after_warmup() and _settle()."""
+
+    PERSIST_ONLY = False       # the captured forward exists on the persistent route only: a suspension leaves nothing to capture
+
+    def __init__(self, model, device, warmup):
+        self.model = model
+        self.store = model.store or get_default_store()
+        self.device = torch.device(device) if device is not None else self.store.device
+        if self.device.type != 'cuda':
+            raise _lib.PwvError('%s needs a GPU (cuda device); there is no CPU path' % type(self).__name__)
+        self._warmup = warmup
+        self._stream = None
+        self._words = None
+        self.graph = None
+        self.captures = 0          # graphs captured so far (new weights, other launch knobs or the end of a suspension capture again)
+        self.eager_calls = 0       # calls that ran the eager forward instead (a suspension, a call that does not fit the capture)
+
+    def _before_capture(self):
+        """The state the warm-up and the capture run on (self._words is set)."""
+
+    def _after_warmup(self):
+        """What the warm-up has to have shown before its launches are captured."""
+
+    def _settle(self):
+        """Ahead of a re-capture: what is in flight on the stale graph."""
+
+    def _capture(self):
+        self.graph = None
+        if self.PERSIST_ONLY and engine.persist_suspended():
+            return           # (no persistent route now: calls run eagerly until the suspension ends, then capture)
+        if self._stream is None:
+            self._stream = torch.cuda.Stream(device=self.device)
+        side = self._stream
+        # the captured launches carry THIS thread's sticky words (engine.current_words): verify() reads these, whoever replays
+        self._words = engine.current_words(self.device)
+        self._before_capture()
+        # warm up on a side stream (plans packed, side streams created, allocator primed), as stream capture requires
+        # (one stream for warm-up AND capture: what the warm-up forwards set up per stream -- the persistent launches' zeroed
+        # workspace, engine._persist_ws -- is then found again by the captured forward instead of being allocated inside the graph)
+        side.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(side):
+            for _ in range(self._warmup):
+                self._enqueue()
+        torch.cuda.current_stream(self.device).wait_stream(side)
+        self._after_warmup()
+        graph = torch.cuda.CUDAGraph()
+        saved, engine.EVENT_LOG = engine.EVENT_LOG, None       # (the log brackets launches with timing events: not inside a capture)
+        try:
+            # thread_local: only this thread's calls are policed during capture (an RCCL watchdog thread of a multi-rank
+            # job may touch the runtime meanwhile); everything captured here is enqueued from this thread
+            with torch.cuda.graph(graph, stream=side, capture_error_mode='thread_local'):
+                self.out = self._enqueue()
+        finally:
+            engine.EVENT_LOG = saved
+        self.graph = graph
+        self._version = self.store.version
+        self._mode = engine.launch_knobs()
+        self.captures += 1
+
+    def _stale(self) -> bool:
+        """No graph, new weights (the captured launches point at stale packs), or other values of what decides WHICH launches a forward
+        enqueues (engine.launch_knobs; a suspension is one of them)."""
+        return self.graph is None or self.store.version != self._version or self._mode != engine.launch_knobs()
+
+    def _ready(self) -> bool:
+        """Ahead of every replay: is there a graph that may be replayed now?  False: the caller runs eagerly (eager_calls)."""
+        if self.PERSIST_ONLY and engine.persist_suspended():
+            self.graph = None       # (the suspension retired the workspace the captured launches point at)
+            return False
+        if self._stale():
+            self._settle()
+            self._capture()
+        return self.graph is not None
+
+    def _verify_words(self, where: str = '') -> None:
+        """engine.verify_enqueued on the captured pair of sticky words, then on the calling thread's where that is another pair (a graph
+        captured by another thread reports into that thread's words)."""
+        engine.verify_enqueued(where, words=self._words)
+        if self._words is not None and self._words is not engine.current_words(self.device):
+            engine.verify_enqueued(where)
+
+
+class GraphedVocoder(_Captured):
 
     def __init__(self, model: IAFVocoder, device=None, warmup: int = 2):
-        self.model = model
-        store = model.store
-        if store is None:
-            from .variables import get_default_store
-            store = get_default_store()
-        self.store = store
-        self.device = torch.device(device) if device is not None else store.device
-        if self.device.type != 'cuda':
-            raise engine._lib.PwvError('GraphedVocoder needs a GPU (cuda device); there is no CPU path')
+        super().__init__(model, device, warmup)
         n, length = int(model.batch_size), int(model.length)
         self.mel = torch.zeros((n, model.t_mel, int(hp.signal.n_mels)), dtype=torch.float32, device=self.device)
         self.z = torch.zeros((n, length, 1), dtype=torch.float32, device=self.device)
@@ -56,44 +133,20 @@ class GraphedVocoder(object):
         self.noise_state = torch.zeros((4,), dtype=torch.int64, device=self.device)
         self._noise_mirror = (0, 0, 0)          # (seed, offset, skip) the device state holds
         self._last_drawn = 0                    # samples the replay that has not been verified yet took from the model's noise stream
-        self._warmup = warmup
         self._capture()
 
-    def _capture(self):
-        # warm up on a side stream (plans packed, side streams created, allocator primed), as stream capture requires
-        # (one stream for warm-up AND capture: what the warm-up forwards set up per stream -- the persistent launches' zeroed
-        # workspace, engine._persist_ws -- is then found again by the captured forward instead of being allocated inside the graph)
-        if getattr(self, '_stream', None) is None:
-            self._stream = torch.cuda.Stream(device=self.device)
-        side = self._stream
-        side.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(side):
-            for _ in range(self._warmup):
-                self.model(None, self.mel, is_training=False, z=self.z)
-        torch.cuda.current_stream(self.device).wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        # the captured launches carry THIS thread's sticky words (engine.current_words): verify() reads these, whoever replays
-        self._words = engine.current_words(self.device)
-        # thread_local: only this thread's calls are policed during capture (an RCCL watchdog thread of a multi-rank
-        # job may touch the runtime meanwhile); everything captured here is enqueued from this thread
-        with torch.cuda.graph(self.graph, stream=side, capture_error_mode='thread_local'):
+    def _enqueue(self):
+        if torch.cuda.is_current_stream_capturing():      # (a node of the graph only: a warm-up forward leaves the device state alone)
             engine.logistic_noise_stream_op(self.z, self.noise_state)
-            self.out = self.model(None, self.mel, is_training=False, z=self.z)
-        self._version = self.store.version
-        self._mode = self._launch_mode()
-
-    @staticmethod
-    def _launch_mode():
-        """what decides WHICH launches a forward enqueues, besides the weights: a graph captured under another value is stale"""
-        return engine.launch_knobs()
+        return self.model(None, self.mel, is_training=False, z=self.z)
 
     def verify(self):
         """Replays only enqueue: wait for them and raise like IAFVocoder.verify().  After a PwvPersistError the engine has
         suspended the persistent launches (engine.suspend_persist); the graph is re-captured on the per-layer path here, so the
         caller's rerun replays launches that can complete -- and once the suspension has counted down (one tick per replay) the
-        next call re-captures on the persistent path again (_launch_mode)."""
+        next call re-captures on the persistent path again (_stale)."""
         try:
-            engine.verify_enqueued(words=self._words)
+            self._verify_words()
         except engine._lib.PwvError as e:
             # the replay that failed drew its noise from the stream already: hand that range back, so that the caller's rerun
             # (z = None again) is a rerun ON THE SAME NOISE, like the eager path's (the device state is rewritten by the next call:
@@ -110,9 +163,8 @@ class GraphedVocoder(object):
         no copy); z [N, length, 1] or None (sample Logistic(0,1), models.py:32-33).
         Returns the graph's output buffer [N, length, 1]: valid until the next call (clone it to keep it).  Enqueue-only, like
         IAFVocoder.__call__(verify=False): call verify() before reading the result."""
-        engine.note_forward()
-        if self.store.version != self._version or self._mode != self._launch_mode():
-            self._capture()      # weights changed (the captured launches point at stale packs) or the engine switched launch paths
+        engine.note_forward()      # (ahead of _ready: the replay that ends a suspension re-captures on the persistent path)
+        self._ready()
         if tuple(melspec.shape) != tuple(self.mel.shape):
             raise ValueError('melspec must be %s (fixed at capture), got %s' % (tuple(self.mel.shape), tuple(melspec.shape)))
         if melspec is not self.mel:      # (a caller that writes its mel straight into the graph's input buffer `self.mel` passes that: no copy)
@@ -140,8 +192,8 @@ class GraphedVocoder(object):
     def _set_noise_state(self, want):
         if want != self._noise_mirror:
             # the state words are uint64 on the device (seeds up to 2**64 - 1, like the eager sampler's c_uint64): same bits as int64
-            wrap = lambda v: (int(v) & ((1 << 64) - 1)) - (1 << 64) if (int(v) & (1 << 63)) else int(v) & ((1 << 64) - 1)  # noqa: E731
-            self.noise_state.copy_(torch.tensor([wrap(want[0]), wrap(want[1]), 0, want[2]], dtype=torch.int64), non_blocking=False)
+            self.noise_state.copy_(torch.tensor([engine.as_int64_bits(want[0]), engine.as_int64_bits(want[1]), 0, want[2]], dtype=torch.int64),
+                                   non_blocking=False)
             self._noise_mirror = want
 
 
@@ -151,7 +203,7 @@ def packed_filler_rows(hop: int) -> int:
     return hop * -(-max(hop, _lib.VARLEN_MIN_ROWS) // hop)
 
 
-class GraphedPackedVocoder(object):
+class GraphedPackedVocoder(_Captured):
     """The packed forward of IAFVocoder.generate_varlen with one noise stream per utterance (seeds=), captured once at a capacity
     of `slots` utterances and `rows` samples and replayed for ANY lengths that fit it ("Graph replay of packed
     batches").  On the packed persistent route no launch argument depends on the individual lengths: the plan is made on N = 1,
@@ -168,17 +220,10 @@ class GraphedPackedVocoder(object):
     a materialised or normalised condition) is refused at construction with PwvError, since its launches depend on the lengths."""
 
     FILLER_SEED = 0
+    PERSIST_ONLY = True
 
     def __init__(self, model: IAFVocoder, slots: int, rows: int, warmup: int = 2, device=None):
-        self.model = model
-        store = model.store
-        if store is None:
-            from .variables import get_default_store
-            store = get_default_store()
-        self.store = store
-        self.device = torch.device(device) if device is not None else store.device
-        if self.device.type != 'cuda':
-            raise _lib.PwvError('GraphedPackedVocoder needs a GPU (cuda device); there is no CPU path')
+        super().__init__(model, device, max(1, int(warmup)))
         self.hop = hop = int(hp.signal.hop_length)
         self.filler = packed_filler_rows(hop)
         self.slots, self.rows = int(slots), int(rows)
@@ -206,12 +251,6 @@ class GraphedPackedVocoder(object):
         self._staging = [torch.zeros((nt,), dtype=torch.uint8).pin_memory() for _ in range(2)]
         self._staged = [None, None]
         self._flip = 0
-        self._warmup = max(1, int(warmup))
-        self._stream = None
-        self._words = None
-        self.graph = None
-        self.captures = 0          # graphs captured so far (a weight or launch-knob change, or the end of a suspension, captures again)
-        self.eager_calls = 0       # calls that ran the eager packed forward instead (a suspension, a layout that does not fit)
         self._capture()
 
     # -- layout ------------------------------------------------------------------------------------------------------------------
@@ -249,15 +288,12 @@ class GraphedPackedVocoder(object):
         self._flip ^= 1
         if self._staged[k] is not None:
             self._staged[k].synchronize()          # (the copy that last read this staging buffer has run)
-        cu_rows, cu_frames = [0], [0]
-        for v in lengths:
-            cu_rows.append(cu_rows[-1] + v)
-            cu_frames.append(cu_frames[-1] + v // self.hop + 1)
+        layout = engine.PackedLayout(lengths, self.hop)
         pairs = list(streams) + [(self.FILLER_SEED, 0)] * (len(lengths) - len(streams))
         buf = self._staging[k].numpy()
         a = 4 * (self.slots + 1)
-        buf[:a] = np.asarray(cu_rows, np.int32).view(np.uint8)
-        buf[a:2 * a] = np.asarray(cu_frames, np.int32).view(np.uint8)
+        buf[:a] = np.asarray(layout.cu_rows_host, np.int32).view(np.uint8)
+        buf[a:2 * a] = np.asarray(layout.cu_frames_host, np.int32).view(np.uint8)
         buf[2 * a:] = np.asarray([engine.as_int64_bits(v) for p in pairs for v in p], np.int64).view(np.uint8)
         self._tables.copy_(self._staging[k], non_blocking=True)
         ev = torch.cuda.Event()
@@ -273,36 +309,18 @@ class GraphedPackedVocoder(object):
         return engine.verified_call(lambda prec: m._forward_varlen(self.store, self.mel, self.z, self._geom, prec or m.precision),
                                     verify=False)
 
-    def _capture(self):
-        self.graph = None
-        if engine.persist_suspended():
-            return           # (no packed persistent route now: calls run eagerly until the suspension ends, then capture)
-        if self._stream is None:
-            self._stream = torch.cuda.Stream(device=self.device)
-        side = self._stream
+    def _before_capture(self):
         layout = self._layout([self.filler])          # capture on an all-filler layout: any layout replays the same launches
         self._write_tables(layout, [])
         self._geom = engine.VarlenGeometry(layout, self.hop, self.device, tables=(self.cu_rows, self.cu_frames, self._unit_map))
         self.mel.zero_()
-        # warm up on the capture stream (plans packed, allocator primed, that stream's persistent workspace created), as GraphedVocoder
-        padded = engine.VARLEN_PADDED
-        side.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(side):
-            for _ in range(self._warmup):
-                self._enqueue()
-        torch.cuda.current_stream(self.device).wait_stream(side)
-        if engine.VARLEN_PADDED != padded:
+        self._padded = engine.VARLEN_PADDED
+
+    def _after_warmup(self):
+        if engine.VARLEN_PADDED != self._padded:
             raise _lib.PwvError('GraphedPackedVocoder: a flow takes the padded fallback at %d slots / %d rows (%s): its launches depend on '
                                 'the lengths, there is nothing to capture' % (self.slots, self.rows, engine.VARLEN_PADDED_WHY))
         engine.verify_enqueued('the warm-up of a packed graph')
-        graph = torch.cuda.CUDAGraph()
-        self._words = engine.current_words(self.device)
-        with torch.cuda.graph(graph, stream=side, capture_error_mode='thread_local'):
-            self.out = self._enqueue()
-        self.graph = graph
-        self._version = self.store.version
-        self._mode = engine.launch_knobs()
-        self.captures += 1
 
     # -- calls -------------------------------------------------------------------------------------------------------------------
     def __call__(self, melspecs, seeds, offsets=None):
@@ -311,23 +329,14 @@ class GraphedPackedVocoder(object):
         a VarlenOutput of [len_i, 1] views of the graph's output buffer: valid until the next call (clone to keep).  Enqueue-only:
         call verify() before reading.  A layout that does not fit, or a call while the persistent launches are suspended, runs the
         eager generate_varlen(verify=False) instead and returns its result."""
-        if not isinstance(melspecs, (list, tuple)) or not melspecs:
-            raise ValueError('melspecs must be a non-empty list of [t_mel, n_mels] tensors')
-        n_mels = int(hp.signal.n_mels)
-        for i, m in enumerate(melspecs):
-            if not hasattr(m, 'dim') or m.dim() != 2 or m.shape[1] != n_mels or m.shape[0] < 2:
-                raise ValueError('melspecs[%d] must be [t_mel >= 2, %d], got %s' % (i, n_mels, tuple(getattr(m, 'shape', ()))))
+        check_packed_mels(melspecs)
         streams = noise_streams(seeds, offsets, len(melspecs))
         if streams is None:
             raise ValueError('a packed graph draws its noise from seeds: pass one per utterance')
         lengths = [(int(m.shape[0]) - 1) * self.hop for m in melspecs]
-        if engine.persist_suspended():
-            self.graph = None       # (the suspension retired the workspace the captured launches point at)
-        if engine.persist_suspended() or not self.fits(lengths):
+        if not self._ready() or not self.fits(lengths):
             self.eager_calls += 1
             return self.model.generate_varlen(list(melspecs), seeds=[s for s, _ in streams], offsets=[o for _, o in streams], verify=False)
-        if self.graph is None or self.store.version != self._version or self._mode != engine.launch_knobs():
-            self._capture()         # first call after a suspension, new weights (the launches point at stale packs), other launch knobs
         engine.note_forward()
         layout = self._layout(lengths)
         real_frames = sum(int(m.shape[0]) for m in melspecs)
@@ -335,23 +344,21 @@ class GraphedPackedVocoder(object):
         self.mel[real_frames:].zero_()
         self._write_tables(layout, streams)
         self.graph.replay()
-        geom = _Layout(lengths, self.hop)
-        return VarlenOutput(self.out[:geom.rows], geom)
+        real = engine.PackedLayout(lengths, self.hop)
+        return VarlenOutput(self.out[:real.rows], real)
 
     def verify(self):
         """Wait for the enqueued calls and raise like IAFVocoder.verify(): PwvPersistError if a persistent launch gave up (the engine
         suspends the persistent launches; calls run eagerly meanwhile and the graph is captured again once the suspension ends),
         PwvRangeError if one left the range of the split-fp16 arithmetic.  The caller reruns with the same seeds: the same noise."""
         try:
-            engine.verify_enqueued()
-            if self._words is not None and self._words is not engine.current_words(self.device):
-                engine.verify_enqueued(words=self._words)       # (a graph captured by another thread reports into that thread's words)
+            self._verify_words()
         except _lib.PwvPersistError:
             self.graph = None
             raise
 
 
-class GraphedStream(object):
+class GraphedStream(_Captured):
     """ONE tick of a StreamingVocoder -- `n` running sessions x `frames` mel frames, T = frames * hop samples each -- captured into a HIP
     graph with the commit on the device ("Graph replay of a streaming tick"; StreamingVocoder.graphed):
 
@@ -368,17 +375,11 @@ class GraphedStream(object):
 
     Refused at construction (PwvError) wherever a flow of an [n, T] push is not the whole-flow persistent streaming launch."""
 
+    PERSIST_ONLY = True
+
     def __init__(self, stream, n: int, frames: int, sample: bool = True, depth: int = 4, warmup: int = 2):
         st = self.stream = stream
-        self.model = st.model
-        store = st.model.store
-        if store is None:
-            from .variables import get_default_store
-            store = get_default_store()
-        self.store = store
-        self.device = st.device
-        if self.device.type != 'cuda':
-            raise _lib.PwvError('GraphedStream needs a GPU (cuda device); there is no CPU path')
+        super().__init__(st.model, st.device, max(1, int(warmup)))
         self.n, self.frames = int(n), int(frames)
         if self.n < 1 or self.frames < 1:
             raise ValueError('a graphed tick needs n >= 1 sessions and frames >= 1, got %r / %r' % (n, frames))
@@ -387,9 +388,7 @@ class GraphedStream(object):
                              'use are fillers on OTHER slots of the stream' % (self.n, self.n, st.n_slots))
         self.T = self.frames * st.hop
         self.sample, self.depth = bool(sample), max(1, int(depth))
-        why = self._refusal()
-        if why is not None:
-            raise _lib.PwvError('GraphedStream: a flow of a %d x %d push is not one persistent streaming launch: %s' % (self.n, self.T, why))
+        self._check_route()
         dev, n = self.device, self.n
         self.mel = torch.zeros((n, self.frames, st.n_mels), dtype=torch.float32, device=dev)
         self.z = torch.zeros((n, self.T, 1), dtype=torch.float32, device=dev)
@@ -411,12 +410,6 @@ class GraphedStream(object):
         self._seen = [0, 0]                     # the counters at the last verify()
         self._carry = 0                         # eager ticks settled on the way (counted by the next verify())
         self._dirty_rows = 0                    # rows of mel / z that may hold a previous tick's values
-        self._warmup = max(1, int(warmup))
-        self._stream = None
-        self._words = None
-        self.graph = None
-        self.captures = 0          # graphs captured so far (new weights, other launch knobs or the end of a suspension capture again)
-        self.eager_calls = 0       # ticks that ran the eager push instead (a suspension, a tick that does not fit the capture)
         self._capture()
 
     # -- capture -----------------------------------------------------------------------------------------------------------------
@@ -430,6 +423,11 @@ class GraphedStream(object):
         if engine.PERSIST == 'auto' and self.n * self.T > engine.PERSIST_AUTO_MAX_ROWS:
             return '%d rows are above PERSIST_AUTO_MAX_ROWS (%d)' % (self.n * self.T, engine.PERSIST_AUTO_MAX_ROWS)
         return None
+
+    def _check_route(self):
+        why = self._refusal()
+        if why is not None:
+            raise _lib.PwvError('GraphedStream: a flow of a %d x %d push is not one persistent streaming launch: %s' % (self.n, self.T, why))
 
     def _tick_args(self) -> _lib.StreamTickArgs:
         st, ta = self.stream, _lib.StreamTickArgs()
@@ -470,53 +468,39 @@ class GraphedStream(object):
         return others
 
     def _capture(self):
-        self.graph = None
-        if engine.persist_suspended():
-            return           # (no persistent streaming launch now: ticks run eagerly until the suspension ends, then capture)
-        why = self._refusal()
-        if why is not None:
-            raise _lib.PwvError('GraphedStream: a flow of a %d x %d push is not one persistent streaming launch: %s' % (self.n, self.T, why))
-        if self._stream is None:
-            self._stream = torch.cuda.Stream(device=self.device)
-        side = self._stream
-        self._words = engine.current_words(self.device)       # the captured launches report into THIS thread's words: verify() reads these
+        # the warm-up is judged by what it enqueued (_after_warmup): it runs under a log of its own where none is live
+        own = engine.EVENT_LOG is None
+        if own:
+            engine.EVENT_LOG = []
+        try:
+            super()._capture()
+        finally:
+            if own:
+                engine.EVENT_LOG = None
+
+    def _before_capture(self):
+        self._check_route()
         # warm up and capture on an all-filler table: no session is touched, any entries replay the same launches
         self._sync_rows(0, [], self._write_entries(0, [], 0))
         self.mel.zero_()
         self.z.zero_()
         self._dirty_rows = 0
-        log, own = engine.EVENT_LOG, engine.EVENT_LOG is None
-        if own:
-            log = engine.EVENT_LOG = []
-        mark = len(log)
-        try:
-            side.wait_stream(torch.cuda.current_stream(self.device))
-            with torch.cuda.stream(side):
-                for _ in range(self._warmup):
-                    self._enqueue()
-            torch.cuda.current_stream(self.device).wait_stream(side)
-        finally:
-            if own:
-                engine.EVENT_LOG = None
-        odd = [e[0] for e in log[mark:] if not (e[0] == 'persist' and e[8] == 1)]
+        self._log_mark = len(engine.EVENT_LOG)
+
+    def _after_warmup(self):
+        log = engine.EVENT_LOG[self._log_mark:]
+        odd = [e[0] for e in log if not (e[0] == 'persist' and e[8] == 1)]
         flows = int(hp.model.n_iaf)
-        if odd or len(log) - mark != self._warmup * flows or not all(e[5] == 1 and e[6] == 1 for e in log[mark:]):
+        if odd or len(log) != self._warmup * flows or not all(e[5] == 1 and e[6] == 1 for e in log):
             raise _lib.PwvError('GraphedStream: a flow of a %d x %d push is not one persistent streaming launch (the warm-up enqueued %s)'
-                                % (self.n, self.T, odd or '%d persistent launches for %d flows' % ((len(log) - mark) // self._warmup, flows)))
+                                % (self.n, self.T, odd or '%d persistent launches for %d flows' % (len(log) // self._warmup, flows)))
         engine.verify_enqueued('the warm-up of a streaming graph')
         self._counters.zero_()
         self._seen = [0, 0]
-        graph = torch.cuda.CUDAGraph()
-        saved, engine.EVENT_LOG = engine.EVENT_LOG, None       # (the log brackets launches with timing events: not inside a capture)
-        try:
-            with torch.cuda.graph(graph, stream=side, capture_error_mode='thread_local'):
-                self.out = self._enqueue()
-        finally:
-            engine.EVENT_LOG = saved
-        self.graph = graph
-        self._version = self.store.version
-        self._mode = engine.launch_knobs()
-        self.captures += 1
+
+    def _settle(self):
+        if self.stream._pending is not None:
+            self._carry = self.verify()        # (what it returns counts the carry in)
 
     # -- ticks -------------------------------------------------------------------------------------------------------------------
     def tick(self, mel, slots, z=None):
@@ -546,19 +530,12 @@ class GraphedStream(object):
             z = engine._require_cuda_f32(z, 'z')
             if tuple(z.shape) != (k, mel.shape[1] * st.hop, 1):
                 raise ValueError('z must be [%d, %d, 1], got %s' % (k, mel.shape[1] * st.hop, tuple(z.shape)))
-        if engine.persist_suspended():
-            self.graph = None       # (the suspension retired the workspace the captured launches point at)
-        if engine.persist_suspended() or mel.shape[1] != self.frames or k > self.n:
-            if st._pending is not None:
-                self._carry = self.verify()        # (what it returns counts the carry in)
+        if not self._ready() or mel.shape[1] != self.frames or k > self.n:
+            self._settle()
             self.eager_calls += 1
             return st.push(mel, slots=slots, z=z, verify=False)
-        if st._pending is not None and st._ticker is not self:
-            self._carry = self.verify()        # (what it returns counts the carry in)            # an eager push that only enqueued (or another graph's ticks): settled first
-        if self.graph is None or self.store.version != self._version or self._mode != engine.launch_knobs():
-            if st._pending is not None:
-                self._carry = self.verify()        # (what it returns counts the carry in)
-            self._capture()         # first tick after a suspension, new weights (the launches point at stale packs), other launch knobs
+        if st._ticker is not self:
+            self._settle()          # an eager push that only enqueued (or another graph's ticks): settled first
         engine.note_forward()
         if len(self._events) >= self.depth:
             self._events.popleft().synchronize()       # bounds the work that can pile up behind a refused tick (and frees staging j)
@@ -596,7 +573,7 @@ class GraphedStream(object):
                     continue
                 seed = seed if seed is not None else 0
             elif seed is None:
-                seed = int.from_bytes(os.urandom(7), 'little') if self.sample else 0
+                seed = engine.os_seed() if self.sample else 0
             want = (st._gen[s], st._emitted[s], engine.as_int64_bits(seed))
             if have != want:
                 rows[i, 0], rows[i, 1], rows[i, 2], rows[i, 3] = want[0], want[1], want[2], 0
@@ -635,16 +612,14 @@ class GraphedStream(object):
             gen, emitted, seed = int(table[s][0]) & 1, int(table[s][1]), int(table[s][2])
             st._gen[s], st._emitted[s], st._running[s] = gen, emitted, True
             if self.sample:
-                st._seed[s] = seed & ((1 << 64) - 1)
+                st._seed[s] = engine.from_int64_bits(seed)
             st._sess_host[s] = (gen, emitted, seed)
         self._inflight.clear()
         self._events.clear()
         st._pending, st._ticker = None, None
         committed, self._carry = committed + self._carry, 0
         try:
-            engine.verify_enqueued('a graphed streaming tick', words=self._words)
-            if self._words is not engine.current_words(self.device):
-                engine.verify_enqueued('a graphed streaming tick')
+            self._verify_words('a graphed streaming tick')
             if refused:
                 raise _lib.PwvError('%d graphed ticks were refused by their commit (a sticky word was raised and has been cleared since)' % refused)
         except _lib.PwvError as e:
@@ -654,14 +629,3 @@ class GraphedStream(object):
             raise
         return committed
 
-
-class _Layout(object):
-    """The layout of a replay's real utterances, in the shape VarlenOutput.geometry has (lengths, cu_rows_host, cu_frames_host)."""
-
-    def __init__(self, lengths, hop):
-        self.lengths, self.hop = list(lengths), hop
-        self.cu_rows_host, self.cu_frames_host = [0], [0]
-        for v in self.lengths:
-            self.cu_rows_host.append(self.cu_rows_host[-1] + v)
-            self.cu_frames_host.append(self.cu_frames_host[-1] + v // hop + 1)
-        self.n, self.rows = len(self.lengths), self.cu_rows_host[-1]

@@ -48,11 +48,17 @@ def noise_streams(seeds, offsets, n, z=None):
         vals = list(vals.tolist() if hasattr(vals, 'tolist') else vals)
         if len(vals) != n:
             raise ValueError('%s holds %d values for %d utterances' % (what, len(vals), n))
-        for i, v in enumerate(vals):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < (1 << 64):
-                raise ValueError('%s[%d] must be an integer in [0, 2**64), got %r' % (what, i, v))
-        return [int(v) for v in vals]
+        return [engine.check_u64(v, '%s[%d]' % (what, i)) for i, v in enumerate(vals)]
     return list(zip(ints(seeds, 'seeds'), ints([0] * n if offsets is None else offsets, 'offsets')))
+
+
+def check_packed_mels(melspecs) -> None:
+    """The mel list of a packed call (IAFVocoder.generate_varlen, graph.GraphedPackedVocoder): [t_mel_i >= 2, n_mels] each."""
+    if not isinstance(melspecs, (list, tuple)) or not melspecs:
+        raise ValueError('melspecs must be a non-empty list of [t_mel, n_mels] tensors')
+    for i, m in enumerate(melspecs):
+        if not hasattr(m, 'dim') or m.dim() != 2 or m.shape[1] != hp.signal.n_mels or m.shape[0] < 2:
+            raise ValueError('melspecs[%d] must be [t_mel >= 2, %d], got %s' % (i, hp.signal.n_mels, tuple(getattr(m, 'shape', ()))))
 
 
 class IAFVocoder(object):
@@ -76,7 +82,7 @@ class IAFVocoder(object):
             return int(seed)
         if self.noise_seed is None:
             env = os.environ.get('PWV_NOISE_SEED')
-            self.noise_seed = int(env) if env else int.from_bytes(os.urandom(7), 'little')
+            self.noise_seed = int(env) if env else engine.os_seed()
         return self.noise_seed
 
     def sample_noise(self, n, device, out=None, seed=None):
@@ -180,11 +186,7 @@ class IAFVocoder(object):
         counter ``offsets[i]`` (default 0): piece i is then exactly what IAFVocoder(1, len_i) with noise_seed = seeds[i] and
         noise_offset = offsets[i] returns for mel i alone, whatever its companions and its position; this model's noise_offset does
         not move.  Not together with ``z``."""
-        if not isinstance(melspecs, (list, tuple)) or not melspecs:
-            raise ValueError('melspecs must be a non-empty list of [t_mel, n_mels] tensors')
-        for i, m in enumerate(melspecs):
-            if not hasattr(m, 'dim') or m.dim() != 2 or m.shape[1] != hp.signal.n_mels or m.shape[0] < 2:
-                raise ValueError('melspecs[%d] must be [t_mel >= 2, %d], got %s' % (i, hp.signal.n_mels, tuple(getattr(m, 'shape', ()))))
+        check_packed_mels(melspecs)
         noise_streams(seeds, offsets, len(melspecs), z)      # (checked before anything touches the device)
         if isinstance(z, (list, tuple)):      # (each piece against its own utterance: a split that only adds up to R would misassign)
             if len(z) != len(melspecs):
@@ -195,10 +197,9 @@ class IAFVocoder(object):
                     raise ValueError('z[%d] must be %s (utterance %d), got %s' % (i, want, i, tuple(getattr(v, 'shape', ()))))
             z = torch_cat([engine._require_cuda_f32(v, 'z[%d]' % i) for i, v in enumerate(z)])
         mels = [engine._require_cuda_f32(m, 'melspecs[%d]' % i) for i, m in enumerate(melspecs)]
-        cu_frames = [0]
-        for m in mels:
-            cu_frames.append(cu_frames[-1] + m.shape[0])
-        return self.forward_packed(torch_cat(mels), cu_frames, z=z, verify=verify, seeds=seeds, offsets=offsets)
+        hop = hp.signal.hop_length
+        layout = engine.PackedLayout([(m.shape[0] - 1) * hop for m in mels], hop)
+        return self.forward_packed(torch_cat(mels), layout.cu_frames_host, z=z, verify=verify, seeds=seeds, offsets=offsets)
 
     def forward_packed(self, mel_packed, cu_frames, z=None, verify=None, seeds=None, offsets=None):
         """generate_varlen on the packed form: `mel_packed` [F, n_mels] holds the utterances' frames one after the other and

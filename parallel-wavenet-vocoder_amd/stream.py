@@ -12,7 +12,6 @@ and the number of samples emitted.  Its size does not depend on the chunk length
 from __future__ import annotations
 
 import ctypes
-import os
 from typing import List, NamedTuple, Optional, Sequence
 
 import numpy as np
@@ -100,11 +99,10 @@ def ragged_plan(frames: Sequence[int], fresh: Sequence[bool], hop: int) -> Ragge
             raise ValueError('every session of a push needs at least one frame, got %r' % (f,))
     samples = [push_samples(int(f), bool(fr), hop) for f, fr in zip(frames, fresh)]
     launch = [i for i, t in enumerate(samples) if t > 0]
-    cu_rows, cu_frames = [0], [0]
-    for i in launch:
-        cu_rows.append(cu_rows[-1] + samples[i])
-        cu_frames.append(cu_frames[-1] + samples[i] // hop + 1)
-    return RaggedPlan(samples, launch, cu_rows, cu_frames)
+    if not launch:
+        return RaggedPlan(samples, launch, [0], [0])
+    layout = engine.PackedLayout([samples[i] for i in launch], hop)
+    return RaggedPlan(samples, launch, layout.cu_rows_host, layout.cu_frames_host)
 
 
 def tick_begin_tables(sess, kept, entries, mel, hop: int):
@@ -247,9 +245,7 @@ class StreamingVocoder(object):
 
     @staticmethod
     def _check_seed(v) -> int:
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < (1 << 64):
-            raise ValueError('a seed must be an integer in [0, 2**64), got %r' % (v,))
-        return int(v)
+        return engine.check_u64(v, 'a seed')
 
     def state(self, slot) -> dict:
         """A copy of the session in `slot` (to park it, or to bring another stream to the same point): load_state takes it."""
@@ -292,7 +288,7 @@ class StreamingVocoder(object):
         """The noise seed of every slot of a push that draws its own noise: given[i] where the call brings one, else the one kept
         from the slot's reset or first push, else drawn from the OS."""
         return [given[i] if (given is not None and given[i] is not None) else
-                (self._seed[s] if self._seed[s] is not None else int.from_bytes(os.urandom(7), 'little')) for i, s in enumerate(slots)]
+                (self._seed[s] if self._seed[s] is not None else engine.os_seed()) for i, s in enumerate(slots)]
 
     def _commit(self, slots, samples, new_seeds, idx, last):
         """The commit of a push that gave slots[i] samples[i] samples: the generation flip, running, emitted, the seeds (where the
@@ -469,7 +465,6 @@ class StreamingVocoder(object):
             commit()
             return RaggedOutput(torch.empty((0, 1), dtype=torch.float32, device=self.device), plan.samples)
         geom = engine.VarlenGeometry([plan.samples[i] for i in plan.launch], self.hop, self.device)
-        assert geom.cu_rows_host == plan.cu_rows and geom.cu_frames_host == plan.cu_frames
         # the packed mel: a running session brings its kept frame in front of its frames, a fresh one does not
         pieces = []
         for i in plan.launch:

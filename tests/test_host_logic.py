@@ -109,18 +109,83 @@ def test_repeated_condition_validation():
                                   'FUSE_PROLOGUE_MAX_OUTPUTS', 'PERSIST_AUTO_MAX_ROWS'])
 def test_every_launch_knob_outdates_a_captured_graph(monkeypatch, knob):
     """A graph captured under one value of a knob that decides which launches a forward enqueues is stale under another
-    (_persist_cooldown: a suspension of the persistent launches)."""
+    (_persist_cooldown: a suspension of the persistent launches) -- for each of the three wrappers, through the one _stale() they
+    share; new weights and a dropped graph make it stale too."""
     from pwv_amd import engine
-    from pwv_amd.graph import GraphedVocoder
-    key = GraphedVocoder._launch_mode()
     saved = getattr(engine, knob)
     other = {'PERSIST': False if saved is not False else 'auto', 'DEFAULT_PRECISION': 'f32' if saved != 'f32' else 'f16x3'}.get(knob)
     if other is None:
         other = (not saved) if isinstance(saved, bool) else saved + 1
-    monkeypatch.setattr(engine, knob, other)
-    assert GraphedVocoder._launch_mode() != key
-    monkeypatch.setattr(engine, knob, saved)
-    assert GraphedVocoder._launch_mode() == key
+    for cls in _graph_classes():
+        g = _captured_stand_in(cls)
+        assert not g._stale(), cls.__name__
+        monkeypatch.setattr(engine, knob, other)
+        assert g._stale(), cls.__name__
+        monkeypatch.setattr(engine, knob, saved)
+        assert not g._stale(), cls.__name__
+        g.store.version += 1
+        assert g._stale(), cls.__name__
+        g.store.version -= 1
+        assert not g._stale(), cls.__name__
+        g.graph = None
+        assert g._stale(), cls.__name__
+
+
+def _graph_classes():
+    from pwv_amd.graph import GraphedPackedVocoder, GraphedStream, GraphedVocoder
+    return GraphedVocoder, GraphedPackedVocoder, GraphedStream
+
+
+def _captured_stand_in(cls):
+    """A wrapper as it stands after a capture made now, without a device: a store with a version, a sentinel for the graph."""
+    import types
+    from pwv_amd import engine
+    g = cls.__new__(cls)
+    g.store = types.SimpleNamespace(version=3)
+    g.graph, g._version, g._mode = object(), g.store.version, engine.launch_knobs()
+    return g
+
+
+def test_ready_policy_under_a_suspension():
+    """_ready(): under a suspension the two wrappers whose forward exists on the persistent route only drop their graph, answer False
+    and capture nothing, GraphedVocoder captures once (the knobs changed: the per-layer path); after the suspension every one of them
+    captures once more; _settle runs ahead of every capture and at no other time."""
+    from pwv_amd import engine
+    for cls in _graph_classes():
+        g, events = _captured_stand_in(cls), []
+
+        def capture(g=g, events=events):
+            events.append('capture')
+            g.graph, g._version, g._mode = object(), g.store.version, engine.launch_knobs()
+        g._capture, g._settle = capture, lambda events=events: events.append('settle')
+        assert g._ready() is True and events == [], cls.__name__
+        engine.suspend_persist()
+        try:
+            for _ in range(2):
+                if cls.PERSIST_ONLY:
+                    assert g._ready() is False and g.graph is None and events == [], cls.__name__
+                else:
+                    assert g._ready() is True and g.graph is not None and events == ['settle', 'capture'], cls.__name__
+        finally:
+            engine.resume_persist()
+        del events[:]
+        for _ in range(2):
+            assert g._ready() is True and g.graph is not None and events == ['settle', 'capture'], cls.__name__
+    assert [cls.PERSIST_ONLY for cls in _graph_classes()] == [False, True, True]
+
+
+def test_u64_helpers():
+    from pwv_amd import engine
+    for bad in (True, -1, 2 ** 64, 1.0):
+        with pytest.raises(ValueError, match=r'a seed must be an integer in \[0, 2\*\*64\), got'):
+            engine.check_u64(bad, 'a seed')
+    for good in (0, 2 ** 64 - 1, np.int64(5)):
+        got = engine.check_u64(good, 'a seed')
+        assert type(got) is int and got == int(good)
+    v = (1 << 63) + 12345
+    assert engine.as_int64_bits(v) == v - (1 << 64) and engine.from_int64_bits(engine.as_int64_bits(v)) == v
+    assert all(engine.from_int64_bits(engine.as_int64_bits(u)) == u for u in (0, 7, (1 << 63) - 1, 1 << 63, (1 << 64) - 1))
+    assert 0 <= engine.os_seed() < 1 << 56
 
 
 def test_fused_supported_matrix():

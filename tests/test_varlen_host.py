@@ -25,6 +25,22 @@ def test_layout_from_lengths():
             _geom(bad)
 
 
+def test_packed_layout_is_the_host_side_of_the_geometry():
+    """engine.PackedLayout: the prefix sums every user of the packed layout takes (VarlenGeometry, the graph's tables, ragged_plan,
+    generate_varlen) -- plain integers, the geometry's checks and messages."""
+    from pwv_amd import engine
+    p = engine.PackedLayout([16000, 80, 4000], 80)
+    assert p.cu_rows_host == [0, 16000, 16080, 20080] and p.cu_frames_host == [0, 201, 203, 254]
+    assert p.lengths == [16000, 80, 4000] and p.frames == [201, 2, 51] and p.hop == 80
+    assert (p.n, p.rows, p.total_frames, p.max_len, p.max_frames) == (3, 20080, 254, 16000, 201)
+    assert isinstance(_geom([80]), engine.PackedLayout) and not hasattr(p, 'device')
+    with pytest.raises(ValueError, match='a packed batch needs at least one utterance'):
+        engine.PackedLayout([], 80)
+    for bad in ([81], [0], [-80]):
+        with pytest.raises(ValueError, match=r'utterance lengths must be positive multiples of hop_length \(80\), got %d' % bad[0]):
+            engine.PackedLayout([160] + bad, 80)
+
+
 def test_padded_index_maps_round_trip():
     g = _geom([3, 5, 2], hop=1)
     x = torch.arange(10, dtype=torch.float32).reshape(10, 1)
