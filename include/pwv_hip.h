@@ -638,6 +638,58 @@ typedef struct pwv_stream_tick_args {
 int pwv_stream_tick_begin(const pwv_stream_tick_args* args, pwv_stream_t stream);
 int pwv_stream_tick_commit(const pwv_stream_tick_args* args, pwv_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * A RAGGED streaming tick with its session state on the device (graph replay of a push_varlen: every session its own frame count, and
+ * the counts too are read on the device).  The state -- sess, kept -- is that of "A streaming TICK" above, unchanged.
+ *
+ * Per tick the caller writes `entries` (int32 [N][4] = {slot, live, frames, 0}; distinct slots) and `mel` (float [in_frames][n_mels]:
+ * the sessions' new frames in entry order, without kept frames).  The CAPACITY is fixed: N entries, in_frames frames in all
+ * (in_frames * hop rows), and min_frames >= 1, the fewest frames an entry may have (the packed persistent launches need 32 rows per
+ * session).  The frame counts as the device reads them:
+ *   cu_in[0] = 0;   f_i = clamp(entries[i].frames, min_frames, in_frames - cu_in[i] - (N-1-i) * min_frames)   for i < N-1;
+ *   f_{N-1} = in_frames - cu_in[N-1];   cu_in[i+1] = cu_in[i] + f_i
+ * so WHATEVER the table holds the N sessions have at least min_frames frames each and fill in_frames exactly: no address leaves the
+ * arrays and the unit map built from cu_rows / cu_frames is well formed.  (The caller writes counts that need no clamping; an entry
+ * that stands for no session is a FILLER, live = 0, with the frames that are left.)
+ *
+ * pwv_stream_tick_ragged_begin, for entry i with slot s and g = sess[s][0]:
+ *   slot_tab[i]  = {2s + g, 2s + 1 - g}
+ *   streams[i]   = {sess[s][2], sess[s][1]}                   (NULL: the noise is the caller's)
+ *   cu_rows[i]   = hop * cu_in[i],  cu_frames[i] = cu_in[i] + i        (i = 0 .. N: the packed layout of pwv_persist_args and of
+ *                                                                        pwv_logistic_noise_packed_f32 / pwv_varlen_unit_map)
+ *   chunk[cu_frames[i]] = kept[s],  chunk[cu_frames[i] + 1 + f] = mel[cu_in[i] + f]  for f < f_i     (chunk: float [in_frames + N][n_mels])
+ * pwv_stream_tick_ragged_commit, the LAST launch of a tick, makes the decision of pwv_stream_tick_commit: words[0] and words[1] are
+ * read once with system-scope atomic loads; both zero: every entry with live != 0 is COMMITTED -- sess[s][0] ^= 1, sess[s][1] +=
+ * hop * f_i, kept[s] = mel[cu_in[i] + f_i - 1] -- and counters[0] += 1; otherwise nothing changes and counters[1] += 1.  The committed
+ * ticks are a prefix of the enqueued ones, a filler is never committed, and a slot outside 0 .. n_slots-1 is read as a filler of slot 0.
+ * One launch each, nothing read on the host: a captured pair replays with whatever the tables hold then.
+ * PWV_EINVAL before a device is needed (pwv_last_error names the field): a NULL pointer (streams alone may be NULL; cu_rows and
+ * cu_frames are required with or without it), N < 1, N > 1024, min_frames < 1, hop < 1, n_mels < 1, n_slots < 1,
+ * in_frames < N * min_frames, in_frames * hop or (in_frames + N) * n_mels beyond 2^31 - 1, struct_size short of the struct.
+ * ------------------------------------------------------------------------------------- */
+typedef struct pwv_stream_tick_ragged_args {
+    size_t struct_size;                    /* = sizeof(pwv_stream_tick_ragged_args) as the caller was compiled */
+    int64_t* sess;                         /* device int64 [n_slots][4] */
+    float* kept;                           /* device float [n_slots][n_mels] */
+    const int32_t* entries;                /* device int32 [N][4] = {slot, live, frames, 0} */
+    const float* mel;                      /* device float [in_frames][n_mels] */
+    int32_t n_slots, N, in_frames, n_mels;
+    int32_t hop;                           /* samples per frame */
+    int32_t min_frames;                    /* the fewest frames of an entry */
+    /* pwv_stream_tick_ragged_begin writes: */
+    int32_t* slot_tab;                     /* device int32 [N][2] */
+    uint64_t* streams;                     /* device uint64 [N][2], or NULL */
+    int32_t* cu_rows;                      /* device int32 [N + 1] */
+    int32_t* cu_frames;                    /* device int32 [N + 1] */
+    float* chunk;                          /* device float [in_frames + N][n_mels] */
+    /* pwv_stream_tick_ragged_commit reads / advances: */
+    const int* words;                      /* the sticky pair (mapped host memory) the tick's launches report into */
+    int64_t* counters;                     /* device int64 [2] = {ticks committed, ticks refused} */
+} pwv_stream_tick_ragged_args;
+
+int pwv_stream_tick_ragged_begin(const pwv_stream_tick_ragged_args* args, pwv_stream_t stream);
+int pwv_stream_tick_ragged_commit(const pwv_stream_tick_ragged_args* args, pwv_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,6 +40,7 @@ EXPORTED_SYMBOLS = (
     'pwv_linear_split_f32', 'pwv_cond_project_f32', 'pwv_pack_first_fold_f16x3', 'pwv_pack_first_fold_f32', 'pwv_cond_split_f16', 'pwv_range_flag', 'pwv_status_words_alloc', 'pwv_status_words_free', 'pwv_range_check_f32', 'pwv_range_stats_f32',
     'pwv_persist_workspace_bytes', 'pwv_persist_short_input', 'pwv_persist_status', 'pwv_wavenet_stack_persist_f32', 'pwv_varlen_unit_map',
     'pwv_wavenet_layer_stream_f32', 'pwv_stream_carry_f32', 'pwv_stream_tick_begin', 'pwv_stream_tick_commit',
+    'pwv_stream_tick_ragged_begin', 'pwv_stream_tick_ragged_commit',
     'pwv_wav_to_mel_db_f32', 'pwv_pack_proj_f32', 'pwv_instance_norm_workspace_bytes', 'pwv_instance_norm_f32', 'pwv_channel_affine_f32', 'pwv_add_f32', 'pwv_gate_f32',
 )
 
@@ -223,6 +224,32 @@ class StreamTickArgs(Structure):
         self.struct_size = ctypes.sizeof(StreamTickArgs)
 
 
+class StreamTickRaggedArgs(Structure):
+    """pwv_stream_tick_ragged_args: the device session table of a stream and the tables of one RAGGED tick (include/pwv_hip.h, "A RAGGED
+    streaming tick")."""
+    _fields_ = [
+        ('struct_size', c_size_t),      # set by __init__
+        ('sess', c_void_p),
+        ('kept', c_void_p),
+        ('entries', c_void_p),
+        ('mel', c_void_p),
+        ('n_slots', ctypes.c_int32), ('N', ctypes.c_int32), ('in_frames', ctypes.c_int32), ('n_mels', ctypes.c_int32),
+        ('hop', ctypes.c_int32),
+        ('min_frames', ctypes.c_int32),
+        ('slot_tab', c_void_p),
+        ('streams', c_void_p),
+        ('cu_rows', c_void_p),
+        ('cu_frames', c_void_p),
+        ('chunk', c_void_p),
+        ('words', c_void_p),
+        ('counters', c_void_p),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = ctypes.sizeof(StreamTickRaggedArgs)
+
+
 # per-source extra flags (none in the product; tools/probes/regw/README.md: the register-stationary probe kernel needs
 # `-mllvm -amdgpu-mfma-vgpr-form=1`, which is why the sources are compiled one by one)
 EXTRA_FLAGS = {}
@@ -357,6 +384,8 @@ def _declare(lib):
     lib.pwv_stream_carry_f32.argtypes = [POINTER(StreamArgs), c_int, c_int, c_void_p]
     lib.pwv_stream_tick_begin.argtypes = [POINTER(StreamTickArgs), c_void_p]
     lib.pwv_stream_tick_commit.argtypes = [POINTER(StreamTickArgs), c_void_p]
+    lib.pwv_stream_tick_ragged_begin.argtypes = [POINTER(StreamTickRaggedArgs), c_void_p]
+    lib.pwv_stream_tick_ragged_commit.argtypes = [POINTER(StreamTickRaggedArgs), c_void_p]
     lib.pwv_head_packed_floats.restype = c_size_t
     lib.pwv_head_packed_floats.argtypes = [c_int]
     lib.pwv_pack_head_f32.argtypes = [f32p] * 6 + [c_int, c_int, f32p, c_void_p]

@@ -12,7 +12,7 @@ follow from the platform, not from the math:
     TensorBoard audio summaries, generate.py:71-73);
   * `data_path: 'synthetic'` (bench cases) or a glob of .npy mel files replaces the wav dataset;
     wav input uses the torch STFT front-end in audio_frontend.py.
-CLI (python-fire style, fire itself is not installed):  python -m pwv_amd.generate <case> [--ckpt=..] [--debug] [--varlen [--seed=S]] [--stream=FRAMES]
+CLI (python-fire style, fire itself is not installed):  python -m pwv_amd.generate <case> [--ckpt=..] [--debug] [--varlen [--seed=S]] [--stream=FRAMES [--graph]]
 """
 from __future__ import absolute_import, division, print_function
 
@@ -139,7 +139,7 @@ def _load_mels_varlen(data_path, batch_size, device):
     return mels
 
 
-def generate(case='default', ckpt=None, debug=False, varlen=False, seed=None, stream=None):
+def generate(case='default', ckpt=None, debug=False, varlen=False, seed=None, stream=None, graph=False):
     '''
     :param case: experiment case name
     :param ckpt: checkpoint to load model
@@ -150,7 +150,11 @@ def generate(case='default', ckpt=None, debug=False, varlen=False, seed=None, st
         its mel and the seed -- not on the other files of the run or their order.
     :param stream: vocode every input at its own length as a STREAM (IAFVocoder.open_stream): one session per input, fed in pushes
         of `stream` mel frames; writes the files --varlen writes.
+    :param graph: (with stream) every session starts with the eager one-frame push, every tick after that is one replay of a captured
+        ragged tick (StreamingVocoder.graphed_varlen at a capacity of one slot per input and inputs x `stream` frames); same files.
     '''
+    if graph and stream is None:
+        raise ValueError('--graph applies to --stream=FRAMES (graph replay of the ragged ticks)')
     if stream is not None:
         stream = int(stream)
         if stream < 1:
@@ -204,7 +208,7 @@ def generate(case='default', ckpt=None, debug=False, varlen=False, seed=None, st
     # (engine.verified_call); what comes back is what the reference's fp32 sess.run would have produced, or an exception.
     # verify=True is EXPLICIT: it outranks PWV_ASYNC=1 (whose default is enqueue-only) -- nothing unverified is written to disk
     if stream:
-        pred = _generate_stream(model, melspec, stream)
+        pred = _generate_stream_graph(model, melspec, stream) if graph else _generate_stream(model, melspec, stream)
     elif varlen:
         pred = model.generate_varlen(melspec, verify=True, seeds=None if seed is None else [seed] * len(melspec))
     else:
@@ -252,6 +256,57 @@ def _generate_stream(model, mels, frames):
         for k, (i, f) in enumerate(zip(slots, counts)):
             outs[i].append(got[k])
             pos[i] += f
+    return [torch.cat(o) for o in outs]
+
+
+def _generate_stream_graph(model, mels, frames, depth=4):
+    """--stream=FRAMES --graph: the sessions of _generate_stream, started by ONE eager push of every input's first frame (it is kept:
+    nothing to generate yet) and then advanced by graphed ragged ticks (graph.GraphedRaggedStream at a capacity of len(mels) slots and
+    len(mels) * frames frames: a tick of all sessions at `frames` frames fills it, a tick with sessions that have ended is filled up by
+    filler sessions, and one that does not fit -- short last chunks in every slot -- runs eagerly inside tick()).  The ticks only
+    enqueue; one verify() every `depth` ticks.  Where verify() reports refused ticks (a chunk outside the range of the split-fp16
+    arithmetic, a persistent launch that gave up) the sessions stand behind the committed ones: the first refused tick is pushed
+    again with the verified eager push_varlen -- which reruns it as the plain --stream would -- and the ticks go on from there."""
+    from . import _lib, engine
+    n, hop = len(mels), int(hp.signal.hop_length)
+    s = model.open_stream(slots=n)
+    first = s.push_varlen([m[:1] for m in mels], verify=True)
+    g = s.graphed_varlen(n, n * frames * hop, sample=True, depth=depth)
+    pos, outs = [1] * n, [[first[i]] for i in range(n)]
+    window = []                # the ticks enqueued since the last verify(): (slots, counts)
+
+    def settle():
+        try:
+            g.verify()
+        except _lib.PwvError as e:
+            if not hasattr(e, 'committed'):
+                raise
+            for slots, counts in window[e.committed:]:        # what the refused ticks returned is not the sessions' audio
+                for i, f in zip(slots, counts):
+                    pos[i] -= f
+                    outs[i].pop()
+            slots, counts = window[e.committed]
+            got = s.push_varlen([mels[i][pos[i]:pos[i] + f] for i, f in zip(slots, counts)], slots=slots, verify=True)
+            for k, (i, f) in enumerate(zip(slots, counts)):
+                outs[i].append(got[k])
+                pos[i] += f
+        del window[:]
+
+    while any(p < m.shape[0] for p, m in zip(pos, mels)):
+        slots = [i for i, m in enumerate(mels) if pos[i] < m.shape[0]]
+        counts = [min(frames, mels[i].shape[0] - pos[i]) for i in slots]
+        if window and (not g.fits(counts) or engine.persist_suspended()):
+            settle()                                 # (tick() would settle them itself, and raise from there)
+            continue
+        got = g.tick([mels[i][pos[i]:pos[i] + f] for i, f in zip(slots, counts)], slots)
+        for k, (i, f) in enumerate(zip(slots, counts)):
+            outs[i].append(got[k].clone())           # (a view of the graph's output buffer: the next tick overwrites it)
+            pos[i] += f
+        window.append((slots, counts))
+        if len(window) >= depth:
+            settle()
+    if window:
+        settle()
     return [torch.cat(o) for o in outs]
 
 

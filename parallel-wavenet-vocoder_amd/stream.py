@@ -140,6 +140,78 @@ def tick_commit(sess, kept, entries, mel, T: int, words):
     return sess, kept, True
 
 
+def ragged_tick_counts(entries, in_frames: int, min_frames: int):
+    """(numpy restatement of ragged_prefix, csrc/pwv_stream_tick.hip)  cu_in int64 [N + 1]: the prefix sums of the frame counts as the
+    device reads them from `entries` (int32 [N, 4] = {slot, live, frames, 0}) at a capacity of `in_frames` frames -- every count
+    clamped to min_frames .. what leaves min_frames for each entry behind it, the last entry the remainder."""
+    entries = np.asarray(entries, np.int32).reshape(-1, 4)
+    n = entries.shape[0]
+    if n < 1 or min_frames < 1 or in_frames < n * min_frames:
+        raise ValueError('%d entries of at least %d frames do not fit %d frames' % (n, min_frames, in_frames))
+    cu = np.zeros((n + 1,), np.int64)
+    for i in range(n - 1):
+        most = in_frames - int(cu[i]) - (n - 1 - i) * min_frames
+        cu[i + 1] = cu[i] + min(max(int(entries[i, 2]), min_frames), most)
+    cu[n] = in_frames
+    return cu
+
+
+def ragged_tick_begin_tables(sess, kept, entries, mel, hop: int, min_frames: int, touched: Optional[dict] = None):
+    """(numpy restatement of stream_tick_ragged_begin_kernel; tests, and the definition of the tables)  From the device session table
+    `sess` (int64 [n_slots, 4]), the kept frames `kept` [n_slots, n_mels], the tick's `entries` (int32 [N, 4] = {slot, live, frames, 0})
+    and its mel [in_frames, n_mels] (the sessions' new frames in entry order): (slot_tab int32 [N, 2], streams int64 [N, 2] = {seed,
+    emitted}, cu_rows int32 [N + 1], cu_frames int32 [N + 1], chunk float32 [in_frames + N, n_mels]) -- what push_varlen builds on the
+    host for the same running sessions.  `live` plays no part here.  `touched` (tests): a dict that receives, per array name, every
+    index the restatement reads or writes."""
+    sess, kept, mel = np.asarray(sess, np.int64), np.asarray(kept, np.float32), np.asarray(mel, np.float32)
+    entries = np.asarray(entries, np.int32).reshape(-1, 4)
+    n, in_frames = entries.shape[0], mel.shape[0]
+    cu = ragged_tick_counts(entries, in_frames, int(min_frames))
+    slots = np.where((entries[:, 0] >= 0) & (entries[:, 0] < sess.shape[0]), entries[:, 0], 0)      # (out of range: a filler of slot 0)
+    g = sess[slots, 0] & 1
+    slot_tab = np.stack([2 * slots + g, 2 * slots + 1 - g], axis=1).astype(np.int32)
+    streams = np.stack([sess[slots, 2], sess[slots, 1]], axis=1).astype(np.int64)
+    cu_rows = (cu * int(hop)).astype(np.int32)
+    cu_frames = (cu + np.arange(n + 1)).astype(np.int32)
+    chunk = np.zeros((in_frames + n, mel.shape[1]), np.float32)
+    seen = {'sess': [], 'kept': [], 'mel': [], 'chunk': []} if touched is None else touched
+    for name in ('sess', 'kept', 'mel', 'chunk'):
+        seen.setdefault(name, [])
+    written = np.zeros((in_frames + n,), bool)
+    for i in range(n):
+        s, at = int(slots[i]), int(cu_frames[i])
+        seen['sess'].append(s), seen['kept'].append(s), seen['chunk'].append(at)
+        chunk[at] = kept[s]
+        written[at] = True
+        for f in range(int(cu[i + 1] - cu[i])):
+            seen['mel'].append(int(cu[i]) + f), seen['chunk'].append(at + 1 + f)
+            chunk[at + 1 + f] = mel[int(cu[i]) + f]
+            written[at + 1 + f] = True
+    assert bool(written.all())          # the N sessions tile the chunk
+    return slot_tab, streams, cu_rows, cu_frames, chunk
+
+
+def ragged_tick_commit(sess, kept, entries, mel, hop: int, min_frames: int, words, touched: Optional[dict] = None):
+    """(numpy restatement of stream_tick_ragged_commit_kernel)  (sess, kept, committed) after the tick's last node: with both sticky
+    `words` (give-up, range) zero every LIVE entry's session flips its generation, has emitted hop * f_i more samples and keeps the
+    last of its frames; otherwise -- and for every filler -- nothing changes.  Returns copies."""
+    sess, kept = np.array(sess, np.int64), np.array(kept, np.float32)
+    mel = np.asarray(mel, np.float32)
+    if int(words[0]) != 0 or int(words[1]) != 0:
+        return sess, kept, False
+    entries = np.asarray(entries, np.int32).reshape(-1, 4)
+    cu = ragged_tick_counts(entries, mel.shape[0], int(min_frames))
+    seen = {} if touched is None else touched
+    for i, (slot, live) in enumerate(entries[:, :2]):
+        if live and 0 <= slot < sess.shape[0]:
+            seen.setdefault('sess', []).append(int(slot)), seen.setdefault('kept', []).append(int(slot))
+            seen.setdefault('mel', []).append(int(cu[i + 1]) - 1)
+            sess[slot, 0] ^= 1
+            sess[slot, 1] += int(hop) * int(cu[i + 1] - cu[i])
+            kept[slot] = mel[int(cu[i + 1]) - 1]
+    return sess, kept, True
+
+
 class RaggedOutput(list):
     """What StreamingVocoder.push_varlen returns: the [T_i, 1] pieces of the call's sessions (views; empty for a fresh session given one
     frame), with the packed [sum T_i, 1] result as `.packed` (as models.VarlenOutput)."""
@@ -279,6 +351,13 @@ class StreamingVocoder(object):
         (graph.GraphedStream; DESIGN.md section 9, "Graph replay of a streaming tick")."""
         from .graph import GraphedStream
         return GraphedStream(self, n, frames, sample=sample, depth=depth, warmup=warmup)
+
+    def graphed_varlen(self, slots: int, rows: int, sample: bool = True, depth: int = 4, warmup: int = 2):
+        """A RAGGED tick -- up to `slots` running sessions, `rows` samples in all, every session its own frame count -- captured into a HIP
+        graph with the frame counts read and the commit made on the device (graph.GraphedRaggedStream; DESIGN.md section 9, "Graph
+        replay of a ragged tick")."""
+        from .graph import GraphedRaggedStream
+        return GraphedRaggedStream(self, slots, rows, sample=sample, depth=depth, warmup=warmup)
 
     # -- a push ----------------------------------------------------------------------------------------------------------
     def _slots(self, slots) -> List[int]:

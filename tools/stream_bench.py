@@ -42,6 +42,21 @@ one synchronisation per tick, median of --steps after --warmup, the legs of a ce
 rounds.  `graph_over_stream`, `graph_pipelined_over_stream`, `overlap_over_graph` per round.
 
     python tools/stream_bench.py --graph [--steps 20] [--warmup 5] [--precision f16x3]
+
+--ragged-graph ("Graph replay of a ragged tick"): the ragged tick as ONE graph replay with the frame counts and the
+commit on the device (StreamingVocoder.graphed_varlen).  The three cells of --ragged, each captured at exactly its sessions and rows.
+Legs, same protocol (explicit z, one synchronisation per tick, median of --steps after --warmup, the legs of a cell one after the other
+in one process, the round twice):
+  ragged                  the eager push_varlen(verify=False) + verify(): the baseline, unchanged code
+  ragged_graph            one tick() + verify()
+  ragged_graph_varying    one tick() + verify() where consecutive ticks differ in their frame counts (two sessions exchange theirs) and
+                          z comes as a list of pieces: the entries are uploaded with every tick, as on a server whose counts change
+  ragged_graph_pipelined  8 ticks enqueued back to back, one verify(), divided by 8
+  uniform                 one push of S sessions x the mean length, as in --ragged
+`spread` = the largest difference between the two medians of a leg; `graph_not_slower_than_ragged`: ragged_graph <= ragged + spread in
+both rounds (`ragged_graph`, whose ticks repeat one table, is the graph's best case: see ragged_graph_varying).
+
+    python tools/stream_bench.py --ragged-graph [--steps 20] [--warmup 5] [--precision f16x3]
 """
 import argparse
 import json
@@ -63,6 +78,8 @@ def main():
     ap.add_argument('--chunks', default='800,1600,8000')
     ap.add_argument('--ragged', action='store_true', help='the ragged-tick cells (push_varlen against grouped pushes) instead of the default legs')
     ap.add_argument('--graph', action='store_true', help='the graphed-tick cells (StreamingVocoder.graphed against the eager push) instead of the default legs')
+    ap.add_argument('--ragged-graph', action='store_true',
+                    help='the ragged-tick cells as graph replays (StreamingVocoder.graphed_varlen against the eager push_varlen) instead of the default legs')
     args = ap.parse_args()
 
     import numpy as np
@@ -171,6 +188,64 @@ def main():
             cell['ragged_over_grouped'] = [round(a / b, 3) for a, b in zip(cell['ragged']['ms'], cell['grouped']['ms'])]
             cell['ragged_over_uniform'] = [round(a / b, 3) for a, b in zip(cell['ragged']['ms'], cell['uniform']['ms'])]
             cell['ragged_not_slower_than_grouped'] = all(a <= b + cell['spread'] for a, b in zip(cell['ragged']['ms'], cell['grouped']['ms']))
+            out['cells'].append(cell)
+            print('# %s' % json.dumps(cell), file=sys.stderr)
+        print(json.dumps(out))
+        return
+
+    if args.ragged_graph:
+        out = {'mode': 'ragged_graph', 'precision': args.precision, 'steps': args.steps, 'warmup': args.warmup, 'pipelined_ticks': 8, 'cells': []}
+        cells = [('mixed_%d' % S, [800 * (1 + i % 4) for i in range(S)]) for S in (8, 32)] + [('utterance_ends', [1600] * 31 + [80])]
+        for name, lens in cells:
+            S = len(lens)
+            model = IAFVocoder(batch_size=S, length=hop, store=store, precision=args.precision)
+            stream = model.open_stream(slots=S)
+            warm = -(-(halo + hop) // hop) * hop
+            stream.push(rand(S, warm // hop + 1, cfg.n_mels), z=rand(S, warm, 1))        # steady state: every session running
+            graphed = stream.graphed_varlen(S, sum(lens), sample=False)
+            slots = list(range(S))
+            mels, zs = [rand(T // hop, cfg.n_mels) for T in lens], [rand(T, 1) for T in lens]
+            z_packed = torch.cat(zs)
+            mean = -(-sum(lens) // (S * hop)) * hop
+            mel_u, z_u = rand(S, mean // hop, cfg.n_mels), rand(S, mean, 1)
+
+            # the same tick with the first and the last session's counts exchanged: alternating the two, every tick uploads its entries
+            lens_b = [lens[-1]] + lens[1:-1] + [lens[0]]
+            mels_b, zs_b = [rand(T // hop, cfg.n_mels) for T in lens_b], [rand(T, 1) for T in lens_b]
+            flip = [0]
+
+            def pipelined():
+                for _ in range(8):
+                    graphed.tick(mels, slots, z=z_packed)
+
+            def varying():
+                flip[0] ^= 1
+                graphed.tick(mels_b if flip[0] else mels, slots, z=zs_b if flip[0] else zs)
+
+            legs = {
+                'ragged': (lambda: stream.push_varlen(mels, z=zs, verify=False), stream.verify, 1),
+                'ragged_graph': (lambda: graphed.tick(mels, slots, z=z_packed), graphed.verify, 1),
+                'ragged_graph_varying': (varying, graphed.verify, 1),
+                'ragged_graph_pipelined': (pipelined, graphed.verify, 8),
+                'uniform': (lambda: stream.push(mel_u, z=z_u, verify=False), stream.verify, 1),
+            }
+            cell = {'cell': name, 'sessions': S, 'lengths': sorted(set(lens)), 'rows': sum(lens), 'uniform_rows': S * mean}
+            for leg in legs:
+                cell[leg] = {'ms': [], 'enqueue_ms': []}
+            for _ in range(2):
+                for leg, (fn, sync, ticks) in legs.items():
+                    ms, host = timed(fn, sync)
+                    cell[leg]['ms'].append(round(ms / ticks, 4))
+                    cell[leg]['enqueue_ms'].append(round(host / ticks, 4))
+            assert graphed.captures == 1 and graphed.eager_calls == 0
+            n_ticks = args.warmup + args.steps
+            assert stream.emitted(0) == warm + 2 * n_ticks * (10 * lens[0] + mean) + n_ticks * (lens[0] + lens_b[0])       # (varying: 2 n ticks, half of each)
+            cell['spread'] = round(max(abs(cell[leg]['ms'][0] - cell[leg]['ms'][1]) for leg in legs), 4)
+            ratio = lambda a, b: [round(x / y, 3) for x, y in zip(cell[a]['ms'], cell[b]['ms'])]      # noqa: E731
+            cell['graph_over_ragged'] = ratio('ragged_graph', 'ragged')
+            cell['graph_pipelined_over_ragged'] = ratio('ragged_graph_pipelined', 'ragged')
+            cell['graph_over_uniform'] = ratio('ragged_graph', 'uniform')
+            cell['graph_not_slower_than_ragged'] = all(g <= e + cell['spread'] for g, e in zip(cell['ragged_graph']['ms'], cell['ragged']['ms']))
             out['cells'].append(cell)
             print('# %s' % json.dumps(cell), file=sys.stderr)
         print(json.dumps(out))
