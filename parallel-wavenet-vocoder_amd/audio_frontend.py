@@ -27,6 +27,7 @@ from __future__ import annotations
 from typing import Optional
 
 import numpy as np
+import torch
 
 from .hparam import hparam as hp
 
@@ -154,7 +155,6 @@ def wav_to_mel_device(wav, normalise: Optional[bool] = None):
     """wav [N, L] float32 on the GPU -> (normalised) dB mel [N, 1 + L/hop, n_mels] on the GPU (pwv_wav_to_mel_db_f32),
     with the current hparams' signal settings.  Like audio.wav2melspec_db (audio.py:350) the dB range is normalised only
     when BOTH max_db and min_db are set; `normalise` overrides."""
-    import torch
     from . import _lib, engine
     s = hp.signal
     wav = engine._require_cuda_f32(wav, 'wav')

@@ -119,19 +119,24 @@ __global__ __launch_bounds__(256) void in_finalize_kernel(const double* __restri
             if (var < 0.0) var = 0.0;
             const double inv = 1.0 / sqrt(var + (double)eps);     // (variance + epsilon) ** .5, modules.py:282
             const double gm = gamma ? (double)gamma[c] : 1.0;
-            ab[(size_t)n * 2 * C + c] = (float)(gm * inv);
-            ab[(size_t)n * 2 * C + C + c] = (float)((beta ? (double)beta[c] : 0.0) - gm * inv * mean);
+            // scale | mean | shift.  The apply pass subtracts the mean BEFORE it scales: y = x * a + (beta - a * mean) cancels in fp32 where
+            // the deviation is small against the mean (T = 1, a near-constant channel: a = gamma / sqrt(eps) = 1e4 gamma, and the two
+            // terms of ~ 5e5 leave an error of 0.03 on a result of O(1)).  What the fp32 mean loses goes into the shift.
+            const float mean_hi = (float)mean;
+            ab[(size_t)n * 3 * C + c] = (float)(gm * inv);
+            ab[(size_t)n * 3 * C + C + c] = mean_hi;
+            ab[(size_t)n * 3 * C + 2 * C + c] = (float)((beta ? (double)beta[c] : 0.0) - gm * inv * (mean - (double)mean_hi));
         }
         __syncthreads();
     }
 }
 
-// Pass 2: y = x * scale[c] + shift[c]
+// Pass 2: y = (x - mean[c]) * scale[c] + shift[c]
 __global__ __launch_bounds__(256) void in_apply_kernel(const float* __restrict__ x, float* __restrict__ y, const float* __restrict__ ab_all,
                                                        int T, int C, int rows_per_block) {
-    extern __shared__ float ab[];      // [C] scale, [C] shift
+    extern __shared__ float ab[];      // [C] scale, [C] mean, [C] shift
     const int n = blockIdx.y;
-    for (int c = threadIdx.x; c < 2 * C; c += 256) ab[c] = ab_all[(size_t)n * 2 * C + c];
+    for (int c = threadIdx.x; c < 3 * C; c += 256) ab[c] = ab_all[(size_t)n * 3 * C + c];
     __syncthreads();
     const int t0 = blockIdx.x * rows_per_block;
     const int t1 = t0 + rows_per_block < T ? t0 + rows_per_block : T;
@@ -139,7 +144,7 @@ __global__ __launch_bounds__(256) void in_apply_kernel(const float* __restrict__
     const size_t total = (size_t)(t1 - t0) * C;
     for (size_t i = threadIdx.x; i < total; i += 256) {
         const int c = (int)((base + i) % C);
-        y[base + i] = fmaf(x[base + i], ab[c], ab[C + c]);
+        y[base + i] = fmaf(x[base + i] - ab[C + c], ab[c], ab[2 * C + c]);
     }
 }
 
@@ -282,7 +287,7 @@ size_t pwv_instance_norm_workspace_bytes(int N, int T, int C) {
     // utterance to 8 blocks -- 165 us per call on a chip that reads the tensor in 2; profiles/r06_configs.md, bench/in)
     int chunks = (T + 63) / 64;
     if (chunks > kInMaxChunks) chunks = kInMaxChunks;
-    return (size_t)N * chunks * C * 2 * sizeof(double) + (size_t)N * 2 * C * sizeof(float);      // partial sums, then scale | shift per (n, c)
+    return (size_t)N * chunks * C * 2 * sizeof(double) + (size_t)N * 3 * C * sizeof(float);      // partial sums, then scale | mean | shift per (n, c)
 }
 
 int pwv_instance_norm_f32(const float* x, float* y, int N, int T, int C, const float* gamma, const float* beta, float eps,
@@ -301,7 +306,7 @@ int pwv_instance_norm_f32(const float* x, float* y, int N, int T, int C, const f
     float* ab = (float*)((double*)workspace + (size_t)N * chunks * C * 2);
     hipLaunchKernelGGL(in_finalize_kernel, dim3(N), dim3(256), 0, s, (const double*)workspace, ab, gamma, beta, T, C, chunks, eps);
     const int rows_per_block = 64;
-    hipLaunchKernelGGL(in_apply_kernel, dim3((T + rows_per_block - 1) / rows_per_block, N), dim3(256), 2 * C * sizeof(float), s, x, y,
+    hipLaunchKernelGGL(in_apply_kernel, dim3((T + rows_per_block - 1) / rows_per_block, N), dim3(256), 3 * C * sizeof(float), s, x, y,
                        (const float*)ab, T, C, rows_per_block);
     PWV_CHECK_HIP(hipGetLastError());
     return PWV_OK;

@@ -1066,9 +1066,10 @@ VARLEN_PADDED_WHY = None  # ... and why the last of them did (graph.GraphedPacke
 def _remap_bank(bank: dict, total_frames: int, remap) -> dict:
     """A projection bank (RepeatedCondition.proj_bank) over other frame rows: the bank's column blocks are views of ONE [F, cols] GEMM
     output, so `remap` (rows in, rows out: a padding, a gather) is applied to that once and the blocks keep their column offsets.  The
-    prologue is per frame: a remapped row holds the bits a prologue over the remapped frames would compute."""
-    base = next(iter(bank.values()))
-    full = base.as_strided((total_frames, base.stride(0)), (base.stride(0), 1), 0)
+    prologue is per frame: a remapped row holds the bits a prologue over the remapped frames would compute.  (The GEMM output starts at
+    its first block, not necessarily at offset 0 of its storage: it may itself be a view into a larger allocation.)"""
+    base = min(bank.values(), key=lambda v: v.storage_offset())
+    full = base.as_strided((total_frames, base.stride(0)), (base.stride(0), 1), base.storage_offset())
     rows = remap(full)
     return {k: rows[:, v.storage_offset() - full.storage_offset():][:, :v.shape[1]] for k, v in bank.items()}
 

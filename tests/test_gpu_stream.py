@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from oracle import iaf_oracle as O
+from tests.guarded import Guard
 from tests.util import TOL_F32, set_hparams, small_cfg
 
 pytestmark = pytest.mark.gpu
@@ -219,20 +220,13 @@ def test_range_rerun_is_transactional(gpu):
 
 @pytest.mark.parametrize('precision', ['f16x3', 'f32'])
 def test_guard_bands_around_the_histories(gpu, precision):
-    """The histories allocated inside a NaN-filled buffer: after a ragged schedule with chunks of 80 and of 4000 samples on the
+    """The histories allocated inside a 0xFF-filled buffer (tests/guarded.py): after a ragged schedule with chunks of 80 and of 4000 samples on the
     default model the bands are untouched, the blocks of a slot that was never pushed are still zero, the pushed slots equal their
     one-shot forwards; and a session's state stays within 2 * sum round32(d_j) * 256 B + 64 KB (j over every layer of every net)."""
     cfg = O.ModelConfig()
     model, _ = _model(gpu, cfg, precision)
-    guard, keep = 1 << 16, []
-
-    def alloc(floats):
-        buf = torch.full((floats + 2 * guard,), float('nan'), device=gpu)
-        buf[guard:guard + floats].zero_()
-        keep.append((buf, floats))
-        return buf[guard:guard + floats]
-
-    s = model.open_stream(slots=3, hist_alloc=alloc)
+    bands = Guard(band_bytes=1 << 18)          # 0xFF on either side of the zero-filled histories, compared byte for byte afterwards
+    s = model.open_stream(slots=3, hist_alloc=lambda floats: bands.allocate((floats,), torch.float32, gpu, 0.0))
     L = 8800
     fd = _Feeder(s)
     ins = [_inputs(cfg, L, gpu, seed=50 + i) for i in range(2)]
@@ -240,9 +234,8 @@ def test_guard_bands_around_the_histories(gpu, precision):
     for T in [80, 4000, 80, 80, 4000, 560]:
         fd.adv([0, 2], T)
     torch.cuda.synchronize()
-    buf, floats = keep[0]
-    assert bool(torch.isnan(buf[:guard]).all()) and bool(torch.isnan(buf[guard + floats:]).all())
-    blocks = buf[guard:guard + floats].view(6, -1)
+    bands.check()
+    blocks = bands.allocations[0].payload().view(6, -1)
     assert not bool(torch.isnan(blocks).any()) and not bool(blocks[2:4].any())
     for slot, u in ((0, ins[0]), (2, ins[1])):
         assert torch.equal(fd.result(slot), _one_shot(model, u[2], u[3])), slot

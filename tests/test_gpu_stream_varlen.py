@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from oracle import iaf_oracle as O
+from tests.guarded import Guard
 from tests.test_gpu_stream import _inputs, _model, _one_shot, _small, _small_wide
 from tests.test_gpu_stream_persist import _Log, _random_state, _short_expected, knobs  # noqa: F401  (knobs: a fixture)
 
@@ -308,20 +309,13 @@ def test_a_session_does_not_depend_on_its_companions(gpu, knobs, precision):
 
 @pytest.mark.parametrize('precision', ['f16x3', 'f32'])
 def test_bystanders_and_guard_bands(gpu, knobs, precision):
-    """The histories inside a NaN-filled buffer (hist_alloc): after ragged pushes on the packed route (the general instantiation
+    """The histories inside a 0xFF-filled buffer (hist_alloc, tests/guarded.py): after ragged pushes on the packed route (the general instantiation
     included) the bands are untouched, no NaN came in, and the blocks of a slot that was never pushed are still zero."""
     cfg = O.ModelConfig()
     model, _ = _model(gpu, cfg, precision)
-    guard, keep = 1 << 16, []
-
-    def alloc(floats):
-        buf = torch.full((floats + 2 * guard,), float('nan'), device=gpu)
-        buf[guard:guard + floats].zero_()
-        keep.append((buf, floats))
-        return buf[guard:guard + floats]
-
+    bands = Guard(band_bytes=1 << 18)          # 0xFF on either side of the zero-filled histories, compared byte for byte afterwards
     S = 17                                   # slot 7 is never pushed
-    s = model.open_stream(slots=S, hist_alloc=alloc)
+    s = model.open_stream(slots=S, hist_alloc=lambda floats: bands.allocate((floats,), torch.float32, gpu, 0.0))
     rng = np.random.default_rng(6)
     ticks = [{i: 30 + i for i in range(S) if i != 7},                    # ~ 37000 rows: general
              {0: 1, 16: 1, 3: 12},
@@ -340,9 +334,8 @@ def test_bystanders_and_guard_bands(gpu, knobs, precision):
         kinds = _check_packed(lg.log, cfg, rows, gpu)
     assert 0 in kinds and 1 in kinds, kinds
     torch.cuda.synchronize()
-    buf, floats = keep[0]
-    assert bool(torch.isnan(buf[:guard]).all()) and bool(torch.isnan(buf[guard + floats:]).all())
-    blocks = buf[guard:guard + floats].view(2 * S, -1)
+    bands.check()
+    blocks = bands.allocations[0].payload().view(2 * S, -1)
     assert not bool(torch.isnan(blocks).any()) and not bool(blocks[14:16].any())
 
 

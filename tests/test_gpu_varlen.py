@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from oracle import iaf_oracle as O
+from tests.guarded import Guard
 from tests.util import TOL_F32, set_hparams, small_cfg
 
 pytestmark = pytest.mark.gpu
@@ -132,7 +133,7 @@ def test_unit_map_matches_numpy(gpu, built_lib):
 
 @pytest.mark.parametrize('precision', ['f16x3', 'f32'])
 def test_guard_bands_around_the_packed_output(gpu, precision):
-    """The affine output of a packed flow written inside a NaN-filled buffer: the bands in front of and behind it stay untouched
+    """The affine output of a packed flow written inside a poisoned buffer (tests/guarded.py): the bands in front of and behind it stay untouched
     (bounded buffer descriptors drop out-of-range stores silently; a parity test alone would not see an off-by-one), and every
     utterance equals its own uniform flow.  Odd lengths without a condition: units straddle every boundary."""
     from pwv_amd import engine
@@ -153,13 +154,13 @@ def test_guard_bands_around_the_packed_output(gpu, precision):
     for k, v in store.vars.items():
         v.copy_(torch.randn_like(v) * 0.1)
     store.version += 1
-    guard = 4096
-    buf = torch.full((R + 2 * guard,), float('nan'), device=gpu)
-    out = buf[guard:guard + R].view(1, R, 1)
+    bands = Guard(band_bytes=16384)            # the output as a NaN payload between two 0xFF bands, compared byte for byte afterwards
+    out = bands.allocate((1, R, 1), torch.float32, gpu, None)
     res = engine._run_nets(flow.nets(), x.view(1, R, 1), None, precision, 0, out, geom)
     torch.cuda.synchronize()
     assert res is not None and res[1], 'the packed flow must run as persistent launches with the affine inside'
-    assert bool(torch.isnan(buf[:guard]).all()) and bool(torch.isnan(buf[guard + R:]).all())
+    bands.check()
+    assert not bool(torch.isnan(out).any())
     for a, b in zip(geom.cu_rows_host, geom.cu_rows_host[1:]):
         want = engine.run_flow(flow.nets(), x[a:b][None], None, precision=precision)
         assert torch.equal(out[0, a:b], want[0])
