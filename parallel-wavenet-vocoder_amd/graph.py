@@ -208,6 +208,35 @@ def packed_filler_rows(hop: int) -> int:
     return hop * -(-max(hop, _lib.VARLEN_MIN_ROWS) // hop)
 
 
+def filler_layout(counts, entries: int, total: int, least: int, unit):
+    """The counts of all `entries` entries of a replay at a fixed capacity: the caller's `counts`, then FILLERS -- all but the last of
+    `least`, the last one what is left of `total`.  With every entry taken the counts fill `total` exactly.  unit = (what an entry is,
+    what is counted), for the messages; ValueError if the counts do not fit."""
+    counts, (whom, what) = [int(v) for v in counts], unit
+    n = len(counts)
+    if not 1 <= n <= entries:
+        raise ValueError('%d %ss for %d slots' % (n, whom, entries))
+    for v in counts:
+        if v < least:
+            raise ValueError('every %s needs at least %d %s, got %d' % (whom, least, what, v))
+    k, left = entries - n, total - sum(counts)
+    if k == 0:
+        if left != 0:
+            raise ValueError('%d %ss in all %d slots must fill the %d %s exactly, they hold %d' % (n, whom, n, total, what, total - left))
+        return counts
+    if left < k * least:
+        raise ValueError('%d %s and %d filler %ss of at least %d %s exceed the %d %s' % (total - left, what, k, whom, least, what, total, what))
+    return counts + [least] * (k - 1) + [left - (k - 1) * least]
+
+
+def _fits(layout, counts) -> bool:
+    try:
+        layout(counts)
+    except ValueError:
+        return False
+    return True
+
+
 class GraphedPackedVocoder(_Captured):
     """The packed forward of IAFVocoder.generate_varlen with one noise stream per utterance (seeds=), captured once at a capacity
     of `slots` utterances and `rows` samples and replayed for ANY lengths that fit it ("Graph replay of packed
@@ -261,30 +290,15 @@ class GraphedPackedVocoder(_Captured):
     # -- layout ------------------------------------------------------------------------------------------------------------------
     def _layout(self, lengths):
         """The lengths of all `slots` utterances of a replay: the real ones, then the fillers; ValueError if they do not fit."""
-        lengths = [int(v) for v in lengths]
-        n = len(lengths)
-        if not 1 <= n <= self.slots:
-            raise ValueError('%d utterances for %d slots' % (n, self.slots))
-        for v in lengths:
-            if v < _lib.VARLEN_MIN_ROWS or v % self.hop:
+        for v in lengths:          # (a multiple of hop of at least VARLEN_MIN_ROWS is at least a filler: filler_layout's own bound holds)
+            if int(v) < _lib.VARLEN_MIN_ROWS or int(v) % self.hop:
                 raise ValueError('utterance lengths must be multiples of hop_length (%d) of at least %d samples, got %d'
                                  % (self.hop, _lib.VARLEN_MIN_ROWS, v))
-        k, left = self.slots - n, self.rows - sum(lengths)
-        if k == 0:
-            if left != 0:
-                raise ValueError('%d utterances in all %d slots must fill the %d rows exactly, they hold %d' % (n, n, self.rows, self.rows - left))
-            return lengths
-        if left < k * self.filler:
-            raise ValueError('%d rows and %d filler utterances of at least %d rows exceed the %d rows' % (self.rows - left, k, self.filler, self.rows))
-        return lengths + [self.filler] * (k - 1) + [left - (k - 1) * self.filler]
+        return filler_layout(lengths, self.slots, self.rows, self.filler, ('utterance', 'rows'))
 
     def fits(self, lengths) -> bool:
         """Can utterances of these lengths (samples) be replayed by this capture?"""
-        try:
-            self._layout(lengths)
-        except ValueError:
-            return False
-        return True
+        return _fits(self._layout, lengths)
 
     def _write_tables(self, lengths, streams):
         """cu_rows, cu_frames and streams of the layout `lengths` (fillers included) into the device tables: one copy from pinned
@@ -364,18 +378,41 @@ class GraphedPackedVocoder(_Captured):
 
 
 class _TickGraph(_Captured):
-    """What the graphed ticks of a StreamingVocoder share (GraphedStream, GraphedRaggedStream): the session table on the device, entries
-    and rewritten session rows through pinned staging, at most `depth` ticks in flight, and verify().  A subclass sets self.stream,
-    self.sample and self.depth, calls _tick_state() and provides the tick itself."""
+    """ONE tick of a StreamingVocoder captured into a HIP graph with the commit on the device -- what GraphedStream and
+    GraphedRaggedStream are ("Graph replay of a streaming tick"):
+
+        begin kernel (session table [+ frame counts] -> slot table, noise streams, cu_rows [, cu_frames], the chunk's frames)  ->
+        packed sampler (sample=True)  ->  [pwv_varlen_unit_map]  ->  StreamingVocoder._enqueue (prologue, carry, one persistent
+        streaming launch per flow)  ->  commit kernel
+
+    The session table lives on the device; a tick's `entries` -- the called slots (live = 1), then FILLERS on other slots of the stream
+    (live = 0: they read their slot's generation g and write generation 1 - g, which is scratch until a flip, and are never committed)
+    -- and rewritten session rows go through pinned staging; at most `depth` ticks are in flight.  A subclass validates its capacity,
+    allocates mel, z and _chunk, calls _start() and provides what differs: ARGS / ENTRY / FIRST_PUSH, _shape_args, _push_args,
+    _capture_columns, _good_warmup, and the tick's _check_mel, _check_z, _columns, _eager and _copy_in."""
 
     PERSIST_ONLY = True
+    PACKED = False             # the push is a packed one: cu_rows with or without a sampler, cu_frames and the unit map besides
 
-    def _tick_state(self, n: int, entry_ints: int):
-        st, dev = self.stream, self.device
-        self._entries = torch.zeros((n, entry_ints), dtype=torch.int32, device=dev)
+    def __init__(self, stream, sample, depth, warmup):
+        self.stream = stream
+        super().__init__(stream.model, stream.device, max(1, int(warmup)))
+        self.sample, self.depth = bool(sample), max(1, int(depth))
+
+    def _start(self, n: int):
+        """The tables and the state of a tick of `n` entries, then the first capture (self.mel, self.z and self._chunk exist)."""
+        st, dev, ints = self.stream, self.device, self.ENTRY_INTS
+        self._n = n
+        self._check_route()
+        self._tab = torch.zeros((n, 2), dtype=torch.int32, device=dev)
+        self._streams = torch.zeros((n, 2), dtype=torch.int64, device=dev) if self.sample else None
+        self._cu_rows = torch.zeros((n + 1,), dtype=torch.int32, device=dev) if self.sample or self.PACKED else None
+        self._cu_frames = torch.zeros((n + 1,), dtype=torch.int32, device=dev) if self.PACKED else None
+        self._unit_map = torch.zeros(((self.z.numel() + 31) // 32 * _lib.VARLEN_REC_INTS,), dtype=torch.int32, device=dev) if self.PACKED else None
+        self._entries = torch.zeros((n, ints), dtype=torch.int32, device=dev)
         self._counters = torch.zeros((2,), dtype=torch.int64, device=dev)      # {ticks committed, ticks refused}
         # pinned staging of the entries and of rewritten session rows: one pair per tick that may be in flight
-        self._entries_host = [torch.zeros((n, entry_ints), dtype=torch.int32).pin_memory() for _ in range(self.depth)]
+        self._entries_host = [torch.zeros((n, ints), dtype=torch.int32).pin_memory() for _ in range(self.depth)]
         self._rows_host = [torch.zeros((n, 4), dtype=torch.int64).pin_memory() for _ in range(self.depth)]
         self._entries_dev = None                # the entries the device table holds, column by column (slots, live flags[, frames])
         self._counters_host = torch.zeros((2,), dtype=torch.int64).pin_memory()
@@ -385,7 +422,8 @@ class _TickGraph(_Captured):
         self._ticks = 0
         self._seen = [0, 0]                     # the counters at the last verify()
         self._carry = 0                         # eager ticks settled on the way (counted by the next verify())
-        self._dirty_rows = 0                    # rows of mel / z that may hold a previous tick's values
+        self._dirty_rows = 0                    # leading rows of mel (and their part of z) that may hold a previous tick's values
+        self._capture()
 
     def _refusal(self, rows: int) -> Optional[str]:
         m = hp.model
@@ -515,362 +553,291 @@ class _TickGraph(_Captured):
             raise
         return committed
 
-
-class GraphedStream(_TickGraph):
-    """ONE tick of a StreamingVocoder -- `n` running sessions x `frames` mel frames, T = frames * hop samples each -- captured into a HIP
-    graph with the commit on the device ("Graph replay of a streaming tick"; StreamingVocoder.graphed):
-
-        begin kernel (session table -> slot table, noise streams, the chunk's frames)  ->  packed sampler (sample=True)  ->
-        StreamingVocoder._enqueue (prologue, carry, one persistent streaming launch per flow)  ->  commit kernel
-
-    tick(mel [k, frames, n_mels], slots, z=None) replays it for 1 <= k <= n distinct RUNNING slots and only enqueues; the other n - k
-    entries are FILLERS on other slots of the stream (live = 0: they read their slot's generation g and write generation 1 - g, which
-    is scratch until a flip, and are never committed).  Ticks may follow each other with no synchronisation: the commit kernel flips a
-    session only if both sticky words are clean, and the words are sticky, so the committed ticks are a PREFIX of the enqueued ones.
-    verify() waits, makes the host's view of the sessions equal to the device table and returns the number of ticks committed; it
-    raises PwvRangeError / PwvPersistError (with that number as `.committed`) where a tick was refused: push the failed chunk again
-    with the eager push and carry on.  While ticks are in flight the stream is pending: push / reset / state refuse until verify().
-
-    Refused at construction (PwvError) wherever a flow of an [n, T] push is not the whole-flow persistent streaming launch."""
-
-    PERSIST_ONLY = True
-
-    def __init__(self, stream, n: int, frames: int, sample: bool = True, depth: int = 4, warmup: int = 2):
-        st = self.stream = stream
-        super().__init__(st.model, st.device, max(1, int(warmup)))
-        self.n, self.frames = int(n), int(frames)
-        if self.n < 1 or self.frames < 1:
-            raise ValueError('a graphed tick needs n >= 1 sessions and frames >= 1, got %r / %r' % (n, frames))
-        if self.n > st.n_slots:
-            raise ValueError('a graph for %d sessions needs a stream of at least %d slots (this one has %d): the entries a tick does not '
-                             'use are fillers on OTHER slots of the stream' % (self.n, self.n, st.n_slots))
-        self.T = self.frames * st.hop
-        self.sample, self.depth = bool(sample), max(1, int(depth))
-        self._check_route()
-        dev, n = self.device, self.n
-        self.mel = torch.zeros((n, self.frames, st.n_mels), dtype=torch.float32, device=dev)
-        self.z = torch.zeros((n, self.T, 1), dtype=torch.float32, device=dev)
-        self._chunk = torch.zeros((n, self.frames + 1, st.n_mels), dtype=torch.float32, device=dev)
-        self._tab = torch.zeros((n, 2), dtype=torch.int32, device=dev)
-        self._streams = torch.zeros((n, 2), dtype=torch.int64, device=dev) if self.sample else None
-        self._cu_rows = torch.zeros((n + 1,), dtype=torch.int32, device=dev) if self.sample else None
-        self._tick_state(n, 2)
-        self._capture()
-
     # -- capture -----------------------------------------------------------------------------------------------------------------
     def _check_route(self):
-        why = self._refusal(self.n * self.T)
+        why = self._refusal(self.z.numel())
         if why is not None:
-            raise _lib.PwvError('GraphedStream: a flow of a %d x %d push is not one persistent streaming launch: %s' % (self.n, self.T, why))
+            raise _lib.PwvError('%s: %s: %s' % (type(self).__name__, self._not_one_launch(), why))
 
-    def _tick_args(self) -> _lib.StreamTickArgs:
-        st, ta = self.stream, _lib.StreamTickArgs()
+    def _tick_args(self):
+        st, ta = self.stream, self.ARGS()
         ta.sess, ta.kept, ta.entries, ta.mel = st._sess.data_ptr(), st._kept.data_ptr(), self._entries.data_ptr(), self.mel.data_ptr()
-        ta.n_slots, ta.N, ta.frames, ta.n_mels, ta.T = st.n_slots, self.n, self.frames, st.n_mels, self.T
+        ta.n_slots, ta.N, ta.n_mels = st.n_slots, self._n, st.n_mels
         ta.slot_tab, ta.chunk = self._tab.data_ptr(), self._chunk.data_ptr()
-        if self.sample:
-            ta.streams, ta.cu_rows = self._streams.data_ptr(), self._cu_rows.data_ptr()
+        for name in ('streams', 'cu_rows', 'cu_frames'):
+            if getattr(self, '_' + name) is not None:
+                setattr(ta, name, getattr(self, '_' + name).data_ptr())
         ta.words, ta.counters = self._words.addr, self._counters.data_ptr()
+        self._shape_args(ta)
         return ta
 
     def _enqueue(self):
-        """The tick the graph holds (only enqueues): begin, sampler, the push's own launches, commit."""
+        """The tick the graph holds (only enqueues): begin, sampler, unit map (a packed push), the push's own launches, commit."""
         st, lib, ta = self.stream, _lib.lib(), self._tick_args()
-        _lib.check(lib.pwv_stream_tick_begin(ctypes.byref(ta), engine._stream()), 'pwv_stream_tick_begin')
+        _lib.check(getattr(lib, self.ENTRY + '_begin')(ctypes.byref(ta), engine._stream()), self.ENTRY + '_begin')
         if self.sample:
-            engine.logistic_noise_packed_op(self._cu_rows, self._streams, self.n * self.T, out=self.z.view(self.n * self.T, 1))
-        out = engine.verified_call(lambda prec: st._enqueue(prec or self.model.precision, self._chunk, self.z, self._tab, self.T), verify=False)
-        _lib.check(lib.pwv_stream_tick_commit(ctypes.byref(ta), engine._stream()), 'pwv_stream_tick_commit')
+            engine.logistic_noise_packed_op(self._cu_rows, self._streams, self.z.numel(), out=self.z.view(-1, 1))
+        if self.PACKED:
+            self._geom.build_unit_map()
+        out = engine.verified_call(lambda prec: st._enqueue(prec or self.model.precision, *self._push_args()), verify=False)
+        _lib.check(getattr(lib, self.ENTRY + '_commit')(ctypes.byref(ta), engine._stream()), self.ENTRY + '_commit')
         return out
 
-    def _write_entries(self, k: int, called, live: int):
-        """The tick's entry table through pinned staging `k`: the called slots with `live`, then fillers -- other slots of the stream,
-        running ones first -- with live = 0."""
-        others = self._fillers(called, self.n - len(called))
-        # (the key holds the live flag of EVERY entry: the same slots in the same order with another number of called ones is another table)
-        table = (tuple(called) + tuple(others), (live,) * len(called) + (0,) * len(others))
-        if table == self._entries_dev:
-            return others                         # (the device table holds these entries already: the previous tick's)
-        buf = self._entries_host[k].numpy()
-        buf[:, 0] = table[0]
-        buf[:, 1] = table[1]
-        self._entries.copy_(self._entries_host[k], non_blocking=True)
-        self._entries_dev = table
+    def _write_entries(self, k: int, called, *columns):
+        """The tick's entry table through pinned staging `k`: {slot, live[, one int of every one of `columns`], 0 ...} -- the called slots
+        with live = 1, then fillers -- other slots of the stream, running ones first -- with live = 0.  Returns the fillers' slots."""
+        others = self._fillers(called, self._entries.shape[0] - len(called))
+        # (the key is the whole table, live flags included: the same slots [and frames] with another number of called sessions differ in them)
+        table = (tuple(called) + tuple(others), (1,) * len(called) + (0,) * len(others)) + tuple(tuple(c) for c in columns)
+        if table != self._entries_dev:          # (else the device table holds these entries already: the previous tick's)
+            buf = self._entries_host[k].numpy()
+            buf[:] = 0
+            for c, column in enumerate(table):
+                buf[:, c] = column
+            self._entries.copy_(self._entries_host[k], non_blocking=True)
+            self._entries_dev = table
         return others
 
     def _before_capture(self):
         self._check_route()
         # warm up and capture on an all-filler table: no session is touched, any entries replay the same launches
-        self._sync_rows(0, [], self._write_entries(0, [], 0))
+        self._sync_rows(0, [], self._write_entries(0, [], *self._capture_columns()))
         self.mel.zero_()
         self.z.zero_()
         self._dirty_rows = 0
         self._log_mark = len(engine.EVENT_LOG)
 
+    @staticmethod
+    def _one_launch(e) -> bool:
+        """An event of the log: a whole-flow persistent launch of one workgroup set, streaming."""
+        return e[0] == 'persist' and e[8] == 1 and e[5] == 1 and e[6] == 1
+
     def _after_warmup(self):
         log = engine.EVENT_LOG[self._log_mark:]
-        odd = [e[0] for e in log if not (e[0] == 'persist' and e[8] == 1)]
-        flows = int(hp.model.n_iaf)
-        if odd or len(log) != self._warmup * flows or not all(e[5] == 1 and e[6] == 1 for e in log):
-            raise _lib.PwvError('GraphedStream: a flow of a %d x %d push is not one persistent streaming launch (the warm-up enqueued %s)'
-                                % (self.n, self.T, odd or '%d persistent launches for %d flows' % (len(log) // self._warmup, flows)))
-        engine.verify_enqueued('the warm-up of a streaming graph')
+        if not self._good_warmup(log, self._warmup * int(hp.model.n_iaf)):
+            raise _lib.PwvError('%s: %s (the warm-up enqueued %s)' % (type(self).__name__, self._not_one_launch(),
+                                                                      [e[0] if e[0] != 'stream_ragged' else e[:5] for e in log]))
+        engine.verify_enqueued('the warm-up of a graphed streaming tick')
         self._counters.zero_()
         self._seen = [0, 0]
 
     # -- ticks -------------------------------------------------------------------------------------------------------------------
     def tick(self, mel, slots, z=None):
-        """Give the RUNNING sessions in `slots` (1 <= k <= n distinct slots) their next `frames` mel frames, mel [k, frames, n_mels];
-        returns their next samples [k, T, 1] as views of the graph's output buffer, valid until the next tick (a caller that pipelines
-        ticks copies them out on the stream).  sample=False: z [k, T, 1] is the noise; sample=True: every slot draws from its own
-        counter stream (a slot without a seed gets one from the OS, as in push).  Enqueue-only; before tick j is enqueued the host
-        waits for the end of tick j - depth.  A tick of another frame count, or one while the persistent launches are suspended,
-        settles what is in flight (verify()) and runs the eager push(verify=False) instead."""
+        """Give the distinct RUNNING sessions in `slots` their next frames `mel` (the subclass says in which form) and return their next
+        samples as views of the graph's output buffer, valid until the next tick (a caller that pipelines ticks copies them out on the
+        stream).  sample=False: z is the noise; sample=True: every slot draws from its own counter stream (a slot without a seed gets
+        one from the OS, as in push).  Enqueue-only; before tick j is enqueued the host waits for the end of tick j - depth.  A tick
+        that does not fit the capture, or one while the persistent launches are suspended, settles what is in flight (verify()) and
+        runs the eager push instead (eager_calls)."""
         st = self.stream
         slots = [st._slot(v) for v in slots]
-        k = len(slots)
-        if k == 0 or len(set(slots)) != k:
+        if not slots or len(set(slots)) != len(slots):
             raise ValueError('slots must be a non-empty list of distinct slots, got %r' % (slots,))
-        mel = engine._require_cuda_f32(mel, 'mel')
-        if mel.dim() != 3 or mel.shape[0] != k or mel.shape[1] < 1 or mel.shape[2] != st.n_mels:
-            raise ValueError('mel must be [%d, f >= 1, %d], got %s' % (k, st.n_mels, tuple(mel.shape)))
+        mel, frames = self._check_mel(mel, len(slots))          # (frames: every session's count)
         for s in slots:
             if not st._running[s]:
-                raise ValueError('slot %d is fresh: a session starts with the eager one-frame push (push(mel[:, :1], slots=[%d]) keeps the '
-                                 'frame and marks the slot running) and takes graphed ticks from then on' % (s, s))
+                raise ValueError('slot %d is fresh: a session starts with the eager one-frame push (%s keeps the frame and marks the '
+                                 'slot running) and takes graphed ticks from then on' % (s, self.FIRST_PUSH % s))
         if self.sample and z is not None:
             raise ValueError('this graph samples its own noise (sample=True): z is not taken')
         if not self.sample:
-            if z is None:
-                raise ValueError('this graph has no sampler (sample=False): z [%d, %d, 1] is required' % (k, mel.shape[1] * st.hop))
-            z = engine._require_cuda_f32(z, 'z')
-            if tuple(z.shape) != (k, mel.shape[1] * st.hop, 1):
-                raise ValueError('z must be [%d, %d, 1], got %s' % (k, mel.shape[1] * st.hop, tuple(z.shape)))
-        if not self._ready() or mel.shape[1] != self.frames or k > self.n:
+            z = self._check_z(z, [f * st.hop for f in frames])
+        columns = self._columns(frames)          # (None: the tick does not fit the capture)
+        if not self._ready() or columns is None:
             self._settle()
             self.eager_calls += 1
-            return st.push(mel, slots=slots, z=z, verify=False)
+            return self._eager(mel, slots=slots, z=z, verify=False)
         j = self._begin_tick()
-        self._sync_rows(j, slots, self._write_entries(j, slots, 1))
+        self._sync_rows(j, slots, self._write_entries(j, slots, *columns))
+        used, out = self._copy_in(mel, z, frames)          # (used: the leading rows of self.mel the tick's sessions take)
+        if self._dirty_rows > used:          # (a filler runs on zeros: nothing of a previous tick's session may reach the range guard)
+            per = self.z.shape[0] // self.mel.shape[0]
+            self.mel[used:self._dirty_rows].zero_()
+            self.z[used * per:self._dirty_rows * per].zero_()
+        self._dirty_rows = used
+        self._replay(slots)
+        return out
+
+
+class GraphedStream(_TickGraph):
+    """The UNIFORM tick -- `n` running sessions x `frames` mel frames, T = frames * hop samples each -- as one graph (_TickGraph;
+    StreamingVocoder.graphed): the [n, T] streaming persistent launch of push.
+
+    tick(mel [k, frames, n_mels], slots, z=None) replays it for 1 <= k <= n distinct RUNNING slots and only enqueues; the other n - k
+    entries are fillers.  It returns the sessions' next samples [k, T, 1]; sample=False: z [k, T, 1] is the noise.  Ticks may follow
+    each other with no synchronisation: the commit kernel flips a session only if both sticky words are clean, and the words are
+    sticky, so the committed ticks are a PREFIX of the enqueued ones.  verify() waits, makes the host's view of the sessions equal to
+    the device table and returns the number of ticks committed; it raises PwvRangeError / PwvPersistError (with that number as
+    `.committed`) where a tick was refused: push the failed chunk again with the eager push and carry on.  While ticks are in flight
+    the stream is pending: push / reset / state refuse until verify().  A tick of another frame count runs push(verify=False).
+
+    Refused at construction (PwvError) wherever a flow of an [n, T] push is not the whole-flow persistent streaming launch."""
+
+    ARGS, ENTRY, ENTRY_INTS = _lib.StreamTickArgs, 'pwv_stream_tick', 2
+    FIRST_PUSH = 'push(mel[:, :1], slots=[%d])'
+
+    def __init__(self, stream, n: int, frames: int, sample: bool = True, depth: int = 4, warmup: int = 2):
+        super().__init__(stream, sample, depth, warmup)
+        st, dev = stream, self.device
+        self.n, self.frames = n, frames = int(n), int(frames)
+        if n < 1 or frames < 1:
+            raise ValueError('a graphed tick needs n >= 1 sessions and frames >= 1, got %r / %r' % (n, frames))
+        if n > st.n_slots:
+            raise ValueError('a graph for %d sessions needs a stream of at least %d slots (this one has %d): the entries a tick does not '
+                             'use are fillers on OTHER slots of the stream' % (n, n, st.n_slots))
+        self.T = frames * st.hop
+        self.mel = torch.zeros((n, frames, st.n_mels), dtype=torch.float32, device=dev)
+        self.z = torch.zeros((n, self.T, 1), dtype=torch.float32, device=dev)
+        self._chunk = torch.zeros((n, frames + 1, st.n_mels), dtype=torch.float32, device=dev)
+        self._start(n)
+
+    def _not_one_launch(self):
+        return 'a flow of a %d x %d push is not one persistent streaming launch' % (self.n, self.T)
+
+    def _shape_args(self, ta):
+        ta.frames, ta.T = self.frames, self.T
+
+    def _push_args(self):
+        return self._chunk, self.z, self._tab, self.T
+
+    def _capture_columns(self):
+        return ()
+
+    def _good_warmup(self, log, launches):
+        return len(log) == launches and all(self._one_launch(e) for e in log)
+
+    def _check_mel(self, mel, k):
+        mel = engine._require_cuda_f32(mel, 'mel')
+        if mel.dim() != 3 or mel.shape[0] != k or mel.shape[1] < 1 or mel.shape[2] != self.stream.n_mels:
+            raise ValueError('mel must be [%d, f >= 1, %d], got %s' % (k, self.stream.n_mels, tuple(mel.shape)))
+        return mel, [int(mel.shape[1])] * k
+
+    def _check_z(self, z, samples):
+        if z is None:
+            raise ValueError('this graph has no sampler (sample=False): z [%d, %d, 1] is required' % (len(samples), samples[0]))
+        z = engine._require_cuda_f32(z, 'z')
+        if tuple(z.shape) != (len(samples), samples[0], 1):
+            raise ValueError('z must be [%d, %d, 1], got %s' % (len(samples), samples[0], tuple(z.shape)))
+        return z
+
+    def _columns(self, frames):
+        return () if frames[0] == self.frames and len(frames) <= self.n else None
+
+    def _eager(self, *args, **kw):
+        return self.stream.push(*args, **kw)
+
+    def _copy_in(self, mel, z, frames):
+        k = len(frames)
         self.mel[:k].copy_(mel, non_blocking=True)
         if z is not None:
             self.z[:k].copy_(z, non_blocking=True)
-        if self._dirty_rows > k:
-            self.mel[k:self._dirty_rows].zero_()
-            self.z[k:self._dirty_rows].zero_()
-        self._dirty_rows = k
-        self._replay(slots)
-        return self.out[:k]
+        return k, self.out[:k]
 
 
 class GraphedRaggedStream(_TickGraph):
-    """A RAGGED tick of a StreamingVocoder -- up to `slots` running sessions, every one its own number of frames, `rows` samples in all --
-    captured into ONE HIP graph with the commit on the device (DESIGN.md section 9, "Graph replay of a ragged tick";
-    StreamingVocoder.graphed_varlen):
-
-        ragged begin kernel (session table + frame counts -> slot table, noise streams, cu_rows, cu_frames, the packed chunk)  ->
-        packed sampler (sample=True)  ->  pwv_varlen_unit_map  ->  StreamingVocoder._enqueue with a geometry on the static tables
-        (prologue, packed carry, one packed persistent streaming launch per flow)  ->  ragged commit kernel
+    """The RAGGED tick -- up to `slots` running sessions, every one its own number of frames, `rows` samples in all -- as one graph
+    (_TickGraph; StreamingVocoder.graphed_varlen): the packed persistent streaming launch of push_varlen.
 
     The packed persistent launch is length-agnostic (GraphedPackedVocoder): the layout reaches the kernels only through cu_rows,
     cu_frames and the unit map in device memory, and here the begin kernel writes them from the tick's `entries` = {slot, live, frames}.
-    tick(mels, slots, z=None) replays the graph for 1 <= k <= `slots` distinct RUNNING sessions whose frames fit (fits()): k < slots adds
-    slots - k FILLERS (live = 0, zero mel, on other slots of the stream), the first slots - k - 1 of min_frames frames, the last one the
-    frames that are left; with k = slots the frames fill rows / hop exactly.  A tick that does not fit runs push_varlen(verify=False).
-    Ticks follow each other with no synchronisation, committed as a prefix (GraphedStream); verify() as there.
+    tick(mels, slots, z=None), mels[i] [f_i, n_mels], replays the graph for 1 <= k <= `slots` distinct RUNNING sessions whose frames fit
+    (fits()): k < slots adds slots - k fillers on zero mel, the first slots - k - 1 of min_frames frames, the last one the frames that are
+    left; with k = slots the frames fill rows / hop exactly.  It returns a RaggedOutput of the sessions' next samples [f_i * hop, 1];
+    sample=False: z is the noise, the packed [sum f_i * hop, 1] or a list of [f_i * hop, 1].  A tick that does not fit runs
+    push_varlen(verify=False).  Ticks in flight, the committed prefix and verify() are GraphedStream's.
 
     Refused at construction (PwvError) wherever a flow of such a push is not one packed streaming persistent launch."""
 
+    ARGS, ENTRY, ENTRY_INTS = _lib.StreamTickRaggedArgs, 'pwv_stream_tick_ragged', 4
+    FIRST_PUSH = 'push_varlen([mel[:1]], slots=[%d])'
+    PACKED = True
+
     def __init__(self, stream, slots: int, rows: int, sample: bool = True, depth: int = 4, warmup: int = 2):
-        st = self.stream = stream
-        super().__init__(st.model, st.device, max(1, int(warmup)))
+        super().__init__(stream, sample, depth, warmup)
+        st, dev = stream, self.device
         self.hop = hop = st.hop
         self.filler = packed_filler_rows(hop)
         self.min_frames = self.filler // hop
-        self.slots, self.rows = int(slots), int(rows)
-        if self.slots < 1:
+        self.slots, self.rows = n, rows = int(slots), int(rows)
+        if n < 1:
             raise ValueError('a graphed ragged tick needs slots >= 1, got %r' % (slots,))
-        if self.rows % hop or self.rows < self.slots * self.filler:
+        if rows % hop or rows < n * self.filler:
             raise _lib.PwvError('GraphedRaggedStream: a capacity of %d slots needs rows a multiple of hop_length (%d) and at least %d '
-                                '(%d frames per session), got %d' % (self.slots, hop, self.slots * self.filler, self.min_frames, self.rows))
-        if self.slots > st.n_slots:
+                                '(%d frames per session), got %d' % (n, hop, n * self.filler, self.min_frames, rows))
+        if n > st.n_slots:
             raise _lib.PwvError('GraphedRaggedStream: a capacity of %d slots needs a stream of at least %d slots (this one has %d): the '
-                                'entries a tick does not use are fillers on OTHER slots of the stream' % (self.slots, self.slots, st.n_slots))
-        self.in_frames = self.rows // hop
-        self.sample, self.depth = bool(sample), max(1, int(depth))
-        self._check_route()
-        dev, n = self.device, self.slots
+                                'entries a tick does not use are fillers on OTHER slots of the stream' % (n, n, st.n_slots))
+        self.in_frames = rows // hop
         self.mel = torch.zeros((self.in_frames, st.n_mels), dtype=torch.float32, device=dev)
-        self.z = torch.zeros((self.rows, 1), dtype=torch.float32, device=dev)
+        self.z = torch.zeros((rows, 1), dtype=torch.float32, device=dev)
         self._chunk = torch.zeros((self.in_frames + n, st.n_mels), dtype=torch.float32, device=dev)
-        self._tab = torch.zeros((n, 2), dtype=torch.int32, device=dev)
-        self._streams = torch.zeros((n, 2), dtype=torch.int64, device=dev) if self.sample else None
-        self._cu_rows = torch.zeros((n + 1,), dtype=torch.int32, device=dev)
-        self._cu_frames = torch.zeros((n + 1,), dtype=torch.int32, device=dev)
-        self._unit_map = torch.zeros(((self.rows + 31) // 32 * _lib.VARLEN_REC_INTS,), dtype=torch.int32, device=dev)
-        self._tick_state(n, 4)
-        self._capture()
+        self._start(n)
 
-    # -- layout ------------------------------------------------------------------------------------------------------------------
     def _layout(self, frames):
-        """The frame counts of all `slots` entries of a tick (GraphedPackedVocoder._layout, in frames): the called sessions', then the
-        fillers'; ValueError if they do not fit."""
-        frames = [int(v) for v in frames]
-        k = len(frames)
-        if not 1 <= k <= self.slots:
-            raise ValueError('%d sessions for %d slots' % (k, self.slots))
-        for v in frames:
-            if v < self.min_frames:
-                raise ValueError('every session of a graphed ragged tick needs at least %d frames (%d samples), got %d'
-                                 % (self.min_frames, self.filler, v))
-        fill, left = self.slots - k, self.in_frames - sum(frames)
-        if fill == 0:
-            if left != 0:
-                raise ValueError('%d sessions in all %d slots must fill the %d frames exactly, they hold %d' % (k, k, self.in_frames, self.in_frames - left))
-            return frames
-        if left < fill * self.min_frames:
-            raise ValueError('%d frames and %d filler sessions of at least %d frames exceed the %d frames'
-                             % (self.in_frames - left, fill, self.min_frames, self.in_frames))
-        return frames + [self.min_frames] * (fill - 1) + [left - (fill - 1) * self.min_frames]
+        """The frame counts of all `slots` entries of a tick: the called sessions', then the fillers'; ValueError if they do not fit."""
+        return filler_layout(frames, self.slots, self.in_frames, self.min_frames, ('session', 'frames'))
 
     def fits(self, frames) -> bool:
         """Can sessions with these frame counts be advanced by one replay of this capture?"""
-        try:
-            self._layout(frames)
-        except ValueError:
-            return False
-        return True
+        return _fits(self._layout, frames)
 
-    # -- capture -----------------------------------------------------------------------------------------------------------------
-    def _check_route(self):
-        why = self._refusal(self.rows)
-        if why is not None:
-            raise _lib.PwvError('GraphedRaggedStream: a flow of a ragged push of %d rows is not one packed persistent streaming launch: %s'
-                                % (self.rows, why))
+    def _not_one_launch(self):
+        return 'a flow of a ragged push of %d slots / %d rows is not one packed persistent streaming launch' % (self.slots, self.rows)
 
-    def _tick_args(self) -> _lib.StreamTickRaggedArgs:
-        st, ta = self.stream, _lib.StreamTickRaggedArgs()
-        ta.sess, ta.kept, ta.entries, ta.mel = st._sess.data_ptr(), st._kept.data_ptr(), self._entries.data_ptr(), self.mel.data_ptr()
-        ta.n_slots, ta.N, ta.in_frames, ta.n_mels = st.n_slots, self.slots, self.in_frames, st.n_mels
-        ta.hop, ta.min_frames = self.hop, self.min_frames
-        ta.slot_tab, ta.chunk = self._tab.data_ptr(), self._chunk.data_ptr()
-        ta.cu_rows, ta.cu_frames = self._cu_rows.data_ptr(), self._cu_frames.data_ptr()
-        if self.sample:
-            ta.streams = self._streams.data_ptr()
-        ta.words, ta.counters = self._words.addr, self._counters.data_ptr()
-        return ta
+    def _shape_args(self, ta):
+        ta.in_frames, ta.hop, ta.min_frames = self.in_frames, self.hop, self.min_frames
 
-    def _enqueue(self):
-        """The tick the graph holds (only enqueues): ragged begin, sampler, unit map, the push's own launches, ragged commit."""
-        st, lib, ta = self.stream, _lib.lib(), self._tick_args()
-        _lib.check(lib.pwv_stream_tick_ragged_begin(ctypes.byref(ta), engine._stream()), 'pwv_stream_tick_ragged_begin')
-        if self.sample:
-            engine.logistic_noise_packed_op(self._cu_rows, self._streams, self.rows, out=self.z)
-        self._geom.build_unit_map()
-        out = engine.verified_call(lambda prec: st._enqueue(prec or self.model.precision, self._chunk[None], self.z, self._tab, 0, self._geom),
-                                   verify=False)
-        _lib.check(lib.pwv_stream_tick_ragged_commit(ctypes.byref(ta), engine._stream()), 'pwv_stream_tick_ragged_commit')
-        return out
+    def _push_args(self):
+        return self._chunk[None], self.z, self._tab, 0, self._geom
 
-    def _write_entries(self, k: int, called, layout):
-        """The tick's entry table {slot, live, frames, 0} through pinned staging `k`: the called slots (live = 1) with their frames, then
-        the fillers -- other slots of the stream, running ones first -- with live = 0 and the rest of `layout`."""
-        others = self._fillers(called, self.slots - len(called))
-        # (the key is the whole table, live flags included: the same slots and frames with another number of called sessions differ in them)
-        table = (tuple(called) + tuple(others), (1,) * len(called) + (0,) * len(others), tuple(layout))
-        if table == self._entries_dev:
-            return others                         # (the device table holds these entries already: the previous tick's)
-        buf = self._entries_host[k].numpy()
-        buf[:, 0] = table[0]
-        buf[:, 1] = table[1]
-        buf[:, 2] = table[2]
-        buf[:, 3] = 0
-        self._entries.copy_(self._entries_host[k], non_blocking=True)
-        self._entries_dev = table
-        return others
-
-    def _before_capture(self):
-        self._check_route()
-        # warm up and capture on an all-filler table: no session is touched, any entries replay the same launches.  The layout holds a
-        # session of min_frames frames wherever one is admissible (slots >= 2), so StreamingVocoder._enqueue, which sizes nothing else
-        # on the host lengths, puts the packed carry launch into the graph whenever a tick can need it
+    def _capture_columns(self):
+        # the layout holds a session of min_frames frames wherever one is admissible (slots >= 2), so StreamingVocoder._enqueue, which
+        # sizes nothing else on the host lengths, puts the packed carry launch into the graph whenever a tick can need it
         layout = [self.min_frames] * (self.slots - 1) + [self.in_frames - (self.slots - 1) * self.min_frames]
-        self._sync_rows(0, [], self._write_entries(0, [], layout))
         self._geom = engine.VarlenGeometry([f * self.hop for f in layout], self.hop, self.device,
                                            tables=(self._cu_rows, self._cu_frames, self._unit_map))
-        self.mel.zero_()
-        self.z.zero_()
-        self._dirty_rows = 0
-        self._log_mark = len(engine.EVENT_LOG)
+        return (layout,)
 
-    def _after_warmup(self):
-        log = engine.EVENT_LOG[self._log_mark:]
-        flows = int(hp.model.n_iaf)
-        good = len(log) == 2 * flows * self._warmup and all(
-            a[0] == 'stream_ragged' and a[3] == 'packed' and b[0] == 'persist' and b[8] == 1 and b[5] == 1 and b[6] == 1
-            for a, b in zip(log[0::2], log[1::2]))
-        if not good:
-            raise _lib.PwvError('GraphedRaggedStream: a flow of a ragged push of %d slots / %d rows is not one packed persistent streaming '
-                                'launch (the warm-up enqueued %s)' % (self.slots, self.rows, [e[0] if e[0] != 'stream_ragged' else e[:5] for e in log]))
-        engine.verify_enqueued('the warm-up of a ragged streaming graph')
-        self._counters.zero_()
-        self._seen = [0, 0]
+    def _good_warmup(self, log, launches):
+        return len(log) == 2 * launches and all(a[0] == 'stream_ragged' and a[3] == 'packed' and self._one_launch(b)
+                                                for a, b in zip(log[0::2], log[1::2]))
 
-    # -- ticks -------------------------------------------------------------------------------------------------------------------
-    def tick(self, mels, slots, z=None):
-        """Give the RUNNING sessions in `slots` (1 <= k distinct slots) their next frames, mels[i] [f_i, n_mels]; returns a RaggedOutput of
-        their next samples [f_i * hop, 1], views of the graph's output buffer that are valid until the next tick (a caller that
-        pipelines ticks copies them out on the stream).  sample=False: z is the noise, the packed [sum f_i * hop, 1] or a list of
-        [f_i * hop, 1]; sample=True: every slot draws from its own counter stream.  Enqueue-only; before tick j is enqueued the host
-        waits for the end of tick j - depth.  A tick that does not fit the capture (fits()), or one while the persistent launches are
-        suspended, settles what is in flight (verify()) and runs the eager push_varlen(verify=False) instead."""
-        st = self.stream
-        if not isinstance(mels, (list, tuple)) or not mels:
-            raise ValueError('mels must be a non-empty list of [f, n_mels] tensors')
-        slots = [st._slot(v) for v in slots]
-        k = len(slots)
-        if k != len(mels) or len(set(slots)) != k:
-            raise ValueError('slots must be distinct, one per mel (%d mels), got %r' % (len(mels), slots))
+    def _check_mel(self, mels, k):
+        if not isinstance(mels, (list, tuple)) or len(mels) != k:
+            raise ValueError('mels must be a list of [f, n_mels] tensors, one per slot (%d slots)' % k)
         mels = [engine._require_cuda_f32(m, 'mels[%d]' % i) for i, m in enumerate(mels)]
         for i, m in enumerate(mels):
-            if m.dim() != 2 or m.shape[0] < 1 or m.shape[1] != st.n_mels:
-                raise ValueError('mels[%d] must be [f >= 1, %d], got %s' % (i, st.n_mels, tuple(m.shape)))
-        for s in slots:
-            if not st._running[s]:
-                raise ValueError('slot %d is fresh: a session starts with the eager one-frame push (push_varlen([mel[:1]], slots=[%d]) keeps '
-                                 'the frame and marks the slot running) and takes graphed ticks from then on' % (s, s))
-        frames = [int(m.shape[0]) for m in mels]
-        samples = [f * self.hop for f in frames]
-        if self.sample and z is not None:
-            raise ValueError('this graph samples its own noise (sample=True): z is not taken')
-        if not self.sample:
-            if z is None:
-                raise ValueError('this graph has no sampler (sample=False): z, the packed [%d, 1] or one [f_i * %d, 1] per session, is required'
-                                 % (sum(samples), self.hop))
-            if isinstance(z, (list, tuple)):
-                if len(z) != k or any(tuple(getattr(v, 'shape', ())) != (t, 1) for v, t in zip(z, samples)):
-                    raise ValueError('z must hold one [f_i * %d, 1] piece per session' % self.hop)
-                z = [engine._require_cuda_f32(v, 'z[%d]' % i) for i, v in enumerate(z)]
-            else:
-                z = engine._require_cuda_f32(z, 'z')
-                if tuple(z.shape) != (sum(samples), 1):
-                    raise ValueError('z must be the packed [%d, 1], got %s' % (sum(samples), tuple(z.shape)))
-        if not self._ready() or not self.fits(frames):
-            self._settle()
-            self.eager_calls += 1
-            return st.push_varlen(mels, slots=slots, z=z, verify=False)
-        j = self._begin_tick()
-        layout = self._layout(frames)
-        self._sync_rows(j, slots, self._write_entries(j, slots, layout))
+            if m.dim() != 2 or m.shape[0] < 1 or m.shape[1] != self.stream.n_mels:
+                raise ValueError('mels[%d] must be [f >= 1, %d], got %s' % (i, self.stream.n_mels, tuple(m.shape)))
+        return mels, [int(m.shape[0]) for m in mels]
+
+    def _check_z(self, z, samples):
+        if z is None:
+            raise ValueError('this graph has no sampler (sample=False): z, the packed [%d, 1] or one [f_i * %d, 1] per session, is required'
+                             % (sum(samples), self.hop))
+        if isinstance(z, (list, tuple)):
+            if len(z) != len(samples) or any(tuple(getattr(v, 'shape', ())) != (t, 1) for v, t in zip(z, samples)):
+                raise ValueError('z must hold one [f_i * %d, 1] piece per session' % self.hop)
+            return [engine._require_cuda_f32(v, 'z[%d]' % i) for i, v in enumerate(z)]
+        z = engine._require_cuda_f32(z, 'z')
+        if tuple(z.shape) != (sum(samples), 1):
+            raise ValueError('z must be the packed [%d, 1], got %s' % (sum(samples), tuple(z.shape)))
+        return z
+
+    def _columns(self, frames):
+        try:
+            return (self._layout(frames),)
+        except ValueError:
+            return None
+
+    def _eager(self, *args, **kw):
+        return self.stream.push_varlen(*args, **kw)
+
+    def _copy_in(self, mels, z, frames):
         real = sum(frames)
         torch.cat(mels, out=self.mel[:real])
         if isinstance(z, list):
             torch.cat(z, out=self.z[:real * self.hop])
         elif z is not None:
             self.z[:real * self.hop].copy_(z, non_blocking=True)
-        if self._dirty_rows > real:          # (a filler runs on zeros: nothing of a previous tick's session may reach the range guard)
-            self.mel[real:self._dirty_rows].zero_()
-            self.z[real * self.hop:self._dirty_rows * self.hop].zero_()
-        self._dirty_rows = real
-        self._replay(slots)
-        return RaggedOutput(self.out[:real * self.hop], samples)
+        return real, RaggedOutput(self.out[:real * self.hop], [f * self.hop for f in frames])

@@ -105,39 +105,33 @@ def ragged_plan(frames: Sequence[int], fresh: Sequence[bool], hop: int) -> Ragge
     return RaggedPlan(samples, launch, layout.cu_rows_host, layout.cu_frames_host)
 
 
-def tick_begin_tables(sess, kept, entries, mel, hop: int):
-    """(numpy restatement of stream_tick_begin_kernel, csrc/pwv_stream_tick.hip; tests, and the definition of the tables)  From the device
-    session table `sess` (int64 [n_slots, 4] = {generation read, samples emitted, seed bits, 0}), the kept frames `kept` [n_slots, n_mels],
-    the tick's `entries` (int32 [N, 2] = {slot, live}) and its mel [N, f, n_mels]: (slot_tab int32 [N, 2], streams int64 [N, 2] =
-    {seed, emitted}, cu_rows int32 [N + 1], frames float32 [N, f + 1, n_mels]) -- what push builds on the host for the same sessions.
-    `live` plays no part here: a filler reads and writes like any other entry."""
-    sess, kept, mel = np.asarray(sess, np.int64), np.asarray(kept, np.float32), np.asarray(mel, np.float32)
-    entries = np.asarray(entries, np.int32).reshape(-1, 2)
-    n, f = entries.shape[0], mel.shape[1]
-    T = f * int(hop)
-    slots = np.where((entries[:, 0] >= 0) & (entries[:, 0] < sess.shape[0]), entries[:, 0], 0)      # (out of range: a filler of slot 0)
-    g = sess[slots, 0] & 1
-    slot_tab = np.stack([2 * slots + g, 2 * slots + 1 - g], axis=1).astype(np.int32)
-    streams = np.stack([sess[slots, 2], sess[slots, 1]], axis=1).astype(np.int64)
-    cu_rows = (np.arange(n + 1, dtype=np.int64) * T).astype(np.int32)
-    frames = np.concatenate([kept[slots][:, None], mel], axis=1).astype(np.float32)
-    return slot_tab, streams, cu_rows, frames
+def _as_ragged_tick(entries, mel):
+    """A uniform tick as the ragged tick it is: entries {slot, live} x mel [N, f, n_mels] -> entries {slot, live, f, 0}, mel [N * f, n_mels]
+    and min_frames = f (no count needs the clamp; in_frames = N * f)."""
+    entries, mel = np.asarray(entries, np.int32).reshape(-1, 2), np.asarray(mel, np.float32)
+    n, f = mel.shape[:2]
+    wide = np.concatenate([entries, np.full((n, 1), f, np.int32), np.zeros((n, 1), np.int32)], axis=1)
+    return wide, mel.reshape(n * f, mel.shape[2]), f
+
+
+def tick_begin_tables(sess, kept, entries, mel, hop: int, sample: bool = True):
+    """(numpy restatement of stream_tick_begin_kernel, csrc/pwv_stream_tick.hip; tests, and the definition of the tables)  The tables of
+    ragged_tick_begin_tables for the tick's `entries` (int32 [N, 2] = {slot, live}) and its mel [N, f, n_mels], every session f frames:
+    (slot_tab int32 [N, 2], streams int64 [N, 2] = {seed, emitted}, cu_rows int32 [N + 1] = i * f * hop, frames float32 [N, f + 1, n_mels])
+    -- what push builds on the host for the same sessions; there is no cu_frames.  sample=False (the tick has no sampler): streams and
+    cu_rows go together, both None."""
+    wide, flat, f = _as_ragged_tick(entries, mel)
+    slot_tab, streams, cu_rows, _, chunk = ragged_tick_begin_tables(sess, kept, wide, flat, hop, f, sample=sample)
+    return slot_tab, streams, cu_rows if sample else None, chunk.reshape(len(wide), f + 1, flat.shape[1])
 
 
 def tick_commit(sess, kept, entries, mel, T: int, words):
-    """(numpy restatement of stream_tick_commit_kernel)  (sess, kept, committed) after the tick's last node: with both sticky `words`
-    (give-up, range) zero every LIVE entry's session flips its generation, has emitted T more samples and keeps the chunk's last
-    frame; otherwise -- and for every filler -- nothing changes.  Returns copies."""
-    sess, kept = np.array(sess, np.int64), np.array(kept, np.float32)
-    mel = np.asarray(mel, np.float32)
-    if int(words[0]) != 0 or int(words[1]) != 0:
-        return sess, kept, False
-    for i, (slot, live) in enumerate(np.asarray(entries, np.int32).reshape(-1, 2)):
-        if live and 0 <= slot < sess.shape[0]:
-            sess[slot, 0] ^= 1
-            sess[slot, 1] += int(T)
-            kept[slot] = mel[i, -1]
-    return sess, kept, True
+    """(numpy restatement of stream_tick_commit_kernel)  ragged_tick_commit for the uniform tick of T = f * hop samples per session:
+    (sess, kept, committed) after the tick's last node.  Returns copies."""
+    wide, flat, f = _as_ragged_tick(entries, mel)
+    if int(T) % f:
+        raise ValueError('T = %d samples are no whole number of samples for each of %d frames' % (T, f))
+    return ragged_tick_commit(sess, kept, wide, flat, int(T) // f, f, words)
 
 
 def ragged_tick_counts(entries, in_frames: int, min_frames: int):
@@ -156,13 +150,14 @@ def ragged_tick_counts(entries, in_frames: int, min_frames: int):
     return cu
 
 
-def ragged_tick_begin_tables(sess, kept, entries, mel, hop: int, min_frames: int, touched: Optional[dict] = None):
+def ragged_tick_begin_tables(sess, kept, entries, mel, hop: int, min_frames: int, touched: Optional[dict] = None, sample: bool = True):
     """(numpy restatement of stream_tick_ragged_begin_kernel; tests, and the definition of the tables)  From the device session table
     `sess` (int64 [n_slots, 4]), the kept frames `kept` [n_slots, n_mels], the tick's `entries` (int32 [N, 4] = {slot, live, frames, 0})
     and its mel [in_frames, n_mels] (the sessions' new frames in entry order): (slot_tab int32 [N, 2], streams int64 [N, 2] = {seed,
     emitted}, cu_rows int32 [N + 1], cu_frames int32 [N + 1], chunk float32 [in_frames + N, n_mels]) -- what push_varlen builds on the
-    host for the same running sessions.  `live` plays no part here.  `touched` (tests): a dict that receives, per array name, every
-    index the restatement reads or writes."""
+    host for the same running sessions.  `live` plays no part here: a filler reads and writes like any other entry.  sample=False (the
+    tick has no sampler, `streams` NULL): streams is None.  `touched` (tests): a dict that receives, per array name, every index the
+    restatement reads or writes."""
     sess, kept, mel = np.asarray(sess, np.int64), np.asarray(kept, np.float32), np.asarray(mel, np.float32)
     entries = np.asarray(entries, np.int32).reshape(-1, 4)
     n, in_frames = entries.shape[0], mel.shape[0]
@@ -170,7 +165,7 @@ def ragged_tick_begin_tables(sess, kept, entries, mel, hop: int, min_frames: int
     slots = np.where((entries[:, 0] >= 0) & (entries[:, 0] < sess.shape[0]), entries[:, 0], 0)      # (out of range: a filler of slot 0)
     g = sess[slots, 0] & 1
     slot_tab = np.stack([2 * slots + g, 2 * slots + 1 - g], axis=1).astype(np.int32)
-    streams = np.stack([sess[slots, 2], sess[slots, 1]], axis=1).astype(np.int64)
+    streams = np.stack([sess[slots, 2], sess[slots, 1]], axis=1).astype(np.int64) if sample else None
     cu_rows = (cu * int(hop)).astype(np.int32)
     cu_frames = (cu + np.arange(n + 1)).astype(np.int32)
     chunk = np.zeros((in_frames + n, mel.shape[1]), np.float32)

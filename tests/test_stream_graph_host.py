@@ -4,7 +4,6 @@ against what StreamingVocoder.push / _commit do on the host today, and the compi
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -18,6 +17,7 @@ def test_abi_symbols_struct_and_version(built_lib, tmp_path):
     """Both symbols are declared in the header, listed in EXPORTED_SYMBOLS and exported by the built library; the C compiler's size and
     offsets of pwv_stream_tick_args equal the ctypes mirror's; no existing struct changed, so the version is still 301."""
     from pwv_amd import _lib
+    from tests.util import c_struct_probe
     header = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', 'pwv_hip.h')).read(), flags=re.S)
     raw = ctypes.CDLL(_lib.LIB_PATH)
     for name in SYMBOLS:
@@ -26,14 +26,7 @@ def test_abi_symbols_struct_and_version(built_lib, tmp_path):
     assert os.path.join(CSRC, 'pwv_stream_tick.hip') in _lib.CSRC
     fields = [f[0] for f in _lib.StreamTickArgs._fields_]
     assert fields[0] == 'struct_size'
-    probe = ['sizeof(pwv_stream_tick_args)'] + ['offsetof(pwv_stream_tick_args, %s)' % f for f in fields]
-    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "pwv_hip.h"\nint main(void){ printf("%s %%d\\n", %s, PWV_HIP_VERSION); return 0; }\n'
-           % (' '.join(['%zu'] * len(probe)), ', '.join(probe)))
-    c, exe = str(tmp_path / 't.c'), str(tmp_path / 't')
-    with open(c, 'w') as f:
-        f.write(src)
-    subprocess.check_call(['gcc', '-std=c99', '-Wall', '-Wextra', '-pedantic', '-Werror', '-I' + os.path.join(ROOT, 'include'), c, '-o', exe])
-    got = [int(x) for x in subprocess.check_output([exe]).decode().split()]
+    got = c_struct_probe('pwv_stream_tick_args', fields, tmp_path)
     S = _lib.StreamTickArgs
     assert got == [ctypes.sizeof(S)] + [getattr(S, f).offset for f in fields] + [301]
     assert S().struct_size == ctypes.sizeof(S)
@@ -170,16 +163,58 @@ def test_ticks_chain_like_pushes():
     assert np.array_equal(sess, host.sess()) and np.array_equal(kept, host.kept)
 
 
+def test_a_uniform_tick_is_a_ragged_tick_with_equal_counts():
+    """Random (n_slots, slots, f, hop, n_mels) with live entries and fillers mixed: tick_begin_tables / tick_commit give exactly -- integer
+    tables and copied floats, dtype included -- what ragged_tick_begin_tables / ragged_tick_commit give on the entries widened to {slot,
+    live, f, 0} with min_frames = f and in_frames = N * f, and every index that ragged call touches lies inside its array."""
+    from pwv_amd import stream
+    rng = np.random.default_rng(77)
+    for case in range(60):
+        n_slots = int(rng.integers(1, 10))
+        n = int(rng.integers(1, n_slots + 1))
+        slots = [int(s) for s in rng.permutation(n_slots)[:n]]
+        f, hop, n_mels = int(rng.integers(1, 7)), int(rng.choice([2, 16, 80, 96])), int(rng.choice([1, 3, 8, 80]))
+        host = _HostStream(rng, n_slots, n_mels)
+        sess, kept = host.sess(), host.kept
+        mel = rng.uniform(-1, 1, (n, f, n_mels)).astype(np.float32)
+        entries = np.array([[s, int(rng.integers(0, 2))] for s in slots], np.int32)
+        wide = np.concatenate([entries, np.full((n, 1), f, np.int32), np.zeros((n, 1), np.int32)], axis=1)
+        flat, touched = mel.reshape(n * f, n_mels), {}
+        for sample in (True, False):
+            tab, streams, cu_rows, frames = stream.tick_begin_tables(sess, kept, entries, mel, hop, sample=sample)
+            r_tab, r_streams, r_cu_rows, r_cu_frames, r_chunk = stream.ragged_tick_begin_tables(sess, kept, wide, flat, hop, f, touched=touched,
+                                                                                                sample=sample)
+            pairs = [(tab, r_tab), (frames, r_chunk.reshape(n, f + 1, n_mels))] + ([(streams, r_streams), (cu_rows, r_cu_rows)] if sample else [])
+            for got, want in pairs:
+                assert got.dtype == want.dtype and np.array_equal(got, want), case
+            if not sample:
+                assert streams is None and cu_rows is None and r_streams is None          # the sampler's tables go together
+            assert np.array_equal(r_cu_frames, np.arange(n + 1) * (f + 1)) and np.array_equal(r_cu_rows, np.arange(n + 1) * f * hop)
+        for words in ((0, 0), (0, 1), (3, 0)):
+            got = stream.tick_commit(sess, kept, entries, mel, f * hop, words)
+            want = stream.ragged_tick_commit(sess, kept, wide, flat, hop, f, words, touched=touched)
+            assert got[2] == want[2] == (words == (0, 0))
+            for g, w in zip(got[:2], want[:2]):
+                assert g.dtype == w.dtype and np.array_equal(g, w), case
+        sizes = {'sess': n_slots, 'kept': n_slots, 'mel': n * f, 'chunk': n * (f + 1)}
+        assert set(touched) == set(sizes)
+        for name, idx in touched.items():
+            assert idx and min(idx) >= 0 and max(idx) < sizes[name], (case, name)
+
+
 def test_the_two_tick_kernels_use_no_scratch():
     """The compiler's resource remarks for pwv_stream_tick.hip (gfx950 device code, no GPU needed): both kernels with 0 bytes of scratch
     and nothing spilled."""
     from tests.util import kernel_resources
-    seen = {}
+    seen, lds = {}, {}
     for name, r in kernel_resources('pwv_stream_tick.hip').items():
         for kernel in ('stream_tick_begin_kernel', 'stream_tick_commit_kernel'):
             if kernel in name:
                 seen[kernel] = (r['scratch'], r['vgpr_spills'], r['sgpr_spills'], r['vgprs'])
-    print('tick kernels (scratch, spilled VGPRs, spilled SGPRs, VGPRs):', seen)
+                lds[kernel] = r['lds']
+    print('tick kernels (scratch, spilled VGPRs, spilled SGPRs, VGPRs):', seen, 'LDS bytes:', lds)
+    # the uniform counts are closed form: no array in LDS, only the commit's one decision word
+    assert lds == {'stream_tick_begin_kernel': 0, 'stream_tick_commit_kernel': 4}, lds
     assert sorted(seen) == ['stream_tick_begin_kernel', 'stream_tick_commit_kernel'], seen
     for kernel, (sc, vs, ss, vg) in seen.items():
         assert sc == 0 and vs == 0 and ss == 0, (kernel, sc, vs, ss)

@@ -5,7 +5,6 @@ entries hold, the layout and filler rule, and the compiler's resource remarks fo
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -18,6 +17,7 @@ def test_abi_symbols_struct_and_version(built_lib, tmp_path):
     """Both symbols are declared in the header, listed in EXPORTED_SYMBOLS and exported by the built library; the C compiler's size and
     offsets of pwv_stream_tick_ragged_args equal the ctypes mirror's; pwv_stream_tick_args is what it was and the version is still 301."""
     from pwv_amd import _lib
+    from tests.util import c_struct_probe
     header = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', 'pwv_hip.h')).read(), flags=re.S)
     raw = ctypes.CDLL(_lib.LIB_PATH)
     for name in SYMBOLS:
@@ -26,15 +26,7 @@ def test_abi_symbols_struct_and_version(built_lib, tmp_path):
     assert len(_lib.EXPORTED_SYMBOLS) == len(set(_lib.EXPORTED_SYMBOLS)) == 52
     fields = [f[0] for f in _lib.StreamTickRaggedArgs._fields_]
     assert fields[0] == 'struct_size'
-    probe = (['sizeof(pwv_stream_tick_ragged_args)'] + ['offsetof(pwv_stream_tick_ragged_args, %s)' % f for f in fields]
-             + ['sizeof(pwv_stream_tick_args)'])
-    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "pwv_hip.h"\nint main(void){ printf("%s %%d\\n", %s, PWV_HIP_VERSION); return 0; }\n'
-           % (' '.join(['%zu'] * len(probe)), ', '.join(probe)))
-    c, exe = str(tmp_path / 't.c'), str(tmp_path / 't')
-    with open(c, 'w') as f:
-        f.write(src)
-    subprocess.check_call(['gcc', '-std=c99', '-Wall', '-Wextra', '-pedantic', '-Werror', '-I' + os.path.join(ROOT, 'include'), c, '-o', exe])
-    got = [int(x) for x in subprocess.check_output([exe]).decode().split()]
+    got = c_struct_probe('pwv_stream_tick_ragged_args', fields, tmp_path, extra=['sizeof(pwv_stream_tick_args)'])
     S = _lib.StreamTickRaggedArgs
     assert got == [ctypes.sizeof(S)] + [getattr(S, f).offset for f in fields] + [ctypes.sizeof(_lib.StreamTickArgs), 301]
     assert ctypes.sizeof(_lib.StreamTickArgs) == 112          # (the size word, 4 pointers, 5 int32 padded to 24 bytes, 6 pointers: as it was)
@@ -303,7 +295,7 @@ def test_the_entries_upload_is_skipped_only_for_the_same_table():
     u = _entry_writer(graph.GraphedStream, 3, 2, n=3)
     for called, want in [([0, 1, 2], [[0, 1], [1, 1], [2, 1]]), ([0, 1], [[0, 1], [1, 1], [2, 0]]), ([0], [[0, 1], [1, 0], [2, 0]]),
                          ([0, 1], [[0, 1], [1, 1], [2, 0]]), ([0, 1, 2], [[0, 1], [1, 1], [2, 1]])]:
-        u._write_entries(0, called, 1)
+        u._write_entries(0, called)
         assert u._entries.tolist() == want, (called, u._entries.tolist())
 
 
@@ -311,12 +303,15 @@ def test_the_two_ragged_tick_kernels_use_no_scratch():
     """The compiler's resource remarks for pwv_stream_tick.hip (gfx950 device code, no GPU needed): both ragged kernels with 0 bytes of
     scratch and nothing spilled."""
     from tests.util import kernel_resources
-    seen = {}
+    seen, lds = {}, {}
     for name, r in kernel_resources('pwv_stream_tick.hip').items():
         for kernel in ('stream_tick_ragged_begin_kernel', 'stream_tick_ragged_commit_kernel'):
             if kernel in name:
                 seen[kernel] = (r['scratch'], r['vgpr_spills'], r['sgpr_spills'], r['vgprs'])
-    print('ragged tick kernels (scratch, spilled VGPRs, spilled SGPRs, VGPRs):', seen)
+                lds[kernel] = r['lds']
+    print('ragged tick kernels (scratch, spilled VGPRs, spilled SGPRs, VGPRs):', seen, 'LDS bytes:', lds)
+    # cu [1025] and slot [1024] (begin), and live [1024] and the decision word besides (commit): what the kernels held before the merge
+    assert lds == {'stream_tick_ragged_begin_kernel': 8208, 'stream_tick_ragged_commit_kernel': 12304}, lds
     assert sorted(seen) == ['stream_tick_ragged_begin_kernel', 'stream_tick_ragged_commit_kernel'], seen
     for kernel, (sc, vs, ss, vg) in seen.items():
         assert sc == 0 and vs == 0 and ss == 0, (kernel, sc, vs, ss)

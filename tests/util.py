@@ -295,6 +295,22 @@ def build_c_abi_smoke(out_path):
     return subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
 
 
+def c_struct_probe(struct, fields, tmp_path, extra=()):
+    """What the C compiler makes of a struct of include/pwv_hip.h (gcc -std=c99 -pedantic -Werror on a probe program): [sizeof(struct),
+    offsetof(struct, f) for f in fields, *extra (further size_t expressions), PWV_HIP_VERSION]."""
+    import os
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    probe = ['sizeof(%s)' % struct] + ['offsetof(%s, %s)' % (struct, f) for f in fields] + list(extra)
+    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "pwv_hip.h"\nint main(void){ printf("%s %%d\\n", %s, PWV_HIP_VERSION); return 0; }\n'
+           % (' '.join(['%zu'] * len(probe)), ', '.join(probe)))
+    c, exe = str(tmp_path / 't.c'), str(tmp_path / 't')
+    with open(c, 'w') as f:
+        f.write(src)
+    subprocess.check_call(['gcc', '-std=c99', '-Wall', '-Wextra', '-pedantic', '-Werror', '-I' + os.path.join(root, 'include'), c, '-o', exe])
+    return [int(x) for x in subprocess.check_output([exe]).decode().split()]
+
+
 def _device_compile(source_name, mode):
     """Run the shipped compile command (_lib.device_compile_command) of csrc/<source_name> for the device side alone; returns the
     CompletedProcess (text)."""
