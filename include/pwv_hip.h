@@ -663,9 +663,25 @@ int pwv_stream_tick_commit(const pwv_stream_tick_args* args, pwv_stream_t stream
  * hop * f_i, kept[s] = mel[cu_in[i] + f_i - 1] -- and counters[0] += 1; otherwise nothing changes and counters[1] += 1.  The committed
  * ticks are a prefix of the enqueued ones, a filler is never committed, and a slot outside 0 .. n_slots-1 is read as a filler of slot 0.
  * One launch each, nothing read on the host: a captured pair replays with whatever the tables hold then.
+ *
+ * STARTS (optional: `starts` non-NULL selects the starts instantiations of both kernels).  A fresh session given the frames m_0 .. m_f
+ * is a running session whose kept frame is m_0, whose history is zeros, whose counter is 0 and whose new frames are m_1 .. m_f: so an
+ * entry that begins a new utterance in this tick -- on a fresh slot or on a running one, whose old utterance ends there -- carries
+ * frames = f in `entries` and m_1 .. m_f in `mel` like any other entry, and the caller writes besides
+ *   starts  int64 [N][2] = {flag, seed (uint64 bits)}: entry i STARTS iff flag != 0 and it is no filler (live != 0, slot in range)
+ *   first   float [N][n_mels]: first[i] = m_0 of a starting entry (read for starting entries only)
+ *   zero_block: the index of a history block that holds zeros and that nothing ever writes (>= 2 * n_slots: no session's block)
+ * For a starting entry, begin writes slot_tab[i] = {zero_block, 2s + 1 - g}, streams[i] = {starts[i].seed, 0} and
+ * chunk[cu_frames[i]] = first[i]; commit -- clean words, as for every entry -- does sess[s][0] ^= 1, sess[s][1] = hop * f_i (set, not
+ * added), sess[s][2] = starts[i].seed, and kept[s] as for every entry.  Everything else is as above; a refused tick changes nothing
+ * for a starting entry either.  Only the FLAG of `starts` decides an address: whatever else the table holds, nothing leaves the arrays.
+ * The three fields are trailing and optional: a caller compiled against the struct without them (struct_size = the offset of `starts`)
+ * is served as before, the fields read as zero.
+ *
  * PWV_EINVAL before a device is needed (pwv_last_error names the field): a NULL pointer (streams alone may be NULL; cu_rows and
  * cu_frames are required with or without it), N < 1, N > 1024, min_frames < 1, hop < 1, n_mels < 1, n_slots < 1,
- * in_frames < N * min_frames, in_frames * hop or (in_frames + N) * n_mels beyond 2^31 - 1, struct_size short of the struct.
+ * in_frames < N * min_frames, in_frames * hop or (in_frames + N) * n_mels beyond 2^31 - 1, struct_size short of the fields up to
+ * `counters`, starts without first, starts with zero_block < 2 * n_slots.
  * ------------------------------------------------------------------------------------- */
 typedef struct pwv_stream_tick_ragged_args {
     size_t struct_size;                    /* = sizeof(pwv_stream_tick_ragged_args) as the caller was compiled */
@@ -685,6 +701,10 @@ typedef struct pwv_stream_tick_ragged_args {
     /* pwv_stream_tick_ragged_commit reads / advances: */
     const int* words;                      /* the sticky pair (mapped host memory) the tick's launches report into */
     int64_t* counters;                     /* device int64 [2] = {ticks committed, ticks refused} */
+    /* optional, trailing (STARTS above); a struct_size that ends in front of a field reads it as zero: */
+    const int64_t* starts;                 /* device int64 [N][2] = {flag, seed bits}, or NULL: no entry starts */
+    const float* first;                    /* device float [N][n_mels]: the first frame of a starting entry; required with starts */
+    int32_t zero_block;                    /* a history block of zeros that is never written, >= 2 * n_slots; read with starts */
 } pwv_stream_tick_ragged_args;
 
 int pwv_stream_tick_ragged_begin(const pwv_stream_tick_ragged_args* args, pwv_stream_t stream);

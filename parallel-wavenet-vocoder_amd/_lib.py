@@ -243,6 +243,10 @@ class StreamTickRaggedArgs(Structure):
         ('chunk', c_void_p),
         ('words', c_void_p),
         ('counters', c_void_p),
+        # optional, trailing ("STARTS"): NULL / 0 = no entry of the tick begins an utterance
+        ('starts', c_void_p),           # device int64 [N, 2] = {flag, seed bits}
+        ('first', c_void_p),            # device float [N, n_mels]: the first frame of a starting entry
+        ('zero_block', ctypes.c_int32),  # a history block of zeros that is never written (>= 2 * n_slots)
     ]
 
     def __init__(self, *args, **kw):

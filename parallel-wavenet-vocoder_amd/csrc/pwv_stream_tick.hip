@@ -4,7 +4,9 @@
 // the tick's last node, advances the sessions iff the tick's launches left both sticky words clean.  A UNIFORM tick is a ragged tick
 // whose frame counts are all equal: both bodies are written once over a COUNTS policy that says where entry i's frames begin --
 // UniformCounts in closed form, RaggedCounts from the device table, clamped so that the packed layout is well formed whatever the table
-// holds.  Plain C++, every address from the arguments, vector stores only.
+// holds.  A ragged tick may START utterances (include/pwv_hip.h, "STARTS"): both bodies have a STARTS form, instantiated as kernels of
+// their own, in which an entry whose flag is set reads the zero block and its first frame from the caller's table and is committed with
+// its counter set and its seed written.  Plain C++, every address from the arguments, vector stores only.
 #include <cstddef>
 
 #include "pwv_common.h"
@@ -29,6 +31,10 @@ struct TickParams {
     float* chunk;
     const int* words;
     long long* counters;
+    // the STARTS form alone reads these (a ragged tick with starts): {flag, seed bits} and the first frame per entry, the block of zeros
+    const long long* starts;
+    const float* first;
+    int zero_block;
 };
 
 // A counts policy: prepare() once per workgroup, by all its threads (it ends on a barrier), then cu(i) -- the frames in front of entry
@@ -98,8 +104,14 @@ struct RaggedCounts {
     }
 };
 
+// STARTS form: does entry i begin a new utterance?  Its flag is set and it is no filler (live, slot inside the table).  The flag is all
+// that is read of the starts table to decide an address.
+__device__ inline bool tick_starting(const TickParams& p, int i) {
+    return p.starts[2 * i] != 0 && p.entries[4 * i + 1] != 0 && (unsigned)p.entries[4 * i] < (unsigned)p.n_slots;
+}
+
 // one thread per float of the chunk; workgroup 0 also writes the tables
-template <class Counts>
+template <class Counts, bool STARTS = false>
 __device__ inline void tick_begin(const TickParams& p) {
     Counts n{p};
     n.prepare();
@@ -110,11 +122,13 @@ __device__ inline void tick_begin(const TickParams& p) {
             if (i == p.N) break;
             const int s = n.slot(i);
             const int g = (int)(p.sess[4 * (long long)s] & 1);
-            p.slot_tab[2 * i] = 2 * s + g;
+            bool starting = false;
+            if constexpr (STARTS) starting = tick_starting(p, i);
+            p.slot_tab[2 * i] = starting ? p.zero_block : 2 * s + g;
             p.slot_tab[2 * i + 1] = 2 * s + 1 - g;
             if (p.streams) {
-                p.streams[2 * i] = (unsigned long long)p.sess[4 * (long long)s + 2];
-                p.streams[2 * i + 1] = (unsigned long long)p.sess[4 * (long long)s + 1];
+                p.streams[2 * i] = (unsigned long long)(starting ? p.starts[2 * i + 1] : p.sess[4 * (long long)s + 2]);
+                p.streams[2 * i + 1] = starting ? 0ull : (unsigned long long)p.sess[4 * (long long)s + 1];
             }
         }
     }
@@ -123,11 +137,17 @@ __device__ inline void tick_begin(const TickParams& p) {
     const int row = (int)(idx / p.n_mels), c = (int)(idx % p.n_mels);
     const int i = n.entry_of(row);
     const int f = row - (n.cu(i) + i);          // 0 .. f_i: row < cu(i + 1) + i + 1
+    if constexpr (STARTS) {
+        if (f == 0 && tick_starting(p, i)) {          // (the utterance's first frame stands where the kept frame would)
+            p.chunk[idx] = p.first[(long long)i * p.n_mels + c];
+            return;
+        }
+    }
     p.chunk[idx] = f == 0 ? p.kept[(long long)n.slot(i) * p.n_mels + c] : p.mel[(long long)(n.cu(i) + f - 1) * p.n_mels + c];
 }
 
 // ONE workgroup: the words are read once, so all entries of a tick see one decision
-template <class Counts>
+template <class Counts, bool STARTS = false>
 __device__ inline void tick_commit(const TickParams& p) {
     __shared__ int clean;
     if (threadIdx.x == 0) {
@@ -143,6 +163,13 @@ __device__ inline void tick_commit(const TickParams& p) {
         if (n.live(i)) {
             const int s = n.slot(i);
             p.sess[4 * (long long)s] ^= 1;
+            if constexpr (STARTS) {
+                if (p.starts[2 * i] != 0) {          // (live: a start, with the counter set and the seed the utterance draws from)
+                    p.sess[4 * (long long)s + 1] = n.rows(i + 1) - n.rows(i);
+                    p.sess[4 * (long long)s + 2] = p.starts[2 * i + 1];
+                    continue;
+                }
+            }
             p.sess[4 * (long long)s + 1] += n.rows(i + 1) - n.rows(i);
         }
     }
@@ -157,6 +184,8 @@ __global__ void stream_tick_begin_kernel(TickParams p) { tick_begin<UniformCount
 __global__ void stream_tick_commit_kernel(TickParams p) { tick_commit<UniformCounts>(p); }
 __global__ void stream_tick_ragged_begin_kernel(TickParams p) { tick_begin<RaggedCounts<false>>(p); }
 __global__ void stream_tick_ragged_commit_kernel(TickParams p) { tick_commit<RaggedCounts<true>>(p); }
+__global__ void stream_tick_starts_begin_kernel(TickParams p) { tick_begin<RaggedCounts<false>, true>(p); }
+__global__ void stream_tick_starts_commit_kernel(TickParams p) { tick_commit<RaggedCounts<true>, true>(p); }
 
 // ---- the entry points: everything is decided before a device is needed ---------------------------------------------------------------
 
@@ -178,16 +207,21 @@ static int tick_check(const TickParams& p, const char* who, bool begin) {
     return PWV_OK;
 }
 
-#define PWV_TICK_STRUCT(a, type)                                                                                                 \
+// `need`: the bytes of `type` the call cannot do without (the whole struct, or what stands in front of its optional trailing fields)
+#define PWV_TICK_STRUCT(a, type, need)                                                                                           \
     PWV_CHECK_ARG(a, "%s: args is NULL", who);                                                                                   \
-    PWV_CHECK_ARG(a->struct_size >= sizeof(type), "%s: struct_size %zu is short of " #type " (%zu bytes)", who, a->struct_size, \
-                  sizeof(type))
+    PWV_CHECK_ARG(a->struct_size >= (need), "%s: struct_size %zu is short of " #type " (%zu bytes)", who, a->struct_size,       \
+                  (size_t)(need))
+
+// an optional trailing field: what the caller's struct holds of it, else zero
+#define PWV_TICK_OPTIONAL(a, type, field) \
+    (a->struct_size >= offsetof(type, field) + sizeof(a->field) ? a->field : decltype(a->field){})
 
 // the uniform tick: frames and T per entry, streams and cu_rows together or not at all, no cu_frames, any N
 static int tick_params(const pwv_stream_tick_args* a, const char* who, bool begin, TickParams* p) {
-    PWV_TICK_STRUCT(a, pwv_stream_tick_args);
+    PWV_TICK_STRUCT(a, pwv_stream_tick_args, sizeof(pwv_stream_tick_args));
     *p = TickParams{(long long*)a->sess, a->kept, a->entries, a->mel, a->n_slots, a->N, 0, a->n_mels, a->frames, a->T, a->slot_tab,
-                    (unsigned long long*)a->streams, a->cu_rows, nullptr, a->chunk, a->words, (long long*)a->counters};
+                    (unsigned long long*)a->streams, a->cu_rows, nullptr, a->chunk, a->words, (long long*)a->counters, nullptr, nullptr, 0};
     const int rc = tick_check(*p, who, begin);
     if (rc != PWV_OK) return rc;
     PWV_CHECK_ARG(a->N >= 1, "%s: N must be >= 1, got %d", who, (int)a->N);
@@ -200,11 +234,14 @@ static int tick_params(const pwv_stream_tick_args* a, const char* who, bool begi
     return PWV_OK;
 }
 
-// the ragged tick: the counts in LDS (N <= RAGGED_MAX_N), cu_rows and cu_frames the launches' layout with or without streams
+// the ragged tick: the counts in LDS (N <= RAGGED_MAX_N), cu_rows and cu_frames the launches' layout with or without streams; starts,
+// first and zero_block are optional trailing fields (a struct that ends in front of one reads it as zero)
 static int tick_params(const pwv_stream_tick_ragged_args* a, const char* who, bool begin, TickParams* p) {
-    PWV_TICK_STRUCT(a, pwv_stream_tick_ragged_args);
+    PWV_TICK_STRUCT(a, pwv_stream_tick_ragged_args, offsetof(pwv_stream_tick_ragged_args, starts));
     *p = TickParams{(long long*)a->sess, a->kept, a->entries, a->mel, a->n_slots, a->N, a->in_frames, a->n_mels, a->min_frames, a->hop,
-                    a->slot_tab, (unsigned long long*)a->streams, a->cu_rows, a->cu_frames, a->chunk, a->words, (long long*)a->counters};
+                    a->slot_tab, (unsigned long long*)a->streams, a->cu_rows, a->cu_frames, a->chunk, a->words, (long long*)a->counters,
+                    (const long long*)PWV_TICK_OPTIONAL(a, pwv_stream_tick_ragged_args, starts),
+                    PWV_TICK_OPTIONAL(a, pwv_stream_tick_ragged_args, first), PWV_TICK_OPTIONAL(a, pwv_stream_tick_ragged_args, zero_block)};
     const int rc = tick_check(*p, who, begin);
     if (rc != PWV_OK) return rc;
     PWV_CHECK_ARG(a->N >= 1 && a->N <= RAGGED_MAX_N, "%s: N must be 1 .. %d, got %d", who, RAGGED_MAX_N, (int)a->N);
@@ -216,15 +253,23 @@ static int tick_params(const pwv_stream_tick_ragged_args* a, const char* who, bo
                   "%s: in_frames * hop and (in_frames + N) * n_mels must stay below 2^31", who);
     PWV_CHECK_ARG(!begin || a->cu_rows, "%s: cu_rows is NULL (required with or without streams: the launches' layout)", who);
     PWV_CHECK_ARG(!begin || a->cu_frames, "%s: cu_frames is NULL", who);
+    if (p->starts) {
+        PWV_CHECK_ARG(p->first, "%s: first is NULL (required with starts: the first frame of a starting entry)", who);
+        PWV_CHECK_ARG((long long)p->zero_block >= 2ll * a->n_slots, "%s: zero_block must be >= 2 * n_slots = %lld (no session's block), got %d",
+                      who, 2ll * a->n_slots, p->zero_block);
+    }
     return PWV_OK;
 }
 
-// check, then one launch: the begin kernel with a thread per float of the chunk, the commit kernel as ONE workgroup
+// check, then one launch: the begin kernel with a thread per float of the chunk, the commit kernel as ONE workgroup; `with_starts` is
+// the kernel of a tick that brings a starts table (the ragged tick alone has one)
 template <class Args>
-static int tick_launch(const Args* a, const char* who, bool begin, void (*kernel)(TickParams), pwv_stream_t stream) {
+static int tick_launch(const Args* a, const char* who, bool begin, void (*kernel)(TickParams), pwv_stream_t stream,
+                       void (*with_starts)(TickParams) = nullptr) {
     TickParams p{};
     const int rc = tick_params(a, who, begin, &p);
     if (rc != PWV_OK) return rc;
+    if (p.starts) kernel = with_starts;
     const long long floats = ((long long)p.in_frames + p.N) * p.n_mels;
     hipLaunchKernelGGL(kernel, dim3(begin ? (unsigned)((floats + 255) / 256) : 1u), dim3(256), 0, (hipStream_t)stream, p);
     PWV_CHECK_HIP(hipGetLastError());
@@ -246,11 +291,11 @@ int pwv_stream_tick_commit(const pwv_stream_tick_args* a, pwv_stream_t stream) {
 }
 
 int pwv_stream_tick_ragged_begin(const pwv_stream_tick_ragged_args* a, pwv_stream_t stream) {
-    return tick_launch(a, "pwv_stream_tick_ragged_begin", true, stream_tick_ragged_begin_kernel, stream);
+    return tick_launch(a, "pwv_stream_tick_ragged_begin", true, stream_tick_ragged_begin_kernel, stream, stream_tick_starts_begin_kernel);
 }
 
 int pwv_stream_tick_ragged_commit(const pwv_stream_tick_ragged_args* a, pwv_stream_t stream) {
-    return tick_launch(a, "pwv_stream_tick_ragged_commit", false, stream_tick_ragged_commit_kernel, stream);
+    return tick_launch(a, "pwv_stream_tick_ragged_commit", false, stream_tick_ragged_commit_kernel, stream, stream_tick_starts_commit_kernel);
 }
 
 }  // extern "C"

@@ -150,8 +150,9 @@ def generate(case='default', ckpt=None, debug=False, varlen=False, seed=None, st
         its mel and the seed -- not on the other files of the run or their order.
     :param stream: vocode every input at its own length as a STREAM (IAFVocoder.open_stream): one session per input, fed in pushes
         of `stream` mel frames; writes the files --varlen writes.
-    :param graph: (with stream) every session starts with the eager one-frame push, every tick after that is one replay of a captured
-        ragged tick (StreamingVocoder.graphed_varlen at a capacity of one slot per input and inputs x `stream` frames); same files.
+    :param graph: (with stream) every tick is one replay of a captured ragged tick (StreamingVocoder.graphed_varlen at a capacity of one
+        slot per input and inputs x `stream` frames), the first one included: it starts the sessions (tick(starts=)); only an input too
+        short for that starts with the eager one-frame push; same files.
     '''
     if graph and stream is None:
         raise ValueError('--graph applies to --stream=FRAMES (graph replay of the ragged ticks)')
@@ -260,20 +261,37 @@ def _generate_stream(model, mels, frames):
 
 
 def _generate_stream_graph(model, mels, frames, depth=4):
-    """--stream=FRAMES --graph: the sessions of _generate_stream, started by ONE eager push of every input's first frame (it is kept:
-    nothing to generate yet) and then advanced by graphed ragged ticks (graph.GraphedRaggedStream at a capacity of len(mels) slots and
-    len(mels) * frames frames: a tick of all sessions at `frames` frames fills it, a tick with sessions that have ended is filled up by
-    filler sessions, and one that does not fit -- short last chunks in every slot -- runs eagerly inside tick()).  The ticks only
-    enqueue; one verify() every `depth` ticks.  Where verify() reports refused ticks (a chunk outside the range of the split-fp16
-    arithmetic, a persistent launch that gave up) the sessions stand behind the committed ones: the first refused tick is pushed
-    again with the verified eager push_varlen -- which reruns it as the plain --stream would -- and the ticks go on from there."""
+    """--stream=FRAMES --graph: the sessions of _generate_stream advanced by graphed ragged ticks (graph.GraphedRaggedStream at a capacity
+    of len(mels) slots and len(mels) * frames frames: a tick of all sessions at `frames` frames fills it, a tick with sessions that have
+    ended is filled up by filler sessions, and one that does not fit -- short last chunks in every slot -- runs eagerly inside tick()).
+    A session's first tick STARTS it (tick(starts=): its first frame and its next `frames` frames, the samples of the latter); only an
+    input whose first chunk has fewer than min_frames + 1 frames starts with the eager one-frame push (its frame is kept: nothing to generate yet).  The
+    seeds are drawn here, one per input in input order, as the first push of _generate_stream draws them.  The ticks only enqueue; one
+    verify() every `depth` ticks.  Where verify() reports refused ticks (a chunk outside the range of the split-fp16 arithmetic, a
+    persistent launch that gave up) the sessions stand behind the committed ones: the first refused tick is pushed again with the
+    verified eager push_varlen -- which reruns it as the plain --stream would -- and the ticks go on from there."""
     from . import _lib, engine
     n, hop = len(mels), int(hp.signal.hop_length)
     s = model.open_stream(slots=n)
-    first = s.push_varlen([m[:1] for m in mels], verify=True)
+    seeds = [engine.os_seed() for _ in mels]
     g = s.graphed_varlen(n, n * frames * hop, sample=True, depth=depth)
-    pos, outs = [1] * n, [[first[i]] for i in range(n)]
-    window = []                # the ticks enqueued since the last verify(): (slots, counts)
+    short = [i for i, m in enumerate(mels) if min(frames, m.shape[0] - 1) < g.min_frames]          # (no start a graphed tick takes)
+    pos, outs = [0] * n, [[] for _ in mels]
+    if short:
+        first = s.push_varlen([mels[i][:1] for i in short], slots=short, seeds=[seeds[i] for i in short], verify=True)
+        for k, i in enumerate(short):
+            pos[i], outs[i] = 1, [first[k]]
+    window = []                # the ticks enqueued since the last verify(): (slots, counts, the slots the tick started)
+
+    def chunk(slots, counts):
+        """The frames of a tick and the slots it starts: a session that has been given nothing yet brings its first frame too."""
+        return ([mels[i][pos[i]:pos[i] + f + (1 if pos[i] == 0 else 0)] for i, f in zip(slots, counts)],
+                {i: seeds[i] for i in slots if pos[i] == 0})
+
+    def advance(slots, counts, got, clone):
+        for k, (i, f) in enumerate(zip(slots, counts)):
+            outs[i].append(got[k].clone() if clone else got[k])      # (a view of the graph's output buffer: the next tick overwrites it)
+            pos[i] += f + (1 if pos[i] == 0 else 0)
 
     def settle():
         try:
@@ -281,28 +299,26 @@ def _generate_stream_graph(model, mels, frames, depth=4):
         except _lib.PwvError as e:
             if not hasattr(e, 'committed'):
                 raise
-            for slots, counts in window[e.committed:]:        # what the refused ticks returned is not the sessions' audio
+            for slots, counts, started in window[e.committed:]:        # what the refused ticks returned is not the sessions' audio
                 for i, f in zip(slots, counts):
-                    pos[i] -= f
+                    pos[i] -= f + (1 if i in started else 0)
                     outs[i].pop()
-            slots, counts = window[e.committed]
-            got = s.push_varlen([mels[i][pos[i]:pos[i] + f] for i, f in zip(slots, counts)], slots=slots, verify=True)
-            for k, (i, f) in enumerate(zip(slots, counts)):
-                outs[i].append(got[k])
-                pos[i] += f
+            slots, counts, _ = window[e.committed]
+            given, starts = chunk(slots, counts)
+            for i, seed in starts.items():
+                s.reset(i, seed)
+            advance(slots, counts, s.push_varlen(given, slots=slots, verify=True), False)
         del window[:]
 
     while any(p < m.shape[0] for p, m in zip(pos, mels)):
         slots = [i for i, m in enumerate(mels) if pos[i] < m.shape[0]]
-        counts = [min(frames, mels[i].shape[0] - pos[i]) for i in slots]
+        counts = [min(frames, mels[i].shape[0] - max(pos[i], 1)) for i in slots]          # (the samples' frames: a first frame brings none)
         if window and (not g.fits(counts) or engine.persist_suspended()):
             settle()                                 # (tick() would settle them itself, and raise from there)
             continue
-        got = g.tick([mels[i][pos[i]:pos[i] + f] for i, f in zip(slots, counts)], slots)
-        for k, (i, f) in enumerate(zip(slots, counts)):
-            outs[i].append(got[k].clone())           # (a view of the graph's output buffer: the next tick overwrites it)
-            pos[i] += f
-        window.append((slots, counts))
+        given, starts = chunk(slots, counts)
+        advance(slots, counts, g.tick(given, slots, starts=starts or None), True)
+        window.append((slots, counts, set(starts)))
         if len(window) >= depth:
             settle()
     if window:

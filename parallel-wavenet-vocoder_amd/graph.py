@@ -423,6 +423,11 @@ class _TickGraph(_Captured):
         self._seen = [0, 0]                     # the counters at the last verify()
         self._carry = 0                         # eager ticks settled on the way (counted by the next verify())
         self._dirty_rows = 0                    # leading rows of mel (and their part of z) that may hold a previous tick's values
+        # starts in flight (GraphedRaggedStream.tick(starts=)): the graphed ticks replayed since the last verify(), (the tick's number
+        # among them, slot, the seed the call gave) per start, and the slots that have one
+        self._window = 0
+        self._starts_log = []
+        self._started = set()
         self._capture()
 
     def _refusal(self, rows: int) -> Optional[str]:
@@ -478,21 +483,22 @@ class _TickGraph(_Captured):
         ev = torch.cuda.Event()
         ev.record()
         self._events.append(ev)
+        self._window += 1
         self._inflight.update(slots)
         st._pending, st._ticker = self.verify, self
 
-    def _sync_rows(self, j: int, slots, fillers) -> None:
+    def _sync_rows(self, j: int, slots, fillers, starts=()) -> None:
         """The session rows of the tick's entries -- the called slots, then the fillers --, rewritten where the host's view says the device
         row differs (first tick, an eager push, reset or load_state since).  A filler needs its row as much as a called slot: the
         generation it WRITES must be the one the session does not stand on.  A slot with ticks in flight is the device's: its row is
-        what those ticks leave."""
+        what those ticks leave.  A slot in `starts` begins an utterance in this tick: its seed and counter come from the starts table."""
         st, rows = self.stream, self._rows_host[j]
         for i, s in enumerate(list(slots) + list(fillers)):
             if s in self._inflight:
                 continue
             have, seed = st._sess_host[s], st._seed[s]
-            if i >= len(slots):
-                # a filler's noise is nobody's: only the generation and the counter have to be the session's
+            if i >= len(slots) or s in starts:
+                # a filler's noise is nobody's (a start brings its own): only the generation and the counter have to be the session's
                 if have is not None and have[:2] == (st._gen[s], st._emitted[s]):
                     continue
                 seed = seed if seed is not None else 0
@@ -532,12 +538,25 @@ class _TickGraph(_Captured):
         committed, refused = counters[0] - self._seen[0], counters[1] - self._seen[1]
         self._seen = counters
         table = self._sess_back.tolist()
+        # the committed ticks are a prefix: a start is committed iff its tick is among the first `committed` of this window
+        began = {s: seed for k, s, seed in self._starts_log if k < committed}
         for s in self._inflight:
             gen, emitted, seed = int(table[s][0]) & 1, int(table[s][1]), int(table[s][2])
-            st._gen[s], st._emitted[s], st._running[s] = gen, emitted, True
+            st._gen[s], st._emitted[s] = gen, emitted
+            st._sess_host[s] = (gen, emitted, seed)
+            if s in self._started and s not in began and not st._running[s]:
+                # a refused start leaves a fresh slot fresh (seed and all); the generation it wrote is scratch, as after a filler
+                st._scratch_dirty[s] = True
+                continue
+            st._running[s] = True
             if self.sample:
                 st._seed[s] = engine.from_int64_bits(seed)
-            st._sess_host[s] = (gen, emitted, seed)
+            elif s in began:
+                st._seed[s] = began[s]          # (the caller's noise: the seed is kept as reset(slot, seed) would keep it)
+            if s in began:
+                st._scratch_dirty[s] = False
+        self._window, self._starts_log = 0, []
+        self._started.clear()
         self._inflight.clear()
         self._events.clear()
         st._pending, st._ticker = None, None
@@ -629,15 +648,36 @@ class _TickGraph(_Captured):
         one from the OS, as in push).  Enqueue-only; before tick j is enqueued the host waits for the end of tick j - depth.  A tick
         that does not fit the capture, or one while the persistent launches are suspended, settles what is in flight (verify()) and
         runs the eager push instead (eager_calls)."""
+        return self._tick(mel, slots, z, None)
+
+    def _check_starts(self, starts, slots, frames) -> dict:
+        """{slot: seed or None} of the sessions that begin an utterance in this tick ({}: none; the ragged tick alone takes any)."""
+        return {}
+
+    def _write_starts(self, j: int, slots, starts, first) -> None:
+        """The starts of the tick into the device tables the graph reads (the ragged tick alone has them)."""
+
+    def _tick(self, mel, slots, z, starts):
         st = self.stream
         slots = [st._slot(v) for v in slots]
         if not slots or len(set(slots)) != len(slots):
             raise ValueError('slots must be a non-empty list of distinct slots, got %r' % (slots,))
         mel, frames = self._check_mel(mel, len(slots))          # (frames: every session's count)
-        for s in slots:
-            if not st._running[s]:
-                raise ValueError('slot %d is fresh: a session starts with the eager one-frame push (%s keeps the frame and marks the '
-                                 'slot running) and takes graphed ticks from then on' % (s, self.FIRST_PUSH % s))
+        starts = self._check_starts(starts, slots, frames)
+
+        def fresh():
+            return [s for s in slots if not st._running[s] and s not in starts and s not in self._started]
+
+        if fresh() and st._pending is not None and st._ticker is not self:
+            self._settle()          # (an eager push that only enqueued -- a start that did not fit the capture -- may be what began them)
+        if fresh():
+            raise ValueError('slot %d is fresh: a session starts with the eager one-frame push (%s keeps the frame and marks the '
+                             'slot running) and takes graphed ticks from then on' % (fresh()[0], self.FIRST_PUSH % fresh()[0]))
+        whole, first = mel, {}
+        if starts:          # a starting session's first frame stands in for a kept frame: the rest are its new frames, like anyone's
+            first = {i: mel[i][:1] for i, s in enumerate(slots) if s in starts}
+            mel = [m[1:] if i in first else m for i, m in enumerate(mel)]
+            frames = [f - 1 if i in first else f for i, f in enumerate(frames)]
         if self.sample and z is not None:
             raise ValueError('this graph samples its own noise (sample=True): z is not taken')
         if not self.sample:
@@ -646,9 +686,12 @@ class _TickGraph(_Captured):
         if not self._ready() or columns is None:
             self._settle()
             self.eager_calls += 1
-            return self._eager(mel, slots=slots, z=z, verify=False)
+            for s, seed in starts.items():          # (a fresh slot keeps the seed its own reset gave it)
+                st.reset(s, seed if seed is not None or st._running[s] else st._seed[s])
+            return self._eager(whole, slots=slots, z=z, verify=False)
         j = self._begin_tick()
-        self._sync_rows(j, slots, self._write_entries(j, slots, *columns))
+        self._sync_rows(j, slots, self._write_entries(j, slots, *columns), starts)
+        self._write_starts(j, slots, starts, first)
         used, out = self._copy_in(mel, z, frames)          # (used: the leading rows of self.mel the tick's sessions take)
         if self._dirty_rows > used:          # (a filler runs on zeros: nothing of a previous tick's session may reach the range guard)
             per = self.z.shape[0] // self.mel.shape[0]
@@ -746,6 +789,13 @@ class GraphedRaggedStream(_TickGraph):
     sample=False: z is the noise, the packed [sum f_i * hop, 1] or a list of [f_i * hop, 1].  A tick that does not fit runs
     push_varlen(verify=False).  Ticks in flight, the committed prefix and verify() are GraphedStream's.
 
+    tick(..., starts={slot: seed}) BEGINS an utterance on the named slots of the tick, fresh or running (a running one is cut off: reset
+    and the first push in one step): mels[i] then holds the utterance's opening f_i + 1 frames and the slot yields f_i * hop samples,
+    what push_varlen gives a fresh session.  The first frame goes into the `first` table in the kept frame's stead, the begin kernel of the
+    graph lets the entry read the stream's zero block and draw from {seed, 0}, the commit kernel sets its counter and seed (include/
+    pwv_hip.h, "STARTS"): no verify(), no eager push, the ticks stay pipelined.  The graph always holds the starts instantiations of the
+    two kernels; a tick without starts finds an all-zero flag column.
+
     Refused at construction (PwvError) wherever a flow of such a push is not one packed streaming persistent launch."""
 
     ARGS, ENTRY, ENTRY_INTS = _lib.StreamTickRaggedArgs, 'pwv_stream_tick_ragged', 4
@@ -771,6 +821,14 @@ class GraphedRaggedStream(_TickGraph):
         self.mel = torch.zeros((self.in_frames, st.n_mels), dtype=torch.float32, device=dev)
         self.z = torch.zeros((rows, 1), dtype=torch.float32, device=dev)
         self._chunk = torch.zeros((self.in_frames + n, st.n_mels), dtype=torch.float32, device=dev)
+        # the starts of a tick: {flag, seed bits} and the first frame per entry, the flags through pinned staging like the entries (a
+        # stream without a zero block -- its histories are a caller's allocation -- has neither: its ticks take no starts)
+        self._starts = self._first = None
+        if st._zero_block is not None:
+            self._starts = torch.zeros((n, 2), dtype=torch.int64, device=dev)
+            self._first = torch.zeros((n, st.n_mels), dtype=torch.float32, device=dev)
+            self._starts_host = [torch.zeros((n, 2), dtype=torch.int64).pin_memory() for _ in range(self.depth)]
+        self._starts_zero = True                # the device table holds no flag
         self._start(n)
 
     def _layout(self, frames):
@@ -786,6 +844,14 @@ class GraphedRaggedStream(_TickGraph):
 
     def _shape_args(self, ta):
         ta.in_frames, ta.hop, ta.min_frames = self.in_frames, self.hop, self.min_frames
+        if self._starts is not None:
+            ta.starts, ta.first, ta.zero_block = self._starts.data_ptr(), self._first.data_ptr(), self.stream._zero_block
+
+    def _before_capture(self):
+        if not self._starts_zero:          # fillers, warm-up and capture have no starts
+            self._starts.zero_()
+            self._starts_zero = True
+        super()._before_capture()
 
     def _push_args(self):
         return self._chunk[None], self.z, self._tab, 0, self._geom
@@ -832,6 +898,57 @@ class GraphedRaggedStream(_TickGraph):
 
     def _eager(self, *args, **kw):
         return self.stream.push_varlen(*args, **kw)
+
+    def tick(self, mels, slots, z=None, starts=None):
+        """_TickGraph.tick for the frames mels[i] [f_i, n_mels] of the distinct sessions `slots`.  `starts` = {slot: seed}: these slots of
+        the tick -- fresh or running -- begin a new utterance with it; mels[i] then holds its opening f_i + 1 frames (f_i >= min_frames),
+        the slot yields f_i * hop samples (sample=False: z[i] is [f_i * hop, 1]) and, with sample=True, draws from `seed` at counter 0
+        (None: the seed the slot's reset was given, else one from the OS -- push_varlen's rule).  A fresh slot that `starts` does not
+        name is refused as ever.  A tick with starts that does not fit the capture, or one during a suspension, settles what is in
+        flight and runs reset(slot, seed) and push_varlen(verify=False)."""
+        return self._tick(mels, slots, z, starts)
+
+    def _check_starts(self, starts, slots, frames) -> dict:
+        if starts is None:
+            return {}
+        if not isinstance(starts, dict):
+            raise ValueError('starts must be a dict {slot: seed or None}, got %r' % (starts,))
+        st, out = self.stream, {}
+        for k, v in starts.items():
+            s = st._slot(k)
+            if s not in slots:
+                raise ValueError('starts names slot %d, which is not among the slots of this tick (%r): a seed goes with a slot that '
+                                 'starts in it' % (s, slots))
+            out[s] = None if v is None else st._check_seed(v)
+            f = frames[slots.index(s)]
+            if f < self.min_frames + 1:
+                raise ValueError('slot %d starts an utterance with %d frames: it needs its first frame and at least %d more (%d in all; '
+                                 'a shorter start is the eager push_varlen\'s)' % (s, f, self.min_frames, self.min_frames + 1))
+        if out and self._starts is None:
+            raise _lib.PwvError('GraphedRaggedStream: this stream has no zero block (its histories are a caller\'s allocation, '
+                                'hist_alloc): its graphed ticks take no starts')
+        return out
+
+    def _write_starts(self, j, slots, starts, first):
+        if self._starts is None or (not starts and self._starts_zero):
+            return          # (the device table holds an all-zero flag column already)
+        st, staged = self.stream, self._starts_host[j]
+        buf = staged.numpy()
+        buf[:] = 0
+        for i, s in enumerate(slots):
+            if s not in starts:
+                continue
+            seed = starts[s]
+            if seed is None and not st._running[s] and s not in self._started:
+                seed = st._seed[s]          # push_varlen's rule: a fresh slot has the seed of its reset
+            self._starts_log.append((self._window, s, seed))          # (what reset(slot, seed) would keep)
+            if seed is None and self.sample:          # ... else one from the OS
+                seed = engine.os_seed()
+            buf[i, 0], buf[i, 1] = 1, engine.as_int64_bits(seed or 0)
+            self._first[i:i + 1].copy_(first[i], non_blocking=True)
+            self._started.add(s)
+        self._starts.copy_(staged, non_blocking=True)
+        self._starts_zero = not starts
 
     def _copy_in(self, mels, z, frames):
         real = sum(frames)

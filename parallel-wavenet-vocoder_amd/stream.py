@@ -150,22 +150,44 @@ def ragged_tick_counts(entries, in_frames: int, min_frames: int):
     return cu
 
 
-def ragged_tick_begin_tables(sess, kept, entries, mel, hop: int, min_frames: int, touched: Optional[dict] = None, sample: bool = True):
+def ragged_tick_starting(entries, starts, n_slots: int):
+    """(numpy restatement of tick_starting, csrc/pwv_stream_tick.hip)  bool [N]: the entries that START an utterance in this tick -- the flag
+    of `starts` (int64 [N, 2] = {flag, seed bits}; None: nobody starts) is set and the entry is no filler (live, slot in range)."""
+    entries = np.asarray(entries, np.int32).reshape(-1, 4)
+    if starts is None:
+        return np.zeros((entries.shape[0],), bool)
+    starts = np.asarray(starts, np.int64).reshape(-1, 2)
+    return (starts[:, 0] != 0) & (entries[:, 1] != 0) & (entries[:, 0] >= 0) & (entries[:, 0] < int(n_slots))
+
+
+def ragged_tick_begin_tables(sess, kept, entries, mel, hop: int, min_frames: int, touched: Optional[dict] = None, sample: bool = True,
+                             starts=None, first=None, zero_block: Optional[int] = None):
     """(numpy restatement of stream_tick_ragged_begin_kernel; tests, and the definition of the tables)  From the device session table
     `sess` (int64 [n_slots, 4]), the kept frames `kept` [n_slots, n_mels], the tick's `entries` (int32 [N, 4] = {slot, live, frames, 0})
     and its mel [in_frames, n_mels] (the sessions' new frames in entry order): (slot_tab int32 [N, 2], streams int64 [N, 2] = {seed,
     emitted}, cu_rows int32 [N + 1], cu_frames int32 [N + 1], chunk float32 [in_frames + N, n_mels]) -- what push_varlen builds on the
     host for the same running sessions.  `live` plays no part here: a filler reads and writes like any other entry.  sample=False (the
     tick has no sampler, `streams` NULL): streams is None.  `touched` (tests): a dict that receives, per array name, every index the
-    restatement reads or writes."""
+    restatement reads or writes.
+    `starts` (int64 [N, 2] = {flag, seed bits}), `first` (float32 [N, n_mels]) and `zero_block`: stream_tick_starts_begin_kernel.  An entry
+    that starts (ragged_tick_starting) reads `zero_block`, draws from {its seed, 0} and has first[i] where the kept frame would stand."""
     sess, kept, mel = np.asarray(sess, np.int64), np.asarray(kept, np.float32), np.asarray(mel, np.float32)
     entries = np.asarray(entries, np.int32).reshape(-1, 4)
     n, in_frames = entries.shape[0], mel.shape[0]
+    starting = ragged_tick_starting(entries, starts, sess.shape[0])
+    if starts is not None:
+        starts, first = np.asarray(starts, np.int64).reshape(-1, 2), np.asarray(first, np.float32)
+        if zero_block is None or int(zero_block) < 2 * sess.shape[0]:
+            raise ValueError('zero_block must be >= 2 * n_slots = %d (no session\'s block), got %r' % (2 * sess.shape[0], zero_block))
     cu = ragged_tick_counts(entries, in_frames, int(min_frames))
     slots = np.where((entries[:, 0] >= 0) & (entries[:, 0] < sess.shape[0]), entries[:, 0], 0)      # (out of range: a filler of slot 0)
     g = sess[slots, 0] & 1
     slot_tab = np.stack([2 * slots + g, 2 * slots + 1 - g], axis=1).astype(np.int32)
     streams = np.stack([sess[slots, 2], sess[slots, 1]], axis=1).astype(np.int64) if sample else None
+    if starting.any():
+        slot_tab[starting, 0] = int(zero_block)
+        if sample:
+            streams[starting, 0], streams[starting, 1] = starts[starting, 1], 0
     cu_rows = (cu * int(hop)).astype(np.int32)
     cu_frames = (cu + np.arange(n + 1)).astype(np.int32)
     chunk = np.zeros((in_frames + n, mel.shape[1]), np.float32)
@@ -175,8 +197,13 @@ def ragged_tick_begin_tables(sess, kept, entries, mel, hop: int, min_frames: int
     written = np.zeros((in_frames + n,), bool)
     for i in range(n):
         s, at = int(slots[i]), int(cu_frames[i])
-        seen['sess'].append(s), seen['kept'].append(s), seen['chunk'].append(at)
-        chunk[at] = kept[s]
+        seen['sess'].append(s), seen['chunk'].append(at)
+        if starting[i]:
+            seen.setdefault('first', []).append(i)
+            chunk[at] = first[i]
+        else:
+            seen['kept'].append(s)
+            chunk[at] = kept[s]
         written[at] = True
         for f in range(int(cu[i + 1] - cu[i])):
             seen['mel'].append(int(cu[i]) + f), seen['chunk'].append(at + 1 + f)
@@ -186,22 +213,28 @@ def ragged_tick_begin_tables(sess, kept, entries, mel, hop: int, min_frames: int
     return slot_tab, streams, cu_rows, cu_frames, chunk
 
 
-def ragged_tick_commit(sess, kept, entries, mel, hop: int, min_frames: int, words, touched: Optional[dict] = None):
+def ragged_tick_commit(sess, kept, entries, mel, hop: int, min_frames: int, words, touched: Optional[dict] = None, starts=None,
+                       first=None, zero_block: Optional[int] = None):
     """(numpy restatement of stream_tick_ragged_commit_kernel)  (sess, kept, committed) after the tick's last node: with both sticky
     `words` (give-up, range) zero every LIVE entry's session flips its generation, has emitted hop * f_i more samples and keeps the
-    last of its frames; otherwise -- and for every filler -- nothing changes.  Returns copies."""
+    last of its frames; otherwise -- and for every filler -- nothing changes.  Returns copies.
+    `starts` (int64 [N, 2] = {flag, seed bits}): stream_tick_starts_commit_kernel.  A live entry that starts has emitted hop * f_i samples
+    in all (set, not added) and its seed is the table's (`first` and `zero_block`, the begin kernel's, are taken and not read)."""
     sess, kept = np.array(sess, np.int64), np.array(kept, np.float32)
     mel = np.asarray(mel, np.float32)
     if int(words[0]) != 0 or int(words[1]) != 0:
         return sess, kept, False
     entries = np.asarray(entries, np.int32).reshape(-1, 4)
     cu = ragged_tick_counts(entries, mel.shape[0], int(min_frames))
+    starting = ragged_tick_starting(entries, starts, sess.shape[0])
     seen = {} if touched is None else touched
     for i, (slot, live) in enumerate(entries[:, :2]):
         if live and 0 <= slot < sess.shape[0]:
             seen.setdefault('sess', []).append(int(slot)), seen.setdefault('kept', []).append(int(slot))
             seen.setdefault('mel', []).append(int(cu[i + 1]) - 1)
             sess[slot, 0] ^= 1
+            if starting[i]:
+                sess[slot, 1], sess[slot, 2] = 0, np.asarray(starts, np.int64).reshape(-1, 2)[i, 1]
             sess[slot, 1] += int(hop) * int(cu[i + 1] - cu[i])
             kept[slot] = mel[int(cu[i + 1]) - 1]
     return sess, kept, True
@@ -263,9 +296,17 @@ class StreamingVocoder(object):
         self.layout = HistoryLayout([list(d) for d in m.dilations[:m.n_iaf]])
         store = model.store or get_default_store()
         self.device = store.device
-        floats = 2 * self.n_slots * self.layout.block_floats
-        self._hist = (hist_alloc(floats) if hist_alloc is not None
-                      else torch.zeros((floats,), dtype=torch.float32, device=self.device)).view(2 * self.n_slots, self.layout.block_floats)
+        # two blocks per slot and, behind them in the same allocation, the ZERO BLOCK: what a session that starts inside a graphed tick
+        # reads as its history (include/pwv_hip.h, "STARTS").  Nothing ever writes it -- every write index is 2 s + 1 - g -- and _hist
+        # is the view of the sessions' blocks alone.  A caller's hist_alloc (tests) is asked for the sessions' blocks and no more, as it
+        # always was: such a stream has no zero block (_zero_block None) and its graphed ticks take no starts.
+        blocks, floats = 2 * self.n_slots, self.layout.block_floats
+        if hist_alloc is not None:
+            self._hist_all, self._zero_block = hist_alloc(blocks * floats).view(blocks, floats), None
+        else:
+            self._hist_all, self._zero_block = torch.zeros(((blocks + 1) * floats,), dtype=torch.float32, device=self.device).view(blocks + 1, floats), blocks
+            self._hist_all[blocks].zero_()
+        self._hist = self._hist_all[:blocks]
         self._carry_tab = torch.tensor([[o, r, w, 0] for o, r, w in self.layout.carry], dtype=torch.int32).to(self.device)
         self._kept = torch.zeros((self.n_slots, self.n_mels), dtype=torch.float32, device=self.device)
         self._gen = [0] * self.n_slots              # the generation a push READS
@@ -350,7 +391,7 @@ class StreamingVocoder(object):
     def graphed_varlen(self, slots: int, rows: int, sample: bool = True, depth: int = 4, warmup: int = 2):
         """A RAGGED tick -- up to `slots` running sessions, `rows` samples in all, every session its own frame count -- captured into a HIP
         graph with the frame counts read and the commit made on the device (graph.GraphedRaggedStream; DESIGN.md section 9, "Graph
-        replay of a ragged tick")."""
+        replay of a ragged tick").  Its tick(..., starts={slot: seed}) begins utterances inside a tick, on fresh or running slots."""
         from .graph import GraphedRaggedStream
         return GraphedRaggedStream(self, slots, rows, sample=sample, depth=depth, warmup=warmup)
 

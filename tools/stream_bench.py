@@ -53,6 +53,9 @@ in one process, the round twice):
                           z comes as a list of pieces: the entries are uploaded with every tick, as on a server whose counts change
   ragged_graph_pipelined  8 ticks enqueued back to back, one verify(), divided by 8
   uniform                 one push of S sessions x the mean length, as in --ragged
+On the mixed cells a CHURN leg besides: in every tick one session ends and another starts on its slot, `churn_sync` with verify(), reset
+and the eager one-frame push in front of the tick (the protocol without starts), `churn_starts` with tick(starts=);
+`starts_not_slower_than_sync`: churn_starts <= churn_sync + spread in both rounds.
 `spread` = the largest difference between the two medians of a leg; `graph_not_slower_than_ragged`: ragged_graph <= ragged + spread in
 both rounds (`ragged_graph`, whose ticks repeat one table, is the graph's best case: see ragged_graph_varying).
 
@@ -240,8 +243,38 @@ def main():
             assert graphed.captures == 1 and graphed.eager_calls == 0
             n_ticks = args.warmup + args.steps
             assert stream.emitted(0) == warm + 2 * n_ticks * (10 * lens[0] + mean) + n_ticks * (lens[0] + lens_b[0])       # (varying: 2 n ticks, half of each)
+            if name.startswith('mixed_'):
+                # CHURN: in every tick one session ends and another starts on its slot (the slots in turn), the tick's rows unchanged
+                firsts = [rand(1, cfg.n_mels) for _ in lens]
+                began = [[torch.cat([firsts[i], m]) if i == r else m for i, m in enumerate(mels)] for r in range(S)]
+                turn, empty = [0], z_packed[:0]
+
+                def churn_sync():          # the protocol without starts: settle, reset, the eager one-frame push, then the tick
+                    r = turn[0] = (turn[0] + 1) % S
+                    graphed.verify()
+                    stream.reset(r)
+                    stream.push_varlen([firsts[r]], slots=[r], z=[empty])
+                    graphed.tick(mels, slots, z=z_packed)
+
+                def churn_starts():
+                    r = turn[0] = (turn[0] + 1) % S
+                    graphed.tick(began[r], slots, z=z_packed, starts={r: None})
+
+                churn = {'churn_sync': churn_sync, 'churn_starts': churn_starts}
+                for leg in churn:
+                    cell[leg] = {'ms': [], 'enqueue_ms': []}
+                for _ in range(2):
+                    for leg, fn in churn.items():
+                        ms, host = timed(fn, graphed.verify)
+                        cell[leg]['ms'].append(round(ms, 4))
+                        cell[leg]['enqueue_ms'].append(round(host, 4))
+                assert graphed.captures == 1 and graphed.eager_calls == 0
+                legs = dict(legs, **churn)
             cell['spread'] = round(max(abs(cell[leg]['ms'][0] - cell[leg]['ms'][1]) for leg in legs), 4)
             ratio = lambda a, b: [round(x / y, 3) for x, y in zip(cell[a]['ms'], cell[b]['ms'])]      # noqa: E731
+            if 'churn_starts' in cell:
+                cell['starts_over_sync'] = ratio('churn_starts', 'churn_sync')
+                cell['starts_not_slower_than_sync'] = all(a <= b + cell['spread'] for a, b in zip(cell['churn_starts']['ms'], cell['churn_sync']['ms']))
             cell['graph_over_ragged'] = ratio('ragged_graph', 'ragged')
             cell['graph_pipelined_over_ragged'] = ratio('ragged_graph_pipelined', 'ragged')
             cell['graph_over_uniform'] = ratio('ragged_graph', 'uniform')
