@@ -44,6 +44,9 @@ EXPORTED_SYMBOLS = (
     'pwv_wav_to_mel_db_f32', 'pwv_pack_proj_f32', 'pwv_instance_norm_workspace_bytes', 'pwv_instance_norm_f32', 'pwv_channel_affine_f32', 'pwv_add_f32', 'pwv_gate_f32',
 )
 
+# the entry points of the extension headers (include/pwv_hip_mel_stream.h): in the same library, outside pwv_hip.h and its list
+EXTENSION_SYMBOLS = ('pwv_wav_to_mel_db_stream_f32',)
+
 
 class PwvError(RuntimeError):
     pass
@@ -254,6 +257,35 @@ class StreamTickRaggedArgs(Structure):
         self.struct_size = ctypes.sizeof(StreamTickRaggedArgs)
 
 
+MEL_STREAM_REC = 12           # PWV_MEL_STREAM_REC: int64 per session of a streaming mel push
+# the fields of such a record, in order (include/pwv_hip_mel_stream.h)
+MEL_REC_FIELDS = ('carry_first', 'carry_len', 'chunk_off', 'chunk_len', 'first_frame', 'frames', 'final_len', 'read_block', 'write_block',
+                  'out_row', 'new_carry_first', 'max_word')
+
+
+class MelStreamArgs(Structure):
+    """pwv_mel_stream_args: one ragged push of the streaming mel front-end."""
+    _fields_ = [
+        ('struct_size', c_size_t),      # set by __init__
+        ('wav', c_void_p),
+        ('window', c_void_p),
+        ('mel_basis', c_void_p),
+        ('mel', c_void_p),
+        ('state', c_void_p),
+        ('max_key', c_void_p),
+        ('rec', c_void_p),
+        ('rec_host', c_void_p),
+        ('wav_len', c_int64), ('mel_rows', c_int64),
+        ('N', ctypes.c_int32), ('n_fft', ctypes.c_int32), ('hop', ctypes.c_int32), ('n_mels', ctypes.c_int32),
+        ('n_blocks', ctypes.c_int32), ('n_words', ctypes.c_int32),
+        ('amin', ctypes.c_float), ('max_db', ctypes.c_float), ('min_db', ctypes.c_float),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = ctypes.sizeof(MelStreamArgs)
+
+
 # per-source extra flags (none in the product; tools/probes/regw/README.md: the register-stationary probe kernel needs
 # `-mllvm -amdgpu-mfma-vgpr-form=1`, which is why the sources are compiled one by one)
 EXTRA_FLAGS = {}
@@ -296,7 +328,7 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
     if os.environ.get('PWV_LIB'):
         return LIB_PATH            # an explicitly chosen library is never rebuilt
     # every header and body of csrc/, by pattern: a new part can never be missing from the staleness check
-    hdrs = glob.glob(os.path.join(_PKG_DIR, 'csrc', '*.h')) + glob.glob(os.path.join(_PKG_DIR, 'csrc', '*.inc')) + [os.path.join(_REPO_ROOT, 'include', 'pwv_hip.h')]
+    hdrs = glob.glob(os.path.join(_PKG_DIR, 'csrc', '*.h')) + glob.glob(os.path.join(_PKG_DIR, 'csrc', '*.inc')) + glob.glob(os.path.join(_REPO_ROOT, 'include', '*.h'))
     hdr_time = max(os.path.getmtime(h) for h in hdrs + [os.path.abspath(__file__)])
     compiles = []                  # (source, object, command without the output)
     for src in CSRC:
@@ -399,6 +431,7 @@ def _declare(lib):
     lib.pwv_wavenet_stack_f32.argtypes = [POINTER(StackArgs), POINTER(c_void_p)]
     lib.pwv_pack_proj_f32.argtypes = [f32p, f32p, f32p, f32p, c_int, c_int, c_int, f32p, f32p, c_void_p]
     lib.pwv_wav_to_mel_db_f32.argtypes = [f32p, f32p, f32p, f32p, c_int, c_int, c_int, c_int, c_int] + [ctypes.c_float] * 4 + [c_int, c_void_p]
+    lib.pwv_wav_to_mel_db_stream_f32.argtypes = [POINTER(MelStreamArgs), c_void_p]
     lib.pwv_instance_norm_workspace_bytes.restype = c_size_t
     lib.pwv_instance_norm_workspace_bytes.argtypes = [c_int, c_int, c_int]
     lib.pwv_instance_norm_f32.argtypes = [f32p, f32p, c_int, c_int, c_int, f32p, f32p, ctypes.c_float, c_void_p, c_size_t, c_void_p]
@@ -420,7 +453,7 @@ def _declare(lib):
     lib.pwv_status_words_alloc.argtypes = [POINTER(c_void_p)]
     lib.pwv_status_words_free.argtypes = [c_void_p]
     lib.pwv_range_check_f32.argtypes = [f32p, c_int64, ctypes.c_float, c_void_p, c_void_p]
-    for name in EXPORTED_SYMBOLS:      # fails loudly (AttributeError) if a symbol is missing
+    for name in EXPORTED_SYMBOLS + EXTENSION_SYMBOLS:      # fails loudly (AttributeError) if a symbol is missing
         getattr(lib, name)
     return lib
 

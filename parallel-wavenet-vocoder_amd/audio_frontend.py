@@ -24,6 +24,7 @@ rate differs from hp.signal.sr).
 """
 from __future__ import annotations
 
+import ctypes
 from typing import Optional
 
 import numpy as np
@@ -151,6 +152,15 @@ def analysis_window(n_fft: int, win_length: int) -> np.ndarray:
 _device_consts = {}
 
 
+def _consts(device, s):
+    """(analysis window [n_fft], mel filterbank [n_mels, 1 + n_fft/2]) as fp32 on `device` for the signal settings `s`, built once."""
+    key = (device, s.sr, s.n_fft, s.win_length, s.n_mels)
+    if key not in _device_consts:
+        _device_consts[key] = (torch.from_numpy(analysis_window(s.n_fft, s.win_length).astype(np.float32)).to(device),
+                               torch.from_numpy(mel_filterbank(s.sr, s.n_fft, s.n_mels).astype(np.float32)).to(device))
+    return _device_consts[key]
+
+
 def wav_to_mel_device(wav, normalise: Optional[bool] = None):
     """wav [N, L] float32 on the GPU -> (normalised) dB mel [N, 1 + L/hop, n_mels] on the GPU (pwv_wav_to_mel_db_f32),
     with the current hparams' signal settings.  Like audio.wav2melspec_db (audio.py:350) the dB range is normalised only
@@ -161,11 +171,7 @@ def wav_to_mel_device(wav, normalise: Optional[bool] = None):
     if wav.dim() != 2:
         raise ValueError('wav must be [N, L], got %s' % (tuple(wav.shape),))
     n, length = wav.shape
-    key = (wav.device, s.sr, s.n_fft, s.win_length, s.n_mels)
-    if key not in _device_consts:
-        _device_consts[key] = (torch.from_numpy(analysis_window(s.n_fft, s.win_length).astype(np.float32)).to(wav.device),
-                               torch.from_numpy(mel_filterbank(s.sr, s.n_fft, s.n_mels).astype(np.float32)).to(wav.device))
-    window, basis = _device_consts[key]
+    window, basis = _consts(wav.device, s)
     mel = torch.empty((n, 1 + length // s.hop_length, s.n_mels), dtype=torch.float32, device=wav.device)
     if normalise is None:
         normalise = bool(s.get('max_db', None) and s.get('min_db', None))
@@ -174,6 +180,202 @@ def wav_to_mel_device(wav, normalise: Optional[bool] = None):
                                                 s.hop_length, s.n_mels, 1e-5, 80.0, max_db, min_db, int(normalise),
                                                 engine._stream()), 'pwv_wav_to_mel_db_f32')
     return mel
+
+
+# ---- the streaming front-end (include/pwv_hip_mel_stream.h; DESIGN.md section 9, "Streaming the mel front-end") ----
+TOP_DB = 80.0       # amplitude_to_db's floor below the utterance maximum (audio.py:347)
+AMIN = 1e-5
+
+
+def frames_ready(received: int, n_fft: int, hop: int) -> int:
+    """K(R): the frames of a centred, reflect-padded STFT whose every sample lies among the first `received` of the utterance, no right
+    reflection involved.  Frame 0's left reflection reads sample n_fft/2; frame k >= 1 ends at sample k hop + n_fft/2 - 1."""
+    h = n_fft // 2
+    return 0 if received < h + 1 else 1 + (received - h) // hop
+
+
+def carry_start(received: int, n_fft: int, hop: int) -> int:
+    """c(R): the first sample a session keeps between pushes.  Samples c .. R - 1 hold whatever a later frame can read: the next frame
+    to emit begins at K hop - n_fft/2, and a right reflection at any final length L >= R reaches back to 2 (L - 1) - (L + n_fft/2 - 1)
+    >= R - n_fft/2 - 1.  Fewer than n_fft samples."""
+    h = n_fft // 2
+    return max(0, min(frames_ready(received, n_fft, hop) * hop - h, received - h - 1))
+
+
+def mel_db_bound(sr: int, n_fft: int, win_length: int, n_mels: int) -> float:
+    """The raw dB no wav with |samples| <= 1 can exceed: every |STFT| bin is at most sum |window|, so a band is at most its filter's
+    row sum times that."""
+    return float(20.0 * np.log10(mel_filterbank(sr, n_fft, n_mels).sum(axis=1).max() * np.abs(analysis_window(n_fft, win_length)).sum()))
+
+
+def _key_to_db(key: int) -> Optional[float]:
+    """The float behind an order-preserving max word (None: nothing seen yet)."""
+    key = int(key)
+    if key == -(1 << 31):
+        return None
+    bits = key if key >= 0 else key ^ 0x7fffffff
+    return float(np.array([bits & 0xffffffff], dtype=np.uint32).view(np.float32)[0])
+
+
+class StreamingMel(object):
+    """wav chunks in, the frames of `wav_to_mel_device` on the whole utterance out -- bit for bit, as soon as their samples are there:
+
+        fe = StreamingMel(slots=4)
+        frames = fe.push([chunk_a, chunk_b], slots=[0, 2])      # [n_i >= 1] float32 on the GPU each -> [f_i, n_mels] each, f_i >= 0
+        tail = fe.finish(0)                                     # the frames that had to wait for the utterance's end
+
+    `slots` independent sessions.  A push emits frames K(R before) .. K(R after) - 1 of every session it feeds (frames_ready); finish
+    fixes the utterance's length at what was received and emits the rest, 1 + L // hop frames in all.  The pieces are views of one
+    packed result and go straight into StreamingVocoder.push_varlen.  push only enqueues.
+
+    NORMALISED mode only (both max_db and min_db set, else ValueError): the one-shot's top_db floor needs the utterance's maximum,
+    which a stream does not have yet; after normalisation the floor changes nothing while max - top_db <= min_db.  No floor is applied
+    here; every session's largest raw dB is kept on the device, and verify() / finish() raise a PwvError naming top_db for a session
+    whose maximum exceeds min_db + top_db: its frames are not the one-shot's.  With the default hparams no wav within [-1, 1] gets
+    there (mel_db_bound: 17 dB against 25).
+
+    `signal`: the settings (sr, n_fft, win_length, hop_length, n_mels, max_db, min_db), default hp.signal."""
+
+    def __init__(self, slots: int, signal=None, device=None):
+        from . import _lib
+        s = hp.signal if signal is None else signal
+        get = (lambda k: s.get(k, None)) if hasattr(s, 'get') else (lambda k: getattr(s, k, None))
+        if not (get('max_db') and get('min_db')):
+            raise ValueError('StreamingMel is the normalised front-end: signal.max_db and signal.min_db must both be set '
+                             '(the top_db floor of the raw dB needs the whole utterance)')
+        if int(slots) < 1:
+            raise ValueError('slots must be >= 1, got %r' % (slots,))
+        self.n_slots = int(slots)
+        self.sr, self.n_fft, self.win_length = int(get('sr')), int(get('n_fft')), int(get('win_length'))
+        self.hop, self.n_mels = int(get('hop_length')), int(get('n_mels'))
+        self.max_db, self.min_db = float(get('max_db')), float(get('min_db'))
+        if self.n_fft < 2 or self.n_fft % 2 or self.n_fft > 2048 or self.hop < 1 or self.max_db == self.min_db:
+            raise ValueError('StreamingMel: n_fft must be even and <= 2048, hop_length >= 1, max_db != min_db')
+        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        self._lib = _lib
+        self._window, self._basis = _consts(self.device, _Signal(self.sr, self.n_fft, self.win_length, self.n_mels))
+        # two blocks of n_fft floats per slot: a push reads block 2 s + gen and writes block 2 s + 1 - gen
+        self._state = torch.zeros((2 * self.n_slots, self.n_fft), dtype=torch.float32, device=self.device)
+        self._max = torch.full((self.n_slots,), -(1 << 31), dtype=torch.int32, device=self.device)
+        self._gen = [0] * self.n_slots
+        self._received = [0] * self.n_slots
+        self._emitted = [0] * self.n_slots
+
+    # -- bookkeeping -----------------------------------------------------------------------------------------------------
+    def _slot(self, slot) -> int:
+        s = int(slot)
+        if not 0 <= s < self.n_slots:
+            raise ValueError('slot %r out of range (0 .. %d)' % (slot, self.n_slots - 1))
+        return s
+
+    def received(self, slot) -> int:
+        """Samples given to `slot` since its last reset."""
+        return self._received[self._slot(slot)]
+
+    def emitted(self, slot) -> int:
+        """Frames `slot` has returned since its last reset."""
+        return self._emitted[self._slot(slot)]
+
+    def state_bytes(self, slot=0) -> int:
+        """Bytes of device memory one session holds: two generations of the carry block and the maximum word."""
+        self._slot(slot)
+        return 2 * self.n_fft * 4 + 4
+
+    def reset(self, slot) -> None:
+        """`slot` starts a new utterance (enqueue-only: the carry needs no clearing, its length is zero)."""
+        s = self._slot(slot)
+        self._received[s], self._emitted[s] = 0, 0
+        self._max[s:s + 1].fill_(-(1 << 31))
+
+    def max_db_seen(self, slot) -> Optional[float]:
+        """The largest raw dB of `slot`'s utterance so far (None before its first frame).  Synchronises."""
+        return _key_to_db(self._max[self._slot(slot)].item())
+
+    def verify(self, slots=None) -> None:
+        """Wait for the pushes so far and raise a PwvError for every session (of `slots`, default all) whose largest raw dB exceeds
+        min_db + top_db: the one-shot would have clipped its quiet bands at max - top_db, above min_db, and its frames differ."""
+        slots = list(range(self.n_slots)) if slots is None else [self._slot(v) for v in slots]
+        keys = self._max.cpu().tolist()
+        limit = self.min_db + TOP_DB
+        over = [(s, _key_to_db(keys[s])) for s in slots if _key_to_db(keys[s]) is not None and _key_to_db(keys[s]) > limit]
+        if over:
+            raise self._lib.PwvError('StreamingMel: the top_db floor of the one-shot front-end would have been active for slot(s) %s: largest raw dB %s '
+                                     '> min_db + top_db = %g; their frames are not the one-shot\'s (compute those utterances with wav_to_mel_device)'
+                                     % ([s for s, _ in over], ['%.2f' % v for _, v in over], limit))
+
+    # -- a push ----------------------------------------------------------------------------------------------------------
+    def _launch(self, slots, chunks, finishing: bool):
+        """One ragged launch: slots[i] receives chunks[i] (finishing: nothing, and its utterance ends).  Returns the frame pieces."""
+        from . import engine
+        lib = self._lib
+        recs, off, row = [], 0, 0
+        after = []
+        for s, chunk in zip(slots, chunks):
+            n = 0 if finishing else int(chunk.shape[0])
+            r0, k0 = self._received[s], self._emitted[s]
+            r1 = r0 + n
+            k1 = 1 + r1 // self.hop if finishing else frames_ready(r1, self.n_fft, self.hop)
+            c0 = carry_start(r0, self.n_fft, self.hop)
+            c1 = c0 if finishing else carry_start(r1, self.n_fft, self.hop)
+            frames = max(k1 - k0, 0)
+            recs.append([c0, r0 - c0, off, n, k0, frames, r1 if finishing else -1, 2 * s + self._gen[s], 2 * s + 1 - self._gen[s], row, c1, s])
+            after.append((s, r1, k0 + frames, row, frames))
+            off, row = off + n, row + frames
+        assert all(len(r) == lib.MEL_STREAM_REC for r in recs)
+        wav = None if finishing else (chunks[0] if len(chunks) == 1 else torch.cat(chunks))
+        mel = torch.empty((row, self.n_mels), dtype=torch.float32, device=self.device)
+        rec_host = torch.tensor(recs, dtype=torch.int64).pin_memory()
+        rec = rec_host.to(self.device, non_blocking=True)
+        a = lib.MelStreamArgs()
+        a.wav, a.wav_len = (None, 0) if wav is None else (wav.data_ptr(), off)
+        a.window, a.mel_basis = self._window.data_ptr(), self._basis.data_ptr()
+        a.mel, a.mel_rows = (mel.data_ptr() if row else None), row
+        a.state, a.max_key = self._state.data_ptr(), self._max.data_ptr()
+        a.rec, a.rec_host = rec.data_ptr(), rec_host.data_ptr()
+        a.N, a.n_fft, a.hop, a.n_mels = len(slots), self.n_fft, self.hop, self.n_mels
+        a.n_blocks, a.n_words = 2 * self.n_slots, self.n_slots
+        a.amin, a.max_db, a.min_db = AMIN, self.max_db, self.min_db
+        lib.check(lib.lib().pwv_wav_to_mel_db_stream_f32(ctypes.byref(a), engine._stream()), 'pwv_wav_to_mel_db_stream_f32')
+        out = []
+        for s, r1, k1, first, frames in after:       # the launch is enqueued: the sessions advance (stream order keeps the generations apart)
+            self._received[s], self._emitted[s] = r1, k1
+            self._gen[s] ^= 1
+            out.append(mel[first:first + frames])
+        return out
+
+    def push(self, chunks, slots=None):
+        """Session slots[i] (default: all slots, in order) receives its next samples chunks[i], [n_i >= 1] float32 on the GPU.  Returns
+        the list of [f_i, n_mels] frame tensors that became ready (f_i may be 0), views of one packed result.  Enqueue-only."""
+        from . import engine
+        if not isinstance(chunks, (list, tuple)) or not chunks:
+            raise ValueError('chunks must be a non-empty list of [n] tensors')
+        slots = list(range(self.n_slots)) if slots is None else [self._slot(v) for v in slots]
+        if len(slots) != len(chunks) or len(set(slots)) != len(slots):
+            raise ValueError('slots must be distinct, one per chunk (%d chunks), got %r' % (len(chunks), slots))
+        for i, c in enumerate(chunks):
+            if not hasattr(c, 'dim') or c.dim() != 1 or c.shape[0] < 1:
+                raise ValueError('chunks[%d] must be [n >= 1], got %s' % (i, tuple(getattr(c, 'shape', ()))))
+        chunks = [engine._require_cuda_f32(c, 'chunks[%d]' % i) for i, c in enumerate(chunks)]
+        return self._launch(slots, chunks, False)
+
+    def finish(self, slot):
+        """The utterance of `slot` ends at the samples received, L: returns its last frames (1 + L // hop in all with those returned
+        before), the right reflection taken at L.  L <= n_fft / 2 is refused, as by the one-shot.  Verifies the slot (synchronises): a
+        PwvError naming top_db if its frames are not the one-shot's.  The slot is fresh afterwards, as after reset."""
+        s = self._slot(slot)
+        out = self._launch([s], [None], True)[0]
+        try:
+            self.verify([s])
+        finally:
+            self.reset(s)
+        return out
+
+
+class _Signal(object):
+    """The signal settings the device constants depend on."""
+
+    def __init__(self, sr, n_fft, win_length, n_mels):
+        self.sr, self.n_fft, self.win_length, self.n_mels = sr, n_fft, win_length, n_mels
 
 
 def load_wav_fixed(path: str, length: int) -> np.ndarray:

@@ -12,7 +12,7 @@ follow from the platform, not from the math:
     TensorBoard audio summaries, generate.py:71-73);
   * `data_path: 'synthetic'` (bench cases) or a glob of .npy mel files replaces the wav dataset;
     wav input uses the torch STFT front-end in audio_frontend.py.
-CLI (python-fire style, fire itself is not installed):  python -m pwv_amd.generate <case> [--ckpt=..] [--debug] [--varlen [--seed=S]] [--stream=FRAMES [--graph]]
+CLI (python-fire style, fire itself is not installed):  python -m pwv_amd.generate <case> [--ckpt=..] [--debug] [--varlen [--seed=S]] [--stream=FRAMES [--graph | --live]]
 """
 from __future__ import absolute_import, division, print_function
 
@@ -139,7 +139,7 @@ def _load_mels_varlen(data_path, batch_size, device):
     return mels
 
 
-def generate(case='default', ckpt=None, debug=False, varlen=False, seed=None, stream=None, graph=False):
+def generate(case='default', ckpt=None, debug=False, varlen=False, seed=None, stream=None, graph=False, live=False):
     '''
     :param case: experiment case name
     :param ckpt: checkpoint to load model
@@ -153,7 +153,11 @@ def generate(case='default', ckpt=None, debug=False, varlen=False, seed=None, st
     :param graph: (with stream) every tick is one replay of a captured ragged tick (StreamingVocoder.graphed_varlen at a capacity of one
         slot per input and inputs x `stream` frames), the first one included: it starts the sessions (tick(starts=)); only an input too
         short for that starts with the eager one-frame push; same files.
+    :param live: (with stream, wav inputs) the front-end streams too: every tick gives each unfinished input its next `stream` x hop
+        SAMPLES through audio_frontend.StreamingMel, and the frames that became ready to the sessions; same files.
     '''
+    if live and (stream is None or graph):
+        raise ValueError('--live applies to --stream=FRAMES without --graph (wav chunks in, wav chunks out)')
     if graph and stream is None:
         raise ValueError('--graph applies to --stream=FRAMES (graph replay of the ragged ticks)')
     if stream is not None:
@@ -169,6 +173,7 @@ def generate(case='default', ckpt=None, debug=False, varlen=False, seed=None, st
         if not 0 <= seed < (1 << 64):
             raise ValueError('--seed must be in [0, 2**64), got %d' % seed)
     hp.set_hparam_yaml(case)
+    live_files = _live_inputs(hp.data_path, hp.generate.batch_size) if live else None
     if not torch.cuda.is_available():
         raise RuntimeError('generate() needs an MI355X: the HIP path has no CPU fallback')
     if int(os.environ.get('WORLD_SIZE', '1')) > 1:
@@ -185,7 +190,10 @@ def generate(case='default', ckpt=None, debug=False, varlen=False, seed=None, st
         # one process per GPU (torchrun): utterances -- or, for a batch smaller than the world, time slices -- shard over
         # the ranks; rank 0 reads the inputs and writes the outputs
         return _generate_over_ranks(store, batch_size, length, device, logdir, ckpt, debug)
-    if varlen or stream:
+    if live:
+        gt_wav, melspec, wavs = None, None, _load_wavs_live(live_files)
+        batch_size, length = 1, sum(len(w) for w in wavs)
+    elif varlen or stream:
         gt_wav, melspec = None, _load_mels_varlen(hp.data_path, batch_size, device)
         batch_size, length = 1, sum(int(m.shape[0] - 1) * hp.signal.hop_length for m in melspec)     # (the timing line: all samples)
     else:
@@ -208,7 +216,9 @@ def generate(case='default', ckpt=None, debug=False, varlen=False, seed=None, st
     # launches, a forward that left the range of the split-fp16 arithmetic in exact fp32 -- on the same noise
     # (engine.verified_call); what comes back is what the reference's fp32 sess.run would have produced, or an exception.
     # verify=True is EXPLICIT: it outranks PWV_ASYNC=1 (whose default is enqueue-only) -- nothing unverified is written to disk
-    if stream:
+    if live:
+        pred = _generate_stream_live(model, wavs, stream, device)
+    elif stream:
         pred = _generate_stream_graph(model, melspec, stream) if graph else _generate_stream(model, melspec, stream)
     elif varlen:
         pred = model.generate_varlen(melspec, verify=True, seeds=None if seed is None else [seed] * len(melspec))
@@ -257,6 +267,61 @@ def _generate_stream(model, mels, frames):
         for k, (i, f) in enumerate(zip(slots, counts)):
             outs[i].append(got[k])
             pos[i] += f
+    return [torch.cat(o) for o in outs]
+
+
+def _live_inputs(data_path, batch_size):
+    """--stream --live: the files _load_mels_varlen would read.  Inputs that are no audio (.npy mels, 'synthetic') have nothing to stream
+    a front-end over: ValueError."""
+    files = [] if data_path == 'synthetic' else sorted(glob.glob(data_path))
+    if data_path != 'synthetic' and not files:
+        raise FileNotFoundError('no input files match data_path %r' % data_path)
+    split = int(len(files) * hp.train.dataset_ratio)
+    files = (files[split:] or files)[:batch_size]
+    if not files or any(f.endswith('.npy') for f in files):
+        raise ValueError('--live streams the mel front-end over wav inputs: data_path %r holds %s' % (data_path, '.npy mels' if files else 'no audio'))
+    return files
+
+
+def _load_wavs_live(files):
+    """--stream --live: the inputs as SAMPLES -- every wav trimmed (data_load.py:42-44) and cut down to a multiple of hop_length, as
+    _load_mels_varlen cuts it."""
+    from .audio_frontend import read_wav, trim_wav
+    hop = hp.signal.hop_length
+    wavs = []
+    for f in files:
+        wav = trim_wav(read_wav(f, hp.signal.sr))
+        wav = wav[:len(wav) // hop * hop].astype(np.float32)
+        if len(wav) == 0:
+            raise ValueError('%s: shorter than one hop (%d samples) after trimming' % (f, hop))
+        wavs.append(wav)
+    print('dataset size is {}'.format(len(wavs)))
+    return wavs
+
+
+def _generate_stream_live(model, wavs, frames, device):
+    """--stream=FRAMES --live: input i is session i of one StreamingMel and of one StreamingVocoder.  Every tick gives each unfinished
+    input its next frames x hop samples in ONE ragged front-end push; an input whose samples are used up is finished in the same tick
+    (its last frames, the right reflection at its length); the frames of the tick go to the sessions in ONE push_varlen (verify=True, as
+    _generate_stream).  A session with no frame yet -- the front-end emits its first frame after n_fft / 2 + 1 samples -- sits the tick
+    out.  Returns the [len_i, 1] waveforms: 1 + len_i / hop frames each, so len_i samples, as --varlen."""
+    from .audio_frontend import StreamingMel
+    n, step = len(wavs), frames * int(hp.signal.hop_length)
+    fe, s = StreamingMel(n, device=device), model.open_stream(slots=n)
+    wavs = [torch.from_numpy(w).to(device) for w in wavs]
+    pos, done, outs = [0] * n, [False] * n, [[] for _ in wavs]
+    while not all(done):
+        feed = [i for i in range(n) if pos[i] < wavs[i].shape[0]]
+        ready = dict(zip(feed, fe.push([wavs[i][pos[i]:pos[i] + step] for i in feed], slots=feed)))
+        for i in feed:
+            pos[i] += step
+            if pos[i] >= wavs[i].shape[0]:
+                ready[i], done[i] = torch.cat([ready[i], fe.finish(i)]), True
+        slots = [i for i in feed if ready[i].shape[0]]
+        if slots:
+            got = s.push_varlen([ready[i] for i in slots], slots=slots, verify=True)
+            for k, i in enumerate(slots):
+                outs[i].append(got[k])
     return [torch.cat(o) for o in outs]
 
 

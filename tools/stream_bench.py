@@ -60,6 +60,18 @@ and the eager one-frame push in front of the tick (the protocol without starts),
 both rounds (`ragged_graph`, whose ticks repeat one table, is the graph's best case: see ragged_graph_varying).
 
     python tools/stream_bench.py --ragged-graph [--steps 20] [--warmup 5] [--precision f16x3]
+
+--live ("Streaming the mel front-end"): what the streaming front-end (audio_frontend.StreamingMel) adds to a tick.
+One cell: 8 running sessions x 10 frames (800 samples each).  Legs, same protocol (explicit z, one synchronisation per tick, median of
+--steps after --warmup, the legs one after the other in one process, the round twice):
+  vocoder    push_varlen(verify=False) of 8 x 10 ready-made frames + verify(): the tick without a front-end
+  live       StreamingMel.push of 8 x 800 samples, its 8 x 10 frames into the same push_varlen + verify(): wav chunks in, wav chunks out
+  frontend   StreamingMel.push alone + a synchronisation
+  one_shot   wav_to_mel_device on the same [8, 800] samples + a synchronisation: the whole-utterance kernel on a tick's worth (11 frames
+             each, both edges reflected -- not the frames of a stream)
+`spread` = the largest difference between the two medians of a leg; `live_over_vocoder` per round.
+
+    python tools/stream_bench.py --live [--steps 20] [--warmup 5] [--precision f16x3]
 """
 import argparse
 import json
@@ -83,6 +95,7 @@ def main():
     ap.add_argument('--graph', action='store_true', help='the graphed-tick cells (StreamingVocoder.graphed against the eager push) instead of the default legs')
     ap.add_argument('--ragged-graph', action='store_true',
                     help='the ragged-tick cells as graph replays (StreamingVocoder.graphed_varlen against the eager push_varlen) instead of the default legs')
+    ap.add_argument('--live', action='store_true', help='the streaming mel front-end in front of push_varlen (audio_frontend.StreamingMel) instead of the default legs')
     args = ap.parse_args()
 
     import numpy as np
@@ -138,6 +151,42 @@ def main():
                     return fn(*a)
                 return wrapped
         return Counting()
+
+    if args.live:
+        from pwv_amd.audio_frontend import StreamingMel, wav_to_mel_device
+        S, frames = 8, 10
+        chunk = frames * hop
+        out = {'mode': 'live', 'precision': args.precision, 'steps': args.steps, 'warmup': args.warmup, 'sessions': S, 'frames': frames, 'chunk': chunk}
+        model = IAFVocoder(batch_size=S, length=hop, store=store, precision=args.precision)
+        stream = model.open_stream(slots=S)
+        warm = -(-(halo + hop) // hop) * hop
+        stream.push(rand(S, warm // hop + 1, cfg.n_mels), z=rand(S, warm, 1))        # steady state: every session running
+        fe = StreamingMel(S)
+        fe.push(list(0.5 * rand(S, chunk)))                                           # steady state: every later 800 samples bring 10 frames
+        wav = 0.5 * rand(S, chunk)
+        chunks, mels, zs = list(wav), [rand(frames, cfg.n_mels) for _ in range(S)], [rand(chunk, 1) for _ in range(S)]
+        assert [int(m.shape[0]) for m in fe.push(chunks)] == [frames] * S
+
+        legs = {
+            'vocoder': (lambda: stream.push_varlen(mels, z=zs, verify=False), stream.verify),
+            'live': (lambda: stream.push_varlen(fe.push(chunks), z=zs, verify=False), stream.verify),
+            'frontend': (lambda: fe.push(chunks), torch.cuda.synchronize),
+            'one_shot': (lambda: wav_to_mel_device(wav), torch.cuda.synchronize),
+        }
+        for leg in legs:
+            out[leg] = {'ms': [], 'enqueue_ms': []}
+        for _ in range(2):
+            for leg, (fn, sync) in legs.items():
+                ms, host = timed(fn, sync)
+                out[leg]['ms'].append(round(ms, 4))
+                out[leg]['enqueue_ms'].append(round(host, 4))
+        fe.verify()
+        out['state_bytes_per_session'] = fe.state_bytes()
+        out['spread'] = round(max(abs(out[leg]['ms'][0] - out[leg]['ms'][1]) for leg in legs), 4)
+        out['live_over_vocoder'] = [round(a / b, 3) for a, b in zip(out['live']['ms'], out['vocoder']['ms'])]
+        out['live_minus_vocoder_ms'] = [round(a - b, 4) for a, b in zip(out['live']['ms'], out['vocoder']['ms'])]
+        print(json.dumps(out))
+        return
 
     if args.ragged:
         out = {'mode': 'ragged', 'precision': args.precision, 'steps': args.steps, 'warmup': args.warmup, 'cells': []}
