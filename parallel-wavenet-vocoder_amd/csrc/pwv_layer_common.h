@@ -129,6 +129,26 @@ __device__ __forceinline__ void unit_rows_varlen(const int* unit_map, int unit, 
     fb = second ? f1 : f0;
 }
 
+// The same in two steps, for a caller that maps a unit's rows twice (the persistent loop: when it requests the rows, and a unit later at the top of
+// the unit that uses them): the record's four scalars {cu_rows[n], cu_frames[n], cu_rows[n+1], cu_frames[n+1]}, read once, and the mapping from them.
+__device__ __forceinline__ void unit_record_varlen(const int* unit_map, int unit, int rows, int (&rec)[4]) {
+    typedef const __attribute__((address_space(4))) int* const_ints_t;
+    const int last = (rows - 1) >> 5;
+    const const_ints_t r = (const_ints_t)(unit_map + (size_t)(unit < last ? unit : last) * kVarlenRec);
+    rec[0] = r[1];
+    rec[1] = r[2];
+    rec[2] = r[3];
+    rec[3] = r[4];
+}
+__device__ __forceinline__ void unit_rows_from_record(const int (&rec)[4], int unit, int lane, int rows, int& row, bool& valid, int& rc, int& fb, int& t) {
+    row = unit * 32 + (lane & 31);
+    valid = row < rows;
+    rc = valid ? row : rows - 1;
+    const bool second = rc >= rec[2];
+    t = rc - (second ? rec[2] : rec[0]);
+    fb = second ? rec[3] : rec[1];
+}
+
 // -DPWV_TRACE: waves of workgroup 0 record s_memtime at phase boundaries (tools/trace_layer.py)
 #ifdef PWV_TRACE
 #define PWV_STAMP(slot)                                                                   \

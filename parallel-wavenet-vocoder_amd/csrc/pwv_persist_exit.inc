@@ -26,6 +26,7 @@
         pt_acc[0] = pt_acc[8] - pt_start;
         long long* tr = p.trace + ((size_t)blockIdx.x * 8 + wave) * 24;
         for (int k = 0; k < 15; ++k) tr[k] = pt_acc[k];
+        for (int k = 15; k < 18; ++k) tr[k + 6] = pt_acc[k];
         tr[16] = net; tr[17] = w; tr[18] = dead ? 1 : 0; tr[19] = __builtin_amdgcn_s_memrealtime(); tr[20] = pt_start_rt;
     }
 #endif

@@ -2,8 +2,8 @@
 // layers' weights, the ring and P descriptors, the history look-back / store of the streaming forms and the row loaders.
 // Expects: F32, MODE, VARLEN, STREAM, p.
 // Defines: SHORT, RAGGED, stat, loader_mode, lds, tid, lane, wave, h, net, w, rows, u_begin, u_end, n, L, ctl, lb, prog_n, uprog_n, proj_n,
-//          packed_n, ring_rs, proj_rs; rows_of, p_base, unit_rec, session_end, dil_of, dil_next, fill_slot, in_soff, out_soff, toff,
-//          hist_lookback, hist_store, load_x, load_xc, load_xb.
+//          packed_n, ring_rs, proj_rs, proj_rs_at; rows_of, rows_of_top, top_rec, top_scalar, p_base, unit_rec, session_end, dil_of, dil_next,
+//          fill_slot, in_soff, out_soff, toff, hist_lookback, hist_store, load_x, load_xc, load_xb.
     constexpr bool SHORT = MODE == 2;      // progress words per unit, stationary units, loader wave, ... (everything below that says SHORT)
     __shared__ __attribute__((aligned(16))) float lds[kLdsFloats];
     const int tid = threadIdx.x;
@@ -29,9 +29,26 @@
         if constexpr (VARLEN) unit_rows_varlen(p.unit_map, unit, lane, rows, row, valid, rc, nn, t);
         else unit_rows(unit, lane, rows, p.N, p.T, p.T_magic, p.T_shift, row, valid, rc, nn, t);
     };
+    // the per-layer dilations live in one VGPR (lane j holds entry j), read with v_readlane: a dynamically indexed kernel
+    // argument is a scalar LOAD plus a wait each time.  The general loop keeps the scalars of the P row's address in the lanes behind
+    // them: left as kernel arguments they are loop-invariant values the register allocator has no SGPR for, and it rematerialises them
+    // as scalar loads, each with its own wait, in front of the P loads of EVERY unit (tests/test_persist_top_isa.py)
+    constexpr int kLaneStride = kMaxPLayers, kLaneHopMagic = kMaxPLayers + 1, kLaneHopShift = kMaxPLayers + 2, kLaneCondOffset = kMaxPLayers + 3,
+                  kLaneCondFrames = kMaxPLayers + 4;
+    static_assert(kMaxPLayers + 5 <= 64, "the dilations and the P row's scalars share one VGPR");
+    int v_dil = p.dil[lane & (kMaxPLayers - 1)];
+    if constexpr (!SHORT) {
+        const int k = lane - kMaxPLayers;
+        const int c = k == 0 ? p.proj_row_stride : (k == 1 ? (int)p.hop_magic : (k == 2 ? (int)p.hop_shift : (k == 3 ? p.cond_offset : p.cond_frames)));
+        v_dil = k >= 0 ? c : v_dil;
+    }
+    auto dil_of = [&](int j) -> int { return __builtin_amdgcn_readlane(v_dil, j); };
+    auto top_scalar = [&](int k) -> int { return __builtin_amdgcn_readlane(v_dil, k); };
+    (void)top_scalar;
     auto p_base = [&](int nn) -> int {
         if constexpr (VARLEN) return nn;
-        else return nn * p.cond_frames;
+        else if constexpr (SHORT) return nn * p.cond_frames;
+        else return nn * top_scalar(kLaneCondFrames);
     };
     // RAGGED (VARLEN && STREAM: sessions of different chunk lengths in one packed launch).  The streaming code needs two things the packed
     // row mapping does not hand out: the lane's session INDEX (slot_tab is indexed by it; `nn` is a frame base here) and the END of the
@@ -72,10 +89,6 @@
     int* uprog_n = p.uprog + (size_t)net * p.units * kUnitStride;
     const float* const proj_n = p.proj[net];
     const float* const packed_n = p.packed[net];
-    // the per-layer dilations live in one VGPR (lane j holds entry j), read with v_readlane: a dynamically indexed kernel
-    // argument is a scalar LOAD plus a wait each time
-    const int v_dil = p.dil[lane & (kMaxPLayers - 1)];
-    auto dil_of = [&](int j) -> int { return __builtin_amdgcn_readlane(v_dil, j); };
     // the layer that reads layer j's rows next: j + 1 of this launch, the tail's layer behind the last one, else (another launch
     // follows: anything) its own
     auto dil_next = [&](int j) -> int { return j + 1 < L ? dil_of(j + 1) : (p.tail_q > 0 ? p.tail_dil : dil_of(j)); };
@@ -93,6 +106,18 @@
     auto fill_slot = [&](int slot, int layer, int first, int step) {
         const float* src = packed_n + (size_t)layer * p.packed_stride + lane * 4;
         float* dst = lds + slot * kSlot;
+        if constexpr (!SHORT) {
+            // (general loop: the refill as BUFFER loads to LDS.  A global_load ... lds is a FLAT-encoded instruction that touches LDS and memory, and while the
+            //  compiler knows of one in flight it turns every vector-memory wait it places into vmcnt(0); it never learns that the refill has landed -- the
+            //  drains of this loop are inline asm -- so with the global form no load of the task loop is ever left in flight across a compiler's wait:
+            //  tests/test_persist_top_isa.py.  Same bytes to the same LDS addresses: lane l's 16 bytes go to the chunk's base + 16 l either way.)
+            const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc((void*)(packed_n + (size_t)layer * p.packed_stride), 0, (kSlotFull + 64) * 4, 0x00020000);
+#pragma clang loop unroll(disable)
+            for (int c = first; c < kSlot / 256; c += step)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(prs, (lptr_t)(dst + c * 256), 16, lane * 16, c * 1024, 0, 0);
+            if (first == 0 && lane < 16) __builtin_amdgcn_raw_ptr_buffer_load_lds(prs, (lptr_t)(lds + kBiasF + slot * 64), 16, lane * 16, kSlotFull * 4, 0, 0);
+            return;
+        }
 #pragma clang loop unroll(disable)
         for (int c = first; c < kSlot / 256; c += step)
             __builtin_amdgcn_global_load_lds((gptr_t)(src + c * 256), (lptr_t)(dst + c * 256), 16, 0, 0);
@@ -119,6 +144,12 @@
         return __builtin_amdgcn_make_buffer_rsrc((void*)(((unsigned long long)hi2 << 32) | lo), 0, 0xFFFFFFFFu, 0x00020000);
     }();
     (void)proj_rs;
+    // (the general loop: a descriptor that starts `floats` -- wave-uniform: the unit's FIRST P row -- behind proj_n.  Its 32-bit offsets then span the
+    //  P rows of one unit and never the whole of P, which a long batch takes past the 4 GB a descriptor reaches)
+    auto proj_rs_at = [&](long long floats) -> __amdgpu_buffer_rsrc_t {
+        return __builtin_amdgcn_make_buffer_rsrc((void*)(proj_n + floats), 0, 0xFFFFFFFFu, 0x00020000);
+    };
+    (void)proj_rs_at;
     const int slot_bytes = (int)(p.ring_stride * 4);
     // (RAGGED: the rotation is pinned in a register of its own.  Left as a kernel argument it is merged into a 16-byte scalar load that the general
     //  instantiations' register allocation marks for a spill slot and then rematerialises: no spill code, but 20 bytes of scratch reserved per lane)
@@ -162,10 +193,12 @@
     // history store: lanes with t >= T - d store their row of layer `jh`'s input to row t + d - T of the block their session writes
     // (RAGGED: T is the lane's session's own T_n, k = rc + d - the session's end.  The fence needs no load beyond the unit's record: a lane of
     //  the unit's first session stores iff it lies within d rows of rec[3]; a unit with a lane of a second session is a boundary unit anyway)
-    auto hist_store = [&](int jh, int d, int nn, int t, int unit, int rc, bool valid, const float (&xr)[32]) {
+    // (`r1_top` >= 0: the end of the unit's first session as the caller already holds it -- the general loop's top_rec -- instead of a read of the record)
+    auto hist_store = [&](int jh, int d, int nn, int t, int unit, int rc, bool valid, const float (&xr)[32], int r1_top = -1) {
         if constexpr (RAGGED) {
-            int s0, r1;
-            unit_rec(unit, s0, r1);
+            int s0 = 0, r1 = r1_top;
+            if (r1_top < 0) unit_rec(unit, s0, r1);
+            (void)s0;
             const bool second = rc >= r1;
             int k = rc + d - r1;                        // (a lane of the unit's first session)
             if (__any(valid && (second || k >= 0))) {
@@ -200,10 +233,24 @@
     };
 
     // x[t-d] / x[t] rows of one unit -> registers
+    // (packed batches, general loop: the record of the unit whose rows load_x requested last -- every unit of the task loop has its rows requested by
+    //  load_x before its top runs, so the top maps its rows from these four scalars instead of reading the record a second time: a scalar load and
+    //  its wait on the address path of the P row, in every unit)
+    int top_rec[4] = {0, 0, 0, 0};
+    auto rows_of_top = [&](int unit, int& row, bool& valid, int& rc, int& nn, int& t) {
+        if constexpr (VARLEN && !SHORT) unit_rows_from_record(top_rec, unit, lane, rows, row, valid, rc, nn, t);
+        else rows_of(unit, row, valid, rc, nn, t);
+    };
+    (void)rows_of_top;
     auto load_x = [&](int j, int unit, float (&xb)[32], float (&xc)[32]) {
         int row, rc, nn, t;
         bool valid;
-        rows_of(unit, row, valid, rc, nn, t);
+        if constexpr (VARLEN && !SHORT) {
+            unit_record_varlen(p.unit_map, unit, rows, top_rec);
+            unit_rows_from_record(top_rec, unit, lane, rows, row, valid, rc, nn, t);
+        } else {
+            rows_of(unit, row, valid, rc, nn, t);
+        }
         const int d = dil_of(j);
         const bool has_prev = t >= d;
         if (p.x_first && j == 0) {

@@ -25,10 +25,11 @@
     // measurements of round 6 did not reward in any form the compiler or inline asm allows; see the comment at the dependency check below.)
     while (u >= 0 && !dead) {
         PT_MARK();
+        PT_BEGIN();      // (slots [15] .. [17]: the three spans of the top, stack_persist.hip)
         // ---- TOP: P row requested; the rows of this unit were requested during the previous one ---------------------------
         int row, rc, nn, t;
         bool valid;
-        rows_of(u, row, valid, rc, nn, t);
+        rows_of_top(u, row, valid, rc, nn, t);
         if constexpr (SHORT) {
             flush_owed();
             PT_EV(3, j, u);
@@ -50,17 +51,26 @@
                     for (int e = 0; e < 4; ++e) acc[it][q * 4 + e] = v[e];
                 }
         } else {
+            // No scalar memory load here: the row stride and the hop constants come out of lanes of v_dil (pwv_persist_geometry.inc).  Buffer
+            // loads, the kind the rows are loaded with: one kind of vector-memory instruction in the queue is what lets the compiler count "all
+            // but the last 16 have landed" for the rows it splits below instead of draining the queue in front of them.  The descriptor starts at
+            // the unit's first P row -- lane 0's: the rows of a unit ascend with the lane and so do their P rows, an utterance's frames lying
+            // inside its own block of P -- and the lanes' offsets are relative to it.
             int prow = 0;
-            if (p.cond_hop > 0) prow = p_base(nn) + fast_div(t + p.cond_offset, p.hop_magic, p.hop_shift);
-            const float* pr = proj_n + (size_t)prow * p.proj_row_stride + j * 128 + h * 64;
+            if (p.cond_hop > 0) prow = p_base(nn) + fast_div(t + top_scalar(kLaneCondOffset), (unsigned)top_scalar(kLaneHopMagic), (unsigned)top_scalar(kLaneHopShift));
+            const int stride = top_scalar(kLaneStride);
+            const int prow0 = __builtin_amdgcn_readfirstlane(prow);
+            const __amdgpu_buffer_rsrc_t prs = proj_rs_at((long long)prow0 * stride);
+            const int po = ((prow - prow0) * stride + h * 64) * 4;
 #pragma unroll
             for (int it = 0; it < 4; ++it)
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    const f32x4 v = *reinterpret_cast<const f32x4*>(pr + it * 16 + q * 4);
+                    const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(prs, po + (it * 16 + q * 4) * 4, j * 512, 0));
 #pragma unroll
                     for (int e = 0; e < 4; ++e) acc[it][q * 4 + e] = v[e];
                 }
+            PT_LAP(15);
         }
         if constexpr (SHORT) {
             // (An "early half" -- GEMM1's x[t] k-steps of pair 0 run while the look-back row is still in flight -- needs the compiler's scoreboard to know that
@@ -109,6 +119,14 @@
                     rxb[4 * g + e] = has_prev ? vb : 0.f;
                 }
             }
+            // (the four scalars are read by every fmaf above, so the rebuilt elements 0 and 1 are born in other registers than the ones the rows are loaded
+            //  into.  The copy home is spelled out HERE, as an instruction of this arm: left to the register allocator, the rebuilt value keeps its register
+            //  and the join stands on the OTHER arm -- a v_mov_b32 behind an `s_waitcnt vmcnt(0)` of the compiler's own, in front of the split of every unit
+            //  of every other layer; tests/test_persist_top_isa.py)
+            const float n0 = rxc[0], n1 = rxc[1], m0 = rxb[0], m1 = rxb[1];
+            __builtin_amdgcn_sched_barrier(0);      // (behind the last reader of the scalars)
+            asm volatile("v_mov_b32 %0, %4\n\tv_mov_b32 %1, %5\n\tv_mov_b32 %2, %6\n\tv_mov_b32 %3, %7"
+                         : "=&v"(rxc[0]), "=&v"(rxc[1]), "=&v"(rxb[0]), "=&v"(rxb[1]) : "v"(n0), "v"(n1), "v"(m0), "v"(m1));
         }
         const float* bias = lds + kBiasF + (j & 1) * 64 + h * 32;
         float o[32];
@@ -120,6 +138,10 @@
             if (!SHORT) PT_EV(5, j, u);
             PT_BEGIN();
             if (!SHORT) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (SHORT: nothing is owed here -- the top of this unit has drained and published)
+            // (... and once more as the builtin, which the compiler's own scoreboard understands: the asm orders memory, this tells it that the P row has
+            //  landed.  Without it the compiler puts its own waits for the P row's registers into GEMM1 -- behind leave_layers' refill, so that the one wave
+            //  that issues a refill would sit out the whole 79 KB in front of its second MFMA; simm16 = vmcnt 0, expcnt 7, lgkmcnt 15)
+            if (!SHORT) __builtin_amdgcn_s_waitcnt(0x0F70);
             PT_END(1);
             PT_EV(6, j, u);
             if constexpr (!SHORT) {      // (SHORT: the top of the unit has done all of it)

@@ -6,14 +6,25 @@
 
             f16x8 bh[8], bl[8];      // B operands: bh[0..3] = x[t-d], bh[4..7] = x[t]; packed K order: x[t] first (pwv_layer_f16.hip)
             float xc[32];
+            // (general loop: the rows to split were requested a unit ago; the 16 P loads of this unit's top are all that was issued behind them.  `vmcnt(16)`
+            //  says exactly that -- loads return in order -- and leaves the P row in flight under the split.  As the BUILTIN it also tells the compiler's own
+            //  scoreboard, which for loads carried over the loop's back-edge otherwise puts `s_waitcnt vmcnt(0)` here: simm16 = vmcnt 16, expcnt 7, lgkmcnt 15)
+            if constexpr (!SHORT) __builtin_amdgcn_s_waitcnt(0x4F70);
 #pragma unroll
             for (int k = 0; k < 32; ++k) xc[k] = rxc[k];
             split8<0>(xc, bh[4], bl[4]);
+            if constexpr (!SHORT) PT_LAP(16);
             split8<8>(xc, bh[5], bl[5]);
             split8<16>(xc, bh[6], bl[6]);
             split8<24>(xc, bh[7], bl[7]);
+            // (the split is register arithmetic, which nothing orders against settle_top's drain: left to itself the compiler runs the drain FIRST, and the
+            //  split then starts only when the P row and the previous unit's stores have landed instead of running under them.  The drain is a volatile asm;
+            //  so is this, and it needs the split's results.)
+            if constexpr (!SHORT)
+                asm volatile("" : "+v"(bh[4]), "+v"(bl[4]), "+v"(bh[5]), "+v"(bl[5]), "+v"(bh[6]), "+v"(bl[6]), "+v"(bh[7]), "+v"(bl[7]));
+            if constexpr (!SHORT) PT_LAP(17);
             settle_top();
-            hist_store(j, dil_of(j), nn, t, u, rc, valid, xc);
+            hist_store(j, dil_of(j), nn, t, u, rc, valid, xc, (RAGGED && !SHORT) ? top_rec[2] : -1);
             auto bxh = [&](int s) -> f16x8 { return bh[s ^ 4]; };
             auto bxl = [&](int s) -> f16x8 { return bl[s ^ 4]; };
             f16x8 oh[4], ol[4];

@@ -13,7 +13,7 @@
                 }
             }
             settle_top();
-            hist_store(j, dil_of(j), nn, t, u, rc, valid, xc);
+            hist_store(j, dil_of(j), nn, t, u, rc, valid, xc, (RAGGED && !SHORT) ? top_rec[2] : -1);
             const float* Af = lds + (j & 1) * kSlot;                 // [kA1 | kA2 minus its last fragment]
             f32x4 a[4];
             f32x4 lf = {0.f, 0.f, 0.f, 0.f};

@@ -123,9 +123,12 @@ struct PersistParams {
 // round 5, phases of a unit of the general loop (PT_PHASE: the time since the previous stamp goes to slot k): [9] top of the unit up
 // to the drain (P row requested, next task located, look-back row split), [10] GEMM1, [11] GEMM2, [12] stores + moving on;
 // inside [11] (PT_LAP: the time since PT_BEGIN or the previous lap goes to slot k): [13] prefetch_next (the next unit's rows requested -- and whatever
-// the wave waits for before it gets on), [14] GEMM2 proper
+// the wave waits for before it gets on), [14] GEMM2 proper;
+// inside [9] (PT_LAP from the loop's header on; the trace record keeps them in its words 21 .. 23): [15] header -> the P row's loads issued (row maps, the P address),
+// [16] -> the first split8 of the unit's own rows done (next task located, its dependency byte read, whatever the wave waits for in front of the rows), [17] -> the
+// other three split8, up to settle_top's drain
 #ifdef PWV_PTRACE
-#define PT_DECL long long pt_acc[15] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; long long pt_t = 0, pt_p = 0; (void)pt_t; (void)pt_p;
+#define PT_DECL long long pt_acc[18] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; long long pt_t = 0, pt_p = 0; (void)pt_t; (void)pt_p;
 #define PT_BEGIN() pt_t = __builtin_amdgcn_s_memtime()
 #define PT_END(k) pt_acc[k] += __builtin_amdgcn_s_memtime() - pt_t
 #define PT_ADD(k, v) pt_acc[k] += (v)

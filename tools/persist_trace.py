@@ -60,6 +60,11 @@ def main():
     for k, name in ((13, 'prefetch_next (next rows requested; any wait behind the loads)'), (14, 'GEMM2 proper (24 MFMAs, gate + split of pair 1)')):
         print('    of GEMM2: %-62s %7.0f cycles per unit (%.1f %% of a unit)'
               % (name, (t[:, k] / t[:, 5]).mean(), 100 * (t[:, k] / tot).mean()))
+    # inside the top (record words 21 .. 23 = slots [15] .. [17]); the split-fp16 unit stamps all three, the exact-fp32 unit the first
+    for k, name in ((21, 'header -> P loads issued (row maps, P address)'), (22, '-> first split8 done (next task, dependency byte, the wait for the rows)'),
+                    (23, '-> the other three split8, up to the drain')):
+        print('    of the top: %-70s %7.0f cycles per unit (%.1f %% of a unit)'
+              % (name, (t[:, k] / t[:, 5]).mean(), 100 * (t[:, k] / tot).mean()))
     t0 = t[:, 20].min()
     st, en = (t[:, 20] - t0) / 100.0, (t[:, 19] - t0) / 100.0
     print('loop start %.1f .. %.1f us, loop end %.1f .. %.1f us (chip-wide 100 MHz clock)' % (st.min(), st.max(), en.min(), en.max()))
