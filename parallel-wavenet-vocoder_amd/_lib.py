@@ -46,6 +46,8 @@ EXPORTED_SYMBOLS = (
 
 # the entry points of the extension headers (include/pwv_hip_mel_stream.h): in the same library, outside pwv_hip.h and its list
 EXTENSION_SYMBOLS = ('pwv_wav_to_mel_db_stream_f32',)
+# ... and of include/pwv_hip_live_tick.h: the streaming front-end inside a captured ragged tick
+LIVE_TICK_SYMBOLS = ('pwv_live_tick_mel', 'pwv_live_tick_commit')
 
 
 class PwvError(RuntimeError):
@@ -286,6 +288,41 @@ class MelStreamArgs(Structure):
         self.struct_size = ctypes.sizeof(MelStreamArgs)
 
 
+LIVE_TICK_REC = 12            # PWV_LIVE_TICK_REC: int64 per record of a live tick
+# the fields of such a record, in order (include/pwv_hip_live_tick.h): the streaming record's, with the slot, the flags and the row of
+# `first` where that one has the two blocks and the max word
+LIVE_REC_FIELDS = ('carry_first', 'carry_len', 'chunk_off', 'chunk_len', 'first_frame', 'frames', 'final_len', 'slot', 'flags',
+                   'out_row', 'new_carry_first', 'first_row')
+LIVE_ACTIVE, LIVE_START, LIVE_FIRST = 1, 2, 4
+
+
+class LiveTickArgs(Structure):
+    """pwv_live_tick_args: the front-end half of a live tick (include/pwv_hip_live_tick.h)."""
+    _fields_ = [
+        ('struct_size', c_size_t),      # set by __init__
+        ('wav', c_void_p),
+        ('window', c_void_p),
+        ('mel_basis', c_void_p),
+        ('mel', c_void_p),
+        ('first', c_void_p),
+        ('state', c_void_p),
+        ('max_key', c_void_p),
+        ('scratch', c_void_p),
+        ('sess', c_void_p),
+        ('rec', c_void_p),
+        ('rec_host', c_void_p),
+        ('words', c_void_p),
+        ('wav_cap', c_int64), ('mel_rows', c_int64),
+        ('N', ctypes.c_int32), ('n_slots', ctypes.c_int32), ('n_first', ctypes.c_int32), ('n_fft', ctypes.c_int32), ('hop', ctypes.c_int32),
+        ('n_mels', ctypes.c_int32),
+        ('amin', ctypes.c_float), ('max_db', ctypes.c_float), ('min_db', ctypes.c_float), ('limit_db', ctypes.c_float),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = ctypes.sizeof(LiveTickArgs)
+
+
 # per-source extra flags (none in the product; tools/probes/regw/README.md: the register-stationary probe kernel needs
 # `-mllvm -amdgpu-mfma-vgpr-form=1`, which is why the sources are compiled one by one)
 EXTRA_FLAGS = {}
@@ -432,6 +469,8 @@ def _declare(lib):
     lib.pwv_pack_proj_f32.argtypes = [f32p, f32p, f32p, f32p, c_int, c_int, c_int, f32p, f32p, c_void_p]
     lib.pwv_wav_to_mel_db_f32.argtypes = [f32p, f32p, f32p, f32p, c_int, c_int, c_int, c_int, c_int] + [ctypes.c_float] * 4 + [c_int, c_void_p]
     lib.pwv_wav_to_mel_db_stream_f32.argtypes = [POINTER(MelStreamArgs), c_void_p]
+    lib.pwv_live_tick_mel.argtypes = [POINTER(LiveTickArgs), c_void_p]
+    lib.pwv_live_tick_commit.argtypes = [POINTER(LiveTickArgs), c_void_p]
     lib.pwv_instance_norm_workspace_bytes.restype = c_size_t
     lib.pwv_instance_norm_workspace_bytes.argtypes = [c_int, c_int, c_int]
     lib.pwv_instance_norm_f32.argtypes = [f32p, f32p, c_int, c_int, c_int, f32p, f32p, ctypes.c_float, c_void_p, c_size_t, c_void_p]
@@ -453,7 +492,7 @@ def _declare(lib):
     lib.pwv_status_words_alloc.argtypes = [POINTER(c_void_p)]
     lib.pwv_status_words_free.argtypes = [c_void_p]
     lib.pwv_range_check_f32.argtypes = [f32p, c_int64, ctypes.c_float, c_void_p, c_void_p]
-    for name in EXPORTED_SYMBOLS + EXTENSION_SYMBOLS:      # fails loudly (AttributeError) if a symbol is missing
+    for name in EXPORTED_SYMBOLS + EXTENSION_SYMBOLS + LIVE_TICK_SYMBOLS:      # fails loudly (AttributeError) if a symbol is missing
         getattr(lib, name)
     return lib
 

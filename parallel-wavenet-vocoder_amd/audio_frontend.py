@@ -25,7 +25,7 @@ rate differs from hp.signal.sr).
 from __future__ import annotations
 
 import ctypes
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -217,6 +217,118 @@ def _key_to_db(key: int) -> Optional[float]:
     return float(np.array([bits & 0xffffffff], dtype=np.uint32).view(np.float32)[0])
 
 
+KEY_NONE = -(1 << 31)      # a max word that has seen nothing
+
+
+class LiveRecord(NamedTuple):
+    """live_record: what one session's part of a tick comes to (the streaming record's arithmetic, StreamingMel._launch)."""
+    carry_first: int         # c(R before)
+    carry_len: int
+    first_frame: int         # K before
+    frames: int              # frames the tick emits
+    final_len: int           # L when the utterance ends with this chunk, else -1
+    new_carry_first: int     # c(R after)
+    received: int            # R after (0 after an end: the slot is fresh)
+    emitted: int             # K after (0 after an end)
+
+
+def live_record(received: int, emitted: int, n: int, end: bool, n_fft: int, hop: int) -> LiveRecord:
+    """A session that has received `received` samples and emitted `emitted` frames is given `n` more; `end`: its utterance ends with
+    them, at L = received + n (L <= n_fft / 2 is a ValueError, as in the one-shot).  Host arithmetic alone."""
+    r1 = received + n
+    if end and r1 <= n_fft // 2:
+        raise ValueError('an utterance of L = %d samples ends: L must exceed n_fft / 2 = %d' % (r1, n_fft // 2))
+    k1 = 1 + r1 // hop if end else frames_ready(r1, n_fft, hop)
+    c0 = carry_start(received, n_fft, hop)
+    frames = max(k1 - emitted, 0)
+    return LiveRecord(c0, received - c0, emitted, frames, r1 if end else -1, c0 if end else carry_start(r1, n_fft, hop),
+                      0 if end else r1, 0 if end else emitted + frames)
+
+
+def _live_clamped(rec, n_slots: int, wav_cap: int, mel_rows: int, n_fft: int):
+    """(numpy restatement of live_record, csrc/pwv_audio.hip)  Record `rec` (12 int64) as both kernels of a live tick read it."""
+    c0, clen, coff, chlen, first, frames, L, slot, flags, row, c1, first_row = [int(v) for v in rec]
+    active = bool(flags & 1) and 0 <= slot < n_slots
+    clen = 0 if flags & 2 else min(max(clen, 0), n_fft)
+    coff = min(max(coff, 0), wav_cap)
+    chlen = min(max(chlen, 0), wav_cap - coff)
+    frames = min(max(frames, 0), mel_rows + 1) if clen + chlen > 0 else 0
+    return dict(active=active, slot=slot if active else 0, flags=flags, c0=min(max(c0, 0), 1 << 62), clen=clen, coff=coff, chlen=chlen,
+                first=min(max(first, 0), 1 << 40), frames=frames, L=min(max(L, -1), 1 << 62), c1=min(max(c1, 0), 1 << 62), row=row,
+                first_row=first_row, scan_frames=min(max(int(rec[5]), 0), mel_rows + 1))
+
+
+def live_tick_rows(recs, sess, n_slots: int, wav_cap: int, mel_rows: int, n_first: int, n_fft: int):
+    """(numpy restatement of live_tick_mel_kernel's bookkeeping)  What the workgroups of a live tick write, from its records (int64
+    [N, 12]) and the front-end session table `sess` (int64 [n_slots, 4]): (frames, carries) with frames = {('mel' | 'first', row): (record,
+    frame number of the utterance, state block read)} and carries = {state block written: (record, state block read, first sample kept,
+    samples kept)}.  Workgroup b of the mel_rows + 2 N is frame x of the first active record whose frames + 1 it falls into, x == frames
+    its carry."""
+    recs = np.asarray(recs, np.int64).reshape(-1, 12)
+    frames, carries = {}, {}
+    for b in range(mel_rows + 2 * len(recs)):
+        x, hit = b, None
+        for i, rec in enumerate(recs):
+            q = _live_clamped(rec, n_slots, wav_cap, mel_rows, n_fft)
+            if not q['active']:
+                continue
+            if x < q['scan_frames'] + 1:
+                hit = (i, q)
+                break
+            x -= q['scan_frames'] + 1
+        if hit is None:
+            continue
+        i, q = hit
+        g = int(sess[q['slot']][0]) & 1
+        rd, wr = 2 * q['slot'] + g, 2 * q['slot'] + 1 - g
+        if x >= q['frames']:
+            if x == q['frames'] and q['L'] < 0 and q['clen'] + q['chlen'] > 0:
+                keep = q['c0'] + q['clen'] + q['chlen'] - q['c1']
+                carries[wr] = (i, rd, q['c1'], max(min(keep, n_fft), 0))
+            continue
+        if q['flags'] & 4:
+            where, row, limit = ('first', q['first_row'], n_first) if x == 0 else ('mel', q['row'] + x - 1, mel_rows)
+        else:
+            where, row, limit = 'mel', q['row'] + x, mel_rows
+        if 0 <= row < limit:
+            frames[(where, row)] = (i, q['first'] + x, rd)
+    return frames, carries
+
+
+def live_tick_commit(sess, max_key, scratch, recs, words, limit_db: float, wav_cap: int, mel_rows: int, n_fft: int):
+    """(numpy restatement of live_tick_commit_kernel)  (sess, max_key, scratch) after the front-end commit of a live tick: with both sticky
+    `words` zero every active record's session flips its generation, advances (a start: sets; an end: zeroes) received and emitted, folds
+    the tick's maximum into its word (a start: replaces it), becomes `over` above limit_db and, at an end, has its word put back; with a
+    word raised nothing of the sessions changes.  The scratch words are KEY_NONE afterwards either way.  Returns copies."""
+    sess, max_key, scratch = np.array(sess, np.int64), np.array(max_key, np.int32), np.array(scratch, np.int32)
+    keys, scratch[:] = scratch.copy(), KEY_NONE
+    if int(words[0]) != 0 or int(words[1]) != 0:
+        return sess, max_key, scratch
+    limit = _db_to_key(limit_db)
+    for i, rec in enumerate(np.asarray(recs, np.int64).reshape(-1, 12)):
+        q = _live_clamped(rec, sess.shape[0], wav_cap, mel_rows, n_fft)
+        if not q['active']:
+            continue
+        s, start = q['slot'], bool(q['flags'] & 2)
+        word = int(keys[i]) if start or int(keys[i]) > int(max_key[s]) else int(max_key[s])
+        sess[s, 0] ^= 1
+        if word > limit:
+            sess[s, 3] = 1
+        if q['L'] >= 0:
+            sess[s, 1], sess[s, 2], word = 0, 0, KEY_NONE
+        else:
+            sess[s, 1] = (0 if start else sess[s, 1]) + q['chlen']
+            sess[s, 2] = (0 if start else sess[s, 2]) + q['frames']
+        max_key[s] = word
+    return sess, max_key, scratch
+
+
+def _db_to_key(db: float) -> int:
+    """The order-preserving max word of a float (float_key, csrc/pwv_audio.hip)."""
+    bits = int(np.array([db], dtype=np.float32).view(np.int32)[0])
+    return bits if bits >= 0 else bits ^ 0x7fffffff
+
+
 class StreamingMel(object):
     """wav chunks in, the frames of `wav_to_mel_device` on the whole utterance out -- bit for bit, as soon as their samples are there:
 
@@ -260,6 +372,12 @@ class StreamingMel(object):
         self._gen = [0] * self.n_slots
         self._received = [0] * self.n_slots
         self._emitted = [0] * self.n_slots
+        # graph replay of a live tick (graph.GraphedLiveStream): the sessions as the device sees them -- int64 [n_slots, 4] = {generation
+        # read, samples received, frames emitted, over the top_db limit} --, per slot what that row is known to hold (None: never written)
+        # and the graph whose ticks are in flight
+        self._sess = torch.zeros((self.n_slots, 4), dtype=torch.int64, device=self.device)
+        self._sess_host = [None] * self.n_slots
+        self._live = None
 
     # -- bookkeeping -----------------------------------------------------------------------------------------------------
     def _slot(self, slot) -> int:
@@ -281,8 +399,21 @@ class StreamingMel(object):
         self._slot(slot)
         return 2 * self.n_fft * 4 + 4
 
+    def _settled(self, what: str) -> None:
+        if self._live is not None:
+            raise self._lib.PwvError('StreamingMel.%s: live ticks are in flight (GraphedLiveStream.tick only enqueues, and the sessions '
+                                     'are the device\'s meanwhile): call verify() of the live graph first' % what)
+
+    def _note_over(self, slots) -> None:
+        """(enqueue-only) The sticky `over` word of the device session table for `slots`, as the commit of a live tick sets it: 1 once the
+        session's largest raw dB exceeds min_db + top_db.  The eager form of a live tick calls it behind its pushes."""
+        idx = torch.tensor(list(slots), dtype=torch.int64).pin_memory().to(self.device, non_blocking=True)
+        over = (self._max.index_select(0, idx) > _db_to_key(self.min_db + TOP_DB)).to(torch.int64)
+        self._sess[:, 3].index_copy_(0, idx, torch.maximum(self._sess[:, 3].index_select(0, idx), over))
+
     def reset(self, slot) -> None:
         """`slot` starts a new utterance (enqueue-only: the carry needs no clearing, its length is zero)."""
+        self._settled('reset')
         s = self._slot(slot)
         self._received[s], self._emitted[s] = 0, 0
         self._max[s:s + 1].fill_(-(1 << 31))
@@ -347,6 +478,7 @@ class StreamingMel(object):
         """Session slots[i] (default: all slots, in order) receives its next samples chunks[i], [n_i >= 1] float32 on the GPU.  Returns
         the list of [f_i, n_mels] frame tensors that became ready (f_i may be 0), views of one packed result.  Enqueue-only."""
         from . import engine
+        self._settled('push')
         if not isinstance(chunks, (list, tuple)) or not chunks:
             raise ValueError('chunks must be a non-empty list of [n] tensors')
         slots = list(range(self.n_slots)) if slots is None else [self._slot(v) for v in slots]
@@ -362,6 +494,7 @@ class StreamingMel(object):
         """The utterance of `slot` ends at the samples received, L: returns its last frames (1 + L // hop in all with those returned
         before), the right reflection taken at L.  L <= n_fft / 2 is refused, as by the one-shot.  Verifies the slot (synchronises): a
         PwvError naming top_db if its frames are not the one-shot's.  The slot is fresh afterwards, as after reset."""
+        self._settled('finish')
         s = self._slot(slot)
         out = self._launch([s], [None], True)[0]
         try:

@@ -7,8 +7,11 @@
 // restatement uses), twiddles from an LDS table.  Not a hot path; it exists so that generate() on wav input keeps the mel
 // on the device.  The STREAMING form (stft_mel_stream_kernel, pwv_wav_to_mel_db_stream_f32) emits the same frames, bit for bit, from wav
 // chunks as they arrive: both kernels include one text of the frame arithmetic, pwv_mel_frame_body.inc.
+// The LIVE tick (live_tick_mel_kernel, live_tick_commit_kernel; include/pwv_hip_live_tick.h) is the streaming form at a fixed capacity, for a
+// captured graph: records and a front-end session table in device memory, the frames straight into a ragged streaming tick's mel, and
+// a commit on the device behind the vocoder's.  It includes the same text.
 #include "pwv_common.h"
-#include "pwv_hip_mel_stream.h"
+#include "pwv_hip_live_tick.h"
 
 namespace pwv {
 
@@ -111,6 +114,154 @@ __global__ __launch_bounds__(256) void stft_mel_stream_kernel(const float* __res
 #undef PWV_MEL_STORE
     __syncthreads();
     if (threadIdx.x == 0) atomicMax(max_key + r[kRecMaxWord], wg_max);
+}
+
+// ---- the LIVE tick (include/pwv_hip_live_tick.h): the capacity form of the streaming kernel and the front-end commit ----
+constexpr int kLiveRec = PWV_LIVE_TICK_REC;
+enum { kLiveSlot = 7, kLiveFlags = 8, kLiveFirstRow = 11 };       // (the other fields are the streaming record's)
+enum { kLiveActive = 1, kLiveStart = 2, kLiveFirst = 4 };
+constexpr int kKeyNone = -2147483647 - 1;
+
+struct LiveParams {
+    const float* wav;
+    const float* window;
+    const float* fb;
+    float* mel;
+    float* first;
+    float* state;
+    int* max_key;
+    int* scratch;
+    long long* sess;
+    const long long* rec;
+    const int* words;
+    long long wav_cap, mel_rows;
+    int N, n_slots, n_first, n_fft, hop, n_mels;
+    float amin, max_db, min_db, limit_db;
+};
+
+// Record i as both kernels read it: every value clamped to what the call was given, whatever the table holds.
+struct LiveRecord {
+    long long c0, clen, coff, chlen, first, frames, L, c1, row, first_row;
+    int slot, flags;
+    bool active;
+};
+
+__device__ __forceinline__ long long clampll(long long v, long long lo, long long hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+__device__ __forceinline__ LiveRecord live_record(const LiveParams& p, int i) {
+    const long long* r = p.rec + (size_t)i * kLiveRec;
+    LiveRecord q;
+    q.flags = (int)r[kLiveFlags];
+    const long long slot = r[kLiveSlot];
+    q.active = (q.flags & kLiveActive) != 0 && slot >= 0 && slot < p.n_slots;
+    q.slot = q.active ? (int)slot : 0;
+    q.c0 = clampll(r[kRecCarryFirst], 0, 1ll << 62);
+    q.clen = (q.flags & kLiveStart) ? 0 : clampll(r[kRecCarryLen], 0, p.n_fft);        // a start reads no carry
+    q.coff = clampll(r[kRecChunkOff], 0, p.wav_cap);
+    q.chlen = clampll(r[kRecChunkLen], 0, p.wav_cap - q.coff);
+    q.first = clampll(r[kRecFirstFrame], 0, 1ll << 40);
+    q.frames = q.clen + q.chlen > 0 ? clampll(r[kRecFrames], 0, p.mel_rows + 1) : 0;   // (no sample held: nothing to read)
+    q.L = clampll(r[kRecFinalLen], -1, 1ll << 62);
+    q.c1 = clampll(r[kRecNewCarryFirst], 0, 1ll << 62);
+    q.row = r[kRecOutRow];
+    q.first_row = r[kLiveFirstRow];
+    return q;
+}
+
+// Workgroup b is frame x of record i, or (x == its frames) its carry: the records' frames + 1 in a row, inactive records none.
+// A workgroup behind them all has nothing to do.
+__global__ __launch_bounds__(256) void live_tick_mel_kernel(LiveParams p) {
+    extern __shared__ double sm[];             // as stft_mel_kernel
+    __shared__ int wg_max;
+    const int n_fft = p.n_fft, n_mels = p.n_mels;
+    const float amin = p.amin;
+    const float* window = p.window;
+    const float* fb = p.fb;
+    double* fr = sm;
+    double* ct = sm + n_fft;
+    double* st = ct + n_fft;
+    double* mag = st + n_fft;
+    long long x = blockIdx.x;
+    int i = 0;
+    for (; i < p.N; ++i) {
+        const long long* r = p.rec + (size_t)i * kLiveRec;
+        const long long slot = r[kLiveSlot];
+        if (!((r[kLiveFlags] & kLiveActive) != 0 && slot >= 0 && slot < p.n_slots)) continue;
+        const long long count = clampll(r[kRecFrames], 0, p.mel_rows + 1) + 1;
+        if (x < count) break;
+        x -= count;
+    }
+    if (i >= p.N) return;
+    const LiveRecord q = live_record(p, i);
+    const int g = (int)(p.sess[4 * (long long)q.slot] & 1);
+    const float* carry = p.state + (size_t)(2 * q.slot + g) * n_fft;
+    const float* chunk = p.wav + q.coff;
+    const long long c0 = q.c0, clen = q.clen, chlen = q.chlen, L = q.L;
+    if (x >= q.frames) {
+        if (x > q.frames || L >= 0 || clen + chlen <= 0) return;      // (a finished utterance carries nothing on)
+        float* next = p.state + (size_t)(2 * q.slot + 1 - g) * n_fft;
+        const long long keep = c0 + clen + chlen - q.c1;
+        for (long long k = threadIdx.x; k < keep && k < n_fft; k += 256) next[k] = stream_sample(carry, chunk, q.c1 + k, c0, clen, chlen);
+        return;
+    }
+    float* out;
+    if (q.flags & kLiveFirst) {
+        const long long row = x == 0 ? q.first_row : q.row + x - 1;
+        if (row < 0 || row >= (x == 0 ? (long long)p.n_first : p.mel_rows)) return;
+        out = (x == 0 ? p.first : p.mel) + (size_t)row * n_mels;
+    } else {
+        const long long row = q.row + x;
+        if (row < 0 || row >= p.mel_rows) return;
+        out = p.mel + (size_t)row * n_mels;
+    }
+    const long long f = q.first + x;
+    const int hop = p.hop;
+    const float max_db = p.max_db, min_db = p.min_db;
+    if (threadIdx.x == 0) wg_max = float_key(-3.0e38f);               // (the body's first barrier orders it)
+#define PWV_MEL_FETCH(i) stream_sample(carry, chunk, stream_index(f * hop + (i) - n_fft / 2, L), c0, clen, chlen)
+#define PWV_MEL_STORE(m, raw)                          \
+    do {                                               \
+        out[m] = normalise_db((raw), max_db, min_db);  \
+        atomicMax(&wg_max, float_key(raw));            \
+    } while (0)
+#include "pwv_mel_frame_body.inc"
+#undef PWV_MEL_FETCH
+#undef PWV_MEL_STORE
+    __syncthreads();
+    if (threadIdx.x == 0) atomicMax(p.scratch + i, wg_max);
+}
+
+// ONE workgroup, behind the ragged tick's commit: the words are read once, so all records of a tick see one decision
+__global__ __launch_bounds__(256) void live_tick_commit_kernel(LiveParams p) {
+    __shared__ int clean;
+    if (threadIdx.x == 0) {
+        const int gave_up = __hip_atomic_load(p.words, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        const int range = __hip_atomic_load(p.words + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        clean = (gave_up == 0 && range == 0) ? 1 : 0;
+    }
+    __syncthreads();
+    const int limit = float_key(p.limit_db);
+    for (int i = threadIdx.x; i < p.N; i += 256) {
+        const int key = p.scratch[i];
+        p.scratch[i] = kKeyNone;
+        if (!clean) continue;
+        const LiveRecord q = live_record(p, i);
+        if (!q.active) continue;
+        long long* s = p.sess + 4 * (long long)q.slot;
+        const bool start = (q.flags & kLiveStart) != 0;
+        int word = p.max_key[q.slot];
+        word = start || key > word ? key : word;
+        s[0] ^= 1;
+        if (word > limit) s[3] = 1;
+        if (q.L >= 0) {
+            s[1] = 0, s[2] = 0;
+            word = kKeyNone;
+        } else {
+            s[1] = (start ? 0 : s[1]) + q.chlen;
+            s[2] = (start ? 0 : s[2]) + q.frames;
+        }
+        p.max_key[q.slot] = word;
+    }
 }
 
 // per utterance: top_db clip against the maximum of the whole spectrogram, then (clip((db - min)/(max - min), 0, 1) - .5) * 2
@@ -216,6 +367,70 @@ int pwv_wav_to_mel_db_stream_f32(const pwv_mel_stream_args* a, pwv_stream_t stre
     const size_t smem = (size_t)(3 * a->n_fft + a->n_fft / 2 + 1) * sizeof(double);
     hipLaunchKernelGGL(stft_mel_stream_kernel, dim3((unsigned)(max_frames + 1), a->N), dim3(256), smem, s, a->wav, a->window, a->mel_basis, a->mel,
                        a->state, a->max_key, (const long long*)a->rec, a->n_fft, a->hop, a->n_mels, a->amin, a->max_db, a->min_db);
+    PWV_CHECK_HIP(hipGetLastError());
+    return PWV_OK;
+}
+
+// the live tick: check, then one launch whose grid N and mel_rows alone decide
+static int live_params(const pwv_live_tick_args* a, const char* who, LiveParams* p) {
+    PWV_CHECK_ARG(a, "%s: args is NULL", who);
+    PWV_CHECK_ARG(a->struct_size >= sizeof(pwv_live_tick_args), "%s: struct_size %zu is short of pwv_live_tick_args (%zu bytes)", who,
+                  a->struct_size, sizeof(pwv_live_tick_args));
+    PWV_CHECK_ARG(a->window, "%s: window is a NULL pointer", who);
+    PWV_CHECK_ARG(a->mel_basis, "%s: mel_basis is a NULL pointer", who);
+    PWV_CHECK_ARG(a->mel, "%s: mel is a NULL pointer", who);
+    PWV_CHECK_ARG(a->state, "%s: state is a NULL pointer", who);
+    PWV_CHECK_ARG(a->max_key, "%s: max_key is a NULL pointer", who);
+    PWV_CHECK_ARG(a->scratch, "%s: scratch is a NULL pointer", who);
+    PWV_CHECK_ARG(a->sess, "%s: sess is a NULL pointer", who);
+    PWV_CHECK_ARG(a->rec, "%s: rec is a NULL pointer", who);
+    PWV_CHECK_ARG(a->words, "%s: words is a NULL pointer", who);
+    PWV_CHECK_ARG(a->wav_cap >= 0 && (a->wav || a->wav_cap == 0), "%s: wav is a NULL pointer (wav_cap %lld)", who, (long long)a->wav_cap);
+    PWV_CHECK_ARG(a->n_first >= 0 && (a->first || a->n_first == 0), "%s: first is a NULL pointer (n_first %d)", who, a->n_first);
+    PWV_CHECK_ARG(a->n_fft >= 2 && a->n_fft % 2 == 0 && a->n_fft <= kMaxFft, "%s: n_fft %d must be even, >= 2 and <= %d", who, a->n_fft, kMaxFft);
+    PWV_CHECK_ARG(a->hop >= 1, "%s: hop %d must be >= 1", who, a->hop);
+    PWV_CHECK_ARG(a->n_mels >= 1, "%s: n_mels %d must be >= 1", who, a->n_mels);
+    PWV_CHECK_ARG(a->max_db != a->min_db, "%s: max_db == min_db (the streaming form is the normalised one)", who);
+    PWV_CHECK_ARG(a->N >= 1 && a->N <= 65535, "%s: N %d out of range (1 .. 65535 records in a tick)", who, a->N);
+    PWV_CHECK_ARG(a->n_slots >= 1, "%s: n_slots %d must be >= 1", who, a->n_slots);
+    PWV_CHECK_ARG(a->mel_rows >= 1 && a->mel_rows + 2ll * a->N < (1ll << 31), "%s: mel_rows %lld out of range", who, (long long)a->mel_rows);
+    for (int i = 0; a->rec_host && i < a->N; ++i) {
+        const int64_t* r = a->rec_host + (size_t)i * kLiveRec;
+        if (!(r[kLiveFlags] & kLiveActive)) continue;
+        const long long clen = r[kRecCarryLen], coff = r[kRecChunkOff], chlen = r[kRecChunkLen], frames = r[kRecFrames], L = r[kRecFinalLen],
+                        row = r[kRecOutRow], in_mel = frames - ((r[kLiveFlags] & kLiveFirst) && frames > 0 ? 1 : 0);
+        PWV_CHECK_ARG(r[kRecCarryFirst] >= 0 && clen >= 0 && clen <= a->n_fft, "%s: record %d: carry %lld + %lld", who, i, (long long)r[kRecCarryFirst], clen);
+        PWV_CHECK_ARG(coff >= 0 && chlen >= 0 && chlen <= a->wav_cap && coff <= a->wav_cap - chlen, "%s: record %d: chunk %lld + %lld leaves wav_cap %lld",
+                      who, i, coff, chlen, (long long)a->wav_cap);
+        PWV_CHECK_ARG(r[kRecFirstFrame] >= 0 && frames >= 0 && row >= 0 && in_mel <= a->mel_rows && row <= a->mel_rows - in_mel,
+                      "%s: record %d: rows %lld + %lld leave mel_rows %lld", who, i, row, in_mel, (long long)a->mel_rows);
+        PWV_CHECK_ARG(r[kLiveSlot] >= 0 && r[kLiveSlot] < a->n_slots, "%s: record %d: slot %lld has no state blocks (n_slots %d)", who, i,
+                      (long long)r[kLiveSlot], a->n_slots);
+        PWV_CHECK_ARG(!(r[kLiveFlags] & kLiveFirst) || (r[kLiveFirstRow] >= 0 && r[kLiveFirstRow] < a->n_first),
+                      "%s: record %d: first row %lld is outside the %d words / rows of first", who, i, (long long)r[kLiveFirstRow], a->n_first);
+        PWV_CHECK_ARG(L == -1 || L > a->n_fft / 2, "%s: record %d: final_len %lld must exceed n_fft / 2 = %d", who, i, L, a->n_fft / 2);
+    }
+    *p = LiveParams{a->wav, a->window, a->mel_basis, a->mel, a->first, a->state, a->max_key, a->scratch, (long long*)a->sess, (const long long*)a->rec,
+                    a->words, a->wav_cap, a->mel_rows, a->N, a->n_slots, a->n_first, a->n_fft, a->hop, a->n_mels, a->amin, a->max_db, a->min_db,
+                    a->limit_db};
+    return PWV_OK;
+}
+
+int pwv_live_tick_mel(const pwv_live_tick_args* a, pwv_stream_t stream) {
+    LiveParams p{};
+    const int rc = live_params(a, "pwv_live_tick_mel", &p);
+    if (rc != PWV_OK) return rc;
+    const size_t smem = (size_t)(3 * p.n_fft + p.n_fft / 2 + 1) * sizeof(double);
+    hipLaunchKernelGGL(live_tick_mel_kernel, dim3((unsigned)(p.mel_rows + 2 * p.N)), dim3(256), smem, (hipStream_t)stream, p);
+    PWV_CHECK_HIP(hipGetLastError());
+    return PWV_OK;
+}
+
+int pwv_live_tick_commit(const pwv_live_tick_args* a, pwv_stream_t stream) {
+    LiveParams p{};
+    const int rc = live_params(a, "pwv_live_tick_commit", &p);
+    if (rc != PWV_OK) return rc;
+    hipLaunchKernelGGL(live_tick_commit_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, p);
     PWV_CHECK_HIP(hipGetLastError());
     return PWV_OK;
 }

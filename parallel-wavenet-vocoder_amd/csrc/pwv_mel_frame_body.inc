@@ -1,6 +1,6 @@
 // One frame of the mel front-end, from its windowed samples to the raw dB of every mel band: the ONE text of the arithmetic, included
-// into stft_mel_kernel (the one-shot) and stft_mel_stream_kernel (csrc/pwv_audio.hip) so that a streamed frame is the one-shot's frame
-// bit for bit.  The two kernels differ in how a sample is fetched and in what becomes of the raw dB, nothing else.
+// into stft_mel_kernel (the one-shot), stft_mel_stream_kernel and live_tick_mel_kernel (csrc/pwv_audio.hip) so that a streamed frame is
+// the one-shot's frame bit for bit.  The kernels differ in how a sample is fetched and in what becomes of the raw dB, nothing else.
 //
 // The including kernel provides, in scope:
 //   double *fr, *ct, *st, *mag      the LDS arrays [n_fft], [n_fft], [n_fft], [n_fft / 2 + 1]

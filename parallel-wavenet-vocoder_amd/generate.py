@@ -154,10 +154,11 @@ def generate(case='default', ckpt=None, debug=False, varlen=False, seed=None, st
         slot per input and inputs x `stream` frames), the first one included: it starts the sessions (tick(starts=)); only an input too
         short for that starts with the eager one-frame push; same files.
     :param live: (with stream, wav inputs) the front-end streams too: every tick gives each unfinished input its next `stream` x hop
-        SAMPLES through audio_frontend.StreamingMel, and the frames that became ready to the sessions; same files.
+        SAMPLES through audio_frontend.StreamingMel, and the frames that became ready to the sessions; same files.  --live=graph:
+        every such tick is one replay of a captured live tick (StreamingVocoder.graphed_live).
     '''
-    if live and (stream is None or graph):
-        raise ValueError('--live applies to --stream=FRAMES without --graph (wav chunks in, wav chunks out)')
+    if live and (stream is None or graph or live not in (True, 'graph')):
+        raise ValueError('--live (or --live=graph) applies to --stream=FRAMES without --graph (wav chunks in, wav chunks out)')
     if graph and stream is None:
         raise ValueError('--graph applies to --stream=FRAMES (graph replay of the ragged ticks)')
     if stream is not None:
@@ -217,7 +218,7 @@ def generate(case='default', ckpt=None, debug=False, varlen=False, seed=None, st
     # (engine.verified_call); what comes back is what the reference's fp32 sess.run would have produced, or an exception.
     # verify=True is EXPLICIT: it outranks PWV_ASYNC=1 (whose default is enqueue-only) -- nothing unverified is written to disk
     if live:
-        pred = _generate_stream_live(model, wavs, stream, device)
+        pred = (_generate_stream_live_graph if live == 'graph' else _generate_stream_live)(model, wavs, stream, device)
     elif stream:
         pred = _generate_stream_graph(model, melspec, stream) if graph else _generate_stream(model, melspec, stream)
     elif varlen:
@@ -322,6 +323,81 @@ def _generate_stream_live(model, wavs, frames, device):
             got = s.push_varlen([ready[i] for i in slots], slots=slots, verify=True)
             for k, i in enumerate(slots):
                 outs[i].append(got[k])
+    return [torch.cat(o) for o in outs]
+
+
+def _generate_stream_live_graph(model, wavs, frames, device, depth=4):
+    """--stream=FRAMES --live=graph: the loop of _generate_stream_live on graphed live ticks (graph.GraphedLiveStream at a capacity of
+    one slot per input and, per input, `frames` frames and those its end adds): an input's first tick names it in `starts` (its seed
+    drawn here, in input order), its last one in `ends`, with the last chunk.  The ticks only enqueue; one verify() every `depth` ticks.  Where it reports refused
+    ticks both halves of every session stand behind the committed ones: the inputs go back to where the first refused tick found them,
+    that tick runs as the verified eager sequence (fe.push / fe.finish / push_varlen(verify=True), which reruns it as --live would), and
+    the ticks go on from there.  A tick that does not fit the capture runs eagerly inside tick()."""
+    from . import _lib, engine
+    from .audio_frontend import StreamingMel
+    from .graph import packed_filler_rows
+    hop = int(hp.signal.hop_length)
+    n, step = len(wavs), frames * hop
+    # one slot more than inputs, for the filler of a tick of all inputs; per input the frames of a chunk and those an end adds to them
+    fe, s = StreamingMel(n + 1, device=device), model.open_stream(slots=n + 1)
+    seeds = [engine.os_seed() for _ in wavs]
+    tail = (int(hp.signal.n_fft) // 2 // hop + 1) * hop
+    live = s.graphed_live(fe, n, n * (step + tail) + packed_filler_rows(hop), sample=True, depth=depth)
+    wavs = [torch.from_numpy(w).to(device) for w in wavs]
+    pos, outs = [0] * n, [[] for _ in wavs]
+    window = []                # the inputs fed by every tick enqueued since the last verify()
+
+    def plan():
+        feed = [i for i in range(n) if pos[i] < wavs[i].shape[0]]
+        return (feed, [wavs[i][pos[i]:pos[i] + step] for i in feed], {i: seeds[i] for i in feed if pos[i] == 0},
+                [i for i in feed if pos[i] + step >= wavs[i].shape[0]])
+
+    def advance(feed, got, clone):
+        for k, i in enumerate(feed):
+            outs[i].append(got[k].clone() if clone else got[k])      # (a view of the graph's output buffer: the next tick overwrites it)
+            pos[i] += step
+
+    def eager_tick():
+        feed, chunks, starts, ends = plan()
+        began = {i: i not in starts and fe.emitted(i) > 0 for i in feed}
+        for i in starts:
+            fe.reset(i)
+        ready = dict(zip(feed, fe.push(chunks, slots=feed)))
+        for i in ends:
+            ready[i] = torch.cat([ready[i], fe.finish(i)])
+        slots = [i for i in feed if ready[i].shape[0]]
+        for i in slots:
+            if not began[i]:
+                s.reset(i, seeds[i])
+        got = dict(zip(slots, s.push_varlen([ready[i] for i in slots], slots=slots, verify=True))) if slots else {}
+        advance(feed, [got.get(i, torch.empty((0, 1), dtype=torch.float32, device=device)) for i in feed], False)
+
+    def refused(e):
+        """The ticks behind the committed prefix are taken back; the first of them runs eagerly, verified."""
+        if not hasattr(e, 'committed') or e.committed >= len(window):
+            raise e
+        for feed in reversed(window[e.committed:]):
+            for i in feed:
+                pos[i] -= step
+                outs[i].pop()
+        del window[:]
+        eager_tick()
+
+    while True:
+        busy = any(pos[i] < wavs[i].shape[0] for i in range(n))
+        if not busy and not window:
+            break
+        try:
+            if busy:
+                feed, chunks, starts, ends = plan()
+                got = live.tick(chunks, feed, starts=starts, ends=ends)          # (settles what is in flight itself where it runs eagerly)
+                advance(feed, got, True)
+                window.append(feed)
+            if window and (not busy or len(window) >= depth):
+                live.verify()
+                del window[:]
+        except _lib.PwvError as e:
+            refused(e)
     return [torch.cat(o) for o in outs]
 
 

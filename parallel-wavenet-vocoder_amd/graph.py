@@ -24,6 +24,9 @@ kernel at its end commits the tick iff the sticky words are clean, so ticks are 
 GraphedRaggedStream is both at once: a RAGGED tick (StreamingVocoder.push_varlen of running sessions, every one its own frame count)
 captured at a capacity of `slots` sessions and `rows` samples, the frame counts read from a device table by the kernel at the head of
 the graph, the free entries taken by filler sessions, the commit on the device.
+
+GraphedLiveStream puts the streaming mel front-end (audio_frontend.StreamingMel) in front of that ragged tick and the front-end's commit
+behind it: wav chunks in, the sessions' next samples out, one graph launch, both halves committed or refused together on the device.
 """
 from __future__ import annotations
 
@@ -657,6 +660,11 @@ class _TickGraph(_Captured):
     def _write_starts(self, j: int, slots, starts, first) -> None:
         """The starts of the tick into the device tables the graph reads (the ragged tick alone has them)."""
 
+    def _split_starts(self, mel, frames, slots, starts):
+        """(the sessions' new frames, their counts, {i: the first frame of starting entry i}) of a tick with starts."""
+        first = {i: mel[i][:1] for i, s in enumerate(slots) if s in starts}
+        return ([m[1:] if i in first else m for i, m in enumerate(mel)], [f - 1 if i in first else f for i, f in enumerate(frames)], first)
+
     def _tick(self, mel, slots, z, starts):
         st = self.stream
         slots = [st._slot(v) for v in slots]
@@ -675,9 +683,7 @@ class _TickGraph(_Captured):
                              'slot running) and takes graphed ticks from then on' % (fresh()[0], self.FIRST_PUSH % fresh()[0]))
         whole, first = mel, {}
         if starts:          # a starting session's first frame stands in for a kept frame: the rest are its new frames, like anyone's
-            first = {i: mel[i][:1] for i, s in enumerate(slots) if s in starts}
-            mel = [m[1:] if i in first else m for i, m in enumerate(mel)]
-            frames = [f - 1 if i in first else f for i, f in enumerate(frames)]
+            mel, frames, first = self._split_starts(mel, frames, slots, starts)
         if self.sample and z is not None:
             raise ValueError('this graph samples its own noise (sample=True): z is not taken')
         if not self.sample:
@@ -809,14 +815,7 @@ class GraphedRaggedStream(_TickGraph):
         self.filler = packed_filler_rows(hop)
         self.min_frames = self.filler // hop
         self.slots, self.rows = n, rows = int(slots), int(rows)
-        if n < 1:
-            raise ValueError('a graphed ragged tick needs slots >= 1, got %r' % (slots,))
-        if rows % hop or rows < n * self.filler:
-            raise _lib.PwvError('GraphedRaggedStream: a capacity of %d slots needs rows a multiple of hop_length (%d) and at least %d '
-                                '(%d frames per session), got %d' % (n, hop, n * self.filler, self.min_frames, rows))
-        if n > st.n_slots:
-            raise _lib.PwvError('GraphedRaggedStream: a capacity of %d slots needs a stream of at least %d slots (this one has %d): the '
-                                'entries a tick does not use are fillers on OTHER slots of the stream' % (n, n, st.n_slots))
+        self._check_capacity(st, n, rows)
         self.in_frames = rows // hop
         self.mel = torch.zeros((self.in_frames, st.n_mels), dtype=torch.float32, device=dev)
         self.z = torch.zeros((rows, 1), dtype=torch.float32, device=dev)
@@ -830,6 +829,19 @@ class GraphedRaggedStream(_TickGraph):
             self._starts_host = [torch.zeros((n, 2), dtype=torch.int64).pin_memory() for _ in range(self.depth)]
         self._starts_zero = True                # the device table holds no flag
         self._start(n)
+
+    @staticmethod
+    def _check_capacity(st, n: int, rows: int) -> None:
+        """The refusals of a capacity of `n` slots and `rows` samples on the stream `st`."""
+        hop, filler = st.hop, packed_filler_rows(st.hop)
+        if n < 1:
+            raise ValueError('a graphed ragged tick needs slots >= 1, got %r' % (n,))
+        if rows % hop or rows < n * filler:
+            raise _lib.PwvError('GraphedRaggedStream: a capacity of %d slots needs rows a multiple of hop_length (%d) and at least %d '
+                                '(%d frames per session), got %d' % (n, hop, n * filler, filler // hop, rows))
+        if n > st.n_slots:
+            raise _lib.PwvError('GraphedRaggedStream: a capacity of %d slots needs a stream of at least %d slots (this one has %d): the '
+                                'entries a tick does not use are fillers on OTHER slots of the stream' % (n, n, st.n_slots))
 
     def _layout(self, frames):
         """The frame counts of all `slots` entries of a tick: the called sessions', then the fillers'; ValueError if they do not fit."""
@@ -945,7 +957,8 @@ class GraphedRaggedStream(_TickGraph):
             if seed is None and self.sample:          # ... else one from the OS
                 seed = engine.os_seed()
             buf[i, 0], buf[i, 1] = 1, engine.as_int64_bits(seed or 0)
-            self._first[i:i + 1].copy_(first[i], non_blocking=True)
+            if first[i] is not None:          # (None: a kernel of the graph writes the row -- the live tick)
+                self._first[i:i + 1].copy_(first[i], non_blocking=True)
             self._started.add(s)
         self._starts.copy_(staged, non_blocking=True)
         self._starts_zero = not starts
@@ -958,3 +971,292 @@ class GraphedRaggedStream(_TickGraph):
         elif z is not None:
             self.z[:real * self.hop].copy_(z, non_blocking=True)
         return real, RaggedOutput(self.out[:real * self.hop], [f * self.hop for f in frames])
+
+
+class GraphedLiveStream(GraphedRaggedStream):
+    """The LIVE tick -- wav chunks in, the sessions' next samples out -- as one graph (StreamingVocoder.graphed_live; DESIGN.md section 9,
+    "Graph replay of a live tick"): the ragged tick of GraphedRaggedStream with the streaming mel front-end in front of it and the
+    front-end's commit behind it (include/pwv_hip_live_tick.h):
+
+        mel tick kernel (records + front-end session table -> the frames, straight into the ragged tick's mel and first rows; carries)  ->
+        the ragged tick (begin, sampler, unit map, the push, commit)  ->  front-end commit
+
+    Slot k of the StreamingMel `fe` and slot k of the stream are ONE session.  tick(chunks, slots, starts=, ends=, z=) gives session
+    slots[i] its next samples chunks[i] [n_i] and returns a RaggedOutput of [f_i * hop, 1] pieces, f_i the frames that became ready
+    (frames_ready: host arithmetic; possibly none).  `starts` = {slot: seed or None}: the slot begins an utterance with this chunk (the
+    front-end's reset; the vocoder session starts, as by GraphedRaggedStream.tick(starts=), in the first tick in which the utterance has a
+    frame -- the seed is remembered until then -- and that tick yields (frames - 1) * hop samples).  `ends` = [slot, ...]: the utterance
+    ends with this chunk (n_i = 0 allowed): the tick emits every frame that is left, the right reflection taken at the length received.
+    Both halves are committed or refused together on the device; verify() is GraphedRaggedStream's and makes the front-end's view of the
+    sessions stand behind the committed prefix as well; it raises the PwvError naming top_db for the slots that went over the limit.
+
+    `slots` and `rows` are graphed_varlen's capacity; the wav buffer holds rows + slots * (n_fft / 2 + hop) samples.  Where the stream has
+    more slots than `slots` (and the rows hold one filler more) the capture has one entry more than sessions, so that a tick of all
+    `slots` sessions leaves its remaining frames to a filler; else such a tick has to fill the rows exactly, as in graphed_varlen.
+
+    A tick runs the eager sequence fe.push / fe.finish / push_varlen(verify=False) instead (eager_calls; same bits) where it does not fit
+    the capture (more slots, samples or frames than the capacity, fewer frames than min_frames in a session, no session with a frame),
+    during a suspension of the persistent launches, or where a vocoder start has fewer than min_frames + 1 frames."""
+
+    def __init__(self, stream, fe, slots: int, rows: int, sample: bool = True, depth: int = 4, warmup: int = 2):
+        for name, a, b in (('slots', fe.n_slots, stream.n_slots), ('hop_length', fe.hop, stream.hop), ('n_mels', fe.n_mels, stream.n_mels)):
+            if a != b:
+                raise _lib.PwvError('GraphedLiveStream: the front-end and the stream disagree on %s (%d against %d): slot k of both is one '
+                                    'session' % (name, a, b))
+        if stream._zero_block is None:
+            raise _lib.PwvError('GraphedLiveStream: this stream has no zero block (its histories are a caller\'s allocation, hist_alloc): '
+                                'its graphed ticks take no starts')
+        self.fe = fe
+        self.sessions, rows = int(slots), int(rows)
+        self._check_capacity(stream, self.sessions, rows)
+        # one entry more than sessions wherever the stream has a slot and the rows a filler for it: a tick of all `slots` sessions then
+        # leaves its remaining frames to a filler, where the ragged tick would have to fill the rows exactly
+        spare = self.sessions < stream.n_slots and rows >= (self.sessions + 1) * packed_filler_rows(stream.hop)
+        super().__init__(stream, self.sessions + (1 if spare else 0), rows, sample=sample, depth=depth, warmup=warmup)
+
+    def _start(self, n: int):
+        fe, dev = self.fe, self.device
+        self.wav_cap = self.rows + self.sessions * (fe.n_fft // 2 + fe.hop)
+        self._wav = torch.zeros((self.wav_cap,), dtype=torch.float32, device=dev)
+        self._rec = torch.zeros((n, _lib.LIVE_TICK_REC), dtype=torch.int64, device=dev)
+        self._scratch = torch.full((n,), -(1 << 31), dtype=torch.int32, device=dev)
+        self._rec_host = [torch.zeros((n, _lib.LIVE_TICK_REC), dtype=torch.int64).pin_memory() for _ in range(self.depth)]
+        self._fe_rows_host = [torch.zeros((n, 4), dtype=torch.int64).pin_memory() for _ in range(self.depth)]
+        self._rec_zero = True                   # the device table holds no active record
+        self._fe_view = {}                      # slot -> (received, emitted) behind the ticks in flight
+        self._seed_wait = {}                    # slot -> the seed of an utterance that has begun and has no frame yet
+        self._undo = []                         # per graphed tick since the last verify(): what it changed of _seed_wait
+        self._eager_undo = None                 # the front-end sessions in front of an eager tick that only enqueued
+        self._ctx = None
+        super()._start(n)
+
+    def _live_args(self):
+        from .audio_frontend import AMIN, TOP_DB
+        fe, la = self.fe, _lib.LiveTickArgs()
+        la.wav, la.window, la.mel_basis = self._wav.data_ptr(), fe._window.data_ptr(), fe._basis.data_ptr()
+        la.mel, la.first = self.mel.data_ptr(), self._first.data_ptr()
+        la.state, la.max_key, la.scratch, la.sess = fe._state.data_ptr(), fe._max.data_ptr(), self._scratch.data_ptr(), fe._sess.data_ptr()
+        la.rec, la.rec_host, la.words = self._rec.data_ptr(), None, self._words.addr
+        la.wav_cap, la.mel_rows = self.wav_cap, self.in_frames
+        la.N, la.n_slots, la.n_first, la.n_fft, la.hop, la.n_mels = self._n, fe.n_slots, self._n, fe.n_fft, fe.hop, fe.n_mels
+        la.amin, la.max_db, la.min_db, la.limit_db = AMIN, fe.max_db, fe.min_db, fe.min_db + TOP_DB
+        return la
+
+    def _before_capture(self):
+        if not self._rec_zero:          # warm-up and capture have no record: the front-end's sessions are not touched
+            self._rec.zero_()
+            self._rec_zero = True
+        super()._before_capture()
+
+    def _enqueue(self):
+        lib, la = _lib.lib(), self._live_args()
+        _lib.check(lib.pwv_live_tick_mel(ctypes.byref(la), engine._stream()), 'pwv_live_tick_mel')
+        out = super()._enqueue()
+        _lib.check(lib.pwv_live_tick_commit(ctypes.byref(la), engine._stream()), 'pwv_live_tick_commit')
+        return out
+
+    # -- the hooks of _TickGraph._tick: the frames are counts here, a kernel of the graph writes them ------------------------------------
+    def _check_mel(self, counts, k):
+        return counts, list(counts)
+
+    def _split_starts(self, mel, frames, slots, starts):
+        first = {i: None for i, s in enumerate(slots) if s in starts}
+        frames = [f - 1 if i in first else f for i, f in enumerate(frames)]
+        return frames, frames, first
+
+    def _begin_tick(self) -> int:
+        self._j = super()._begin_tick()
+        return self._j
+
+    def _eager(self, whole, slots, z, verify):
+        return self._eager_live(self._ctx, reset_vocoder=False)
+
+    def _copy_in(self, mel, z, frames):
+        """The front-end half of the tick through pinned staging: the records, the chunks into the wav buffer, the front-end session rows
+        where the host's view says the device row differs (an eager push, finish or reset since)."""
+        fe, j, c = self.fe, self._j, self._ctx
+        buf = self._rec_host[j].numpy()
+        buf[:] = 0
+        off = row = entry = 0
+        undo = {}
+        for i, s in enumerate(c['slots']):
+            r, n = c['recs'][i], int(c['chunks'][i].shape[0])
+            flags = _lib.LIVE_ACTIVE | (_lib.LIVE_START if s in c['starts'] else 0) | (_lib.LIVE_FIRST if c['vstart'][i] else 0)
+            part = r.frames >= 1
+            buf[i] = (r.carry_first, r.carry_len, off, n, r.first_frame, r.frames, r.final_len, s, flags, row, r.new_carry_first,
+                      entry if part else 0)
+            off += n
+            if part:
+                row, entry = row + r.frames - (1 if c['vstart'][i] else 0), entry + 1
+        self._rec.copy_(self._rec_host[j], non_blocking=True)
+        self._rec_zero = False
+        given = [ch for ch in c['chunks'] if ch.shape[0]]
+        if given:
+            torch.cat(given, out=self._wav[:off])
+        rows = self._fe_rows_host[j]
+        for i, s in enumerate(c['slots']):
+            if s not in self._fe_view:          # (a slot with ticks in flight is the device's)
+                want = (fe._gen[s], fe._received[s], fe._emitted[s])
+                if fe._sess_host[s] != want:
+                    rows[i, 0], rows[i, 1], rows[i, 2] = want
+                    fe._sess[s, :3].copy_(rows[i, :3], non_blocking=True)          # (the sticky `over` word stays the device's)
+                    fe._sess_host[s] = want
+            self._fe_view[s] = (c['recs'][i].received, c['recs'][i].emitted)
+            undo[s] = self._seed_wait.get(s, self)          # (self: no entry)
+        self._note_seeds(c)
+        self._undo.append(undo)
+        fe._live = self
+        real = sum(frames)
+        if isinstance(z, list):
+            torch.cat(z, out=self.z[:real * self.hop])
+        elif z is not None:
+            self.z[:real * self.hop].copy_(z, non_blocking=True)
+        return real, RaggedOutput(self.out[:real * self.hop], [f * self.hop for f in frames])
+
+    def _note_seeds(self, c) -> None:
+        """The seeds that wait for their utterance's first frame, after the tick `c`."""
+        for i, s in enumerate(c['slots']):
+            if c['vstart'][i] or c['recs'][i].final_len >= 0:
+                self._seed_wait.pop(s, None)
+            elif s in c['starts']:
+                self._seed_wait[s] = c['starts'][s]
+
+    # -- a tick ------------------------------------------------------------------------------------------------------------------
+    def tick(self, chunks, slots, starts=None, ends=None, z=None):
+        """Session slots[i] receives its next samples chunks[i], [n_i >= 1] float32 on the GPU (n_i = 0 for a slot in `ends`); see the
+        class.  Returns a RaggedOutput of [f_i * hop, 1] views of the graph's output buffer, valid until the next tick.  Enqueue-only."""
+        from .audio_frontend import live_record
+        st, fe = self.stream, self.fe
+        slots = [st._slot(v) for v in slots]
+        if not slots or len(set(slots)) != len(slots):
+            raise ValueError('slots must be a non-empty list of distinct slots, got %r' % (slots,))
+        if not isinstance(chunks, (list, tuple)) or len(chunks) != len(slots):
+            raise ValueError('chunks must be a list of [n] tensors, one per slot (%d slots)' % len(slots))
+        if starts is not None and not isinstance(starts, dict):
+            raise ValueError('starts must be a dict {slot: seed or None}, got %r' % (starts,))
+        starts = {st._slot(k): (None if v is None else st._check_seed(v)) for k, v in (starts or {}).items()}
+        ends = [st._slot(v) for v in (ends or [])]
+        for s in list(starts) + ends:
+            if s not in slots:
+                raise ValueError('starts / ends name slot %d, which is not among the slots of this tick (%r)' % (s, slots))
+        for i, c in enumerate(chunks):
+            if not hasattr(c, 'dim') or c.dim() != 1 or (c.shape[0] < 1 and slots[i] not in ends):
+                raise ValueError('chunks[%d] must be [n >= 1] (n = 0 only for a slot in ends), got %s' % (i, tuple(getattr(c, 'shape', ()))))
+        chunks = [engine._require_cuda_f32(c, 'chunks[%d]' % i) for i, c in enumerate(chunks)]
+        if st._pending is not None and st._ticker is not self:
+            self._settle()          # an eager tick that only enqueued, or another graph's ticks
+        if fe._live is not None and fe._live is not self:
+            fe._live.verify()
+        recs, vstart = [], []
+        for i, s in enumerate(slots):
+            received, emitted = (0, 0) if s in starts else self._fe_view.get(s, (fe._received[s], fe._emitted[s]))
+            recs.append(live_record(received, emitted, int(chunks[i].shape[0]), s in ends, fe.n_fft, fe.hop))
+            vstart.append(emitted == 0 and recs[i].frames >= 1)          # the utterance's first frame: the vocoder side starts
+        part = [i for i in range(len(slots)) if recs[i].frames >= 1]
+        samples = [(recs[i].frames - (1 if vstart[i] else 0)) * self.hop for i in range(len(slots))]
+        if self.sample and z is not None:
+            raise ValueError('this graph samples its own noise (sample=True): z is not taken')
+        if not self.sample:
+            if z is None:
+                raise ValueError('this graph has no sampler (sample=False): z, one [f_i * %d, 1] per slot or the packed [%d, 1], is required'
+                                 % (self.hop, sum(samples)))
+            if not isinstance(z, (list, tuple)):
+                z = engine._require_cuda_f32(z, 'z')
+                if tuple(z.shape) != (sum(samples), 1):
+                    raise ValueError('z must be the packed [%d, 1], got %s' % (sum(samples), tuple(z.shape)))
+                z = list(RaggedOutput(z, samples))
+            if len(z) != len(slots) or any(tuple(getattr(v, 'shape', ())) != (t, 1) for v, t in zip(z, samples)):
+                raise ValueError('z must hold one [f_i * %d, 1] piece per slot: %r samples' % (self.hop, samples))
+            z = [engine._require_cuda_f32(z[i], 'z[%d]' % i) for i in part]
+        vslots = [slots[i] for i in part]
+        vstarts = {slots[i]: (starts[slots[i]] if slots[i] in starts else self._seed_wait.get(slots[i])) for i in part if vstart[i]}
+        self._ctx = c = dict(slots=slots, chunks=chunks, starts=starts, ends=ends, recs=recs, vstart=vstart, part=part, z=z,
+                             vslots=vslots, vstarts=vstarts, samples=samples)
+        short = any(vstart[i] and recs[i].frames < self.min_frames + 1 for i in part)
+        fits = (bool(part) and not short and len(slots) <= self.sessions and sum(int(ch.shape[0]) for ch in chunks) <= self.wav_cap
+                and self._ready() and self._columns([t // self.hop for t in (samples[i] for i in part)]) is not None)
+        if fits:
+            out = self._tick([recs[i].frames for i in part], vslots, z, vstarts or None)
+        else:
+            self._settle()
+            self.eager_calls += 1
+            out = self._eager_live(c, reset_vocoder=True)
+        return RaggedOutput(out.packed, samples)
+
+    def _eager_live(self, c, reset_vocoder: bool):
+        """The tick `c` as the eager sequence: reset / push / finish of the front-end, then reset and push_varlen(verify=False) of the
+        sessions that have a frame.  What is in flight has been settled."""
+        st, fe, slots = self.stream, self.fe, c['slots']
+        self._eager_undo = ({s: (fe._gen[s], fe._received[s], fe._emitted[s]) for s in slots}, {s: self._seed_wait.get(s, self) for s in slots})
+        for s in c['starts']:
+            fe.reset(s)
+        fed = [i for i in range(len(slots)) if c['chunks'][i].shape[0]]
+        pieces = {i: [] for i in range(len(slots))}
+        if fed:
+            for i, p in zip(fed, fe.push([c['chunks'][i] for i in fed], slots=[slots[i] for i in fed])):
+                pieces[i].append(p)
+            fe._note_over([slots[i] for i in fed])
+        for s in c['ends']:
+            pieces[slots.index(s)].append(fe._launch([s], [None], True)[0])
+            fe._note_over([s])
+            fe.reset(s)
+        self._note_seeds(c)
+        if not c['part']:          # nobody has a frame: the vocoder sits the tick out
+            self._carry += 1          # (a tick all the same: the next verify() counts it)
+            return RaggedOutput(torch.empty((0, 1), dtype=torch.float32, device=self.device), [])
+        if reset_vocoder:
+            for s, seed in c['vstarts'].items():          # (a fresh slot keeps the seed its own reset gave it)
+                st.reset(s, seed if seed is not None or st._running[s] else st._seed[s])
+        mels = [pieces[i][0] if len(pieces[i]) == 1 else torch.cat(pieces[i]) for i in c['part']]
+        out = st.push_varlen(mels, slots=c['vslots'], z=c['z'] if not self.sample else None, verify=False)
+        if st._pending is None:          # (first frames alone: kept at once, nothing enqueued -- a tick all the same)
+            self._carry += 1
+        return out
+
+    def verify(self) -> int:
+        """GraphedRaggedStream.verify(), for both halves: the front-end's received / emitted / generation of the sessions of the ticks in
+        flight are read back from its device table -- they stand behind the committed prefix, like the vocoder's --, and a PwvError
+        naming top_db is raised for the slots whose utterance went over min_db + top_db since the last verify() (checked when nothing
+        else is reported)."""
+        from .audio_frontend import TOP_DB
+        st, fe = self.stream, self.fe
+        mine, carry, err = st._ticker is self, self._carry, None
+        try:
+            done = super().verify()
+        except _lib.PwvError as e:
+            if not hasattr(e, 'committed'):
+                raise
+            err, done = e, e.committed
+        table = fe._sess.cpu().tolist()
+        if mine:
+            for s in self._fe_view:
+                gen, received, emitted = int(table[s][0]) & 1, int(table[s][1]), int(table[s][2])
+                fe._gen[s], fe._received[s], fe._emitted[s] = gen, received, emitted
+                fe._sess_host[s] = (gen, received, emitted)
+            for undo in reversed(self._undo[max(done - carry, 0):]):          # the refused ticks changed nothing
+                self._restore_seeds(undo)
+        elif err is not None and self._eager_undo is not None:          # an eager tick whose push did not commit
+            for s, (gen, received, emitted) in self._eager_undo[0].items():
+                fe._gen[s], fe._received[s], fe._emitted[s] = gen, received, emitted
+            self._restore_seeds(self._eager_undo[1])
+        self._fe_view, self._undo, self._eager_undo = {}, [], None
+        if fe._live is self:
+            fe._live = None
+        if err is not None:
+            raise err
+        over = [s for s in range(fe.n_slots) if table[s][3]]
+        if over:
+            fe._sess[:, 3].zero_()
+            e = _lib.PwvError('GraphedLiveStream: the top_db floor of the one-shot front-end would have been active for slot(s) %s: an '
+                              'utterance\'s largest raw dB went over min_db + top_db = %g; its frames are not the one-shot\'s'
+                              % (over, fe.min_db + TOP_DB))
+            e.committed = done
+            raise e
+        return done
+
+    def _restore_seeds(self, undo) -> None:
+        for s, seed in undo.items():
+            if seed is self:
+                self._seed_wait.pop(s, None)
+            else:
+                self._seed_wait[s] = seed

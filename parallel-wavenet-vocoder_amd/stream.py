@@ -395,6 +395,14 @@ class StreamingVocoder(object):
         from .graph import GraphedRaggedStream
         return GraphedRaggedStream(self, slots, rows, sample=sample, depth=depth, warmup=warmup)
 
+    def graphed_live(self, fe, slots: int, rows: int, sample: bool = True, depth: int = 4, warmup: int = 2):
+        """A LIVE tick -- wav chunks in, wav chunks out -- captured into a HIP graph: the ragged tick of graphed_varlen at a capacity of
+        `slots` sessions and `rows` samples with the streaming mel front-end `fe` (audio_frontend.StreamingMel; slot k of both is one
+        session) at its head and the front-end's commit at its end (graph.GraphedLiveStream; DESIGN.md section 9, "Graph replay of a
+        live tick")."""
+        from .graph import GraphedLiveStream
+        return GraphedLiveStream(self, fe, slots, rows, sample=sample, depth=depth, warmup=warmup)
+
     # -- a push ----------------------------------------------------------------------------------------------------------
     def _slots(self, slots) -> List[int]:
         return list(range(self.n_slots)) if slots is None else [self._slot(v) for v in slots]

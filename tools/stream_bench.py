@@ -66,6 +66,8 @@ One cell: 8 running sessions x 10 frames (800 samples each).  Legs, same protoco
 --steps after --warmup, the legs one after the other in one process, the round twice):
   vocoder    push_varlen(verify=False) of 8 x 10 ready-made frames + verify(): the tick without a front-end
   live       StreamingMel.push of 8 x 800 samples, its 8 x 10 frames into the same push_varlen + verify(): wav chunks in, wav chunks out
+  live_graph the same tick as ONE graph launch (StreamingVocoder.graphed_live: front-end, ragged tick and both commits on the device) +
+             verify(); `live_graph_below_live`: every live_graph median is below every live median of the run
   frontend   StreamingMel.push alone + a synchronisation
   one_shot   wav_to_mel_device on the same [8, 800] samples + a synchronisation: the whole-utterance kernel on a tick's worth (11 frames
              each, both edges reflected -- not the frames of a stream)
@@ -167,9 +169,19 @@ def main():
         chunks, mels, zs = list(wav), [rand(frames, cfg.n_mels) for _ in range(S)], [rand(chunk, 1) for _ in range(S)]
         assert [int(m.shape[0]) for m in fe.push(chunks)] == [frames] * S
 
+        # the live tick as ONE graph launch (graph.GraphedLiveStream), on a stream and a front-end of its own in the same steady state; a
+        # slot and a filler's rows to spare, so that the tick of all 8 sessions replays
+        from pwv_amd.graph import packed_filler_rows
+        stream_g, fe_g = model.open_stream(slots=S + 1), StreamingMel(S + 1)
+        stream_g.push(rand(S, warm // hop + 1, cfg.n_mels), slots=list(range(S)), z=rand(S, warm, 1))
+        fe_g.push(list(0.5 * rand(S, chunk)), slots=list(range(S)))
+        live = stream_g.graphed_live(fe_g, S, S * chunk + packed_filler_rows(hop), sample=False)
+        assert [int(o.shape[0]) for o in live.tick(chunks, list(range(S)), z=zs)] == [chunk] * S and live.verify() == 1 and live.eager_calls == 0
+
         legs = {
             'vocoder': (lambda: stream.push_varlen(mels, z=zs, verify=False), stream.verify),
             'live': (lambda: stream.push_varlen(fe.push(chunks), z=zs, verify=False), stream.verify),
+            'live_graph': (lambda: live.tick(chunks, list(range(S)), z=zs), live.verify),
             'frontend': (lambda: fe.push(chunks), torch.cuda.synchronize),
             'one_shot': (lambda: wav_to_mel_device(wav), torch.cuda.synchronize),
         }
@@ -185,6 +197,9 @@ def main():
         out['spread'] = round(max(abs(out[leg]['ms'][0] - out[leg]['ms'][1]) for leg in legs), 4)
         out['live_over_vocoder'] = [round(a / b, 3) for a, b in zip(out['live']['ms'], out['vocoder']['ms'])]
         out['live_minus_vocoder_ms'] = [round(a - b, 4) for a, b in zip(out['live']['ms'], out['vocoder']['ms'])]
+        out['live_graph_over_live'] = [round(a / b, 3) for a, b in zip(out['live_graph']['ms'], out['live']['ms'])]
+        out['live_graph_below_live'] = max(out['live_graph']['ms']) < min(out['live']['ms'])          # every median below every median
+        out['live_graph_eager_calls'], out['live_graph_captures'] = live.eager_calls, live.captures
         print(json.dumps(out))
         return
 
