@@ -18,7 +18,7 @@ _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 _REPO_ROOT = os.path.dirname(_PKG_DIR)
 LIB_PATH = os.environ.get('PWV_LIB') or os.path.join(_PKG_DIR, 'libpwv_hip.so')   # PWV_LIB: A/B another build
 CSRC = [os.path.join(_PKG_DIR, 'csrc', f) for f in ('pwv_layer.hip', 'pwv_layer_f16.hip', 'pwv_layer_h16.hip', 'pwv_misc.hip',
-                                                    'pwv_stack_persist.hip', 'pwv_norm.hip', 'pwv_audio.hip', 'pwv_stream_tick.hip')]
+                                                    'pwv_stack_persist.hip', 'pwv_norm.hip', 'pwv_audio.hip', 'pwv_stream_tick.hip', 'pwv_score.hip')]
 
 HEADER_VERSION = 301          # PWV_HIP_VERSION of include/pwv_hip.h these ctypes mirrors were written against
 FIRST_FOLD_FLOATS = 2048      # PWV_FIRST_FOLD_FLOATS
@@ -48,6 +48,8 @@ EXPORTED_SYMBOLS = (
 EXTENSION_SYMBOLS = ('pwv_wav_to_mel_db_stream_f32',)
 # ... and of include/pwv_hip_live_tick.h: the streaming front-end inside a captured ragged tick
 LIVE_TICK_SYMBOLS = ('pwv_live_tick_mel', 'pwv_live_tick_commit')
+# ... and of include/pwv_hip_score.h: the L1 and the STFT power loss of generated audio
+SCORE_SYMBOLS = ('pwv_score_workspace_bytes', 'pwv_score_f32')
 
 
 class PwvError(RuntimeError):
@@ -323,6 +325,30 @@ class LiveTickArgs(Structure):
         self.struct_size = ctypes.sizeof(LiveTickArgs)
 
 
+SCORE_MAX_WIN = 1024          # PWV_SCORE_MAX_WIN
+SCORE_TILE = 1024             # PWV_SCORE_TILE: samples per L1 partial
+
+
+class ScoreArgs(Structure):
+    """pwv_score_args: one scoring call over n utterances, uniform or packed (include/pwv_hip_score.h)."""
+    _fields_ = [
+        ('struct_size', c_size_t),      # set by __init__
+        ('out', c_void_p),
+        ('y', c_void_p),
+        ('cu_rows', c_void_p),          # NULL: the uniform form
+        ('n', ctypes.c_int32), ('T', ctypes.c_int32),
+        ('rows', c_int64),
+        ('win_length', ctypes.c_int32), ('hop_length', ctypes.c_int32),
+        ('result', c_void_p),
+        ('workspace', c_void_p),
+        ('workspace_bytes', c_size_t),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = ctypes.sizeof(ScoreArgs)
+
+
 # per-source extra flags (none in the product; tools/probes/regw/README.md: the register-stationary probe kernel needs
 # `-mllvm -amdgpu-mfma-vgpr-form=1`, which is why the sources are compiled one by one)
 EXTRA_FLAGS = {}
@@ -471,6 +497,9 @@ def _declare(lib):
     lib.pwv_wav_to_mel_db_stream_f32.argtypes = [POINTER(MelStreamArgs), c_void_p]
     lib.pwv_live_tick_mel.argtypes = [POINTER(LiveTickArgs), c_void_p]
     lib.pwv_live_tick_commit.argtypes = [POINTER(LiveTickArgs), c_void_p]
+    lib.pwv_score_workspace_bytes.restype = c_size_t
+    lib.pwv_score_workspace_bytes.argtypes = [POINTER(ScoreArgs)]
+    lib.pwv_score_f32.argtypes = [POINTER(ScoreArgs), c_void_p]
     lib.pwv_instance_norm_workspace_bytes.restype = c_size_t
     lib.pwv_instance_norm_workspace_bytes.argtypes = [c_int, c_int, c_int]
     lib.pwv_instance_norm_f32.argtypes = [f32p, f32p, c_int, c_int, c_int, f32p, f32p, ctypes.c_float, c_void_p, c_size_t, c_void_p]
@@ -492,7 +521,7 @@ def _declare(lib):
     lib.pwv_status_words_alloc.argtypes = [POINTER(c_void_p)]
     lib.pwv_status_words_free.argtypes = [c_void_p]
     lib.pwv_range_check_f32.argtypes = [f32p, c_int64, ctypes.c_float, c_void_p, c_void_p]
-    for name in EXPORTED_SYMBOLS + EXTENSION_SYMBOLS + LIVE_TICK_SYMBOLS:      # fails loudly (AttributeError) if a symbol is missing
+    for name in EXPORTED_SYMBOLS + EXTENSION_SYMBOLS + LIVE_TICK_SYMBOLS + SCORE_SYMBOLS:      # fails loudly (AttributeError) if a symbol is missing
         getattr(lib, name)
     return lib
 

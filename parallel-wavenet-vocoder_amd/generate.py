@@ -12,7 +12,7 @@ follow from the platform, not from the math:
     TensorBoard audio summaries, generate.py:71-73);
   * `data_path: 'synthetic'` (bench cases) or a glob of .npy mel files replaces the wav dataset;
     wav input uses the torch STFT front-end in audio_frontend.py.
-CLI (python-fire style, fire itself is not installed):  python -m pwv_amd.generate <case> [--ckpt=..] [--debug] [--varlen [--seed=S]] [--stream=FRAMES [--graph | --live]]
+CLI (python-fire style, fire itself is not installed):  python -m pwv_amd.generate <case> [--ckpt=..] [--debug] [--varlen [--seed=S]] [--stream=FRAMES [--graph | --live]] [--score]
 """
 from __future__ import absolute_import, division, print_function
 
@@ -39,11 +39,14 @@ def _latest_checkpoint(logdir):
     return cands[-1] if cands else None
 
 
-def _load_mels(data_path, batch_size, length, device):
-    """(gt_wav or None, melspec[N, t_mel, n_mels]) for the first `batch_size` items."""
+def _load_mels(data_path, batch_size, length, device, info=None):
+    """(gt_wav or None, melspec[N, t_mel, n_mels]) for the first `batch_size` items.  `info`, a dict, receives 'files': the name of
+    every item's input."""
     hop, n_mels = hp.signal.hop_length, hp.signal.n_mels
     t_mel = 1 + length // hop
+    info = {} if info is None else info
     if data_path == 'synthetic':
+        info['files'] = ['synthetic:%d' % i for i in range(batch_size)]
         g = torch.Generator().manual_seed(0)
         return None, (torch.rand((batch_size, t_mel, n_mels), generator=g) * 2 - 1).to(device)
     files = sorted(glob.glob(data_path))
@@ -53,6 +56,7 @@ def _load_mels(data_path, batch_size, length, device):
     split = int(len(files) * hp.train.dataset_ratio)
     files = (files[split:] or files)[:batch_size]
     print('dataset size is {}'.format(len(files)))
+    info['files'] = (files + [files[-1]] * batch_size)[:batch_size]
     if all(not f.endswith('.npy') for f in files):
         # wav input: host reads / trims / pads (data_load.py:42-50), then the spectrogram is computed ON THE DEVICE
         # (audio_frontend.wav_to_mel_device) -- the mel never visits the host between the front-end and the network
@@ -109,25 +113,31 @@ def forward_over_ranks(mel, batch_size, length, device, make_model, noise_window
                                        mel, n_mels, length, hop, halo, device, group=group)
 
 
-def _load_mels_varlen(data_path, batch_size, device):
+def _load_mels_varlen(data_path, batch_size, device, info=None):
     """--varlen: one [t_mel_i, n_mels] mel per input at the input's OWN length -- a .npy mel as stored (at least 2 frames), a wav
     trimmed (data_load.py:42-44) and cut down to a multiple of hop_length, its mel computed on the device.  'synthetic' has no lengths
-    of its own: every utterance is generate.length long."""
+    of its own: every utterance is generate.length long.  `info`, a dict, receives 'files' and 'wavs': per input its name and the
+    trimmed wav its mel was computed from (None for a mel that was given)."""
     hop = hp.signal.hop_length
+    info = {} if info is None else info
     if data_path == 'synthetic':
-        return list(_load_mels(data_path, batch_size, hp.generate.length, device)[1].unbind(0))
+        mels = list(_load_mels(data_path, batch_size, hp.generate.length, device, info)[1].unbind(0))
+        info['wavs'] = [None] * len(mels)
+        return mels
     files = sorted(glob.glob(data_path))
     if not files:
         raise FileNotFoundError('no input files match data_path %r (use data_path: synthetic for seeded noise mel)' % data_path)
     split = int(len(files) * hp.train.dataset_ratio)
     files = (files[split:] or files)[:batch_size]
-    mels = []
+    mels, wavs = [], []
+    info['files'], info['wavs'] = files, wavs
     for f in files:
         if f.endswith('.npy'):
             m = np.load(f).astype(np.float32)
             if m.ndim != 2 or m.shape[0] < 2:
                 raise ValueError('%s: a mel needs at least 2 frames, got shape %s' % (f, m.shape))
             mels.append(torch.from_numpy(m).to(device))
+            wavs.append(None)
         else:
             from .audio_frontend import read_wav, trim_wav, wav_to_mel_device
             wav = trim_wav(read_wav(f, hp.signal.sr))
@@ -135,11 +145,74 @@ def _load_mels_varlen(data_path, batch_size, device):
             if len(wav) == 0:
                 raise ValueError('%s: shorter than one hop (%d samples) after trimming' % (f, hop))
             mels.append(wav_to_mel_device(torch.from_numpy(wav[None]).to(device))[0])
+            wavs.append(wav)
     print('dataset size is {}'.format(len(mels)))
     return mels
 
 
-def generate(case='default', ckpt=None, debug=False, varlen=False, seed=None, stream=None, graph=False, live=False):
+def _score_outputs(pred, gt_wavs, mels, files, logdir, device):
+    """--score: the forward's result against what went in, on the device (score.py), under the reference's names.
+      pred      [N, L, 1] (tensor or array), or a list of [len_i, 1]
+      gt_wavs   the ground-truth wavs laid out as `pred` ([N, L, 1] / a list of [len_i]; None entries allowed in a list), or None
+      mels      the input mels ([N, t_mel, n_mels] or a list of [t_mel_i, n_mels]); None: computed from the ground truth
+    Prints loss/likelihood, loss/power and loss/total of the batch and writes scores.json into `logdir`: those three, weight_power_loss,
+    and per input file, samples, l1, frames, power and mel_l1 -- the L1 between the mel of the prediction (the device front-end) and the
+    input mel.  l1 and power are null where an input has no ground-truth wav; the batch numbers cover the inputs that have one.  mel_l1 is
+    null only for a prediction too short for the front-end (n_fft / 2 samples or fewer).  Returns the dict it wrote."""
+    import json
+    from . import score as S
+    from .audio_frontend import wav_to_mel_device
+
+    def dev(a):
+        return (a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))).to(device)
+
+    uniform = not isinstance(pred, (list, tuple))
+    preds = [p.reshape(-1, 1) for p in (dev(pred).unbind(0) if uniform else [dev(p) for p in pred])]
+    n = len(preds)
+    gts = [None] * n if gt_wavs is None else [None if g is None else dev(g).reshape(-1, 1) for g in gt_wavs]
+    mels = [None] * n if mels is None else list(mels.unbind(0) if isinstance(mels, torch.Tensor) else mels)
+    half = int(hp.signal.n_fft) // 2
+    for i in range(n):
+        if mels[i] is None and gts[i] is not None and gts[i].shape[0] > half:
+            mels[i] = wav_to_mel_device(gts[i].reshape(1, -1))[0]
+
+    def clean(v):
+        v = float(v)
+        return v if np.isfinite(v) else None
+
+    have = [i for i in range(n) if gts[i] is not None]
+    per = [dict(file=files[i] if files else None, samples=int(preds[i].shape[0]), l1=None, frames=0, power=None, mel_l1=None) for i in range(n)]
+    weight = float(hp.train.weight_power_loss)
+    batch = dict(likelihood=None, power=None, total=None)
+    if have:
+        if uniform and len(have) == n:
+            s = S.score(torch.stack(preds), torch.stack(gts))
+        else:
+            s = S.score_varlen([preds[i] for i in have], [gts[i] for i in have])
+        l1, power, frames = s.l1, s.power, s.frames
+        for k, i in enumerate(have):
+            per[i].update(l1=clean(l1[k]), power=clean(power[k]), frames=int(frames[k]))
+        batch = dict(likelihood=clean(s.likelihood), power=clean(s.power_loss), total=clean(s.total(weight)))
+    able = [i for i in range(n) if mels[i] is not None and preds[i].shape[0] > half]
+    if able:
+        pred_mels = [wav_to_mel_device(preds[i].reshape(1, -1))[0] for i in able]
+        m = S.mel_l1(pred_mels, [mels[i].to(device).float() for i in able]).l1
+        for k, i in enumerate(able):
+            per[i]['mel_l1'] = clean(m[k])
+    out = {'loss/likelihood': batch['likelihood'], 'loss/power': batch['power'], 'loss/total': batch['total'], 'weight_power_loss': weight,
+           'win_length': int(hp.signal.win_length), 'hop_length': int(hp.signal.hop_length), 'inputs': per}
+    for name in ('loss/likelihood', 'loss/power', 'loss/total'):
+        print('%s: %s' % (name, 'n/a (no ground-truth wav)' if out[name] is None else '%.6g' % out[name]))
+    try:
+        os.makedirs(logdir, exist_ok=True)
+        with open(os.path.join(logdir, 'scores.json'), 'w') as f:
+            json.dump(out, f, indent=1)
+    except OSError as e:
+        print('could not write scores.json to %s: %s' % (logdir, e))
+    return out
+
+
+def generate(case='default', ckpt=None, debug=False, varlen=False, seed=None, stream=None, graph=False, live=False, score=False):
     '''
     :param case: experiment case name
     :param ckpt: checkpoint to load model
@@ -156,6 +229,8 @@ def generate(case='default', ckpt=None, debug=False, varlen=False, seed=None, st
     :param live: (with stream, wav inputs) the front-end streams too: every tick gives each unfinished input its next `stream` x hop
         SAMPLES through audio_frontend.StreamingMel, and the frames that became ready to the sessions; same files.  --live=graph:
         every such tick is one replay of a captured live tick (StreamingVocoder.graphed_live).
+    :param score: (every mode) after the forward, score the result on the device against the ground-truth wavs and the input mels
+        (_score_outputs): prints loss/likelihood, loss/power and loss/total and writes scores.json next to the waveforms.
     '''
     if live and (stream is None or graph or live not in (True, 'graph')):
         raise ValueError('--live (or --live=graph) applies to --stream=FRAMES without --graph (wav chunks in, wav chunks out)')
@@ -190,15 +265,17 @@ def generate(case='default', ckpt=None, debug=False, varlen=False, seed=None, st
             raise ValueError('--varlen / --stream run on one GPU (a packed batch or a set of sessions is not sharded over ranks)')
         # one process per GPU (torchrun): utterances -- or, for a batch smaller than the world, time slices -- shard over
         # the ranks; rank 0 reads the inputs and writes the outputs
-        return _generate_over_ranks(store, batch_size, length, device, logdir, ckpt, debug)
+        return _generate_over_ranks(store, batch_size, length, device, logdir, ckpt, debug, score)
+    info = {}                  # what --score needs of the inputs: their names and, where they are audio, the trimmed wavs
     if live:
         gt_wav, melspec, wavs = None, None, _load_wavs_live(live_files)
+        info.update(files=live_files, wavs=wavs)
         batch_size, length = 1, sum(len(w) for w in wavs)
     elif varlen or stream:
-        gt_wav, melspec = None, _load_mels_varlen(hp.data_path, batch_size, device)
+        gt_wav, melspec = None, _load_mels_varlen(hp.data_path, batch_size, device, info)
         batch_size, length = 1, sum(int(m.shape[0] - 1) * hp.signal.hop_length for m in melspec)     # (the timing line: all samples)
     else:
-        gt_wav, melspec = _load_mels(hp.data_path, batch_size, length, device)
+        gt_wav, melspec = _load_mels(hp.data_path, batch_size, length, device, info)
 
     model = IAFVocoder(batch_size=batch_size, length=length, store=store)
 
@@ -247,10 +324,14 @@ def generate(case='default', ckpt=None, debug=False, varlen=False, seed=None, st
     if varlen or stream:
         pred_wav = [p.cpu().numpy() for p in pred]
         _write_outputs_varlen(pred_wav, logdir)
+        if score:
+            _score_outputs(list(pred), info.get('wavs'), melspec, info.get('files'), logdir, device)
         print('Done.')
         return pred_wav
     pred_wav = pred.cpu().numpy()
     _write_outputs(pred_wav, logdir)
+    if score:
+        _score_outputs(pred, gt_wav, melspec, info.get('files'), logdir, device)
     print('Done.')
     return pred_wav
 
@@ -492,8 +573,8 @@ def _write_outputs_varlen(pred_wavs, logdir):
         print('could not write outputs to %s: %s' % (logdir, e))
 
 
-def _generate_over_ranks(store, batch_size, length, device, logdir, ckpt, debug):
-    """generate() under a launcher (WORLD_SIZE > 1): see forward_over_ranks."""
+def _generate_over_ranks(store, batch_size, length, device, logdir, ckpt, debug, score=False):
+    """generate() under a launcher (WORLD_SIZE > 1): see forward_over_ranks.  --score: rank 0 scores the gathered result."""
     import torch.distributed as dist
     from . import engine
     from .timeshard import chain_halo
@@ -502,7 +583,8 @@ def _generate_over_ranks(store, batch_size, length, device, logdir, ckpt, debug)
         dist.init_process_group(backend='nccl', device_id=device)      # 'nccl' IS RCCL on ROCm (xGMI)
     rank = dist.get_rank()
     hop, n_mels = hp.signal.hop_length, hp.signal.n_mels
-    melspec = _load_mels(hp.data_path, batch_size, length, device)[1] if rank == 0 else None
+    info = {}
+    gt_wav, melspec = _load_mels(hp.data_path, batch_size, length, device, info) if rank == 0 else (None, None)
     ckpt = '{}/{}'.format(logdir, ckpt) if ckpt else (_latest_checkpoint(logdir) if os.path.isdir(logdir) else None)
     if ckpt:
         store.load_checkpoint(ckpt, use_ema=bool(hp.train.use_ema))
@@ -564,6 +646,8 @@ def _generate_over_ranks(store, batch_size, length, device, logdir, ckpt, debug)
         return None
     pred_wav = pred.cpu().numpy()
     _write_outputs(pred_wav, logdir)
+    if score:
+        _score_outputs(pred, gt_wav, melspec, info.get('files'), logdir, device)
     print('Done.')
     return pred_wav
 
