@@ -18,7 +18,7 @@ _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 _REPO_ROOT = os.path.dirname(_PKG_DIR)
 LIB_PATH = os.environ.get('PWV_LIB') or os.path.join(_PKG_DIR, 'libpwv_hip.so')   # PWV_LIB: A/B another build
 CSRC = [os.path.join(_PKG_DIR, 'csrc', f) for f in ('pwv_layer.hip', 'pwv_layer_f16.hip', 'pwv_layer_h16.hip', 'pwv_misc.hip',
-                                                    'pwv_stack_persist.hip', 'pwv_norm.hip', 'pwv_audio.hip', 'pwv_stream_tick.hip', 'pwv_score.hip')]
+                                                    'pwv_stack_persist.hip', 'pwv_norm.hip', 'pwv_audio.hip', 'pwv_stream_tick.hip', 'pwv_score.hip', 'pwv_train.hip')]
 
 HEADER_VERSION = 301          # PWV_HIP_VERSION of include/pwv_hip.h these ctypes mirrors were written against
 FIRST_FOLD_FLOATS = 2048      # PWV_FIRST_FOLD_FLOATS
@@ -50,6 +50,9 @@ EXTENSION_SYMBOLS = ('pwv_wav_to_mel_db_stream_f32',)
 LIVE_TICK_SYMBOLS = ('pwv_live_tick_mel', 'pwv_live_tick_commit')
 # ... and of include/pwv_hip_score.h: the L1 and the STFT power loss of generated audio
 SCORE_SYMBOLS = ('pwv_score_workspace_bytes', 'pwv_score_f32')
+# ... and of include/pwv_hip_train.h: the forward with saved activations and the backward pass
+TRAIN_SYMBOLS = ('pwv_train_workspace_bytes', 'pwv_train_front_fwd_f32', 'pwv_train_layer_fwd_f32', 'pwv_train_head_fwd_f32',
+                 'pwv_train_head_bwd_f32', 'pwv_train_layer_bwd_f32', 'pwv_train_front_bwd_f32')
 
 
 class PwvError(RuntimeError):
@@ -349,6 +352,26 @@ class ScoreArgs(Structure):
         self.struct_size = ctypes.sizeof(ScoreArgs)
 
 
+TRAIN_RESIDUAL, TRAIN_LAST = 0, 1      # PWV_TRAIN_RESIDUAL, PWV_TRAIN_LAST
+
+
+class TrainArgs(Structure):
+    """pwv_train_args: one training kernel call on one net (include/pwv_hip_train.h)."""
+    _fields_ = ([('struct_size', c_size_t)]      # set by __init__
+                + [(n, ctypes.c_int32) for n in ('N', 'T', 'form', 'dilation', 'next_dilation', 'cond_hop', 'cond_offset', 'cond_frames',
+                                                 'proj_row_stride', 'd_proj_row_stride', 'max_workgroups', 'accumulate')]
+                + [(n, c_void_p) for n in ('in_', 'x', 'x_out', 'proj', 'y', 'causal_filter', 'filter', 'gate', 'dense', 'dense_bias',
+                                           'skip', 'skip_bias', 'post1', 'post1_bias', 'post2', 'post2_bias',
+                                           'd_out', 'd_mul', 'scale', 'u_next', 'v_next', 'd_o',
+                                           'u', 'v', 'd_o_out', 'd_in', 'd_proj', 'd_causal_filter', 'd_filter', 'd_gate', 'd_dense', 'd_dense_bias',
+                                           'd_skip', 'd_skip_bias', 'd_post1', 'd_post1_bias', 'd_post2', 'd_post2_bias', 'workspace')]
+                + [('workspace_bytes', c_size_t)])
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = ctypes.sizeof(TrainArgs)
+
+
 # per-source extra flags (none in the product; tools/probes/regw/README.md: the register-stationary probe kernel needs
 # `-mllvm -amdgpu-mfma-vgpr-form=1`, which is why the sources are compiled one by one)
 EXTRA_FLAGS = {}
@@ -500,6 +523,10 @@ def _declare(lib):
     lib.pwv_score_workspace_bytes.restype = c_size_t
     lib.pwv_score_workspace_bytes.argtypes = [POINTER(ScoreArgs)]
     lib.pwv_score_f32.argtypes = [POINTER(ScoreArgs), c_void_p]
+    lib.pwv_train_workspace_bytes.restype = c_size_t
+    lib.pwv_train_workspace_bytes.argtypes = [POINTER(TrainArgs)]
+    for name in TRAIN_SYMBOLS[1:]:
+        getattr(lib, name).argtypes = [POINTER(TrainArgs), c_void_p]
     lib.pwv_instance_norm_workspace_bytes.restype = c_size_t
     lib.pwv_instance_norm_workspace_bytes.argtypes = [c_int, c_int, c_int]
     lib.pwv_instance_norm_f32.argtypes = [f32p, f32p, c_int, c_int, c_int, f32p, f32p, ctypes.c_float, c_void_p, c_size_t, c_void_p]
@@ -521,7 +548,7 @@ def _declare(lib):
     lib.pwv_status_words_alloc.argtypes = [POINTER(c_void_p)]
     lib.pwv_status_words_free.argtypes = [c_void_p]
     lib.pwv_range_check_f32.argtypes = [f32p, c_int64, ctypes.c_float, c_void_p, c_void_p]
-    for name in EXPORTED_SYMBOLS + EXTENSION_SYMBOLS + LIVE_TICK_SYMBOLS + SCORE_SYMBOLS:      # fails loudly (AttributeError) if a symbol is missing
+    for name in EXPORTED_SYMBOLS + EXTENSION_SYMBOLS + LIVE_TICK_SYMBOLS + SCORE_SYMBOLS + TRAIN_SYMBOLS:      # fails loudly (AttributeError) if a symbol is missing
         getattr(lib, name)
     return lib
 

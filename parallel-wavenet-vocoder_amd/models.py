@@ -1,9 +1,10 @@
-"""IAFVocoder: the 4-flow IAF-WaveNet student, generation (forward) path only.
+"""IAFVocoder: the 4-flow IAF-WaveNet student, the generation (forward) path.
 
 Counterpart of /root/reference/models.py:16-141 with the same constructor / call signature
 (`IAFVocoder(batch_size, length)`, `model(wav, melspec, is_training, name='iaf_vocoder')`,
 `_upsample_cond(melspec, is_training, strides)`), reading the same global `hparam`.
-Training hooks (tensorpack ModelDesc, losses, optimizer: models.py:80-103) are out of scope.
+The training side of models.py:80-103 (the L1 loss, its gradients, Adam and the EMA) is pwv_amd/train.py; tensorpack's ModelDesc is
+not mirrored.
 """
 from __future__ import annotations
 

@@ -1,0 +1,478 @@
+"""Training of the IAF-WaveNet student on one GPU: the L1 loss (models.py:90-99 at weight_power_loss 0), its gradient for every
+variable (pwv_train_* kernels, include/pwv_hip_train.h), TensorFlow's Adam and the reference's EMA (models.py:72-76, :101-103), and
+the loop of train.py:25-71.  DESIGN.md section 9, "Training".
+
+    python -m pwv_amd.train CASE [--ckpt=NAME] [--steps=N] [--seed=S]
+
+Scope: what hparams/default.yaml trains -- filter_width 2, R = D = 64, S = 128, 'repeat' conditioning, no normalisers, no skip
+accumulation, separate scaler and shifter nets, uniform [N, T] batches, exact-fp32 arithmetic.  Everything else is refused with a
+PwvError that names the reason (`refusal`); nothing falls back to another implementation.
+
+Division of work.  Sample rate (the hot path): HIP kernels, one net per call -- the forward keeps every layer's input and the last
+layer's gated output, the backward recomputes F, G, o and the head's hidden layers from them.  Frame rate (plumbing, in torch): the
+conditioning dense + ReLU, the projections P = frames [gc_filter | gc_gate] + [filter_bias | gate_bias] of all net-layers as ONE matrix
+product, and their backward from the dP the kernels leave; the flow's affine out = in * s + b and the loss.
+"""
+from __future__ import annotations
+
+import ctypes
+import glob
+import math
+import os
+import sys
+from typing import Dict, List, Optional
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import PwvError
+from .hparam import hparam as hp
+from .variables import EMA_SUFFIX, get_default_store, variable_scope
+
+SCOPE = 'iaf_vocoder'
+ADAM_BETA1 = 0.9            # tf.train.AdamOptimizer's defaults (models.py:101-103 sets the learning rate and beta2 only)
+ADAM_EPS = 1e-8
+
+
+# ---- what is refused ----------------------------------------------------------------------------------------------------------------
+def refusal(model=None, wav=None, melspec=None) -> Optional[str]:
+    """Why the current hparams / this model / these inputs cannot be trained here, or None.  Looks at structure only: no GPU."""
+    m = hp.model
+    if m.cond_upsample_method != 'repeat':
+        return "cond_upsample_method %r: only 'repeat' conditioning is differentiated (transposed-conv conditioning is not)" % m.cond_upsample_method
+    if m.get('normalize_cond'):
+        return 'normalize_cond %r: normalised conditioning is not differentiated' % m.normalize_cond
+    if m.get('normalize_wavenet'):
+        return "normalize_wavenet %r: the 'bn' / 'in' normalisers are not differentiated" % m.normalize_wavenet
+    if m.get('normalize'):
+        return "normalize %r: the 'bn' / 'in' normalisers are not differentiated" % m.normalize
+    if m.use_skip_connection:
+        return 'use_skip_connection True: skip accumulation over all layers is not differentiated'
+    if m.get('shared_nets'):
+        return 'shared_nets True: one shared net per flow is not differentiated (separate scaler and shifter nets only)'
+    shape = (m.filter_width, m.residual_channels, m.dilation_channels, m.skip_channels)
+    if shape != (2, 64, 64, 128):
+        return 'filter_width, residual, dilation, skip channels = %s: outside the fused shape (2, 64, 64, 128)' % (shape,)
+    if len(m.dilations) != m.n_iaf or any(len(d) < 1 or min(d) < 1 for d in m.dilations):
+        return 'dilations %r do not give n_iaf = %d flows of at least one layer' % (m.dilations, m.n_iaf)
+    if float(hp.train.get('weight_power_loss', 0) or 0) > 0:
+        return 'train.weight_power_loss %g > 0: the gradient of the STFT power loss is not built' % float(hp.train.weight_power_loss)
+    prec = getattr(model, 'precision', None)
+    if prec not in (None, 'f32'):
+        return "precision %r: training runs in exact fp32 ('f16x3' / 'f16' are not differentiated)" % prec
+    for what, t in (('wav', wav), ('melspec', melspec)):
+        if isinstance(t, (list, tuple)):
+            return 'packed inputs: %s is a list of utterances (uniform [N, T] batches only)' % what
+        if t is not None and (hasattr(t, 'push') or hasattr(t, 'cu_rows')):
+            return 'streaming inputs: %s is a stream (uniform [N, T] batches only)' % what
+    if melspec is not None and getattr(melspec, 'dim', lambda: 3)() != 3:
+        return 'packed inputs: melspec must be [N, t_mel, n_mels], got %s' % (tuple(melspec.shape),)
+    return None
+
+
+# ---- the variables ------------------------------------------------------------------------------------------------------------------
+class _Net(object):
+    """One WaveNet of the model: its variables by role, its dilations, its first column in the projection bank."""
+
+    def __init__(self, net, col):
+        self.scope, self.dilations, self.col = net.full_scope, list(net.dilations), col
+        self.cf = net.causal_filter()
+        self.layers = [net.layer_variables(j, with_cond=True) for j in range(len(self.dilations))]
+        self.head = net.head_variables()
+
+    def name(self, j, role):
+        return '%s/dilated_stack/layer%d/%s' % (self.scope, j, role)
+
+
+def model_nets(model, store) -> List[List[_Net]]:
+    """[[scaler, shifter] per flow]; creates (glorot / zeros, like tf.get_variable) every variable the store lacks."""
+    with variable_scope(SCOPE, absolute=True):
+        flows = model._flows(store, True, 'f32')
+    out, col = [], 0
+    for iaf in flows:
+        pair = []
+        for net in iaf.nets():
+            pair.append(_Net(net, col))
+            col += 128 * len(net.dilations)
+        out.append(pair)
+    return out
+
+
+def cond_dense(store):
+    return store.get_variable(SCOPE + '/cond/dense', [1, hp.signal.n_mels, hp.model.condition_channels])
+
+
+def trainable_names(store) -> List[str]:
+    return sorted(store.trainable_variables(SCOPE))
+
+
+# ---- the kernels --------------------------------------------------------------------------------------------------------------------
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _call(name, args):
+    from . import engine
+    _lib.check(getattr(_lib.lib(), name)(ctypes.byref(args), engine._stream()), name)
+
+
+def _tile32(rows, device):
+    return torch.empty(((rows + 31) // 32) * 32 * 64, dtype=torch.float32, device=device)
+
+
+class _Geometry(object):
+    def __init__(self, N, T, t_mel, cols, max_workgroups):
+        self.N, self.T, self.rows, self.frames, self.cols = N, T, N * T, t_mel, cols
+        self.hop, self.off = hp.signal.hop_length, hp.signal.hop_length // 2
+        self.kmax = (self.hop + 30) // 32 + 1
+        self.max_workgroups = max_workgroups
+
+    def args(self, **kw):
+        a = _lib.TrainArgs(N=self.N, T=self.T, cond_hop=self.hop, cond_offset=self.off, cond_frames=self.frames, proj_row_stride=self.cols,
+                           d_proj_row_stride=self.cols, max_workgroups=self.max_workgroups, dilation=1, next_dilation=1)
+        for k, v in kw.items():
+            setattr(a, k, _ptr(v) if isinstance(v, torch.Tensor) else v)
+        return a
+
+
+def _net_forward(net: _Net, geo: _Geometry, xin, P):
+    """x_j for every layer, the last layer's o and the net's output y [rows]."""
+    dev, L = xin.device, len(net.dilations)
+    xs = [_tile32(geo.rows, dev) for _ in range(L)]
+    o, y = _tile32(geo.rows, dev), torch.empty(geo.rows, dtype=torch.float32, device=dev)
+    _call('pwv_train_front_fwd_f32', geo.args(in_=xin, causal_filter=net.cf, x_out=xs[0]))
+    for j, d in enumerate(net.dilations):
+        v, last = net.layers[j], j == L - 1
+        _call('pwv_train_layer_fwd_f32', geo.args(form=_lib.TRAIN_LAST if last else _lib.TRAIN_RESIDUAL, dilation=d, x=xs[j],
+                                                 proj=P[0, net.col + 128 * j:], filter=v['filter'], gate=v['gate'], dense=v['dense'],
+                                                 dense_bias=v.get('dense_bias'), x_out=o if last else xs[j + 1]))
+    h, lv = net.head, net.layers[-1]
+    _call('pwv_train_head_fwd_f32', geo.args(x=o, skip=lv['skip'], skip_bias=lv.get('skip_bias'), post1=h['postprocess1'],
+                                            post1_bias=h.get('postprocess1_bias'), post2=h['postprocess2'],
+                                            post2_bias=h.get('postprocess2_bias'), y=y))
+    return xs, o, y
+
+
+def _net_backward(net: _Net, geo: _Geometry, saved, xin, d_out, d_mul, scale, d_in, accumulate, dP, ws, grads):
+    """The net's share of the gradients into `grads`, of dP and of d_in."""
+    xs, o, _ = saved
+    dev, L = xin.device, len(net.dilations)
+    g = lambda name, like: grads.setdefault(name, torch.empty_like(like))
+    h, lv = net.head, net.layers[-1]
+    hp_ = net.scope + '/postprocessing/'
+    opt = lambda d, key, name: g(name, d[key]) if key in d else None
+    d_o = _tile32(geo.rows, dev)
+    _call('pwv_train_head_bwd_f32', geo.args(
+        x=o, d_out=d_out, d_mul=d_mul, skip=lv['skip'], skip_bias=lv.get('skip_bias'), post1=h['postprocess1'],
+        post1_bias=h.get('postprocess1_bias'), post2=h['postprocess2'], post2_bias=h.get('postprocess2_bias'), d_o_out=d_o,
+        d_skip=g(net.name(L - 1, 'skip'), lv['skip']), d_skip_bias=opt(lv, 'skip_bias', net.name(L - 1, 'skip_bias')),
+        d_post1=g(hp_ + 'postprocess1', h['postprocess1']), d_post1_bias=opt(h, 'postprocess1_bias', hp_ + 'postprocess1_bias'),
+        d_post2=g(hp_ + 'postprocess2', h['postprocess2']), d_post2_bias=opt(h, 'postprocess2_bias', hp_ + 'postprocess2_bias'),
+        workspace=ws, workspace_bytes=ws.numel() * 4))
+    uv = [(_tile32(geo.rows, dev), _tile32(geo.rows, dev)) for _ in range(2)]
+    for j in range(L - 1, -1, -1):
+        v, last = net.layers[j], j == L - 1
+        u_next, v_next = (None, None) if last else uv[(j + 1) & 1]
+        _call('pwv_train_layer_bwd_f32', geo.args(
+            form=_lib.TRAIN_LAST if last else _lib.TRAIN_RESIDUAL, dilation=net.dilations[j],
+            next_dilation=1 if last else net.dilations[j + 1], x=xs[j], proj=geo.P[0, net.col + 128 * j:],
+            filter=v['filter'], gate=v['gate'], dense=v['dense'], u_next=u_next, v_next=v_next, d_o=d_o if last else None,
+            u=uv[j & 1][0], v=uv[j & 1][1], d_proj=dP[0, net.col + 128 * j:],
+            d_filter=g(net.name(j, 'filter'), v['filter']), d_gate=g(net.name(j, 'gate'), v['gate']),
+            d_dense=None if last else g(net.name(j, 'dense'), v['dense']),
+            d_dense_bias=None if last else opt(v, 'dense_bias', net.name(j, 'dense_bias')),
+            workspace=ws, workspace_bytes=ws.numel() * 4))
+    _call('pwv_train_front_bwd_f32', geo.args(
+        in_=xin, causal_filter=net.cf, u_next=uv[0][0], v_next=uv[0][1], next_dilation=net.dilations[0], d_out=d_out, scale=scale,
+        d_in=d_in, accumulate=int(accumulate), d_causal_filter=g(net.scope + '/causal_layer/filter', net.cf),
+        workspace=ws, workspace_bytes=ws.numel() * 4))
+
+
+def loss_and_grad(model, wav, melspec, z=None, seed=None, max_workgroups: int = 0):
+    """(loss, pred, grads) of one batch: `loss` the L1 mean |pred - wav| as a device scalar (models.py:93 `loss/likelihood`), `pred`
+    [N, T, 1] the model's output, `grads` {name: device tensor of the variable's shape} for EVERY trainable variable of the store under
+    'iaf_vocoder' -- exact zeros for the ones the model never reads (skip / skip_bias of every layer but the last, dense / dense_bias of
+    the last).  wav [N, T] or [N, T, 1], melspec [N, 1 + T / hop, n_mels], both on the GPU; z [N, T, 1] replaces the logistic noise the
+    forward draws (`seed`: as IAFVocoder.sample_noise).  Only enqueues; `max_workgroups` (0: two per compute unit) sets the number of
+    partials of every weight-gradient reduction."""
+    from . import engine
+    why = refusal(model, wav, melspec)
+    if why:
+        raise PwvError('training refused: ' + why)
+    store = model.store or get_default_store()
+    melspec = engine._require_cuda_f32(melspec, 'melspec')
+    wav = engine._require_cuda_f32(wav, 'wav')
+    N, t_mel, n_mels = melspec.shape
+    T, hop = model.length, hp.signal.hop_length
+    if n_mels != hp.signal.n_mels or T % hop or hop % 2 or t_mel != 1 + T // hop:
+        raise ValueError('melspec must be [N, 1 + %d / %d, %d] with an even hop that divides the length, got %s' % (T, hop, hp.signal.n_mels, tuple(melspec.shape)))
+    if wav.numel() != N * T:
+        raise ValueError('wav must be [%d, %d] or [%d, %d, 1], got %s' % (N, T, N, T, tuple(wav.shape)))
+    dev = melspec.device
+    if z is None:
+        noise = model.sample_noise(N, dev, seed=seed)
+    else:
+        noise = engine._require_cuda_f32(z, 'z')
+        if noise.numel() != N * T:
+            raise ValueError('z must be [%d, %d, 1], got %s' % (N, T, tuple(noise.shape)))
+    flows = model_nets(model, store)
+    dense = cond_dense(store)
+    nets = [net for pair in flows for net in pair]
+    cols = sum(128 * len(net.dilations) for net in nets)
+    geo = _Geometry(N, T, t_mel, cols, int(max_workgroups))
+
+    # frame rate, forward: frames = relu(mel dense); P = frames [gc_filter | gc_gate] + [filter_bias | gate_bias] for every net-layer
+    zeros64 = torch.zeros(64, dtype=torch.float32, device=dev)
+    mel2 = melspec.reshape(N * t_mel, n_mels)
+    pre = mel2 @ dense[0]
+    frames = torch.relu(pre)
+    bank_w = torch.cat([v[k][0] for net in nets for v in net.layers for k in ('gc_filter', 'gc_gate')], dim=1)          # [C, cols]
+    bank_b = torch.cat([v.get(k, zeros64) for net in nets for v in net.layers for k in ('filter_bias', 'gate_bias')])
+    geo.P = (frames @ bank_w + bank_b).contiguous()                                                                    # [M, cols]
+
+    # sample rate, forward
+    ws_bytes = _lib.lib().pwv_train_workspace_bytes(ctypes.byref(geo.args()))
+    if not ws_bytes:
+        _lib.check(-1, 'pwv_train_workspace_bytes')
+    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=dev)
+    x = noise.reshape(N * T).contiguous()
+    saved = []
+    for pair in flows:
+        s = [_net_forward(net, geo, x, geo.P) for net in pair]
+        saved.append((x, s))
+        x = x * s[0][2] + s[1][2]                                                       # modules.py:59
+    y = wav.reshape(N * T)
+    diff = x - y
+    loss = diff.abs().mean()
+    d_out = torch.sign(diff) / float(N * T)
+
+    # sample rate, backward
+    grads: Dict[str, torch.Tensor] = {}
+    dP = torch.zeros((N * t_mel * geo.kmax, cols), dtype=torch.float32, device=dev)       # K slots per P row (include/pwv_hip_train.h)
+    for i in range(len(flows) - 1, -1, -1):
+        xin, s = saved[i]
+        d_in = torch.empty_like(xin) if i > 0 else None
+        _net_backward(flows[i][0], geo, s[0], xin, d_out, xin, s[0][2], d_in, False, dP, ws, grads)      # ds = d out * in
+        _net_backward(flows[i][1], geo, s[1], xin, d_out, None, None, d_in, True, dP, ws, grads)         # db = d out
+        d_out = d_in
+
+    # frame rate, backward
+    dPs = dP.reshape(N * t_mel, geo.kmax, cols).sum(dim=1)
+    d_bank_w = frames.t() @ dPs                                                                                          # [C, cols]
+    d_bank_b = dPs.sum(dim=0)
+    d_pre = (dPs @ bank_w.t()) * (pre > 0).to(torch.float32)
+    grads[SCOPE + '/cond/dense'] = (mel2.t() @ d_pre).unsqueeze(0)
+    C = bank_w.shape[0]
+    gw = d_bank_w.reshape(C, cols // 64, 64).permute(1, 0, 2).contiguous()                                               # [2 per net-layer, C, 64]
+    gb = d_bank_b.reshape(cols // 64, 64)
+    i = 0
+    for net in nets:
+        for j, v in enumerate(net.layers):
+            grads[net.name(j, 'gc_filter')], grads[net.name(j, 'gc_gate')] = gw[i:i + 1], gw[i + 1:i + 2]
+            if 'filter_bias' in v:
+                grads[net.name(j, 'filter_bias')], grads[net.name(j, 'gate_bias')] = gb[i], gb[i + 1]
+            i += 2
+    for name in trainable_names(store):                 # what the model never reads
+        if name not in grads:
+            grads[name] = torch.zeros_like(store.vars[name])
+    return loss, x.reshape(N, T, 1), grads
+
+
+# ---- the optimiser ------------------------------------------------------------------------------------------------------------------
+def adam_ema_update(vars, grads, state, lr, beta1=ADAM_BETA1, beta2=0.999, eps=ADAM_EPS, ema_decay=None):
+    """One step of tf.train.AdamOptimizer on the tensors `vars` (updated in place) with `grads`, then the reference's EMA
+    (models.py:72-76) of the UPDATED variables.  `state` is None at the first step, else what the last step returned:
+    {'t', 'm', 'v', 'shadow'} (lists parallel to `vars`; the shadows start at the initial values; 'shadow' is None without ema_decay).
+        lr_t = lr sqrt(1 - beta2^t) / (1 - beta1^t);  m <- beta1 m + (1 - beta1) g;  v <- beta2 v + (1 - beta2) g^2
+        var <- var - lr_t m / (sqrt(v) + eps)                 (TensorFlow's epsilon placement, not torch's)
+        shadow <- shadow - (1 - decay) (shadow - var)
+    Tensors of any device and float dtype; torch._foreach ops only, no per-variable arithmetic."""
+    vars, grads = list(vars), list(grads)
+    if state is None:
+        state = {'t': 0, 'm': [torch.zeros_like(v) for v in vars], 'v': [torch.zeros_like(v) for v in vars],
+                 'shadow': [v.clone() for v in vars] if ema_decay is not None else None}
+    state['t'] += 1
+    t = state['t']
+    lr_t = float(lr) * math.sqrt(1.0 - beta2 ** t) / (1.0 - beta1 ** t)
+    m, v = state['m'], state['v']
+    torch._foreach_mul_(m, beta1)
+    torch._foreach_add_(m, grads, alpha=1.0 - beta1)
+    torch._foreach_mul_(v, beta2)
+    torch._foreach_addcmul_(v, grads, grads, value=1.0 - beta2)
+    denom = torch._foreach_sqrt(v)
+    torch._foreach_add_(denom, eps)
+    torch._foreach_addcdiv_(vars, m, denom, value=-lr_t)
+    if ema_decay is not None:
+        if state.get('shadow') is None:
+            state['shadow'] = [x.clone() for x in vars]
+        gap = torch._foreach_sub(state['shadow'], vars)
+        torch._foreach_add_(state['shadow'], gap, alpha=-(1.0 - float(ema_decay)))
+    return state
+
+
+_UNSET = object()
+
+
+class Trainer(object):
+    """The reference's training step (models.py:80-103) on one model: loss_and_grad, then adam_ema_update on the store's variables in
+    place.  Defaults from hparams: lr = train.lr, beta2 = train.adam_beta2, ema_decay = train.ema_decay if train.use_ema."""
+
+    def __init__(self, model, lr=None, beta2=None, ema_decay=_UNSET, max_workgroups: int = 0):
+        self.model = model
+        self.store = model.store or get_default_store()
+        self.lr = float(hp.train.lr if lr is None else lr)
+        self.beta1, self.beta2 = ADAM_BETA1, float(hp.train.adam_beta2 if beta2 is None else beta2)
+        if ema_decay is _UNSET:
+            ema_decay = hp.train.ema_decay if hp.train.use_ema else None
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.max_workgroups = max_workgroups
+        self.names: Optional[List[str]] = None
+        self.state = None
+
+    def _bind(self):
+        """Every variable of the model exists from here on; the optimiser's lists follow the sorted names."""
+        why = refusal(self.model)
+        if why:
+            raise PwvError('training refused: ' + why)
+        if self.names is None:
+            model_nets(self.model, self.store)
+            cond_dense(self.store)
+            self.names = trainable_names(self.store)
+        return [self.store.vars[n] for n in self.names]
+
+    def step(self, wav, mel, z=None):
+        """One step on one batch; returns the loss BEFORE the update (a device scalar)."""
+        vars = self._bind()
+        loss, _, grads = loss_and_grad(self.model, wav, mel, z=z, max_workgroups=self.max_workgroups)
+        self.state = adam_ema_update(vars, [grads[n] for n in self.names], self.state, self.lr, self.beta1, self.beta2, ADAM_EPS, self.ema_decay)
+        self.store.touch()
+        return loss
+
+    @property
+    def steps(self) -> int:
+        return 0 if self.state is None else self.state['t']
+
+    def shadows(self) -> Dict[str, torch.Tensor]:
+        return {} if self.state is None or self.state['shadow'] is None else dict(zip(self.names, self.state['shadow']))
+
+    def save(self, path: str) -> None:
+        """An .npz under TensorFlow's names: the variables, <name>/ExponentialMovingAverage, <name>/Adam (m), <name>/Adam_1 (v),
+        beta1_power and beta2_power (beta^(t + 1), as AdamOptimizer keeps them after t steps)."""
+        vars = self._bind()
+        out = {n: v.detach().cpu().numpy() for n, v in zip(self.names, vars)}
+        t = self.steps
+        if self.state is not None:
+            for n, m, v in zip(self.names, self.state['m'], self.state['v']):
+                out[n + '/Adam'], out[n + '/Adam_1'] = m.cpu().numpy(), v.cpu().numpy()
+        if self.ema_decay is not None:
+            shadows = self.shadows()
+            for n, v in zip(self.names, vars):           # (before the first step a shadow is the variable itself)
+                out[n + EMA_SUFFIX] = shadows.get(n, v).detach().cpu().numpy()
+        out['beta1_power'] = np.float64(self.beta1 ** (t + 1))
+        out['beta2_power'] = np.float64(self.beta2 ** (t + 1))
+        out['global_step'] = np.int64(t)
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, 'wb') as f:
+            np.savez(f, **out)
+
+    def load(self, path: str) -> int:
+        """Resume from a file `save` wrote; returns the step count."""
+        vars = self._bind()
+        with np.load(path) as zf:
+            data = {k: zf[k] for k in zf.files}
+        dev = self.store.device
+        put = lambda a, like: torch.as_tensor(np.asarray(a), dtype=like.dtype).reshape(like.shape).to(like.device)
+        for n, v in zip(self.names, vars):
+            if n not in data:
+                raise KeyError('%s has no variable %s' % (path, n))
+            v.copy_(put(data[n], v))
+        t = int(data['global_step']) if 'global_step' in data else int(round(math.log(float(data['beta1_power'])) / math.log(self.beta1))) - 1
+        if t > 0:
+            self.state = {'t': t, 'm': [put(data[n + '/Adam'], v) for n, v in zip(self.names, vars)],
+                          'v': [put(data[n + '/Adam_1'], v) for n, v in zip(self.names, vars)],
+                          'shadow': [put(data.get(n + EMA_SUFFIX, data[n]), v) for n, v in zip(self.names, vars)] if self.ema_decay is not None else None}
+        else:
+            self.state = None
+        self.store.touch()
+        return t
+
+
+# ---- train.py:25-71 on one GPU ------------------------------------------------------------------------------------------------------
+def _synthetic_wavs(n_items: int, length: int, seed: int) -> np.ndarray:
+    """Seeded stand-ins for a wav dataset: a few decaying harmonics over noise, |x| < 1."""
+    rng = np.random.RandomState(seed)
+    t = np.arange(length) / float(hp.signal.sr)
+    out = np.zeros((n_items, length), dtype=np.float32)
+    for i in range(n_items):
+        f0 = rng.uniform(90, 300)
+        x = sum(rng.uniform(0.05, 0.3) / k * np.sin(2 * np.pi * f0 * k * t + rng.uniform(0, 6.28)) for k in range(1, 6))
+        out[i] = (x + 0.02 * rng.randn(length)).astype(np.float32)
+    return np.clip(out, -0.99, 0.99)
+
+
+def _dataset(length: int, seed: int) -> List[np.ndarray]:
+    """The training split (data_load.py:22-25: the first dataset_ratio share of the files) as trimmed wavs of at least `length` samples."""
+    if hp.data_path == 'synthetic':
+        return list(_synthetic_wavs(8, 4 * length, seed))
+    from .audio_frontend import fix_length, read_wav, trim_wav
+    files = sorted(glob.glob(hp.data_path))
+    if not files:
+        raise FileNotFoundError('no input files match data_path %r (use data_path: synthetic for seeded stand-ins)' % hp.data_path)
+    files = files[:max(int(len(files) * hp.train.dataset_ratio), 1)]
+    wavs = [trim_wav(read_wav(f, hp.signal.sr)).astype(np.float32) for f in files]
+    return [fix_length(w, length) if len(w) < length else w for w in wavs]
+
+
+def train(case='default', ckpt=None, steps=None, seed=0):
+    """train.py:25-71 on one GPU: per step a seeded random crop of hp.signal.length samples per item (data_load.py:46-50), its mel from
+    the device front-end, one Trainer.step; prints loss/likelihood per step; saves into hp.logdir (PWV_LOGDIR overrides) every
+    train.save_per_epoch * train.steps_per_epoch steps and at the end.  `ckpt` names a file in the log directory to resume from (default:
+    the newest .npz there)."""
+    from .audio_frontend import wav_to_mel_device
+    from .models import IAFVocoder
+    from .variables import reset_default_store
+    hp.set_hparam_yaml(case)
+    why = refusal()
+    if why:
+        raise PwvError('training refused: ' + why)
+    if not torch.cuda.is_available():
+        raise RuntimeError('train() needs an MI355X: the HIP path has no CPU fallback')
+    device = torch.device('cuda', torch.cuda.current_device())
+    logdir = os.environ.get('PWV_LOGDIR', hp.logdir)
+    seed = int(seed)
+    length, batch = int(hp.signal.length), int(hp.train.batch_size)
+    steps = int(steps) if steps is not None else int(hp.train.num_epochs) * int(hp.train.steps_per_epoch)
+    store = reset_default_store(device=device)
+    model = IAFVocoder(batch_size=batch, length=length, store=store, precision='f32')
+    model.noise_seed = seed
+    trainer = Trainer(model)
+    path = os.path.join(logdir, ckpt) if ckpt else (sorted(glob.glob(os.path.join(logdir, '*.npz')), key=os.path.getmtime) or [None])[-1]
+    if path and os.path.exists(path):
+        print('resumed from %s at step %d' % (path, trainer.load(path)))
+    wavs = _dataset(length, seed)
+    rng = np.random.RandomState(seed + trainer.steps)
+    every = max(int(hp.train.save_per_epoch) * int(hp.train.steps_per_epoch), 1)
+    saved_at = None
+    for _ in range(steps):
+        crop = np.empty((batch, length), dtype=np.float32)
+        for b in range(batch):
+            w = wavs[rng.randint(len(wavs))]
+            at = rng.randint(len(w) - length + 1)
+            crop[b] = w[at:at + length]
+        wav = torch.from_numpy(crop).to(device)
+        loss = trainer.step(wav, wav_to_mel_device(wav))
+        print('step %d loss/likelihood %.6f' % (trainer.steps, float(loss)))
+        if trainer.steps % every == 0:
+            saved_at = os.path.join(logdir, 'model-%d.npz' % trainer.steps)
+            trainer.save(saved_at)
+    final = os.path.join(logdir, 'model-%d.npz' % trainer.steps)
+    if saved_at != final:
+        trainer.save(final)
+    print('saved %s' % final)
+    return final
+
+
+if __name__ == '__main__':
+    from .generate import _fire
+    _fire(train, sys.argv[1:])

@@ -117,9 +117,16 @@ class VariableStore:
         to its shadow name (generate.py:59-63) and fails on a missing key; callers that mirror it treat this list as an error."""
         return sorted(k for k in self.vars if k in self.restored_without_shadow and k.startswith(scope) and is_trainable(k))
 
+    def touch(self) -> None:
+        """The variables were changed IN PLACE (a training step): everything keyed on `version`, the packed-weight caches first, is stale."""
+        self.version += 1
+
     def load_npz(self, path: str, use_ema: bool = False) -> int:
+        """A checkpoint written by train.Trainer.save also holds the optimiser's state under TensorFlow's names (<name>/Adam,
+        <name>/Adam_1, beta1_power, beta2_power, global_step): like the TF path below, generation does not read it."""
+        slot = lambda k: k.endswith('/Adam') or k.endswith('/Adam_1') or k in ('beta1_power', 'beta2_power', 'global_step')
         with np.load(path) as z:
-            return self.load_dict({k: z[k] for k in z.files}, use_ema=use_ema)
+            return self.load_dict({k: z[k] for k in z.files if not slot(k)}, use_ema=use_ema)
 
     def load_checkpoint(self, path: str, use_ema: bool = False) -> int:
         """`path` is an .npz of TF-named arrays or a TensorFlow V2 checkpoint prefix (<path>.index +
