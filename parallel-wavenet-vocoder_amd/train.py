@@ -1,6 +1,7 @@
-"""Training of the IAF-WaveNet student on one GPU: the L1 loss (models.py:90-99 at weight_power_loss 0), its gradient for every
-variable (pwv_train_* kernels, include/pwv_hip_train.h), TensorFlow's Adam and the reference's EMA (models.py:72-76, :101-103), and
-the loop of train.py:25-71.  DESIGN.md section 9, "Training".
+"""Training of the IAF-WaveNet student on one GPU: the reference's loss (models.py:90-99: the L1, and on request weight_power_loss
+times the STFT power loss -- pwv_train_loss_f32, include/pwv_hip_train_loss.h), its gradient for every variable (pwv_train_* kernels,
+include/pwv_hip_train.h), TensorFlow's Adam and the reference's EMA (models.py:72-76, :101-103), and the loop of train.py:25-71.
+DESIGN.md section 9, "Training".
 
     python -m pwv_amd.train CASE [--ckpt=NAME] [--steps=N] [--seed=S]
 
@@ -36,8 +37,10 @@ ADAM_EPS = 1e-8
 
 
 # ---- what is refused ----------------------------------------------------------------------------------------------------------------
-def refusal(model=None, wav=None, melspec=None) -> Optional[str]:
-    """Why the current hparams / this model / these inputs cannot be trained here, or None.  Looks at structure only: no GPU."""
+def refusal(model=None, wav=None, melspec=None, power_weight=None) -> Optional[str]:
+    """Why the current hparams / this model / these inputs cannot be trained here, or None.  Looks at structure only: no GPU.
+    `power_weight`: the weight of the STFT power loss the caller asks for explicitly (loss_and_grad's argument); None = the L1 alone,
+    and then hparams that ask for a power loss are refused instead of being trained without it."""
     m = hp.model
     if m.cond_upsample_method != 'repeat':
         return "cond_upsample_method %r: only 'repeat' conditioning is differentiated (transposed-conv conditioning is not)" % m.cond_upsample_method
@@ -56,8 +59,16 @@ def refusal(model=None, wav=None, melspec=None) -> Optional[str]:
         return 'filter_width, residual, dilation, skip channels = %s: outside the fused shape (2, 64, 64, 128)' % (shape,)
     if len(m.dilations) != m.n_iaf or any(len(d) < 1 or min(d) < 1 for d in m.dilations):
         return 'dilations %r do not give n_iaf = %d flows of at least one layer' % (m.dilations, m.n_iaf)
-    if float(hp.train.get('weight_power_loss', 0) or 0) > 0:
-        return 'train.weight_power_loss %g > 0: the gradient of the STFT power loss is not built' % float(hp.train.weight_power_loss)
+    if power_weight is None and float(hp.train.get('weight_power_loss', 0) or 0) > 0:
+        return ('train.weight_power_loss %g > 0: this call differentiates the L1 alone; the STFT power loss is trained on request '
+                '(loss_and_grad / Trainer: power_weight=...)' % float(hp.train.weight_power_loss))
+    if power_weight is not None:
+        if not (math.isfinite(float(power_weight)) and float(power_weight) >= 0):
+            return 'power_weight %r must be a finite number >= 0' % (power_weight,)
+        length = getattr(model, 'length', None)
+        if float(power_weight) > 0 and length is not None and length < int(hp.signal.win_length):
+            return ('power_weight %g > 0 with length %d shorter than signal.win_length %d: the STFT power loss has no frame'
+                    % (float(power_weight), length, int(hp.signal.win_length)))
     prec = getattr(model, 'precision', None)
     if prec not in (None, 'f32'):
         return "precision %r: training runs in exact fp32 ('f16x3' / 'f16' are not differentiated)" % prec
@@ -189,15 +200,41 @@ def _net_backward(net: _Net, geo: _Geometry, saved, xin, d_out, d_mul, scale, d_
         workspace=ws, workspace_bytes=ws.numel() * 4))
 
 
-def loss_and_grad(model, wav, melspec, z=None, seed=None, max_workgroups: int = 0):
+def _loss_head(pred, y, N, T, w):
+    """The loss head on the device (pwv_train_loss_f32): weight_l1 = 1, weight_power = w, hp.signal.win_length / hop_length.  Returns
+    (d_out [N T] float32, {'likelihood', 'power', 'total'} float32 device scalars); only enqueues."""
+    a = _lib.TrainLossArgs(out=_ptr(pred), y=_ptr(y), n=N, T=T, win_length=int(hp.signal.win_length), hop_length=int(hp.signal.hop_length),
+                           weight_l1=1.0, weight_power=float(w))
+    need = int(_lib.lib().pwv_train_loss_workspace_bytes(ctypes.byref(a)))
+    if not need:
+        _lib.check(-1, 'pwv_train_loss_workspace_bytes')
+    d_out = torch.empty(N * T, dtype=torch.float32, device=pred.device)
+    table = torch.empty((N, 4), dtype=torch.float64, device=pred.device)
+    work = torch.empty(need // 8, dtype=torch.float64, device=pred.device)
+    a.d_out, a.result, a.workspace, a.workspace_bytes = _ptr(d_out), _ptr(table), _ptr(work), need
+    _call('pwv_train_loss_f32', a)
+    sums = table.sum(dim=0)                                              # {abs_sum, samples, power_sum, terms} of the batch
+    likelihood = sums[0] / sums[1]
+    power = sums[2] / sums[3] if w > 0 else torch.zeros_like(likelihood)       # (weight 0: no frame is formed, terms = 0)
+    total = likelihood + float(w) * power
+    return d_out, {'likelihood': likelihood.to(torch.float32), 'power': power.to(torch.float32), 'total': total.to(torch.float32)}
+
+
+def loss_and_grad(model, wav, melspec, z=None, seed=None, max_workgroups: int = 0, power_weight: Optional[float] = None,
+                  terms: Optional[dict] = None):
     """(loss, pred, grads) of one batch: `loss` the L1 mean |pred - wav| as a device scalar (models.py:93 `loss/likelihood`), `pred`
     [N, T, 1] the model's output, `grads` {name: device tensor of the variable's shape} for EVERY trainable variable of the store under
     'iaf_vocoder' -- exact zeros for the ones the model never reads (skip / skip_bias of every layer but the last, dense / dense_bias of
     the last).  wav [N, T] or [N, T, 1], melspec [N, 1 + T / hop, n_mels], both on the GPU; z [N, T, 1] replaces the logistic noise the
     forward draws (`seed`: as IAFVocoder.sample_noise).  Only enqueues; `max_workgroups` (0: two per compute unit) sets the number of
-    partials of every weight-gradient reduction."""
+    partials of every weight-gradient reduction.
+
+    `power_weight` = w >= 0 asks for the reference's whole cost, likelihood + w * power (models.py:95-99; hp.train.weight_power_loss is
+    not consulted): the loss head is then one pwv_train_loss_f32 (include/pwv_hip_train_loss.h) with hp.signal.win_length / hop_length,
+    `loss` is the total as a float32 device scalar, and `terms`, if a dict is passed, receives the device scalars 'likelihood', 'power'
+    and 'total'.  None: the L1 alone, and hparams with train.weight_power_loss > 0 are refused."""
     from . import engine
-    why = refusal(model, wav, melspec)
+    why = refusal(model, wav, melspec, power_weight=power_weight)
     if why:
         raise PwvError('training refused: ' + why)
     store = model.store or get_default_store()
@@ -243,9 +280,15 @@ def loss_and_grad(model, wav, melspec, z=None, seed=None, max_workgroups: int = 
         saved.append((x, s))
         x = x * s[0][2] + s[1][2]                                                       # modules.py:59
     y = wav.reshape(N * T)
-    diff = x - y
-    loss = diff.abs().mean()
-    d_out = torch.sign(diff) / float(N * T)
+    if power_weight is None:
+        diff = x - y
+        loss = diff.abs().mean()
+        d_out = torch.sign(diff) / float(N * T)
+    else:
+        d_out, parts = _loss_head(x.contiguous(), y.contiguous(), N, T, float(power_weight))
+        loss = parts['total']
+        if terms is not None:
+            terms.update(parts)
 
     # sample rate, backward
     grads: Dict[str, torch.Tensor] = {}
@@ -316,10 +359,13 @@ _UNSET = object()
 
 class Trainer(object):
     """The reference's training step (models.py:80-103) on one model: loss_and_grad, then adam_ema_update on the store's variables in
-    place.  Defaults from hparams: lr = train.lr, beta2 = train.adam_beta2, ema_decay = train.ema_decay if train.use_ema."""
+    place.  Defaults from hparams: lr = train.lr, beta2 = train.adam_beta2, ema_decay = train.ema_decay if train.use_ema.
+    `power_weight` goes to every loss_and_grad; `terms` then holds the last step's 'likelihood', 'power' and 'total' (device scalars)."""
 
-    def __init__(self, model, lr=None, beta2=None, ema_decay=_UNSET, max_workgroups: int = 0):
+    def __init__(self, model, lr=None, beta2=None, ema_decay=_UNSET, max_workgroups: int = 0, power_weight: Optional[float] = None):
         self.model = model
+        self.power_weight = power_weight        # None: the L1 alone; w >= 0: likelihood + w * power (loss_and_grad)
+        self.terms: Dict[str, torch.Tensor] = {}
         self.store = model.store or get_default_store()
         self.lr = float(hp.train.lr if lr is None else lr)
         self.beta1, self.beta2 = ADAM_BETA1, float(hp.train.adam_beta2 if beta2 is None else beta2)
@@ -332,7 +378,7 @@ class Trainer(object):
 
     def _bind(self):
         """Every variable of the model exists from here on; the optimiser's lists follow the sorted names."""
-        why = refusal(self.model)
+        why = refusal(self.model, power_weight=self.power_weight)
         if why:
             raise PwvError('training refused: ' + why)
         if self.names is None:
@@ -342,9 +388,12 @@ class Trainer(object):
         return [self.store.vars[n] for n in self.names]
 
     def step(self, wav, mel, z=None):
-        """One step on one batch; returns the loss BEFORE the update (a device scalar)."""
+        """One step on one batch; returns the loss BEFORE the update (a device scalar; with a power_weight: the total)."""
         vars = self._bind()
-        loss, _, grads = loss_and_grad(self.model, wav, mel, z=z, max_workgroups=self.max_workgroups)
+        terms: Dict[str, torch.Tensor] = {}
+        loss, _, grads = loss_and_grad(self.model, wav, mel, z=z, max_workgroups=self.max_workgroups, power_weight=self.power_weight,
+                                       terms=terms)
+        self.terms = terms
         self.state = adam_ema_update(vars, [grads[n] for n in self.names], self.state, self.lr, self.beta1, self.beta2, ADAM_EPS, self.ema_decay)
         self.store.touch()
         return loss
@@ -426,14 +475,17 @@ def _dataset(length: int, seed: int) -> List[np.ndarray]:
 
 def train(case='default', ckpt=None, steps=None, seed=0):
     """train.py:25-71 on one GPU: per step a seeded random crop of hp.signal.length samples per item (data_load.py:46-50), its mel from
-    the device front-end, one Trainer.step; prints loss/likelihood per step; saves into hp.logdir (PWV_LOGDIR overrides) every
+    the device front-end, one Trainer.step; prints loss/likelihood per step (with train.weight_power_loss > 0 the power loss is trained
+    too, and the line carries loss/likelihood, loss/power and loss/total); saves into hp.logdir (PWV_LOGDIR overrides) every
     train.save_per_epoch * train.steps_per_epoch steps and at the end.  `ckpt` names a file in the log directory to resume from (default:
     the newest .npz there)."""
     from .audio_frontend import wav_to_mel_device
     from .models import IAFVocoder
     from .variables import reset_default_store
     hp.set_hparam_yaml(case)
-    why = refusal()
+    power_weight = float(hp.train.get('weight_power_loss', 0) or 0)
+    power_weight = power_weight if power_weight > 0 else None
+    why = refusal(power_weight=power_weight)
     if why:
         raise PwvError('training refused: ' + why)
     if not torch.cuda.is_available():
@@ -446,7 +498,7 @@ def train(case='default', ckpt=None, steps=None, seed=0):
     store = reset_default_store(device=device)
     model = IAFVocoder(batch_size=batch, length=length, store=store, precision='f32')
     model.noise_seed = seed
-    trainer = Trainer(model)
+    trainer = Trainer(model, power_weight=power_weight)
     path = os.path.join(logdir, ckpt) if ckpt else (sorted(glob.glob(os.path.join(logdir, '*.npz')), key=os.path.getmtime) or [None])[-1]
     if path and os.path.exists(path):
         print('resumed from %s at step %d' % (path, trainer.load(path)))
@@ -462,7 +514,11 @@ def train(case='default', ckpt=None, steps=None, seed=0):
             crop[b] = w[at:at + length]
         wav = torch.from_numpy(crop).to(device)
         loss = trainer.step(wav, wav_to_mel_device(wav))
-        print('step %d loss/likelihood %.6f' % (trainer.steps, float(loss)))
+        if power_weight is None:
+            print('step %d loss/likelihood %.6f' % (trainer.steps, float(loss)))
+        else:
+            print('step %d loss/likelihood %.6f loss/power %.6f loss/total %.6f'
+                  % (trainer.steps, float(trainer.terms['likelihood']), float(trainer.terms['power']), float(loss)))
         if trainer.steps % every == 0:
             saved_at = os.path.join(logdir, 'model-%d.npz' % trainer.steps)
             trainer.save(saved_at)

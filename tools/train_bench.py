@@ -12,6 +12,13 @@ stream around the call:
 There is no threshold: the file records a first measurement.  Writes profiles/train_bench.json and prints it as one JSON line.
 
     python tools/train_bench.py [--steps 20] [--warmup 3]
+
+--power measures what the STFT power loss adds instead (same model, batch and machine, one run): loss_and_grad with
+power_weight=0.0005 (the loss head is pwv_train_loss_f32, csrc/pwv_train_loss.hip) and with power_weight=None (the L1 in torch), the two
+ALTERNATING call by call so that clock and co-tenants treat them alike, and the loss head alone (the C call on a fixed pred, timed over
+runs of 20 calls) at weight 0.0005 and at weight 0 (the L1 alone).  Writes profiles/train_power_bench.json.
+
+    python tools/train_bench.py --power [--steps 20] [--warmup 3]
 """
 import argparse
 import json
@@ -29,8 +36,11 @@ def main():
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--batch', type=int, default=8)
     ap.add_argument('--length', type=int, default=4000)
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'train_bench.json'))
+    ap.add_argument('--power', action='store_true', help='measure loss_and_grad with and without the STFT power loss instead')
+    ap.add_argument('--out', default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, 'profiles', 'train_power_bench.json' if args.power else 'train_bench.json')
     steps, warmup = max(args.steps, 20), max(args.warmup, 3)
 
     import numpy as np
@@ -84,6 +94,9 @@ def main():
     cols = 128 * 2 * sum(len(d) for d in cfg.dilations)
     train_forward.P = torch.zeros((n * mel.shape[1], cols), dtype=torch.float32, device=dev)
 
+    if args.power:
+        return power_legs(args, TR, model, wav, mel, z, steps, warmup)
+
     legs = {}
     legs['forward_f32'] = timed(forward)
     model.verify()
@@ -100,6 +113,67 @@ def main():
     out['repack_ms'] = round(legs['forward_after_step'][0] - legs['forward_f32'][0], 3)
     out['backward_over_train_forward'] = round((legs['loss_and_grad'][0] - legs['train_forward'][0]) / legs['train_forward'][0], 2)
     out['loss_and_grad_over_forward_f32'] = round(legs['loss_and_grad'][0] / legs['forward_f32'][0], 2)
+    with open(args.out, 'w') as f:
+        json.dump(out, f, indent=1)
+        f.write('\n')
+    print(json.dumps(out))
+
+
+def power_legs(args, TR, model, wav, mel, z, steps, warmup, weight=0.0005):
+    import ctypes
+    import torch
+    from pwv_amd import _lib
+    from pwv_amd.hparam import hparam as hp
+
+    def once(fn):
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+
+    variants = {'loss_and_grad_power': lambda: TR.loss_and_grad(model, wav, mel, z=z, power_weight=weight),
+                'loss_and_grad_l1': lambda: TR.loss_and_grad(model, wav, mel, z=z)}
+    ms = {k: [] for k in variants}
+    for k in range(warmup + steps):
+        for name, fn in variants.items():            # alternating: A B A B ...
+            t = once(fn)
+            if k >= warmup:
+                ms[name].append(t)
+
+    # the loss head alone, on the prediction of the model: 20 calls per timed window (one call is tens of microseconds)
+    n, length = args.batch, args.length
+    _, pred, _ = TR.loss_and_grad(model, wav, mel, z=z)
+    pred, y = pred.reshape(-1).contiguous(), wav.reshape(-1).contiguous()
+    win, hop = int(hp.signal.win_length), int(hp.signal.hop_length)
+    lib, stream, calls = _lib.lib(), torch.cuda.current_stream().cuda_stream, 20
+    head = {}
+    for name, w in (('loss_head_power', weight), ('loss_head_l1', 0.0)):
+        a = _lib.TrainLossArgs(out=pred.data_ptr(), y=y.data_ptr(), n=n, T=length, win_length=win, hop_length=hop, weight_l1=1.0, weight_power=w)
+        need = int(lib.pwv_train_loss_workspace_bytes(ctypes.byref(a)))
+        d_out = torch.empty(n * length, dtype=torch.float32, device=pred.device)
+        table = torch.empty((n, 4), dtype=torch.float64, device=pred.device)
+        work = torch.empty(need // 8, dtype=torch.float64, device=pred.device)
+        a.d_out, a.result, a.workspace, a.workspace_bytes = d_out.data_ptr(), table.data_ptr(), work.data_ptr(), need
+
+        def run(a=a):
+            for _ in range(calls):
+                _lib.check(lib.pwv_train_loss_f32(ctypes.byref(a), stream), 'pwv_train_loss_f32')
+
+        head[name] = [once(run) / calls for k in range(warmup + steps)][warmup:]
+    frames = 1 + (length - win) // hop
+    nfft = 1
+    while nfft < win:
+        nfft *= 2
+    out = {'model': 'default (4 flows, 10 + 10 + 10 + 30 layers, 2 nets each)', 'batch': n, 'length': length, 'steps': steps, 'warmup': warmup,
+           'device': torch.cuda.get_device_name(0), 'power_weight': weight, 'win_length': win, 'hop_length': hop, 'frames_per_utterance': frames,
+           'loss_head_f64_fma': n * frames * (4 * (nfft // 2) * win + 2 * (nfft // 2 + 1) * win)}
+    for k, v in list(ms.items()) + list(head.items()):
+        out[k + '_ms'] = {'median': round(statistics.median(v), 4), 'min': round(min(v), 4), 'max': round(max(v), 4)}
+    out['power_minus_l1_ms'] = round(statistics.median(ms['loss_and_grad_power']) - statistics.median(ms['loss_and_grad_l1']), 4)
+    out['paired_difference_ms'] = {'median': round(statistics.median(a - b for a, b in zip(ms['loss_and_grad_power'], ms['loss_and_grad_l1'])), 4)}
     with open(args.out, 'w') as f:
         json.dump(out, f, indent=1)
         f.write('\n')
