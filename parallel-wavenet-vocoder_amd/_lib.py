@@ -18,7 +18,8 @@ _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 _REPO_ROOT = os.path.dirname(_PKG_DIR)
 LIB_PATH = os.environ.get('PWV_LIB') or os.path.join(_PKG_DIR, 'libpwv_hip.so')   # PWV_LIB: A/B another build
 CSRC = [os.path.join(_PKG_DIR, 'csrc', f) for f in ('pwv_layer.hip', 'pwv_layer_f16.hip', 'pwv_layer_h16.hip', 'pwv_misc.hip',
-                                                    'pwv_stack_persist.hip', 'pwv_norm.hip', 'pwv_audio.hip', 'pwv_stream_tick.hip', 'pwv_score.hip', 'pwv_train.hip', 'pwv_train_loss.hip')]
+                                                    'pwv_stack_persist.hip', 'pwv_norm.hip', 'pwv_audio.hip', 'pwv_stream_tick.hip', 'pwv_score.hip', 'pwv_train.hip', 'pwv_train_loss.hip',
+                                                    'pwv_train_varlen.hip')]
 
 HEADER_VERSION = 301          # PWV_HIP_VERSION of include/pwv_hip.h these ctypes mirrors were written against
 FIRST_FOLD_FLOATS = 2048      # PWV_FIRST_FOLD_FLOATS
@@ -55,6 +56,9 @@ TRAIN_SYMBOLS = ('pwv_train_workspace_bytes', 'pwv_train_front_fwd_f32', 'pwv_tr
                  'pwv_train_head_bwd_f32', 'pwv_train_layer_bwd_f32', 'pwv_train_front_bwd_f32')
 # ... and of include/pwv_hip_train_loss.h: the loss head of training, L1 + STFT power loss and their gradient for the prediction
 TRAIN_LOSS_SYMBOLS = ('pwv_train_loss_workspace_bytes', 'pwv_train_loss_f32')
+# ... and of include/pwv_hip_train_varlen.h: training on packed batches of mixed-length utterances, and their loss head
+TRAIN_VARLEN_SYMBOLS = ('pwv_train_varlen_front_fwd_f32', 'pwv_train_varlen_layer_fwd_f32', 'pwv_train_varlen_layer_bwd_f32',
+                        'pwv_train_varlen_front_bwd_f32', 'pwv_train_loss_varlen_workspace_bytes', 'pwv_train_loss_varlen_f32')
 
 
 class PwvError(RuntimeError):
@@ -394,6 +398,40 @@ class TrainLossArgs(Structure):
         self.struct_size = ctypes.sizeof(TrainLossArgs)
 
 
+class TrainVarlenArgs(Structure):
+    """pwv_train_varlen_args: one training kernel call on one net over a packed batch (include/pwv_hip_train_varlen.h): the fields of
+    TrainArgs, then the packed batch."""
+    _fields_ = (TrainArgs._fields_
+                + [('cu_rows', c_void_p), ('cu_frames', c_void_p)]
+                + [(n, ctypes.c_int32) for n in ('n', 'rows', 'proj_rows')])
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = ctypes.sizeof(TrainVarlenArgs)
+
+
+class TrainLossVarlenArgs(Structure):
+    """pwv_train_loss_varlen_args: the loss terms of a packed batch and their gradient for the prediction
+    (include/pwv_hip_train_varlen.h)."""
+    _fields_ = [
+        ('struct_size', c_size_t),      # set by __init__
+        ('out', c_void_p),
+        ('y', c_void_p),
+        ('cu_rows', c_void_p),
+        ('n', ctypes.c_int32), ('rows', ctypes.c_int32),
+        ('win_length', ctypes.c_int32), ('hop_length', ctypes.c_int32),
+        ('weight_l1', ctypes.c_double), ('weight_power', ctypes.c_double),
+        ('d_out', c_void_p),
+        ('result', c_void_p),
+        ('workspace', c_void_p),
+        ('workspace_bytes', c_size_t),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = ctypes.sizeof(TrainLossVarlenArgs)
+
+
 # per-source extra flags (none in the product; tools/probes/regw/README.md: the register-stationary probe kernel needs
 # `-mllvm -amdgpu-mfma-vgpr-form=1`, which is why the sources are compiled one by one)
 EXTRA_FLAGS = {}
@@ -552,6 +590,11 @@ def _declare(lib):
     lib.pwv_train_loss_workspace_bytes.restype = c_size_t
     lib.pwv_train_loss_workspace_bytes.argtypes = [POINTER(TrainLossArgs)]
     lib.pwv_train_loss_f32.argtypes = [POINTER(TrainLossArgs), c_void_p]
+    for name in TRAIN_VARLEN_SYMBOLS[:4]:
+        getattr(lib, name).argtypes = [POINTER(TrainVarlenArgs), c_void_p]
+    lib.pwv_train_loss_varlen_workspace_bytes.restype = c_size_t
+    lib.pwv_train_loss_varlen_workspace_bytes.argtypes = [POINTER(TrainLossVarlenArgs)]
+    lib.pwv_train_loss_varlen_f32.argtypes = [POINTER(TrainLossVarlenArgs), c_void_p]
     lib.pwv_instance_norm_workspace_bytes.restype = c_size_t
     lib.pwv_instance_norm_workspace_bytes.argtypes = [c_int, c_int, c_int]
     lib.pwv_instance_norm_f32.argtypes = [f32p, f32p, c_int, c_int, c_int, f32p, f32p, ctypes.c_float, c_void_p, c_size_t, c_void_p]
@@ -573,7 +616,7 @@ def _declare(lib):
     lib.pwv_status_words_alloc.argtypes = [POINTER(c_void_p)]
     lib.pwv_status_words_free.argtypes = [c_void_p]
     lib.pwv_range_check_f32.argtypes = [f32p, c_int64, ctypes.c_float, c_void_p, c_void_p]
-    for name in EXPORTED_SYMBOLS + EXTENSION_SYMBOLS + LIVE_TICK_SYMBOLS + SCORE_SYMBOLS + TRAIN_SYMBOLS + TRAIN_LOSS_SYMBOLS:      # fails loudly (AttributeError) if a symbol is missing
+    for name in EXPORTED_SYMBOLS + EXTENSION_SYMBOLS + LIVE_TICK_SYMBOLS + SCORE_SYMBOLS + TRAIN_SYMBOLS + TRAIN_LOSS_SYMBOLS + TRAIN_VARLEN_SYMBOLS:      # fails loudly (AttributeError) if a symbol is missing
         getattr(lib, name)
     return lib
 

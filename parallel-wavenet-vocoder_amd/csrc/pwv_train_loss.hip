@@ -1,6 +1,7 @@
 // The loss head of training (include/pwv_hip_train_loss.h; DESIGN.md section 9, "Training"): weight_l1 * mean |out - y| +
 // weight_power * mean over frames and bins of (|STFT out|^2 - |STFT y|^2)^2, the table of pwv_hip_score.h, and the gradient of that sum
-// for `out`.  The STFT is the one of csrc/pwv_score.hip (tf.contrib.signal.stft at its defaults), uniform batches only.
+// for `out`.  The STFT is the one of csrc/pwv_score.hip (tf.contrib.signal.stft at its defaults), uniform batches only (the packed
+// form, csrc/pwv_train_varlen.hip, runs the same frame body: pwv_train_loss_frame.h).
 // Everything is fp64 on the fp32 inputs.  Two launches, no floating-point atomics:
 //   loss_frames_kernel   one workgroup per (utterance, frame): the direct real DFT of both windowed frames, one thread per bin, twiddles
 //                        from an LDS table of sincospi; D_b (Ar_b, Ai_b) of every bin goes back into LDS and the same table runs backward,
@@ -14,13 +15,9 @@
 
 #include "pwv_common.h"
 #include "pwv_hip_train_loss.h"
+#include "pwv_train_loss_frame.h"
 
 namespace pwv {
-
-constexpr int kLossThreads = 256;       // workgroup size of both kernels, and the stride of the reduction's first pass
-constexpr int kLossTile = PWV_SCORE_TILE;
-
-typedef double f64x2 __attribute__((ext_vector_type(2)));
 
 struct LossParams {
     const float* out;
@@ -34,22 +31,8 @@ struct LossParams {
     int frames, tiles;                  // per utterance; frames = 0: the L1 alone
 };
 
-// the sum of the workgroup's 256 values, added as a fixed tree; every thread gets it
-__device__ __forceinline__ double loss_block_sum(double v, double* red) {
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = kLossThreads / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
-
 // blockIdx.x < n frames: frame blockIdx.x % frames of utterance blockIdx.x / frames; else a tile of the L1
 __global__ __launch_bounds__(256) void loss_frames_kernel(LossParams p) {
-    // [256] reduction, [nfft] (cos, sin), [nfft / 2 + 1] D (Ar, Ai), [win] (out, y) of the frame under the window
     extern __shared__ __attribute__((aligned(16))) double loss_sm[];
     double* red = loss_sm;
     const int tid = threadIdx.x;
@@ -57,69 +40,8 @@ __global__ __launch_bounds__(256) void loss_frames_kernel(LossParams p) {
     long long slot = blockIdx.x;
     if (slot < n_frames) {
         const int i = (int)(slot / p.frames), f = (int)(slot % p.frames);
-        const int win = p.win, nfft = p.nfft, half = nfft / 2;
-        f64x2* tw = (f64x2*)(red + kLossThreads);
-        f64x2* cw = tw + nfft;
-        f64x2* fr = cw + (half + 1);
         const long long at = (long long)i * p.T + (long long)f * p.hop;      // the frame ends at i T + f hop + win - 1 <= (i + 1) T - 1
-        const float* a = p.out + at;
-        const float* b = p.y + at;
-        for (int j = tid; j < win; j += kLossThreads) {
-            const double w = 0.5 - 0.5 * cospi(2.0 * j / win);
-            fr[j] = f64x2{(double)a[j] * w, (double)b[j] * w};
-        }
-        for (int j = tid; j < nfft; j += kLossThreads) {
-            double sn, cs;
-            sincospi(2.0 * j / nfft, &sn, &cs);
-            tw[j] = f64x2{cs, sn};
-        }
-        __syncthreads();
-        double acc = 0.0;
-        // bins 0 .. nfft / 2 - 1 (nfft = 1: its only bin)
-        for (int bin = tid; bin < (half > 0 ? half : 1); bin += kLossThreads) {
-            double ar = 0.0, ai = 0.0, br = 0.0, bi = 0.0;
-            int k = 0;                                                    // (bin * j) mod nfft
-            for (int j = 0; j < win; ++j) {
-                const f64x2 t = tw[k], v = fr[j];
-                ar = fma(v.x, t.x, ar);
-                ai = fma(v.x, t.y, ai);
-                br = fma(v.y, t.x, br);
-                bi = fma(v.y, t.y, bi);
-                k = (k + bin) & (nfft - 1);
-            }
-            const double d = (ar * ar + ai * ai) - (br * br + bi * bi);
-            cw[bin] = f64x2{d * ar, d * ai};
-            acc = fma(d, d, acc);
-        }
-        if (half > 0) {                                                   // the Nyquist bin: cos(pi j) = (-1)^j, sin(pi j) = 0
-            double na = 0.0, nb = 0.0;
-            for (int j = tid; j < win; j += kLossThreads) {
-                const f64x2 v = fr[j];
-                na += (j & 1) ? -v.x : v.x;
-                nb += (j & 1) ? -v.y : v.y;
-            }
-            na = loss_block_sum(na, red);
-            nb = loss_block_sum(nb, red);
-            if (tid == 0) {
-                const double d = na * na - nb * nb;
-                cw[half] = f64x2{d * na, 0.0};
-                acc = fma(d, d, acc);
-            }
-        }
-        acc = loss_block_sum(acc, red);                                   // (its barriers also publish cw)
-        if (tid == 0) p.part[slot] = acc;
-        double* g = p.grad + (size_t)slot * win;
-        for (int j = tid; j < win; j += kLossThreads) {
-            double sr = 0.0, si = 0.0;
-            int k = 0;                                                    // (bin * j) mod nfft
-            for (int bin = 0; bin <= half; ++bin) {
-                const f64x2 t = tw[k], c = cw[bin];
-                sr = fma(c.x, t.x, sr);
-                si = fma(c.y, t.y, si);
-                k = (k + j) & (nfft - 1);
-            }
-            g[j] = (0.5 - 0.5 * cospi(2.0 * j / win)) * (sr + si);
-        }
+        loss_frame(p.out + at, p.y + at, p.win, p.nfft, red, p.part + slot, p.grad + (size_t)slot * p.win);
         return;
     }
     slot -= n_frames;

@@ -3,16 +3,18 @@ times the STFT power loss -- pwv_train_loss_f32, include/pwv_hip_train_loss.h), 
 include/pwv_hip_train.h), TensorFlow's Adam and the reference's EMA (models.py:72-76, :101-103), and the loop of train.py:25-71.
 DESIGN.md section 9, "Training".
 
-    python -m pwv_amd.train CASE [--ckpt=NAME] [--steps=N] [--seed=S]
+    python -m pwv_amd.train CASE [--ckpt=NAME] [--steps=N] [--seed=S] [--varlen]
 
 Scope: what hparams/default.yaml trains -- filter_width 2, R = D = 64, S = 128, 'repeat' conditioning, no normalisers, no skip
-accumulation, separate scaler and shifter nets, uniform [N, T] batches, exact-fp32 arithmetic.  Everything else is refused with a
-PwvError that names the reason (`refusal`); nothing falls back to another implementation.
+accumulation, separate scaler and shifter nets, exact-fp32 arithmetic; uniform [N, T] batches (loss_and_grad) or packed batches of
+utterances of different lengths, unpadded (loss_and_grad_varlen, `--varlen`).  Everything else is refused with a PwvError that names
+the reason (`refusal`); nothing falls back to another implementation.
 
 Division of work.  Sample rate (the hot path): HIP kernels, one net per call -- the forward keeps every layer's input and the last
-layer's gated output, the backward recomputes F, G, o and the head's hidden layers from them.  Frame rate (plumbing, in torch): the
-conditioning dense + ReLU, the projections P = frames [gc_filter | gc_gate] + [filter_bias | gate_bias] of all net-layers as ONE matrix
-product, and their backward from the dP the kernels leave; the flow's affine out = in * s + b and the loss.
+layer's gated output, the backward recomputes F, G, o and the head's hidden layers from them.  Frame rate: the conditioning dense +
+ReLU and the projections P = frames [gc_filter | gc_gate] + [filter_bias | gate_bias] of all net-layers as ONE matrix product, both on
+the project's exact-fp32 GEMM (pwv_linear_f32: a row of P does not depend on the rows next to it); in torch (plumbing) their backward
+from the dP the kernels leave, the flow's affine out = in * s + b and the loss.
 """
 from __future__ import annotations
 
@@ -37,10 +39,11 @@ ADAM_EPS = 1e-8
 
 
 # ---- what is refused ----------------------------------------------------------------------------------------------------------------
-def refusal(model=None, wav=None, melspec=None, power_weight=None) -> Optional[str]:
+def refusal(model=None, wav=None, melspec=None, power_weight=None, packed=False) -> Optional[str]:
     """Why the current hparams / this model / these inputs cannot be trained here, or None.  Looks at structure only: no GPU.
     `power_weight`: the weight of the STFT power loss the caller asks for explicitly (loss_and_grad's argument); None = the L1 alone,
-    and then hparams that ask for a power loss are refused instead of being trained without it."""
+    and then hparams that ask for a power loss are refused instead of being trained without it.  `packed`: the caller is
+    loss_and_grad_varlen, which takes its lengths from the utterances and not from the model."""
     m = hp.model
     if m.cond_upsample_method != 'repeat':
         return "cond_upsample_method %r: only 'repeat' conditioning is differentiated (transposed-conv conditioning is not)" % m.cond_upsample_method
@@ -65,7 +68,7 @@ def refusal(model=None, wav=None, melspec=None, power_weight=None) -> Optional[s
     if power_weight is not None:
         if not (math.isfinite(float(power_weight)) and float(power_weight) >= 0):
             return 'power_weight %r must be a finite number >= 0' % (power_weight,)
-        length = getattr(model, 'length', None)
+        length = None if packed else getattr(model, 'length', None)
         if float(power_weight) > 0 and length is not None and length < int(hp.signal.win_length):
             return ('power_weight %g > 0 with length %d shorter than signal.win_length %d: the STFT power loss has no frame'
                     % (float(power_weight), length, int(hp.signal.win_length)))
@@ -139,12 +142,42 @@ class _Geometry(object):
         self.kmax = (self.hop + 30) // 32 + 1
         self.max_workgroups = max_workgroups
 
-    def args(self, **kw):
-        a = _lib.TrainArgs(N=self.N, T=self.T, cond_hop=self.hop, cond_offset=self.off, cond_frames=self.frames, proj_row_stride=self.cols,
-                           d_proj_row_stride=self.cols, max_workgroups=self.max_workgroups, dilation=1, next_dilation=1)
+    def _fill(self, a, kw):
         for k, v in kw.items():
             setattr(a, k, _ptr(v) if isinstance(v, torch.Tensor) else v)
         return a
+
+    def args(self, **kw):
+        return self._fill(_lib.TrainArgs(N=self.N, T=self.T, cond_hop=self.hop, cond_offset=self.off, cond_frames=self.frames,
+                                         proj_row_stride=self.cols, d_proj_row_stride=self.cols, max_workgroups=self.max_workgroups,
+                                         dilation=1, next_dilation=1), kw)
+
+    head_args = args                        # the head is row-independent: the same call for either geometry
+
+    def entry(self, kind):
+        """The entry point of 'front_fwd', 'layer_fwd', 'layer_bwd' or 'front_bwd' for this geometry."""
+        return 'pwv_train_%s_f32' % kind
+
+
+class _PackedGeometry(_Geometry):
+    """A packed batch (include/pwv_hip_train_varlen.h): `layout` an engine.VarlenGeometry.  The four entry points that depend on where
+    an utterance begins take the device tables; the head and the workspace are the uniform ones at N = 1, T = rows."""
+
+    def __init__(self, layout, cols, max_workgroups):
+        super().__init__(1, layout.rows, layout.total_frames, cols, max_workgroups)
+        self.layout = layout
+
+    def args(self, **kw):
+        g = self.layout
+        return self._fill(_lib.TrainVarlenArgs(cond_hop=self.hop, cond_offset=self.off, proj_row_stride=self.cols, d_proj_row_stride=self.cols,
+                                               max_workgroups=self.max_workgroups, dilation=1, next_dilation=1, cu_rows=_ptr(g.cu_rows),
+                                               cu_frames=_ptr(g.cu_frames), n=g.n, rows=g.rows, proj_rows=g.total_frames), kw)
+
+    def head_args(self, **kw):
+        return _Geometry.args(self, **kw)
+
+    def entry(self, kind):
+        return 'pwv_train_varlen_%s_f32' % kind
 
 
 def _net_forward(net: _Net, geo: _Geometry, xin, P):
@@ -152,14 +185,14 @@ def _net_forward(net: _Net, geo: _Geometry, xin, P):
     dev, L = xin.device, len(net.dilations)
     xs = [_tile32(geo.rows, dev) for _ in range(L)]
     o, y = _tile32(geo.rows, dev), torch.empty(geo.rows, dtype=torch.float32, device=dev)
-    _call('pwv_train_front_fwd_f32', geo.args(in_=xin, causal_filter=net.cf, x_out=xs[0]))
+    _call(geo.entry('front_fwd'), geo.args(in_=xin, causal_filter=net.cf, x_out=xs[0]))
     for j, d in enumerate(net.dilations):
         v, last = net.layers[j], j == L - 1
-        _call('pwv_train_layer_fwd_f32', geo.args(form=_lib.TRAIN_LAST if last else _lib.TRAIN_RESIDUAL, dilation=d, x=xs[j],
+        _call(geo.entry('layer_fwd'), geo.args(form=_lib.TRAIN_LAST if last else _lib.TRAIN_RESIDUAL, dilation=d, x=xs[j],
                                                  proj=P[0, net.col + 128 * j:], filter=v['filter'], gate=v['gate'], dense=v['dense'],
                                                  dense_bias=v.get('dense_bias'), x_out=o if last else xs[j + 1]))
     h, lv = net.head, net.layers[-1]
-    _call('pwv_train_head_fwd_f32', geo.args(x=o, skip=lv['skip'], skip_bias=lv.get('skip_bias'), post1=h['postprocess1'],
+    _call('pwv_train_head_fwd_f32', geo.head_args(x=o, skip=lv['skip'], skip_bias=lv.get('skip_bias'), post1=h['postprocess1'],
                                             post1_bias=h.get('postprocess1_bias'), post2=h['postprocess2'],
                                             post2_bias=h.get('postprocess2_bias'), y=y))
     return xs, o, y
@@ -174,7 +207,7 @@ def _net_backward(net: _Net, geo: _Geometry, saved, xin, d_out, d_mul, scale, d_
     hp_ = net.scope + '/postprocessing/'
     opt = lambda d, key, name: g(name, d[key]) if key in d else None
     d_o = _tile32(geo.rows, dev)
-    _call('pwv_train_head_bwd_f32', geo.args(
+    _call('pwv_train_head_bwd_f32', geo.head_args(
         x=o, d_out=d_out, d_mul=d_mul, skip=lv['skip'], skip_bias=lv.get('skip_bias'), post1=h['postprocess1'],
         post1_bias=h.get('postprocess1_bias'), post2=h['postprocess2'], post2_bias=h.get('postprocess2_bias'), d_o_out=d_o,
         d_skip=g(net.name(L - 1, 'skip'), lv['skip']), d_skip_bias=opt(lv, 'skip_bias', net.name(L - 1, 'skip_bias')),
@@ -185,7 +218,7 @@ def _net_backward(net: _Net, geo: _Geometry, saved, xin, d_out, d_mul, scale, d_
     for j in range(L - 1, -1, -1):
         v, last = net.layers[j], j == L - 1
         u_next, v_next = (None, None) if last else uv[(j + 1) & 1]
-        _call('pwv_train_layer_bwd_f32', geo.args(
+        _call(geo.entry('layer_bwd'), geo.args(
             form=_lib.TRAIN_LAST if last else _lib.TRAIN_RESIDUAL, dilation=net.dilations[j],
             next_dilation=1 if last else net.dilations[j + 1], x=xs[j], proj=geo.P[0, net.col + 128 * j:],
             filter=v['filter'], gate=v['gate'], dense=v['dense'], u_next=u_next, v_next=v_next, d_o=d_o if last else None,
@@ -194,7 +227,7 @@ def _net_backward(net: _Net, geo: _Geometry, saved, xin, d_out, d_mul, scale, d_
             d_dense=None if last else g(net.name(j, 'dense'), v['dense']),
             d_dense_bias=None if last else opt(v, 'dense_bias', net.name(j, 'dense_bias')),
             workspace=ws, workspace_bytes=ws.numel() * 4))
-    _call('pwv_train_front_bwd_f32', geo.args(
+    _call(geo.entry('front_bwd'), geo.args(
         in_=xin, causal_filter=net.cf, u_next=uv[0][0], v_next=uv[0][1], next_dilation=net.dilations[0], d_out=d_out, scale=scale,
         d_in=d_in, accumulate=int(accumulate), d_causal_filter=g(net.scope + '/causal_layer/filter', net.cf),
         workspace=ws, workspace_bytes=ws.numel() * 4))
@@ -254,45 +287,60 @@ def loss_and_grad(model, wav, melspec, z=None, seed=None, max_workgroups: int = 
         if noise.numel() != N * T:
             raise ValueError('z must be [%d, %d, 1], got %s' % (N, T, tuple(noise.shape)))
     flows = model_nets(model, store)
-    dense = cond_dense(store)
-    nets = [net for pair in flows for net in pair]
-    cols = sum(128 * len(net.dilations) for net in nets)
+    cols = sum(128 * len(net.dilations) for pair in flows for net in pair)
     geo = _Geometry(N, T, t_mel, cols, int(max_workgroups))
 
-    # frame rate, forward: frames = relu(mel dense); P = frames [gc_filter | gc_gate] + [filter_bias | gate_bias] for every net-layer
+    def head(x, y):
+        if power_weight is None:
+            diff = x - y
+            return diff.abs().mean(), torch.sign(diff) / float(N * T)
+        d_out, parts = _loss_head(x.contiguous(), y.contiguous(), N, T, float(power_weight))
+        if terms is not None:
+            terms.update(parts)
+        return parts['total'], d_out
+
+    loss, x, grads = _forward_backward(store, flows, geo, melspec.reshape(N * t_mel, n_mels), noise.reshape(N * T).contiguous(),
+                                       wav.reshape(N * T), head)
+    return loss, x.reshape(N, T, 1), grads
+
+
+def _forward_backward(store, flows, geo, mel2, x, y, head):
+    """What a uniform and a packed batch share: `mel2` [M, n_mels] the frames of the batch row after row, `x` [rows] the noise, `y`
+    [rows] the ground truth, `geo` the geometry of the kernels' calls, `head(pred, y)` -> (loss, d_out [rows]).  Returns (loss, pred
+    [rows], grads)."""
+    dev = mel2.device
+    dense = cond_dense(store)
+    nets = [net for pair in flows for net in pair]
+    cols = geo.cols
+
+    # frame rate, forward: frames = relu(mel dense); P = frames [gc_filter | gc_gate] + [filter_bias | gate_bias] for every net-layer.
+    # Both products run on the project's exact-fp32 GEMM (pwv_linear_f32), whose sum over K has one order whatever the number of rows:
+    # a row of P, and with it an utterance's prediction, does not depend on what else is in the batch.  (A BLAS picks its kernel, and
+    # the order of that sum, by the row count.)
+    from . import engine
     zeros64 = torch.zeros(64, dtype=torch.float32, device=dev)
-    mel2 = melspec.reshape(N * t_mel, n_mels)
-    pre = mel2 @ dense[0]
-    frames = torch.relu(pre)
+    mel2 = mel2.contiguous()
+    frames = engine.linear_op(mel2, dense[0].contiguous(), None, True, 'f32')
     bank_w = torch.cat([v[k][0] for net in nets for v in net.layers for k in ('gc_filter', 'gc_gate')], dim=1)          # [C, cols]
     bank_b = torch.cat([v.get(k, zeros64) for net in nets for v in net.layers for k in ('filter_bias', 'gate_bias')])
-    geo.P = (frames @ bank_w + bank_b).contiguous()                                                                    # [M, cols]
+    geo.P = engine.linear_op(frames, bank_w, bank_b, False, 'f32')                                                     # [M, cols]
 
     # sample rate, forward
-    ws_bytes = _lib.lib().pwv_train_workspace_bytes(ctypes.byref(geo.args()))
+    ws_bytes = _lib.lib().pwv_train_workspace_bytes(ctypes.byref(geo.head_args()))
     if not ws_bytes:
         _lib.check(-1, 'pwv_train_workspace_bytes')
     ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=dev)
-    x = noise.reshape(N * T).contiguous()
     saved = []
     for pair in flows:
         s = [_net_forward(net, geo, x, geo.P) for net in pair]
         saved.append((x, s))
         x = x * s[0][2] + s[1][2]                                                       # modules.py:59
-    y = wav.reshape(N * T)
-    if power_weight is None:
-        diff = x - y
-        loss = diff.abs().mean()
-        d_out = torch.sign(diff) / float(N * T)
-    else:
-        d_out, parts = _loss_head(x.contiguous(), y.contiguous(), N, T, float(power_weight))
-        loss = parts['total']
-        if terms is not None:
-            terms.update(parts)
+    loss, d_out = head(x, y)
 
     # sample rate, backward
     grads: Dict[str, torch.Tensor] = {}
-    dP = torch.zeros((N * t_mel * geo.kmax, cols), dtype=torch.float32, device=dev)       # K slots per P row (include/pwv_hip_train.h)
+    M = mel2.shape[0]
+    dP = torch.zeros((M * geo.kmax, cols), dtype=torch.float32, device=dev)               # K slots per P row (include/pwv_hip_train.h)
     for i in range(len(flows) - 1, -1, -1):
         xin, s = saved[i]
         d_in = torch.empty_like(xin) if i > 0 else None
@@ -301,10 +349,10 @@ def loss_and_grad(model, wav, melspec, z=None, seed=None, max_workgroups: int = 
         d_out = d_in
 
     # frame rate, backward
-    dPs = dP.reshape(N * t_mel, geo.kmax, cols).sum(dim=1)
+    dPs = dP.reshape(M, geo.kmax, cols).sum(dim=1)
     d_bank_w = frames.t() @ dPs                                                                                          # [C, cols]
     d_bank_b = dPs.sum(dim=0)
-    d_pre = (dPs @ bank_w.t()) * (pre > 0).to(torch.float32)
+    d_pre = (dPs @ bank_w.t()) * (frames > 0).to(torch.float32)
     grads[SCOPE + '/cond/dense'] = (mel2.t() @ d_pre).unsqueeze(0)
     C = bank_w.shape[0]
     gw = d_bank_w.reshape(C, cols // 64, 64).permute(1, 0, 2).contiguous()                                               # [2 per net-layer, C, 64]
@@ -319,7 +367,103 @@ def loss_and_grad(model, wav, melspec, z=None, seed=None, max_workgroups: int = 
     for name in trainable_names(store):                 # what the model never reads
         if name not in grads:
             grads[name] = torch.zeros_like(store.vars[name])
-    return loss, x.reshape(N, T, 1), grads
+    return loss, x, grads
+
+
+# ---- packed batches: utterances of different lengths, unpadded ("Packed training") ------------------------------
+def _loss_head_varlen(pred, y, layout, w):
+    """The packed loss head on the device (pwv_train_loss_varlen_f32): weight_l1 = 1, weight_power = w, hp.signal.win_length /
+    hop_length, the lengths read from layout.cu_rows on the device.  Returns (d_out [rows] float32, {'likelihood', 'power', 'total'}
+    float32 device scalars); only enqueues."""
+    a = _lib.TrainLossVarlenArgs(out=_ptr(pred), y=_ptr(y), cu_rows=_ptr(layout.cu_rows), n=layout.n, rows=layout.rows,
+                                 win_length=int(hp.signal.win_length), hop_length=int(hp.signal.hop_length), weight_l1=1.0, weight_power=float(w))
+    need = int(_lib.lib().pwv_train_loss_varlen_workspace_bytes(ctypes.byref(a)))
+    if not need:
+        _lib.check(-1, 'pwv_train_loss_varlen_workspace_bytes')
+    d_out = torch.empty(layout.rows, dtype=torch.float32, device=pred.device)
+    table = torch.empty((layout.n, 4), dtype=torch.float64, device=pred.device)
+    work = torch.empty(need // 8, dtype=torch.float64, device=pred.device)
+    a.d_out, a.result, a.workspace, a.workspace_bytes = _ptr(d_out), _ptr(table), _ptr(work), need
+    _call('pwv_train_loss_varlen_f32', a)
+    sums = table.sum(dim=0)                                              # {abs_sum, samples, power_sum, terms} of the batch
+    likelihood = sums[0] / sums[1]
+    power = sums[2] / sums[3] if w > 0 else torch.zeros_like(likelihood)
+    total = likelihood + float(w) * power
+    return d_out, {'likelihood': likelihood.to(torch.float32), 'power': power.to(torch.float32), 'total': total.to(torch.float32)}
+
+
+def loss_and_grad_varlen(model, wavs, mels, z=None, seeds=None, max_workgroups: int = 0, power_weight: Optional[float] = None,
+                         terms: Optional[dict] = None):
+    """loss_and_grad over utterances of DIFFERENT lengths in one packed batch, without padding: (loss, preds, grads).  wavs[i] is [T_i] or
+    [T_i, 1] and mels[i] [1 + T_i / hop, n_mels], both on the GPU, T_i >= hop a multiple of hop.  `loss` = sum |pred - wav| / sum T_i
+    (with `power_weight` = w: + w * power, the STFT power loss over the frames of all utterances that are at least win_length long --
+    pwv_train_loss_varlen_f32; `terms` as for loss_and_grad); `preds` a list of [T_i, 1] views of one packed result; `grads` the dict of
+    loss_and_grad, exact zeros for unread variables included.  `seeds` (one integer per utterance) gives every utterance a noise stream
+    of its own, as IAFVocoder.generate_varlen does; `z`, a list of [T_i, 1] (or [T_i]), replaces the noise; with neither, one draw of
+    sum T_i counters continues the model's stream.  The constructor's batch_size and length are not used.  Only enqueues: the kernels
+    read the lengths from device tables (include/pwv_hip_train_varlen.h)."""
+    from . import engine
+    from .models import noise_streams
+    why = refusal(model, power_weight=power_weight, packed=True)
+    if why:
+        raise PwvError('training refused: ' + why)
+    if not isinstance(wavs, (list, tuple)) or not isinstance(mels, (list, tuple)) or not wavs:
+        raise ValueError('wavs and mels must be non-empty lists of tensors, one entry per utterance')
+    if len(wavs) != len(mels):
+        raise ValueError('wavs holds %d utterances, mels %d' % (len(wavs), len(mels)))
+    n, hop = len(wavs), int(hp.signal.hop_length)
+    if hop % 2:
+        raise ValueError('hop_length %d must be even' % hop)
+    lengths = []
+    for i, (w, m) in enumerate(zip(wavs, mels)):
+        T = int(w.numel())
+        if getattr(w, 'dim', lambda: 0)() not in (1, 2) or (w.dim() == 2 and w.shape[1] != 1):
+            raise ValueError('wavs[%d] must be [T] or [T, 1], got %s' % (i, tuple(w.shape)))
+        if T < hop or T % hop:
+            raise ValueError('wavs[%d]: utterance %d has %d samples, not a multiple of hop_length %d (at least one hop)' % (i, i, T, hop))
+        if m.dim() != 2 or m.shape[1] != hp.signal.n_mels or m.shape[0] != 1 + T // hop:
+            raise ValueError('mels[%d]: utterance %d of %d samples needs a mel of [%d, %d], got %s'
+                             % (i, i, T, 1 + T // hop, hp.signal.n_mels, tuple(m.shape)))
+        lengths.append(T)
+    if power_weight is not None and float(power_weight) > 0 and max(lengths) < int(hp.signal.win_length):
+        raise PwvError('training refused: power_weight %g > 0 with no utterance as long as signal.win_length %d (the longest has %d samples): '
+                       'the STFT power loss has no frame' % (float(power_weight), int(hp.signal.win_length), max(lengths)))
+    streams = noise_streams(seeds, None, n, z)
+    if z is not None:
+        if not isinstance(z, (list, tuple)) or len(z) != n:
+            raise ValueError('z must be a list of %d tensors, one [T_i, 1] per utterance' % n)
+        for i, v in enumerate(z):
+            if int(v.numel()) != lengths[i]:
+                raise ValueError('z[%d] must be [%d, 1] (utterance %d), got %s' % (i, lengths[i], i, tuple(v.shape)))
+    store = model.store or get_default_store()
+    mels = [engine._require_cuda_f32(m, 'mels[%d]' % i) for i, m in enumerate(mels)]
+    wavs = [engine._require_cuda_f32(w, 'wavs[%d]' % i) for i, w in enumerate(wavs)]
+    dev = mels[0].device
+    layout = engine.VarlenGeometry(lengths, hop, dev)
+    if streams is not None:
+        noise = engine.logistic_noise_packed_op(layout.cu_rows, layout.stream_table(streams), layout.rows)
+    elif z is None:
+        noise = engine.logistic_noise_op((layout.rows, 1), dev, seed=model._seed(), offset=model.noise_offset)
+        model.noise_offset += layout.rows
+    else:
+        noise = torch.cat([engine._require_cuda_f32(v, 'z[%d]' % i).reshape(-1) for i, v in enumerate(z)])
+    flows = model_nets(model, store)
+    cols = sum(128 * len(net.dilations) for pair in flows for net in pair)
+    geo = _PackedGeometry(layout, cols, int(max_workgroups))
+
+    def head(x, y):
+        if power_weight is None:
+            diff = x - y
+            return diff.abs().mean(), torch.sign(diff) / float(layout.rows)
+        d_out, parts = _loss_head_varlen(x.contiguous(), y.contiguous(), layout, float(power_weight))
+        if terms is not None:
+            terms.update(parts)
+        return parts['total'], d_out
+
+    loss, x, grads = _forward_backward(store, flows, geo, torch.cat(mels), noise.reshape(layout.rows).contiguous(),
+                                       torch.cat([w.reshape(-1) for w in wavs]), head)
+    packed = x.reshape(layout.rows, 1)
+    return loss, [packed[a:b] for a, b in zip(layout.cu_rows_host, layout.cu_rows_host[1:])], grads
 
 
 # ---- the optimiser ------------------------------------------------------------------------------------------------------------------
@@ -376,9 +520,9 @@ class Trainer(object):
         self.names: Optional[List[str]] = None
         self.state = None
 
-    def _bind(self):
+    def _bind(self, packed=False):
         """Every variable of the model exists from here on; the optimiser's lists follow the sorted names."""
-        why = refusal(self.model, power_weight=self.power_weight)
+        why = refusal(self.model, power_weight=self.power_weight, packed=packed)
         if why:
             raise PwvError('training refused: ' + why)
         if self.names is None:
@@ -393,6 +537,18 @@ class Trainer(object):
         terms: Dict[str, torch.Tensor] = {}
         loss, _, grads = loss_and_grad(self.model, wav, mel, z=z, max_workgroups=self.max_workgroups, power_weight=self.power_weight,
                                        terms=terms)
+        return self._update(vars, loss, grads, terms)
+
+    def step_varlen(self, wavs, mels, z=None):
+        """One step on one packed batch of utterances of different lengths (loss_and_grad_varlen: lists of [T_i] wavs and
+        [1 + T_i / hop, n_mels] mels); returns the loss BEFORE the update."""
+        vars = self._bind(packed=True)
+        terms: Dict[str, torch.Tensor] = {}
+        loss, _, grads = loss_and_grad_varlen(self.model, wavs, mels, z=z, max_workgroups=self.max_workgroups, power_weight=self.power_weight,
+                                              terms=terms)
+        return self._update(vars, loss, grads, terms)
+
+    def _update(self, vars, loss, grads, terms):
         self.terms = terms
         self.state = adam_ema_update(vars, [grads[n] for n in self.names], self.state, self.lr, self.beta1, self.beta2, ADAM_EPS, self.ema_decay)
         self.store.touch()
@@ -460,9 +616,14 @@ def _synthetic_wavs(n_items: int, length: int, seed: int) -> np.ndarray:
     return np.clip(out, -0.99, 0.99)
 
 
-def _dataset(length: int, seed: int) -> List[np.ndarray]:
-    """The training split (data_load.py:22-25: the first dataset_ratio share of the files) as trimmed wavs of at least `length` samples."""
+def _dataset(length: int, seed: int, varlen: bool = False) -> List[np.ndarray]:
+    """The training split (data_load.py:22-25: the first dataset_ratio share of the files) as trimmed wavs of at least `length` samples;
+    `varlen`: as long as they are (nothing is padded; files too short for one hop or for the mel front-end's n_fft / 2 < L are left
+    out), the stand-ins of seeded, differing lengths between one and four times `length`."""
     if hp.data_path == 'synthetic':
+        if varlen:
+            rng = np.random.RandomState(seed + 1)
+            return [_synthetic_wavs(1, int(rng.randint(length, 4 * length + 1)), seed + 2 + i)[0] for i in range(8)]
         return list(_synthetic_wavs(8, 4 * length, seed))
     from .audio_frontend import fix_length, read_wav, trim_wav
     files = sorted(glob.glob(hp.data_path))
@@ -470,15 +631,24 @@ def _dataset(length: int, seed: int) -> List[np.ndarray]:
         raise FileNotFoundError('no input files match data_path %r (use data_path: synthetic for seeded stand-ins)' % hp.data_path)
     files = files[:max(int(len(files) * hp.train.dataset_ratio), 1)]
     wavs = [trim_wav(read_wav(f, hp.signal.sr)).astype(np.float32) for f in files]
+    if varlen:
+        hop = int(hp.signal.hop_length)
+        wavs = [w for w in wavs if len(w) >= hop and len(w) // hop * hop > int(hp.signal.n_fft) // 2]
+        if not wavs:
+            raise ValueError('no file of data_path %r is long enough (one hop of %d samples, more than n_fft / 2 = %d)'
+                             % (hp.data_path, hop, int(hp.signal.n_fft) // 2))
+        return wavs
     return [fix_length(w, length) if len(w) < length else w for w in wavs]
 
 
-def train(case='default', ckpt=None, steps=None, seed=0):
+def train(case='default', ckpt=None, steps=None, seed=0, varlen=False):
     """train.py:25-71 on one GPU: per step a seeded random crop of hp.signal.length samples per item (data_load.py:46-50), its mel from
     the device front-end, one Trainer.step; prints loss/likelihood per step (with train.weight_power_loss > 0 the power loss is trained
     too, and the line carries loss/likelihood, loss/power and loss/total); saves into hp.logdir (PWV_LOGDIR overrides) every
     train.save_per_epoch * train.steps_per_epoch steps and at the end.  `ckpt` names a file in the log directory to resume from (default:
-    the newest .npz there)."""
+    the newest .npz there).  `varlen` (--varlen): every step trains ONE PACKED BATCH of batch_size files at their own lengths -- each cut
+    to a whole number of hops and to at most train.varlen_max_length samples (default 4 * signal.length; a longer file is cut at a seeded
+    offset), nothing padded (Trainer.step_varlen)."""
     from .audio_frontend import wav_to_mel_device
     from .models import IAFVocoder
     from .variables import reset_default_store
@@ -502,18 +672,30 @@ def train(case='default', ckpt=None, steps=None, seed=0):
     path = os.path.join(logdir, ckpt) if ckpt else (sorted(glob.glob(os.path.join(logdir, '*.npz')), key=os.path.getmtime) or [None])[-1]
     if path and os.path.exists(path):
         print('resumed from %s at step %d' % (path, trainer.load(path)))
-    wavs = _dataset(length, seed)
+    varlen = bool(varlen) and varlen != 'False'
+    wavs = _dataset(length, seed, varlen)
+    hop = int(hp.signal.hop_length)
+    max_len = max(int(hp.train.get('varlen_max_length', 0) or 4 * length) // hop * hop, hop)
     rng = np.random.RandomState(seed + trainer.steps)
     every = max(int(hp.train.save_per_epoch) * int(hp.train.steps_per_epoch), 1)
     saved_at = None
     for _ in range(steps):
-        crop = np.empty((batch, length), dtype=np.float32)
-        for b in range(batch):
-            w = wavs[rng.randint(len(wavs))]
-            at = rng.randint(len(w) - length + 1)
-            crop[b] = w[at:at + length]
-        wav = torch.from_numpy(crop).to(device)
-        loss = trainer.step(wav, wav_to_mel_device(wav))
+        if varlen:
+            pieces = []
+            for b in range(batch):
+                w = wavs[rng.randint(len(wavs))]
+                n = min(len(w) // hop * hop, max_len)
+                at = rng.randint(len(w) - n + 1)
+                pieces.append(torch.from_numpy(np.ascontiguousarray(w[at:at + n])).to(device))
+            loss = trainer.step_varlen(pieces, [wav_to_mel_device(p.unsqueeze(0))[0] for p in pieces])
+        else:
+            crop = np.empty((batch, length), dtype=np.float32)
+            for b in range(batch):
+                w = wavs[rng.randint(len(wavs))]
+                at = rng.randint(len(w) - length + 1)
+                crop[b] = w[at:at + length]
+            wav = torch.from_numpy(crop).to(device)
+            loss = trainer.step(wav, wav_to_mel_device(wav))
         if power_weight is None:
             print('step %d loss/likelihood %.6f' % (trainer.steps, float(loss)))
         else:

@@ -19,6 +19,16 @@ ALTERNATING call by call so that clock and co-tenants treat them alike, and the 
 runs of 20 calls) at weight 0.0005 and at weight 0 (the L1 alone).  Writes profiles/train_power_bench.json.
 
     python tools/train_bench.py --power [--steps 20] [--warmup 3]
+
+--varlen measures packed training ("Packed training"; train.loss_and_grad_varlen -> pwv_train_varlen_*), four legs
+ALTERNATING call by call in one run, same model and z:
+  a_uniform_8x4000         loss_and_grad at 8 x 4000
+  b_packed_equal           loss_and_grad_varlen at eight equal lengths of 4000: what the per-unit lookup of the packed kernels costs
+  c_packed_mixed           loss_and_grad_varlen at eight mixed lengths that sum to 32000
+  d_uniform_padded_mixed   loss_and_grad on the same mixed lengths zero-padded to the longest: what a user pays today
+Writes profiles/train_varlen_bench.json.
+
+    python tools/train_bench.py --varlen [--steps 20] [--warmup 3]
 """
 import argparse
 import json
@@ -37,10 +47,12 @@ def main():
     ap.add_argument('--batch', type=int, default=8)
     ap.add_argument('--length', type=int, default=4000)
     ap.add_argument('--power', action='store_true', help='measure loss_and_grad with and without the STFT power loss instead')
+    ap.add_argument('--varlen', action='store_true', help='measure packed batches against uniform and padded ones instead')
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, 'profiles', 'train_power_bench.json' if args.power else 'train_bench.json')
+        name = 'train_power_bench.json' if args.power else 'train_varlen_bench.json' if args.varlen else 'train_bench.json'
+        args.out = os.path.join(ROOT, 'profiles', name)
     steps, warmup = max(args.steps, 20), max(args.warmup, 3)
 
     import numpy as np
@@ -96,6 +108,8 @@ def main():
 
     if args.power:
         return power_legs(args, TR, model, wav, mel, z, steps, warmup)
+    if args.varlen:
+        return varlen_legs(args, TR, O, cfg, store, model, wav, mel, z, steps, warmup)
 
     legs = {}
     legs['forward_f32'] = timed(forward)
@@ -174,6 +188,61 @@ def power_legs(args, TR, model, wav, mel, z, steps, warmup, weight=0.0005):
         out[k + '_ms'] = {'median': round(statistics.median(v), 4), 'min': round(min(v), 4), 'max': round(max(v), 4)}
     out['power_minus_l1_ms'] = round(statistics.median(ms['loss_and_grad_power']) - statistics.median(ms['loss_and_grad_l1']), 4)
     out['paired_difference_ms'] = {'median': round(statistics.median(a - b for a, b in zip(ms['loss_and_grad_power'], ms['loss_and_grad_l1'])), 4)}
+    with open(args.out, 'w') as f:
+        json.dump(out, f, indent=1)
+        f.write('\n')
+    print(json.dumps(out))
+
+
+MIXED = [8000, 6400, 4800, 4000, 3200, 2400, 1600, 1600]       # sum 32000 = 8 x 4000; padded to the longest: 64000 rows
+
+
+def varlen_legs(args, TR, O, cfg, store, model, wav, mel, z, steps, warmup):
+    import numpy as np
+    import torch
+    from pwv_amd.models import IAFVocoder
+    dev = wav.device
+    n, length, hop = args.batch, args.length, cfg.hop_length
+    assert sum(MIXED) == n * length and all(T % hop == 0 for T in MIXED), 'the mixed lengths are for --batch 8 --length 4000'
+
+    def once(fn):
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+
+    eq = ([wav[i] for i in range(n)], [mel[i] for i in range(n)], [z[i] for i in range(n)])
+    longest = max(MIXED)
+    mel_p, z_p = O.synthetic_inputs(n, longest, cfg, mel_seed=7, z_seed=8)
+    wav_p = (0.3 * np.random.RandomState(9).randn(n, longest)).astype(np.float32)
+    for i, T in enumerate(MIXED):                       # the padded batch: zeros behind every utterance's end
+        wav_p[i, T:] = 0
+    mel_p, z_p, wav_p = (torch.from_numpy(a).to(dev) for a in (mel_p, z_p, wav_p))
+    mixed = ([wav_p[i, :T] for i, T in enumerate(MIXED)], [mel_p[i, :1 + T // hop] for i, T in enumerate(MIXED)],
+             [z_p[i, :T] for i, T in enumerate(MIXED)])
+    padded_model = IAFVocoder(batch_size=n, length=longest, store=store, precision='f32')
+    variants = {'a_uniform_8x4000': lambda: TR.loss_and_grad(model, wav, mel, z=z),
+                'b_packed_equal': lambda: TR.loss_and_grad_varlen(model, eq[0], eq[1], z=eq[2]),
+                'c_packed_mixed': lambda: TR.loss_and_grad_varlen(model, mixed[0], mixed[1], z=mixed[2]),
+                'd_uniform_padded_mixed': lambda: TR.loss_and_grad(padded_model, wav_p, mel_p, z=z_p)}
+    ms = {k: [] for k in variants}
+    for k in range(warmup + steps):
+        for name, fn in variants.items():            # alternating: A B C D A B C D ...
+            t = once(fn)
+            if k >= warmup:
+                ms[name].append(t)
+    out = {'model': 'default (4 flows, 10 + 10 + 10 + 30 layers, 2 nets each)', 'batch': n, 'length': length, 'steps': steps, 'warmup': warmup,
+           'device': torch.cuda.get_device_name(0), 'mixed_lengths': MIXED, 'rows_packed': sum(MIXED), 'rows_padded': n * longest}
+    for k, v in ms.items():
+        out[k + '_ms'] = {'median': round(statistics.median(v), 3), 'min': round(min(v), 3), 'max': round(max(v), 3)}
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    out['b_over_a'] = round(med['b_packed_equal'] / med['a_uniform_8x4000'], 4)
+    out['paired_b_minus_a_ms'] = {'median': round(statistics.median(b - a for a, b in zip(ms['a_uniform_8x4000'], ms['b_packed_equal'])), 3)}
+    out['d_over_c'] = round(med['d_uniform_padded_mixed'] / med['c_packed_mixed'], 4)
+    out['rows_padded_over_packed'] = round(n * longest / float(sum(MIXED)), 4)
     with open(args.out, 'w') as f:
         json.dump(out, f, indent=1)
         f.write('\n')
