@@ -19,7 +19,7 @@ _REPO_ROOT = os.path.dirname(_PKG_DIR)
 LIB_PATH = os.environ.get('PWV_LIB') or os.path.join(_PKG_DIR, 'libpwv_hip.so')   # PWV_LIB: A/B another build
 CSRC = [os.path.join(_PKG_DIR, 'csrc', f) for f in ('pwv_layer.hip', 'pwv_layer_f16.hip', 'pwv_layer_h16.hip', 'pwv_misc.hip',
                                                     'pwv_stack_persist.hip', 'pwv_norm.hip', 'pwv_audio.hip', 'pwv_stream_tick.hip', 'pwv_score.hip', 'pwv_train.hip', 'pwv_train_loss.hip',
-                                                    'pwv_train_varlen.hip')]
+                                                    'pwv_train_varlen.hip', 'pwv_train_cond.hip')]
 
 HEADER_VERSION = 301          # PWV_HIP_VERSION of include/pwv_hip.h these ctypes mirrors were written against
 FIRST_FOLD_FLOATS = 2048      # PWV_FIRST_FOLD_FLOATS
@@ -59,6 +59,9 @@ TRAIN_LOSS_SYMBOLS = ('pwv_train_loss_workspace_bytes', 'pwv_train_loss_f32')
 # ... and of include/pwv_hip_train_varlen.h: training on packed batches of mixed-length utterances, and their loss head
 TRAIN_VARLEN_SYMBOLS = ('pwv_train_varlen_front_fwd_f32', 'pwv_train_varlen_layer_fwd_f32', 'pwv_train_varlen_layer_bwd_f32',
                         'pwv_train_varlen_front_bwd_f32', 'pwv_train_loss_varlen_workspace_bytes', 'pwv_train_loss_varlen_f32')
+# ... and of include/pwv_hip_train_cond.h: the layer kernels of training with a per-sample (transposed-conv) condition
+TRAIN_COND_SYMBOLS = ('pwv_train_cond_workspace_bytes', 'pwv_train_cond_layer_fwd_f32', 'pwv_train_cond_layer_bwd_f32')
+TRAIN_COND_MAX = 96           # PWV_TRAIN_COND_MAX: condition channels the per-sample layer kernels take
 
 
 class PwvError(RuntimeError):
@@ -410,6 +413,19 @@ class TrainVarlenArgs(Structure):
         self.struct_size = ctypes.sizeof(TrainVarlenArgs)
 
 
+class TrainCondArgs(Structure):
+    """pwv_train_cond_args: one layer call of training with a per-sample condition (include/pwv_hip_train_cond.h): the embedded
+    pwv_train_args (its fields flat here, at the same offsets), then the condition."""
+    _fields_ = (TrainArgs._fields_
+                + [(n, c_void_p) for n in ('cond', 'gc_filter', 'gc_gate', 'filter_bias', 'gate_bias', 'd_cond', 'd_gc_filter', 'd_gc_gate',
+                                           'd_filter_bias', 'd_gate_bias')]
+                + [(n, ctypes.c_int32) for n in ('cond_channels', 'cond_row_stride', 'cond_utt_rows', 'd_cond_accumulate')])
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = ctypes.sizeof(TrainCondArgs)
+
+
 class TrainLossVarlenArgs(Structure):
     """pwv_train_loss_varlen_args: the loss terms of a packed batch and their gradient for the prediction
     (include/pwv_hip_train_varlen.h)."""
@@ -595,6 +611,10 @@ def _declare(lib):
     lib.pwv_train_loss_varlen_workspace_bytes.restype = c_size_t
     lib.pwv_train_loss_varlen_workspace_bytes.argtypes = [POINTER(TrainLossVarlenArgs)]
     lib.pwv_train_loss_varlen_f32.argtypes = [POINTER(TrainLossVarlenArgs), c_void_p]
+    lib.pwv_train_cond_workspace_bytes.restype = c_size_t
+    lib.pwv_train_cond_workspace_bytes.argtypes = [POINTER(TrainCondArgs)]
+    for name in TRAIN_COND_SYMBOLS[1:]:
+        getattr(lib, name).argtypes = [POINTER(TrainCondArgs), c_void_p]
     lib.pwv_instance_norm_workspace_bytes.restype = c_size_t
     lib.pwv_instance_norm_workspace_bytes.argtypes = [c_int, c_int, c_int]
     lib.pwv_instance_norm_f32.argtypes = [f32p, f32p, c_int, c_int, c_int, f32p, f32p, ctypes.c_float, c_void_p, c_size_t, c_void_p]
@@ -616,7 +636,7 @@ def _declare(lib):
     lib.pwv_status_words_alloc.argtypes = [POINTER(c_void_p)]
     lib.pwv_status_words_free.argtypes = [c_void_p]
     lib.pwv_range_check_f32.argtypes = [f32p, c_int64, ctypes.c_float, c_void_p, c_void_p]
-    for name in EXPORTED_SYMBOLS + EXTENSION_SYMBOLS + LIVE_TICK_SYMBOLS + SCORE_SYMBOLS + TRAIN_SYMBOLS + TRAIN_LOSS_SYMBOLS + TRAIN_VARLEN_SYMBOLS:      # fails loudly (AttributeError) if a symbol is missing
+    for name in EXPORTED_SYMBOLS + EXTENSION_SYMBOLS + LIVE_TICK_SYMBOLS + SCORE_SYMBOLS + TRAIN_SYMBOLS + TRAIN_LOSS_SYMBOLS + TRAIN_VARLEN_SYMBOLS + TRAIN_COND_SYMBOLS:      # fails loudly (AttributeError) if a symbol is missing
         getattr(lib, name)
     return lib
 

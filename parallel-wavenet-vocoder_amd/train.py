@@ -7,14 +7,22 @@ DESIGN.md section 9, "Training".
 
 Scope: what hparams/default.yaml trains -- filter_width 2, R = D = 64, S = 128, 'repeat' conditioning, no normalisers, no skip
 accumulation, separate scaler and shifter nets, exact-fp32 arithmetic; uniform [N, T] batches (loss_and_grad) or packed batches of
-utterances of different lengths, unpadded (loss_and_grad_varlen, `--varlen`).  Everything else is refused with a PwvError that names
-the reason (`refusal`); nothing falls back to another implementation.
+utterances of different lengths, unpadded (loss_and_grad_varlen, `--varlen`).  And the reference's second architecture,
+cond_upsample_method 'transposed_conv' (models.py:109-124; hparams test/tran): uniform batches at hop_length 80 = 4 * 4 * 5, an even
+condition_channels <= 96, no normalised conditioning.  Everything else is refused with a PwvError that names the reason (`refusal`);
+nothing falls back to another implementation.
 
 Division of work.  Sample rate (the hot path): HIP kernels, one net per call -- the forward keeps every layer's input and the last
 layer's gated output, the backward recomputes F, G, o and the head's hidden layers from them.  Frame rate: the conditioning dense +
 ReLU and the projections P = frames [gc_filter | gc_gate] + [filter_bias | gate_bias] of all net-layers as ONE matrix product, both on
 the project's exact-fp32 GEMM (pwv_linear_f32: a row of P does not depend on the rows next to it); in torch (plumbing) their backward
 from the dP the kernels leave, the flow's affine out = in * s + b and the loss.
+
+Transposed-conv conditioning.  The condition changes every sample, so there is no P: the layer kernels of
+include/pwv_hip_train_cond.h form c[t] [gc_filter | gc_gate] + biases, the gradients of gc_* and of the biases, and d_cond inside the
+unit.  The three stride-4/4/5 stages run as linear_op(..., relu) on the re-laid-out [Cin, s C] weights (as models._condition does) and
+keep their outputs; the kernels read the last stage's UNCROPPED output through a row offset (no crop), add every net-layer's d_cond
+into one buffer of the same shape whose margins stay zero (the crop's adjoint), and torch takes that back through the stages.
 """
 from __future__ import annotations
 
@@ -36,6 +44,7 @@ from .variables import EMA_SUFFIX, get_default_store, variable_scope
 SCOPE = 'iaf_vocoder'
 ADAM_BETA1 = 0.9            # tf.train.AdamOptimizer's defaults (models.py:101-103 sets the learning rate and beta2 only)
 ADAM_EPS = 1e-8
+TCONV_STRIDES = (4, 4, 5)   # models.py:109-124: the strides of the three transposed convolutions; their product is the hop
 
 
 # ---- what is refused ----------------------------------------------------------------------------------------------------------------
@@ -45,8 +54,19 @@ def refusal(model=None, wav=None, melspec=None, power_weight=None, packed=False)
     and then hparams that ask for a power loss are refused instead of being trained without it.  `packed`: the caller is
     loss_and_grad_varlen, which takes its lengths from the utterances and not from the model."""
     m = hp.model
-    if m.cond_upsample_method != 'repeat':
-        return "cond_upsample_method %r: only 'repeat' conditioning is differentiated (transposed-conv conditioning is not)" % m.cond_upsample_method
+    if m.cond_upsample_method == 'transposed_conv':
+        what = "cond_upsample_method 'transposed_conv': transposed-conv conditioning is differentiated "
+        hop, C = int(hp.signal.hop_length), int(m.condition_channels)
+        if hop != int(np.prod(TCONV_STRIDES)):
+            return what + 'at hop_length 80 only, not at hop_length %d: the strides %s multiply to %d' % (hop, TCONV_STRIDES, int(np.prod(TCONV_STRIDES)))
+        if m.get('normalize_cond'):
+            return what + 'without normalisers only, not with normalize_cond %r' % m.normalize_cond
+        if C < 2 or C % 2 or C > _lib.TRAIN_COND_MAX:
+            return what + 'for an even condition_channels of 2 .. %d, not %d (the per-sample layer kernels)' % (_lib.TRAIN_COND_MAX, C)
+        if packed or any(isinstance(t, (list, tuple)) for t in (wav, melspec)):
+            return what + 'on uniform [N, T] batches only: per-sample conditioning is not packed (generate_varlen pads such batches too)'
+    elif m.cond_upsample_method != 'repeat':
+        return "cond_upsample_method %r: only 'repeat' and 'transposed_conv' conditioning are differentiated" % m.cond_upsample_method
     if m.get('normalize_cond'):
         return 'normalize_cond %r: normalised conditioning is not differentiated' % m.normalize_cond
     if m.get('normalize_wavenet'):
@@ -117,6 +137,18 @@ def cond_dense(store):
     return store.get_variable(SCOPE + '/cond/dense', [1, hp.signal.n_mels, hp.model.condition_channels])
 
 
+def cond_tconv(store):
+    """The three transposed-conv weights, TF layout [1, stride, C, Cin] (models.py:113-116)."""
+    C = hp.model.condition_channels
+    return [store.get_variable(SCOPE + '/cond/transposed_conv_%d_weights' % i, [1, s, C, C if i else hp.signal.n_mels])
+            for i, s in enumerate(TCONV_STRIDES)]
+
+
+def cond_variables(store):
+    """The variables of the conditioning the hparams choose (created if the store lacks them)."""
+    return cond_tconv(store) if hp.model.cond_upsample_method == 'transposed_conv' else [cond_dense(store)]
+
+
 def trainable_names(store) -> List[str]:
     return sorted(store.trainable_variables(SCOPE))
 
@@ -154,9 +186,24 @@ class _Geometry(object):
 
     head_args = args                        # the head is row-independent: the same call for either geometry
 
+    def layer_args(self, **kw):
+        """The layers' struct: the front's, but for a per-sample condition."""
+        return self.args(**kw)
+
     def entry(self, kind):
         """The entry point of 'front_fwd', 'layer_fwd', 'layer_bwd' or 'front_bwd' for this geometry."""
         return 'pwv_train_%s_f32' % kind
+
+    def workspace_bytes(self):
+        return _lib.lib().pwv_train_workspace_bytes(ctypes.byref(self.head_args())), 'pwv_train_workspace_bytes'
+
+    def cond_fwd(self, net, j, v):
+        """What a layer's forward call reads of the conditioning: this layer's 128 columns of P."""
+        return dict(proj=self.P[0, net.col + 128 * j:])
+
+    def cond_bwd(self, net, j, v, dP, g, opt):
+        """... and its backward call: P, and the dP slots it fills."""
+        return dict(proj=self.P[0, net.col + 128 * j:], d_proj=dP[0, net.col + 128 * j:])
 
 
 class _PackedGeometry(_Geometry):
@@ -180,7 +227,45 @@ class _PackedGeometry(_Geometry):
         return 'pwv_train_varlen_%s_f32' % kind
 
 
-def _net_forward(net: _Net, geo: _Geometry, xin, P):
+class _CondGeometry(_Geometry):
+    """A uniform batch with a per-sample condition (include/pwv_hip_train_cond.h): the layer calls read `cond`, the uncropped
+    [N, T + hop, C] output of the last transposed-conv stage, through a row offset of hop / 2, and add to `d_cond` of the same shape
+    (zeros to begin with: its margins are the crop's adjoint).  The front, the head and the loss are the uniform ones."""
+
+    def __init__(self, N, T, t_mel, C, max_workgroups):
+        super().__init__(N, T, t_mel, 0, max_workgroups)
+        self.C = C
+        self.cond = self.d_cond = None
+        self.started = 0                    # the first layer backward of a step writes its rows of d_cond, the others add
+
+    def set_cond(self, cond):
+        assert tuple(cond.shape) == (self.N, self.T + self.hop, self.C) and cond.is_contiguous()
+        self.cond, self.d_cond, self.started = cond, torch.zeros_like(cond), 0
+
+    def layer_args(self, **kw):
+        skip = self.off * self.C * 4        # bytes to sample 0 of utterance 0
+        return self._fill(_lib.TrainCondArgs(N=self.N, T=self.T, max_workgroups=self.max_workgroups, dilation=1, next_dilation=1,
+                                             cond=self.cond.data_ptr() + skip, d_cond=self.d_cond.data_ptr() + skip, cond_channels=self.C,
+                                             cond_row_stride=self.C, cond_utt_rows=self.T + self.hop), kw)
+
+    def entry(self, kind):
+        return 'pwv_train_cond_%s_f32' % kind if kind.startswith('layer') else 'pwv_train_%s_f32' % kind
+
+    def workspace_bytes(self):
+        return _lib.lib().pwv_train_cond_workspace_bytes(ctypes.byref(self.layer_args())), 'pwv_train_cond_workspace_bytes'
+
+    def cond_fwd(self, net, j, v):
+        return dict(gc_filter=v['gc_filter'], gc_gate=v['gc_gate'], filter_bias=v.get('filter_bias'), gate_bias=v.get('gate_bias'))
+
+    def cond_bwd(self, net, j, v, dP, g, opt):
+        kw = dict(self.cond_fwd(net, j, v), d_gc_filter=g(net.name(j, 'gc_filter'), v['gc_filter']),
+                  d_gc_gate=g(net.name(j, 'gc_gate'), v['gc_gate']), d_filter_bias=opt(v, 'filter_bias', net.name(j, 'filter_bias')),
+                  d_gate_bias=opt(v, 'gate_bias', net.name(j, 'gate_bias')), d_cond_accumulate=self.started)
+        self.started = 1
+        return kw
+
+
+def _net_forward(net: _Net, geo: _Geometry, xin):
     """x_j for every layer, the last layer's o and the net's output y [rows]."""
     dev, L = xin.device, len(net.dilations)
     xs = [_tile32(geo.rows, dev) for _ in range(L)]
@@ -188,9 +273,9 @@ def _net_forward(net: _Net, geo: _Geometry, xin, P):
     _call(geo.entry('front_fwd'), geo.args(in_=xin, causal_filter=net.cf, x_out=xs[0]))
     for j, d in enumerate(net.dilations):
         v, last = net.layers[j], j == L - 1
-        _call(geo.entry('layer_fwd'), geo.args(form=_lib.TRAIN_LAST if last else _lib.TRAIN_RESIDUAL, dilation=d, x=xs[j],
-                                                 proj=P[0, net.col + 128 * j:], filter=v['filter'], gate=v['gate'], dense=v['dense'],
-                                                 dense_bias=v.get('dense_bias'), x_out=o if last else xs[j + 1]))
+        _call(geo.entry('layer_fwd'), geo.layer_args(form=_lib.TRAIN_LAST if last else _lib.TRAIN_RESIDUAL, dilation=d, x=xs[j],
+                                                       filter=v['filter'], gate=v['gate'], dense=v['dense'], dense_bias=v.get('dense_bias'),
+                                                       x_out=o if last else xs[j + 1], **geo.cond_fwd(net, j, v)))
     h, lv = net.head, net.layers[-1]
     _call('pwv_train_head_fwd_f32', geo.head_args(x=o, skip=lv['skip'], skip_bias=lv.get('skip_bias'), post1=h['postprocess1'],
                                             post1_bias=h.get('postprocess1_bias'), post2=h['postprocess2'],
@@ -218,11 +303,11 @@ def _net_backward(net: _Net, geo: _Geometry, saved, xin, d_out, d_mul, scale, d_
     for j in range(L - 1, -1, -1):
         v, last = net.layers[j], j == L - 1
         u_next, v_next = (None, None) if last else uv[(j + 1) & 1]
-        _call(geo.entry('layer_bwd'), geo.args(
+        _call(geo.entry('layer_bwd'), geo.layer_args(
             form=_lib.TRAIN_LAST if last else _lib.TRAIN_RESIDUAL, dilation=net.dilations[j],
-            next_dilation=1 if last else net.dilations[j + 1], x=xs[j], proj=geo.P[0, net.col + 128 * j:],
+            next_dilation=1 if last else net.dilations[j + 1], x=xs[j],
             filter=v['filter'], gate=v['gate'], dense=v['dense'], u_next=u_next, v_next=v_next, d_o=d_o if last else None,
-            u=uv[j & 1][0], v=uv[j & 1][1], d_proj=dP[0, net.col + 128 * j:],
+            u=uv[j & 1][0], v=uv[j & 1][1], **geo.cond_bwd(net, j, v, dP, g, opt),
             d_filter=g(net.name(j, 'filter'), v['filter']), d_gate=g(net.name(j, 'gate'), v['gate']),
             d_dense=None if last else g(net.name(j, 'dense'), v['dense']),
             d_dense_bias=None if last else opt(v, 'dense_bias', net.name(j, 'dense_bias')),
@@ -288,7 +373,10 @@ def loss_and_grad(model, wav, melspec, z=None, seed=None, max_workgroups: int = 
             raise ValueError('z must be [%d, %d, 1], got %s' % (N, T, tuple(noise.shape)))
     flows = model_nets(model, store)
     cols = sum(128 * len(net.dilations) for pair in flows for net in pair)
-    geo = _Geometry(N, T, t_mel, cols, int(max_workgroups))
+    if hp.model.cond_upsample_method == 'transposed_conv':
+        geo = _CondGeometry(N, T, t_mel, int(hp.model.condition_channels), int(max_workgroups))
+    else:
+        geo = _Geometry(N, T, t_mel, cols, int(max_workgroups))
 
     def head(x, y):
         if power_weight is None:
@@ -304,14 +392,43 @@ def loss_and_grad(model, wav, melspec, z=None, seed=None, max_workgroups: int = 
     return loss, x.reshape(N, T, 1), grads
 
 
+def _tconv_forward(store, mel2, C):
+    """The three transposed convolutions of models.py:109-124 on the frames `mel2` [M, n_mels], kernel width == stride:
+    out[t s + j, co] = sum_ci in[t, ci] w[0, j, co, ci], a GEMM on the re-laid-out [Cin, s C] weight, + ReLU (as models._condition runs
+    them, on the project's row-independent exact-fp32 GEMM).  Returns [(input [rows, Cin], weight [Cin, s C], output [rows, s C])] per
+    stage, kept for the backward; the last output, seen as [M * 80, C], is the uncropped condition."""
+    from . import engine
+    stages, cur = [], mel2
+    for w, stride in zip(cond_tconv(store), TCONV_STRIDES):
+        wmat = w[0].permute(2, 0, 1).reshape(w.shape[3], stride * C).contiguous()
+        out = engine.linear_op(cur, wmat, None, True, 'f32')
+        stages.append((cur, wmat, out))
+        cur = out.reshape(-1, C)
+    return stages
+
+
+def _tconv_backward(stages, d_cond, grads):
+    """d_cond (the shape of the uncropped condition; zero margins: the crop's adjoint) back through the stages, in torch: per stage
+    d_pre = d_out * (out > 0), dW = in^T d_pre -- into `grads` in the TF layout [1, s, C, Cin] --, d_in = d_pre Wmat^T."""
+    C = d_cond.shape[-1]
+    d = d_cond.reshape(-1, C)
+    for i in range(len(stages) - 1, -1, -1):
+        cur, wmat, out = stages[i]
+        d_pre = d.reshape(out.shape) * (out > 0).to(torch.float32)
+        dw = cur.t() @ d_pre                                                                                             # [Cin, s C]
+        grads[SCOPE + '/cond/transposed_conv_%d_weights' % i] = dw.reshape(wmat.shape[0], TCONV_STRIDES[i], C).permute(1, 2, 0).unsqueeze(0).contiguous()
+        if i > 0:
+            d = d_pre @ wmat.t()
+
+
 def _forward_backward(store, flows, geo, mel2, x, y, head):
     """What a uniform and a packed batch share: `mel2` [M, n_mels] the frames of the batch row after row, `x` [rows] the noise, `y`
     [rows] the ground truth, `geo` the geometry of the kernels' calls, `head(pred, y)` -> (loss, d_out [rows]).  Returns (loss, pred
     [rows], grads)."""
     dev = mel2.device
-    dense = cond_dense(store)
     nets = [net for pair in flows for net in pair]
     cols = geo.cols
+    per_sample = isinstance(geo, _CondGeometry)
 
     # frame rate, forward: frames = relu(mel dense); P = frames [gc_filter | gc_gate] + [filter_bias | gate_bias] for every net-layer.
     # Both products run on the project's exact-fp32 GEMM (pwv_linear_f32), whose sum over K has one order whatever the number of rows:
@@ -320,19 +437,24 @@ def _forward_backward(store, flows, geo, mel2, x, y, head):
     from . import engine
     zeros64 = torch.zeros(64, dtype=torch.float32, device=dev)
     mel2 = mel2.contiguous()
-    frames = engine.linear_op(mel2, dense[0].contiguous(), None, True, 'f32')
-    bank_w = torch.cat([v[k][0] for net in nets for v in net.layers for k in ('gc_filter', 'gc_gate')], dim=1)          # [C, cols]
-    bank_b = torch.cat([v.get(k, zeros64) for net in nets for v in net.layers for k in ('filter_bias', 'gate_bias')])
-    geo.P = engine.linear_op(frames, bank_w, bank_b, False, 'f32')                                                     # [M, cols]
+    if per_sample:
+        stages = _tconv_forward(store, mel2, geo.C)
+        geo.set_cond(stages[-1][2].reshape(geo.N, geo.T + geo.hop, geo.C))          # uncropped: the kernels skip hop / 2 rows themselves
+    else:
+        dense = cond_dense(store)
+        frames = engine.linear_op(mel2, dense[0].contiguous(), None, True, 'f32')
+        bank_w = torch.cat([v[k][0] for net in nets for v in net.layers for k in ('gc_filter', 'gc_gate')], dim=1)          # [C, cols]
+        bank_b = torch.cat([v.get(k, zeros64) for net in nets for v in net.layers for k in ('filter_bias', 'gate_bias')])
+        geo.P = engine.linear_op(frames, bank_w, bank_b, False, 'f32')                                                     # [M, cols]
 
     # sample rate, forward
-    ws_bytes = _lib.lib().pwv_train_workspace_bytes(ctypes.byref(geo.head_args()))
+    ws_bytes, ws_name = geo.workspace_bytes()
     if not ws_bytes:
-        _lib.check(-1, 'pwv_train_workspace_bytes')
+        _lib.check(-1, ws_name)
     ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=dev)
     saved = []
     for pair in flows:
-        s = [_net_forward(net, geo, x, geo.P) for net in pair]
+        s = [_net_forward(net, geo, x) for net in pair]
         saved.append((x, s))
         x = x * s[0][2] + s[1][2]                                                       # modules.py:59
     loss, d_out = head(x, y)
@@ -340,13 +462,18 @@ def _forward_backward(store, flows, geo, mel2, x, y, head):
     # sample rate, backward
     grads: Dict[str, torch.Tensor] = {}
     M = mel2.shape[0]
-    dP = torch.zeros((M * geo.kmax, cols), dtype=torch.float32, device=dev)               # K slots per P row (include/pwv_hip_train.h)
+    # K slots per P row (include/pwv_hip_train.h); a per-sample condition has no P: its layers add to geo.d_cond instead
+    dP = None if per_sample else torch.zeros((M * geo.kmax, cols), dtype=torch.float32, device=dev)
     for i in range(len(flows) - 1, -1, -1):
         xin, s = saved[i]
         d_in = torch.empty_like(xin) if i > 0 else None
         _net_backward(flows[i][0], geo, s[0], xin, d_out, xin, s[0][2], d_in, False, dP, ws, grads)      # ds = d out * in
         _net_backward(flows[i][1], geo, s[1], xin, d_out, None, None, d_in, True, dP, ws, grads)         # db = d out
         d_out = d_in
+
+    if per_sample:       # (the gradients of gc_* and of the biases came straight from the kernels)
+        _tconv_backward(stages, geo.d_cond, grads)
+        return _fill_unread(store, grads, loss, x)
 
     # frame rate, backward
     dPs = dP.reshape(M, geo.kmax, cols).sum(dim=1)
@@ -364,6 +491,10 @@ def _forward_backward(store, flows, geo, mel2, x, y, head):
             if 'filter_bias' in v:
                 grads[net.name(j, 'filter_bias')], grads[net.name(j, 'gate_bias')] = gb[i], gb[i + 1]
             i += 2
+    return _fill_unread(store, grads, loss, x)
+
+
+def _fill_unread(store, grads, loss, x):
     for name in trainable_names(store):                 # what the model never reads
         if name not in grads:
             grads[name] = torch.zeros_like(store.vars[name])
@@ -527,7 +658,7 @@ class Trainer(object):
             raise PwvError('training refused: ' + why)
         if self.names is None:
             model_nets(self.model, self.store)
-            cond_dense(self.store)
+            cond_variables(self.store)
             self.names = trainable_names(self.store)
         return [self.store.vars[n] for n in self.names]
 

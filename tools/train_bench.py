@@ -29,6 +29,14 @@ ALTERNATING call by call in one run, same model and z:
 Writes profiles/train_varlen_bench.json.
 
     python tools/train_bench.py --varlen [--steps 20] [--warmup 3]
+
+--tran measures training of the transposed-conv conditioning (DESIGN.md section 9, "Training the transposed-conv conditioning";
+include/pwv_hip_train_cond.h) against the default 'repeat' conditioning: the default model at 8 x 4000 with either conditioning, same
+mel, z and wav, the two loss_and_grad ALTERNATING call by call in one run, and the conditioning stages alone (the three transposed-conv
+GEMMs + ReLU forward, their backward in torch on a fixed d_cond), whose share of the step is reported.  There is no threshold.  Writes
+profiles/train_tran_bench.json.
+
+    python tools/train_bench.py --tran [--steps 20] [--warmup 3]
 """
 import argparse
 import json
@@ -48,10 +56,12 @@ def main():
     ap.add_argument('--length', type=int, default=4000)
     ap.add_argument('--power', action='store_true', help='measure loss_and_grad with and without the STFT power loss instead')
     ap.add_argument('--varlen', action='store_true', help='measure packed batches against uniform and padded ones instead')
+    ap.add_argument('--tran', action='store_true', help='measure transposed-conv conditioning against repeat conditioning instead')
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
     if args.out is None:
-        name = 'train_power_bench.json' if args.power else 'train_varlen_bench.json' if args.varlen else 'train_bench.json'
+        name = ('train_power_bench.json' if args.power else 'train_varlen_bench.json' if args.varlen else 'train_tran_bench.json' if args.tran
+                else 'train_bench.json')
         args.out = os.path.join(ROOT, 'profiles', name)
     steps, warmup = max(args.steps, 20), max(args.warmup, 3)
 
@@ -100,7 +110,7 @@ def main():
         geo.P = train_forward.P
         x = z.reshape(-1)
         for pair in flows:
-            s = [TR._net_forward(net, geo, x, geo.P) for net in pair]
+            s = [TR._net_forward(net, geo, x) for net in pair]
             x = x * s[0][2] + s[1][2]
 
     cols = 128 * 2 * sum(len(d) for d in cfg.dilations)
@@ -110,6 +120,8 @@ def main():
         return power_legs(args, TR, model, wav, mel, z, steps, warmup)
     if args.varlen:
         return varlen_legs(args, TR, O, cfg, store, model, wav, mel, z, steps, warmup)
+    if args.tran:
+        return tran_legs(args, TR, O, cfg, store, model, wav, mel, z, steps, warmup)
 
     legs = {}
     legs['forward_f32'] = timed(forward)
@@ -243,6 +255,60 @@ def varlen_legs(args, TR, O, cfg, store, model, wav, mel, z, steps, warmup):
     out['paired_b_minus_a_ms'] = {'median': round(statistics.median(b - a for a, b in zip(ms['a_uniform_8x4000'], ms['b_packed_equal'])), 3)}
     out['d_over_c'] = round(med['d_uniform_padded_mixed'] / med['c_packed_mixed'], 4)
     out['rows_padded_over_packed'] = round(n * longest / float(sum(MIXED)), 4)
+    with open(args.out, 'w') as f:
+        json.dump(out, f, indent=1)
+        f.write('\n')
+    print(json.dumps(out))
+
+
+def tran_legs(args, TR, O, cfg, store, model, wav, mel, z, steps, warmup):
+    import torch
+    from pwv_amd.models import IAFVocoder
+    from pwv_amd.variables import VariableStore
+    from tests.util import set_hparams
+    dev = wav.device
+    n, length = args.batch, args.length
+    tcfg = O.ModelConfig(cond_upsample_method='transposed_conv')
+    set_hparams(tcfg)
+    tstore = VariableStore(device=dev)
+    tstore.load_dict(O.init_weights(tcfg, seed=2))
+    tmodel = IAFVocoder(batch_size=n, length=length, store=tstore, precision='f32')
+
+    def once(fn):
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+
+    # the conditioning stages alone, on a fixed d_cond of the condition's shape
+    mel2 = mel.reshape(-1, mel.shape[2]).contiguous()
+    C = tcfg.condition_channels
+    stages = TR._tconv_forward(tstore, mel2, C)
+    d_cond = torch.randn(n, length + tcfg.hop_length, C, device=dev)
+    variants = {'repeat': (cfg, lambda: TR.loss_and_grad(model, wav, mel, z=z)),
+                'transposed_conv': (tcfg, lambda: TR.loss_and_grad(tmodel, wav, mel, z=z)),
+                'cond_stages_forward': (tcfg, lambda: TR._tconv_forward(tstore, mel2, C)),
+                'cond_stages_backward': (tcfg, lambda: TR._tconv_backward(stages, d_cond, {}))}
+    ms = {k: [] for k in variants}
+    for k in range(warmup + steps):
+        for name, (c, fn) in variants.items():            # alternating: A B C D A B C D ...
+            set_hparams(c)                                  # (outside the timed window)
+            t = once(fn)
+            if k >= warmup:
+                ms[name].append(t)
+    set_hparams(cfg)
+    out = {'model': 'default (4 flows, 10 + 10 + 10 + 30 layers, 2 nets each)', 'batch': n, 'length': length, 'steps': steps, 'warmup': warmup,
+           'device': torch.cuda.get_device_name(0), 'condition_channels': C, 'peak_allocated_MiB': round(torch.cuda.max_memory_allocated() / 2 ** 20, 1)}
+    for k, v in ms.items():
+        key = 'loss_and_grad_%s_ms' % k if k in ('repeat', 'transposed_conv') else k + '_ms'
+        out[key] = {'median': round(statistics.median(v), 3), 'min': round(min(v), 3), 'max': round(max(v), 3)}
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    out['transposed_over_repeat'] = round(med['transposed_conv'] / med['repeat'], 4)
+    out['paired_ratio'] = {'median': round(statistics.median(b / a for a, b in zip(ms['repeat'], ms['transposed_conv'])), 4)}
+    out['cond_stages_share'] = round((med['cond_stages_forward'] + med['cond_stages_backward']) / med['transposed_conv'], 4)
     with open(args.out, 'w') as f:
         json.dump(out, f, indent=1)
         f.write('\n')
