@@ -74,7 +74,8 @@ class VariableStore:
         t = torch.as_tensor(np.asarray(value), dtype=torch.float32)
         if name in self.vars and tuple(self.vars[name].shape) != tuple(t.shape):
             raise ValueError('shape mismatch for %s: %s vs %s' % (name, tuple(self.vars[name].shape), tuple(t.shape)))
-        self.vars[name] = t.to(self.device).contiguous()
+        # a copy of its own, on a CPU store too: a training step updates the variables in place, and must not write into the caller's array
+        self.vars[name] = t.to(self.device, copy=True).contiguous()
         self.version += 1
 
     def load_dict(self, weights: Dict[str, np.ndarray], use_ema: bool = False, strict: bool = False) -> int:

@@ -32,12 +32,14 @@ def _dev(a, device):
     return torch.from_numpy(np.ascontiguousarray(a)).to(device)
 
 
-def _layer_backward(c, last, device, g=None, max_workgroups=0):
-    """The layer backward (and, in the last form, the head backward in front of it) on one net; returns float64 numpy: the input
-    gradient assembled with its look-ahead, dP with its slots added, every weight and bias gradient."""
+def _layer_backward(c, last, device, g=None, max_workgroups=0, next_dilation=1, v_next=None):
+    """The layer backward (and, in the last form, the head backward in front of it) on one net, at the shape of the case `c`; returns
+    float64 numpy: the input gradient assembled with its look-ahead, dP with its slots added, every weight and bias gradient.  The
+    residual form takes the gradient for its output as the layer above would leave it: U = g (default: c['g']) and V = v_next
+    [N, T, 64] (default: zeros), gathered with next_dilation."""
     from pwv_amd import _lib
     lib = _lib.lib()
-    N, T, d, hop, frames = TO.N, TO.T, c['d'], c['hop'], c['frames']
+    N, T, d, hop, frames = c['N'], c['T'], c['d'], c['hop'], c['frames']
     rows = N * T
     kmax = (hop + 30) // 32 + 1
     t = {k: _dev(c[k], device) for k in ('P', 'filter', 'gate', 'dense', 'dense_bias', 'skip', 'skip_bias', 'post1', 'post1_bias', 'post2', 'post2_bias', 'dy')}
@@ -46,8 +48,8 @@ def _layer_backward(c, last, device, g=None, max_workgroups=0):
     tile = lambda: nan(((rows + 31) // 32) * 32 * 64)
     u, v = tile(), tile()
     dP = torch.zeros((N * frames * kmax, 128), dtype=torch.float32, device=device)
-    base = dict(N=N, T=T, cond_hop=hop, cond_offset=hop // 2, cond_frames=frames, proj_row_stride=128, d_proj_row_stride=128,
-                max_workgroups=max_workgroups, dilation=d, next_dilation=1)
+    base = dict(N=N, T=T, cond_hop=hop, cond_offset=c['offset'], cond_frames=frames, proj_row_stride=128, d_proj_row_stride=128,
+                max_workgroups=max_workgroups, dilation=d, next_dilation=next_dilation)
     ws = nan(lib.pwv_train_workspace_bytes(ctypes.byref(_lib.TrainArgs(**base))) // 4)
     assert ws.numel() > 0
     out = {k: nan(*c[k].shape) for k in (TO.LAYER_LAST if last else TO.LAYER_RESIDUAL) if k not in ('x', 'P')}
@@ -67,9 +69,9 @@ def _layer_backward(c, last, device, g=None, max_workgroups=0):
         _lib.check(lib.pwv_train_head_bwd_f32(ctypes.byref(a), stream), 'head_bwd')
         a = _lib.TrainArgs(form=_lib.TRAIN_LAST, d_o=ptr(d_o), **common)
     else:
-        # the gradient for the layer's output as the layer above would leave it: U = g, V = 0, taken with next_dilation 1
+        # the gradient for the layer's output as the layer above would leave it: U = g, V = 0 unless given
         gu = _dev(TO.to_tile32((c['g'] if g is None else g).reshape(rows, 64)), device)
-        gv = torch.zeros_like(gu)
+        gv = torch.zeros_like(gu) if v_next is None else _dev(TO.to_tile32(v_next.reshape(rows, 64)), device)
         a = _lib.TrainArgs(form=_lib.TRAIN_RESIDUAL, dense=ptr(t['dense']), u_next=ptr(gu), v_next=ptr(gv), d_dense=ptr(out['dense']),
                            d_dense_bias=ptr(out['dense_bias']), **common)
     _lib.check(lib.pwv_train_layer_bwd_f32(ctypes.byref(a), stream), 'layer_bwd')

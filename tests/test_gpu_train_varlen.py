@@ -35,9 +35,10 @@ def _dev(a, device):
 
 
 # ---- one layer through ctypes ---------------------------------------------------------------------------------------------------------
-def _layer_backward(c, last, device, g=None, max_workgroups=0):
+def _layer_backward(c, last, device, g=None, max_workgroups=0, next_dilation=1, v_next=None):
     """The packed layer backward (and, in the last form, the head backward in front of it); returns float64 numpy: the input gradient
-    assembled with its look-ahead per utterance, dP with its slots added, every weight and bias gradient, and the raw U, V."""
+    assembled with its look-ahead per utterance, dP with its slots added, every weight and bias gradient, and the raw U, V.  The residual
+    form takes U = g (default: c['g']) and V = v_next [rows, 64] (default: zeros), gathered with next_dilation."""
     from pwv_amd import _lib
     lib = _lib.lib()
     d, hop, lengths, cu_rows, cu_frames = c['d'], c['hop'], c['lengths'], c['cu_rows'], c['cu_frames']
@@ -53,7 +54,7 @@ def _layer_backward(c, last, device, g=None, max_workgroups=0):
     ptr = lambda a: a.data_ptr()
     flat = dict(N=1, T=rows, max_workgroups=max_workgroups)
     base = dict(cond_hop=hop, cond_offset=hop // 2, proj_row_stride=128, d_proj_row_stride=128, max_workgroups=max_workgroups, dilation=d,
-                next_dilation=1, cu_rows=ptr(cu_r), cu_frames=ptr(cu_f), n=n, rows=rows, proj_rows=prows)
+                next_dilation=next_dilation, cu_rows=ptr(cu_r), cu_frames=ptr(cu_f), n=n, rows=rows, proj_rows=prows)
     ws = nan(lib.pwv_train_workspace_bytes(ctypes.byref(_lib.TrainArgs(**flat))) // 4)
     assert ws.numel() > 0
     out = {k: nan(*c[k].shape) for k in (TO.LAYER_LAST if last else TO.LAYER_RESIDUAL) if k not in ('x', 'P')}
@@ -72,9 +73,9 @@ def _layer_backward(c, last, device, g=None, max_workgroups=0):
         _lib.check(lib.pwv_train_head_bwd_f32(ctypes.byref(a), stream), 'head_bwd')
         a = _lib.TrainVarlenArgs(form=_lib.TRAIN_LAST, d_o=ptr(d_o), **common)
     else:
-        # the gradient for the layer's output as the layer above would leave it: U = g, V = 0, taken with next_dilation 1
+        # the gradient for the layer's output as the layer above would leave it: U = g, V = 0 unless given
         gu = _dev(TO.to_tile32(c['g'] if g is None else g), device)
-        gv = torch.zeros_like(gu)
+        gv = torch.zeros_like(gu) if v_next is None else _dev(TO.to_tile32(v_next), device)
         a = _lib.TrainVarlenArgs(form=_lib.TRAIN_RESIDUAL, dense=ptr(t['dense']), u_next=ptr(gu), v_next=ptr(gv), d_dense=ptr(out['dense']),
                                  d_dense_bias=ptr(out['dense_bias']), **common)
     _lib.check(lib.pwv_train_varlen_layer_bwd_f32(ctypes.byref(a), stream), 'varlen layer_bwd')

@@ -9,21 +9,57 @@ import torch
 from oracle import iaf_oracle as O
 from oracle import torch_cpu as TC
 
-N, T = 2, 208
+N, T, HOP = 2, 208, 16
 LR, BETA1, BETA2, EPS, DECAY = 2e-4, 0.9, 0.999, 1e-8, 0.998
+# Conditions on the INPUTS of a model-level problem (not bars): a conditioning pre-activation closer to zero than RELU_MARGIN may fall
+# on either side of the ReLU in a float32 evaluation (tests/train_cond_oracle.py), and a prediction closer to its target than
+# SIGN_MARGIN = 5 x tests.util.TOL_F32 may legitimately give the L1's sign(pred - wav) either value; one flipped ReLU or sign would
+# then decide a comparison of gradients.
+RELU_MARGIN = 1e-6
+SIGN_MARGIN = 1e-4
+WAV_SEED = 5                            # the first wav seed tried; problem() takes the first from here upward that keeps SIGN_MARGIN
 
 
-def small_cfg():
-    return O.ModelConfig(dilations=[[1, 2, 32, 64], [4, 48, 256, 3]], n_iaf=2, hop_length=16)
+def small_cfg(hop=HOP):
+    return O.ModelConfig(dilations=[[1, 2, 32, 64], [4, 48, 256, 3]], n_iaf=2, hop_length=hop)
+
+
+def relu_margin(weights, mel):
+    """The smallest |pre-activation| of the conditioning dense + ReLU in float64."""
+    return float(np.abs(np.asarray(mel, dtype=np.float64) @ weights['iaf_vocoder/cond/dense'][0].astype(np.float64)).min())
+
+
+def pred64(weights, mel, z, cfg):
+    """The model's output in float64, [N, T, 1] numpy."""
+    with torch.no_grad():
+        W = {k: torch.from_numpy(np.ascontiguousarray(v)).double() for k, v in weights.items()}
+        return forward(W, torch.from_numpy(mel).double(), torch.from_numpy(z).double(), cfg).numpy()
+
+
+def draw_wav(pred, first_seed, shapes):
+    """[0.3 randn(shape) float32 from seed first_seed + k + i for the i-th shape] at the first k >= 0 for which every sample keeps
+    |pred - wav| >= SIGN_MARGIN (`pred`: the float64 predictions, one array per shape); asserts the margin it returns with."""
+    for k in range(64):
+        wavs = [(0.3 * np.random.RandomState(first_seed + k + i).randn(*shape)).astype(np.float32) for i, shape in enumerate(shapes)]
+        if min(float(np.abs(p - w).min()) for p, w in zip(pred, wavs)) >= SIGN_MARGIN:
+            break
+    assert min(float(np.abs(p - w).min()) for p, w in zip(pred, wavs)) >= SIGN_MARGIN, 'no wav seed keeps the predictions off their targets'
+    return wavs
+
+
+def problem(N=N, T=T, hop=HOP):
+    """(cfg, weights, mel, z, wav) of the small model on N x T samples at hop length `hop` (the default: 2 x 208 samples, hop 16).  The
+    weights do not depend on the shape.  Asserts RELU_MARGIN and SIGN_MARGIN of the inputs."""
+    return _problem(int(N), int(T), int(hop))
 
 
 @functools.lru_cache(maxsize=None)
-def problem():
-    """(cfg, weights, mel, z, wav) of the small model: 2 x 208 samples, hop 16."""
-    cfg = small_cfg()
+def _problem(N, T, hop):
+    cfg = small_cfg(hop)
     w = O.init_weights(cfg, seed=3)
     mel, z = O.synthetic_inputs(N, T, cfg)
-    wav = (0.3 * np.random.RandomState(5).randn(N, T, 1)).astype(np.float32)
+    assert relu_margin(w, mel) >= RELU_MARGIN, 'a conditioning pre-activation sits on the ReLU: draw another seed'
+    wav, = draw_wav([pred64(w, mel, z, cfg)], WAV_SEED, [(N, T, 1)])
     return cfg, w, mel, z, wav
 
 
@@ -54,11 +90,15 @@ def loss_only(weights, mel, z, wav, cfg):
         return float((pred - torch.from_numpy(wav).double()).abs().mean())
 
 
-@functools.lru_cache(maxsize=None)
-def reference():
-    """{'loss', 'pred', 'g64', 'g32', 'E32'}: float64 and float32 autograd of the small problem; E32 = max over the variables of
+def reference(N=N, T=T, hop=HOP):
+    """{'loss', 'pred', 'g64', 'g32', 'E32'}: float64 and float32 autograd of problem(N, T, hop); E32 = max over the variables of
     max|g32 - g64| / max|g64|."""
-    cfg, w, mel, z, wav = problem()
+    return _reference(int(N), int(T), int(hop))
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(N, T, hop):
+    cfg, w, mel, z, wav = problem(N, T, hop)
     l64, p64, g64 = loss_and_grads(w, mel, z, wav, cfg, torch.float64)
     _, _, g32 = loss_and_grads(w, mel, z, wav, cfg, torch.float32)
     return {'loss': l64, 'pred': p64, 'g64': g64, 'g32': g32, 'E32': max(rel_err(g32[k], v) for k, v in g64.items() if v is not None)}
@@ -116,13 +156,15 @@ def from_tile32(buf, rows, C):
     return np.asarray(buf).reshape(blocks, C // 4, 32, 4).transpose(0, 2, 1, 3).reshape(blocks * 32, C)[:rows]
 
 
-def layer_case(d, seed=11, hop=16):
-    """Inputs of one gated layer on 2 x 208 rows: x [N, T, 64], P [N * frames, 128] (natural column order), the weights in TF
-    layouts, g [N, T, 64] for the residual form and dy [N, T] for the last-layer + head form."""
+def layer_case(d, seed=11, hop=HOP, N=N, T=T, offset=None):
+    """Inputs of one gated layer on N x T rows (the default: 2 x 208): x [N, T, 64], P [N * frames, 128] (natural column order; sample t
+    reads frame (t + offset) // hop, offset = hop // 2 unless given), the weights in TF layouts, g [N, T, 64] for the residual form and
+    dy [N, T] for the last-layer + head form."""
     rng = np.random.RandomState(seed + d)
-    frames = 1 + T // hop
+    offset = hop // 2 if offset is None else offset
+    frames = (T - 1 + offset) // hop + 1
     f32 = lambda a: a.astype(np.float32)
-    c = {'d': d, 'hop': hop, 'frames': frames,
+    c = {'d': d, 'hop': hop, 'frames': frames, 'N': N, 'T': T, 'offset': offset,
          'x': f32(rng.randn(N, T, 64)), 'P': f32(0.5 * rng.randn(N * frames, 128)),
          'filter': f32(0.15 * rng.randn(2, 64, 64)), 'gate': f32(0.15 * rng.randn(2, 64, 64)),
          'dense': f32(0.15 * rng.randn(1, 64, 64)), 'dense_bias': f32(0.1 * rng.randn(64)),
@@ -142,10 +184,10 @@ def layer_grads(c, last, dtype, g=None):
     variables named in LAYER_RESIDUAL / LAYER_LAST; float64 numpy."""
     names = LAYER_LAST if last else LAYER_RESIDUAL
     v = {k: torch.from_numpy(c[k]).to(dtype).requires_grad_(True) for k in names}
-    d, hop = c['d'], c['hop']
+    d, hop, N, T = c['d'], c['hop'], c['N'], c['T']
     x = v['x']
     fg = TC.causal_conv_torch(x, torch.cat([v['filter'], v['gate']], dim=2), d)
-    idx = (torch.arange(T) + hop // 2) // hop
+    idx = (torch.arange(T) + c['offset']) // hop
     fg = fg + v['P'].reshape(N, c['frames'], 128)[:, idx, :]
     o = torch.tanh(fg[..., :64]) * torch.sigmoid(fg[..., 64:])
     if last:
@@ -157,3 +199,69 @@ def layer_grads(c, last, dtype, g=None):
         loss = (out * torch.from_numpy(c['g'] if g is None else g).to(dtype)).sum()
     loss.backward()
     return {k: t.grad.double().numpy() for k, t in v.items()}
+
+
+def look_ahead(U, V, dn, cu_rows):
+    """g[t] = U[t] + V[t + dn] while t + dn is inside the utterance: U, V [rows, C], utterance i = rows cu_rows[i] .. cu_rows[i + 1] - 1."""
+    g = U.copy()
+    for a, b in zip(cu_rows, cu_rows[1:]):
+        if dn < b - a:
+            g[a:b - dn] += V[a + dn:b]
+    return g
+
+
+# ---- the front: the causal layer and the affine --------------------------------------------------------------------------------------
+FRONT_BASES = ('zero', 'affine', 'accumulate')
+
+
+def front_case(lengths, dn, seed=21):
+    """Inputs of the front backward on utterances of `lengths` samples, one after the other (a uniform batch: N times T): in, d_out,
+    scale, d_in0 [rows], the causal filter cf [2, 1, 64], and U, V [rows, 64] of layer 0, whose dilation is dn."""
+    rng = np.random.RandomState(seed + dn + 7 * len(lengths) + sum(lengths))
+    rows = int(sum(lengths))
+    f32 = lambda a: a.astype(np.float32)
+    return {'lengths': [int(T) for T in lengths], 'cu_rows': [0] + [int(v) for v in np.cumsum(lengths)], 'dn': dn,
+            'in': f32(rng.randn(rows)), 'cf': f32(0.3 * rng.randn(2, 1, 64)), 'U': f32(rng.randn(rows, 64)), 'V': f32(rng.randn(rows, 64)),
+            'd_out': f32(rng.randn(rows)), 'scale': f32(0.5 + rng.rand(rows)), 'd_in0': f32(rng.randn(rows))}
+
+
+def front_base(c, base, dtype=np.float64):
+    """What d_in starts from: nothing, d_out * scale (the affine), or what d_in held (accumulate)."""
+    if base == 'affine':
+        return c['d_out'].astype(dtype) * c['scale'].astype(dtype)
+    return c['d_in0'].astype(dtype) if base == 'accumulate' else np.zeros(len(c['in']), dtype=dtype)
+
+
+def front_backward(c, base, dtype=np.float64):
+    """The front backward restated in numpy of `dtype` (include/pwv_hip_train.h; x_0[t] = in[t - 1] cf[0] + in[t] cf[1], in[-1] = 0):
+        g0[t]   = U[t] + V[t + dn] while t + dn < T
+        d cf[0] = sum_{t > 0} in[t - 1] g0[t],   d cf[1] = sum_t in[t] g0[t]
+        d_in[t] = base[t] + g0[t] . cf[1] + (t + 1 < T) g0[t + 1] . cf[0]
+    per utterance; returns {'cf': [2, 1, 64], 'd_in': [rows]} in `dtype`."""
+    cu = c['cu_rows']
+    x, cf = c['in'].astype(dtype), c['cf'].astype(dtype)
+    g0 = look_ahead(c['U'].astype(dtype), c['V'].astype(dtype), c['dn'], cu)
+    d_in = front_base(c, base, dtype) + g0 @ cf[1, 0]
+    nxt = g0 @ cf[0, 0]
+    dcf = np.zeros((2, 1, 64), dtype=dtype)
+    for a, b in zip(cu, cu[1:]):
+        d_in[a:b - 1] += nxt[a + 1:b]
+        dcf[0, 0] += x[a:b - 1] @ g0[a + 1:b]
+        dcf[1, 0] += x[a:b] @ g0[a:b]
+    assert d_in.dtype == dtype and dcf.dtype == dtype
+    return {'cf': dcf, 'd_in': d_in}
+
+
+def front_backward_autograd(c, base):
+    """The same by float64 autograd of in -> x_0 (oracle.torch_cpu.causal_conv_torch at dilation 1, every utterance on its own) under
+    sum(x_0 * g0); pins front_backward."""
+    x = torch.from_numpy(c['in']).double().requires_grad_(True)
+    cf = torch.from_numpy(c['cf']).double().requires_grad_(True)
+    cu = c['cu_rows']
+    g0 = torch.from_numpy(look_ahead(c['U'].astype(np.float64), c['V'].astype(np.float64), c['dn'], cu))
+    loss = 0
+    for a, b in zip(cu, cu[1:]):
+        x0 = TC.causal_conv_torch(x[a:b].reshape(1, b - a, 1), cf, 1)
+        loss = loss + (x0[0] * g0[a:b]).sum()
+    loss.backward()
+    return {'cf': cf.grad.numpy(), 'd_in': front_base(c, base) + x.grad.numpy()}

@@ -25,18 +25,26 @@ FRAMES = [1 + T // HOP for T in LENGTHS]
 CU_FRAMES = [0] + [int(v) for v in np.cumsum(FRAMES)]
 
 
+WAV_SEED = 60                           # utterance i draws its wav from seed WAV_SEED + k + i, k the first that keeps TO.SIGN_MARGIN
+
+
+def problem(lengths=tuple(LENGTHS), hop=HOP):
+    """(cfg, weights, mels, zs, wavs) of the small model on a packed batch: per utterance mel [1, 1 + T_i / hop, 80], z [1, T_i, 1] and wav
+    [1, T_i, 1], each from seeds of its own.  Asserts tests.train_oracle's RELU_MARGIN and SIGN_MARGIN of the inputs."""
+    return _problem(tuple(int(T) for T in lengths), int(hop))
+
+
 @functools.lru_cache(maxsize=None)
-def problem(lengths=tuple(LENGTHS)):
-    """(cfg, weights, mels, zs, wavs) of the small model on a packed batch: per utterance mel [1, 1 + T_i / 16, 80], z [1, T_i, 1] and wav
-    [1, T_i, 1], each from seeds of its own."""
-    cfg = TO.small_cfg()
+def _problem(lengths, hop):
+    cfg = TO.small_cfg(hop)
     w = TO.problem()[1]
-    mels, zs, wavs = [], [], []
+    mels, zs = [], []
     for i, T in enumerate(lengths):
         mel, z = O.synthetic_inputs(1, T, cfg, mel_seed=20 + i, z_seed=40 + i)
         mels.append(mel)
         zs.append(z)
-        wavs.append((0.3 * np.random.RandomState(60 + i).randn(1, T, 1)).astype(np.float32))
+    assert min(TO.relu_margin(w, mel) for mel in mels) >= TO.RELU_MARGIN, 'a conditioning pre-activation sits on the ReLU: draw another seed'
+    wavs = TO.draw_wav([TO.pred64(w, mel, z, cfg) for mel, z in zip(mels, zs)], WAV_SEED, [(1, T, 1) for T in lengths])
     return cfg, w, mels, zs, wavs
 
 
@@ -82,11 +90,15 @@ def loss_and_grads(weights, mels, zs, wavs, cfg, dtype, w=None, win=None):
     return terms, [p.detach().double().numpy().reshape(-1) for p in preds], _grads(W)
 
 
-@functools.lru_cache(maxsize=None)
-def reference(w=None, win=None, lengths=tuple(LENGTHS)):
+def reference(w=None, win=None, lengths=tuple(LENGTHS), hop=HOP):
     """{'terms', 'preds', 'g64', 'g32', 'E32'}: float64 and float32 autograd of the packed problem (L1, or L1 + w * power at `win`); E32 =
     max over the variables of max|g32 - g64| / max|g64|, as tests.train_oracle.reference computes it."""
-    cfg, weights, mels, zs, wavs = problem(lengths)
+    return _reference(w, win, tuple(int(T) for T in lengths), int(hop))
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(w, win, lengths, hop):
+    cfg, weights, mels, zs, wavs = problem(lengths, hop)
     t64, p64, g64 = loss_and_grads(weights, mels, zs, wavs, cfg, torch.float64, w, win)
     _, _, g32 = loss_and_grads(weights, mels, zs, wavs, cfg, torch.float32, w, win)
     return {'terms': t64, 'preds': p64, 'g64': g64, 'g32': g32,
@@ -137,7 +149,7 @@ def head_grad(preds, ys, win, hop, wl1, wp, dtype):
 # ---- one layer on the packed rows ------------------------------------------------------------------------------------------------------
 def layer_case(d, seed=11, lengths=tuple(LENGTHS), hop=HOP):
     """tests.train_oracle.layer_case on a packed batch: x, g [rows, 64], dy [rows], P [sum frames, 128]; the weights of the uniform case."""
-    c = dict(TO.layer_case(d, seed))
+    c = {k: v for k, v in TO.layer_case(d, seed).items() if k not in ('N', 'T', 'offset')}
     rng = np.random.RandomState(seed + d + 1000)
     f32 = lambda a: a.astype(np.float32)
     rows, frames = sum(lengths), [1 + T // hop for T in lengths]
