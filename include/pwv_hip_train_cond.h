@@ -34,7 +34,7 @@ extern "C" {
  *
  * LDS.  The backward stages [x[t-d] | x[t]] (32 x 129), FG / dFG (32 x 129), g, d o and o (32 x 65 each) and the condition tile
  * (32 x 97): 70.4 KB side by side, over the 64 KiB a kernel may declare statically.  d o and o ALIAS: the gating pass reads d o[r][c] and
- * writes o[r][c] in its place, the same thread the same element, and nothing reads d o afterwards.  That leaves 62208 bytes of static
+ * writes o[r][c] in its place, the same thread the same element, and nothing reads d o afterwards.  That leaves 62080 bytes of static
  * LDS (forward: 53760; no launch requests dynamic LDS), and two workgroups share a CU's 160 KiB, as in pwv_hip_train.h.
  *
  * Every call only enqueues on `stream`.  Refused with PWV_EINVAL before a device is touched, pwv_last_error naming the field: args NULL,

@@ -6,9 +6,10 @@
 //   weight gradients         A[i][k = row] and B[k = row][j] both from LDS: the 32 rows of the unit are the K dimension, the tile stays in
 //                            the wave's accumulators over all units of the workgroup and leaves once, as the workgroup's partial.
 // A second launch (train_reduce_kernel) adds the partials in a fixed order and scatters them to the TF layouts.  No atomics.
-// The unit bodies that depend on where an utterance begins and ends live in pwv_train_units.h, written over a geometry policy; the
-// kernels here are their uniform [N, T] instances (csrc/pwv_train_varlen.hip holds the packed ones), next to the head, which is
-// row-independent, and the reduction.
+// The unit bodies that depend on where an utterance begins and ends live in pwv_train_units.h, written over a geometry and a
+// conditioning policy, with the host text of their entry points; the kernels here are their uniform [N, T] instances on the
+// frame-rate projection (csrc/pwv_train_varlen.hip holds the packed ones, csrc/pwv_train_cond.hip those of a per-sample condition),
+// next to the head, which is row-independent, and the reduction.
 #include "pwv_common.h"
 #include "pwv_hip_train.h"
 #include "pwv_train_units.h"
@@ -33,7 +34,7 @@ __global__ __launch_bounds__(kTrThreads) void train_front_fwd_kernel(const float
     }
 }
 
-__global__ __launch_bounds__(kTrThreads) void train_layer_fwd_kernel(LayerFwdParams p) { layer_fwd_body<UniformGeo>(p); }
+__global__ __launch_bounds__(kTrThreads) void train_layer_fwd_kernel(LayerFwdParams p) { layer_fwd_body<UniformGeo, ProjCond>(p, {}); }
 
 struct HeadParams {
     const float *o, *skip, *skip_bias, *post1, *post1_bias, *post2, *post2_bias;
@@ -161,7 +162,7 @@ __global__ __launch_bounds__(kTrThreads) void train_head_bwd_kernel(HeadParams p
 
 template <bool LAST>
 __global__ __launch_bounds__(kTrThreads) void train_layer_bwd_kernel(LayerBwdParams p) {
-    layer_bwd_body<UniformGeo, LAST>(p);
+    layer_bwd_body<UniformGeo, ProjCond, LAST>(p, {});
 }
 
 __global__ __launch_bounds__(kTrThreads) void train_front_bwd_kernel(FrontBwdParams p) { front_bwd_body<UniformGeo>(p); }
@@ -213,7 +214,8 @@ __global__ __launch_bounds__(kTrThreads) void train_reduce_kernel(ReduceParams p
 // host
 // ------------------------------------------------------------------------------------------------------------------------------
 int train_grid_size(int max_workgroups, int units) {
-    // two per compute unit by default: 58 KiB of LDS and < 256 registers let two share a CU, and one hides the other's operand loads
+    // two per compute unit by default: at most 62 KB of LDS (the per-sample layer backward) and <= 256 registers let two share a CU,
+    // and one hides the other's operand loads
     int cap = max_workgroups > 0 ? max_workgroups : 2 * device_cus();
     if (cap < 1) cap = 1;
     return units < cap ? units : cap;
@@ -228,13 +230,6 @@ static int train_check(const pwv_train_args* a, const char* who) {
     PWV_CHECK_ARG(a->N >= 1 && a->T >= 1, "%s: N = %d, T = %d must be >= 1", who, a->N, a->T);
     PWV_CHECK_ARG((long long)a->N * a->T < (1ll << 31) - 64, "%s: N T = %lld is beyond int32", who, (long long)a->N * a->T);
     PWV_CHECK_ARG(a->max_workgroups >= 0, "%s: max_workgroups %d is negative", who, a->max_workgroups);
-    return PWV_OK;
-}
-
-static int train_check_ws(const pwv_train_args* a, const char* who, int grid, int part) {
-    PWV_CHECK_ARG(a->workspace, "%s: workspace is a NULL pointer", who);
-    PWV_CHECK_ARG(a->workspace_bytes >= (size_t)grid * part * sizeof(float), "%s: workspace_bytes %zu is short of %zu", who, a->workspace_bytes,
-                  (size_t)grid * part * sizeof(float));
     return PWV_OK;
 }
 
@@ -266,28 +261,6 @@ int train_reduce(const ReduceParams& rp, hipStream_t st) {
     return PWV_OK;
 }
 
-int train_reduce_layer(const float* part, int grid, bool last, float* d_filter, float* d_gate, float* d_dense, float* d_dense_bias, hipStream_t st) {
-    ReduceParams rp;
-    rp.part = part; rp.n_part = grid; rp.stride = kLayerPart;
-    rp.seg[0].begin = 0; rp.seg[0].end = 128 * 128; rp.seg[0].dst = d_filter; rp.seg[0].dst2 = d_gate;
-    rp.n_seg = 1;
-    rp.total = 128 * 128;
-    if (!last) {
-        rp.seg[1].begin = 128 * 128; rp.seg[1].end = 128 * 128 + 64 * 64; rp.seg[1].dst = d_dense; rp.seg[1].dst2 = nullptr;
-        rp.seg[2].begin = rp.seg[1].end; rp.seg[2].end = kLayerPart; rp.seg[2].dst = d_dense_bias; rp.seg[2].dst2 = nullptr;
-        rp.n_seg = 3;
-        rp.total = kLayerPart;
-    }
-    return train_reduce(rp, st);
-}
-
-int train_reduce_front(const float* part, int grid, float* d_causal_filter, hipStream_t st) {
-    ReduceParams rp;
-    rp.part = part; rp.n_part = grid; rp.stride = kFrontPart; rp.total = kFrontPart; rp.n_seg = 1;
-    rp.seg[0].begin = 0; rp.seg[0].end = kFrontPart; rp.seg[0].dst = d_causal_filter; rp.seg[0].dst2 = nullptr;
-    return train_reduce(rp, st);
-}
-
 }  // namespace pwv
 
 using namespace pwv;
@@ -312,17 +285,11 @@ extern "C" int pwv_train_front_fwd_f32(const pwv_train_args* a, pwv_stream_t str
 extern "C" int pwv_train_layer_fwd_f32(const pwv_train_args* a, pwv_stream_t stream) {
     const char* who = "pwv_train_layer_fwd_f32";
     if (int e = train_check(a, who)) return e;
-    LayerFwdParams p{};
-    if (int e = train_geom(a, who, p.g, true)) return e;
-    PWV_CHECK_ARG(a->form == PWV_TRAIN_RESIDUAL || a->form == PWV_TRAIN_LAST, "%s: form %d", who, a->form);
-    PWV_CHECK_ARG(a->x && a->proj && a->filter && a->gate && a->x_out, "%s: x, proj, filter, gate or x_out is a NULL pointer", who);
-    PWV_CHECK_ARG(a->form == PWV_TRAIN_LAST || a->dense, "%s: dense is a NULL pointer", who);
-    p.x = a->x; p.proj = a->proj; p.filter = a->filter; p.gate = a->gate; p.dense = a->dense; p.dense_bias = a->dense_bias;
-    p.x_out = a->x_out;
-    p.last = a->form == PWV_TRAIN_LAST;
-    hipLaunchKernelGGL(train_layer_fwd_kernel, dim3(train_grid(a, (p.g.rows + 31) / 32)), dim3(kTrThreads), 0, (hipStream_t)stream, p);
-    PWV_CHECK_HIP(hipGetLastError());
-    return PWV_OK;
+    Geom g;
+    if (int e = train_geom(a, who, g, true)) return e;
+    return train_layer_fwd<ProjCond>(a, who, g, PackedTables{}, [&](int grid, const LayerFwdParams& p) {
+        hipLaunchKernelGGL(train_layer_fwd_kernel, dim3(grid), dim3(kTrThreads), 0, (hipStream_t)stream, p);
+    });
 }
 
 static int head_params(const pwv_train_args* a, const char* who, HeadParams& p) {
@@ -370,44 +337,20 @@ extern "C" int pwv_train_head_bwd_f32(const pwv_train_args* a, pwv_stream_t stre
 extern "C" int pwv_train_layer_bwd_f32(const pwv_train_args* a, pwv_stream_t stream) {
     const char* who = "pwv_train_layer_bwd_f32";
     if (int e = train_check(a, who)) return e;
-    LayerBwdParams p{};
-    if (int e = train_geom(a, who, p.g, true)) return e;
-    PWV_CHECK_ARG(a->form == PWV_TRAIN_RESIDUAL || a->form == PWV_TRAIN_LAST, "%s: form %d", who, a->form);
-    const bool last = a->form == PWV_TRAIN_LAST;
-    PWV_CHECK_ARG(a->x && a->proj && a->filter && a->gate, "%s: x, proj, filter or gate is a NULL pointer", who);
-    PWV_CHECK_ARG(a->u && a->v && a->d_proj && a->d_filter && a->d_gate, "%s: u, v, d_proj, d_filter or d_gate is a NULL pointer", who);
-    PWV_CHECK_ARG(a->d_proj_row_stride >= 128, "%s: d_proj_row_stride %d is below 128", who, a->d_proj_row_stride);
-    if (last) {
-        PWV_CHECK_ARG(a->d_o, "%s: d_o is a NULL pointer", who);
-    } else {
-        PWV_CHECK_ARG(a->dense && a->u_next && a->v_next && a->d_dense, "%s: dense, u_next, v_next or d_dense is a NULL pointer", who);
-        PWV_CHECK_ARG(a->next_dilation >= 1, "%s: next_dilation %d must be >= 1", who, a->next_dilation);
-        PWV_CHECK_ARG(a->u != a->u_next && a->v != a->v_next && a->u != a->v_next && a->v != a->u_next, "%s: u / v alias u_next / v_next", who);
-    }
-    const int grid = train_grid(a, (p.g.rows + 31) / 32);
-    if (int e = train_check_ws(a, who, grid, kLayerPart)) return e;
-    p.x = a->x; p.proj = a->proj; p.filter = a->filter; p.gate = a->gate; p.dense = a->dense;
-    p.u_next = a->u_next; p.v_next = a->v_next; p.d_o = a->d_o;
-    p.u = a->u; p.v = a->v; p.d_proj = a->d_proj; p.part = (float*)a->workspace;
-    if (last) hipLaunchKernelGGL(train_layer_bwd_kernel<true>, dim3(grid), dim3(kTrThreads), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(train_layer_bwd_kernel<false>, dim3(grid), dim3(kTrThreads), 0, (hipStream_t)stream, p);
-    PWV_CHECK_HIP(hipGetLastError());
-    return train_reduce_layer(p.part, grid, last, a->d_filter, a->d_gate, a->d_dense, a->d_dense_bias, (hipStream_t)stream);
+    Geom g;
+    if (int e = train_geom(a, who, g, true)) return e;
+    return train_layer_bwd<ProjCond>(a, who, g, PackedTables{}, {}, nullptr, 0, (hipStream_t)stream, [&](bool last, int grid, const LayerBwdParams& p) {
+        if (last) hipLaunchKernelGGL(train_layer_bwd_kernel<true>, dim3(grid), dim3(kTrThreads), 0, (hipStream_t)stream, p);
+        else hipLaunchKernelGGL(train_layer_bwd_kernel<false>, dim3(grid), dim3(kTrThreads), 0, (hipStream_t)stream, p);
+    });
 }
 
 extern "C" int pwv_train_front_bwd_f32(const pwv_train_args* a, pwv_stream_t stream) {
     const char* who = "pwv_train_front_bwd_f32";
     if (int e = train_check(a, who)) return e;
-    FrontBwdParams p{};
-    if (int e = train_geom(a, who, p.g, false)) return e;
-    PWV_CHECK_ARG(a->in && a->causal_filter && a->u_next && a->v_next && a->d_causal_filter,
-                  "%s: in, causal_filter, u_next, v_next or d_causal_filter is a NULL pointer", who);
-    PWV_CHECK_ARG(a->next_dilation >= 1, "%s: next_dilation %d must be >= 1", who, a->next_dilation);
-    const int grid = train_grid(a, (p.g.rows + 31) / 32);
-    if (int e = train_check_ws(a, who, grid, kFrontPart)) return e;
-    p.in = a->in; p.cf = a->causal_filter; p.u_next = a->u_next; p.v_next = a->v_next; p.d_out = a->d_out; p.scale = a->scale;
-    p.d_in = a->d_in; p.part = (float*)a->workspace; p.accumulate = a->accumulate;
-    hipLaunchKernelGGL(train_front_bwd_kernel, dim3(grid), dim3(kTrThreads), 0, (hipStream_t)stream, p);
-    PWV_CHECK_HIP(hipGetLastError());
-    return train_reduce_front(p.part, grid, a->d_causal_filter, (hipStream_t)stream);
+    Geom g;
+    if (int e = train_geom(a, who, g, false)) return e;
+    return train_front_bwd(a, who, g, PackedTables{}, (hipStream_t)stream, [&](int grid, const FrontBwdParams& p) {
+        hipLaunchKernelGGL(train_front_bwd_kernel, dim3(grid), dim3(kTrThreads), 0, (hipStream_t)stream, p);
+    });
 }

@@ -1,5 +1,7 @@
 // The unit bodies of training that depend on where an utterance begins and ends ("Training" and "Packed
-// training"): front forward, layer forward, layer backward, front backward, written once over a GEOMETRY POLICY.
+// training"): front forward, layer forward, layer backward, front backward, written once over a GEOMETRY POLICY and, the two layer
+// bodies, a CONDITIONING POLICY (ProjCond below: a row of the frame-rate projection P; SampleCond, csrc/pwv_train_cond.hip: a condition
+// row per sample).
 //   UniformGeo   utterance n owns rows n T .. (n + 1) T - 1 and P rows n frames ..: t, n and the P row are arithmetic on the row
 //                (csrc/pwv_train.hip instantiates the bodies with it under the kernel names of include/pwv_hip_train.h).
 //   PackedGeo    utterance i owns rows cu_rows[i] .. cu_rows[i + 1] - 1 and P rows cu_frames[i] ..: 33 threads LOCATE the rows of a
@@ -15,6 +17,7 @@
 #define PWV_TRAIN_UNITS_H
 
 #include "pwv_common.h"
+#include "pwv_hip_train.h"
 
 namespace pwv {
 
@@ -208,9 +211,9 @@ __device__ __forceinline__ void load_g(float* dst, int ld, const float* U, const
     }
 }
 
-// a = [x[t - d] | x[t]] of unit u into LDS [32][kLdW], and the P row of every row (-1 beyond the batch)
+// a = [x[t - d] | x[t]] of unit u into LDS [32][kLdW]
 template <class Geo>
-__device__ __forceinline__ void load_a(float* a, int* s_fr, const float* x, int u, const Geom& g, const typename Geo::Loc& loc) {
+__device__ __forceinline__ void load_a(float* a, const float* x, int u, const Geom& g, const typename Geo::Loc& loc) {
     for (int idx = threadIdx.x; idx < 1024; idx += kTrThreads) {
         const int q = idx >> 5, r = idx & 31, row = 32 * u + r;
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
@@ -221,31 +224,8 @@ __device__ __forceinline__ void load_a(float* a, int* s_fr, const float* x, int 
         float* d = a + r * kLdW + 4 * q;
         d[0] = v[0]; d[1] = v[1]; d[2] = v[2]; d[3] = v[3];
     }
-    if (threadIdx.x < 32) {
-        const int row = 32 * u + threadIdx.x;
-        int f = -1;
-        if (row < g.rows) f = Geo::frame(loc, threadIdx.x, row, g);
-        s_fr[threadIdx.x] = f;
-    }
 }
 
-// FG = a Wfg + P into LDS fg [32][kLdW]: wave w owns columns 32 w .. 32 w + 31 (F: waves 0, 1; G: waves 2, 3)
-__device__ __forceinline__ void compute_fg(float* fg, const float* a, const int* s_fr, const float* filter, const float* gate, const float* proj,
-                                           const Geom& g) {
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5;
-    f32x16 acc = zero16();
-    gemm_xw<128>(acc, a, kLdW, (w < 2 ? filter : gate) + 32 * (w & 1), 64);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int i = acc_row(r, h), f = s_fr[i];
-        const float p = f >= 0 ? proj[(size_t)f * g.pstride + 32 * w + j] : 0.f;
-        fg[i * kLdW + 32 * w + j] = acc[r] + p;
-    }
-}
-
-// ------------------------------------------------------------------------------------------------------------------------------
-// forward
-// ------------------------------------------------------------------------------------------------------------------------------
 struct LayerFwdParams {
     const float *x, *proj, *filter, *gate, *dense, *dense_bias;
     float* x_out;
@@ -254,20 +234,99 @@ struct LayerFwdParams {
     PackedTables tab;
 };
 
-template <class Geo>
-__device__ __forceinline__ void layer_fwd_body(const LayerFwdParams& p) {
+struct LayerBwdParams {
+    const float *x, *proj, *filter, *gate, *dense;
+    const float *u_next, *v_next, *d_o;
+    float *u, *v, *d_proj, *part;
+    Geom g;
+    PackedTables tab;
+};
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// conditioning policies: how the condition enters FG of a unit and how its gradient leaves
+//   Params      what the kernel takes beside the layer's parameters
+//   Tile        what `stage` leaves in LDS for the unit (a barrier of the body publishes it)
+//   Acc         accumulators that live in registers over a workgroup's units and leave in `flush`
+//   stage       fill the tile of unit u                  fg           FG = a Wfg + the conditioning term
+//   unit_grad   the unit's share of the condition's gradient, from dFG in LDS
+//   part_floats the floats of a workgroup's partial      flush        write what lies behind its first kLayerPart floats
+// ProjCond: the condition is a row of the frame-rate projection P (Geom: hop, off, pstride, dpstride, kmax); SampleCond, a condition
+// row per sample, is csrc/pwv_train_cond.hip's.  A hook holds its text itself: as a wrapper around a free function, one more level
+// of inlining, `fg` cost the projection kernels registers ("One text for both conditionings").
+// ------------------------------------------------------------------------------------------------------------------------------
+struct ProjCond {
+    static constexpr bool kProjected = true;
+    struct Params {};
+    struct Tile {
+        int fr[32];                             // the P row of every row of the unit, -1 beyond the batch
+    };
+    struct Acc {};
+    template <class Geo>
+    __device__ static __forceinline__ void stage(Tile& tile, int u, const Geom& g, const typename Geo::Loc& loc, const Params&) {
+        if (threadIdx.x < 32) {
+            const int row = 32 * u + threadIdx.x;
+            int f = -1;
+            if (row < g.rows) f = Geo::frame(loc, threadIdx.x, row, g);
+            tile.fr[threadIdx.x] = f;
+        }
+    }
+    // FG = a Wfg + P into LDS fg [32][kLdW]: wave w owns columns 32 w .. 32 w + 31 (F: waves 0, 1; G: waves 2, 3)
+    __device__ static __forceinline__ void fg(float* fg, const float* a, const Tile& tile, const float* filter, const float* gate, const float* proj,
+                                              const Geom& g, const Params&) {
+        const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5;
+        f32x16 acc = zero16();
+        gemm_xw<128>(acc, a, kLdW, (w < 2 ? filter : gate) + 32 * (w & 1), 64);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int i = acc_row(r, h), f = tile.fr[i];
+            const float p = f >= 0 ? proj[(size_t)f * g.pstride + 32 * w + j] : 0.f;
+            fg[i * kLdW + 32 * w + j] = acc[r] + p;
+        }
+    }
+    // dP: threads 128 .. 255 sum column c of dFG over the rows of each frame, in row order, into the frame's slot of this unit
+    template <class Geo>
+    __device__ static __forceinline__ void unit_grad(Acc&, const Tile& tile, const float* fg, int u, const LayerBwdParams& p,
+                                                     const typename Geo::Loc& loc, const Params&) {
+        if (threadIdx.x >= 128) {
+            const int c = threadIdx.x - 128;
+            float s = 0.f;
+            int cur = -1;
+            for (int r = 0; r <= 32; ++r) {
+                const int f = r < 32 ? tile.fr[r] : -1;
+                if (f != cur) {
+                    if (cur >= 0) {
+                        const int k = Geo::slot(loc, r - 1, cur, u, p.g);
+                        p.d_proj[((size_t)cur * p.g.kmax + k) * p.g.dpstride + c] = s;
+                    }
+                    cur = f;
+                    s = 0.f;
+                }
+                if (f >= 0) s += fg[r * kLdW + c];
+            }
+        }
+    }
+    __host__ __device__ static __forceinline__ int part_floats(const Params&) { return kLayerPart; }
+    __device__ static __forceinline__ void flush(const Acc&, float*, const Params&) {}
+};
+
+// ------------------------------------------------------------------------------------------------------------------------------
+// forward
+// ------------------------------------------------------------------------------------------------------------------------------
+template <class Geo, class Cond>
+__device__ __forceinline__ void layer_fwd_body(const LayerFwdParams& p, const typename Cond::Params& cp) {
     __shared__ float a[32 * kLdW];
     __shared__ float fg[32 * kLdW];
     __shared__ float o[32 * kLdH];
-    __shared__ int s_fr[32];
+    __shared__ typename Cond::Tile tile;
     __shared__ typename Geo::Loc loc;
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5;
     const int units = (p.g.rows + 31) / 32;
     for (int u = blockIdx.x; u < units; u += gridDim.x) {
         Geo::locate(loc, u, p.g, p.tab);
-        load_a<Geo>(a, s_fr, p.x, u, p.g, loc);
+        load_a<Geo>(a, p.x, u, p.g, loc);
+        Cond::template stage<Geo>(tile, u, p.g, loc, cp);
         __syncthreads();
-        compute_fg(fg, a, s_fr, p.filter, p.gate, p.proj, p.g);
+        Cond::fg(fg, a, tile, p.filter, p.gate, p.proj, p.g, cp);
         __syncthreads();
         for (int idx = threadIdx.x; idx < 2048; idx += kTrThreads) {
             const int r = idx >> 6, c = idx & 63;
@@ -297,73 +356,50 @@ __device__ __forceinline__ void layer_fwd_body(const LayerFwdParams& p) {
 // ------------------------------------------------------------------------------------------------------------------------------
 // backward
 // ------------------------------------------------------------------------------------------------------------------------------
-struct LayerBwdParams {
-    const float *x, *proj, *filter, *gate, *dense;
-    const float *u_next, *v_next, *d_o;
-    float *u, *v, *d_proj, *part;
-    Geom g;
-    PackedTables tab;
-};
-
-template <class Geo, bool LAST>
-__device__ __forceinline__ void layer_bwd_body(const LayerBwdParams& p) {
+template <class Geo, class Cond, bool LAST>
+__device__ __forceinline__ void layer_bwd_body(const LayerBwdParams& p, const typename Cond::Params& cp) {
     __shared__ float a[32 * kLdW];              // [x[t - d] | x[t]], then [V | U]
     __shared__ float fg[32 * kLdW];             // FG, then dFG
-    __shared__ float o[32 * kLdH];
+    __shared__ float od[32 * kLdH];             // d o, then o: the gating pass replaces element by element ("LDS: aliasing")
     __shared__ float gin[32 * kLdH];            // g
-    __shared__ float dob[32 * kLdH];            // d o
-    __shared__ int s_fr[32];
+    __shared__ typename Cond::Tile tile;
     __shared__ typename Geo::Loc loc;
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5;
+    const int w = threadIdx.x >> 6;
     const int units = (p.g.rows + 31) / 32;
     f32x16 g_wfg[4], g_dense = zero16();
 #pragma unroll
     for (int b = 0; b < 4; ++b) g_wfg[b] = zero16();
     float g_db = 0.f;                           // thread c < 64: d dense_bias[c]
+    typename Cond::Acc g_cond;
     for (int u = blockIdx.x; u < units; u += gridDim.x) {
         Geo::locate(loc, u, p.g, p.tab);
-        load_a<Geo>(a, s_fr, p.x, u, p.g, loc);
-        if (LAST) tile32_to_lds(dob, kLdH, 0, p.d_o, u, p.g.rows);
+        load_a<Geo>(a, p.x, u, p.g, loc);
+        Cond::template stage<Geo>(tile, u, p.g, loc, cp);
+        if (LAST) tile32_to_lds(od, kLdH, 0, p.d_o, u, p.g.rows);
         else load_g<Geo>(gin, kLdH, p.u_next, p.v_next, u, 32, p.g, loc);
         __syncthreads();
-        compute_fg(fg, a, s_fr, p.filter, p.gate, p.proj, p.g);
+        Cond::fg(fg, a, tile, p.filter, p.gate, p.proj, p.g, cp);
         if (!LAST && w < 2) {                   // d o = g dense^T, columns 32 w ..
             f32x16 acc = zero16();
             gemm_xwt<64>(acc, gin, kLdH, p.dense + (size_t)32 * w * 64, 64);
-            acc_to_lds(acc, dob, kLdH, 32 * w);
+            acc_to_lds(acc, od, kLdH, 32 * w);
         }
         __syncthreads();
         for (int idx = threadIdx.x; idx < 2048; idx += kTrThreads) {
             const int r = idx >> 6, c = idx & 63;
-            const float th = tanhf(fg[r * kLdW + c]), sg = sigmoid_f(fg[r * kLdW + 64 + c]), d = dob[r * kLdH + c];
-            o[r * kLdH + c] = th * sg;
+            const float th = tanhf(fg[r * kLdW + c]), sg = sigmoid_f(fg[r * kLdW + 64 + c]), d = od[r * kLdH + c];
+            od[r * kLdH + c] = th * sg;
             fg[r * kLdW + c] = d * sg * (1.f - th * th);
             fg[r * kLdW + 64 + c] = d * th * sg * (1.f - sg);
         }
         __syncthreads();
         for (int b = 0; b < 4; ++b) gemm_tn(g_wfg[b], a, kLdW, 32 * b, fg, kLdW, 32 * w);         // dWfg += a^T dFG
         if (!LAST) {
-            gemm_tn(g_dense, o, kLdH, 32 * (w >> 1), gin, kLdH, 32 * (w & 1));                    // d dense += o^T g
+            gemm_tn(g_dense, od, kLdH, 32 * (w >> 1), gin, kLdH, 32 * (w & 1));                   // d dense += o^T g
             if (threadIdx.x < 64)
                 for (int r = 0; r < 32; ++r) g_db += gin[r * kLdH + threadIdx.x];
         }
-        if (threadIdx.x >= 128) {               // dP: column c of dFG summed over the rows of each frame, in row order
-            const int c = threadIdx.x - 128;
-            float s = 0.f;
-            int cur = -1;
-            for (int r = 0; r <= 32; ++r) {
-                const int f = r < 32 ? s_fr[r] : -1;
-                if (f != cur) {
-                    if (cur >= 0) {
-                        const int k = Geo::slot(loc, r - 1, cur, u, p.g);
-                        p.d_proj[((size_t)cur * p.g.kmax + k) * p.g.dpstride + c] = s;
-                    }
-                    cur = f;
-                    s = 0.f;
-                }
-                if (f >= 0) s += fg[r * kLdW + c];
-            }
-        }
+        Cond::template unit_grad<Geo>(g_cond, tile, fg, u, p, loc, cp);
         // [V | U] = dFG Wfg^T: wave w owns input channels 32 w .. of the 128 (0..63: the tap at t - d, 64..127: the tap at t)
         f32x16 acc = zero16();
         gemm_xwt<64>(acc, fg, kLdW, p.filter + (size_t)32 * w * 64, 64);
@@ -382,12 +418,13 @@ __device__ __forceinline__ void layer_bwd_body(const LayerBwdParams& p) {
         lds_to_tile32(p.u, u, a, kLdW, 64);
         __syncthreads();
     }
-    float* part = p.part + (size_t)blockIdx.x * kLayerPart;
+    float* part = p.part + (size_t)blockIdx.x * Cond::part_floats(cp);
     for (int b = 0; b < 4; ++b) acc_to_part(g_wfg[b], part, 128, 32 * b, 32 * w);
     if (!LAST) {
         acc_to_part(g_dense, part + 128 * 128, 64, 32 * (w >> 1), 32 * (w & 1));
         if (threadIdx.x < 64) part[128 * 128 + 64 * 64 + threadIdx.x] = g_db;
     }
+    Cond::flush(g_cond, part + kLayerPart, cp);
 }
 
 struct FrontBwdParams {
@@ -454,7 +491,7 @@ __device__ __forceinline__ void front_bwd_body(const FrontBwdParams& p) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
-// host: stage two of every weight gradient (train_reduce_kernel, csrc/pwv_train.hip) and the launches both geometries share
+// host: stage two of every weight gradient (train_reduce_kernel, csrc/pwv_train.hip) and the entry points every ABI struct shares
 // ------------------------------------------------------------------------------------------------------------------------------
 struct ReduceSeg {
     int begin, end;                             // elements [begin, end) of a partial
@@ -468,10 +505,98 @@ struct ReduceParams {
 };
 
 int train_reduce(const ReduceParams& rp, hipStream_t st);
-// the reductions behind a layer's / the front's backward launch of `grid` workgroups over `part`
-int train_reduce_layer(const float* part, int grid, bool last, float* d_filter, float* d_gate, float* d_dense, float* d_dense_bias, hipStream_t st);
-int train_reduce_front(const float* part, int grid, float* d_causal_filter, hipStream_t st);
 int train_grid_size(int max_workgroups, int units);
+
+// The three entry-point kinds that depend on where an utterance begins, once for every ABI struct: pwv_train_args (also as the head of
+// pwv_train_cond_args) and pwv_train_varlen_args share the names of the fields read here.  The caller has checked the struct and its
+// geometry and filled `g`, `tab` and the condition's parameters; `launch` enqueues its kernel on its stream.
+template <class Args>
+int train_check_ws(const Args* a, const char* who, int grid, int part) {
+    PWV_CHECK_ARG(a->workspace, "%s: workspace is a NULL pointer", who);
+    PWV_CHECK_ARG(a->workspace_bytes >= (size_t)grid * part * sizeof(float), "%s: workspace_bytes %zu is short of %zu", who, a->workspace_bytes,
+                  (size_t)grid * part * sizeof(float));
+    return PWV_OK;
+}
+
+template <class Cond, class Args, class Launch>
+int train_layer_fwd(const Args* a, const char* who, const Geom& g, const PackedTables& tab, Launch launch) {      // launch(grid, p)
+    PWV_CHECK_ARG(a->form == PWV_TRAIN_RESIDUAL || a->form == PWV_TRAIN_LAST, "%s: form %d", who, a->form);
+    PWV_CHECK_ARG(a->x && a->filter && a->gate && a->x_out, "%s: x, filter, gate or x_out is a NULL pointer", who);
+    PWV_CHECK_ARG(!Cond::kProjected || a->proj, "%s: proj is a NULL pointer", who);
+    PWV_CHECK_ARG(a->form == PWV_TRAIN_LAST || a->dense, "%s: dense is a NULL pointer", who);
+    LayerFwdParams p{};
+    p.x = a->x; p.proj = a->proj; p.filter = a->filter; p.gate = a->gate; p.dense = a->dense; p.dense_bias = a->dense_bias;
+    p.x_out = a->x_out;
+    p.g = g;
+    p.last = a->form == PWV_TRAIN_LAST;
+    p.tab = tab;
+    launch(train_grid_size(a->max_workgroups, (g.rows + 31) / 32), p);
+    PWV_CHECK_HIP(hipGetLastError());
+    return PWV_OK;
+}
+
+// `extra`: the segments of the partial behind its first kLayerPart floats (Cond::flush), reduced with the layer's own
+template <class Cond, class Args, class Launch>
+int train_layer_bwd(const Args* a, const char* who, const Geom& g, const PackedTables& tab, const typename Cond::Params& cp, const ReduceSeg* extra,
+                    int n_extra, hipStream_t st, Launch launch) {                                                 // launch(last, grid, p)
+    PWV_CHECK_ARG(a->form == PWV_TRAIN_RESIDUAL || a->form == PWV_TRAIN_LAST, "%s: form %d", who, a->form);
+    const bool last = a->form == PWV_TRAIN_LAST;
+    PWV_CHECK_ARG(a->x && a->filter && a->gate, "%s: x, filter or gate is a NULL pointer", who);
+    PWV_CHECK_ARG(a->u && a->v && a->d_filter && a->d_gate, "%s: u, v, d_filter or d_gate is a NULL pointer", who);
+    if (Cond::kProjected) {
+        PWV_CHECK_ARG(a->proj && a->d_proj, "%s: proj or d_proj is a NULL pointer", who);
+        PWV_CHECK_ARG(a->d_proj_row_stride >= 128, "%s: d_proj_row_stride %d is below 128", who, a->d_proj_row_stride);
+    }
+    if (last) {
+        PWV_CHECK_ARG(a->d_o, "%s: d_o is a NULL pointer", who);
+    } else {
+        PWV_CHECK_ARG(a->dense && a->u_next && a->v_next && a->d_dense, "%s: dense, u_next, v_next or d_dense is a NULL pointer", who);
+        PWV_CHECK_ARG(a->next_dilation >= 1, "%s: next_dilation %d must be >= 1", who, a->next_dilation);
+        PWV_CHECK_ARG(a->u != a->u_next && a->v != a->v_next && a->u != a->v_next && a->v != a->u_next, "%s: u / v alias u_next / v_next", who);
+    }
+    const int grid = train_grid_size(a->max_workgroups, (g.rows + 31) / 32), part = Cond::part_floats(cp);
+    if (int e = train_check_ws(a, who, grid, part)) return e;
+    LayerBwdParams p{};
+    p.x = a->x; p.proj = a->proj; p.filter = a->filter; p.gate = a->gate; p.dense = a->dense;
+    p.u_next = a->u_next; p.v_next = a->v_next; p.d_o = a->d_o;
+    p.u = a->u; p.v = a->v; p.d_proj = a->d_proj; p.part = (float*)a->workspace;
+    p.g = g;
+    p.tab = tab;
+    launch(last, grid, p);
+    PWV_CHECK_HIP(hipGetLastError());
+    // stage two: dWfg | d dense | d dense_bias | extra; a PWV_TRAIN_LAST layer has no dense, and what nobody wants at the end is not summed
+    ReduceParams rp;
+    rp.part = p.part; rp.n_part = grid; rp.stride = part;
+    rp.seg[0] = ReduceSeg{0, 128 * 128, a->d_filter, a->d_gate};
+    rp.seg[1] = ReduceSeg{128 * 128, 128 * 128 + 64 * 64, last ? nullptr : a->d_dense, nullptr};
+    rp.seg[2] = ReduceSeg{128 * 128 + 64 * 64, kLayerPart, last ? nullptr : a->d_dense_bias, nullptr};
+    PWV_CHECK_ARG(3 + n_extra <= (int)(sizeof(rp.seg) / sizeof(rp.seg[0])), "%s: %d segments behind the layer's own are more than a reduction holds", who, n_extra);
+    for (int s = 0; s < n_extra; ++s) rp.seg[3 + s] = extra[s];
+    rp.n_seg = 3 + n_extra;
+    while (rp.n_seg > 1 && !rp.seg[rp.n_seg - 1].dst) --rp.n_seg;
+    rp.total = rp.seg[rp.n_seg - 1].end;
+    return train_reduce(rp, st);
+}
+
+template <class Args, class Launch>
+int train_front_bwd(const Args* a, const char* who, const Geom& g, const PackedTables& tab, hipStream_t st, Launch launch) {  // launch(grid, p)
+    PWV_CHECK_ARG(a->in && a->causal_filter && a->u_next && a->v_next && a->d_causal_filter,
+                  "%s: in, causal_filter, u_next, v_next or d_causal_filter is a NULL pointer", who);
+    PWV_CHECK_ARG(a->next_dilation >= 1, "%s: next_dilation %d must be >= 1", who, a->next_dilation);
+    const int grid = train_grid_size(a->max_workgroups, (g.rows + 31) / 32);
+    if (int e = train_check_ws(a, who, grid, kFrontPart)) return e;
+    FrontBwdParams p{};
+    p.in = a->in; p.cf = a->causal_filter; p.u_next = a->u_next; p.v_next = a->v_next; p.d_out = a->d_out; p.scale = a->scale;
+    p.d_in = a->d_in; p.part = (float*)a->workspace; p.accumulate = a->accumulate;
+    p.g = g;
+    p.tab = tab;
+    launch(grid, p);
+    PWV_CHECK_HIP(hipGetLastError());
+    ReduceParams rp;
+    rp.part = p.part; rp.n_part = grid; rp.stride = kFrontPart; rp.total = kFrontPart; rp.n_seg = 1;
+    rp.seg[0] = ReduceSeg{0, kFrontPart, a->d_causal_filter, nullptr};
+    return train_reduce(rp, st);
+}
 
 }  // namespace pwv
 

@@ -35,11 +35,11 @@ __global__ __launch_bounds__(kTrThreads) void train_front_fwd_varlen_kernel(Fron
     }
 }
 
-__global__ __launch_bounds__(kTrThreads) void train_layer_fwd_varlen_kernel(LayerFwdParams p) { layer_fwd_body<PackedGeo>(p); }
+__global__ __launch_bounds__(kTrThreads) void train_layer_fwd_varlen_kernel(LayerFwdParams p) { layer_fwd_body<PackedGeo, ProjCond>(p, {}); }
 
 template <bool LAST>
 __global__ __launch_bounds__(kTrThreads) void train_layer_bwd_varlen_kernel(LayerBwdParams p) {
-    layer_bwd_body<PackedGeo, LAST>(p);
+    layer_bwd_body<PackedGeo, ProjCond, LAST>(p, {});
 }
 
 __global__ __launch_bounds__(kTrThreads) void train_front_bwd_varlen_kernel(FrontBwdParams p) { front_bwd_body<PackedGeo>(p); }
@@ -79,13 +79,6 @@ static int varlen_check(const pwv_train_varlen_args* a, const char* who, Geom& g
         PWV_CHECK_ARG(a->dilation >= 1, "%s: dilation %d must be >= 1", who, a->dilation);
         PWV_CHECK_ARG(a->proj_row_stride >= 128, "%s: proj_row_stride %d is below 128", who, a->proj_row_stride);
     }
-    return PWV_OK;
-}
-
-static int varlen_check_ws(const pwv_train_varlen_args* a, const char* who, int grid, int part) {
-    PWV_CHECK_ARG(a->workspace, "%s: workspace is a NULL pointer", who);
-    PWV_CHECK_ARG(a->workspace_bytes >= (size_t)grid * part * sizeof(float), "%s: workspace_bytes %zu is short of %zu", who, a->workspace_bytes,
-                  (size_t)grid * part * sizeof(float));
     return PWV_OK;
 }
 
@@ -278,61 +271,33 @@ extern "C" int pwv_train_varlen_front_fwd_f32(const pwv_train_varlen_args* a, pw
 
 extern "C" int pwv_train_varlen_layer_fwd_f32(const pwv_train_varlen_args* a, pwv_stream_t stream) {
     const char* who = "pwv_train_varlen_layer_fwd_f32";
-    LayerFwdParams p{};
-    if (int e = varlen_check(a, who, p.g, p.tab, true)) return e;
-    PWV_CHECK_ARG(a->form == PWV_TRAIN_RESIDUAL || a->form == PWV_TRAIN_LAST, "%s: form %d", who, a->form);
-    PWV_CHECK_ARG(a->x && a->proj && a->filter && a->gate && a->x_out, "%s: x, proj, filter, gate or x_out is a NULL pointer", who);
-    PWV_CHECK_ARG(a->form == PWV_TRAIN_LAST || a->dense, "%s: dense is a NULL pointer", who);
-    p.x = a->x; p.proj = a->proj; p.filter = a->filter; p.gate = a->gate; p.dense = a->dense; p.dense_bias = a->dense_bias;
-    p.x_out = a->x_out;
-    p.last = a->form == PWV_TRAIN_LAST;
-    const int grid = train_grid_size(a->max_workgroups, (p.g.rows + 31) / 32);
-    hipLaunchKernelGGL(train_layer_fwd_varlen_kernel, dim3(grid), dim3(kTrThreads), 0, (hipStream_t)stream, p);
-    PWV_CHECK_HIP(hipGetLastError());
-    return PWV_OK;
+    Geom g;
+    PackedTables tab;
+    if (int e = varlen_check(a, who, g, tab, true)) return e;
+    return train_layer_fwd<ProjCond>(a, who, g, tab, [&](int grid, const LayerFwdParams& p) {
+        hipLaunchKernelGGL(train_layer_fwd_varlen_kernel, dim3(grid), dim3(kTrThreads), 0, (hipStream_t)stream, p);
+    });
 }
 
 extern "C" int pwv_train_varlen_layer_bwd_f32(const pwv_train_varlen_args* a, pwv_stream_t stream) {
     const char* who = "pwv_train_varlen_layer_bwd_f32";
-    LayerBwdParams p{};
-    if (int e = varlen_check(a, who, p.g, p.tab, true)) return e;
-    PWV_CHECK_ARG(a->form == PWV_TRAIN_RESIDUAL || a->form == PWV_TRAIN_LAST, "%s: form %d", who, a->form);
-    const bool last = a->form == PWV_TRAIN_LAST;
-    PWV_CHECK_ARG(a->x && a->proj && a->filter && a->gate, "%s: x, proj, filter or gate is a NULL pointer", who);
-    PWV_CHECK_ARG(a->u && a->v && a->d_proj && a->d_filter && a->d_gate, "%s: u, v, d_proj, d_filter or d_gate is a NULL pointer", who);
-    PWV_CHECK_ARG(a->d_proj_row_stride >= 128, "%s: d_proj_row_stride %d is below 128", who, a->d_proj_row_stride);
-    if (last) {
-        PWV_CHECK_ARG(a->d_o, "%s: d_o is a NULL pointer", who);
-    } else {
-        PWV_CHECK_ARG(a->dense && a->u_next && a->v_next && a->d_dense, "%s: dense, u_next, v_next or d_dense is a NULL pointer", who);
-        PWV_CHECK_ARG(a->next_dilation >= 1, "%s: next_dilation %d must be >= 1", who, a->next_dilation);
-        PWV_CHECK_ARG(a->u != a->u_next && a->v != a->v_next && a->u != a->v_next && a->v != a->u_next, "%s: u / v alias u_next / v_next", who);
-    }
-    const int grid = train_grid_size(a->max_workgroups, (p.g.rows + 31) / 32);
-    if (int e = varlen_check_ws(a, who, grid, kLayerPart)) return e;
-    p.x = a->x; p.proj = a->proj; p.filter = a->filter; p.gate = a->gate; p.dense = a->dense;
-    p.u_next = a->u_next; p.v_next = a->v_next; p.d_o = a->d_o;
-    p.u = a->u; p.v = a->v; p.d_proj = a->d_proj; p.part = (float*)a->workspace;
-    if (last) hipLaunchKernelGGL(train_layer_bwd_varlen_kernel<true>, dim3(grid), dim3(kTrThreads), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(train_layer_bwd_varlen_kernel<false>, dim3(grid), dim3(kTrThreads), 0, (hipStream_t)stream, p);
-    PWV_CHECK_HIP(hipGetLastError());
-    return train_reduce_layer(p.part, grid, last, a->d_filter, a->d_gate, a->d_dense, a->d_dense_bias, (hipStream_t)stream);
+    Geom g;
+    PackedTables tab;
+    if (int e = varlen_check(a, who, g, tab, true)) return e;
+    return train_layer_bwd<ProjCond>(a, who, g, tab, {}, nullptr, 0, (hipStream_t)stream, [&](bool last, int grid, const LayerBwdParams& p) {
+        if (last) hipLaunchKernelGGL(train_layer_bwd_varlen_kernel<true>, dim3(grid), dim3(kTrThreads), 0, (hipStream_t)stream, p);
+        else hipLaunchKernelGGL(train_layer_bwd_varlen_kernel<false>, dim3(grid), dim3(kTrThreads), 0, (hipStream_t)stream, p);
+    });
 }
 
 extern "C" int pwv_train_varlen_front_bwd_f32(const pwv_train_varlen_args* a, pwv_stream_t stream) {
     const char* who = "pwv_train_varlen_front_bwd_f32";
-    FrontBwdParams p{};
-    if (int e = varlen_check(a, who, p.g, p.tab, false)) return e;
-    PWV_CHECK_ARG(a->in && a->causal_filter && a->u_next && a->v_next && a->d_causal_filter,
-                  "%s: in, causal_filter, u_next, v_next or d_causal_filter is a NULL pointer", who);
-    PWV_CHECK_ARG(a->next_dilation >= 1, "%s: next_dilation %d must be >= 1", who, a->next_dilation);
-    const int grid = train_grid_size(a->max_workgroups, (p.g.rows + 31) / 32);
-    if (int e = varlen_check_ws(a, who, grid, kFrontPart)) return e;
-    p.in = a->in; p.cf = a->causal_filter; p.u_next = a->u_next; p.v_next = a->v_next; p.d_out = a->d_out; p.scale = a->scale;
-    p.d_in = a->d_in; p.part = (float*)a->workspace; p.accumulate = a->accumulate;
-    hipLaunchKernelGGL(train_front_bwd_varlen_kernel, dim3(grid), dim3(kTrThreads), 0, (hipStream_t)stream, p);
-    PWV_CHECK_HIP(hipGetLastError());
-    return train_reduce_front(p.part, grid, a->d_causal_filter, (hipStream_t)stream);
+    Geom g;
+    PackedTables tab;
+    if (int e = varlen_check(a, who, g, tab, false)) return e;
+    return train_front_bwd(a, who, g, tab, (hipStream_t)stream, [&](int grid, const FrontBwdParams& p) {
+        hipLaunchKernelGGL(train_front_bwd_varlen_kernel, dim3(grid), dim3(kTrThreads), 0, (hipStream_t)stream, p);
+    });
 }
 
 extern "C" size_t pwv_train_loss_varlen_workspace_bytes(const pwv_train_loss_varlen_args* a) {

@@ -232,8 +232,8 @@ class _CondGeometry(_Geometry):
     [N, T + hop, C] output of the last transposed-conv stage, through a row offset of hop / 2, and add to `d_cond` of the same shape
     (zeros to begin with: its margins are the crop's adjoint).  The front, the head and the loss are the uniform ones."""
 
-    def __init__(self, N, T, t_mel, C, max_workgroups):
-        super().__init__(N, T, t_mel, 0, max_workgroups)
+    def __init__(self, N, T, C, max_workgroups):
+        super().__init__(N, T, 0, 0, max_workgroups)         # no frames, no P: nothing here is at frame rate
         self.C = C
         self.cond = self.d_cond = None
         self.started = 0                    # the first layer backward of a step writes its rows of d_cond, the others add
@@ -318,24 +318,45 @@ def _net_backward(net: _Net, geo: _Geometry, saved, xin, d_out, d_mul, scale, d_
         workspace=ws, workspace_bytes=ws.numel() * 4))
 
 
-def _loss_head(pred, y, N, T, w):
-    """The loss head on the device (pwv_train_loss_f32): weight_l1 = 1, weight_power = w, hp.signal.win_length / hop_length.  Returns
-    (d_out [N T] float32, {'likelihood', 'power', 'total'} float32 device scalars); only enqueues."""
-    a = _lib.TrainLossArgs(out=_ptr(pred), y=_ptr(y), n=N, T=T, win_length=int(hp.signal.win_length), hop_length=int(hp.signal.hop_length),
-                           weight_l1=1.0, weight_power=float(w))
-    need = int(_lib.lib().pwv_train_loss_workspace_bytes(ctypes.byref(a)))
+def _loss_head(pred, y, shape, w):
+    """The loss head on the device: weight_l1 = 1, weight_power = w, hp.signal.win_length / hop_length.  `shape`: (N, T) of a uniform
+    batch (pwv_train_loss_f32) or the engine.VarlenGeometry of a packed one (pwv_train_loss_varlen_f32: the lengths are read from
+    layout.cu_rows on the device).  Returns (d_out [rows] float32, {'likelihood', 'power', 'total'} float32 device scalars); only
+    enqueues."""
+    kw = dict(out=_ptr(pred), y=_ptr(y), win_length=int(hp.signal.win_length), hop_length=int(hp.signal.hop_length), weight_l1=1.0,
+              weight_power=float(w))
+    if isinstance(shape, tuple):
+        (n, T), name = shape, 'pwv_train_loss'
+        rows, a = n * T, _lib.TrainLossArgs(n=n, T=T, **kw)
+    else:
+        n, rows, name = shape.n, shape.rows, 'pwv_train_loss_varlen'
+        a = _lib.TrainLossVarlenArgs(cu_rows=_ptr(shape.cu_rows), n=n, rows=rows, **kw)
+    need = int(getattr(_lib.lib(), name + '_workspace_bytes')(ctypes.byref(a)))
     if not need:
-        _lib.check(-1, 'pwv_train_loss_workspace_bytes')
-    d_out = torch.empty(N * T, dtype=torch.float32, device=pred.device)
-    table = torch.empty((N, 4), dtype=torch.float64, device=pred.device)
+        _lib.check(-1, name + '_workspace_bytes')
+    d_out = torch.empty(rows, dtype=torch.float32, device=pred.device)
+    table = torch.empty((n, 4), dtype=torch.float64, device=pred.device)
     work = torch.empty(need // 8, dtype=torch.float64, device=pred.device)
     a.d_out, a.result, a.workspace, a.workspace_bytes = _ptr(d_out), _ptr(table), _ptr(work), need
-    _call('pwv_train_loss_f32', a)
+    _call(name + '_f32', a)
     sums = table.sum(dim=0)                                              # {abs_sum, samples, power_sum, terms} of the batch
     likelihood = sums[0] / sums[1]
     power = sums[2] / sums[3] if w > 0 else torch.zeros_like(likelihood)       # (weight 0: no frame is formed, terms = 0)
     total = likelihood + float(w) * power
     return d_out, {'likelihood': likelihood.to(torch.float32), 'power': power.to(torch.float32), 'total': total.to(torch.float32)}
+
+
+def _head(shape, rows, power_weight, terms):
+    """head(pred, y) -> (loss, d_out [rows]) of _forward_backward: the L1 in torch (power_weight None) or _loss_head on `shape`."""
+    def head(x, y):
+        if power_weight is None:
+            diff = x - y
+            return diff.abs().mean(), torch.sign(diff) / float(rows)
+        d_out, parts = _loss_head(x.contiguous(), y.contiguous(), shape, float(power_weight))
+        if terms is not None:
+            terms.update(parts)
+        return parts['total'], d_out
+    return head
 
 
 def loss_and_grad(model, wav, melspec, z=None, seed=None, max_workgroups: int = 0, power_weight: Optional[float] = None,
@@ -374,21 +395,12 @@ def loss_and_grad(model, wav, melspec, z=None, seed=None, max_workgroups: int = 
     flows = model_nets(model, store)
     cols = sum(128 * len(net.dilations) for pair in flows for net in pair)
     if hp.model.cond_upsample_method == 'transposed_conv':
-        geo = _CondGeometry(N, T, t_mel, int(hp.model.condition_channels), int(max_workgroups))
+        geo = _CondGeometry(N, T, int(hp.model.condition_channels), int(max_workgroups))
     else:
         geo = _Geometry(N, T, t_mel, cols, int(max_workgroups))
 
-    def head(x, y):
-        if power_weight is None:
-            diff = x - y
-            return diff.abs().mean(), torch.sign(diff) / float(N * T)
-        d_out, parts = _loss_head(x.contiguous(), y.contiguous(), N, T, float(power_weight))
-        if terms is not None:
-            terms.update(parts)
-        return parts['total'], d_out
-
     loss, x, grads = _forward_backward(store, flows, geo, melspec.reshape(N * t_mel, n_mels), noise.reshape(N * T).contiguous(),
-                                       wav.reshape(N * T), head)
+                                       wav.reshape(N * T), _head((N, T), N * T, power_weight, terms))
     return loss, x.reshape(N, T, 1), grads
 
 
@@ -502,27 +514,6 @@ def _fill_unread(store, grads, loss, x):
 
 
 # ---- packed batches: utterances of different lengths, unpadded ("Packed training") ------------------------------
-def _loss_head_varlen(pred, y, layout, w):
-    """The packed loss head on the device (pwv_train_loss_varlen_f32): weight_l1 = 1, weight_power = w, hp.signal.win_length /
-    hop_length, the lengths read from layout.cu_rows on the device.  Returns (d_out [rows] float32, {'likelihood', 'power', 'total'}
-    float32 device scalars); only enqueues."""
-    a = _lib.TrainLossVarlenArgs(out=_ptr(pred), y=_ptr(y), cu_rows=_ptr(layout.cu_rows), n=layout.n, rows=layout.rows,
-                                 win_length=int(hp.signal.win_length), hop_length=int(hp.signal.hop_length), weight_l1=1.0, weight_power=float(w))
-    need = int(_lib.lib().pwv_train_loss_varlen_workspace_bytes(ctypes.byref(a)))
-    if not need:
-        _lib.check(-1, 'pwv_train_loss_varlen_workspace_bytes')
-    d_out = torch.empty(layout.rows, dtype=torch.float32, device=pred.device)
-    table = torch.empty((layout.n, 4), dtype=torch.float64, device=pred.device)
-    work = torch.empty(need // 8, dtype=torch.float64, device=pred.device)
-    a.d_out, a.result, a.workspace, a.workspace_bytes = _ptr(d_out), _ptr(table), _ptr(work), need
-    _call('pwv_train_loss_varlen_f32', a)
-    sums = table.sum(dim=0)                                              # {abs_sum, samples, power_sum, terms} of the batch
-    likelihood = sums[0] / sums[1]
-    power = sums[2] / sums[3] if w > 0 else torch.zeros_like(likelihood)
-    total = likelihood + float(w) * power
-    return d_out, {'likelihood': likelihood.to(torch.float32), 'power': power.to(torch.float32), 'total': total.to(torch.float32)}
-
-
 def loss_and_grad_varlen(model, wavs, mels, z=None, seeds=None, max_workgroups: int = 0, power_weight: Optional[float] = None,
                          terms: Optional[dict] = None):
     """loss_and_grad over utterances of DIFFERENT lengths in one packed batch, without padding: (loss, preds, grads).  wavs[i] is [T_i] or
@@ -582,17 +573,8 @@ def loss_and_grad_varlen(model, wavs, mels, z=None, seeds=None, max_workgroups: 
     cols = sum(128 * len(net.dilations) for pair in flows for net in pair)
     geo = _PackedGeometry(layout, cols, int(max_workgroups))
 
-    def head(x, y):
-        if power_weight is None:
-            diff = x - y
-            return diff.abs().mean(), torch.sign(diff) / float(layout.rows)
-        d_out, parts = _loss_head_varlen(x.contiguous(), y.contiguous(), layout, float(power_weight))
-        if terms is not None:
-            terms.update(parts)
-        return parts['total'], d_out
-
     loss, x, grads = _forward_backward(store, flows, geo, torch.cat(mels), noise.reshape(layout.rows).contiguous(),
-                                       torch.cat([w.reshape(-1) for w in wavs]), head)
+                                       torch.cat([w.reshape(-1) for w in wavs]), _head(layout, layout.rows, power_weight, terms))
     packed = x.reshape(layout.rows, 1)
     return loss, [packed[a:b] for a, b in zip(layout.cu_rows_host, layout.cu_rows_host[1:])], grads
 
