@@ -8,13 +8,16 @@
 // Two kernels, no atomics: score_partials_kernel writes one partial per (utterance, frame) and per (utterance, tile of samples),
 // score_reduce_kernel adds an utterance's partials in an order that depends on their index within the utterance alone -- a row of the
 // result does not depend on what else is in the batch.  The lengths of a packed batch are read on the device (cu_rows): the grid is sized
-// from the capacities, every workgroup finds its utterance by bisection and leaves if its slot is not in use.
+// from the capacities, every workgroup finds its utterance by bisection and leaves if its slot is not in use (pwv_spans.h, which the
+// loss head of training, csrc/pwv_train_loss.hip, shares; the DFT body here is this file's own: its Nyquist bin goes through the twiddle
+// table, the loss head's through a reduction).
 #include "pwv_common.h"
 #include "pwv_hip_score.h"
+#include "pwv_spans.h"
 
 namespace pwv {
 
-constexpr int kScoreThreads = 256;      // workgroup size of both kernels, and the stride of the reduction's first pass
+constexpr int kScoreThreads = kSumThreads;      // workgroup size of both kernels, and the stride of the reduction's first pass
 constexpr int kScoreTile = PWV_SCORE_TILE;
 
 struct ScoreParams {
@@ -27,58 +30,20 @@ struct ScoreParams {
     int n, T, win, hop, nfft;
 };
 
-// bound i of the batch (0 .. n), inside 0 .. rows whatever the table holds
-__device__ __forceinline__ long long score_bound(const ScoreParams& p, int i) {
-    const long long v = p.cu ? (long long)p.cu[i] : (long long)i * p.T;
-    return v < 0 ? 0 : (v > p.rows ? p.rows : v);
-}
-
-// utterance i = samples [s, e)
-__device__ __forceinline__ void score_span(const ScoreParams& p, int i, long long& s, long long& e) {
-    s = score_bound(p, i);
-    e = score_bound(p, i + 1);
-    if (e < s) e = s;
-}
-
-__device__ __forceinline__ long long score_frames(const ScoreParams& p, long long L) {
-    return p.win < 1 || L < p.win ? 0 : 1 + (L - p.win) / p.hop;
-}
-
-// The utterance that owns `slot` where utterance i's slots begin at bound(i) / unit + i (strictly increasing in i), and the slot's index
-// within it (negative: before the first utterance's).  Every thread of the workgroup gets the same answer.
-__device__ __forceinline__ int score_owner(const ScoreParams& p, long long slot, int unit, long long& idx) {
-    int lo = 0, hi = p.n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (score_bound(p, mid) / unit + mid <= slot) lo = mid; else hi = mid - 1;
-    }
-    idx = slot - (score_bound(p, lo) / unit + lo);
-    return lo;
-}
-
-// the sum of the workgroup's 256 values, added as a fixed tree; every thread gets it
-__device__ __forceinline__ double score_block_sum(double v, double* red) {
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = kScoreThreads / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
+// (the parameters keep the layout they had before pwv_spans.h: both kernels compile to the instruction streams of before)
+__device__ __forceinline__ Spans score_spans(const ScoreParams& p) { return Spans{p.cu, p.rows, p.n, p.T, p.win, p.hop}; }
 
 // blockIdx.x < frame_slots: a frame slot; else a tile slot
 __global__ __launch_bounds__(256) void score_partials_kernel(ScoreParams p) {
     extern __shared__ __attribute__((aligned(16))) double score_sm[];      // [256] reduction, [win] out frame, [win] y frame, [nfft] cos, [nfft] sin
     double* red = score_sm;
     const int tid = threadIdx.x;
+    const Spans sp = score_spans(p);
     long long slot = blockIdx.x, idx, s, e;
     if (slot < p.frame_slots) {
-        const int i = score_owner(p, slot, p.hop, idx);
-        score_span(p, i, s, e);
-        if (idx < 0 || idx >= score_frames(p, e - s)) return;             // (uniform over the workgroup: before any barrier)
+        const int i = span_owner(sp, slot, p.hop, idx);
+        span_of(sp, i, s, e);
+        if (idx < 0 || idx >= span_frames(sp, e - s)) return;                 // (uniform over the workgroup: before any barrier)
         const int win = p.win, nfft = p.nfft;
         double* fa = red + kScoreThreads;
         double* fb = fa + win;
@@ -113,18 +78,18 @@ __global__ __launch_bounds__(256) void score_partials_kernel(ScoreParams p) {
             const double d = (ar * ar + ai * ai) - (br * br + bi * bi);
             acc = fma(d, d, acc);
         }
-        acc = score_block_sum(acc, red);
+        acc = block_sum(acc, red);
         if (tid == 0) p.part[slot] = acc;
         return;
     }
     slot -= p.frame_slots;
-    const int i = score_owner(p, slot, kScoreTile, idx);
-    score_span(p, i, s, e);
+    const int i = span_owner(sp, slot, kScoreTile, idx);
+    span_of(sp, i, s, e);
     const long long L = e - s, first = idx * kScoreTile;
     if (idx < 0 || first >= L) return;
     double acc = 0.0;
     for (long long t = first + tid; t < first + kScoreTile && t < L; t += kScoreThreads) acc += fabs((double)p.out[s + t] - (double)p.y[s + t]);
-    acc = score_block_sum(acc, red);
+    acc = block_sum(acc, red);
     if (tid == 0) p.part[p.frame_slots + slot] = acc;
 }
 
@@ -132,9 +97,10 @@ __global__ __launch_bounds__(256) void score_partials_kernel(ScoreParams p) {
 __global__ __launch_bounds__(256) void score_reduce_kernel(ScoreParams p) {
     __shared__ double red[kScoreThreads];
     const int i = blockIdx.x, tid = threadIdx.x;
+    const Spans sp = score_spans(p);
     long long s, e;
-    score_span(p, i, s, e);
-    const long long L = e - s, frames = score_frames(p, L), tiles = (L + kScoreTile - 1) / kScoreTile;
+    span_of(sp, i, s, e);
+    const long long L = e - s, frames = span_frames(sp, L), tiles = (L + kScoreTile - 1) / kScoreTile;
     double pw = 0.0, l1 = 0.0;
     if (frames > 0) {
         const double* part = p.part + (s / p.hop + i);
@@ -142,8 +108,8 @@ __global__ __launch_bounds__(256) void score_reduce_kernel(ScoreParams p) {
     }
     const double* part = p.part + p.frame_slots + (s / kScoreTile + i);
     for (long long t = tid; t < tiles; t += kScoreThreads) l1 += part[t];
-    pw = score_block_sum(pw, red);
-    l1 = score_block_sum(l1, red);
+    pw = block_sum(pw, red);
+    l1 = block_sum(l1, red);
     if (tid == 0) {
         double* r = p.result + 4 * (size_t)i;
         r[0] = l1;

@@ -19,20 +19,7 @@ namespace pwv {
 // ------------------------------------------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kTrThreads) void train_front_fwd_kernel(const float* __restrict__ in, const float* __restrict__ cf, float* __restrict__ x0,
-                                                                     int rows, int T) {
-    const int u = blockIdx.x;
-    for (int idx = threadIdx.x; idx < 512; idx += kTrThreads) {
-        const int q = idx >> 5, r = idx & 31, row = 32 * u + r;
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (row < rows) {
-            const float cur = in[row], prev = row % T > 0 ? in[row - 1] : 0.f;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = prev * cf[4 * q + e] + cur * cf[64 + 4 * q + e];
-        }
-        *reinterpret_cast<f32x4*>(x0 + (size_t)u * 2048 + q * 128 + r * 4) = v;
-    }
-}
+__global__ __launch_bounds__(kTrThreads) void train_front_fwd_kernel(FrontFwdParams p) { front_fwd_body<UniformGeo>(p); }
 
 __global__ __launch_bounds__(kTrThreads) void train_layer_fwd_kernel(LayerFwdParams p) { layer_fwd_body<UniformGeo, ProjCond>(p, {}); }
 
@@ -223,14 +210,17 @@ int train_grid_size(int max_workgroups, int units) {
 
 static int train_grid(const pwv_train_args* a, int units) { return train_grid_size(a->max_workgroups, units); }
 
-static int train_check(const pwv_train_args* a, const char* who) {
+int train_check_batch(const pwv_train_args* a, const char* who, const char* field, size_t size, const char* name) {
     PWV_CHECK_ARG(a, "%s: args is NULL", who);
-    PWV_CHECK_ARG(a->struct_size == sizeof(pwv_train_args), "%s: struct_size %zu is not sizeof(pwv_train_args) = %zu", who, a->struct_size,
-                  sizeof(pwv_train_args));
+    PWV_CHECK_ARG(a->struct_size == size, "%s: %s %zu is not sizeof(%s) = %zu", who, field, a->struct_size, name, size);
     PWV_CHECK_ARG(a->N >= 1 && a->T >= 1, "%s: N = %d, T = %d must be >= 1", who, a->N, a->T);
     PWV_CHECK_ARG((long long)a->N * a->T < (1ll << 31) - 64, "%s: N T = %lld is beyond int32", who, (long long)a->N * a->T);
     PWV_CHECK_ARG(a->max_workgroups >= 0, "%s: max_workgroups %d is negative", who, a->max_workgroups);
     return PWV_OK;
+}
+
+static int train_check(const pwv_train_args* a, const char* who) {
+    return train_check_batch(a, who, "struct_size", sizeof(pwv_train_args), "pwv_train_args");
 }
 
 static int train_geom(const pwv_train_args* a, const char* who, Geom& g, bool layer) {
@@ -274,12 +264,11 @@ extern "C" size_t pwv_train_workspace_bytes(const pwv_train_args* a) {
 extern "C" int pwv_train_front_fwd_f32(const pwv_train_args* a, pwv_stream_t stream) {
     const char* who = "pwv_train_front_fwd_f32";
     if (int e = train_check(a, who)) return e;
-    PWV_CHECK_ARG(a->in && a->causal_filter && a->x_out, "%s: in, causal_filter or x_out is a NULL pointer", who);
-    const int rows = a->N * a->T;
-    hipLaunchKernelGGL(train_front_fwd_kernel, dim3((rows + 31) / 32), dim3(kTrThreads), 0, (hipStream_t)stream, a->in, a->causal_filter, a->x_out,
-                       rows, a->T);
-    PWV_CHECK_HIP(hipGetLastError());
-    return PWV_OK;
+    Geom g;
+    if (int e = train_geom(a, who, g, false)) return e;
+    return train_front_fwd(a, who, g, PackedTables{}, [&](int grid, const FrontFwdParams& p) {
+        hipLaunchKernelGGL(train_front_fwd_kernel, dim3(grid), dim3(kTrThreads), 0, (hipStream_t)stream, p);
+    });
 }
 
 extern "C" int pwv_train_layer_fwd_f32(const pwv_train_args* a, pwv_stream_t stream) {

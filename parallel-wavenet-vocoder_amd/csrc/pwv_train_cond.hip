@@ -147,11 +147,7 @@ __global__ __launch_bounds__(kTrThreads, 2) void train_cond_layer_bwd_kernel(Lay
 static int cond_check(const pwv_train_cond_args* c, const char* who, bool sizes_only, Geom& g, CondParams& cp) {
     PWV_CHECK_ARG(c, "%s: args is NULL", who);
     const pwv_train_args* a = &c->train;
-    PWV_CHECK_ARG(a->struct_size == sizeof(pwv_train_cond_args), "%s: train.struct_size %zu is not sizeof(pwv_train_cond_args) = %zu", who,
-                  a->struct_size, sizeof(pwv_train_cond_args));
-    PWV_CHECK_ARG(a->N >= 1 && a->T >= 1, "%s: N = %d, T = %d must be >= 1", who, a->N, a->T);
-    PWV_CHECK_ARG((long long)a->N * a->T < (1ll << 31) - 64, "%s: N T = %lld is beyond int32", who, (long long)a->N * a->T);
-    PWV_CHECK_ARG(a->max_workgroups >= 0, "%s: max_workgroups %d is negative", who, a->max_workgroups);
+    if (int e = train_check_batch(a, who, "train.struct_size", sizeof(pwv_train_cond_args), "pwv_train_cond_args")) return e;
     PWV_CHECK_ARG(c->cond_channels >= 2 && c->cond_channels <= kCondMax && c->cond_channels % 2 == 0,
                   "%s: cond_channels %d must be even and in 2 .. %d", who, c->cond_channels, kCondMax);
     cp = CondParams{c->cond, c->gc_filter, c->gc_gate, c->filter_bias, c->gate_bias, c->d_cond,

@@ -1,31 +1,18 @@
-// What the loss head of training shares between its uniform form (csrc/pwv_train_loss.hip) and its packed form
-// (csrc/pwv_train_varlen.hip): the workgroup reduction and the body of one frame -- the direct real DFT of both windowed frames in fp64
-// and the same twiddle table run backward into the frame's gradient.
+// The body of one frame of training's loss head (csrc/pwv_train_loss.hip, both its forms): the direct real DFT of both windowed frames
+// in fp64 and the same twiddle table run backward into the frame's gradient.  The workgroup sum is block_sum of pwv_spans.h.
 #ifndef PWV_TRAIN_LOSS_FRAME_H
 #define PWV_TRAIN_LOSS_FRAME_H
 
 #include "pwv_common.h"
 #include "pwv_hip_score.h"
+#include "pwv_spans.h"
 
 namespace pwv {
 
-constexpr int kLossThreads = 256;       // workgroup size of both kernels, and the stride of the reduction's first pass
+constexpr int kLossThreads = kSumThreads;      // workgroup size of both kernels, and the stride of the reduction's first pass
 constexpr int kLossTile = PWV_SCORE_TILE;
 
 typedef double f64x2 __attribute__((ext_vector_type(2)));
-
-// the sum of the workgroup's 256 values, added as a fixed tree; every thread gets it
-__device__ __forceinline__ double loss_block_sum(double v, double* red) {
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = kLossThreads / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
 
 // One frame, by the whole workgroup: a, b = the win samples of out and y; the frame's power partial goes to *part, its win gradient
 // values (unscaled) to g.  red: LDS, [256] reduction, [nfft] (cos, sin), [nfft / 2 + 1] D (Ar, Ai), [win] (out, y) under the window.
@@ -68,15 +55,15 @@ __device__ __forceinline__ void loss_frame(const float* a, const float* b, int w
             na += (j & 1) ? -v.x : v.x;
             nb += (j & 1) ? -v.y : v.y;
         }
-        na = loss_block_sum(na, red);
-        nb = loss_block_sum(nb, red);
+        na = block_sum(na, red);
+        nb = block_sum(nb, red);
         if (tid == 0) {
             const double d = na * na - nb * nb;
             cw[half] = f64x2{d * na, 0.0};
             acc = fma(d, d, acc);
         }
     }
-    acc = loss_block_sum(acc, red);                                   // (its barriers also publish cw)
+    acc = block_sum(acc, red);                                        // (its barriers also publish cw)
     if (tid == 0) *part = acc;
     for (int j = tid; j < win; j += kLossThreads) {
         double sr = 0.0, si = 0.0;

@@ -13,6 +13,8 @@
 //   weight gradients         A[i][k = row] and B[k = row][j] both from LDS: the 32 rows of the unit are the K dimension, the tile stays in
 //                            the wave's accumulators over all units of the workgroup and leaves once, as the workgroup's partial.
 // A second launch (train_reduce_kernel, csrc/pwv_train.hip) adds the partials in a fixed order and scatters them to the TF layouts.
+// Behind the bodies the host text of the four entry-point kinds (train_front_fwd, train_layer_fwd, train_layer_bwd, train_front_bwd),
+// once for every ABI struct; what a uniform struct is checked for first is train_check_batch of csrc/pwv_train.hip.
 #ifndef PWV_TRAIN_UNITS_H
 #define PWV_TRAIN_UNITS_H
 
@@ -312,6 +314,31 @@ struct ProjCond {
 // ------------------------------------------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------------------------------------------
+struct FrontFwdParams {
+    const float *in, *cf;
+    float* x0;
+    Geom g;
+    PackedTables tab;
+};
+
+// x_0[t] = in[t - 1] cf[0] + in[t] cf[1], in[-1] = 0 at every utterance's first sample; one unit per workgroup
+template <class Geo>
+__device__ __forceinline__ void front_fwd_body(const FrontFwdParams& p) {
+    __shared__ typename Geo::Loc loc;
+    const int u = blockIdx.x;
+    Geo::locate(loc, u, p.g, p.tab);
+    for (int idx = threadIdx.x; idx < 512; idx += kTrThreads) {
+        const int q = idx >> 5, r = idx & 31, row = 32 * u + r;
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (row < p.g.rows) {
+            const float cur = p.in[row], prev = Geo::t(loc, r, row, p.g) > 0 ? p.in[row - 1] : 0.f;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = prev * p.cf[4 * q + e] + cur * p.cf[64 + 4 * q + e];
+        }
+        *reinterpret_cast<f32x4*>(p.x0 + (size_t)u * 2048 + q * 128 + r * 4) = v;
+    }
+}
+
 template <class Geo, class Cond>
 __device__ __forceinline__ void layer_fwd_body(const LayerFwdParams& p, const typename Cond::Params& cp) {
     __shared__ float a[32 * kLdW];
@@ -506,8 +533,10 @@ struct ReduceParams {
 
 int train_reduce(const ReduceParams& rp, hipStream_t st);
 int train_grid_size(int max_workgroups, int units);
+// what every uniform entry point checks first: the struct (`field` of size `size` = sizeof(`name`)), N, T, N T and max_workgroups
+int train_check_batch(const pwv_train_args* a, const char* who, const char* field, size_t size, const char* name);
 
-// The three entry-point kinds that depend on where an utterance begins, once for every ABI struct: pwv_train_args (also as the head of
+// The four entry-point kinds that depend on where an utterance begins, once for every ABI struct: pwv_train_args (also as the head of
 // pwv_train_cond_args) and pwv_train_varlen_args share the names of the fields read here.  The caller has checked the struct and its
 // geometry and filled `g`, `tab` and the condition's parameters; `launch` enqueues its kernel on its stream.
 template <class Args>
@@ -515,6 +544,18 @@ int train_check_ws(const Args* a, const char* who, int grid, int part) {
     PWV_CHECK_ARG(a->workspace, "%s: workspace is a NULL pointer", who);
     PWV_CHECK_ARG(a->workspace_bytes >= (size_t)grid * part * sizeof(float), "%s: workspace_bytes %zu is short of %zu", who, a->workspace_bytes,
                   (size_t)grid * part * sizeof(float));
+    return PWV_OK;
+}
+
+template <class Args, class Launch>
+int train_front_fwd(const Args* a, const char* who, const Geom& g, const PackedTables& tab, Launch launch) {      // launch(grid, p)
+    PWV_CHECK_ARG(a->in && a->causal_filter && a->x_out, "%s: in, causal_filter or x_out is a NULL pointer", who);
+    FrontFwdParams p{};
+    p.in = a->in; p.cf = a->causal_filter; p.x0 = a->x_out;
+    p.g = g;
+    p.tab = tab;
+    launch((g.rows + 31) / 32, p);
+    PWV_CHECK_HIP(hipGetLastError());
     return PWV_OK;
 }
 

@@ -32,6 +32,7 @@ from __future__ import annotations
 
 import collections
 import ctypes
+import gc
 from typing import Optional
 
 import numpy as np
@@ -94,6 +95,12 @@ class _Captured(object):
         self._after_warmup()
         graph = torch.cuda.CUDAGraph()
         saved, engine.EVENT_LOG = engine.EVENT_LOG, None       # (the log brackets launches with timing events: not inside a capture)
+        # No garbage collection inside the capture either: torch.cuda.graph does not collect before it begins, so a collection that
+        # falls due while the forward is enqueued would run the finalizers of dead cycles from before -- device and pinned memory,
+        # events -- as runtime calls of the capturing thread, which are none of the captured ones and which the runtime may refuse.
+        # Whatever is due is collected behind the capture.
+        collecting = gc.isenabled()
+        gc.disable()
         try:
             # thread_local: only this thread's calls are policed during capture (an RCCL watchdog thread of a multi-rank
             # job may touch the runtime meanwhile); everything captured here is enqueued from this thread
@@ -101,6 +108,8 @@ class _Captured(object):
                 self.out = self._enqueue()
         finally:
             engine.EVENT_LOG = saved
+            if collecting:
+                gc.enable()
         self.graph = graph
         self._version = self.store.version
         self._mode = engine.launch_knobs()

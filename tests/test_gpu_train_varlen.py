@@ -347,6 +347,24 @@ def test_packed_loss_head_keeps_utterances_apart(gpu):
         assert not torch.equal(ta[i, 0], tb[i, 0])
 
 
+@pytest.mark.parametrize('weights', [(1.0, 1.0), (0.0, 1.0), (1.0, 0.0)], ids=['both', 'power', 'l1'])
+@pytest.mark.parametrize('T,win,hop', [(208, 48, 16), (100, 16, 24), (210, 48, 20), (4400, 48, 16)])
+def test_equal_lengths_give_the_bits_of_the_uniform_loss_head(gpu, T, win, hop, weights):
+    """Two utterances of equal length T through pwv_train_loss_varlen_f32 with cu_rows = [0, T, 2 T] and through pwv_train_loss_f32: d_out
+    and the [n, 4] table are the same bits.  Both forms divide 4 w by the same integer n F B and weight_l1 by the same n T, add a
+    sample's frames in ascending f and an utterance's partials in the same order.  The shapes: nfft above win; hop above win (gaps and a
+    tail); a tail behind the last frame; 273 frames and 5 tiles per utterance (the strided partial sums make a second pass, the gather
+    crosses tile boundaries).  The data: train_power_oracle.case(T, 2); at T = 4400 with seed 1, since none of the 50 draws of seed 0
+    keeps all 8800 samples clear of a zero difference, which case() insists on."""
+    from tests.test_gpu_train_power import _loss_head as _uniform_loss_head
+    pred, y = PO.case(T, 2, seed=1 if T == 4400 else 0)
+    wl1, wp = weights
+    d_u, table_u = _uniform_loss_head(pred, y, win, hop, wl1, wp, gpu)
+    d_p, table_p = _loss_head(list(pred), list(y), win, hop, wl1, wp, gpu)
+    assert torch.isfinite(d_u).all() and torch.isfinite(table_u).all()
+    assert torch.equal(d_p, d_u.reshape(-1)) and torch.equal(table_p, table_u)
+
+
 @pytest.fixture()
 def small_power(gpu):
     from pwv_amd.hparam import hparam as hp

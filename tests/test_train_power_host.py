@@ -219,10 +219,13 @@ def test_small_power_case_is_small_plus_the_weight():
 
 
 def test_train_loss_kernel_resources():
-    """The compiler's resource remarks (gfx950 device code) for both kernels of csrc/pwv_train_loss.hip: no scratch, no spilled register;
-    the largest dynamic LDS request, at win = nfft = 1024, fits the 64 KiB a workgroup may ask for."""
+    """The compiler's resource remarks (gfx950 device code) for the four kernels of csrc/pwv_train_loss.hip, the uniform and the packed
+    instances of the loss head: no scratch, no spilled register; the largest dynamic LDS request, at win = nfft = 1024, fits the 64 KiB
+    a workgroup may ask for."""
     res = kernel_resources('pwv_train_loss.hip')
-    assert len(res) == 2 and any('loss_frames_kernel' in n for n in res) and any('loss_gather_kernel' in n for n in res), sorted(res)
+    assert len(res) == 4, sorted(res)
+    for k in ('loss_frames_kernel', 'loss_gather_kernel', 'loss_frames_varlen_kernel', 'loss_gather_varlen_kernel'):
+        assert any(k in n for n in res), (k, sorted(res))
     for name, r in res.items():
         assert r['scratch'] == 0 and r['vgpr_spills'] == 0 and r['sgpr_spills'] == 0 and not r['dynamic_stack'], (name, r)
     assert 8 * (256 + 2 * 1024 + 2 * 513 + 2 * 1024) <= 64 * 1024
