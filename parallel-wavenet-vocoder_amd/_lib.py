@@ -19,7 +19,7 @@ _REPO_ROOT = os.path.dirname(_PKG_DIR)
 LIB_PATH = os.environ.get('PWV_LIB') or os.path.join(_PKG_DIR, 'libpwv_hip.so')   # PWV_LIB: A/B another build
 CSRC = [os.path.join(_PKG_DIR, 'csrc', f) for f in ('pwv_layer.hip', 'pwv_layer_f16.hip', 'pwv_layer_h16.hip', 'pwv_misc.hip',
                                                     'pwv_stack_persist.hip', 'pwv_norm.hip', 'pwv_audio.hip', 'pwv_stream_tick.hip', 'pwv_score.hip', 'pwv_train.hip', 'pwv_train_loss.hip',
-                                                    'pwv_train_varlen.hip', 'pwv_train_cond.hip')]
+                                                    'pwv_train_varlen.hip', 'pwv_train_cond.hip', 'pwv_train_opt.hip')]
 
 HEADER_VERSION = 301          # PWV_HIP_VERSION of include/pwv_hip.h these ctypes mirrors were written against
 FIRST_FOLD_FLOATS = 2048      # PWV_FIRST_FOLD_FLOATS
@@ -62,6 +62,11 @@ TRAIN_VARLEN_SYMBOLS = ('pwv_train_varlen_front_fwd_f32', 'pwv_train_varlen_laye
 # ... and of include/pwv_hip_train_cond.h: the layer kernels of training with a per-sample (transposed-conv) condition
 TRAIN_COND_SYMBOLS = ('pwv_train_cond_workspace_bytes', 'pwv_train_cond_layer_fwd_f32', 'pwv_train_cond_layer_bwd_f32')
 TRAIN_COND_MAX = 96           # PWV_TRAIN_COND_MAX: condition channels the per-sample layer kernels take
+# ... and of include/pwv_hip_train_opt.h: the gradient arena (pack / unpack) and the fused Adam + EMA over it
+TRAIN_OPT_SYMBOLS = ('pwv_train_opt_pack_f32', 'pwv_train_opt_unpack_f32', 'pwv_train_opt_adam_ema_f32')
+TRAIN_OPT_REC = 3             # PWV_TRAIN_OPT_REC: int64 per record of an arena table = {tensor address, arena offset, count}
+TRAIN_OPT_CHUNK = 1024        # PWV_TRAIN_OPT_CHUNK: floats per record of a block map
+TRAIN_OPT_MAX_GRID = 2048     # PWV_TRAIN_OPT_MAX_GRID: workgroups of a launch at most
 
 
 class PwvError(RuntimeError):
@@ -448,6 +453,48 @@ class TrainLossVarlenArgs(Structure):
         self.struct_size = ctypes.sizeof(TrainLossVarlenArgs)
 
 
+class TrainOptPackArgs(Structure):
+    """pwv_train_opt_pack_args: tensors into an arena, or an arena into the tensors (include/pwv_hip_train_opt.h)."""
+    _fields_ = [
+        ('struct_size', c_size_t),      # set by __init__
+        ('table', c_void_p),
+        ('block_map', c_void_p),
+        ('table_host', c_void_p),
+        ('block_map_host', c_void_p),
+        ('arena', c_void_p),
+        ('arena_floats', c_int64),
+        ('n', ctypes.c_int32), ('blocks', ctypes.c_int32),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = ctypes.sizeof(TrainOptPackArgs)
+
+
+class TrainOptAdamArgs(Structure):
+    """pwv_train_opt_adam_args: one Adam + EMA step over the arenas (include/pwv_hip_train_opt.h)."""
+    _fields_ = [
+        ('struct_size', c_size_t),      # set by __init__
+        ('table', c_void_p),
+        ('block_map', c_void_p),
+        ('table_host', c_void_p),
+        ('block_map_host', c_void_p),
+        ('grad', c_void_p),
+        ('m', c_void_p),
+        ('v', c_void_p),
+        ('shadow', c_void_p),
+        ('arena_floats', c_int64),
+        ('n', ctypes.c_int32), ('blocks', ctypes.c_int32),
+        ('lr_t', ctypes.c_double), ('beta1', ctypes.c_double), ('beta2', ctypes.c_double), ('eps', ctypes.c_double),
+        ('decay', ctypes.c_double),
+        ('grad_scale', ctypes.c_double),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = ctypes.sizeof(TrainOptAdamArgs)
+
+
 # per-source extra flags (none in the product; tools/probes/regw/README.md: the register-stationary probe kernel needs
 # `-mllvm -amdgpu-mfma-vgpr-form=1`, which is why the sources are compiled one by one)
 EXTRA_FLAGS = {}
@@ -615,6 +662,9 @@ def _declare(lib):
     lib.pwv_train_cond_workspace_bytes.argtypes = [POINTER(TrainCondArgs)]
     for name in TRAIN_COND_SYMBOLS[1:]:
         getattr(lib, name).argtypes = [POINTER(TrainCondArgs), c_void_p]
+    lib.pwv_train_opt_pack_f32.argtypes = [POINTER(TrainOptPackArgs), c_void_p]
+    lib.pwv_train_opt_unpack_f32.argtypes = [POINTER(TrainOptPackArgs), c_void_p]
+    lib.pwv_train_opt_adam_ema_f32.argtypes = [POINTER(TrainOptAdamArgs), c_void_p]
     lib.pwv_instance_norm_workspace_bytes.restype = c_size_t
     lib.pwv_instance_norm_workspace_bytes.argtypes = [c_int, c_int, c_int]
     lib.pwv_instance_norm_f32.argtypes = [f32p, f32p, c_int, c_int, c_int, f32p, f32p, ctypes.c_float, c_void_p, c_size_t, c_void_p]
@@ -636,7 +686,7 @@ def _declare(lib):
     lib.pwv_status_words_alloc.argtypes = [POINTER(c_void_p)]
     lib.pwv_status_words_free.argtypes = [c_void_p]
     lib.pwv_range_check_f32.argtypes = [f32p, c_int64, ctypes.c_float, c_void_p, c_void_p]
-    for name in EXPORTED_SYMBOLS + EXTENSION_SYMBOLS + LIVE_TICK_SYMBOLS + SCORE_SYMBOLS + TRAIN_SYMBOLS + TRAIN_LOSS_SYMBOLS + TRAIN_VARLEN_SYMBOLS + TRAIN_COND_SYMBOLS:      # fails loudly (AttributeError) if a symbol is missing
+    for name in EXPORTED_SYMBOLS + EXTENSION_SYMBOLS + LIVE_TICK_SYMBOLS + SCORE_SYMBOLS + TRAIN_SYMBOLS + TRAIN_LOSS_SYMBOLS + TRAIN_VARLEN_SYMBOLS + TRAIN_COND_SYMBOLS + TRAIN_OPT_SYMBOLS:      # fails loudly (AttributeError) if a symbol is missing
         getattr(lib, name)
     return lib
 

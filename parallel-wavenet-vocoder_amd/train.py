@@ -1,9 +1,9 @@
-"""Training of the IAF-WaveNet student on one GPU: the reference's loss (models.py:90-99: the L1, and on request weight_power_loss
+"""Training of the IAF-WaveNet student, on one GPU or data-parallel over the GPUs of a node: the reference's loss (models.py:90-99: the L1, and on request weight_power_loss
 times the STFT power loss -- pwv_train_loss_f32, include/pwv_hip_train_loss.h), its gradient for every variable (pwv_train_* kernels,
 include/pwv_hip_train.h), TensorFlow's Adam and the reference's EMA (models.py:72-76, :101-103), and the loop of train.py:25-71.
 DESIGN.md section 9, "Training".
 
-    python -m pwv_amd.train CASE [--ckpt=NAME] [--steps=N] [--seed=S] [--varlen]
+    python -m pwv_amd.train CASE [--ckpt=NAME] [--steps=N] [--seed=S] [--varlen] [--gpus=N]
 
 Scope: what hparams/default.yaml trains -- filter_width 2, R = D = 64, S = 128, 'repeat' conditioning, no normalisers, no skip
 accumulation, separate scaler and shifter nets, exact-fp32 arithmetic; uniform [N, T] batches (loss_and_grad) or packed batches of
@@ -11,6 +11,10 @@ utterances of different lengths, unpadded (loss_and_grad_varlen, `--varlen`).  A
 cond_upsample_method 'transposed_conv' (models.py:109-124; hparams test/tran): uniform batches at hop_length 80 = 4 * 4 * 5, an even
 condition_channels <= 96, no normalised conditioning.  Everything else is refused with a PwvError that names the reason (`refusal`);
 nothing falls back to another implementation.
+
+Data-parallel (the reference's SyncMultiGPUTrainerReplicated, train.py:66-69): DataParallelTrainer, one replica per rank; the gradients
+of a step are packed into ONE flat arena, all-reduced once, and one fused Adam + EMA launch applies the same update on every rank
+(include/pwv_hip_train_opt.h; Trainer(fused=True) is the same optimiser in one process).  DESIGN.md section 9, "Data-parallel training".
 
 Division of work.  Sample rate (the hot path): HIP kernels, one net per call -- the forward keeps every layer's input and the last
 layer's gated output, the backward recomputes F, G, o and the head's hidden layers from them.  Frame rate: the conditioning dense +
@@ -506,10 +510,16 @@ def _forward_backward(store, flows, geo, mel2, x, y, head):
     return _fill_unread(store, grads, loss, x)
 
 
+class _Grads(dict):
+    """The gradients of a step by name; `unread`: the names whose entries are the zeros of variables the model never reads."""
+    unread = ()
+
+
 def _fill_unread(store, grads, loss, x):
-    for name in trainable_names(store):                 # what the model never reads
-        if name not in grads:
-            grads[name] = torch.zeros_like(store.vars[name])
+    grads = _Grads(grads)
+    grads.unread = tuple(name for name in trainable_names(store) if name not in grads)       # what the model never reads
+    for name in grads.unread:
+        grads[name] = torch.zeros_like(store.vars[name])
     return loss, x, grads
 
 
@@ -611,16 +621,211 @@ def adam_ema_update(vars, grads, state, lr, beta1=ADAM_BETA1, beta2=0.999, eps=A
     return state
 
 
+# ---- the gradient arena and the fused optimiser (include/pwv_hip_train_opt.h; DESIGN.md section 9, "Data-parallel training") ----------
+class ArenaLayout(object):
+    """Where every variable lies in a flat float32 arena: `names` sorted, `shapes`, `counts`, `offsets` (floats, multiples of 4) parallel
+    to them, `total` floats = sum of the counts rounded up to 4."""
+
+    def __init__(self, names, shapes, counts, offsets, total):
+        self.names, self.shapes, self.counts, self.offsets, self.total = names, shapes, counts, offsets, total
+        self.index = {n: i for i, n in enumerate(names)}
+
+    def views(self, arena):
+        """One view of `arena` per variable, in the variable's shape."""
+        return [arena[o:o + c].view(s) for o, c, s in zip(self.offsets, self.counts, self.shapes)]
+
+
+def arena_layout(names, shapes) -> ArenaLayout:
+    """THE layout of the gradient, m, v and shadow arenas, a pure function of the variables' names and shapes: variables in sorted-name
+    order, each at an offset that is a multiple of 4 floats (16 bytes), the up to 3 floats of padding behind a variable never written.
+    `shapes`: a mapping name -> shape, or a sequence parallel to `names`."""
+    names = list(names)
+    if len(set(names)) != len(names):
+        raise ValueError('arena_layout: a name occurs twice')
+    by_name = dict(shapes) if isinstance(shapes, dict) else dict(zip(names, shapes))
+    order = sorted(names)
+    out_shapes = [tuple(int(d) for d in by_name[n]) for n in order]
+    counts = [int(np.prod(s, dtype=np.int64)) if len(s) else 1 for s in out_shapes]
+    if any(c < 1 for c in counts):
+        raise ValueError('arena_layout: a variable without elements')
+    offsets, at = [], 0
+    for c in counts:
+        offsets.append(at)
+        at += (c + 3) // 4 * 4
+    return ArenaLayout(order, out_shapes, counts, offsets, at)
+
+
+def arena_block_map(counts) -> np.ndarray:
+    """int32 [blocks, 2] = {tensor, chunk}: every chunk of _lib.TRAIN_OPT_CHUNK floats of every tensor once, tensor after tensor."""
+    recs = [(i, c) for i, count in enumerate(counts) for c in range((int(count) + _lib.TRAIN_OPT_CHUNK - 1) // _lib.TRAIN_OPT_CHUNK)]
+    return np.asarray(recs, dtype=np.int32).reshape(-1, 2)
+
+
+def noise_offset(step: int, world: int, rank: int, N: int, T: int) -> int:
+    """The first noise counter of rank `rank` at (0-based) step `step` of data-parallel training on uniform [N, T] local batches: with one
+    noise_seed the ranks together draw exactly the counters that one process training the concatenated [world N, T] batch draws at that
+    step -- (step world + rank) N T."""
+    return (int(step) * int(world) + int(rank)) * int(N) * int(T)
+
+
+def allreduce_sum_(flat, group=None, host=None):
+    """SUM all-reduce of the flat tensor `flat` over `group`, in place.  A CPU tensor, or any tensor under the `nccl` backend (RCCL), is
+    reduced where it is; a GPU tensor under another backend (gloo: the CPU tests, the one-GPU dry run) goes through `host`, a pinned CPU
+    tensor of the same size (made here if None).  Every rank ends with the same bits.  Returns `flat`."""
+    import torch.distributed as dist
+    if not flat.is_cuda or dist.get_backend(group) == 'nccl':
+        dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group)
+        return flat
+    return _through_host(flat, host, lambda t: dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group))
+
+
+def broadcast_(flat, src=0, group=None, host=None):
+    """`flat` of rank `src` to every rank, in place; the route of allreduce_sum_."""
+    import torch.distributed as dist
+    if not flat.is_cuda or dist.get_backend(group) == 'nccl':
+        dist.broadcast(flat, src=src, group=group)
+        return flat
+    return _through_host(flat, host, lambda t: dist.broadcast(t, src=src, group=group))
+
+
+def _through_host(flat, host, collective):
+    if host is None:
+        host = torch.empty(flat.numel(), dtype=flat.dtype, pin_memory=True)
+    host.copy_(flat)                    # (synchronises with the stream that filled `flat`)
+    collective(host)
+    flat.copy_(host)
+    return flat
+
+
+class _Tables(object):
+    """The tables of one call of include/pwv_hip_train_opt.h: n tensors at their arena offsets and the block map, on the device and on the
+    host (the library reads its refusals from the host copies)."""
+
+    def __init__(self, tensors, offsets, counts, device):
+        self.tensors = tensors              # kept alive until the launch that reads their addresses is enqueued
+        self.table_host = np.ascontiguousarray([[t.data_ptr(), o, c] for t, o, c in zip(tensors, offsets, counts)], dtype=np.int64)
+        self.map_host = arena_block_map(counts)
+        self.table, self.map = torch.from_numpy(self.table_host).to(device), torch.from_numpy(self.map_host).to(device)
+        self.n, self.blocks = len(tensors), int(self.map_host.shape[0])
+        self._pinned, self._turn = None, 0
+
+    def retarget(self, tensors):
+        """The same layout over other tensors of the same sizes (the gradients of the next step): only the addresses change."""
+        self.tensors = tensors
+        self.table_host[:, 0] = [t.data_ptr() for t in tensors]
+        # an asynchronous upload from one of two pinned copies, so that a step does not wait for the device; a pinned copy is written
+        # again two steps later, once the event behind its upload has passed
+        if self._pinned is None:
+            self._pinned = [[torch.empty(self.table_host.shape, dtype=torch.int64, pin_memory=True), None] for _ in range(2)]
+        slot = self._pinned[self._turn]
+        self._turn ^= 1
+        if slot[1] is not None:
+            slot[1].synchronize()
+        slot[0].numpy()[:] = self.table_host
+        self.table.copy_(slot[0], non_blocking=True)
+        slot[1] = torch.cuda.Event()
+        slot[1].record()
+        return self
+
+    def fields(self):
+        return dict(table=self.table.data_ptr(), block_map=self.map.data_ptr(), table_host=self.table_host.ctypes.data,
+                    block_map_host=self.map_host.ctypes.data, n=self.n, blocks=self.blocks)
+
+
+def _arena_tensor(t, what):
+    if not (t.is_cuda and t.dtype == torch.float32):
+        raise PwvError('%s must be a float32 tensor on the GPU: the arena kernels have no CPU fallback' % what)
+    return t if t.is_contiguous() else t.contiguous()
+
+
+class _Arenas(object):
+    """The four arenas of a fused trainer over the variables `vars` (parallel to the sorted `names`), and the launches over them."""
+
+    def __init__(self, names, vars, ema):
+        vars = [_arena_tensor(v, n) for n, v in zip(names, vars)]
+        self.layout = arena_layout(names, [tuple(v.shape) for v in vars])
+        assert self.layout.names == list(names)
+        dev, total = vars[0].device, self.layout.total
+        self.device = dev
+        self.grad, self.m, self.v = (torch.zeros(total, dtype=torch.float32, device=dev) for _ in range(3))
+        self.shadow = torch.zeros(total, dtype=torch.float32, device=dev) if ema else None
+        self.vars = _Tables(vars, self.layout.offsets, self.layout.counts, dev)
+        self._grad_tables = None
+
+    def pack(self, tables, arena, unpack=False):
+        a = _lib.TrainOptPackArgs(arena=arena.data_ptr(), arena_floats=arena.numel(), **tables.fields())
+        _call('pwv_train_opt_unpack_f32' if unpack else 'pwv_train_opt_pack_f32', a)
+
+    def pack_grads(self, grads):
+        """The gradients the model formed into the gradient arena, one launch; the slots of `grads.unread` keep their zeros."""
+        lay = self.layout
+        unread = getattr(grads, 'unread', ())
+        if self._grad_tables is None or self._grad_tables[0] != unread:
+            skip = frozenset(unread)
+            names = [n for n in lay.names if n not in skip]
+            idx = [lay.index[n] for n in names]
+            tensors = [_arena_tensor(grads[n], 'the gradient of ' + n) for n in names]
+            tables = _Tables(tensors, [lay.offsets[i] for i in idx], [lay.counts[i] for i in idx], self.device)
+            self._grad_tables = (unread, names, tables, tables.table_host[:, 2].tolist())
+        else:
+            _, names, tables, counts = self._grad_tables
+            tensors = [_arena_tensor(grads[n], 'the gradient of ' + n) for n in names]
+            tables.retarget(tensors)
+        _, names, tables, counts = self._grad_tables
+        if [t.numel() for t in tensors] != counts:
+            raise PwvError('a gradient does not have the size of its variable')
+        self.pack(tables, self.grad)
+
+    def adam_ema(self, lr_t, beta1, beta2, eps, decay, grad_scale):
+        a = _lib.TrainOptAdamArgs(grad=self.grad.data_ptr(), m=self.m.data_ptr(), v=self.v.data_ptr(), shadow=_ptr(self.shadow),
+                                  arena_floats=self.grad.numel(), lr_t=lr_t, beta1=beta1, beta2=beta2, eps=eps,
+                                  decay=-1.0 if decay is None else float(decay), grad_scale=grad_scale, **self.vars.fields())
+        _call('pwv_train_opt_adam_ema_f32', a)
+
+
+def arena_pack(tensors, layout: ArenaLayout, arena):
+    """One pwv_train_opt_pack_f32 launch: `tensors` (float32, on the GPU, parallel to layout.names) into the flat `arena`."""
+    _arena_copy(tensors, layout, arena, False)
+
+
+def arena_unpack(tensors, layout: ArenaLayout, arena):
+    """One pwv_train_opt_unpack_f32 launch: the flat `arena` into `tensors` (contiguous, float32, on the GPU, parallel to layout.names)."""
+    _arena_copy(tensors, layout, arena, True)
+
+
+def _arena_copy(tensors, layout, arena, unpack):
+    tensors = list(tensors)
+    if len(tensors) != len(layout.names) or any(t.numel() != c for t, c in zip(tensors, layout.counts)):
+        raise ValueError('the tensors do not have the sizes of the layout')
+    if unpack and not all(t.is_contiguous() for t in tensors):
+        raise ValueError('arena_unpack writes contiguous tensors only')
+    if arena.numel() < layout.total or not arena.is_contiguous():
+        raise ValueError('the arena must be flat and hold the layout\'s %d floats' % layout.total)
+    tensors = [_arena_tensor(t, n) for n, t in zip(layout.names, tensors)]
+    tables = _Tables(tensors, layout.offsets, layout.counts, _arena_tensor(arena, 'the arena').device)
+    a = _lib.TrainOptPackArgs(arena=arena.data_ptr(), arena_floats=arena.numel(), **tables.fields())
+    _call('pwv_train_opt_unpack_f32' if unpack else 'pwv_train_opt_pack_f32', a)
+
+
 _UNSET = object()
 
 
 class Trainer(object):
     """The reference's training step (models.py:80-103) on one model: loss_and_grad, then adam_ema_update on the store's variables in
     place.  Defaults from hparams: lr = train.lr, beta2 = train.adam_beta2, ema_decay = train.ema_decay if train.use_ema.
-    `power_weight` goes to every loss_and_grad; `terms` then holds the last step's 'likelihood', 'power' and 'total' (device scalars)."""
+    `power_weight` goes to every loss_and_grad; `terms` then holds the last step's 'likelihood', 'power' and 'total' (device scalars).
 
-    def __init__(self, model, lr=None, beta2=None, ema_decay=_UNSET, max_workgroups: int = 0, power_weight: Optional[float] = None):
+    `fused` (default False: adam_ema_update's torch._foreach passes, launch for launch what they were): the gradients of a step are
+    packed into one flat arena by one launch and ONE pwv_train_opt_adam_ema_f32 launch updates the model
+    (include/pwv_hip_train_opt.h); state['m' | 'v' | 'shadow'] are then views into the m, v and shadow arenas, and save / load /
+    shadows() work as before -- an .npz of either path loads into the other."""
+
+    def __init__(self, model, lr=None, beta2=None, ema_decay=_UNSET, max_workgroups: int = 0, power_weight: Optional[float] = None,
+                 fused: bool = False):
         self.model = model
+        self.fused = bool(fused)
+        self.arenas: Optional[_Arenas] = None
+        self._vars_version = None
         self.power_weight = power_weight        # None: the L1 alone; w >= 0: likelihood + w * power (loss_and_grad)
         self.terms: Dict[str, torch.Tensor] = {}
         self.store = model.store or get_default_store()
@@ -652,20 +857,65 @@ class Trainer(object):
                                        terms=terms)
         return self._update(vars, loss, grads, terms)
 
-    def step_varlen(self, wavs, mels, z=None):
+    def step_varlen(self, wavs, mels, z=None, seeds=None):
         """One step on one packed batch of utterances of different lengths (loss_and_grad_varlen: lists of [T_i] wavs and
-        [1 + T_i / hop, n_mels] mels); returns the loss BEFORE the update."""
+        [1 + T_i / hop, n_mels] mels; `seeds`: one noise seed per utterance); returns the loss BEFORE the update."""
         vars = self._bind(packed=True)
         terms: Dict[str, torch.Tensor] = {}
-        loss, _, grads = loss_and_grad_varlen(self.model, wavs, mels, z=z, max_workgroups=self.max_workgroups, power_weight=self.power_weight,
-                                              terms=terms)
+        loss, _, grads = loss_and_grad_varlen(self.model, wavs, mels, z=z, seeds=seeds, max_workgroups=self.max_workgroups,
+                                              power_weight=self.power_weight, terms=terms)
         return self._update(vars, loss, grads, terms)
 
     def _update(self, vars, loss, grads, terms):
         self.terms = terms
-        self.state = adam_ema_update(vars, [grads[n] for n in self.names], self.state, self.lr, self.beta1, self.beta2, ADAM_EPS, self.ema_decay)
+        if self.fused:
+            self._fused_update(vars, grads)
+        else:
+            self.state = adam_ema_update(vars, [grads[n] for n in self.names], self.state, self.lr, self.beta1, self.beta2, ADAM_EPS, self.ema_decay)
         self.store.touch()
+        self._vars_version = self.store.version
         return loss
+
+    # -- the fused path: one pack launch, (a replicated trainer's all-reduce,) one Adam + EMA launch ---------------------------------
+    def _arenas(self, vars) -> _Arenas:
+        """The arenas over the store's variables; made at the first use, their table of addresses rebuilt if the store has changed
+        behind the trainer's back (an assign replaces a variable's tensor)."""
+        if self.arenas is None:
+            self.arenas = _Arenas(self.names, vars, self.ema_decay is not None)
+        elif self._vars_version != self.store.version:
+            self.arenas.vars = _Tables([_arena_tensor(v, n) for n, v in zip(self.names, vars)], self.arenas.layout.offsets,
+                                       self.arenas.layout.counts, self.arenas.device)
+        self._vars_version = self.store.version
+        return self.arenas
+
+    def _fused_state(self, vars, t):
+        """state whose 'm', 'v' and 'shadow' are views into the arenas."""
+        ar = self._arenas(vars)
+        lay = ar.layout
+        return {'t': t, 'm': lay.views(ar.m), 'v': lay.views(ar.v), 'shadow': lay.views(ar.shadow) if ar.shadow is not None else None}
+
+    def _reduce(self, arena) -> float:
+        """What happens to the gradient arena between the pack and the optimiser; returns grad_scale.  One process: nothing."""
+        return 1.0
+
+    def _fused_update(self, vars, grads):
+        ar = self._arenas(vars)
+        if self.state is None:
+            ar.m.zero_()
+            ar.v.zero_()
+            if ar.shadow is not None:
+                ar.pack(ar.vars, ar.shadow)                  # the shadows start at the initial values
+            self.state = self._fused_state(vars, 0)
+        ar.pack_grads(grads)
+        scale = self._reduce(ar.grad)
+        self.state['t'] += 1
+        t = self.state['t']
+        lr_t = self.lr * math.sqrt(1.0 - self.beta2 ** t) / (1.0 - self.beta1 ** t)
+        ar.adam_ema(lr_t, self.beta1, self.beta2, ADAM_EPS, self.ema_decay, scale)
+
+    def gradients(self) -> Dict[str, torch.Tensor]:
+        """A fused trainer's gradient arena by name, as the last step left it (views; in a replicated trainer: the SUM over the ranks)."""
+        return {} if self.arenas is None else dict(zip(self.names, self.arenas.layout.views(self.arenas.grad)))
 
     @property
     def steps(self) -> int:
@@ -695,25 +945,183 @@ class Trainer(object):
             np.savez(f, **out)
 
     def load(self, path: str) -> int:
-        """Resume from a file `save` wrote; returns the step count."""
+        """Resume from a file `save` wrote (by either path, fused or not); returns the step count."""
         vars = self._bind()
         with np.load(path) as zf:
             data = {k: zf[k] for k in zf.files}
-        dev = self.store.device
-        put = lambda a, like: torch.as_tensor(np.asarray(a), dtype=like.dtype).reshape(like.shape).to(like.device)
-        for n, v in zip(self.names, vars):
+        for n in self.names:
             if n not in data:
                 raise KeyError('%s has no variable %s' % (path, n))
-            v.copy_(put(data[n], v))
         t = int(data['global_step']) if 'global_step' in data else int(round(math.log(float(data['beta1_power'])) / math.log(self.beta1))) - 1
-        if t > 0:
-            self.state = {'t': t, 'm': [put(data[n + '/Adam'], v) for n, v in zip(self.names, vars)],
-                          'v': [put(data[n + '/Adam_1'], v) for n, v in zip(self.names, vars)],
-                          'shadow': [put(data.get(n + EMA_SUFFIX, data[n]), v) for n, v in zip(self.names, vars)] if self.ema_decay is not None else None}
+        if self.fused:
+            # every arena is laid out on the host and uploaded whole; the variables come out of theirs by one unpack launch
+            ar = self._arenas(vars)
+            lay = ar.layout
+
+            def upload(arena, key):
+                flat = np.zeros(lay.total, dtype=np.float32)
+                for n, o, c in zip(lay.names, lay.offsets, lay.counts):
+                    flat[o:o + c] = np.asarray(data[key(n)], dtype=np.float32).reshape(-1)
+                arena.copy_(torch.from_numpy(flat))
+
+            upload(ar.grad, lambda n: n)
+            ar.pack(ar.vars, ar.grad, unpack=True)
+            ar.grad.zero_()
+            if t > 0:
+                upload(ar.m, lambda n: n + '/Adam')
+                upload(ar.v, lambda n: n + '/Adam_1')
+                if ar.shadow is not None:
+                    upload(ar.shadow, lambda n: n + EMA_SUFFIX if n + EMA_SUFFIX in data else n)
+            self.state = self._fused_state(vars, t) if t > 0 else None
         else:
-            self.state = None
+            put = lambda a, like: torch.as_tensor(np.asarray(a), dtype=like.dtype).reshape(like.shape).to(like.device)
+            for n, v in zip(self.names, vars):
+                v.copy_(put(data[n], v))
+            if t > 0:
+                self.state = {'t': t, 'm': [put(data[n + '/Adam'], v) for n, v in zip(self.names, vars)],
+                              'v': [put(data[n + '/Adam_1'], v) for n, v in zip(self.names, vars)],
+                              'shadow': [put(data.get(n + EMA_SUFFIX, data[n]), v) for n, v in zip(self.names, vars)] if self.ema_decay is not None else None}
+            else:
+                self.state = None
         self.store.touch()
+        self._vars_version = self.store.version
         return t
+
+
+class DataParallelTrainer(Trainer):
+    """The reference's replicated trainer (train.py:66-69, tensorpack's SyncMultiGPUTrainerReplicated): one process and one replica of
+    the model per GPU, a fused Trainer on every rank.  `group`: a torch.distributed process group (None: the default group, which must
+    be initialised).
+
+    When the variables are bound, rank 0's go through pack -> broadcast -> unpack, so the replicas start identical.  `step` /
+    `step_varlen` take the rank's LOCAL batch; after the pack ONE all-reduce (SUM) runs over the gradient arena and the optimiser launch
+    reads the sum times 1 / world, so every rank applies the same update and the replicas stay bit-identical.  That is the plain mean of
+    the ranks' gradients, as tensorpack forms it: with equal local batch sizes it is the gradient of the mean loss of the global batch;
+    with packed batches of unequal total length it is NOT (each rank's loss is a mean over its own samples) -- the ranks are weighted
+    equally, not the samples.  The returned loss is the local one; mean_loss() all-reduces it on request.
+
+    Under the `nccl` backend (RCCL) the collectives run on the device arena; under any other (gloo) they go through a pinned host copy.
+    Before a uniform step the trainer sets model.noise_offset = noise_offset(step, world, rank, N, T): with one noise_seed on every rank
+    the ranks draw the counters that one process training the concatenated batch would.  A packed step takes distinct per-utterance
+    `seeds` from the caller.  save() writes on rank 0 only; load() reads on every rank."""
+
+    def __init__(self, model, group=None, **kw):
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()):
+            raise PwvError('DataParallelTrainer needs an initialised torch.distributed process group')
+        kw.pop('fused', None)
+        super().__init__(model, fused=True, **kw)
+        self.group = group
+        self.world, self.rank = dist.get_world_size(group), dist.get_rank(group)
+        self._host = None
+        self._local_loss = None
+
+    def _host_copy(self, arena):
+        import torch.distributed as dist
+        if arena.is_cuda and dist.get_backend(self.group) != 'nccl' and self._host is None:
+            self._host = torch.empty(arena.numel(), dtype=torch.float32, pin_memory=True)
+        return self._host
+
+    def _bind(self, packed=False):
+        first = self.names is None
+        vars = super()._bind(packed)
+        if first:
+            ar = self._arenas(vars)
+            ar.pack(ar.vars, ar.grad)
+            broadcast_(ar.grad, 0, self.group, self._host_copy(ar.grad))
+            ar.pack(ar.vars, ar.grad, unpack=True)
+            ar.grad.zero_()
+            self.store.touch()
+            self._vars_version = self.store.version
+        return vars
+
+    def _reduce(self, arena) -> float:
+        allreduce_sum_(arena, self.group, self._host_copy(arena))
+        return 1.0 / self.world
+
+    def step(self, wav, mel, z=None):
+        self._bind()
+        if z is None:
+            self.model.noise_offset = noise_offset(self.steps, self.world, self.rank, int(mel.shape[0]), int(self.model.length))
+        self._local_loss = super().step(wav, mel, z=z)
+        return self._local_loss
+
+    def step_varlen(self, wavs, mels, z=None, seeds=None):
+        self._local_loss = super().step_varlen(wavs, mels, z=z, seeds=seeds)
+        return self._local_loss
+
+    def mean_loss(self):
+        """The mean over the ranks of the last step's local losses (one all-reduce of a scalar); a device scalar."""
+        if self._local_loss is None:
+            raise PwvError('mean_loss: no step has run')
+        total = self._local_loss.detach().clone().reshape(1)
+        allreduce_sum_(total, self.group)
+        return total[0] / self.world
+
+    def save(self, path: str) -> None:
+        self._bind()                    # (a collective the first time: every rank calls save, rank 0 writes)
+        if self.rank == 0:
+            super().save(path)
+
+
+MAX_RANKS = 8               # the reference's largest job (hparams ema/*: num_gpu 8), one node
+
+
+def _spawn_ranks(n, argv):
+    """`n` fresh child processes, one rank each (`python -m pwv_amd.train` + argv under RANK / LOCAL_RANK / WORLD_SIZE and a rendezvous
+    on a free local port): no process that has opened a GPU is replaced or forked.  Rank 0's output is this process's.  Returns the
+    first non-zero exit code, else 0; when a rank fails the others are ended, since they would wait in a collective for ever."""
+    import socket
+    import subprocess
+    import time
+    s = socket.socket()
+    s.bind(('127.0.0.1', 0))
+    port = s.getsockname()[1]
+    s.close()
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    procs = []
+    for r in range(n):
+        env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(n), MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port),
+                   PYTHONPATH=root + os.pathsep + os.environ.get('PYTHONPATH', ''))
+        procs.append(subprocess.Popen([sys.executable, '-m', 'pwv_amd.train'] + list(argv), env=env,
+                                      stdout=None if r == 0 else subprocess.DEVNULL))
+    code = 0
+    try:
+        live = list(procs)
+        while live and code == 0:
+            for p in list(live):
+                rc = p.poll()
+                if rc is not None:
+                    live.remove(p)
+                    code = code or rc
+            if live and code == 0:
+                time.sleep(0.05)
+    finally:
+        for p in procs:
+            if p.poll() is None:
+                p.terminate()
+        for p in procs:
+            try:
+                p.wait(timeout=30)
+            except subprocess.TimeoutExpired:
+                p.kill()
+                p.wait()
+    return code
+
+
+def _ranks_wanted(gpus) -> int:
+    """How many ranks train() runs: `gpus` if given, else hp.train.num_gpu; refused beyond the visible devices and beyond MAX_RANKS.
+    PWV_TRAIN_DRYRUN_ONE_GPU=1 (a test hook, like bench.py's PWV_BENCH_DRYRUN_ONE_GPU): the ranks share GPU 0 and meet over gloo."""
+    n = int(gpus) if gpus is not None else int(hp.train.get('num_gpu', 1) or 1)
+    if n < 1:
+        raise PwvError('training refused: num_gpu %d must be >= 1' % n)
+    if n > 1 and os.environ.get('PWV_TRAIN_DRYRUN_ONE_GPU') != '1':
+        visible = torch.cuda.device_count()
+        if n > visible:
+            raise PwvError('training refused: num_gpu %d exceeds the %d visible device(s); one rank trains on one GPU' % (n, visible))
+    if n > MAX_RANKS:
+        raise PwvError('training refused: num_gpu %d exceeds the %d ranks of one node this trainer starts' % (n, MAX_RANKS))
+    return n
 
 
 # ---- train.py:25-71 on one GPU ------------------------------------------------------------------------------------------------------
@@ -754,26 +1162,62 @@ def _dataset(length: int, seed: int, varlen: bool = False) -> List[np.ndarray]:
     return [fix_length(w, length) if len(w) < length else w for w in wavs]
 
 
-def train(case='default', ckpt=None, steps=None, seed=0, varlen=False):
-    """train.py:25-71 on one GPU: per step a seeded random crop of hp.signal.length samples per item (data_load.py:46-50), its mel from
+def train(case='default', ckpt=None, steps=None, seed=0, varlen=False, gpus=None):
+    """train.py:25-71: per step a seeded random crop of hp.signal.length samples per item (data_load.py:46-50), its mel from
     the device front-end, one Trainer.step; prints loss/likelihood per step (with train.weight_power_loss > 0 the power loss is trained
     too, and the line carries loss/likelihood, loss/power and loss/total); saves into hp.logdir (PWV_LOGDIR overrides) every
     train.save_per_epoch * train.steps_per_epoch steps and at the end.  `ckpt` names a file in the log directory to resume from (default:
     the newest .npz there).  `varlen` (--varlen): every step trains ONE PACKED BATCH of batch_size files at their own lengths -- each cut
     to a whole number of hops and to at most train.varlen_max_length samples (default 4 * signal.length; a longer file is cut at a seeded
-    offset), nothing padded (Trainer.step_varlen)."""
-    from .audio_frontend import wav_to_mel_device
-    from .models import IAFVocoder
-    from .variables import reset_default_store
+    offset), nothing padded (Trainer.step_varlen).
+
+    Data-parallel (train.py:66-69): `gpus` (--gpus N), else hp.train.num_gpu, ranks -- at most 8, never more than the visible devices.
+    Under a launcher (WORLD_SIZE set) this process is one rank and joins the group; otherwise N > 1 starts N fresh child processes, one
+    per GPU.  Every rank runs a DataParallelTrainer on its own batch of train.batch_size items (batch_size is per rank, as with
+    tensorpack's towers), its crops drawn from RandomState([seed, step base, rank]); rank 0 prints its local loss and saves."""
     hp.set_hparam_yaml(case)
     power_weight = float(hp.train.get('weight_power_loss', 0) or 0)
     power_weight = power_weight if power_weight > 0 else None
     why = refusal(power_weight=power_weight)
     if why:
         raise PwvError('training refused: ' + why)
+    launched = 'WORLD_SIZE' in os.environ
+    world = int(os.environ['WORLD_SIZE']) if launched else _ranks_wanted(gpus)
+    if not launched and world > 1:
+        argv = [str(case), '--steps=%d' % int(steps)] if steps is not None else [str(case)]
+        argv += ['--seed=%d' % int(seed)] + (['--ckpt=%s' % ckpt] if ckpt else []) + (['--varlen'] if varlen and varlen != 'False' else [])
+        code = _spawn_ranks(world, argv)
+        if code:
+            raise PwvError('data-parallel training failed: a rank exited with status %d' % code)
+        logdir = os.environ.get('PWV_LOGDIR', hp.logdir)
+        return (sorted(glob.glob(os.path.join(logdir, '*.npz')), key=os.path.getmtime) or [None])[-1]
     if not torch.cuda.is_available():
         raise RuntimeError('train() needs an MI355X: the HIP path has no CPU fallback')
+    rank = int(os.environ.get('RANK', '0')) if launched else 0
+    if world > 1:
+        import torch.distributed as dist
+        one_gpu = os.environ.get('PWV_TRAIN_DRYRUN_ONE_GPU') == '1'
+        torch.cuda.set_device(0 if one_gpu else int(os.environ.get('LOCAL_RANK', rank)))
     device = torch.device('cuda', torch.cuda.current_device())
+    if world > 1:
+        os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
+        if one_gpu:
+            dist.init_process_group(backend='gloo')
+        else:
+            dist.init_process_group(backend='nccl', device_id=device)       # 'nccl' is RCCL on ROCm
+    try:
+        return _train_rank(power_weight, device, seed, steps, ckpt, varlen, world, rank)
+    finally:
+        if world > 1:
+            dist.destroy_process_group()
+
+
+def _train_rank(power_weight, device, seed, steps, ckpt, varlen, world, rank):
+    """The loop of train() in one process: the only rank, or one of `world`."""
+    from .audio_frontend import wav_to_mel_device
+    from .models import IAFVocoder
+    from .variables import reset_default_store
+    say = print if rank == 0 else (lambda *a: None)
     logdir = os.environ.get('PWV_LOGDIR', hp.logdir)
     seed = int(seed)
     length, batch = int(hp.signal.length), int(hp.train.batch_size)
@@ -781,15 +1225,15 @@ def train(case='default', ckpt=None, steps=None, seed=0, varlen=False):
     store = reset_default_store(device=device)
     model = IAFVocoder(batch_size=batch, length=length, store=store, precision='f32')
     model.noise_seed = seed
-    trainer = Trainer(model, power_weight=power_weight)
+    trainer = DataParallelTrainer(model, power_weight=power_weight) if world > 1 else Trainer(model, power_weight=power_weight)
     path = os.path.join(logdir, ckpt) if ckpt else (sorted(glob.glob(os.path.join(logdir, '*.npz')), key=os.path.getmtime) or [None])[-1]
     if path and os.path.exists(path):
-        print('resumed from %s at step %d' % (path, trainer.load(path)))
+        say('resumed from %s at step %d' % (path, trainer.load(path)))
     varlen = bool(varlen) and varlen != 'False'
     wavs = _dataset(length, seed, varlen)
     hop = int(hp.signal.hop_length)
     max_len = max(int(hp.train.get('varlen_max_length', 0) or 4 * length) // hop * hop, hop)
-    rng = np.random.RandomState(seed + trainer.steps)
+    rng = np.random.RandomState([seed, trainer.steps, rank]) if world > 1 else np.random.RandomState(seed + trainer.steps)
     every = max(int(hp.train.save_per_epoch) * int(hp.train.steps_per_epoch), 1)
     saved_at = None
     for _ in range(steps):
@@ -800,7 +1244,9 @@ def train(case='default', ckpt=None, steps=None, seed=0, varlen=False):
                 n = min(len(w) // hop * hop, max_len)
                 at = rng.randint(len(w) - n + 1)
                 pieces.append(torch.from_numpy(np.ascontiguousarray(w[at:at + n])).to(device))
-            loss = trainer.step_varlen(pieces, [wav_to_mel_device(p.unsqueeze(0))[0] for p in pieces])
+            # (replicas: one distinct noise seed per utterance of the job, drawn from the rank's own stream)
+            seeds = [int(rng.randint(1 << 31)) * MAX_RANKS + rank for _ in pieces] if world > 1 else None
+            loss = trainer.step_varlen(pieces, [wav_to_mel_device(p.unsqueeze(0))[0] for p in pieces], seeds=seeds)
         else:
             crop = np.empty((batch, length), dtype=np.float32)
             for b in range(batch):
@@ -809,7 +1255,9 @@ def train(case='default', ckpt=None, steps=None, seed=0, varlen=False):
                 crop[b] = w[at:at + length]
             wav = torch.from_numpy(crop).to(device)
             loss = trainer.step(wav, wav_to_mel_device(wav))
-        if power_weight is None:
+        if rank != 0:
+            pass
+        elif power_weight is None:
             print('step %d loss/likelihood %.6f' % (trainer.steps, float(loss)))
         else:
             print('step %d loss/likelihood %.6f loss/power %.6f loss/total %.6f'
@@ -820,7 +1268,7 @@ def train(case='default', ckpt=None, steps=None, seed=0, varlen=False):
     final = os.path.join(logdir, 'model-%d.npz' % trainer.steps)
     if saved_at != final:
         trainer.save(final)
-    print('saved %s' % final)
+    say('saved %s' % final)
     return final
 
 

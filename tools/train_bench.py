@@ -37,6 +37,16 @@ GEMMs + ReLU forward, their backward in torch on a fixed d_cond), whose share of
 profiles/train_tran_bench.json.
 
     python tools/train_bench.py --tran [--steps 20] [--warmup 3]
+
+--opt measures the fused optimiser ("Data-parallel training"; include/pwv_hip_train_opt.h): Trainer.step with
+fused=False (adam_ema_update's torch._foreach passes) and with fused=True (one pack launch + one Adam + EMA launch), two trainers over
+two copies of the model ALTERNATING call by call in one run, and alone, timed over runs of 20 calls: the pack of a step's gradients
+(the upload of its table of addresses included), the Adam + EMA launch, an unpack of the variables, and adam_ema_update on the same
+gradients.  With --gpus N it also starts, for every world size in {1, 2, 4, 8} up to N that the machine has devices for, that many
+fresh processes, one per GPU, and measures DataParallelTrainer.step per rank at the same per-rank batch and the all-reduce of the
+gradient arena alone (the slowest rank's median).  There is no threshold.  Writes profiles/train_dp_bench.json.
+
+    python tools/train_bench.py --opt [--gpus N] [--steps 20] [--warmup 3]
 """
 import argparse
 import json
@@ -57,10 +67,13 @@ def main():
     ap.add_argument('--power', action='store_true', help='measure loss_and_grad with and without the STFT power loss instead')
     ap.add_argument('--varlen', action='store_true', help='measure packed batches against uniform and padded ones instead')
     ap.add_argument('--tran', action='store_true', help='measure transposed-conv conditioning against repeat conditioning instead')
+    ap.add_argument('--opt', action='store_true', help='measure the fused optimiser against the torch._foreach one instead')
+    ap.add_argument('--gpus', type=int, default=1, help='with --opt: also measure data-parallel steps at world sizes up to this')
+    ap.add_argument('--dp-rank', action='store_true', help=argparse.SUPPRESS)          # one rank of a --gpus measurement
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
     if args.out is None:
-        name = ('train_power_bench.json' if args.power else 'train_varlen_bench.json' if args.varlen else 'train_tran_bench.json' if args.tran
+        name = ('train_dp_bench.json' if args.opt else 'train_power_bench.json' if args.power else 'train_varlen_bench.json' if args.varlen else 'train_tran_bench.json' if args.tran
                 else 'train_bench.json')
         args.out = os.path.join(ROOT, 'profiles', name)
     steps, warmup = max(args.steps, 20), max(args.warmup, 3)
@@ -73,7 +86,8 @@ def main():
     from pwv_amd.variables import VariableStore
     from tests.util import set_hparams
 
-    dev = torch.device('cuda', 0)
+    dev = torch.device('cuda', int(os.environ.get('LOCAL_RANK', '0')) if args.dp_rank else 0)
+    torch.cuda.set_device(dev)
     cfg = O.ModelConfig()
     set_hparams(cfg)
     store = VariableStore(device=dev)
@@ -116,6 +130,10 @@ def main():
     cols = 128 * 2 * sum(len(d) for d in cfg.dilations)
     train_forward.P = torch.zeros((n * mel.shape[1], cols), dtype=torch.float32, device=dev)
 
+    if args.dp_rank:
+        return dp_rank(args, TR, model, wav, mel, z, steps, warmup)
+    if args.opt:
+        return opt_legs(args, TR, O, cfg, store, model, wav, mel, z, steps, warmup)
     if args.power:
         return power_legs(args, TR, model, wav, mel, z, steps, warmup)
     if args.varlen:
@@ -313,6 +331,130 @@ def tran_legs(args, TR, O, cfg, store, model, wav, mel, z, steps, warmup):
         json.dump(out, f, indent=1)
         f.write('\n')
     print(json.dumps(out))
+
+
+def opt_legs(args, TR, O, cfg, store, model, wav, mel, z, steps, warmup):
+    import subprocess
+    import torch
+    from pwv_amd.models import IAFVocoder
+    from pwv_amd.variables import VariableStore
+    dev = wav.device
+    n, length = args.batch, args.length
+
+    def once(fn):
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+
+    store2 = VariableStore(device=dev)
+    store2.load_dict(O.init_weights(cfg, seed=2))
+    model2 = IAFVocoder(batch_size=n, length=length, store=store2, precision='f32')
+    unfused, fused = TR.Trainer(model), TR.Trainer(model2, fused=True)
+    variants = {'trainer_step_unfused': lambda: unfused.step(wav, mel, z=z), 'trainer_step_fused': lambda: fused.step(wav, mel, z=z)}
+    ms = {k: [] for k in variants}
+    for k in range(warmup + steps):
+        for name, fn in variants.items():            # alternating: A B A B ...
+            t = once(fn)
+            if k >= warmup:
+                ms[name].append(t)
+
+    # the launches alone, on the gradients of one step: 20 calls per timed window
+    _, _, grads = TR.loss_and_grad(model2, wav, mel, z=z)
+    ar, calls = fused.arenas, 20
+    vars1 = [store.vars[k] for k in unfused.names]
+    glist, state = [grads[k] for k in unfused.names], [None]
+
+    def foreach():
+        state[0] = TR.adam_ema_update(vars1, glist, state[0], unfused.lr, unfused.beta1, unfused.beta2, TR.ADAM_EPS, unfused.ema_decay)
+
+    alone = {'pack': lambda: ar.pack_grads(grads), 'adam_ema': lambda: ar.adam_ema(1e-4, 0.9, 0.999, 1e-8, 0.998, 1.0),
+             'unpack': lambda: ar.pack(ar.vars, ar.shadow, unpack=True), 'foreach_update': foreach}
+    for name, fn in alone.items():
+        def run(fn=fn):
+            for _ in range(calls):
+                fn()
+        ms[name] = [once(run) / calls for k in range(warmup + steps)][warmup:]
+    lay = ar.layout
+    out = {'model': 'default (4 flows, 10 + 10 + 10 + 30 layers, 2 nets each)', 'batch': n, 'length': length, 'steps': steps, 'warmup': warmup,
+           'device': torch.cuda.get_device_name(0), 'variables': len(lay.names), 'arena_floats': lay.total,
+           'parameters': sum(lay.counts), 'packed_tensors': ar._grad_tables[2].n, 'blocks': ar.vars.blocks,
+           'adam_ema_bytes': 4 * sum(lay.counts) * 9}
+    for k, v in ms.items():
+        out[k + '_ms'] = {'median': round(statistics.median(v), 4), 'min': round(min(v), 4), 'max': round(max(v), 4)}
+    out['fused_minus_unfused_ms'] = {'median': round(statistics.median(b - a for a, b in zip(ms['trainer_step_unfused'], ms['trainer_step_fused'])), 4)}
+    out['adam_ema_GBps'] = round(out['adam_ema_bytes'] / (statistics.median(ms['adam_ema']) * 1e-3) / 1e9, 1)
+
+    # data-parallel steps: N fresh processes per world size, one per GPU
+    visible = torch.cuda.device_count()
+    out['visible_devices'] = visible
+    out['data_parallel'] = {}
+    for world in (1, 2, 4, 8):
+        if world > min(args.gpus, visible):
+            continue
+        import socket
+        s = socket.socket()
+        s.bind(('127.0.0.1', 0))
+        port = s.getsockname()[1]
+        s.close()
+        procs = []
+        for r in range(world):
+            env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(world), MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port))
+            cmd = [sys.executable, os.path.abspath(__file__), '--dp-rank', '--steps', str(steps), '--warmup', str(warmup), '--batch', str(n),
+                   '--length', str(length)]
+            procs.append(subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE if r == 0 else subprocess.DEVNULL, text=True))
+        text, _ = procs[0].communicate(timeout=900)
+        codes = [p.wait(timeout=60) for p in procs]
+        if any(codes):
+            raise SystemExit('a rank of the world size %d measurement exited with %r' % (world, codes))
+        out['data_parallel'][str(world)] = json.loads([l for l in text.splitlines() if l.startswith('{')][-1])
+    if visible < 2 or args.gpus < 2:
+        out['scaling'] = 'unmeasured: %d device(s) visible, --gpus %d' % (visible, args.gpus)
+    with open(args.out, 'w') as f:
+        json.dump(out, f, indent=1)
+        f.write('\n')
+    print(json.dumps(out))
+
+
+def dp_rank(args, TR, model, wav, mel, z, steps, warmup):
+    """One rank of a data-parallel measurement: DataParallelTrainer.step on this rank's batch and the all-reduce of the gradient arena
+    alone; every figure is the MAX over the ranks of the ranks' medians.  Rank 0 prints one JSON line."""
+    import torch
+    import torch.distributed as dist
+    dev = wav.device
+    dist.init_process_group(backend='nccl', device_id=dev)
+    try:
+        tr = TR.DataParallelTrainer(model)
+
+        def once(fn):
+            torch.cuda.synchronize()
+            dist.barrier()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1)
+
+        step = [once(lambda: tr.step(wav, mel, z=z)) for k in range(warmup + steps)][warmup:]
+        calls = 20
+
+        def reduce():
+            for _ in range(calls):
+                TR.allreduce_sum_(tr.arenas.grad, tr.group)
+
+        alone = [once(reduce) / calls for k in range(warmup + steps)][warmup:]
+        meds = torch.tensor([statistics.median(step), statistics.median(alone)], dtype=torch.float64, device=dev)
+        dist.all_reduce(meds, op=dist.ReduceOp.MAX)
+        res = {'world': tr.world, 'backend': dist.get_backend(), 'per_rank_batch': args.batch, 'step_ms': round(float(meds[0]), 3),
+               'allreduce_ms': round(float(meds[1]), 4), 'arena_MB': round(4 * tr.arenas.grad.numel() / 1e6, 2)}
+    finally:
+        dist.destroy_process_group()
+    if tr.rank == 0:
+        print(json.dumps(res))
 
 
 if __name__ == '__main__':
