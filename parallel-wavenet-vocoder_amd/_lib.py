@@ -19,7 +19,7 @@ _REPO_ROOT = os.path.dirname(_PKG_DIR)
 LIB_PATH = os.environ.get('PWV_LIB') or os.path.join(_PKG_DIR, 'libpwv_hip.so')   # PWV_LIB: A/B another build
 CSRC = [os.path.join(_PKG_DIR, 'csrc', f) for f in ('pwv_layer.hip', 'pwv_layer_f16.hip', 'pwv_layer_h16.hip', 'pwv_misc.hip',
                                                     'pwv_stack_persist.hip', 'pwv_norm.hip', 'pwv_audio.hip', 'pwv_stream_tick.hip', 'pwv_score.hip', 'pwv_train.hip', 'pwv_train_loss.hip',
-                                                    'pwv_train_varlen.hip', 'pwv_train_cond.hip', 'pwv_train_opt.hip')]
+                                                    'pwv_train_varlen.hip', 'pwv_train_cond.hip', 'pwv_train_opt.hip', 'pwv_train_skip.hip')]
 
 HEADER_VERSION = 301          # PWV_HIP_VERSION of include/pwv_hip.h these ctypes mirrors were written against
 FIRST_FOLD_FLOATS = 2048      # PWV_FIRST_FOLD_FLOATS
@@ -64,6 +64,9 @@ TRAIN_COND_SYMBOLS = ('pwv_train_cond_workspace_bytes', 'pwv_train_cond_layer_fw
 TRAIN_COND_MAX = 96           # PWV_TRAIN_COND_MAX: condition channels the per-sample layer kernels take
 # ... and of include/pwv_hip_train_opt.h: the gradient arena (pack / unpack) and the fused Adam + EMA over it
 TRAIN_OPT_SYMBOLS = ('pwv_train_opt_pack_f32', 'pwv_train_opt_unpack_f32', 'pwv_train_opt_adam_ema_f32')
+# ... and of include/pwv_hip_train_skip.h: the layer and head kernels of training the skip-connection architecture
+TRAIN_SKIP_SYMBOLS = ('pwv_train_skip_workspace_bytes', 'pwv_train_skip_layer_fwd_f32', 'pwv_train_skip_head_fwd_f32',
+                      'pwv_train_skip_head_bwd_f32', 'pwv_train_skip_layer_bwd_f32')
 TRAIN_OPT_REC = 3             # PWV_TRAIN_OPT_REC: int64 per record of an arena table = {tensor address, arena offset, count}
 TRAIN_OPT_CHUNK = 1024        # PWV_TRAIN_OPT_CHUNK: floats per record of a block map
 TRAIN_OPT_MAX_GRID = 2048     # PWV_TRAIN_OPT_MAX_GRID: workgroups of a launch at most
@@ -431,6 +434,29 @@ class TrainCondArgs(Structure):
         self.struct_size = ctypes.sizeof(TrainCondArgs)
 
 
+class TrainSkipArgs(Structure):
+    """pwv_train_skip_args: one layer or head call of training the skip-connection architecture (include/pwv_hip_train_skip.h): the
+    embedded pwv_train_args as `train` (the new struct has fields named like two of its own: d_skip, d_skip_bias), then the skip sum
+    and the packed batch.  `set` routes a name to the new fields first, then to `train`."""
+    _fields_ = ([('train', TrainArgs)]
+                + [(n, c_void_p) for n in ('skip_sum', 'd_skip_sum', 'd_skip_sum_out', 'd_skip', 'd_skip_bias')]
+                + [('skip_accumulate', ctypes.c_int32)]
+                + [('cu_rows', c_void_p), ('cu_frames', c_void_p)]
+                + [(n, ctypes.c_int32) for n in ('n', 'rows', 'proj_rows')])
+    OWN = frozenset(('skip_sum', 'd_skip_sum', 'd_skip_sum_out', 'd_skip', 'd_skip_bias', 'skip_accumulate', 'cu_rows', 'cu_frames', 'n',
+                     'rows', 'proj_rows'))
+
+    def __init__(self, **kw):
+        super().__init__()
+        self.set(**kw)
+        self.train.struct_size = ctypes.sizeof(TrainSkipArgs)
+
+    def set(self, **kw):
+        for k, v in kw.items():
+            setattr(self if k in TrainSkipArgs.OWN else self.train, k, v)
+        return self
+
+
 class TrainLossVarlenArgs(Structure):
     """pwv_train_loss_varlen_args: the loss terms of a packed batch and their gradient for the prediction
     (include/pwv_hip_train_varlen.h)."""
@@ -662,6 +688,10 @@ def _declare(lib):
     lib.pwv_train_cond_workspace_bytes.argtypes = [POINTER(TrainCondArgs)]
     for name in TRAIN_COND_SYMBOLS[1:]:
         getattr(lib, name).argtypes = [POINTER(TrainCondArgs), c_void_p]
+    lib.pwv_train_skip_workspace_bytes.restype = c_size_t
+    lib.pwv_train_skip_workspace_bytes.argtypes = [POINTER(TrainSkipArgs)]
+    for name in TRAIN_SKIP_SYMBOLS[1:]:
+        getattr(lib, name).argtypes = [POINTER(TrainSkipArgs), c_void_p]
     lib.pwv_train_opt_pack_f32.argtypes = [POINTER(TrainOptPackArgs), c_void_p]
     lib.pwv_train_opt_unpack_f32.argtypes = [POINTER(TrainOptPackArgs), c_void_p]
     lib.pwv_train_opt_adam_ema_f32.argtypes = [POINTER(TrainOptAdamArgs), c_void_p]
@@ -686,7 +716,7 @@ def _declare(lib):
     lib.pwv_status_words_alloc.argtypes = [POINTER(c_void_p)]
     lib.pwv_status_words_free.argtypes = [c_void_p]
     lib.pwv_range_check_f32.argtypes = [f32p, c_int64, ctypes.c_float, c_void_p, c_void_p]
-    for name in EXPORTED_SYMBOLS + EXTENSION_SYMBOLS + LIVE_TICK_SYMBOLS + SCORE_SYMBOLS + TRAIN_SYMBOLS + TRAIN_LOSS_SYMBOLS + TRAIN_VARLEN_SYMBOLS + TRAIN_COND_SYMBOLS + TRAIN_OPT_SYMBOLS:      # fails loudly (AttributeError) if a symbol is missing
+    for name in EXPORTED_SYMBOLS + EXTENSION_SYMBOLS + LIVE_TICK_SYMBOLS + SCORE_SYMBOLS + TRAIN_SYMBOLS + TRAIN_LOSS_SYMBOLS + TRAIN_VARLEN_SYMBOLS + TRAIN_COND_SYMBOLS + TRAIN_OPT_SYMBOLS + TRAIN_SKIP_SYMBOLS:      # fails loudly (AttributeError) if a symbol is missing
         getattr(lib, name)
     return lib
 

@@ -1,7 +1,8 @@
 // The unit bodies of training that depend on where an utterance begins and ends ("Training" and "Packed
 // training"): front forward, layer forward, layer backward, front backward, written once over a GEOMETRY POLICY and, the two layer
 // bodies, a CONDITIONING POLICY (ProjCond below: a row of the frame-rate projection P; SampleCond, csrc/pwv_train_cond.hip: a condition
-// row per sample).
+// row per sample) and a SKIP POLICY (NoSkip below: the head reads the last layer's o; SumSkip: every layer adds o skip + skip_bias to the
+// net's skip sum S and takes dS skip^T into its d o, csrc/pwv_train_skip.hip).
 //   UniformGeo   utterance n owns rows n T .. (n + 1) T - 1 and P rows n frames ..: t, n and the P row are arithmetic on the row
 //                (csrc/pwv_train.hip instantiates the bodies with it under the kernel names of include/pwv_hip_train.h).
 //   PackedGeo    utterance i owns rows cu_rows[i] .. cu_rows[i + 1] - 1 and P rows cu_frames[i] ..: 33 threads LOCATE the rows of a
@@ -228,6 +229,62 @@ __device__ __forceinline__ void load_a(float* a, const float* x, int u, const Ge
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------
+// skip policies: whether a layer feeds the net's skip sum S (tile32, 128 channels: block u = 4096 floats) and reads its gradient dS
+//   Params      what the kernel takes beside the layer's parameters
+//   Tile        the unit's dS rows in LDS (backward)             kPartFloats   what a workgroup's partial grows by: d skip [64][128]
+// NoSkip is empty: a body instantiated with it is the text it was before the policy existed.
+// ------------------------------------------------------------------------------------------------------------------------------
+struct NoSkip {
+    static constexpr bool kOn = false;
+    static constexpr int kPartFloats = 0;
+    struct Params {};
+    struct Tile {};
+};
+
+struct SkipParams {
+    const float *skip, *skip_bias;              // this layer's skip [64][128], skip_bias [128] or NULL
+    float* sum;                                 // S (forward)
+    const float* d_sum;                         // dS (backward)
+    int accumulate;                             // forward: 0 = S is written (layer 0), 1 = S is added to
+};
+
+struct SumSkip {
+    static constexpr bool kOn = true;
+    static constexpr int kPartFloats = 64 * 128;
+    using Params = SkipParams;
+    struct Tile {
+        float ds[32 * kLdW];
+    };
+};
+
+// block u of a 128-channel tile32 buffer -> LDS [32][ld]; rows beyond the batch read as zeros.  RELU: max(v, 0)
+template <bool RELU>
+__device__ __forceinline__ void tile32w_to_lds(float* dst, int ld, const float* src, int u, int rows) {
+    for (int idx = threadIdx.x; idx < 1024; idx += kTrThreads) {
+        const int q = idx >> 5, r = idx & 31;
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (32 * u + r < rows) v = *reinterpret_cast<const f32x4*>(src + (size_t)u * 4096 + q * 128 + r * 4);
+        float* d = dst + r * ld + 4 * q;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) d[e] = RELU ? fmaxf(v[e], 0.f) : v[e];
+    }
+}
+
+// 32 rows x 128 channels of an LDS array -> block u of a 128-channel tile32 buffer, the rows of the batch alone (a padding row is
+// neither read nor written); accumulate: dst + src, one rounding
+__device__ __forceinline__ void lds_to_tile32w(float* dst, int u, const float* src, int ld, int rows, int accumulate) {
+    for (int idx = threadIdx.x; idx < 1024; idx += kTrThreads) {
+        const int q = idx >> 5, r = idx & 31;
+        if (32 * u + r >= rows) continue;
+        const float* s = src + r * ld + 4 * q;
+        f32x4 v = {s[0], s[1], s[2], s[3]};
+        f32x4* d = reinterpret_cast<f32x4*>(dst + (size_t)u * 4096 + q * 128 + r * 4);
+        if (accumulate) v = *d + v;
+        *d = v;
+    }
+}
+
 struct LayerFwdParams {
     const float *x, *proj, *filter, *gate, *dense, *dense_bias;
     float* x_out;
@@ -339,8 +396,8 @@ __device__ __forceinline__ void front_fwd_body(const FrontFwdParams& p) {
     }
 }
 
-template <class Geo, class Cond>
-__device__ __forceinline__ void layer_fwd_body(const LayerFwdParams& p, const typename Cond::Params& cp) {
+template <class Geo, class Cond, class Skip = NoSkip>
+__device__ __forceinline__ void layer_fwd_body(const LayerFwdParams& p, const typename Cond::Params& cp, const typename Skip::Params& sp = {}) {
     __shared__ float a[32 * kLdW];
     __shared__ float fg[32 * kLdW];
     __shared__ float o[32 * kLdH];
@@ -360,7 +417,30 @@ __device__ __forceinline__ void layer_fwd_body(const LayerFwdParams& p, const ty
             o[r * kLdH + c] = tanhf(fg[r * kLdW + c]) * sigmoid_f(fg[r * kLdW + 64 + c]);
         }
         __syncthreads();
-        if (p.last) {
+        if constexpr (Skip::kOn) {
+            // o skip + skip_bias, columns 32 w .., into fg (FG is spent); x + o dense + dense_bias into columns 0 .. 63 of a (the tap at
+            // t - d is spent, and wave w reads and writes its own columns): no barrier between the two
+            {
+                f32x16 acc = zero16();
+                gemm_xw<64>(acc, o, kLdH, sp.skip + 32 * w, 128);
+                const float b = sp.skip_bias ? sp.skip_bias[32 * w + j] : 0.f;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) fg[acc_row(r, h) * kLdW + 32 * w + j] = acc[r] + b;
+            }
+            if (!p.last && w < 2) {
+                f32x16 acc = zero16();
+                gemm_xw<64>(acc, o, kLdH, p.dense + 32 * w, 64);
+                const float b = p.dense_bias ? p.dense_bias[32 * w + j] : 0.f;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int i = acc_row(r, h);
+                    a[i * kLdW + 32 * w + j] = a[i * kLdW + 64 + 32 * w + j] + acc[r] + b;
+                }
+            }
+            __syncthreads();
+            lds_to_tile32w(sp.sum, u, fg, kLdW, p.g.rows, sp.accumulate);
+            if (!p.last) lds_to_tile32(p.x_out, u, a, kLdW, 0);
+        } else if (p.last) {
             lds_to_tile32(p.x_out, u, o, kLdH, 0);
         } else {
             if (w < 2) {        // x + o dense + dense_bias, columns 32 w ..
@@ -383,32 +463,37 @@ __device__ __forceinline__ void layer_fwd_body(const LayerFwdParams& p, const ty
 // ------------------------------------------------------------------------------------------------------------------------------
 // backward
 // ------------------------------------------------------------------------------------------------------------------------------
-template <class Geo, class Cond, bool LAST>
-__device__ __forceinline__ void layer_bwd_body(const LayerBwdParams& p, const typename Cond::Params& cp) {
+template <class Geo, class Cond, bool LAST, class Skip = NoSkip>
+__device__ __forceinline__ void layer_bwd_body(const LayerBwdParams& p, const typename Cond::Params& cp, const typename Skip::Params& sp = {}) {
     __shared__ float a[32 * kLdW];              // [x[t - d] | x[t]], then [V | U]
     __shared__ float fg[32 * kLdW];             // FG, then dFG
     __shared__ float od[32 * kLdH];             // d o, then o: the gating pass replaces element by element ("LDS: aliasing")
     __shared__ float gin[32 * kLdH];            // g
     __shared__ typename Cond::Tile tile;
+    __shared__ typename Skip::Tile stile;       // dS
     __shared__ typename Geo::Loc loc;
     const int w = threadIdx.x >> 6;
     const int units = (p.g.rows + 31) / 32;
-    f32x16 g_wfg[4], g_dense = zero16();
+    f32x16 g_wfg[4], g_dense = zero16(), g_skip[2];
 #pragma unroll
     for (int b = 0; b < 4; ++b) g_wfg[b] = zero16();
+    g_skip[0] = zero16();
+    g_skip[1] = zero16();
     float g_db = 0.f;                           // thread c < 64: d dense_bias[c]
     typename Cond::Acc g_cond;
     for (int u = blockIdx.x; u < units; u += gridDim.x) {
         Geo::locate(loc, u, p.g, p.tab);
         load_a<Geo>(a, p.x, u, p.g, loc);
         Cond::template stage<Geo>(tile, u, p.g, loc, cp);
-        if (LAST) tile32_to_lds(od, kLdH, 0, p.d_o, u, p.g.rows);
-        else load_g<Geo>(gin, kLdH, p.u_next, p.v_next, u, 32, p.g, loc);
+        if constexpr (Skip::kOn) tile32w_to_lds<false>(stile.ds, kLdW, sp.d_sum, u, p.g.rows);
+        if (LAST && !Skip::kOn) tile32_to_lds(od, kLdH, 0, p.d_o, u, p.g.rows);
+        if (!LAST) load_g<Geo>(gin, kLdH, p.u_next, p.v_next, u, 32, p.g, loc);
         __syncthreads();
         Cond::fg(fg, a, tile, p.filter, p.gate, p.proj, p.g, cp);
-        if (!LAST && w < 2) {                   // d o = g dense^T, columns 32 w ..
+        if ((!LAST || Skip::kOn) && w < 2) {    // d o = g dense^T (+ dS skip^T), columns 32 w ..
             f32x16 acc = zero16();
-            gemm_xwt<64>(acc, gin, kLdH, p.dense + (size_t)32 * w * 64, 64);
+            if (!LAST) gemm_xwt<64>(acc, gin, kLdH, p.dense + (size_t)32 * w * 64, 64);
+            if constexpr (Skip::kOn) gemm_xwt<128>(acc, stile.ds, kLdW, sp.skip + (size_t)32 * w * 128, 128);
             acc_to_lds(acc, od, kLdH, 32 * w);
         }
         __syncthreads();
@@ -426,6 +511,8 @@ __device__ __forceinline__ void layer_bwd_body(const LayerBwdParams& p, const ty
             if (threadIdx.x < 64)
                 for (int r = 0; r < 32; ++r) g_db += gin[r * kLdH + threadIdx.x];
         }
+        if constexpr (Skip::kOn)
+            for (int b = 0; b < 2; ++b) gemm_tn(g_skip[b], od, kLdH, 32 * b, stile.ds, kLdW, 32 * w);   // d skip += o^T dS
         Cond::template unit_grad<Geo>(g_cond, tile, fg, u, p, loc, cp);
         // [V | U] = dFG Wfg^T: wave w owns input channels 32 w .. of the 128 (0..63: the tap at t - d, 64..127: the tap at t)
         f32x16 acc = zero16();
@@ -445,13 +532,15 @@ __device__ __forceinline__ void layer_bwd_body(const LayerBwdParams& p, const ty
         lds_to_tile32(p.u, u, a, kLdW, 64);
         __syncthreads();
     }
-    float* part = p.part + (size_t)blockIdx.x * Cond::part_floats(cp);
+    float* part = p.part + (size_t)blockIdx.x * (Cond::part_floats(cp) + Skip::kPartFloats);
     for (int b = 0; b < 4; ++b) acc_to_part(g_wfg[b], part, 128, 32 * b, 32 * w);
     if (!LAST) {
         acc_to_part(g_dense, part + 128 * 128, 64, 32 * (w >> 1), 32 * (w & 1));
         if (threadIdx.x < 64) part[128 * 128 + 64 * 64 + threadIdx.x] = g_db;
     }
     Cond::flush(g_cond, part + kLayerPart, cp);
+    if constexpr (Skip::kOn)
+        for (int b = 0; b < 2; ++b) acc_to_part(g_skip[b], part + Cond::part_floats(cp), 128, 32 * b, 32 * w);
 }
 
 struct FrontBwdParams {

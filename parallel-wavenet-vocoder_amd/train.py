@@ -9,8 +9,12 @@ Scope: what hparams/default.yaml trains -- filter_width 2, R = D = 64, S = 128, 
 accumulation, separate scaler and shifter nets, exact-fp32 arithmetic; uniform [N, T] batches (loss_and_grad) or packed batches of
 utterances of different lengths, unpadded (loss_and_grad_varlen, `--varlen`).  And the reference's second architecture,
 cond_upsample_method 'transposed_conv' (models.py:109-124; hparams test/tran): uniform batches at hop_length 80 = 4 * 4 * 5, an even
-condition_channels <= 96, no normalised conditioning.  Everything else is refused with a PwvError that names the reason (`refusal`);
-nothing falls back to another implementation.
+condition_channels <= 96, no normalised conditioning.  And, on request (use_skip_connection=True; the command line asks when the case
+sets model.use_skip_connection, hparams train/small_skip), the skip-connection architecture (modules.py:142-147, :242-250): the head
+of every net reads the sum of all layers' skip outputs -- uniform and packed batches, one GPU or data-parallel, with or without the
+power loss (include/pwv_hip_train_skip.h; DESIGN.md section 9, "Training the skip-connection architecture"); not together with
+'transposed_conv'.  Everything else is refused with a PwvError that names the reason (`refusal`); nothing falls back to another
+implementation.
 
 Data-parallel (the reference's SyncMultiGPUTrainerReplicated, train.py:66-69): DataParallelTrainer, one replica per rank; the gradients
 of a step are packed into ONE flat arena, all-reduced once, and one fused Adam + EMA launch applies the same update on every rank
@@ -52,12 +56,19 @@ TCONV_STRIDES = (4, 4, 5)   # models.py:109-124: the strides of the three transp
 
 
 # ---- what is refused ----------------------------------------------------------------------------------------------------------------
-def refusal(model=None, wav=None, melspec=None, power_weight=None, packed=False) -> Optional[str]:
+def refusal(model=None, wav=None, melspec=None, power_weight=None, packed=False, use_skip_connection=None) -> Optional[str]:
     """Why the current hparams / this model / these inputs cannot be trained here, or None.  Looks at structure only: no GPU.
     `power_weight`: the weight of the STFT power loss the caller asks for explicitly (loss_and_grad's argument); None = the L1 alone,
     and then hparams that ask for a power loss are refused instead of being trained without it.  `packed`: the caller is
-    loss_and_grad_varlen, which takes its lengths from the utterances and not from the model."""
+    loss_and_grad_varlen, which takes its lengths from the utterances and not from the model.  `use_skip_connection`: True = the
+    caller asks for the skip-connection architecture (hparams that say False are then a mismatch); None = the default architecture,
+    and hparams with model.use_skip_connection are refused instead of being trained as something else."""
     m = hp.model
+    if use_skip_connection not in (None, True):
+        return 'use_skip_connection %r: pass True to train the skip-connection architecture, None for the default one' % (use_skip_connection,)
+    if use_skip_connection and not m.use_skip_connection:
+        return ('use_skip_connection=True under hparams with model.use_skip_connection False: the request does not match the '
+                'architecture the hparams describe')
     if m.cond_upsample_method == 'transposed_conv':
         what = "cond_upsample_method 'transposed_conv': transposed-conv conditioning is differentiated "
         hop, C = int(hp.signal.hop_length), int(m.condition_channels)
@@ -77,8 +88,13 @@ def refusal(model=None, wav=None, melspec=None, power_weight=None, packed=False)
         return "normalize_wavenet %r: the 'bn' / 'in' normalisers are not differentiated" % m.normalize_wavenet
     if m.get('normalize'):
         return "normalize %r: the 'bn' / 'in' normalisers are not differentiated" % m.normalize
-    if m.use_skip_connection:
-        return 'use_skip_connection True: skip accumulation over all layers is not differentiated'
+    if m.use_skip_connection and not use_skip_connection:
+        return ('use_skip_connection True: skip accumulation over all layers is not differentiated by a bare call; it is trained on '
+                'request (loss_and_grad / loss_and_grad_varlen / Trainer: use_skip_connection=True)')
+    if m.use_skip_connection and m.cond_upsample_method == 'transposed_conv':
+        return ("use_skip_connection True with cond_upsample_method 'transposed_conv': skip accumulation is not differentiated together "
+                'with per-sample conditioning (the per-sample layer kernels\' 62 KB of LDS and the dS tile leave no room for two workgroups '
+                'per compute unit)')
     if m.get('shared_nets'):
         return 'shared_nets True: one shared net per flow is not differentiated (separate scaler and shifter nets only)'
     shape = (m.filter_width, m.residual_channels, m.dilation_channels, m.skip_channels)
@@ -269,6 +285,104 @@ class _CondGeometry(_Geometry):
         return kw
 
 
+class _Skip(object):
+    """The skip-connection architecture over a uniform or a packed geometry (include/pwv_hip_train_skip.h): the layer and head calls
+    take pwv_train_skip_args -- the geometry's own struct in front, the packed tables copied behind it --, the front calls and the
+    loss stay the geometry's."""
+    skip = True
+
+    def layer_args(self, **kw):
+        base = self.args()
+        a = _lib.TrainSkipArgs()
+        ctypes.memmove(ctypes.addressof(a.train), ctypes.addressof(base), ctypes.sizeof(_lib.TrainArgs))
+        a.train.struct_size = ctypes.sizeof(_lib.TrainSkipArgs)
+        if isinstance(base, _lib.TrainVarlenArgs):
+            a.set(cu_rows=base.cu_rows, cu_frames=base.cu_frames, n=base.n, rows=base.rows, proj_rows=base.proj_rows)
+        return a.set(**{k: _ptr(v) if isinstance(v, torch.Tensor) else v for k, v in kw.items()})
+
+    head_args = layer_args
+
+    def entry(self, kind):
+        return 'pwv_train_skip_%s_f32' % kind if kind.startswith('layer') else super().entry(kind)
+
+    def workspace_bytes(self):
+        return _lib.lib().pwv_train_skip_workspace_bytes(ctypes.byref(self.layer_args())), 'pwv_train_skip_workspace_bytes'
+
+
+class _SkipGeometry(_Skip, _Geometry):
+    pass
+
+
+class _SkipPackedGeometry(_Skip, _PackedGeometry):
+    pass
+
+
+def _tile32w(rows, device):
+    return torch.empty(((rows + 31) // 32) * 32 * 128, dtype=torch.float32, device=device)
+
+
+def _net_forward_skip(net: _Net, geo: _Geometry, xin):
+    """The skip-connection architecture: x_j for every layer, the net's skip sum S and its output y [rows].  Layer 0 writes S, every
+    other layer adds to it in stream order; the last layer has no dense product and leaves no o."""
+    dev, L = xin.device, len(net.dilations)
+    xs = [_tile32(geo.rows, dev) for _ in range(L)]
+    S, y = _tile32w(geo.rows, dev), torch.empty(geo.rows, dtype=torch.float32, device=dev)
+    _call(geo.entry('front_fwd'), geo.args(in_=xin, causal_filter=net.cf, x_out=xs[0]))
+    for j, d in enumerate(net.dilations):
+        v, last = net.layers[j], j == L - 1
+        _call(geo.entry('layer_fwd'), geo.layer_args(form=_lib.TRAIN_LAST if last else _lib.TRAIN_RESIDUAL, dilation=d, x=xs[j],
+                                                       filter=v['filter'], gate=v['gate'], dense=None if last else v['dense'],
+                                                       dense_bias=None if last else v.get('dense_bias'), x_out=None if last else xs[j + 1],
+                                                       skip=v['skip'], skip_bias=v.get('skip_bias'), skip_sum=S, skip_accumulate=int(j > 0),
+                                                       **geo.cond_fwd(net, j, v)))
+    h = net.head
+    _call('pwv_train_skip_head_fwd_f32', geo.head_args(skip_sum=S, post1=h['postprocess1'], post1_bias=h.get('postprocess1_bias'),
+                                                       post2=h['postprocess2'], post2_bias=h.get('postprocess2_bias'), y=y))
+    return xs, S, y
+
+
+def _net_backward_skip(net: _Net, geo: _Geometry, saved, xin, d_out, d_mul, scale, d_in, accumulate, dP, ws, grads):
+    """_net_backward for the skip-connection architecture: the head leaves dS and its column sums, which are every layer's
+    d skip_bias; every layer takes dS skip^T into its d o and leaves its d skip."""
+    xs, S, _ = saved
+    dev, L = xin.device, len(net.dilations)
+    g = lambda name, like: grads.setdefault(name, torch.empty_like(like))
+    h = net.head
+    hp_ = net.scope + '/postprocessing/'
+    opt = lambda d, key, name: g(name, d[key]) if key in d else None
+    dS = _tile32w(geo.rows, dev)
+    biased = [j for j in range(L) if 'skip_bias' in net.layers[j]]
+    sums = torch.empty(128, dtype=torch.float32, device=dev) if biased else None
+    _call('pwv_train_skip_head_bwd_f32', geo.head_args(
+        skip_sum=S, d_out=d_out, d_mul=d_mul, post1=h['postprocess1'], post1_bias=h.get('postprocess1_bias'), post2=h['postprocess2'],
+        post2_bias=h.get('postprocess2_bias'), d_skip_sum_out=dS, d_skip_bias=sums,
+        d_post1=g(hp_ + 'postprocess1', h['postprocess1']), d_post1_bias=opt(h, 'postprocess1_bias', hp_ + 'postprocess1_bias'),
+        d_post2=g(hp_ + 'postprocess2', h['postprocess2']), d_post2_bias=opt(h, 'postprocess2_bias', hp_ + 'postprocess2_bias'),
+        workspace=ws, workspace_bytes=ws.numel() * 4))
+    if biased:
+        copies = sums.repeat(len(biased), 1)                                            # one launch: the same bits for every layer
+        for k, j in enumerate(biased):
+            grads[net.name(j, 'skip_bias')] = copies[k]
+    uv = [(_tile32(geo.rows, dev), _tile32(geo.rows, dev)) for _ in range(2)]
+    for j in range(L - 1, -1, -1):
+        v, last = net.layers[j], j == L - 1
+        u_next, v_next = (None, None) if last else uv[(j + 1) & 1]
+        _call(geo.entry('layer_bwd'), geo.layer_args(
+            form=_lib.TRAIN_LAST if last else _lib.TRAIN_RESIDUAL, dilation=net.dilations[j],
+            next_dilation=1 if last else net.dilations[j + 1], x=xs[j],
+            filter=v['filter'], gate=v['gate'], dense=None if last else v['dense'], u_next=u_next, v_next=v_next,
+            skip=v['skip'], d_skip_sum=dS, d_skip=g(net.name(j, 'skip'), v['skip']),
+            u=uv[j & 1][0], v=uv[j & 1][1], **geo.cond_bwd(net, j, v, dP, g, opt),
+            d_filter=g(net.name(j, 'filter'), v['filter']), d_gate=g(net.name(j, 'gate'), v['gate']),
+            d_dense=None if last else g(net.name(j, 'dense'), v['dense']),
+            d_dense_bias=None if last else opt(v, 'dense_bias', net.name(j, 'dense_bias')),
+            workspace=ws, workspace_bytes=ws.numel() * 4))
+    _call(geo.entry('front_bwd'), geo.args(
+        in_=xin, causal_filter=net.cf, u_next=uv[0][0], v_next=uv[0][1], next_dilation=net.dilations[0], d_out=d_out, scale=scale,
+        d_in=d_in, accumulate=int(accumulate), d_causal_filter=g(net.scope + '/causal_layer/filter', net.cf),
+        workspace=ws, workspace_bytes=ws.numel() * 4))
+
+
 def _net_forward(net: _Net, geo: _Geometry, xin):
     """x_j for every layer, the last layer's o and the net's output y [rows]."""
     dev, L = xin.device, len(net.dilations)
@@ -364,7 +478,7 @@ def _head(shape, rows, power_weight, terms):
 
 
 def loss_and_grad(model, wav, melspec, z=None, seed=None, max_workgroups: int = 0, power_weight: Optional[float] = None,
-                  terms: Optional[dict] = None):
+                  terms: Optional[dict] = None, use_skip_connection: Optional[bool] = None):
     """(loss, pred, grads) of one batch: `loss` the L1 mean |pred - wav| as a device scalar (models.py:93 `loss/likelihood`), `pred`
     [N, T, 1] the model's output, `grads` {name: device tensor of the variable's shape} for EVERY trainable variable of the store under
     'iaf_vocoder' -- exact zeros for the ones the model never reads (skip / skip_bias of every layer but the last, dense / dense_bias of
@@ -375,9 +489,14 @@ def loss_and_grad(model, wav, melspec, z=None, seed=None, max_workgroups: int = 
     `power_weight` = w >= 0 asks for the reference's whole cost, likelihood + w * power (models.py:95-99; hp.train.weight_power_loss is
     not consulted): the loss head is then one pwv_train_loss_f32 (include/pwv_hip_train_loss.h) with hp.signal.win_length / hop_length,
     `loss` is the total as a float32 device scalar, and `terms`, if a dict is passed, receives the device scalars 'likelihood', 'power'
-    and 'total'.  None: the L1 alone, and hparams with train.weight_power_loss > 0 are refused."""
+    and 'total'.  None: the L1 alone, and hparams with train.weight_power_loss > 0 are refused.
+
+    `use_skip_connection` = True asks for the skip-connection architecture (hparams with model.use_skip_connection; the kernels of
+    include/pwv_hip_train_skip.h): the head of every net reads the sum of all layers' skip outputs, every layer's skip / skip_bias has a
+    gradient and the exact zeros are the last layer's dense / dense_bias.  None: the default architecture, launch for launch what it
+    was, and hparams with model.use_skip_connection are refused."""
     from . import engine
-    why = refusal(model, wav, melspec, power_weight=power_weight)
+    why = refusal(model, wav, melspec, power_weight=power_weight, use_skip_connection=use_skip_connection)
     if why:
         raise PwvError('training refused: ' + why)
     store = model.store or get_default_store()
@@ -401,7 +520,7 @@ def loss_and_grad(model, wav, melspec, z=None, seed=None, max_workgroups: int = 
     if hp.model.cond_upsample_method == 'transposed_conv':
         geo = _CondGeometry(N, T, int(hp.model.condition_channels), int(max_workgroups))
     else:
-        geo = _Geometry(N, T, t_mel, cols, int(max_workgroups))
+        geo = (_SkipGeometry if use_skip_connection else _Geometry)(N, T, t_mel, cols, int(max_workgroups))
 
     loss, x, grads = _forward_backward(store, flows, geo, melspec.reshape(N * t_mel, n_mels), noise.reshape(N * T).contiguous(),
                                        wav.reshape(N * T), _head((N, T), N * T, power_weight, terms))
@@ -469,8 +588,9 @@ def _forward_backward(store, flows, geo, mel2, x, y, head):
         _lib.check(-1, ws_name)
     ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=dev)
     saved = []
+    net_forward, net_backward = (_net_forward_skip, _net_backward_skip) if getattr(geo, 'skip', False) else (_net_forward, _net_backward)
     for pair in flows:
-        s = [_net_forward(net, geo, x) for net in pair]
+        s = [net_forward(net, geo, x) for net in pair]
         saved.append((x, s))
         x = x * s[0][2] + s[1][2]                                                       # modules.py:59
     loss, d_out = head(x, y)
@@ -483,8 +603,8 @@ def _forward_backward(store, flows, geo, mel2, x, y, head):
     for i in range(len(flows) - 1, -1, -1):
         xin, s = saved[i]
         d_in = torch.empty_like(xin) if i > 0 else None
-        _net_backward(flows[i][0], geo, s[0], xin, d_out, xin, s[0][2], d_in, False, dP, ws, grads)      # ds = d out * in
-        _net_backward(flows[i][1], geo, s[1], xin, d_out, None, None, d_in, True, dP, ws, grads)         # db = d out
+        net_backward(flows[i][0], geo, s[0], xin, d_out, xin, s[0][2], d_in, False, dP, ws, grads)       # ds = d out * in
+        net_backward(flows[i][1], geo, s[1], xin, d_out, None, None, d_in, True, dP, ws, grads)          # db = d out
         d_out = d_in
 
     if per_sample:       # (the gradients of gc_* and of the biases came straight from the kernels)
@@ -525,7 +645,7 @@ def _fill_unread(store, grads, loss, x):
 
 # ---- packed batches: utterances of different lengths, unpadded ("Packed training") ------------------------------
 def loss_and_grad_varlen(model, wavs, mels, z=None, seeds=None, max_workgroups: int = 0, power_weight: Optional[float] = None,
-                         terms: Optional[dict] = None):
+                         terms: Optional[dict] = None, use_skip_connection: Optional[bool] = None):
     """loss_and_grad over utterances of DIFFERENT lengths in one packed batch, without padding: (loss, preds, grads).  wavs[i] is [T_i] or
     [T_i, 1] and mels[i] [1 + T_i / hop, n_mels], both on the GPU, T_i >= hop a multiple of hop.  `loss` = sum |pred - wav| / sum T_i
     (with `power_weight` = w: + w * power, the STFT power loss over the frames of all utterances that are at least win_length long --
@@ -533,10 +653,10 @@ def loss_and_grad_varlen(model, wavs, mels, z=None, seeds=None, max_workgroups: 
     loss_and_grad, exact zeros for unread variables included.  `seeds` (one integer per utterance) gives every utterance a noise stream
     of its own, as IAFVocoder.generate_varlen does; `z`, a list of [T_i, 1] (or [T_i]), replaces the noise; with neither, one draw of
     sum T_i counters continues the model's stream.  The constructor's batch_size and length are not used.  Only enqueues: the kernels
-    read the lengths from device tables (include/pwv_hip_train_varlen.h)."""
+    read the lengths from device tables (include/pwv_hip_train_varlen.h).  `use_skip_connection`: as for loss_and_grad."""
     from . import engine
     from .models import noise_streams
-    why = refusal(model, power_weight=power_weight, packed=True)
+    why = refusal(model, power_weight=power_weight, packed=True, use_skip_connection=use_skip_connection)
     if why:
         raise PwvError('training refused: ' + why)
     if not isinstance(wavs, (list, tuple)) or not isinstance(mels, (list, tuple)) or not wavs:
@@ -581,7 +701,7 @@ def loss_and_grad_varlen(model, wavs, mels, z=None, seeds=None, max_workgroups: 
         noise = torch.cat([engine._require_cuda_f32(v, 'z[%d]' % i).reshape(-1) for i, v in enumerate(z)])
     flows = model_nets(model, store)
     cols = sum(128 * len(net.dilations) for pair in flows for net in pair)
-    geo = _PackedGeometry(layout, cols, int(max_workgroups))
+    geo = (_SkipPackedGeometry if use_skip_connection else _PackedGeometry)(layout, cols, int(max_workgroups))
 
     loss, x, grads = _forward_backward(store, flows, geo, torch.cat(mels), noise.reshape(layout.rows).contiguous(),
                                        torch.cat([w.reshape(-1) for w in wavs]), _head(layout, layout.rows, power_weight, terms))
@@ -814,6 +934,7 @@ class Trainer(object):
     """The reference's training step (models.py:80-103) on one model: loss_and_grad, then adam_ema_update on the store's variables in
     place.  Defaults from hparams: lr = train.lr, beta2 = train.adam_beta2, ema_decay = train.ema_decay if train.use_ema.
     `power_weight` goes to every loss_and_grad; `terms` then holds the last step's 'likelihood', 'power' and 'total' (device scalars).
+    `use_skip_connection` goes to every loss_and_grad too: True trains the skip-connection architecture.
 
     `fused` (default False: adam_ema_update's torch._foreach passes, launch for launch what they were): the gradients of a step are
     packed into one flat arena by one launch and ONE pwv_train_opt_adam_ema_f32 launch updates the model
@@ -821,8 +942,9 @@ class Trainer(object):
     shadows() work as before -- an .npz of either path loads into the other."""
 
     def __init__(self, model, lr=None, beta2=None, ema_decay=_UNSET, max_workgroups: int = 0, power_weight: Optional[float] = None,
-                 fused: bool = False):
+                 fused: bool = False, *, use_skip_connection: Optional[bool] = None):
         self.model = model
+        self.use_skip_connection = use_skip_connection      # None: the default architecture; True: skip connections (loss_and_grad)
         self.fused = bool(fused)
         self.arenas: Optional[_Arenas] = None
         self._vars_version = None
@@ -840,7 +962,7 @@ class Trainer(object):
 
     def _bind(self, packed=False):
         """Every variable of the model exists from here on; the optimiser's lists follow the sorted names."""
-        why = refusal(self.model, power_weight=self.power_weight, packed=packed)
+        why = refusal(self.model, power_weight=self.power_weight, packed=packed, use_skip_connection=self.use_skip_connection)
         if why:
             raise PwvError('training refused: ' + why)
         if self.names is None:
@@ -854,7 +976,7 @@ class Trainer(object):
         vars = self._bind()
         terms: Dict[str, torch.Tensor] = {}
         loss, _, grads = loss_and_grad(self.model, wav, mel, z=z, max_workgroups=self.max_workgroups, power_weight=self.power_weight,
-                                       terms=terms)
+                                       terms=terms, use_skip_connection=self.use_skip_connection)
         return self._update(vars, loss, grads, terms)
 
     def step_varlen(self, wavs, mels, z=None, seeds=None):
@@ -863,7 +985,7 @@ class Trainer(object):
         vars = self._bind(packed=True)
         terms: Dict[str, torch.Tensor] = {}
         loss, _, grads = loss_and_grad_varlen(self.model, wavs, mels, z=z, seeds=seeds, max_workgroups=self.max_workgroups,
-                                              power_weight=self.power_weight, terms=terms)
+                                              power_weight=self.power_weight, terms=terms, use_skip_connection=self.use_skip_connection)
         return self._update(vars, loss, grads, terms)
 
     def _update(self, vars, loss, grads, terms):
@@ -1178,7 +1300,8 @@ def train(case='default', ckpt=None, steps=None, seed=0, varlen=False, gpus=None
     hp.set_hparam_yaml(case)
     power_weight = float(hp.train.get('weight_power_loss', 0) or 0)
     power_weight = power_weight if power_weight > 0 else None
-    why = refusal(power_weight=power_weight)
+    use_skip = True if hp.model.use_skip_connection else None       # the case's architecture is what the loop asks for
+    why = refusal(power_weight=power_weight, use_skip_connection=use_skip)
     if why:
         raise PwvError('training refused: ' + why)
     launched = 'WORLD_SIZE' in os.environ
@@ -1206,13 +1329,13 @@ def train(case='default', ckpt=None, steps=None, seed=0, varlen=False, gpus=None
         else:
             dist.init_process_group(backend='nccl', device_id=device)       # 'nccl' is RCCL on ROCm
     try:
-        return _train_rank(power_weight, device, seed, steps, ckpt, varlen, world, rank)
+        return _train_rank(power_weight, device, seed, steps, ckpt, varlen, world, rank, use_skip)
     finally:
         if world > 1:
             dist.destroy_process_group()
 
 
-def _train_rank(power_weight, device, seed, steps, ckpt, varlen, world, rank):
+def _train_rank(power_weight, device, seed, steps, ckpt, varlen, world, rank, use_skip=None):
     """The loop of train() in one process: the only rank, or one of `world`."""
     from .audio_frontend import wav_to_mel_device
     from .models import IAFVocoder
@@ -1225,7 +1348,8 @@ def _train_rank(power_weight, device, seed, steps, ckpt, varlen, world, rank):
     store = reset_default_store(device=device)
     model = IAFVocoder(batch_size=batch, length=length, store=store, precision='f32')
     model.noise_seed = seed
-    trainer = DataParallelTrainer(model, power_weight=power_weight) if world > 1 else Trainer(model, power_weight=power_weight)
+    kw = dict(power_weight=power_weight, use_skip_connection=use_skip)
+    trainer = DataParallelTrainer(model, **kw) if world > 1 else Trainer(model, **kw)
     path = os.path.join(logdir, ckpt) if ckpt else (sorted(glob.glob(os.path.join(logdir, '*.npz')), key=os.path.getmtime) or [None])[-1]
     if path and os.path.exists(path):
         say('resumed from %s at step %d' % (path, trainer.load(path)))

@@ -47,6 +47,14 @@ fresh processes, one per GPU, and measures DataParallelTrainer.step per rank at 
 gradient arena alone (the slowest rank's median).  There is no threshold.  Writes profiles/train_dp_bench.json.
 
     python tools/train_bench.py --opt [--gpus N] [--steps 20] [--warmup 3]
+
+--skip measures training of the skip-connection architecture (DESIGN.md section 9, "Training the skip-connection architecture";
+include/pwv_hip_train_skip.h) against the default one: the default model at 8 x 4000 with and without model.use_skip_connection, the
+same weights, mel, z and wav, the two loss_and_grad ALTERNATING call by call in one run, and the residual layer-backward launch alone
+(kernel + reduction, dilation 1, timed over runs of 20 calls) in both forms.  There is no threshold.  Writes
+profiles/train_skip_bench.json.
+
+    python tools/train_bench.py --skip [--steps 20] [--warmup 3]
 """
 import argparse
 import json
@@ -68,13 +76,14 @@ def main():
     ap.add_argument('--varlen', action='store_true', help='measure packed batches against uniform and padded ones instead')
     ap.add_argument('--tran', action='store_true', help='measure transposed-conv conditioning against repeat conditioning instead')
     ap.add_argument('--opt', action='store_true', help='measure the fused optimiser against the torch._foreach one instead')
+    ap.add_argument('--skip', action='store_true', help='measure the skip-connection architecture against the default one instead')
     ap.add_argument('--gpus', type=int, default=1, help='with --opt: also measure data-parallel steps at world sizes up to this')
     ap.add_argument('--dp-rank', action='store_true', help=argparse.SUPPRESS)          # one rank of a --gpus measurement
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
     if args.out is None:
         name = ('train_dp_bench.json' if args.opt else 'train_power_bench.json' if args.power else 'train_varlen_bench.json' if args.varlen else 'train_tran_bench.json' if args.tran
-                else 'train_bench.json')
+                else 'train_skip_bench.json' if args.skip else 'train_bench.json')
         args.out = os.path.join(ROOT, 'profiles', name)
     steps, warmup = max(args.steps, 20), max(args.warmup, 3)
 
@@ -140,6 +149,8 @@ def main():
         return varlen_legs(args, TR, O, cfg, store, model, wav, mel, z, steps, warmup)
     if args.tran:
         return tran_legs(args, TR, O, cfg, store, model, wav, mel, z, steps, warmup)
+    if args.skip:
+        return skip_legs(args, TR, O, cfg, store, model, wav, mel, z, steps, warmup)
 
     legs = {}
     legs['forward_f32'] = timed(forward)
@@ -327,6 +338,83 @@ def tran_legs(args, TR, O, cfg, store, model, wav, mel, z, steps, warmup):
     out['transposed_over_repeat'] = round(med['transposed_conv'] / med['repeat'], 4)
     out['paired_ratio'] = {'median': round(statistics.median(b / a for a, b in zip(ms['repeat'], ms['transposed_conv'])), 4)}
     out['cond_stages_share'] = round((med['cond_stages_forward'] + med['cond_stages_backward']) / med['transposed_conv'], 4)
+    with open(args.out, 'w') as f:
+        json.dump(out, f, indent=1)
+        f.write('\n')
+    print(json.dumps(out))
+
+
+def skip_legs(args, TR, O, cfg, store, model, wav, mel, z, steps, warmup):
+    import ctypes
+    import torch
+    from pwv_amd import _lib
+    from tests.util import set_hparams
+    dev = wav.device
+    n, length = args.batch, args.length
+    scfg = O.ModelConfig(use_skip_connection=True)          # the same variables: the two architectures differ in what they read
+
+    def once(fn):
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+
+    variants = {'default': (cfg, lambda: TR.loss_and_grad(model, wav, mel, z=z)),
+                'skip': (scfg, lambda: TR.loss_and_grad(model, wav, mel, z=z, use_skip_connection=True))}
+    ms = {k: [] for k in variants}
+    for k in range(warmup + steps):
+        for name, (c, fn) in variants.items():            # alternating: A B A B ...
+            set_hparams(c)                                  # (outside the timed window)
+            t = once(fn)
+            if k >= warmup:
+                ms[name].append(t)
+    set_hparams(cfg)
+    peak = round(torch.cuda.max_memory_allocated() / 2 ** 20, 1)
+
+    # the residual layer-backward launch alone (kernel + reduction), both forms, on buffers of the step's size: 20 calls per window
+    rows, frames, hop = n * length, mel.shape[1], cfg.hop_length
+    kmax = (hop + 30) // 32 + 1
+    t64 = lambda: torch.randn(((rows + 31) // 32) * 32 * 64, device=dev)
+    x, u, v, un, vn = t64(), t64(), t64(), t64(), t64()
+    dS = torch.randn(((rows + 31) // 32) * 32 * 128, device=dev)
+    P, dP = 0.5 * torch.randn(n * frames, 128, device=dev), torch.zeros(n * frames * kmax, 128, device=dev)
+    w = {k: 0.1 * torch.randn(*shape, device=dev) for k, shape in (('filter', (2, 64, 64)), ('gate', (2, 64, 64)), ('dense', (1, 64, 64)),
+                                                                   ('skip', (1, 64, 128)))}
+    d = {k: torch.empty_like(t) for k, t in w.items()}
+    d['dense_bias'] = torch.empty(64, device=dev)
+    base = dict(N=n, T=length, cond_hop=hop, cond_offset=hop // 2, cond_frames=frames, proj_row_stride=128, d_proj_row_stride=128, dilation=1,
+                next_dilation=1, form=_lib.TRAIN_RESIDUAL)
+    lib, stream, calls = _lib.lib(), torch.cuda.current_stream().cuda_stream, 20
+    ws = torch.empty(lib.pwv_train_skip_workspace_bytes(ctypes.byref(_lib.TrainSkipArgs(**base))) // 4, device=dev)
+    ptrs = dict(x=x, proj=P, filter=w['filter'], gate=w['gate'], dense=w['dense'], u_next=un, v_next=vn, u=u, v=v, d_proj=dP,
+                d_filter=d['filter'], d_gate=d['gate'], d_dense=d['dense'], d_dense_bias=d['dense_bias'], workspace=ws)
+    ptrs = {k: t.data_ptr() for k, t in ptrs.items()}
+    plain = _lib.TrainArgs(workspace_bytes=ws.numel() * 4, **base, **ptrs)
+    skip = _lib.TrainSkipArgs(workspace_bytes=ws.numel() * 4, skip=w['skip'].data_ptr(), d_skip_sum=dS.data_ptr(), d_skip=d['skip'].data_ptr(),
+                              **base, **ptrs)
+    launches = (('layer_bwd_default', 'pwv_train_layer_bwd_f32', plain), ('layer_bwd_skip', 'pwv_train_skip_layer_bwd_f32', skip))
+    ms.update({name: [] for name, _, _ in launches})
+    for k in range(warmup + steps):                         # alternating windows of 20 calls
+        for name, entry, a in launches:
+            def run(entry=entry, a=a):
+                for _ in range(calls):
+                    _lib.check(getattr(lib, entry)(ctypes.byref(a), stream), entry)
+            t = once(run) / calls
+            if k >= warmup:
+                ms[name].append(t)
+    out = {'model': 'default (4 flows, 10 + 10 + 10 + 30 layers, 2 nets each)', 'batch': n, 'length': length, 'steps': steps, 'warmup': warmup,
+           'device': torch.cuda.get_device_name(0), 'peak_allocated_MiB': peak}
+    for k, vals in ms.items():
+        key = 'loss_and_grad_%s_ms' % k if k in variants else k + '_ms'
+        out[key] = {'median': round(statistics.median(vals), 4), 'min': round(min(vals), 4), 'max': round(max(vals), 4)}
+    med = {k: statistics.median(vals) for k, vals in ms.items()}
+    out['skip_over_default'] = round(med['skip'] / med['default'], 4)
+    out['paired_ratio'] = {'median': round(statistics.median(b / a for a, b in zip(ms['default'], ms['skip'])), 4)}
+    out['layer_bwd_skip_over_default'] = round(med['layer_bwd_skip'] / med['layer_bwd_default'], 4)
+    out['layer_bwd_estimate_by_operation_count'] = 1.25
     with open(args.out, 'w') as f:
         json.dump(out, f, indent=1)
         f.write('\n')
