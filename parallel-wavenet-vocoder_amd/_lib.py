@@ -19,7 +19,8 @@ _REPO_ROOT = os.path.dirname(_PKG_DIR)
 LIB_PATH = os.environ.get('PWV_LIB') or os.path.join(_PKG_DIR, 'libpwv_hip.so')   # PWV_LIB: A/B another build
 CSRC = [os.path.join(_PKG_DIR, 'csrc', f) for f in ('pwv_layer.hip', 'pwv_layer_f16.hip', 'pwv_layer_h16.hip', 'pwv_misc.hip',
                                                     'pwv_stack_persist.hip', 'pwv_norm.hip', 'pwv_audio.hip', 'pwv_stream_tick.hip', 'pwv_score.hip', 'pwv_train.hip', 'pwv_train_loss.hip',
-                                                    'pwv_train_varlen.hip', 'pwv_train_cond.hip', 'pwv_train_opt.hip', 'pwv_train_skip.hip')]
+                                                    'pwv_train_varlen.hip', 'pwv_train_cond.hip', 'pwv_train_opt.hip', 'pwv_train_skip.hip',
+                                                    'pwv_train_shared.hip')]
 
 HEADER_VERSION = 301          # PWV_HIP_VERSION of include/pwv_hip.h these ctypes mirrors were written against
 FIRST_FOLD_FLOATS = 2048      # PWV_FIRST_FOLD_FLOATS
@@ -67,6 +68,9 @@ TRAIN_OPT_SYMBOLS = ('pwv_train_opt_pack_f32', 'pwv_train_opt_unpack_f32', 'pwv_
 # ... and of include/pwv_hip_train_skip.h: the layer and head kernels of training the skip-connection architecture
 TRAIN_SKIP_SYMBOLS = ('pwv_train_skip_workspace_bytes', 'pwv_train_skip_layer_fwd_f32', 'pwv_train_skip_head_fwd_f32',
                       'pwv_train_skip_head_bwd_f32', 'pwv_train_skip_layer_bwd_f32')
+# ... and of include/pwv_hip_train_shared.h: the two-output head of training the shared-net architecture, on o or on the skip sum
+TRAIN_SHARED_SYMBOLS = ('pwv_train_shared_workspace_bytes', 'pwv_train_shared_head_fwd_f32', 'pwv_train_shared_head_bwd_f32')
+TRAIN_HEAD_IN_GATED, TRAIN_HEAD_IN_SKIPSUM = 0, 1      # PWV_TRAIN_HEAD_IN_GATED, PWV_TRAIN_HEAD_IN_SKIPSUM
 TRAIN_OPT_REC = 3             # PWV_TRAIN_OPT_REC: int64 per record of an arena table = {tensor address, arena offset, count}
 TRAIN_OPT_CHUNK = 1024        # PWV_TRAIN_OPT_CHUNK: floats per record of a block map
 TRAIN_OPT_MAX_GRID = 2048     # PWV_TRAIN_OPT_MAX_GRID: workgroups of a launch at most
@@ -457,6 +461,25 @@ class TrainSkipArgs(Structure):
         return self
 
 
+class TrainSharedArgs(Structure):
+    """pwv_train_shared_args: one head call of training the shared-net architecture (include/pwv_hip_train_shared.h): the embedded
+    pwv_train_args as `train`, then the head's input mode, the skip sum, dS and the shift plane (train.y is the scale plane).  `set`
+    routes a name to the new fields first, then to `train`."""
+    _fields_ = ([('train', TrainArgs), ('head_in', ctypes.c_int32)]
+                + [(n, c_void_p) for n in ('skip_sum', 'd_skip_sum_out', 'y_shift')])
+    OWN = frozenset(('head_in', 'skip_sum', 'd_skip_sum_out', 'y_shift'))
+
+    def __init__(self, **kw):
+        super().__init__()
+        self.set(**kw)
+        self.train.struct_size = ctypes.sizeof(TrainSharedArgs)
+
+    def set(self, **kw):
+        for k, v in kw.items():
+            setattr(self if k in TrainSharedArgs.OWN else self.train, k, v)
+        return self
+
+
 class TrainLossVarlenArgs(Structure):
     """pwv_train_loss_varlen_args: the loss terms of a packed batch and their gradient for the prediction
     (include/pwv_hip_train_varlen.h)."""
@@ -692,6 +715,10 @@ def _declare(lib):
     lib.pwv_train_skip_workspace_bytes.argtypes = [POINTER(TrainSkipArgs)]
     for name in TRAIN_SKIP_SYMBOLS[1:]:
         getattr(lib, name).argtypes = [POINTER(TrainSkipArgs), c_void_p]
+    lib.pwv_train_shared_workspace_bytes.restype = c_size_t
+    lib.pwv_train_shared_workspace_bytes.argtypes = [POINTER(TrainSharedArgs)]
+    for name in TRAIN_SHARED_SYMBOLS[1:]:
+        getattr(lib, name).argtypes = [POINTER(TrainSharedArgs), c_void_p]
     lib.pwv_train_opt_pack_f32.argtypes = [POINTER(TrainOptPackArgs), c_void_p]
     lib.pwv_train_opt_unpack_f32.argtypes = [POINTER(TrainOptPackArgs), c_void_p]
     lib.pwv_train_opt_adam_ema_f32.argtypes = [POINTER(TrainOptAdamArgs), c_void_p]
@@ -716,7 +743,7 @@ def _declare(lib):
     lib.pwv_status_words_alloc.argtypes = [POINTER(c_void_p)]
     lib.pwv_status_words_free.argtypes = [c_void_p]
     lib.pwv_range_check_f32.argtypes = [f32p, c_int64, ctypes.c_float, c_void_p, c_void_p]
-    for name in EXPORTED_SYMBOLS + EXTENSION_SYMBOLS + LIVE_TICK_SYMBOLS + SCORE_SYMBOLS + TRAIN_SYMBOLS + TRAIN_LOSS_SYMBOLS + TRAIN_VARLEN_SYMBOLS + TRAIN_COND_SYMBOLS + TRAIN_OPT_SYMBOLS + TRAIN_SKIP_SYMBOLS:      # fails loudly (AttributeError) if a symbol is missing
+    for name in EXPORTED_SYMBOLS + EXTENSION_SYMBOLS + LIVE_TICK_SYMBOLS + SCORE_SYMBOLS + TRAIN_SYMBOLS + TRAIN_LOSS_SYMBOLS + TRAIN_VARLEN_SYMBOLS + TRAIN_COND_SYMBOLS + TRAIN_OPT_SYMBOLS + TRAIN_SKIP_SYMBOLS + TRAIN_SHARED_SYMBOLS:      # fails loudly (AttributeError) if a symbol is missing
         getattr(lib, name)
     return lib
 

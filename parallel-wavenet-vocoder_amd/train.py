@@ -13,8 +13,12 @@ condition_channels <= 96, no normalised conditioning.  And, on request (use_skip
 sets model.use_skip_connection, hparams train/small_skip), the skip-connection architecture (modules.py:142-147, :242-250): the head
 of every net reads the sum of all layers' skip outputs -- uniform and packed batches, one GPU or data-parallel, with or without the
 power loss (include/pwv_hip_train_skip.h; DESIGN.md section 9, "Training the skip-connection architecture"); not together with
-'transposed_conv'.  Everything else is refused with a PwvError that names the reason (`refusal`); nothing falls back to another
-implementation.
+'transposed_conv'.  And, on request too (shared_nets=True; the command line asks when the case sets model.shared_nets, hparams
+train/small_shared), the project's own shared-net architecture (modules.SharedIAFLayer, bench/c2): ONE net per flow whose head has two
+outputs, out = x y[..., 0] + y[..., 1] -- the two-output head of include/pwv_hip_train_shared.h on the unchanged layer kernels; uniform
+and packed batches, with skip connections (both requests), the power loss, fused or data-parallel, or 'transposed_conv' (DESIGN.md
+section 9, "Training the shared-net architecture").  Everything else is refused with a PwvError that names the reason (`refusal`);
+nothing falls back to another implementation.
 
 Data-parallel (the reference's SyncMultiGPUTrainerReplicated, train.py:66-69): DataParallelTrainer, one replica per rank; the gradients
 of a step are packed into ONE flat arena, all-reduced once, and one fused Adam + EMA launch applies the same update on every rank
@@ -56,19 +60,26 @@ TCONV_STRIDES = (4, 4, 5)   # models.py:109-124: the strides of the three transp
 
 
 # ---- what is refused ----------------------------------------------------------------------------------------------------------------
-def refusal(model=None, wav=None, melspec=None, power_weight=None, packed=False, use_skip_connection=None) -> Optional[str]:
+def refusal(model=None, wav=None, melspec=None, power_weight=None, packed=False, use_skip_connection=None, *,
+            shared_nets: Optional[bool] = None) -> Optional[str]:
     """Why the current hparams / this model / these inputs cannot be trained here, or None.  Looks at structure only: no GPU.
     `power_weight`: the weight of the STFT power loss the caller asks for explicitly (loss_and_grad's argument); None = the L1 alone,
     and then hparams that ask for a power loss are refused instead of being trained without it.  `packed`: the caller is
     loss_and_grad_varlen, which takes its lengths from the utterances and not from the model.  `use_skip_connection`: True = the
     caller asks for the skip-connection architecture (hparams that say False are then a mismatch); None = the default architecture,
-    and hparams with model.use_skip_connection are refused instead of being trained as something else."""
+    and hparams with model.use_skip_connection are refused instead of being trained as something else.  `shared_nets`: the same for
+    the shared-net architecture (model.shared_nets: one net with two outputs per flow); the two requests combine."""
     m = hp.model
     if use_skip_connection not in (None, True):
         return 'use_skip_connection %r: pass True to train the skip-connection architecture, None for the default one' % (use_skip_connection,)
     if use_skip_connection and not m.use_skip_connection:
         return ('use_skip_connection=True under hparams with model.use_skip_connection False: the request does not match the '
                 'architecture the hparams describe')
+    if shared_nets not in (None, True):
+        return 'shared_nets %r: pass True to train the shared-net architecture, None for separate scaler and shifter nets' % (shared_nets,)
+    if shared_nets and not m.get('shared_nets'):
+        return ('shared_nets=True under hparams with model.shared_nets False: the request does not match the architecture the hparams '
+                'describe')
     if m.cond_upsample_method == 'transposed_conv':
         what = "cond_upsample_method 'transposed_conv': transposed-conv conditioning is differentiated "
         hop, C = int(hp.signal.hop_length), int(m.condition_channels)
@@ -95,8 +106,9 @@ def refusal(model=None, wav=None, melspec=None, power_weight=None, packed=False,
         return ("use_skip_connection True with cond_upsample_method 'transposed_conv': skip accumulation is not differentiated together "
                 'with per-sample conditioning (the per-sample layer kernels\' 62 KB of LDS and the dS tile leave no room for two workgroups '
                 'per compute unit)')
-    if m.get('shared_nets'):
-        return 'shared_nets True: one shared net per flow is not differentiated (separate scaler and shifter nets only)'
+    if m.get('shared_nets') and not shared_nets:
+        return ('shared_nets True: one shared net per flow is not differentiated by a bare call; it is trained on request '
+                '(loss_and_grad / loss_and_grad_varlen / Trainer: shared_nets=True)')
     shape = (m.filter_width, m.residual_channels, m.dilation_channels, m.skip_channels)
     if shape != (2, 64, 64, 128):
         return 'filter_width, residual, dilation, skip channels = %s: outside the fused shape (2, 64, 64, 128)' % (shape,)
@@ -205,6 +217,21 @@ class _Geometry(object):
                                          dilation=1, next_dilation=1), kw)
 
     head_args = args                        # the head is row-independent: the same call for either geometry
+
+    shared = False                          # True: one net per flow with two outputs; its heads are the calls of shared_head_args
+
+    def shared_head_args(self, head_in, **kw):
+        """The two-output head's struct (include/pwv_hip_train_shared.h): the uniform struct in front -- row-local, so a packed batch is
+        N = 1, T = rows --, then the input mode and the new fields."""
+        base = _Geometry.args(self)
+        a = _lib.TrainSharedArgs()
+        ctypes.memmove(ctypes.addressof(a.train), ctypes.addressof(base), ctypes.sizeof(_lib.TrainArgs))
+        a.train.struct_size = ctypes.sizeof(_lib.TrainSharedArgs)
+        return a.set(head_in=head_in, **{k: _ptr(v) if isinstance(v, torch.Tensor) else v for k, v in kw.items()})
+
+    def shared_workspace_bytes(self):
+        return (_lib.lib().pwv_train_shared_workspace_bytes(ctypes.byref(self.shared_head_args(_lib.TRAIN_HEAD_IN_GATED))),
+                'pwv_train_shared_workspace_bytes')
 
     def layer_args(self, **kw):
         """The layers' struct: the front's, but for a per-sample condition."""
@@ -336,6 +363,12 @@ def _net_forward_skip(net: _Net, geo: _Geometry, xin):
                                                        skip=v['skip'], skip_bias=v.get('skip_bias'), skip_sum=S, skip_accumulate=int(j > 0),
                                                        **geo.cond_fwd(net, j, v)))
     h = net.head
+    if geo.shared:                          # two outputs: y = [scale plane, shift plane]
+        y = torch.empty((2, geo.rows), dtype=torch.float32, device=dev)
+        _call('pwv_train_shared_head_fwd_f32', geo.shared_head_args(
+            _lib.TRAIN_HEAD_IN_SKIPSUM, skip_sum=S, post1=h['postprocess1'], post1_bias=h.get('postprocess1_bias'), post2=h['postprocess2'],
+            post2_bias=h.get('postprocess2_bias'), y=y[0], y_shift=y[1]))
+        return xs, S, y
     _call('pwv_train_skip_head_fwd_f32', geo.head_args(skip_sum=S, post1=h['postprocess1'], post1_bias=h.get('postprocess1_bias'),
                                                        post2=h['postprocess2'], post2_bias=h.get('postprocess2_bias'), y=y))
     return xs, S, y
@@ -353,7 +386,9 @@ def _net_backward_skip(net: _Net, geo: _Geometry, saved, xin, d_out, d_mul, scal
     dS = _tile32w(geo.rows, dev)
     biased = [j for j in range(L) if 'skip_bias' in net.layers[j]]
     sums = torch.empty(128, dtype=torch.float32, device=dev) if biased else None
-    _call('pwv_train_skip_head_bwd_f32', geo.head_args(
+    head_bwd, head_args = (('pwv_train_shared_head_bwd_f32', lambda **kw: geo.shared_head_args(_lib.TRAIN_HEAD_IN_SKIPSUM, **kw)) if geo.shared
+                           else ('pwv_train_skip_head_bwd_f32', geo.head_args))
+    _call(head_bwd, head_args(
         skip_sum=S, d_out=d_out, d_mul=d_mul, post1=h['postprocess1'], post1_bias=h.get('postprocess1_bias'), post2=h['postprocess2'],
         post2_bias=h.get('postprocess2_bias'), d_skip_sum_out=dS, d_skip_bias=sums,
         d_post1=g(hp_ + 'postprocess1', h['postprocess1']), d_post1_bias=opt(h, 'postprocess1_bias', hp_ + 'postprocess1_bias'),
@@ -395,6 +430,12 @@ def _net_forward(net: _Net, geo: _Geometry, xin):
                                                        filter=v['filter'], gate=v['gate'], dense=v['dense'], dense_bias=v.get('dense_bias'),
                                                        x_out=o if last else xs[j + 1], **geo.cond_fwd(net, j, v)))
     h, lv = net.head, net.layers[-1]
+    if geo.shared:                          # two outputs: y = [scale plane, shift plane]
+        y = torch.empty((2, geo.rows), dtype=torch.float32, device=dev)
+        _call('pwv_train_shared_head_fwd_f32', geo.shared_head_args(
+            _lib.TRAIN_HEAD_IN_GATED, x=o, skip=lv['skip'], skip_bias=lv.get('skip_bias'), post1=h['postprocess1'],
+            post1_bias=h.get('postprocess1_bias'), post2=h['postprocess2'], post2_bias=h.get('postprocess2_bias'), y=y[0], y_shift=y[1]))
+        return xs, o, y
     _call('pwv_train_head_fwd_f32', geo.head_args(x=o, skip=lv['skip'], skip_bias=lv.get('skip_bias'), post1=h['postprocess1'],
                                             post1_bias=h.get('postprocess1_bias'), post2=h['postprocess2'],
                                             post2_bias=h.get('postprocess2_bias'), y=y))
@@ -410,7 +451,9 @@ def _net_backward(net: _Net, geo: _Geometry, saved, xin, d_out, d_mul, scale, d_
     hp_ = net.scope + '/postprocessing/'
     opt = lambda d, key, name: g(name, d[key]) if key in d else None
     d_o = _tile32(geo.rows, dev)
-    _call('pwv_train_head_bwd_f32', geo.head_args(
+    head_bwd, head_args = (('pwv_train_shared_head_bwd_f32', lambda **kw: geo.shared_head_args(_lib.TRAIN_HEAD_IN_GATED, **kw)) if geo.shared
+                           else ('pwv_train_head_bwd_f32', geo.head_args))
+    _call(head_bwd, head_args(
         x=o, d_out=d_out, d_mul=d_mul, skip=lv['skip'], skip_bias=lv.get('skip_bias'), post1=h['postprocess1'],
         post1_bias=h.get('postprocess1_bias'), post2=h['postprocess2'], post2_bias=h.get('postprocess2_bias'), d_o_out=d_o,
         d_skip=g(net.name(L - 1, 'skip'), lv['skip']), d_skip_bias=opt(lv, 'skip_bias', net.name(L - 1, 'skip_bias')),
@@ -478,7 +521,7 @@ def _head(shape, rows, power_weight, terms):
 
 
 def loss_and_grad(model, wav, melspec, z=None, seed=None, max_workgroups: int = 0, power_weight: Optional[float] = None,
-                  terms: Optional[dict] = None, use_skip_connection: Optional[bool] = None):
+                  terms: Optional[dict] = None, use_skip_connection: Optional[bool] = None, *, shared_nets: Optional[bool] = None):
     """(loss, pred, grads) of one batch: `loss` the L1 mean |pred - wav| as a device scalar (models.py:93 `loss/likelihood`), `pred`
     [N, T, 1] the model's output, `grads` {name: device tensor of the variable's shape} for EVERY trainable variable of the store under
     'iaf_vocoder' -- exact zeros for the ones the model never reads (skip / skip_bias of every layer but the last, dense / dense_bias of
@@ -494,9 +537,14 @@ def loss_and_grad(model, wav, melspec, z=None, seed=None, max_workgroups: int = 
     `use_skip_connection` = True asks for the skip-connection architecture (hparams with model.use_skip_connection; the kernels of
     include/pwv_hip_train_skip.h): the head of every net reads the sum of all layers' skip outputs, every layer's skip / skip_bias has a
     gradient and the exact zeros are the last layer's dense / dense_bias.  None: the default architecture, launch for launch what it
-    was, and hparams with model.use_skip_connection are refused."""
+    was, and hparams with model.use_skip_connection are refused.
+
+    `shared_nets` = True asks for the shared-net architecture (hparams with model.shared_nets; the two-output head of
+    include/pwv_hip_train_shared.h): each flow has ONE net whose head leaves the scale and the shift plane, one backward per flow, and
+    the variables are 'iaf_vocoder/iafK/shared/...'.  It combines with use_skip_connection=True, the power loss, packed batches and
+    transposed-conv conditioning.  None: two nets per flow, and hparams with model.shared_nets are refused."""
     from . import engine
-    why = refusal(model, wav, melspec, power_weight=power_weight, use_skip_connection=use_skip_connection)
+    why = refusal(model, wav, melspec, power_weight=power_weight, use_skip_connection=use_skip_connection, shared_nets=shared_nets)
     if why:
         raise PwvError('training refused: ' + why)
     store = model.store or get_default_store()
@@ -521,6 +569,7 @@ def loss_and_grad(model, wav, melspec, z=None, seed=None, max_workgroups: int = 
         geo = _CondGeometry(N, T, int(hp.model.condition_channels), int(max_workgroups))
     else:
         geo = (_SkipGeometry if use_skip_connection else _Geometry)(N, T, t_mel, cols, int(max_workgroups))
+    geo.shared = bool(shared_nets)
 
     loss, x, grads = _forward_backward(store, flows, geo, melspec.reshape(N * t_mel, n_mels), noise.reshape(N * T).contiguous(),
                                        wav.reshape(N * T), _head((N, T), N * T, power_weight, terms))
@@ -586,13 +635,22 @@ def _forward_backward(store, flows, geo, mel2, x, y, head):
     ws_bytes, ws_name = geo.workspace_bytes()
     if not ws_bytes:
         _lib.check(-1, ws_name)
+    if geo.shared:                          # the two-output head's partial is the larger one
+        assert all(len(pair) == 1 for pair in flows)
+        more, more_name = geo.shared_workspace_bytes()
+        if not more:
+            _lib.check(-1, more_name)
+        ws_bytes = max(ws_bytes, more)
     ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=dev)
     saved = []
     net_forward, net_backward = (_net_forward_skip, _net_backward_skip) if getattr(geo, 'skip', False) else (_net_forward, _net_backward)
     for pair in flows:
         s = [net_forward(net, geo, x) for net in pair]
         saved.append((x, s))
-        x = x * s[0][2] + s[1][2]                                                       # modules.py:59
+        if geo.shared:
+            x = x * s[0][2][0] + s[0][2][1]                                             # SharedIAFLayer: out = x y[..., 0] + y[..., 1]
+        else:
+            x = x * s[0][2] + s[1][2]                                                   # modules.py:59
     loss, d_out = head(x, y)
 
     # sample rate, backward
@@ -603,6 +661,10 @@ def _forward_backward(store, flows, geo, mel2, x, y, head):
     for i in range(len(flows) - 1, -1, -1):
         xin, s = saved[i]
         d_in = torch.empty_like(xin) if i > 0 else None
+        if geo.shared:                      # one net: the head forms ds = d out * in and db = d out itself
+            net_backward(flows[i][0], geo, s[0], xin, d_out, xin, s[0][2][0], d_in, False, dP, ws, grads)
+            d_out = d_in
+            continue
         net_backward(flows[i][0], geo, s[0], xin, d_out, xin, s[0][2], d_in, False, dP, ws, grads)       # ds = d out * in
         net_backward(flows[i][1], geo, s[1], xin, d_out, None, None, d_in, True, dP, ws, grads)          # db = d out
         d_out = d_in
@@ -645,7 +707,8 @@ def _fill_unread(store, grads, loss, x):
 
 # ---- packed batches: utterances of different lengths, unpadded ("Packed training") ------------------------------
 def loss_and_grad_varlen(model, wavs, mels, z=None, seeds=None, max_workgroups: int = 0, power_weight: Optional[float] = None,
-                         terms: Optional[dict] = None, use_skip_connection: Optional[bool] = None):
+                         terms: Optional[dict] = None, use_skip_connection: Optional[bool] = None, *,
+                         shared_nets: Optional[bool] = None):
     """loss_and_grad over utterances of DIFFERENT lengths in one packed batch, without padding: (loss, preds, grads).  wavs[i] is [T_i] or
     [T_i, 1] and mels[i] [1 + T_i / hop, n_mels], both on the GPU, T_i >= hop a multiple of hop.  `loss` = sum |pred - wav| / sum T_i
     (with `power_weight` = w: + w * power, the STFT power loss over the frames of all utterances that are at least win_length long --
@@ -653,10 +716,10 @@ def loss_and_grad_varlen(model, wavs, mels, z=None, seeds=None, max_workgroups: 
     loss_and_grad, exact zeros for unread variables included.  `seeds` (one integer per utterance) gives every utterance a noise stream
     of its own, as IAFVocoder.generate_varlen does; `z`, a list of [T_i, 1] (or [T_i]), replaces the noise; with neither, one draw of
     sum T_i counters continues the model's stream.  The constructor's batch_size and length are not used.  Only enqueues: the kernels
-    read the lengths from device tables (include/pwv_hip_train_varlen.h).  `use_skip_connection`: as for loss_and_grad."""
+    read the lengths from device tables (include/pwv_hip_train_varlen.h).  `use_skip_connection`, `shared_nets`: as for loss_and_grad."""
     from . import engine
     from .models import noise_streams
-    why = refusal(model, power_weight=power_weight, packed=True, use_skip_connection=use_skip_connection)
+    why = refusal(model, power_weight=power_weight, packed=True, use_skip_connection=use_skip_connection, shared_nets=shared_nets)
     if why:
         raise PwvError('training refused: ' + why)
     if not isinstance(wavs, (list, tuple)) or not isinstance(mels, (list, tuple)) or not wavs:
@@ -702,6 +765,7 @@ def loss_and_grad_varlen(model, wavs, mels, z=None, seeds=None, max_workgroups: 
     flows = model_nets(model, store)
     cols = sum(128 * len(net.dilations) for pair in flows for net in pair)
     geo = (_SkipPackedGeometry if use_skip_connection else _PackedGeometry)(layout, cols, int(max_workgroups))
+    geo.shared = bool(shared_nets)
 
     loss, x, grads = _forward_backward(store, flows, geo, torch.cat(mels), noise.reshape(layout.rows).contiguous(),
                                        torch.cat([w.reshape(-1) for w in wavs]), _head(layout, layout.rows, power_weight, terms))
@@ -934,7 +998,8 @@ class Trainer(object):
     """The reference's training step (models.py:80-103) on one model: loss_and_grad, then adam_ema_update on the store's variables in
     place.  Defaults from hparams: lr = train.lr, beta2 = train.adam_beta2, ema_decay = train.ema_decay if train.use_ema.
     `power_weight` goes to every loss_and_grad; `terms` then holds the last step's 'likelihood', 'power' and 'total' (device scalars).
-    `use_skip_connection` goes to every loss_and_grad too: True trains the skip-connection architecture.
+    `use_skip_connection` goes to every loss_and_grad too: True trains the skip-connection architecture.  So does `shared_nets`: True
+    trains the shared-net architecture (one net per flow; the variables and the .npz names are 'iaf_vocoder/iafK/shared/...').
 
     `fused` (default False: adam_ema_update's torch._foreach passes, launch for launch what they were): the gradients of a step are
     packed into one flat arena by one launch and ONE pwv_train_opt_adam_ema_f32 launch updates the model
@@ -942,9 +1007,10 @@ class Trainer(object):
     shadows() work as before -- an .npz of either path loads into the other."""
 
     def __init__(self, model, lr=None, beta2=None, ema_decay=_UNSET, max_workgroups: int = 0, power_weight: Optional[float] = None,
-                 fused: bool = False, *, use_skip_connection: Optional[bool] = None):
+                 fused: bool = False, *, use_skip_connection: Optional[bool] = None, shared_nets: Optional[bool] = None):
         self.model = model
         self.use_skip_connection = use_skip_connection      # None: the default architecture; True: skip connections (loss_and_grad)
+        self.shared_nets = shared_nets                      # None: two nets per flow; True: one shared net per flow (loss_and_grad)
         self.fused = bool(fused)
         self.arenas: Optional[_Arenas] = None
         self._vars_version = None
@@ -962,7 +1028,8 @@ class Trainer(object):
 
     def _bind(self, packed=False):
         """Every variable of the model exists from here on; the optimiser's lists follow the sorted names."""
-        why = refusal(self.model, power_weight=self.power_weight, packed=packed, use_skip_connection=self.use_skip_connection)
+        why = refusal(self.model, power_weight=self.power_weight, packed=packed, use_skip_connection=self.use_skip_connection,
+                      shared_nets=self.shared_nets)
         if why:
             raise PwvError('training refused: ' + why)
         if self.names is None:
@@ -976,7 +1043,7 @@ class Trainer(object):
         vars = self._bind()
         terms: Dict[str, torch.Tensor] = {}
         loss, _, grads = loss_and_grad(self.model, wav, mel, z=z, max_workgroups=self.max_workgroups, power_weight=self.power_weight,
-                                       terms=terms, use_skip_connection=self.use_skip_connection)
+                                       terms=terms, use_skip_connection=self.use_skip_connection, shared_nets=self.shared_nets)
         return self._update(vars, loss, grads, terms)
 
     def step_varlen(self, wavs, mels, z=None, seeds=None):
@@ -985,7 +1052,8 @@ class Trainer(object):
         vars = self._bind(packed=True)
         terms: Dict[str, torch.Tensor] = {}
         loss, _, grads = loss_and_grad_varlen(self.model, wavs, mels, z=z, seeds=seeds, max_workgroups=self.max_workgroups,
-                                              power_weight=self.power_weight, terms=terms, use_skip_connection=self.use_skip_connection)
+                                              power_weight=self.power_weight, terms=terms, use_skip_connection=self.use_skip_connection,
+                                              shared_nets=self.shared_nets)
         return self._update(vars, loss, grads, terms)
 
     def _update(self, vars, loss, grads, terms):
@@ -1301,7 +1369,8 @@ def train(case='default', ckpt=None, steps=None, seed=0, varlen=False, gpus=None
     power_weight = float(hp.train.get('weight_power_loss', 0) or 0)
     power_weight = power_weight if power_weight > 0 else None
     use_skip = True if hp.model.use_skip_connection else None       # the case's architecture is what the loop asks for
-    why = refusal(power_weight=power_weight, use_skip_connection=use_skip)
+    shared = True if hp.model.get('shared_nets') else None
+    why = refusal(power_weight=power_weight, use_skip_connection=use_skip, shared_nets=shared)
     if why:
         raise PwvError('training refused: ' + why)
     launched = 'WORLD_SIZE' in os.environ
@@ -1329,13 +1398,13 @@ def train(case='default', ckpt=None, steps=None, seed=0, varlen=False, gpus=None
         else:
             dist.init_process_group(backend='nccl', device_id=device)       # 'nccl' is RCCL on ROCm
     try:
-        return _train_rank(power_weight, device, seed, steps, ckpt, varlen, world, rank, use_skip)
+        return _train_rank(power_weight, device, seed, steps, ckpt, varlen, world, rank, use_skip, shared)
     finally:
         if world > 1:
             dist.destroy_process_group()
 
 
-def _train_rank(power_weight, device, seed, steps, ckpt, varlen, world, rank, use_skip=None):
+def _train_rank(power_weight, device, seed, steps, ckpt, varlen, world, rank, use_skip=None, shared=None):
     """The loop of train() in one process: the only rank, or one of `world`."""
     from .audio_frontend import wav_to_mel_device
     from .models import IAFVocoder
@@ -1348,7 +1417,7 @@ def _train_rank(power_weight, device, seed, steps, ckpt, varlen, world, rank, us
     store = reset_default_store(device=device)
     model = IAFVocoder(batch_size=batch, length=length, store=store, precision='f32')
     model.noise_seed = seed
-    kw = dict(power_weight=power_weight, use_skip_connection=use_skip)
+    kw = dict(power_weight=power_weight, use_skip_connection=use_skip, shared_nets=shared)
     trainer = DataParallelTrainer(model, **kw) if world > 1 else Trainer(model, **kw)
     path = os.path.join(logdir, ckpt) if ckpt else (sorted(glob.glob(os.path.join(logdir, '*.npz')), key=os.path.getmtime) or [None])[-1]
     if path and os.path.exists(path):

@@ -55,6 +55,14 @@ same weights, mel, z and wav, the two loss_and_grad ALTERNATING call by call in 
 profiles/train_skip_bench.json.
 
     python tools/train_bench.py --skip [--steps 20] [--warmup 3]
+
+--shared measures training of the shared-net architecture (DESIGN.md section 9, "Training the shared-net architecture";
+include/pwv_hip_train_shared.h) against the default one: the default model (8 nets) and bench/c2's model (model.shared_nets: 4 nets,
+weights of its own) at 8 x 4000 on the same mel, z and wav, the two loss_and_grad ALTERNATING call by call in one run, and the head
+backward launch alone (kernel + reduction, timed over runs of 20 calls): the existing one-output head against the two-output one on
+the same o.  There is no threshold.  Writes profiles/train_shared_bench.json.
+
+    python tools/train_bench.py --shared [--steps 20] [--warmup 3]
 """
 import argparse
 import json
@@ -77,13 +85,14 @@ def main():
     ap.add_argument('--tran', action='store_true', help='measure transposed-conv conditioning against repeat conditioning instead')
     ap.add_argument('--opt', action='store_true', help='measure the fused optimiser against the torch._foreach one instead')
     ap.add_argument('--skip', action='store_true', help='measure the skip-connection architecture against the default one instead')
+    ap.add_argument('--shared', action='store_true', help='measure the shared-net architecture against the default one instead')
     ap.add_argument('--gpus', type=int, default=1, help='with --opt: also measure data-parallel steps at world sizes up to this')
     ap.add_argument('--dp-rank', action='store_true', help=argparse.SUPPRESS)          # one rank of a --gpus measurement
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
     if args.out is None:
         name = ('train_dp_bench.json' if args.opt else 'train_power_bench.json' if args.power else 'train_varlen_bench.json' if args.varlen else 'train_tran_bench.json' if args.tran
-                else 'train_skip_bench.json' if args.skip else 'train_bench.json')
+                else 'train_skip_bench.json' if args.skip else 'train_shared_bench.json' if args.shared else 'train_bench.json')
         args.out = os.path.join(ROOT, 'profiles', name)
     steps, warmup = max(args.steps, 20), max(args.warmup, 3)
 
@@ -151,6 +160,8 @@ def main():
         return tran_legs(args, TR, O, cfg, store, model, wav, mel, z, steps, warmup)
     if args.skip:
         return skip_legs(args, TR, O, cfg, store, model, wav, mel, z, steps, warmup)
+    if args.shared:
+        return shared_legs(args, TR, O, cfg, store, model, wav, mel, z, steps, warmup)
 
     legs = {}
     legs['forward_f32'] = timed(forward)
@@ -415,6 +426,81 @@ def skip_legs(args, TR, O, cfg, store, model, wav, mel, z, steps, warmup):
     out['paired_ratio'] = {'median': round(statistics.median(b / a for a, b in zip(ms['default'], ms['skip'])), 4)}
     out['layer_bwd_skip_over_default'] = round(med['layer_bwd_skip'] / med['layer_bwd_default'], 4)
     out['layer_bwd_estimate_by_operation_count'] = 1.25
+    with open(args.out, 'w') as f:
+        json.dump(out, f, indent=1)
+        f.write('\n')
+    print(json.dumps(out))
+
+
+def shared_legs(args, TR, O, cfg, store, model, wav, mel, z, steps, warmup):
+    import ctypes
+    import torch
+    from pwv_amd import _lib
+    from pwv_amd.models import IAFVocoder
+    from pwv_amd.variables import VariableStore
+    from tests.util import set_hparams
+    dev = wav.device
+    n, length = args.batch, args.length
+    scfg = O.ModelConfig(shared_nets=True)                  # bench/c2: one net per flow, variables of its own
+    set_hparams(scfg)
+    sstore = VariableStore(device=dev)
+    sstore.load_dict(O.init_weights(scfg, seed=2))
+    smodel = IAFVocoder(batch_size=n, length=length, store=sstore, precision='f32')
+
+    def once(fn):
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+
+    variants = {'default': (cfg, lambda: TR.loss_and_grad(model, wav, mel, z=z)),
+                'shared': (scfg, lambda: TR.loss_and_grad(smodel, wav, mel, z=z, shared_nets=True))}
+    ms = {k: [] for k in variants}
+    for k in range(warmup + steps):
+        for name, (c, fn) in variants.items():            # alternating: A B A B ...
+            set_hparams(c)                                  # (outside the timed window)
+            t = once(fn)
+            if k >= warmup:
+                ms[name].append(t)
+    set_hparams(cfg)
+    peak = round(torch.cuda.max_memory_allocated() / 2 ** 20, 1)
+
+    # the head backward launch alone (kernel + reduction), one output against two, on buffers of the step's size: 20 calls per window
+    rows = n * length
+    o, d_o = (torch.randn(((rows + 31) // 32) * 32 * 64, device=dev) for _ in range(2))
+    d_out, d_mul = torch.randn(rows, device=dev), torch.randn(rows, device=dev)
+    shapes = (('skip', (1, 64, 128)), ('skip_bias', (128,)), ('post1', (1, 128, 128)), ('post1_bias', (128,)))
+    w = {k: 0.1 * torch.randn(*shape, device=dev) for k, shape in shapes + (('post2', (1, 128, 2)), ('post2_bias', (2,)))}
+    d = {k: torch.empty_like(t) for k, t in w.items()}
+    lib, stream, calls = _lib.lib(), torch.cuda.current_stream().cuda_stream, 20
+    ws = torch.empty(lib.pwv_train_shared_workspace_bytes(ctypes.byref(_lib.TrainSharedArgs(N=n, T=length))) // 4, device=dev)
+    ptrs = dict(x=o, d_out=d_out, d_mul=d_mul, d_o_out=d_o, workspace=ws, **w, **{'d_' + k: t for k, t in d.items()})
+    ptrs = {k: t.data_ptr() for k, t in ptrs.items()}
+    one = _lib.TrainArgs(N=n, T=length, workspace_bytes=ws.numel() * 4, **ptrs)      # (reads column 0 of post2 alone: 128 of its floats)
+    two = _lib.TrainSharedArgs(N=n, T=length, workspace_bytes=ws.numel() * 4, head_in=_lib.TRAIN_HEAD_IN_GATED, **ptrs)
+    launches = (('head_bwd_default', 'pwv_train_head_bwd_f32', one), ('head_bwd_shared', 'pwv_train_shared_head_bwd_f32', two))
+    ms.update({name: [] for name, _, _ in launches})
+    for k in range(warmup + steps):                         # alternating windows of 20 calls
+        for name, entry, a in launches:
+            def run(entry=entry, a=a):
+                for _ in range(calls):
+                    _lib.check(getattr(lib, entry)(ctypes.byref(a), stream), entry)
+            t = once(run) / calls
+            if k >= warmup:
+                ms[name].append(t)
+    out = {'model': 'default (4 flows, 10 + 10 + 10 + 30 layers, 2 nets each) against shared_nets (1 net each)', 'batch': n, 'length': length,
+           'steps': steps, 'warmup': warmup, 'device': torch.cuda.get_device_name(0), 'peak_allocated_MiB': peak}
+    for k, vals in ms.items():
+        key = 'loss_and_grad_%s_ms' % k if k in variants else k + '_ms'
+        out[key] = {'median': round(statistics.median(vals), 4), 'min': round(min(vals), 4), 'max': round(max(vals), 4)}
+    med = {k: statistics.median(vals) for k, vals in ms.items()}
+    out['shared_over_default'] = round(med['shared'] / med['default'], 4)
+    out['paired_ratio'] = {'median': round(statistics.median(b / a for a, b in zip(ms['default'], ms['shared'])), 4)}
+    out['head_bwd_shared_over_default'] = round(med['head_bwd_shared'] / med['head_bwd_default'], 4)
+    out['estimate_by_operation_count'] = 0.5
     with open(args.out, 'w') as f:
         json.dump(out, f, indent=1)
         f.write('\n')
