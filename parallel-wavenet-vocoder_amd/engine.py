@@ -1519,12 +1519,13 @@ _STREAM_STRUCTURE_WHY = {'samples': 'per-sample (transposed-conv) conditioning',
 
 def stream_refusal(nets, cond, precision: Optional[str] = None) -> Optional[str]:
     """Why a flow (its nets) has no streaming form -- or None.  The per-layer kernels stream in three forms only: layer 0 folded onto
-    its scalar input, a plain residual layer, the last layer with the head fused behind it."""
+    its scalar input, a plain residual layer, the last layer with the head fused behind it.  Two flow shapes stream (_flow_structure):
+    two nets of one output each, and one shared net of two outputs (its launches carry G = 1 and a head / tail of Q = 2)."""
     net0 = nets[0]
     if _instance_norm(nets):
         return "instance normalisation ('in'): its statistics span the whole time axis"
     key = _flow_structure(nets, cond, precision)
-    if key is None and not (len(nets) == 2 and not net0.normalize and len(net0.dilations) >= 2):       # (no shared net, no normaliser)
+    if key is None and (net0.normalize or len(net0.dilations) < 2):       # (_flow_structure has settled the nets: two of one output or one of two)
         key = 'shape'
     if key is not None:
         return _STREAM_STRUCTURE_WHY[key]
@@ -1641,7 +1642,8 @@ def run_flow_stream(nets: Sequence, x: torch.Tensor, cond, precision: Optional[s
       * the persistent STREAMING launches (pwv_persist_args.hist; the affine inside the last one: one launch per run of
         _persist_runs, one for a stack of up to PERSIST_MAX_LAYERS + 1 layers) where _choose_path gives an [N, T] forward persistent
         runs with the tail and the fused, folded layer 0 -- PERSIST not False, not suspended, rows <= PERSIST_AUTO_MAX_ROWS, L >= 4;
-      * else L streaming layer launches of both nets (G = 2), then the affine (PWV_PERSIST=0 keeps this route in use and tested).
+      * else L streaming layer launches of all the flow's nets (G = 2, or G = 1 with a head of two outputs for a shared net), then the
+        affine (PWV_PERSIST=0 keeps this route in use and tested).
     Same bits, same written history rows either way.  Only enqueues, like run_flow; the written blocks become the sessions' state
     when the caller flips their generation -- so a push whose persistent launch gave up is rerun by verified_call on the per-layer
     launches (persist_suspended()) from the same generation.
@@ -1667,7 +1669,7 @@ def run_flow_stream(nets: Sequence, x: torch.Tensor, cond, precision: Optional[s
     if EVENT_LOG is not None:
         EVENT_LOG.append(('layer_stream', None, None, G, L))      # L calls of pwv_wavenet_layer_stream_f32 + the affine
     projs = _projections(cond, prep.mode, plans, prep.precision, None)
-    outs = [torch.empty((n, t, 1), dtype=torch.float32, device=x.device) for _ in plans]
+    outs = [torch.empty((n, t, net0.out_channels), dtype=torch.float32, device=x.device) for _ in plans]
     bufs = [[torch.empty((lib.pwv_tile32_floats(n * t, 64),), dtype=torch.float32, device=x.device) for _ in range(2)] for _ in plans]
     for j in range(L):
         la = _layer_args(net0, plans, projs, projs[0].stride(0), prep.cond_geom, bufs, j, (j + 1) & 1, j & 1, x)
@@ -1681,6 +1683,6 @@ def run_flow_stream(nets: Sequence, x: torch.Tensor, cond, precision: Optional[s
         if j == L - 1:
             for g in range(G):
                 la.head_packed[g], la.head_out[g] = plans[g].packed_head.data_ptr(), outs[g].data_ptr()
-            la.head_q = 1
+            la.head_q = net0.out_channels
         check(lib.pwv_wavenet_layer_stream_f32(ctypes.byref(la), ctypes.byref(hist), s), 'pwv_wavenet_layer_stream_f32')
     return _flow_affine(x, outs)

@@ -29,7 +29,8 @@ def round32(d: int) -> int:
 class HistoryLayout:
     """Where every history of the model lies inside a block (float offsets): per flow the d0 + 1 scalars of layer 0's input
     (padded to 64 floats), then per net and layer j >= 1 a tile32 buffer of round32(d_j) rows x 64 channels.  `carry` lists every
-    history as (offset, rows, floats per row): the table of pwv_stream_carry_f32."""
+    history as (offset, rows, floats per row): the table of pwv_stream_carry_f32.  `nets_per_flow`: 2 for the default architecture,
+    1 for the shared-net one (one two-output net per flow: one row history per layer)."""
 
     def __init__(self, dilations: Sequence[Sequence[int]], nets_per_flow: int = 2):
         self.scalar_off: List[int] = []
@@ -263,9 +264,16 @@ class StreamingVocoder(object):
     New weights in the store (store.version) re-plan the kernels' packed weights at the next push; open sessions KEEP their
     history -- it is activations, not weights (what they then produce is the new weights' continuation of the old context).
 
+    Two architectures stream, on the same routes and with the same contract: the default one (two scalar-input nets per flow) and the
+    shared-net one (model.shared_nets: True -- ONE net of two outputs per flow, out = x y[..., 0] + y[..., 1]; every launch then
+    carries one net, G = 1, the tail or the fused head two outputs, and the affine reads them interleaved).  A shared-net session keeps
+    one row history per layer and flow instead of two (HistoryLayout(dilations, nets_per_flow=1)): at the default dilations (bench/c2)
+    2 x 1,737,728 B + 320 B = 3,475,776 B (3.48 MB) per session against 6,949,184 B (6.95 MB) for the default model; state_bytes,
+    state and load_state follow the layout, and a state of the other architecture is turned away by its block_floats.
+
     Refused with a PwvError that names the reason (nothing is launched): per-sample (transposed-conv) conditioning, skip
-    accumulation, precision 'f16', any normaliser -- instance normalisation's statistics span the whole time axis --, shared nets,
-    nets outside the fused shape."""
+    accumulation (a shared-net model with skip connections is refused as a skip model), precision 'f16', any normaliser -- instance
+    normalisation's statistics span the whole time axis --, nets outside the fused shape."""
 
     def __init__(self, model, slots: int, hist_alloc=None):
         m = hp.model
@@ -280,8 +288,6 @@ class StreamingVocoder(object):
             why = "precision 'f16': the fp16 storage mode has no streaming kernels ('f16x3' and 'f32' have)"
         elif m.get('normalize') or m.get('normalize_cond') or m.get('normalize_wavenet'):
             why = 'a normaliser (normalize / normalize_cond / normalize_wavenet): outside the fused shape that streams'
-        elif m.get('shared_nets', False):
-            why = 'shared nets: outside the fused shape that streams (two scalar-input nets per flow)'
         elif not (m.filter_width == 2 and m.residual_channels == 64 and m.dilation_channels == 64 and m.skip_channels == 128
                   and all(len(d) >= 2 for d in m.dilations[:m.n_iaf])):
             why = 'nets outside the fused shape (W = 2, R = D = 64, S = 128, at least 2 layers per net)'
@@ -293,7 +299,7 @@ class StreamingVocoder(object):
         self.n_slots = int(slots)
         self.hop = int(hp.signal.hop_length)
         self.n_mels = int(hp.signal.n_mels)
-        self.layout = HistoryLayout([list(d) for d in m.dilations[:m.n_iaf]])
+        self.layout = HistoryLayout([list(d) for d in m.dilations[:m.n_iaf]], nets_per_flow=1 if m.get('shared_nets', False) else 2)
         store = model.store or get_default_store()
         self.device = store.device
         # two blocks per slot and, behind them in the same allocation, the ZERO BLOCK: what a session that starts inside a graphed tick

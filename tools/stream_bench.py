@@ -1,5 +1,6 @@
 """Streaming against overlap-and-discard ("Streaming"): what one TICK of a server costs that advances
-`sessions` sessions by `chunk` samples each, default model, random weights, one GPU, steady state (every session has emitted more
+`sessions` sessions by `chunk` samples each, default model (or --case: 'bench/c2' = the shared-net architecture, one two-output net per
+flow, at the default dilations), random weights, one GPU, steady state (every session has emitted more
 than timeshard.chain_halo samples).
 
 Legs of a cell (sessions x chunk):
@@ -16,7 +17,7 @@ same process, the whole round twice ('ms' holds both medians: their difference i
 count of the library's launch calls in one untimed push per streaming leg: `launches` = {leg: {calls, per-flow routes, short-input
 instantiation per persistent launch}}.  Prints one JSON line.
 
-    python tools/stream_bench.py [--steps 20] [--warmup 5] [--precision f16x3] [--sessions 1,8,32] [--chunks 800,1600,8000]
+    python tools/stream_bench.py [--case default] [--steps 20] [--warmup 5] [--precision f16x3] [--sessions 1,8,32] [--chunks 800,1600,8000]
 
 --ragged ("Ragged pushes"): a tick whose sessions get DIFFERENT numbers of frames.  Cells: S = 8 and 32 running
 sessions, session i given 800 * (1 + i % 4) samples (four distinct lengths, R = 2000 S rows), and one "utterance ends" cell: 31 x 1600
@@ -98,6 +99,8 @@ def main():
     ap.add_argument('--ragged-graph', action='store_true',
                     help='the ragged-tick cells as graph replays (StreamingVocoder.graphed_varlen against the eager push_varlen) instead of the default legs')
     ap.add_argument('--live', action='store_true', help='the streaming mel front-end in front of push_varlen (audio_frontend.StreamingMel) instead of the default legs')
+    ap.add_argument('--case', default='default', help="the hparams case whose model streams: 'default', or 'bench/c2' for the shared-net "
+                    "architecture (one two-output net per flow); every mode takes it, and the result line names it")
     args = ap.parse_args()
 
     import numpy as np
@@ -107,10 +110,12 @@ def main():
     from pwv_amd.models import IAFVocoder
     from pwv_amd.timeshard import chain_halo
     from pwv_amd.variables import VariableStore
+    from pwv_amd.hparam import hparam as hp
     from tests.util import set_hparams
 
     dev = torch.device('cuda', 0)
-    cfg = O.ModelConfig()
+    hp.set_hparam_yaml(args.case)
+    cfg = O.ModelConfig.from_hparam(hp)
     set_hparams(cfg)
     store = VariableStore(device=dev)
     store.load_dict(O.init_weights(cfg, seed=2))
@@ -158,7 +163,7 @@ def main():
         from pwv_amd.audio_frontend import StreamingMel, wav_to_mel_device
         S, frames = 8, 10
         chunk = frames * hop
-        out = {'mode': 'live', 'precision': args.precision, 'steps': args.steps, 'warmup': args.warmup, 'sessions': S, 'frames': frames, 'chunk': chunk}
+        out = {'mode': 'live', 'case': args.case, 'precision': args.precision, 'steps': args.steps, 'warmup': args.warmup, 'sessions': S, 'frames': frames, 'chunk': chunk}
         model = IAFVocoder(batch_size=S, length=hop, store=store, precision=args.precision)
         stream = model.open_stream(slots=S)
         warm = -(-(halo + hop) // hop) * hop
@@ -204,7 +209,7 @@ def main():
         return
 
     if args.ragged:
-        out = {'mode': 'ragged', 'precision': args.precision, 'steps': args.steps, 'warmup': args.warmup, 'cells': []}
+        out = {'mode': 'ragged', 'case': args.case, 'precision': args.precision, 'steps': args.steps, 'warmup': args.warmup, 'cells': []}
         cells = [('mixed_%d' % S, [800 * (1 + i % 4) for i in range(S)]) for S in (8, 32)] + [('utterance_ends', [1600] * 31 + [80])]
         for name, lens in cells:
             S = len(lens)
@@ -261,7 +266,7 @@ def main():
         return
 
     if args.ragged_graph:
-        out = {'mode': 'ragged_graph', 'precision': args.precision, 'steps': args.steps, 'warmup': args.warmup, 'pipelined_ticks': 8, 'cells': []}
+        out = {'mode': 'ragged_graph', 'case': args.case, 'precision': args.precision, 'steps': args.steps, 'warmup': args.warmup, 'pipelined_ticks': 8, 'cells': []}
         cells = [('mixed_%d' % S, [800 * (1 + i % 4) for i in range(S)]) for S in (8, 32)] + [('utterance_ends', [1600] * 31 + [80])]
         for name, lens in cells:
             S = len(lens)
@@ -349,7 +354,7 @@ def main():
         return
 
     if args.graph:
-        out = {'mode': 'graph', 'precision': args.precision, 'steps': args.steps, 'warmup': args.warmup, 'chain_halo': halo, 'pipelined_ticks': 8,
+        out = {'mode': 'graph', 'case': args.case, 'precision': args.precision, 'steps': args.steps, 'warmup': args.warmup, 'chain_halo': halo, 'pipelined_ticks': 8,
                'cells': []}
         for S, chunk in ((1, 800), (1, 1600), (2, 800), (8, 800), (32, 1600)):
             model = IAFVocoder(batch_size=S, length=chunk, store=store, precision=args.precision)
@@ -393,7 +398,7 @@ def main():
         print(json.dumps(out))
         return
 
-    out = {'precision': args.precision, 'steps': args.steps, 'warmup': args.warmup, 'chain_halo': halo, 'cells': []}
+    out = {'case': args.case, 'precision': args.precision, 'steps': args.steps, 'warmup': args.warmup, 'chain_halo': halo, 'cells': []}
     for S in [int(v) for v in args.sessions.split(',')]:
         for chunk in [int(v) for v in args.chunks.split(',')]:
             model = IAFVocoder(batch_size=S, length=chunk, store=store, precision=args.precision)
