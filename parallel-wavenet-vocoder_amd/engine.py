@@ -1209,13 +1209,17 @@ def _instance_norm(nets) -> bool:
     return any(getattr(n, 'normalize', None) == 'in' for n in nets)
 
 
-def _flow_structure(nets, cond, precision: Optional[str] = None) -> Optional[str]:
+def _flow_structure(nets, cond, precision: Optional[str] = None, per_sample: bool = False) -> Optional[str]:
     """Which structural property keeps a flow (its nets) off the forms that run it whole inside the fused launches -- the packed batch's
     and the streaming ones -- as a key, or None: 'samples' (per-sample conditioning), 'skip' (skip accumulation), 'f16' (the fp16
     storage mode), 'shape' (not two scalar-in / scalar-out nets or one shared net of two outputs, all fused-capable, of one structure
-    and one precision).  varlen_fallback_reason and stream_refusal word them."""
+    and one precision).  varlen_fallback_reason and stream_refusal word them.  per_sample=True asks about the per-layer streaming route
+    with a per-sample condition (run_flow_stream): 'samples' is then no obstacle, and a condition that is NOT per sample is 'frames'."""
     net0 = nets[0]
-    if cond is not None and not isinstance(cond, RepeatedCondition):
+    if per_sample:
+        if cond is None or isinstance(cond, RepeatedCondition):
+            return 'frames'
+    elif cond is not None and not isinstance(cond, RepeatedCondition):
         return 'samples'
     if net0.use_skip_connection:
         return 'skip'
@@ -1512,19 +1516,23 @@ def _run_stack_layers(path: _Path, nets, plans, projs, bufs, outs, x, x_limit, c
 
 
 # ---- streaming: a flow on one CHUNK of N sessions (include/pwv_hip.h "STREAMING"; stream.StreamingVocoder owns the sessions) ---------
-_STREAM_STRUCTURE_WHY = {'samples': 'per-sample (transposed-conv) conditioning', 'skip': 'skip accumulation (use_skip_connection)',
+_STREAM_STRUCTURE_WHY = {'samples': 'per-sample (transposed-conv) conditioning',
+                         'frames': 'per_sample=True without a per-sample condition (a [N, T, C] tensor at sample rate)', 'skip': 'skip accumulation (use_skip_connection)',
                          'f16': "precision 'f16' (the fp16 storage mode)",
                          'shape': 'a net outside the fused shape (two scalar-input nets per flow, W = 2, R = D = 64, S = 128, no normaliser, at least 2 layers)'}
 
 
-def stream_refusal(nets, cond, precision: Optional[str] = None) -> Optional[str]:
+def stream_refusal(nets, cond, precision: Optional[str] = None, per_sample: bool = False) -> Optional[str]:
     """Why a flow (its nets) has no streaming form -- or None.  The per-layer kernels stream in three forms only: layer 0 folded onto
     its scalar input, a plain residual layer, the last layer with the head fused behind it.  Two flow shapes stream (_flow_structure):
-    two nets of one output each, and one shared net of two outputs (its launches carry G = 1 and a head / tail of Q = 2)."""
+    two nets of one output each, and one shared net of two outputs (its launches carry G = 1 and a head / tail of Q = 2).
+    per_sample=True: the same question for the streaming forms with a per-sample condition (pwv_wavenet_layer_stream_cond_f32: layer 0
+    folded, a plain residual layer, the last layer gated with the head launch behind it); `cond` is then the [N, T, C] tensor, or the
+    PackedSampleCondition of a ragged chunk."""
     net0 = nets[0]
     if _instance_norm(nets):
         return "instance normalisation ('in'): its statistics span the whole time axis"
-    key = _flow_structure(nets, cond, precision)
+    key = _flow_structure(nets, cond, precision, per_sample)
     if key is None and (net0.normalize or len(net0.dilations) < 2):       # (_flow_structure has settled the nets: two of one output or one of two)
         key = 'shape'
     if key is not None:
@@ -1547,6 +1555,27 @@ def _prepare_flow_stream(nets, x: torch.Tensor, cond, precision: Optional[str]) 
 RAGGED_F32 = True
 
 
+def ragged_cond_rows(cu_frames_i: int, t: int, hop: int):
+    """(host arithmetic of the ragged per-sample route) The rows of the UNCROPPED packed condition -- hop rows per packed frame, frame f
+    at rows hop f .. hop f + hop - 1 -- that are the condition of a session whose frames start at packed frame cu_frames_i and whose
+    chunk has t samples: sample s reads row hop cu_frames_i + hop / 2 + s, the session's own crop [hop/2 : hop/2 + t] (models.py:124).
+    A crop of the packed tensor as a whole would be wrong for every session but the first: each session owns one frame more than t / hop."""
+    import numpy as np
+    return np.arange(hop * int(cu_frames_i) + hop // 2, hop * int(cu_frames_i) + hop // 2 + int(t))
+
+
+class PackedSampleCondition(object):
+    """The per-sample condition of a RAGGED chunk: `full` [F hop, C], the transposed convolutions' output over the packed frames, uncropped
+    (every row depends on its own frame alone, so the stages run once per tick); a group of sessions gathers its rows (ragged_cond_rows)."""
+
+    def __init__(self, full: torch.Tensor, hop: int):
+        self.full, self.hop = full, int(hop)
+
+    @property
+    def shape(self):
+        return tuple(self.full.shape)
+
+
 class _StreamGroup(object):
     """The sessions of a ragged push that share one chunk length (the grouped route of run_flow_stream): their rows and frames in the
     packed tensors (device index vectors) and their rows of the slot table."""
@@ -1555,6 +1584,7 @@ class _StreamGroup(object):
         import numpy as np
         fr = t // geom.hop + 1
         self.t, self.n, self.frames = t, len(members), fr
+        self.first_frames = [geom.cu_frames_host[i] for i in members]
         self.rows_idx = geom._upload(np.concatenate([np.arange(geom.cu_rows_host[i], geom.cu_rows_host[i] + t) for i in members]), torch.int64)
         self.frames_idx = geom._upload(np.concatenate([np.arange(geom.cu_frames_host[i], geom.cu_frames_host[i] + fr) for i in members]), torch.int64)
         self.tab = tab.index_select(0, geom._upload(list(members), torch.int64)).contiguous()
@@ -1567,6 +1597,12 @@ class _StreamGroup(object):
             return None
         if self._cond is not None and self._cond[0]() is cond:
             return self._cond[1]
+        if isinstance(cond, PackedSampleCondition):      # the members' own crops of the uncropped packed condition: [n, t, C]
+            import numpy as np
+            idx = geom._upload(np.concatenate([ragged_cond_rows(f0, self.t, cond.hop) for f0 in self.first_frames]), torch.int64)
+            out = cond.full.index_select(0, idx).reshape(self.n, self.t, cond.full.shape[1])
+            self._cond = (weakref.ref(cond), out)
+            return out
         c = cond.frames.shape[2]
         out = RepeatedCondition(cond.frames.reshape(geom.total_frames, c).index_select(0, self.frames_idx).reshape(self.n, self.frames, c),
                                 cond.hop, cond.offset, self.t)
@@ -1588,7 +1624,7 @@ def stream_groups(geom: 'VarlenGeometry', tab: torch.Tensor) -> List[_StreamGrou
     return groups
 
 
-def _run_flow_stream_ragged(nets, x, cond, precision, hist, scalar_off, row_off, geom, slot_tab):
+def _run_flow_stream_ragged(nets, x, cond, precision, hist, scalar_off, row_off, geom, slot_tab, per_sample=False):
     """run_flow_stream on a ragged chunk (geom: session i has geom.lengths[i] rows of the packed x [R, 1]; route 4 of DESIGN.md section 9
     "Routes").  The launches, chosen once per flow:
       * the PACKED streaming persistent launches (pwv_persist_args.cu_rows with hist->cu_rows, stack_persist_ragged_kernel) where a uniform
@@ -1597,11 +1633,13 @@ def _run_flow_stream_ragged(nets, x, cond, precision, hist, scalar_off, row_off,
       * else the GROUPED route: the sessions grouped by chunk length, each group the uniform streaming flow (persistent or per layer, as
         run_flow_stream decides for it) on its own rows of x, its own frames and its own rows of the slot table, scattered back.
     Same bits: a session's rows do not depend on which sessions were advanced with it.  EVENT_LOG gets ('stream_ragged', None, None,
-    'packed' | 'grouped', why, groups) ahead of the route's own entries."""
+    'packed' | 'grouped', why, groups) ahead of the route's own entries.
+    per_sample (cond a PackedSampleCondition): the grouped route only -- the packed route is the persistent kernel, which cannot host a
+    per-sample condition."""
     x = _require_cuda_f32(x, 'input')
     if x.dim() != 2 or tuple(x.shape) != (geom.rows, 1):
         raise ValueError('input must be the packed chunk [%d, 1], got %s' % (geom.rows, tuple(x.shape)))
-    why = varlen_fallback_reason(nets, cond, geom, precision)
+    why = 'per-sample conditioning (the packed route is the persistent launch)' if per_sample else varlen_fallback_reason(nets, cond, geom, precision)
     if why is None:
         x3 = x.reshape(1, geom.rows, 1)
         prep = _prepare_flow_stream(nets, x3, cond, precision)
@@ -1628,13 +1666,13 @@ def _run_flow_stream_ragged(nets, x, cond, precision, hist, scalar_off, row_off,
         ctypes.memmove(ctypes.addressof(hg), ctypes.addressof(hist), ctypes.sizeof(_lib.StreamArgs))
         hg.slot_tab, hg.cu_rows = grp.tab.data_ptr(), None
         yg = run_flow_stream(nets, x.index_select(0, grp.rows_idx).reshape(grp.n, grp.t, 1), grp.condition(cond, geom), precision, hg,
-                             scalar_off, row_off)
+                             scalar_off, row_off, per_sample=per_sample)
         out.index_copy_(0, grp.rows_idx, yg.reshape(grp.n * grp.t, 1))
     return out
 
 
 def run_flow_stream(nets: Sequence, x: torch.Tensor, cond, precision: Optional[str], hist: _lib.StreamArgs, scalar_off: int,
-                    row_off, geom=None, slot_tab: Optional[torch.Tensor] = None) -> torch.Tensor:
+                    row_off, geom=None, slot_tab: Optional[torch.Tensor] = None, per_sample: bool = False) -> torch.Tensor:
     """One IAF flow on a chunk: x [N, T, 1] = the T samples that follow what each of the N sessions has seen, `cond` the chunk's own
     frames (a RepeatedCondition of T / hop + 1 frames per session).  `hist` carries the history blocks and the slot table of the call
     (read / written block per session); `scalar_off` and `row_off[g][j]` (j >= 1) say where this flow's histories lie in a block.
@@ -1649,14 +1687,19 @@ def run_flow_stream(nets: Sequence, x: torch.Tensor, cond, precision: Optional[s
     launches (persist_suspended()) from the same generation.
     With `geom` (a VarlenGeometry) the chunk is RAGGED: session i brings geom.lengths[i] rows, x is the packed [R, 1], `cond` spans the
     packed frames (geom.frames[i] per session) and `slot_tab` is the device int32 [N, 2] table hist.slot_tab points at
-    (_run_flow_stream_ragged: packed persistent launches, else the sessions grouped by length on the routes above)."""
-    why = stream_refusal(nets, cond, precision)
+    (_run_flow_stream_ragged: packed persistent launches, else the sessions grouped by length on the routes above).
+    per_sample=True (a transposed-conv model's stream): `cond` is the chunk's condition at sample rate, [N, T, C] -- a PackedSampleCondition
+    for a ragged chunk -- and the flow is L calls of pwv_wavenet_layer_stream_cond_f32, the head launch and the affine
+    (_run_flow_stream_cond); the persistent launch cannot host a per-sample condition."""
+    why = stream_refusal(nets, cond, precision, per_sample=per_sample)
     if why is not None:
         raise _lib.PwvError('run_flow_stream: no streaming form: ' + why)
     if geom is not None:
-        return _run_flow_stream_ragged(nets, x, cond, precision, hist, scalar_off, row_off, geom, slot_tab)
+        return _run_flow_stream_ragged(nets, x, cond, precision, hist, scalar_off, row_off, geom, slot_tab, per_sample)
     x = _require_cuda_f32(x, 'input')
     prep = _prepare_flow_stream(nets, x, cond, precision)
+    if per_sample:
+        return _run_flow_stream_cond(prep, nets, x, hist, scalar_off, row_off)
     if prep.path.whole_flow:
         hist.scalar_off = scalar_off
         out = torch.empty_like(x)
@@ -1685,4 +1728,39 @@ def run_flow_stream(nets: Sequence, x: torch.Tensor, cond, precision: Optional[s
                 la.head_packed[g], la.head_out[g] = plans[g].packed_head.data_ptr(), outs[g].data_ptr()
             la.head_q = net0.out_channels
         check(lib.pwv_wavenet_layer_stream_f32(ctypes.byref(la), ctypes.byref(hist), s), 'pwv_wavenet_layer_stream_f32')
+    return _flow_affine(x, outs)
+
+
+def _run_flow_stream_cond(prep: _FlowPrep, nets, x: torch.Tensor, hist: _lib.StreamArgs, scalar_off: int, row_off) -> torch.Tensor:
+    """run_flow_stream with a per-sample condition ("Streaming transposed-conv conditioning"): L streaming layer
+    launches of all the flow's nets with the condition GEMM inside (pwv_wavenet_layer_stream_cond_f32; prep.cond_t is the chunk's
+    condition as the kernels of this arithmetic read it, P the bias-only row, as in the one-shot 'samples' mode), the last one with gated
+    output; the head launch on it -- the fused head has no room for the condition weights --; the affine."""
+    lib, s = _lib.lib(), _stream()
+    net0, plans = nets[0], prep.plans
+    n, t, _ = x.shape
+    G, L = len(plans), plans[0].n_layers
+    assert prep.mode == 'samples' and prep.cond_t is not None
+    if EVENT_LOG is not None:
+        EVENT_LOG.append(('layer_stream_cond', None, None, G, L))      # L calls of pwv_wavenet_layer_stream_cond_f32 + the head + the affine
+    projs = _projections(None, prep.mode, plans, prep.precision, None)
+    outs = [torch.empty((n, t, net0.out_channels), dtype=torch.float32, device=x.device) for _ in plans]
+    bufs = [[torch.empty((lib.pwv_tile32_floats(n * t, 64),), dtype=torch.float32, device=x.device) for _ in range(2)] for _ in plans]
+    for j in range(L):
+        la = _layer_args(net0, plans, projs, projs[0].stride(0), prep.cond_geom, bufs, j, (j + 1) & 1, j & 1, x)
+        la.cond, la.cond_channels = _ptr(prep.cond_t), net0.condition_channels
+        la.out_mode = _lib.OUT_GATED if j == L - 1 else _lib.OUT_RESIDUAL
+        if j == 0:
+            _set_x_first(la, plans, x, prep.x_limit)
+            hist.scalar_off = scalar_off
+        else:
+            for g in range(G):
+                hist.row_off[g] = row_off[g][j]
+        check(lib.pwv_wavenet_layer_stream_cond_f32(ctypes.byref(la), ctypes.byref(hist), s), 'pwv_wavenet_layer_stream_cond_f32')
+    ha = _lib.HeadArgs()
+    ha.G, ha.N, ha.T, ha.Q = G, n, t, net0.out_channels
+    ha.in_mode, ha.precision = _lib.HEAD_IN_GATED, plans[0].precision
+    for g, p in enumerate(plans):
+        ha.in_[g], ha.packed[g], ha.out[g] = bufs[g][(L - 1) & 1].data_ptr(), p.packed_head.data_ptr(), outs[g].data_ptr()
+    check(lib.pwv_wavenet_head_f32(ctypes.byref(ha), s), 'pwv_wavenet_head_f32')
     return _flow_affine(x, outs)

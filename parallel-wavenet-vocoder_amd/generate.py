@@ -23,6 +23,7 @@ import sys
 import numpy as np
 import torch
 
+from . import _lib
 from .hparam import hparam as hp
 from .models import IAFVocoder
 from .variables import reset_default_store
@@ -222,7 +223,8 @@ def generate(case='default', ckpt=None, debug=False, varlen=False, seed=None, st
     :param seed: (with varlen) every utterance draws its noise from stream `seed` at counter 0, so a file's audio depends only on
         its mel and the seed -- not on the other files of the run or their order.
     :param stream: vocode every input at its own length as a STREAM (IAFVocoder.open_stream): one session per input, fed in pushes
-        of `stream` mel frames; writes the files --varlen writes.
+        of `stream` mel frames; writes the files --varlen writes.  A case with cond_upsample_method 'transposed_conv' streams too (on
+        per-layer launches; --graph and --live=graph are refused for it by name).
     :param graph: (with stream) every tick is one replay of a captured ragged tick (StreamingVocoder.graphed_varlen at a capacity of one
         slot per input and inputs x `stream` frames), the first one included: it starts the sessions (tick(starts=)); only an input too
         short for that starts with the eager one-frame push; same files.
@@ -249,6 +251,9 @@ def generate(case='default', ckpt=None, debug=False, varlen=False, seed=None, st
         if not 0 <= seed < (1 << 64):
             raise ValueError('--seed must be in [0, 2**64), got %d' % seed)
     hp.set_hparam_yaml(case)
+    if stream is not None and hp.model.cond_upsample_method == 'transposed_conv' and (graph or live == 'graph'):
+        raise _lib.PwvError('--graph / --live=graph: per-sample (transposed-conv) conditioning streams on per-layer launches only; a graphed '
+                            'tick needs the whole-flow persistent launch (use --stream=FRAMES or --stream=FRAMES --live)')
     live_files = _live_inputs(hp.data_path, hp.generate.batch_size) if live else None
     if not torch.cuda.is_available():
         raise RuntimeError('generate() needs an MI355X: the HIP path has no CPU fallback')
@@ -336,11 +341,17 @@ def generate(case='default', ckpt=None, debug=False, varlen=False, seed=None, st
     return pred_wav
 
 
+def _open_stream(model, slots):
+    """The stream of --stream: a case with model.cond_upsample_method 'transposed_conv' makes the request for its streaming form
+    (IAFVocoder.open_stream(transposed_conv=True)), as the train command line asks for skip / shared."""
+    return model.open_stream(slots=slots, transposed_conv=hp.model.cond_upsample_method == 'transposed_conv')
+
+
 def _generate_stream(model, mels, frames):
     """--stream: input i is session i of one StreamingVocoder; every tick gives each unfinished session its next `frames` frames (the
     rest at its end) in ONE ragged push (push_varlen: fresh and running sessions and short last chunks share the launch; verify=True:
     explicit, as above).  Returns the [len_i, 1] waveforms."""
-    s = model.open_stream(slots=len(mels))
+    s = _open_stream(model, len(mels))
     pos, outs = [0] * len(mels), [[] for _ in mels]
     while any(p < m.shape[0] for p, m in zip(pos, mels)):
         slots = [i for i, m in enumerate(mels) if pos[i] < m.shape[0]]
@@ -389,7 +400,7 @@ def _generate_stream_live(model, wavs, frames, device):
     out.  Returns the [len_i, 1] waveforms: 1 + len_i / hop frames each, so len_i samples, as --varlen."""
     from .audio_frontend import StreamingMel
     n, step = len(wavs), frames * int(hp.signal.hop_length)
-    fe, s = StreamingMel(n, device=device), model.open_stream(slots=n)
+    fe, s = StreamingMel(n, device=device), _open_stream(model, n)
     wavs = [torch.from_numpy(w).to(device) for w in wavs]
     pos, done, outs = [0] * n, [False] * n, [[] for _ in wavs]
     while not all(done):
@@ -420,7 +431,7 @@ def _generate_stream_live_graph(model, wavs, frames, device, depth=4):
     hop = int(hp.signal.hop_length)
     n, step = len(wavs), frames * hop
     # one slot more than inputs, for the filler of a tick of all inputs; per input the frames of a chunk and those an end adds to them
-    fe, s = StreamingMel(n + 1, device=device), model.open_stream(slots=n + 1)
+    fe, s = StreamingMel(n + 1, device=device), _open_stream(model, n + 1)
     seeds = [engine.os_seed() for _ in wavs]
     tail = (int(hp.signal.n_fft) // 2 // hop + 1) * hop
     live = s.graphed_live(fe, n, n * (step + tail) + packed_filler_rows(hop), sample=True, depth=depth)
@@ -494,7 +505,7 @@ def _generate_stream_graph(model, mels, frames, depth=4):
     verified eager push_varlen -- which reruns it as the plain --stream would -- and the ticks go on from there."""
     from . import _lib, engine
     n, hop = len(mels), int(hp.signal.hop_length)
-    s = model.open_stream(slots=n)
+    s = _open_stream(model, n)
     seeds = [engine.os_seed() for _ in mels]
     g = s.graphed_varlen(n, n * frames * hop, sample=True, depth=depth)
     short = [i for i, m in enumerate(mels) if min(frames, m.shape[0] - 1) < g.min_frames]          # (no start a graphed tick takes)

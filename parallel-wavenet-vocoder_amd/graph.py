@@ -407,6 +407,7 @@ class _TickGraph(_Captured):
     PACKED = False             # the push is a packed one: cu_rows with or without a sampler, cu_frames and the unit map besides
 
     def __init__(self, stream, sample, depth, warmup):
+        stream._refuse_graph(type(self).__name__)      # (per-sample conditioning: no whole-flow persistent launch to capture)
         self.stream = stream
         super().__init__(stream.model, stream.device, max(1, int(warmup)))
         self.sample, self.depth = bool(sample), max(1, int(depth))

@@ -246,7 +246,7 @@ class IAFVocoder(object):
         return self._forward(store, mel.unsqueeze(0), noise, False, 'iaf_vocoder', precision, length=geom.rows, geom=geom)
 
     # -- streaming ("Streaming") ---------------------------------------------------------------------
-    def open_stream(self, slots=1, hist_alloc=None):
+    def open_stream(self, slots=1, hist_alloc=None, transposed_conv=False):
         """A stream.StreamingVocoder over this model's weights: `slots` independent sessions that take their mel frames in pushes
         and return each push's samples -- bit for bit the samples the one-shot forward gives for the whole utterance, at the cost
         of the pushed rows alone (every layer keeps the last `dilation` rows of its input per session).  The constructor's
@@ -258,9 +258,14 @@ class IAFVocoder(object):
         numbers of frames, new sessions next to running ones, a short last chunk -- is one call too: ``s.push_varlen([mel_i [f_i,
         n_mels], ...], slots=[...])`` returns the [T_i, 1] pieces (views of one packed tensor, `.packed`) from ONE packed launch per flow
         instead of one push per (frame count, fresh or running) group; same bits, same transaction rule.  `hist_alloc` (tests):
-        called with a float count, returns the zero-filled float32 buffer the histories live in."""
+        called with a float count, returns the zero-filled float32 buffer the histories live in.
+        ``transposed_conv=True`` is the request to stream a model with model.cond_upsample_method 'transposed_conv' (the bare call
+        refuses such hparams, and the request under 'repeat' hparams is a PwvError): every sample of the condition depends on one mel
+        frame, so the chunks still equal the one-shot forward bit for bit; a flow is then L per-layer launches with the condition GEMM
+        inside, the head launch and the affine (no persistent launch, no graph replay).  DESIGN.md section 9, "Streaming transposed-conv
+        conditioning" has the routes and the measured ticks."""
         from .stream import StreamingVocoder
-        return StreamingVocoder(self, slots, hist_alloc=hist_alloc)
+        return StreamingVocoder(self, slots, hist_alloc=hist_alloc, transposed_conv=transposed_conv)
 
     def verify(self):
         """For callers of the enqueue-only form (verify=False / PWV_ASYNC=1): wait for the enqueued forwards and raise
@@ -284,10 +289,11 @@ class IAFVocoder(object):
         return self._mel_limit_val
 
     # -- condition upsampling (models.py:105-136) ----------------------------------------------------
-    def _condition(self, melspec, is_training, strides, store, precision=None, nets=None, length=None):
+    def _condition(self, melspec, is_training, strides, store, precision=None, nets=None, length=None, crop=True):
         """The condition in the form the kernels want: a lazy RepeatedCondition for 'repeat'
         (projected at frame rate inside the nets), a materialised [N, T, C] tensor for
-        'transposed_conv', None otherwise.  `length` overrides the constructor's."""
+        'transposed_conv', None otherwise.  `length` overrides the constructor's.  crop=False ('transposed_conv', a ragged streaming
+        chunk): the stages' output as it is, [N, t_mel * hop, C], without the crop of models.py:124."""
         precision = precision or self.precision
         n_samples = self.length if length is None else length
         hop = hp.signal.hop_length
@@ -328,6 +334,8 @@ class IAFVocoder(object):
                     cond = normalize(cond.reshape(n, length, C), is_training, hp.model.normalize_cond,
                                      name='normalize_transposed_conv_{}'.format(i), store=store).reshape(n * length, C)
             cond = cond.reshape(n, length, C)
+            if not crop:
+                return cond
             return engine.crop_time_op(cond, length - hop, hop // 2)            # models.py:124
         elif method == 'repeat':
             w = get_variable('dense', [1, n_mels, C], store=store)

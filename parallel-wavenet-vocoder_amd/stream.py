@@ -271,17 +271,33 @@ class StreamingVocoder(object):
     2 x 1,737,728 B + 320 B = 3,475,776 B (3.48 MB) per session against 6,949,184 B (6.95 MB) for the default model; state_bytes,
     state and load_state follow the layout, and a state of the other architecture is turned away by its block_floats.
 
-    Refused with a PwvError that names the reason (nothing is launched): per-sample (transposed-conv) conditioning, skip
-    accumulation (a shared-net model with skip connections is refused as a skip model), precision 'f16', any normaliser -- instance
+    A third streams on request, ``open_stream(slots, transposed_conv=True)`` under model.cond_upsample_method 'transposed_conv' (the
+    reference's test/tran; with or without shared_nets): the three transposed convolutions have kernel width == stride, so sample t of
+    the condition depends on mel frame (t + hop/2) // hop alone -- the frame geometry of the 'repeat' streams, kept frame included.  The
+    chunk's frames go through the stage GEMMs, the T rows enter every layer per sample (pwv_wavenet_layer_stream_cond_f32), and a flow is
+    L layer launches, the head launch and the affine: the persistent launch has no LDS for the condition weights.  push, push_varlen
+    (the grouped route), state / load_state, reset, verify and the noise contract are the same; graphed / graphed_varlen / graphed_live
+    refuse by name (they capture the persistent launch).  The request under 'repeat' hparams is a PwvError, and so is hop_length != 80.
+
+    Refused with a PwvError that names the reason (nothing is launched): per-sample (transposed-conv) conditioning without that
+    request, skip accumulation (a shared-net model with skip connections is refused as a skip model), precision 'f16', any normaliser -- instance
     normalisation's statistics span the whole time axis --, nets outside the fused shape."""
 
-    def __init__(self, model, slots: int, hist_alloc=None):
+    def __init__(self, model, slots: int, hist_alloc=None, transposed_conv: bool = False):
         m = hp.model
         why = None
+        per_sample = bool(transposed_conv)
+        if per_sample and m.cond_upsample_method != 'transposed_conv':
+            raise _lib.PwvError("open_stream(transposed_conv=True) does not match these hparams: model.cond_upsample_method is %r"
+                                % (m.cond_upsample_method,))
         if 'in' in (m.get('normalize'), m.get('normalize_cond'), m.get('normalize_wavenet')):
             why = "instance normalisation ('in'): its statistics span the whole time axis, a chunk does not have them"
-        elif m.cond_upsample_method != 'repeat':
+        elif m.cond_upsample_method != 'repeat' and not per_sample:
             why = "per-sample (transposed-conv) conditioning: only 'repeat' conditioning streams (frames enter at frame rate)"
+        elif per_sample and int(hp.signal.hop_length) != 80:
+            why = 'hop_length %d: the transposed convolutions (strides 4, 4, 5) upsample by 80' % int(hp.signal.hop_length)
+        elif per_sample and m.condition_channels != 80:
+            why = 'condition_channels %r: the per-sample layer kernels take 80' % (m.condition_channels,)
         elif m.use_skip_connection:
             why = 'skip accumulation (use_skip_connection: True): the per-layer kernels stream without skip sums only'
         elif (model.precision or engine.DEFAULT_PRECISION) == 'f16':
@@ -296,6 +312,7 @@ class StreamingVocoder(object):
         if int(slots) < 1:
             raise ValueError('slots must be >= 1, got %r' % (slots,))
         self.model = model
+        self.per_sample = per_sample                # a transposed-conv model: the condition enters every layer per sample (_enqueue)
         self.n_slots = int(slots)
         self.hop = int(hp.signal.hop_length)
         self.n_mels = int(hp.signal.n_mels)
@@ -388,9 +405,16 @@ class StreamingVocoder(object):
         if commit is not None:
             commit()
 
+    def _refuse_graph(self, what: str) -> None:
+        """The graph wrappers capture the whole-flow persistent launch, which cannot host a per-sample condition."""
+        if self.per_sample:
+            raise _lib.PwvError('%s: per-sample (transposed-conv) conditioning streams on per-layer launches only; a graphed tick needs the '
+                                'whole-flow persistent launch.  Nothing was captured: push / push_varlen go on as before' % what)
+
     def graphed(self, n: int, frames: int, sample: bool = True, depth: int = 4, warmup: int = 2):
         """One tick of `n` running sessions x `frames` frames captured into a HIP graph with the commit on the device
         (graph.GraphedStream; DESIGN.md section 9, "Graph replay of a streaming tick")."""
+        self._refuse_graph('graphed')
         from .graph import GraphedStream
         return GraphedStream(self, n, frames, sample=sample, depth=depth, warmup=warmup)
 
@@ -398,6 +422,7 @@ class StreamingVocoder(object):
         """A RAGGED tick -- up to `slots` running sessions, `rows` samples in all, every session its own frame count -- captured into a HIP
         graph with the frame counts read and the commit made on the device (graph.GraphedRaggedStream; DESIGN.md section 9, "Graph
         replay of a ragged tick").  Its tick(..., starts={slot: seed}) begins utterances inside a tick, on fresh or running slots."""
+        self._refuse_graph('graphed_varlen')
         from .graph import GraphedRaggedStream
         return GraphedRaggedStream(self, slots, rows, sample=sample, depth=depth, warmup=warmup)
 
@@ -406,6 +431,7 @@ class StreamingVocoder(object):
         `slots` sessions and `rows` samples with the streaming mel front-end `fe` (audio_frontend.StreamingMel; slot k of both is one
         session) at its head and the front-end's commit at its end (graph.GraphedLiveStream; DESIGN.md section 9, "Graph replay of a
         live tick")."""
+        self._refuse_graph('graphed_live')
         from .graph import GraphedLiveStream
         return GraphedLiveStream(self, fe, slots, rows, sample=sample, depth=depth, warmup=warmup)
 
@@ -527,7 +553,15 @@ class StreamingVocoder(object):
             flows = model._flows(store, False, precision)
             nets = [net for iaf in flows for net in iaf.nets()]
             with variable_scope('cond'):
-                cond = model._condition(frames, False, strides=[4, 4, 5], store=store, precision=precision, nets=nets, length=rows)
+                if self.per_sample:
+                    # sample t of the cropped condition depends on frame (t + hop/2) // hop alone (kernel width == stride in every stage):
+                    # the chunk's T / hop + 1 frames give its T rows.  A ragged chunk runs the stages once over the packed frames,
+                    # uncropped, and every group of sessions gathers its own crops (engine.PackedSampleCondition)
+                    cond = model._condition(frames, False, strides=[4, 4, 5], store=store, precision=precision, length=rows, crop=geom is None)
+                    if geom is not None:
+                        cond = engine.PackedSampleCondition(cond.reshape(-1, cond.shape[2]), self.hop)
+                else:
+                    cond = model._condition(frames, False, strides=[4, 4, 5], store=store, precision=precision, nets=nets, length=rows)
             engine.project_all(nets, cond, precision=precision)
             if shortest < lay.max_rows:
                 sa.cu_rows = None if geom is None else geom.cu_rows.data_ptr()      # (packed form: T = 0, every session's own length)
@@ -535,7 +569,8 @@ class StreamingVocoder(object):
                 sa.cu_rows = None
             x = z
             for i, iaf in enumerate(flows):
-                x = engine.run_flow_stream(iaf.nets(), x, cond, precision, sa, lay.scalar_off[i], lay.row_off[i], geom=geom, slot_tab=tab)
+                x = engine.run_flow_stream(iaf.nets(), x, cond, precision, sa, lay.scalar_off[i], lay.row_off[i], geom=geom, slot_tab=tab,
+                                           per_sample=self.per_sample)
         return x
 
     # -- a ragged push ---------------------------------------------------------------------------------------------------

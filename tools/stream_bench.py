@@ -1,6 +1,7 @@
 """Streaming against overlap-and-discard ("Streaming"): what one TICK of a server costs that advances
 `sessions` sessions by `chunk` samples each, default model (or --case: 'bench/c2' = the shared-net architecture, one two-output net per
-flow, at the default dilations), random weights, one GPU, steady state (every session has emitted more
+flow, at the default dilations; 'bench/c5' = transposed-conv conditioning, whose stream is per-layer launches with the condition GEMM
+inside -- its `stream` leg is that route and there is no `stream_layers` leg; the graph modes refuse it), random weights, one GPU, steady state (every session has emitted more
 than timeshard.chain_halo samples).
 
 Legs of a cell (sessions x chunk):
@@ -99,8 +100,8 @@ def main():
     ap.add_argument('--ragged-graph', action='store_true',
                     help='the ragged-tick cells as graph replays (StreamingVocoder.graphed_varlen against the eager push_varlen) instead of the default legs')
     ap.add_argument('--live', action='store_true', help='the streaming mel front-end in front of push_varlen (audio_frontend.StreamingMel) instead of the default legs')
-    ap.add_argument('--case', default='default', help="the hparams case whose model streams: 'default', or 'bench/c2' for the shared-net "
-                    "architecture (one two-output net per flow); every mode takes it, and the result line names it")
+    ap.add_argument('--case', default='default', help="the hparams case whose model streams: 'default', 'bench/c2' for the shared-net "
+                    "architecture (one two-output net per flow), 'bench/c5' for transposed-conv conditioning; the result line names it")
     args = ap.parse_args()
 
     import numpy as np
@@ -122,6 +123,12 @@ def main():
     hop = cfg.hop_length
     halo = chain_halo(cfg.dilations, cfg.filter_width, cfg.n_iaf, hop)
     rng = np.random.default_rng(0)
+
+    # a transposed-conv case ('bench/c5') makes the request for its streaming form: per-layer launches with the condition GEMM inside
+    per_sample = cfg.cond_upsample_method == 'transposed_conv'
+
+    def open_stream(model, slots):
+        return model.open_stream(slots=slots, transposed_conv=per_sample)
 
     def rand(*shape):
         return torch.from_numpy(rng.uniform(-1, 1, shape).astype(np.float32)).to(dev)
@@ -165,7 +172,7 @@ def main():
         chunk = frames * hop
         out = {'mode': 'live', 'case': args.case, 'precision': args.precision, 'steps': args.steps, 'warmup': args.warmup, 'sessions': S, 'frames': frames, 'chunk': chunk}
         model = IAFVocoder(batch_size=S, length=hop, store=store, precision=args.precision)
-        stream = model.open_stream(slots=S)
+        stream = open_stream(model, S)
         warm = -(-(halo + hop) // hop) * hop
         stream.push(rand(S, warm // hop + 1, cfg.n_mels), z=rand(S, warm, 1))        # steady state: every session running
         fe = StreamingMel(S)
@@ -177,7 +184,7 @@ def main():
         # the live tick as ONE graph launch (graph.GraphedLiveStream), on a stream and a front-end of its own in the same steady state; a
         # slot and a filler's rows to spare, so that the tick of all 8 sessions replays
         from pwv_amd.graph import packed_filler_rows
-        stream_g, fe_g = model.open_stream(slots=S + 1), StreamingMel(S + 1)
+        stream_g, fe_g = open_stream(model, S + 1), StreamingMel(S + 1)
         stream_g.push(rand(S, warm // hop + 1, cfg.n_mels), slots=list(range(S)), z=rand(S, warm, 1))
         fe_g.push(list(0.5 * rand(S, chunk)), slots=list(range(S)))
         live = stream_g.graphed_live(fe_g, S, S * chunk + packed_filler_rows(hop), sample=False)
@@ -214,7 +221,7 @@ def main():
         for name, lens in cells:
             S = len(lens)
             model = IAFVocoder(batch_size=S, length=hop, store=store, precision=args.precision)
-            stream = model.open_stream(slots=S)
+            stream = open_stream(model, S)
             warm = -(-(halo + hop) // hop) * hop
             stream.push(rand(S, warm // hop + 1, cfg.n_mels), z=rand(S, warm, 1))        # steady state: every session running
             mels, zs = [rand(T // hop, cfg.n_mels) for T in lens], [rand(T, 1) for T in lens]
@@ -271,7 +278,7 @@ def main():
         for name, lens in cells:
             S = len(lens)
             model = IAFVocoder(batch_size=S, length=hop, store=store, precision=args.precision)
-            stream = model.open_stream(slots=S)
+            stream = open_stream(model, S)
             warm = -(-(halo + hop) // hop) * hop
             stream.push(rand(S, warm // hop + 1, cfg.n_mels), z=rand(S, warm, 1))        # steady state: every session running
             graphed = stream.graphed_varlen(S, sum(lens), sample=False)
@@ -358,7 +365,7 @@ def main():
                'cells': []}
         for S, chunk in ((1, 800), (1, 1600), (2, 800), (8, 800), (32, 1600)):
             model = IAFVocoder(batch_size=S, length=chunk, store=store, precision=args.precision)
-            stream = model.open_stream(slots=S)
+            stream = open_stream(model, S)
             warm = -(-(halo + hop) // hop) * hop
             stream.push(rand(S, warm // hop + 1, cfg.n_mels), z=rand(S, warm, 1))        # steady state: emitted > chain_halo
             graphed = stream.graphed(S, chunk // hop, sample=False)
@@ -402,7 +409,7 @@ def main():
     for S in [int(v) for v in args.sessions.split(',')]:
         for chunk in [int(v) for v in args.chunks.split(',')]:
             model = IAFVocoder(batch_size=S, length=chunk, store=store, precision=args.precision)
-            stream = model.open_stream(slots=S)
+            stream = open_stream(model, S)
             warm = -(-(halo + hop) // hop) * hop
             stream.push(rand(S, warm // hop + 1, cfg.n_mels), z=rand(S, warm, 1))        # steady state: emitted > chain_halo
             mel_s, z_s = rand(S, chunk // hop, cfg.n_mels), rand(S, chunk, 1)
@@ -422,8 +429,11 @@ def main():
                 'overlap': (lambda: over(None, mel_o, z=z_o, verify=False)[:, halo:], lambda: engine.verify_enqueued('overlap')),
                 'rows': (lambda: model(None, mel_r, z=z_r, verify=False), lambda: engine.verify_enqueued('rows')),
             }
+            if per_sample:          # (one streaming route only: PERSIST plays no part)
+                del legs['stream_layers']
+            stream_legs = [name for name in ('stream', 'stream_layers') if name in legs]
             cell = {'sessions': S, 'chunk': chunk, 'stream_rows': S * chunk, 'overlap_rows': S * (chunk + halo), 'launches': {}}
-            for name in ('stream', 'stream_layers'):        # one untimed push per streaming leg: what it enqueues
+            for name in stream_legs:        # one untimed push per streaming leg: what it enqueues
                 log, calls = [], []
                 engine.EVENT_LOG, _lib.lib = log, (lambda: counting(calls))
                 try:
@@ -441,9 +451,10 @@ def main():
                     ms, host = timed(fn, sync)
                     cell[name]['ms'].append(round(ms, 3))
                     cell[name]['enqueue_ms'].append(round(host, 3))
-            assert stream.emitted(0) == warm + (4 * (args.warmup + args.steps) + 2) * chunk
+            assert stream.emitted(0) == warm + len(stream_legs) * (2 * (args.warmup + args.steps) + 1) * chunk
             cell['overlap_over_stream'] = [round(o / s, 3) for o, s in zip(cell['overlap']['ms'], cell['stream']['ms'])]
-            cell['stream_over_stream_layers'] = [round(a / b, 3) for a, b in zip(cell['stream']['ms'], cell['stream_layers']['ms'])]
+            if 'stream_layers' in legs:
+                cell['stream_over_stream_layers'] = [round(a / b, 3) for a, b in zip(cell['stream']['ms'], cell['stream_layers']['ms'])]
             cell['stream_over_rows'] = [round(a / b, 3) for a, b in zip(cell['stream']['ms'], cell['rows']['ms'])]
             out['cells'].append(cell)
             print('# %s' % json.dumps(cell), file=sys.stderr)
