@@ -166,9 +166,17 @@ class StackArgs(Structure):
     ]
 
 
-class PersistArgs(Structure):
+class SizedStructure(Structure):
+    """A struct that begins with `struct_size`: __init__ stamps it with the size of the class that is constructed."""
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_size = ctypes.sizeof(type(self))
+
+
+class PersistArgs(SizedStructure):
     _fields_ = [
-        ('struct_size', c_size_t),      # set by __init__
+        ('struct_size', c_size_t),      # set by SizedStructure
         ('G', c_int),
         ('n_layers', c_int),
         ('dilations', POINTER(c_int)),
@@ -210,14 +218,10 @@ class PersistArgs(Structure):
         ('hist_row_off', POINTER(c_size_t) * PWV_MAX_NETS),
     ]
 
-    def __init__(self, *args, **kw):
-        super().__init__(*args, **kw)
-        self.struct_size = ctypes.sizeof(PersistArgs)
-
-class StreamArgs(Structure):
+class StreamArgs(SizedStructure):
     """pwv_stream_args: where a streaming layer launch finds its sessions' histories (include/pwv_hip.h, "STREAMING")."""
     _fields_ = [
-        ('struct_size', c_size_t),      # set by __init__
+        ('struct_size', c_size_t),      # set by SizedStructure
         ('hist_rd', c_void_p),
         ('hist_wr', c_void_p),
         ('block_stride', c_size_t),
@@ -229,15 +233,11 @@ class StreamArgs(Structure):
         ('cu_rows', c_void_p),          # NULL: the uniform [N, T] chunk; else device int32 [N + 1]: sessions of different chunk lengths (the ragged launch)
     ]
 
-    def __init__(self, *args, **kw):
-        super().__init__(*args, **kw)
-        self.struct_size = ctypes.sizeof(StreamArgs)
 
-
-class StreamTickArgs(Structure):
+class StreamTickArgs(SizedStructure):
     """pwv_stream_tick_args: the device session table of a stream and the tables of one tick (include/pwv_hip.h, "A streaming TICK")."""
     _fields_ = [
-        ('struct_size', c_size_t),      # set by __init__
+        ('struct_size', c_size_t),      # set by SizedStructure
         ('sess', c_void_p),
         ('kept', c_void_p),
         ('entries', c_void_p),
@@ -252,16 +252,12 @@ class StreamTickArgs(Structure):
         ('counters', c_void_p),
     ]
 
-    def __init__(self, *args, **kw):
-        super().__init__(*args, **kw)
-        self.struct_size = ctypes.sizeof(StreamTickArgs)
 
-
-class StreamTickRaggedArgs(Structure):
+class StreamTickRaggedArgs(SizedStructure):
     """pwv_stream_tick_ragged_args: the device session table of a stream and the tables of one RAGGED tick (include/pwv_hip.h, "A RAGGED
     streaming tick")."""
     _fields_ = [
-        ('struct_size', c_size_t),      # set by __init__
+        ('struct_size', c_size_t),      # set by SizedStructure
         ('sess', c_void_p),
         ('kept', c_void_p),
         ('entries', c_void_p),
@@ -282,10 +278,6 @@ class StreamTickRaggedArgs(Structure):
         ('zero_block', ctypes.c_int32),  # a history block of zeros that is never written (>= 2 * n_slots)
     ]
 
-    def __init__(self, *args, **kw):
-        super().__init__(*args, **kw)
-        self.struct_size = ctypes.sizeof(StreamTickRaggedArgs)
-
 
 MEL_STREAM_REC = 12           # PWV_MEL_STREAM_REC: int64 per session of a streaming mel push
 # the fields of such a record, in order (include/pwv_hip_mel_stream.h)
@@ -293,10 +285,10 @@ MEL_REC_FIELDS = ('carry_first', 'carry_len', 'chunk_off', 'chunk_len', 'first_f
                   'out_row', 'new_carry_first', 'max_word')
 
 
-class MelStreamArgs(Structure):
+class MelStreamArgs(SizedStructure):
     """pwv_mel_stream_args: one ragged push of the streaming mel front-end."""
     _fields_ = [
-        ('struct_size', c_size_t),      # set by __init__
+        ('struct_size', c_size_t),      # set by SizedStructure
         ('wav', c_void_p),
         ('window', c_void_p),
         ('mel_basis', c_void_p),
@@ -311,10 +303,6 @@ class MelStreamArgs(Structure):
         ('amin', ctypes.c_float), ('max_db', ctypes.c_float), ('min_db', ctypes.c_float),
     ]
 
-    def __init__(self, *args, **kw):
-        super().__init__(*args, **kw)
-        self.struct_size = ctypes.sizeof(MelStreamArgs)
-
 
 LIVE_TICK_REC = 12            # PWV_LIVE_TICK_REC: int64 per record of a live tick
 # the fields of such a record, in order (include/pwv_hip_live_tick.h): the streaming record's, with the slot, the flags and the row of
@@ -324,10 +312,10 @@ LIVE_REC_FIELDS = ('carry_first', 'carry_len', 'chunk_off', 'chunk_len', 'first_
 LIVE_ACTIVE, LIVE_START, LIVE_FIRST = 1, 2, 4
 
 
-class LiveTickArgs(Structure):
+class LiveTickArgs(SizedStructure):
     """pwv_live_tick_args: the front-end half of a live tick (include/pwv_hip_live_tick.h)."""
     _fields_ = [
-        ('struct_size', c_size_t),      # set by __init__
+        ('struct_size', c_size_t),      # set by SizedStructure
         ('wav', c_void_p),
         ('window', c_void_p),
         ('mel_basis', c_void_p),
@@ -346,19 +334,15 @@ class LiveTickArgs(Structure):
         ('amin', ctypes.c_float), ('max_db', ctypes.c_float), ('min_db', ctypes.c_float), ('limit_db', ctypes.c_float),
     ]
 
-    def __init__(self, *args, **kw):
-        super().__init__(*args, **kw)
-        self.struct_size = ctypes.sizeof(LiveTickArgs)
-
 
 SCORE_MAX_WIN = 1024          # PWV_SCORE_MAX_WIN
 SCORE_TILE = 1024             # PWV_SCORE_TILE: samples per L1 partial
 
 
-class ScoreArgs(Structure):
+class ScoreArgs(SizedStructure):
     """pwv_score_args: one scoring call over n utterances, uniform or packed (include/pwv_hip_score.h)."""
     _fields_ = [
-        ('struct_size', c_size_t),      # set by __init__
+        ('struct_size', c_size_t),      # set by SizedStructure
         ('out', c_void_p),
         ('y', c_void_p),
         ('cu_rows', c_void_p),          # NULL: the uniform form
@@ -370,17 +354,13 @@ class ScoreArgs(Structure):
         ('workspace_bytes', c_size_t),
     ]
 
-    def __init__(self, *args, **kw):
-        super().__init__(*args, **kw)
-        self.struct_size = ctypes.sizeof(ScoreArgs)
-
 
 TRAIN_RESIDUAL, TRAIN_LAST = 0, 1      # PWV_TRAIN_RESIDUAL, PWV_TRAIN_LAST
 
 
-class TrainArgs(Structure):
+class TrainArgs(SizedStructure):
     """pwv_train_args: one training kernel call on one net (include/pwv_hip_train.h)."""
-    _fields_ = ([('struct_size', c_size_t)]      # set by __init__
+    _fields_ = ([('struct_size', c_size_t)]      # set by SizedStructure
                 + [(n, ctypes.c_int32) for n in ('N', 'T', 'form', 'dilation', 'next_dilation', 'cond_hop', 'cond_offset', 'cond_frames',
                                                  'proj_row_stride', 'd_proj_row_stride', 'max_workgroups', 'accumulate')]
                 + [(n, c_void_p) for n in ('in_', 'x', 'x_out', 'proj', 'y', 'causal_filter', 'filter', 'gate', 'dense', 'dense_bias',
@@ -390,15 +370,11 @@ class TrainArgs(Structure):
                                            'd_skip', 'd_skip_bias', 'd_post1', 'd_post1_bias', 'd_post2', 'd_post2_bias', 'workspace')]
                 + [('workspace_bytes', c_size_t)])
 
-    def __init__(self, *args, **kw):
-        super().__init__(*args, **kw)
-        self.struct_size = ctypes.sizeof(TrainArgs)
 
-
-class TrainLossArgs(Structure):
+class TrainLossArgs(SizedStructure):
     """pwv_train_loss_args: the loss terms of a uniform batch and their gradient for the prediction (include/pwv_hip_train_loss.h)."""
     _fields_ = [
-        ('struct_size', c_size_t),      # set by __init__
+        ('struct_size', c_size_t),      # set by SizedStructure
         ('out', c_void_p),
         ('y', c_void_p),
         ('n', ctypes.c_int32), ('T', ctypes.c_int32),
@@ -410,24 +386,16 @@ class TrainLossArgs(Structure):
         ('workspace_bytes', c_size_t),
     ]
 
-    def __init__(self, *args, **kw):
-        super().__init__(*args, **kw)
-        self.struct_size = ctypes.sizeof(TrainLossArgs)
 
-
-class TrainVarlenArgs(Structure):
+class TrainVarlenArgs(SizedStructure):
     """pwv_train_varlen_args: one training kernel call on one net over a packed batch (include/pwv_hip_train_varlen.h): the fields of
     TrainArgs, then the packed batch."""
     _fields_ = (TrainArgs._fields_
                 + [('cu_rows', c_void_p), ('cu_frames', c_void_p)]
                 + [(n, ctypes.c_int32) for n in ('n', 'rows', 'proj_rows')])
 
-    def __init__(self, *args, **kw):
-        super().__init__(*args, **kw)
-        self.struct_size = ctypes.sizeof(TrainVarlenArgs)
 
-
-class TrainCondArgs(Structure):
+class TrainCondArgs(SizedStructure):
     """pwv_train_cond_args: one layer call of training with a per-sample condition (include/pwv_hip_train_cond.h): the embedded
     pwv_train_args (its fields flat here, at the same offsets), then the condition."""
     _fields_ = (TrainArgs._fields_
@@ -435,12 +403,31 @@ class TrainCondArgs(Structure):
                                            'd_filter_bias', 'd_gate_bias')]
                 + [(n, ctypes.c_int32) for n in ('cond_channels', 'cond_row_stride', 'cond_utt_rows', 'd_cond_accumulate')])
 
-    def __init__(self, *args, **kw):
-        super().__init__(*args, **kw)
-        self.struct_size = ctypes.sizeof(TrainCondArgs)
+
+class EmbedsTrainArgs(Structure):
+    """A struct that begins with an embedded pwv_train_args, `train`, whose struct_size holds the size of the WHOLE struct; OWN: the
+    names of the fields behind it.  `set` routes a name to the new fields first, then to `train`; `embed` takes a filled TrainArgs."""
+    OWN = frozenset()
+
+    def __init__(self, **kw):
+        super().__init__()
+        self.set(**kw)
+        self.train.struct_size = ctypes.sizeof(type(self))
+
+    def set(self, **kw):
+        for k, v in kw.items():
+            setattr(self if k in self.OWN else self.train, k, v)
+        return self
+
+    def embed(self, base):
+        """Copy `base`, a filled TrainArgs (or the front of a struct that begins with its fields, as TrainVarlenArgs does), into
+        `train`; its struct_size stays the whole struct's."""
+        ctypes.memmove(ctypes.addressof(self.train), ctypes.addressof(base), ctypes.sizeof(TrainArgs))
+        self.train.struct_size = ctypes.sizeof(type(self))
+        return self
 
 
-class TrainSkipArgs(Structure):
+class TrainSkipArgs(EmbedsTrainArgs):
     """pwv_train_skip_args: one layer or head call of training the skip-connection architecture (include/pwv_hip_train_skip.h): the
     embedded pwv_train_args as `train` (the new struct has fields named like two of its own: d_skip, d_skip_bias), then the skip sum
     and the packed batch.  `set` routes a name to the new fields first, then to `train`."""
@@ -452,18 +439,8 @@ class TrainSkipArgs(Structure):
     OWN = frozenset(('skip_sum', 'd_skip_sum', 'd_skip_sum_out', 'd_skip', 'd_skip_bias', 'skip_accumulate', 'cu_rows', 'cu_frames', 'n',
                      'rows', 'proj_rows'))
 
-    def __init__(self, **kw):
-        super().__init__()
-        self.set(**kw)
-        self.train.struct_size = ctypes.sizeof(TrainSkipArgs)
 
-    def set(self, **kw):
-        for k, v in kw.items():
-            setattr(self if k in TrainSkipArgs.OWN else self.train, k, v)
-        return self
-
-
-class TrainSharedArgs(Structure):
+class TrainSharedArgs(EmbedsTrainArgs):
     """pwv_train_shared_args: one head call of training the shared-net architecture (include/pwv_hip_train_shared.h): the embedded
     pwv_train_args as `train`, then the head's input mode, the skip sum, dS and the shift plane (train.y is the scale plane).  `set`
     routes a name to the new fields first, then to `train`."""
@@ -471,22 +448,12 @@ class TrainSharedArgs(Structure):
                 + [(n, c_void_p) for n in ('skip_sum', 'd_skip_sum_out', 'y_shift')])
     OWN = frozenset(('head_in', 'skip_sum', 'd_skip_sum_out', 'y_shift'))
 
-    def __init__(self, **kw):
-        super().__init__()
-        self.set(**kw)
-        self.train.struct_size = ctypes.sizeof(TrainSharedArgs)
 
-    def set(self, **kw):
-        for k, v in kw.items():
-            setattr(self if k in TrainSharedArgs.OWN else self.train, k, v)
-        return self
-
-
-class TrainLossVarlenArgs(Structure):
+class TrainLossVarlenArgs(SizedStructure):
     """pwv_train_loss_varlen_args: the loss terms of a packed batch and their gradient for the prediction
     (include/pwv_hip_train_varlen.h)."""
     _fields_ = [
-        ('struct_size', c_size_t),      # set by __init__
+        ('struct_size', c_size_t),      # set by SizedStructure
         ('out', c_void_p),
         ('y', c_void_p),
         ('cu_rows', c_void_p),
@@ -499,15 +466,11 @@ class TrainLossVarlenArgs(Structure):
         ('workspace_bytes', c_size_t),
     ]
 
-    def __init__(self, *args, **kw):
-        super().__init__(*args, **kw)
-        self.struct_size = ctypes.sizeof(TrainLossVarlenArgs)
 
-
-class TrainOptPackArgs(Structure):
+class TrainOptPackArgs(SizedStructure):
     """pwv_train_opt_pack_args: tensors into an arena, or an arena into the tensors (include/pwv_hip_train_opt.h)."""
     _fields_ = [
-        ('struct_size', c_size_t),      # set by __init__
+        ('struct_size', c_size_t),      # set by SizedStructure
         ('table', c_void_p),
         ('block_map', c_void_p),
         ('table_host', c_void_p),
@@ -517,15 +480,11 @@ class TrainOptPackArgs(Structure):
         ('n', ctypes.c_int32), ('blocks', ctypes.c_int32),
     ]
 
-    def __init__(self, *args, **kw):
-        super().__init__(*args, **kw)
-        self.struct_size = ctypes.sizeof(TrainOptPackArgs)
 
-
-class TrainOptAdamArgs(Structure):
+class TrainOptAdamArgs(SizedStructure):
     """pwv_train_opt_adam_args: one Adam + EMA step over the arenas (include/pwv_hip_train_opt.h)."""
     _fields_ = [
-        ('struct_size', c_size_t),      # set by __init__
+        ('struct_size', c_size_t),      # set by SizedStructure
         ('table', c_void_p),
         ('block_map', c_void_p),
         ('table_host', c_void_p),
@@ -540,10 +499,6 @@ class TrainOptAdamArgs(Structure):
         ('decay', ctypes.c_double),
         ('grad_scale', ctypes.c_double),
     ]
-
-    def __init__(self, *args, **kw):
-        super().__init__(*args, **kw)
-        self.struct_size = ctypes.sizeof(TrainOptAdamArgs)
 
 
 # per-source extra flags (none in the product; tools/probes/regw/README.md: the register-stationary probe kernel needs

@@ -9,10 +9,10 @@
 // The unit bodies that depend on where an utterance begins and ends live in pwv_train_units.h, written over a geometry and a
 // conditioning policy, with the host text of their entry points; the kernels here are their uniform [N, T] instances on the
 // frame-rate projection (csrc/pwv_train_varlen.hip holds the packed ones, csrc/pwv_train_cond.hip those of a per-sample condition),
-// next to the head, which is row-independent, and the reduction.
+// next to the one-output instance of the head (csrc/pwv_train_head.h), which is row-independent, and the reduction.
 #include "pwv_common.h"
 #include "pwv_hip_train.h"
-#include "pwv_train_units.h"
+#include "pwv_train_head.h"
 
 namespace pwv {
 
@@ -23,129 +23,12 @@ __global__ __launch_bounds__(kTrThreads) void train_front_fwd_kernel(FrontFwdPar
 
 __global__ __launch_bounds__(kTrThreads) void train_layer_fwd_kernel(LayerFwdParams p) { layer_fwd_body<UniformGeo, ProjCond>(p, {}); }
 
-struct HeadParams {
-    const float *o, *skip, *skip_bias, *post1, *post1_bias, *post2, *post2_bias;
-    float* y;                                   // forward
-    const float *d_out, *d_mul;                 // backward
-    float* d_o;
-    float* part;
-    int rows;
-};
-
-// h1 = relu(o skip + sb), h2 = relu(h1 post1 + b1) of one unit; o is in LDS
-__device__ __forceinline__ void head_hidden(float* h1, float* h2, const float* o, const HeadParams& p) {
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5;
-    {
-        f32x16 acc = zero16();
-        gemm_xw<64>(acc, o, kLdH, p.skip + 32 * w, 128);
-        const float b = p.skip_bias ? p.skip_bias[32 * w + j] : 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) h1[acc_row(r, h) * kLdW + 32 * w + j] = fmaxf(acc[r] + b, 0.f);
-    }
-    __syncthreads();
-    {
-        f32x16 acc = zero16();
-        gemm_xw<128>(acc, h1, kLdW, p.post1 + 32 * w, 128);
-        const float b = p.post1_bias ? p.post1_bias[32 * w + j] : 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) h2[acc_row(r, h) * kLdW + 32 * w + j] = fmaxf(acc[r] + b, 0.f);
-    }
-    __syncthreads();
-}
-
-__global__ __launch_bounds__(kTrThreads) void train_head_fwd_kernel(HeadParams p) {
-    __shared__ float o[32 * kLdH];
-    __shared__ float h1[32 * kLdW];
-    __shared__ float h2[32 * kLdW];
-    const int units = (p.rows + 31) / 32;
-    for (int u = blockIdx.x; u < units; u += gridDim.x) {
-        tile32_to_lds(o, kLdH, 0, p.o, u, p.rows);
-        __syncthreads();
-        head_hidden(h1, h2, o, p);
-        // y[r] = h2[r] . post2 + b2: 8 lanes per row, 16 columns each, then a fixed tree over the 8
-        const int r = threadIdx.x >> 3, part = threadIdx.x & 7;
-        float s = 0.f;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) s += h2[r * kLdW + 16 * part + e] * p.post2[16 * part + e];
-        s += __shfl_xor(s, 1);
-        s += __shfl_xor(s, 2);
-        s += __shfl_xor(s, 4);
-        if (part == 0 && 32 * u + r < p.rows) p.y[32 * u + r] = s + (p.post2_bias ? p.post2_bias[0] : 0.f);
-        __syncthreads();
-    }
-}
+__global__ __launch_bounds__(kTrThreads) void train_head_fwd_kernel(HeadParams p) { head_fwd_body<GatedIn, 1>(p); }
 
 // ------------------------------------------------------------------------------------------------------------------------------
 // backward
 // ------------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kTrThreads) void train_head_bwd_kernel(HeadParams p) {
-    __shared__ float o[32 * kLdH];
-    __shared__ float h1[32 * kLdW];             // h1, then dz1
-    __shared__ float h2[32 * kLdW];             // h2, then dz2
-    __shared__ float dy[32];
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5;
-    const int units = (p.rows + 31) / 32;
-    f32x16 g_post1[4], g_skip[2];
-#pragma unroll
-    for (int b = 0; b < 4; ++b) g_post1[b] = zero16();
-    g_skip[0] = zero16();
-    g_skip[1] = zero16();
-    float g_p2 = 0.f, g_b1 = 0.f, g_sb = 0.f, g_b2 = 0.f;      // thread c < 128: column c; g_b2: thread 128
-    for (int u = blockIdx.x; u < units; u += gridDim.x) {
-        tile32_to_lds(o, kLdH, 0, p.o, u, p.rows);
-        if (threadIdx.x < 32) {
-            const int row = 32 * u + threadIdx.x;
-            dy[threadIdx.x] = row < p.rows ? p.d_out[row] * (p.d_mul ? p.d_mul[row] : 1.f) : 0.f;
-        }
-        __syncthreads();
-        head_hidden(h1, h2, o, p);
-        if (threadIdx.x < 128) {                // d post2, dz2 = dy post2^T where h2 > 0, d b1
-            const int c = threadIdx.x;
-            const float w2 = p.post2[c];
-            for (int r = 0; r < 32; ++r) {
-                const float v = h2[r * kLdW + c], z = v > 0.f ? dy[r] * w2 : 0.f;
-                g_p2 += v * dy[r];
-                g_b1 += z;
-                h2[r * kLdW + c] = z;
-            }
-        } else if (threadIdx.x == 128) {
-            for (int r = 0; r < 32; ++r) g_b2 += dy[r];
-        }
-        __syncthreads();
-        for (int b = 0; b < 4; ++b) gemm_tn(g_post1[b], h1, kLdW, 32 * b, h2, kLdW, 32 * w);      // d post1 += h1^T dz2
-        f32x16 acc = zero16();                  // dh1 = dz2 post1^T, columns 32 w ..
-        gemm_xwt<128>(acc, h2, kLdW, p.post1 + (size_t)32 * w * 128, 128);
-        __syncthreads();                        // every wave has read h1 as an operand
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            float* e = h1 + acc_row(r, h) * kLdW + 32 * w + j;
-            *e = *e > 0.f ? acc[r] : 0.f;       // dz1
-        }
-        __syncthreads();
-        if (threadIdx.x < 128) {
-            const int c = threadIdx.x;
-            for (int r = 0; r < 32; ++r) g_sb += h1[r * kLdW + c];
-        }
-        for (int b = 0; b < 2; ++b) gemm_tn(g_skip[b], o, kLdH, 32 * b, h1, kLdW, 32 * w);        // d skip += o^T dz1
-        f32x16 d_o_acc = zero16();
-        if (w < 2) gemm_xwt<128>(d_o_acc, h1, kLdW, p.skip + (size_t)32 * w * 128, 128);             // d o = dz1 skip^T, columns 32 w ..
-        __syncthreads();                        // every wave has read o
-        if (w < 2) acc_to_lds(d_o_acc, o, kLdH, 32 * w);
-        __syncthreads();
-        lds_to_tile32(p.d_o, u, o, kLdH, 0);
-        __syncthreads();
-    }
-    float* part = p.part + (size_t)blockIdx.x * kHeadPart;
-    for (int b = 0; b < 2; ++b) acc_to_part(g_skip[b], part, 128, 32 * b, 32 * w);
-    for (int b = 0; b < 4; ++b) acc_to_part(g_post1[b], part + 64 * 128 + 128, 128, 32 * b, 32 * w);
-    if (threadIdx.x < 128) {
-        part[64 * 128 + threadIdx.x] = g_sb;
-        part[64 * 128 + 128 + 128 * 128 + threadIdx.x] = g_b1;
-        part[64 * 128 + 128 + 128 * 128 + 128 + threadIdx.x] = g_p2;
-    } else if (threadIdx.x == 128) {
-        part[kHeadPart - 1] = g_b2;
-    }
-}
+__global__ __launch_bounds__(kTrThreads) void train_head_bwd_kernel(HeadParams p) { head_bwd_body<GatedIn, 1>(p); }
 
 template <bool LAST>
 __global__ __launch_bounds__(kTrThreads) void train_layer_bwd_kernel(LayerBwdParams p) {
@@ -281,46 +164,28 @@ extern "C" int pwv_train_layer_fwd_f32(const pwv_train_args* a, pwv_stream_t str
     });
 }
 
-static int head_params(const pwv_train_args* a, const char* who, HeadParams& p) {
+static int head_check(const pwv_train_args* a, const char* who) {
+    if (int e = train_check(a, who)) return e;
     PWV_CHECK_ARG(a->x && a->skip && a->post1 && a->post2, "%s: x, skip, post1 or post2 is a NULL pointer", who);
-    p.o = a->x; p.skip = a->skip; p.skip_bias = a->skip_bias; p.post1 = a->post1; p.post1_bias = a->post1_bias;
-    p.post2 = a->post2; p.post2_bias = a->post2_bias;
-    p.y = a->y; p.d_out = a->d_out; p.d_mul = a->d_mul; p.d_o = a->d_o_out; p.part = (float*)a->workspace;
-    p.rows = a->N * a->T;
     return PWV_OK;
 }
 
 extern "C" int pwv_train_head_fwd_f32(const pwv_train_args* a, pwv_stream_t stream) {
     const char* who = "pwv_train_head_fwd_f32";
-    if (int e = train_check(a, who)) return e;
-    HeadParams p;
-    if (int e = head_params(a, who, p)) return e;
+    if (int e = head_check(a, who)) return e;
     PWV_CHECK_ARG(a->y, "%s: y is a NULL pointer", who);
-    hipLaunchKernelGGL(train_head_fwd_kernel, dim3(train_grid(a, (p.rows + 31) / 32)), dim3(kTrThreads), 0, (hipStream_t)stream, p);
-    PWV_CHECK_HIP(hipGetLastError());
-    return PWV_OK;
+    const HeadParams p = head_params(a, a->N * a->T);
+    return head_fwd_launch(train_head_fwd_kernel, p, train_grid(a, (p.rows + 31) / 32), (hipStream_t)stream);
 }
 
 extern "C" int pwv_train_head_bwd_f32(const pwv_train_args* a, pwv_stream_t stream) {
     const char* who = "pwv_train_head_bwd_f32";
-    if (int e = train_check(a, who)) return e;
-    HeadParams p;
-    if (int e = head_params(a, who, p)) return e;
+    if (int e = head_check(a, who)) return e;
     PWV_CHECK_ARG(a->d_out && a->d_o_out, "%s: d_out or d_o_out is a NULL pointer", who);
+    const HeadParams p = head_params(a, a->N * a->T);
     const int grid = train_grid(a, (p.rows + 31) / 32);
-    if (int e = train_check_ws(a, who, grid, kHeadPart)) return e;
-    hipLaunchKernelGGL(train_head_bwd_kernel, dim3(grid), dim3(kTrThreads), 0, (hipStream_t)stream, p);
-    PWV_CHECK_HIP(hipGetLastError());
-    ReduceParams rp;
-    rp.part = p.part; rp.n_part = grid; rp.stride = kHeadPart; rp.total = kHeadPart; rp.n_seg = 6;
-    int at = 0;
-    const int len[6] = {64 * 128, 128, 128 * 128, 128, 128, 1};
-    float* dst[6] = {a->d_skip, a->d_skip_bias, a->d_post1, a->d_post1_bias, a->d_post2, a->d_post2_bias};
-    for (int s = 0; s < 6; ++s) {
-        rp.seg[s].begin = at; rp.seg[s].end = at + len[s]; rp.seg[s].dst = dst[s]; rp.seg[s].dst2 = nullptr;
-        at += len[s];
-    }
-    return train_reduce(rp, (hipStream_t)stream);
+    if (int e = train_check_ws(a, who, grid, head_part<GatedIn, 1>())) return e;
+    return head_bwd_launch_and_reduce<GatedIn, 1>(train_head_bwd_kernel, p, grid, a, a->d_skip_bias, (hipStream_t)stream);
 }
 
 extern "C" int pwv_train_layer_bwd_f32(const pwv_train_args* a, pwv_stream_t stream) {

@@ -8,7 +8,7 @@
 // zero columns give zero tiles that are not written to the partial.
 #include "pwv_common.h"
 #include "pwv_hip_train_cond.h"
-#include "pwv_train_units.h"
+#include "pwv_train_head.h"
 
 namespace pwv {
 

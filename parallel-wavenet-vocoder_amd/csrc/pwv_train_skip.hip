@@ -2,16 +2,15 @@
 // architecture"): the head of a net reads S = sum_j (o_j skip_j + skip_bias_j) over ALL layers.  The layer kernels are the bodies of
 // pwv_train_units.h instantiated with the skip policy SumSkip, over the uniform and the packed geometry: the forward adds the unit's
 // o skip + skip_bias to S (tile32, 128 channels), the backward stages the unit's dS rows, adds dS skip^T to d o and accumulates
-// d skip = o^T dS in registers.  The head kernels are csrc/pwv_train.hip's without the o skip product in front: they begin at S and
-// end at dS and its column sums (every layer's d skip_bias).  The reduction of the partials is train_reduce_kernel's.
+// d skip = o^T dS in registers.  The head kernels are the one-output instances of csrc/pwv_train_head.h over its input policy SumIn:
+// they begin at S and end at dS and its column sums (every layer's d skip_bias).  The reduction of the partials is train_reduce_kernel's.
 #include "pwv_common.h"
 #include "pwv_hip_train_skip.h"
-#include "pwv_train_units.h"
+#include "pwv_train_head.h"
 
 namespace pwv {
 
 constexpr int kSkipLayerPart = kLayerPart + SumSkip::kPartFloats;             // dWfg | d dense | d dense_bias | d skip
-constexpr int kSkipHeadPart = 128 + 128 * 128 + 128 + 128 + 1;                // sum dS | d post1 | d b1 | d post2 | d b2
 constexpr int kSkipMaxPart = kSkipLayerPart > kMaxPart ? kSkipLayerPart : kMaxPart;
 
 template <class Geo>
@@ -27,103 +26,9 @@ __global__ __launch_bounds__(kTrThreads, 2) void train_skip_layer_bwd_kernel(Lay
     layer_bwd_body<Geo, ProjCond, LAST, SumSkip>(p, {}, sp);
 }
 
-struct SkipHeadParams {
-    const float *s, *post1, *post1_bias, *post2, *post2_bias;
-    float* y;                                   // forward
-    const float *d_out, *d_mul;                 // backward
-    float* d_s;
-    float* part;
-    int rows;
-};
+__global__ __launch_bounds__(kTrThreads) void train_skip_head_fwd_kernel(HeadParams p) { head_fwd_body<SumIn, 1>(p); }
 
-// h1 = relu(S), h2 = relu(h1 post1 + b1) of unit u
-__device__ __forceinline__ void skip_head_hidden(float* h1, float* h2, int u, const SkipHeadParams& p) {
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5;
-    tile32w_to_lds<true>(h1, kLdW, p.s, u, p.rows);
-    __syncthreads();
-    f32x16 acc = zero16();
-    gemm_xw<128>(acc, h1, kLdW, p.post1 + 32 * w, 128);
-    const float b = p.post1_bias ? p.post1_bias[32 * w + j] : 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) h2[acc_row(r, h) * kLdW + 32 * w + j] = fmaxf(acc[r] + b, 0.f);
-    __syncthreads();
-}
-
-__global__ __launch_bounds__(kTrThreads) void train_skip_head_fwd_kernel(SkipHeadParams p) {
-    __shared__ float h1[32 * kLdW];
-    __shared__ float h2[32 * kLdW];
-    const int units = (p.rows + 31) / 32;
-    for (int u = blockIdx.x; u < units; u += gridDim.x) {
-        skip_head_hidden(h1, h2, u, p);
-        // y[r] = h2[r] . post2 + b2: 8 lanes per row, 16 columns each, then a fixed tree over the 8
-        const int r = threadIdx.x >> 3, part = threadIdx.x & 7;
-        float s = 0.f;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) s += h2[r * kLdW + 16 * part + e] * p.post2[16 * part + e];
-        s += __shfl_xor(s, 1);
-        s += __shfl_xor(s, 2);
-        s += __shfl_xor(s, 4);
-        if (part == 0 && 32 * u + r < p.rows) p.y[32 * u + r] = s + (p.post2_bias ? p.post2_bias[0] : 0.f);
-        __syncthreads();
-    }
-}
-
-__global__ __launch_bounds__(kTrThreads) void train_skip_head_bwd_kernel(SkipHeadParams p) {
-    __shared__ float h1[32 * kLdW];             // h1, then dS
-    __shared__ float h2[32 * kLdW];             // h2, then dz2
-    __shared__ float dy[32];
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5;
-    const int units = (p.rows + 31) / 32;
-    f32x16 g_post1[4];
-#pragma unroll
-    for (int b = 0; b < 4; ++b) g_post1[b] = zero16();
-    float g_p2 = 0.f, g_b1 = 0.f, g_s = 0.f, g_b2 = 0.f;       // thread c < 128: column c; g_b2: thread 128
-    for (int u = blockIdx.x; u < units; u += gridDim.x) {
-        if (threadIdx.x < 32) {
-            const int row = 32 * u + threadIdx.x;
-            dy[threadIdx.x] = row < p.rows ? p.d_out[row] * (p.d_mul ? p.d_mul[row] : 1.f) : 0.f;
-        }
-        skip_head_hidden(h1, h2, u, p);         // (its barriers publish dy)
-        if (threadIdx.x < 128) {                // d post2, dz2 = dy post2^T where h2 > 0, d b1
-            const int c = threadIdx.x;
-            const float w2 = p.post2[c];
-            for (int r = 0; r < 32; ++r) {
-                const float v = h2[r * kLdW + c], z = v > 0.f ? dy[r] * w2 : 0.f;
-                g_p2 += v * dy[r];
-                g_b1 += z;
-                h2[r * kLdW + c] = z;
-            }
-        } else if (threadIdx.x == 128) {
-            for (int r = 0; r < 32; ++r) g_b2 += dy[r];
-        }
-        __syncthreads();
-        for (int b = 0; b < 4; ++b) gemm_tn(g_post1[b], h1, kLdW, 32 * b, h2, kLdW, 32 * w);      // d post1 += h1^T dz2
-        f32x16 acc = zero16();                  // dh1 = dz2 post1^T, columns 32 w ..
-        gemm_xwt<128>(acc, h2, kLdW, p.post1 + (size_t)32 * w * 128, 128);
-        __syncthreads();                        // every wave has read h1 as an operand
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            float* e = h1 + acc_row(r, h) * kLdW + 32 * w + j;
-            *e = *e > 0.f ? acc[r] : 0.f;       // dS = dh1 where S > 0
-        }
-        __syncthreads();
-        if (threadIdx.x < 128) {
-            const int c = threadIdx.x;
-            for (int r = 0; r < 32; ++r) g_s += h1[r * kLdW + c];
-        }
-        lds_to_tile32w(p.d_s, u, h1, kLdW, p.rows, 0);
-        __syncthreads();
-    }
-    float* part = p.part + (size_t)blockIdx.x * kSkipHeadPart;
-    for (int b = 0; b < 4; ++b) acc_to_part(g_post1[b], part + 128, 128, 32 * b, 32 * w);
-    if (threadIdx.x < 128) {
-        part[threadIdx.x] = g_s;
-        part[128 + 128 * 128 + threadIdx.x] = g_b1;
-        part[128 + 128 * 128 + 128 + threadIdx.x] = g_p2;
-    } else if (threadIdx.x == 128) {
-        part[kSkipHeadPart - 1] = g_b2;
-    }
-}
+__global__ __launch_bounds__(kTrThreads) void train_skip_head_bwd_kernel(HeadParams p) { head_bwd_body<SumIn, 1>(p); }
 
 // ------------------------------------------------------------------------------------------------------------------------------
 // host
@@ -187,14 +92,11 @@ static int skip_check_ws(const pwv_train_args* a, const char* who, int grid) {
     return PWV_OK;
 }
 
-static int skip_head_params(const pwv_train_skip_args* s, const char* who, const Geom& g, SkipHeadParams& p) {
-    const pwv_train_args* a = &s->train;
+static int skip_head_check(const pwv_train_skip_args* s, const char* who, Geom& g) {
+    PackedTables tab;
+    if (int e = skip_check(s, who, false, g, tab)) return e;
     PWV_CHECK_ARG(s->skip_sum, "%s: skip_sum is a NULL pointer", who);
-    PWV_CHECK_ARG(a->post1 && a->post2, "%s: post1 or post2 is a NULL pointer", who);
-    p = SkipHeadParams{};
-    p.s = s->skip_sum; p.post1 = a->post1; p.post1_bias = a->post1_bias; p.post2 = a->post2; p.post2_bias = a->post2_bias;
-    p.y = a->y; p.d_out = a->d_out; p.d_mul = a->d_mul; p.d_s = s->d_skip_sum_out; p.part = (float*)a->workspace;
-    p.rows = g.rows;
+    PWV_CHECK_ARG(s->train.post1 && s->train.post2, "%s: post1 or post2 is a NULL pointer", who);
     return PWV_OK;
 }
 
@@ -238,41 +140,23 @@ extern "C" int pwv_train_skip_layer_fwd_f32(const pwv_train_skip_args* s, pwv_st
 extern "C" int pwv_train_skip_head_fwd_f32(const pwv_train_skip_args* s, pwv_stream_t stream) {
     const char* who = "pwv_train_skip_head_fwd_f32";
     Geom g;
-    PackedTables tab;
-    if (int e = skip_check(s, who, false, g, tab)) return e;
-    SkipHeadParams p;
-    if (int e = skip_head_params(s, who, g, p)) return e;
-    PWV_CHECK_ARG(p.y, "%s: y is a NULL pointer", who);
+    if (int e = skip_head_check(s, who, g)) return e;
+    PWV_CHECK_ARG(s->train.y, "%s: y is a NULL pointer", who);
     const int grid = train_grid_size(s->train.max_workgroups, (g.rows + 31) / 32);
-    hipLaunchKernelGGL(train_skip_head_fwd_kernel, dim3(grid), dim3(kTrThreads), 0, (hipStream_t)stream, p);
-    PWV_CHECK_HIP(hipGetLastError());
-    return PWV_OK;
+    return head_fwd_launch(train_skip_head_fwd_kernel, head_params(&s->train, g.rows, s->skip_sum), grid, (hipStream_t)stream);
 }
 
 extern "C" int pwv_train_skip_head_bwd_f32(const pwv_train_skip_args* s, pwv_stream_t stream) {
     const char* who = "pwv_train_skip_head_bwd_f32";
     Geom g;
-    PackedTables tab;
-    if (int e = skip_check(s, who, false, g, tab)) return e;
-    SkipHeadParams p;
-    if (int e = skip_head_params(s, who, g, p)) return e;
+    if (int e = skip_head_check(s, who, g)) return e;
     const pwv_train_args* a = &s->train;
     PWV_CHECK_ARG(a->d_out, "%s: d_out is a NULL pointer", who);
     PWV_CHECK_ARG(s->d_skip_sum_out, "%s: d_skip_sum_out is a NULL pointer", who);
     const int grid = train_grid_size(a->max_workgroups, (g.rows + 31) / 32);
     if (int e = skip_check_ws(a, who, grid)) return e;
-    hipLaunchKernelGGL(train_skip_head_bwd_kernel, dim3(grid), dim3(kTrThreads), 0, (hipStream_t)stream, p);
-    PWV_CHECK_HIP(hipGetLastError());
-    ReduceParams rp;
-    rp.part = p.part; rp.n_part = grid; rp.stride = kSkipHeadPart; rp.total = kSkipHeadPart; rp.n_seg = 5;
-    int at = 0;
-    const int len[5] = {128, 128 * 128, 128, 128, 1};
-    float* dst[5] = {s->d_skip_bias, a->d_post1, a->d_post1_bias, a->d_post2, a->d_post2_bias};
-    for (int k = 0; k < 5; ++k) {
-        rp.seg[k].begin = at; rp.seg[k].end = at + len[k]; rp.seg[k].dst = dst[k]; rp.seg[k].dst2 = nullptr;
-        at += len[k];
-    }
-    return train_reduce(rp, (hipStream_t)stream);
+    const HeadParams p = head_params(a, g.rows, s->skip_sum, s->d_skip_sum_out);
+    return head_bwd_launch_and_reduce<SumIn, 1>(train_skip_head_bwd_kernel, p, grid, a, s->d_skip_bias, (hipStream_t)stream);
 }
 
 extern "C" int pwv_train_skip_layer_bwd_f32(const pwv_train_skip_args* s, pwv_stream_t stream) {

@@ -28,9 +28,7 @@ constexpr int kTrThreads = 256;
 constexpr int kLdW = 129;               // LDS row stride of a 128-column array (odd: a column walk over rows is conflict-free)
 constexpr int kLdH = 65;                // ... of a 64-column array
 constexpr int kLayerPart = 128 * 128 + 64 * 64 + 64;                       // dWfg | d dense | d dense_bias
-constexpr int kHeadPart = 64 * 128 + 128 + 128 * 128 + 128 + 128 + 1;      // d skip | d skip_bias | d post1 | d b1 | d post2 | d b2
 constexpr int kFrontPart = 128;                                            // d cf[0] | d cf[1]
-constexpr int kMaxPart = kHeadPart;
 
 struct Geom {
     int rows, T, d, dnext, hop, off, frames, pstride, dpstride, kmax;       // (T, frames: uniform batches)

@@ -30,6 +30,11 @@ ReLU and the projections P = frames [gc_filter | gc_gate] + [filter_bias | gate_
 the project's exact-fp32 GEMM (pwv_linear_f32: a row of P does not depend on the rows next to it); in torch (plumbing) their backward
 from the dP the kernels leave, the flow's affine out = in * s + b and the loss.
 
+The driver.  One _net_forward and one _net_backward serve every architecture and both head widths.  What differs between them is
+data on the _Geometry of the batch: the batch itself (_Uniform or _Packed), the conditioning (_Projected: P; _PerSample: the
+condition below) and the two architecture flags; its `front`, `layer` and `head` name the entry point of a call and fill its struct,
+and _call is the one place a training kernel is enqueued.
+
 Transposed-conv conditioning.  The condition changes every sample, so there is no P: the layer kernels of
 include/pwv_hip_train_cond.h form c[t] [gc_filter | gc_gate] + biases, the gradients of gc_* and of the biases, and d_cond inside the
 unit.  The three stride-4/4/5 stages run as linear_op(..., relu) on the re-laid-out [Cin, s C] weights (as models._condition does) and
@@ -199,202 +204,209 @@ def _tile32(rows, device):
     return torch.empty(((rows + 31) // 32) * 32 * 64, dtype=torch.float32, device=device)
 
 
-class _Geometry(object):
-    def __init__(self, N, T, t_mel, cols, max_workgroups):
-        self.N, self.T, self.rows, self.frames, self.cols = N, T, N * T, t_mel, cols
-        self.hop, self.off = hp.signal.hop_length, hp.signal.hop_length // 2
-        self.kmax = (self.hop + 30) // 32 + 1
-        self.max_workgroups = max_workgroups
+def _tile32w(rows, device):
+    return torch.empty(((rows + 31) // 32) * 32 * 128, dtype=torch.float32, device=device)
 
-    def _fill(self, a, kw):
-        for k, v in kw.items():
-            setattr(a, k, _ptr(v) if isinstance(v, torch.Tensor) else v)
-        return a
 
-    def args(self, **kw):
-        return self._fill(_lib.TrainArgs(N=self.N, T=self.T, cond_hop=self.hop, cond_offset=self.off, cond_frames=self.frames,
-                                         proj_row_stride=self.cols, d_proj_row_stride=self.cols, max_workgroups=self.max_workgroups,
-                                         dilation=1, next_dilation=1), kw)
+def _fill(a, kw):
+    """Set the fields `kw` of the struct `a`, tensors as their addresses (a struct with an embedded pwv_train_args routes the names)."""
+    kw = {k: _ptr(v) if isinstance(v, torch.Tensor) else v for k, v in kw.items()}
+    if isinstance(a, _lib.EmbedsTrainArgs):
+        return a.set(**kw)
+    for k, v in kw.items():
+        setattr(a, k, v)
+    return a
 
-    head_args = args                        # the head is row-independent: the same call for either geometry
 
-    shared = False                          # True: one net per flow with two outputs; its heads are the calls of shared_head_args
+class _Uniform(object):
+    """A uniform batch [N, T] with `frames` condition frames per utterance (include/pwv_hip_train.h)."""
+    prefix = 'pwv_train_'
 
-    def shared_head_args(self, head_in, **kw):
-        """The two-output head's struct (include/pwv_hip_train_shared.h): the uniform struct in front -- row-local, so a packed batch is
-        N = 1, T = rows --, then the input mode and the new fields."""
-        base = _Geometry.args(self)
-        a = _lib.TrainSharedArgs()
-        ctypes.memmove(ctypes.addressof(a.train), ctypes.addressof(base), ctypes.sizeof(_lib.TrainArgs))
-        a.train.struct_size = ctypes.sizeof(_lib.TrainSharedArgs)
-        return a.set(head_in=head_in, **{k: _ptr(v) if isinstance(v, torch.Tensor) else v for k, v in kw.items()})
+    def __init__(self, N, T, frames):
+        self.N, self.T, self.rows, self.frames = N, T, N * T, frames
 
-    def shared_workspace_bytes(self):
-        return (_lib.lib().pwv_train_shared_workspace_bytes(ctypes.byref(self.shared_head_args(_lib.TRAIN_HEAD_IN_GATED))),
-                'pwv_train_shared_workspace_bytes')
+    def tables(self):
+        return {}
 
-    def layer_args(self, **kw):
-        """The layers' struct: the front's, but for a per-sample condition."""
-        return self.args(**kw)
+    def args(self, **common):
+        return _lib.TrainArgs(N=self.N, T=self.T, cond_frames=self.frames, **common)
 
-    def entry(self, kind):
-        """The entry point of 'front_fwd', 'layer_fwd', 'layer_bwd' or 'front_bwd' for this geometry."""
-        return 'pwv_train_%s_f32' % kind
 
-    def workspace_bytes(self):
-        return _lib.lib().pwv_train_workspace_bytes(ctypes.byref(self.head_args())), 'pwv_train_workspace_bytes'
+class _Packed(object):
+    """A packed batch (include/pwv_hip_train_varlen.h): `layout` an engine.VarlenGeometry.  The entry points that depend on where an
+    utterance begins take the device tables; to a row-local call (the head, the workspace) the batch is uniform at N = 1, T = rows."""
+    prefix = 'pwv_train_varlen_'
 
-    def cond_fwd(self, net, j, v):
-        """What a layer's forward call reads of the conditioning: this layer's 128 columns of P."""
+    def __init__(self, layout):
+        self.layout = layout
+        self.N, self.T, self.rows, self.frames = 1, layout.rows, layout.rows, layout.total_frames
+
+    def tables(self):
+        g = self.layout
+        return dict(cu_rows=_ptr(g.cu_rows), cu_frames=_ptr(g.cu_frames), n=g.n, rows=g.rows, proj_rows=g.total_frames)
+
+    def args(self, **common):
+        return _lib.TrainVarlenArgs(**common, **self.tables())
+
+
+class _Projected(object):
+    """Conditioning at frame rate: a layer reads its 128 columns of the projection `P` and fills its slots of dP."""
+    per_sample = False
+    P = None
+
+    def fwd(self, net, j, v):
+        """What a layer's forward call reads of the conditioning."""
         return dict(proj=self.P[0, net.col + 128 * j:])
 
-    def cond_bwd(self, net, j, v, dP, g, opt):
+    def bwd(self, net, j, v, dP, g, opt):
         """... and its backward call: P, and the dP slots it fills."""
         return dict(proj=self.P[0, net.col + 128 * j:], d_proj=dP[0, net.col + 128 * j:])
 
 
-class _PackedGeometry(_Geometry):
-    """A packed batch (include/pwv_hip_train_varlen.h): `layout` an engine.VarlenGeometry.  The four entry points that depend on where
-    an utterance begins take the device tables; the head and the workspace are the uniform ones at N = 1, T = rows."""
-
-    def __init__(self, layout, cols, max_workgroups):
-        super().__init__(1, layout.rows, layout.total_frames, cols, max_workgroups)
-        self.layout = layout
-
-    def args(self, **kw):
-        g = self.layout
-        return self._fill(_lib.TrainVarlenArgs(cond_hop=self.hop, cond_offset=self.off, proj_row_stride=self.cols, d_proj_row_stride=self.cols,
-                                               max_workgroups=self.max_workgroups, dilation=1, next_dilation=1, cu_rows=_ptr(g.cu_rows),
-                                               cu_frames=_ptr(g.cu_frames), n=g.n, rows=g.rows, proj_rows=g.total_frames), kw)
-
-    def head_args(self, **kw):
-        return _Geometry.args(self, **kw)
-
-    def entry(self, kind):
-        return 'pwv_train_varlen_%s_f32' % kind
-
-
-class _CondGeometry(_Geometry):
-    """A uniform batch with a per-sample condition (include/pwv_hip_train_cond.h): the layer calls read `cond`, the uncropped
+class _PerSample(object):
+    """A per-sample condition on a uniform batch (include/pwv_hip_train_cond.h): the layer calls read `cond`, the uncropped
     [N, T + hop, C] output of the last transposed-conv stage, through a row offset of hop / 2, and add to `d_cond` of the same shape
     (zeros to begin with: its margins are the crop's adjoint).  The front, the head and the loss are the uniform ones."""
+    per_sample = True
 
-    def __init__(self, N, T, C, max_workgroups):
-        super().__init__(N, T, 0, 0, max_workgroups)         # no frames, no P: nothing here is at frame rate
+    def __init__(self, C):
         self.C = C
         self.cond = self.d_cond = None
         self.started = 0                    # the first layer backward of a step writes its rows of d_cond, the others add
 
-    def set_cond(self, cond):
-        assert tuple(cond.shape) == (self.N, self.T + self.hop, self.C) and cond.is_contiguous()
+    def set(self, cond):
+        assert cond.is_contiguous()
         self.cond, self.d_cond, self.started = cond, torch.zeros_like(cond), 0
 
-    def layer_args(self, **kw):
-        skip = self.off * self.C * 4        # bytes to sample 0 of utterance 0
-        return self._fill(_lib.TrainCondArgs(N=self.N, T=self.T, max_workgroups=self.max_workgroups, dilation=1, next_dilation=1,
-                                             cond=self.cond.data_ptr() + skip, d_cond=self.d_cond.data_ptr() + skip, cond_channels=self.C,
-                                             cond_row_stride=self.C, cond_utt_rows=self.T + self.hop), kw)
+    def args(self, geo):
+        skip = geo.off * self.C * 4         # bytes to sample 0 of utterance 0
+        return _lib.TrainCondArgs(N=geo.N, T=geo.T, max_workgroups=geo.max_workgroups, dilation=1, next_dilation=1,
+                                  cond=self.cond.data_ptr() + skip, d_cond=self.d_cond.data_ptr() + skip, cond_channels=self.C,
+                                  cond_row_stride=self.C, cond_utt_rows=geo.T + geo.hop)
 
-    def entry(self, kind):
-        return 'pwv_train_cond_%s_f32' % kind if kind.startswith('layer') else 'pwv_train_%s_f32' % kind
-
-    def workspace_bytes(self):
-        return _lib.lib().pwv_train_cond_workspace_bytes(ctypes.byref(self.layer_args())), 'pwv_train_cond_workspace_bytes'
-
-    def cond_fwd(self, net, j, v):
+    def fwd(self, net, j, v):
         return dict(gc_filter=v['gc_filter'], gc_gate=v['gc_gate'], filter_bias=v.get('filter_bias'), gate_bias=v.get('gate_bias'))
 
-    def cond_bwd(self, net, j, v, dP, g, opt):
-        kw = dict(self.cond_fwd(net, j, v), d_gc_filter=g(net.name(j, 'gc_filter'), v['gc_filter']),
+    def bwd(self, net, j, v, dP, g, opt):
+        kw = dict(self.fwd(net, j, v), d_gc_filter=g(net.name(j, 'gc_filter'), v['gc_filter']),
                   d_gc_gate=g(net.name(j, 'gc_gate'), v['gc_gate']), d_filter_bias=opt(v, 'filter_bias', net.name(j, 'filter_bias')),
                   d_gate_bias=opt(v, 'gate_bias', net.name(j, 'gate_bias')), d_cond_accumulate=self.started)
         self.started = 1
         return kw
 
 
-class _Skip(object):
-    """The skip-connection architecture over a uniform or a packed geometry (include/pwv_hip_train_skip.h): the layer and head calls
-    take pwv_train_skip_args -- the geometry's own struct in front, the packed tables copied behind it --, the front calls and the
-    loss stay the geometry's."""
-    skip = True
+class _Geometry(object):
+    """Which entry point a call of a batch goes to and the struct it takes: `batch` a _Uniform or a _Packed, `cond` a _Projected (`cols`
+    the columns of P) or a _PerSample, `skip` the skip-connection architecture (include/pwv_hip_train_skip.h: its layer and head calls
+    take pwv_train_skip_args -- the batch's own struct in front, the packed tables copied behind it), `shared` one net per flow with
+    two outputs (include/pwv_hip_train_shared.h: its head calls take pwv_train_shared_args -- the uniform struct in front, row-local).
+    `front`, `layer` and `head` return (entry point, filled struct): the arguments of _call."""
 
-    def layer_args(self, **kw):
-        base = self.args()
-        a = _lib.TrainSkipArgs()
-        ctypes.memmove(ctypes.addressof(a.train), ctypes.addressof(base), ctypes.sizeof(_lib.TrainArgs))
-        a.train.struct_size = ctypes.sizeof(_lib.TrainSkipArgs)
-        if isinstance(base, _lib.TrainVarlenArgs):
-            a.set(cu_rows=base.cu_rows, cu_frames=base.cu_frames, n=base.n, rows=base.rows, proj_rows=base.proj_rows)
-        return a.set(**{k: _ptr(v) if isinstance(v, torch.Tensor) else v for k, v in kw.items()})
+    def __init__(self, batch, cond, cols, max_workgroups, skip=False, shared=False):
+        self.batch, self.cond, self.cols, self.max_workgroups, self.skip, self.shared = batch, cond, cols, max_workgroups, skip, shared
+        self.N, self.T, self.rows, self.frames = batch.N, batch.T, batch.rows, batch.frames
+        self.hop, self.off = hp.signal.hop_length, hp.signal.hop_length // 2
+        self.kmax = (self.hop + 30) // 32 + 1
 
-    head_args = layer_args
+    def _common(self):
+        return dict(cond_hop=self.hop, cond_offset=self.off, proj_row_stride=self.cols, d_proj_row_stride=self.cols,
+                    max_workgroups=self.max_workgroups, dilation=1, next_dilation=1)
 
-    def entry(self, kind):
-        return 'pwv_train_skip_%s_f32' % kind if kind.startswith('layer') else super().entry(kind)
+    def _row_local(self):
+        return _lib.TrainArgs(N=self.N, T=self.T, cond_frames=self.frames, **self._common())
 
-    def workspace_bytes(self):
-        return _lib.lib().pwv_train_skip_workspace_bytes(ctypes.byref(self.layer_args())), 'pwv_train_skip_workspace_bytes'
+    def _skip_args(self):
+        return _lib.TrainSkipArgs(**self.batch.tables()).embed(self.batch.args(**self._common()))
+
+    def front(self, kind, **kw):
+        """'front_fwd' or 'front_bwd'."""
+        return '%s%s_f32' % (self.batch.prefix, kind), _fill(self.batch.args(**self._common()), kw)
+
+    def layer(self, kind, **kw):
+        """'layer_fwd' or 'layer_bwd'."""
+        if self.skip:
+            return 'pwv_train_skip_%s_f32' % kind, _fill(self._skip_args(), kw)
+        if self.cond.per_sample:
+            return 'pwv_train_cond_%s_f32' % kind, _fill(self.cond.args(self), kw)
+        return self.front(kind, **kw)
+
+    def head(self, kind, **kw):
+        """'fwd' or 'bwd' of the head, which is row-independent: the same call for either batch."""
+        if self.shared:
+            head_in = _lib.TRAIN_HEAD_IN_SKIPSUM if self.skip else _lib.TRAIN_HEAD_IN_GATED
+            return 'pwv_train_shared_head_%s_f32' % kind, _fill(_lib.TrainSharedArgs(head_in=head_in).embed(self._row_local()), kw)
+        if self.skip:
+            return 'pwv_train_skip_head_%s_f32' % kind, _fill(self._skip_args(), kw)
+        return 'pwv_train_head_%s_f32' % kind, _fill(self._row_local(), kw)
+
+    def workspace(self, device):
+        """The workspace of every weight-gradient reduction of the batch: the largest any of its calls asks for."""
+        if self.skip:
+            asks = [('pwv_train_skip_workspace_bytes', self._skip_args())]
+        elif self.cond.per_sample:
+            asks = [('pwv_train_cond_workspace_bytes', self.cond.args(self))]
+        else:
+            asks = [('pwv_train_workspace_bytes', self._row_local())]
+        if self.shared:                     # the two-output head's partial is the larger one
+            asks.append(('pwv_train_shared_workspace_bytes', self.head('fwd')[1]))
+        need = 0
+        for name, a in asks:
+            got = getattr(_lib.lib(), name)(ctypes.byref(a))
+            if not got:
+                _lib.check(-1, name)
+            need = max(need, got)
+        return torch.empty(need // 4, dtype=torch.float32, device=device)
 
 
-class _SkipGeometry(_Skip, _Geometry):
-    pass
-
-
-class _SkipPackedGeometry(_Skip, _PackedGeometry):
-    pass
-
-
-def _tile32w(rows, device):
-    return torch.empty(((rows + 31) // 32) * 32 * 128, dtype=torch.float32, device=device)
-
-
-def _net_forward_skip(net: _Net, geo: _Geometry, xin):
-    """The skip-connection architecture: x_j for every layer, the net's skip sum S and its output y [rows].  Layer 0 writes S, every
-    other layer adds to it in stream order; the last layer has no dense product and leaves no o."""
+def _net_forward(net: _Net, geo: _Geometry, xin):
+    """x_j for every layer, the head's input and the net's output y [rows] ([2, rows] of a shared net: the scale plane, the shift
+    plane).  The head's input is the last layer's o -- or, under skip connections, the net's skip sum S: layer 0 writes it, every other
+    layer adds to it in stream order, and the last layer has no dense product and leaves no o."""
     dev, L = xin.device, len(net.dilations)
     xs = [_tile32(geo.rows, dev) for _ in range(L)]
-    S, y = _tile32w(geo.rows, dev), torch.empty(geo.rows, dtype=torch.float32, device=dev)
-    _call(geo.entry('front_fwd'), geo.args(in_=xin, causal_filter=net.cf, x_out=xs[0]))
+    hin = (_tile32w if geo.skip else _tile32)(geo.rows, dev)
+    y = torch.empty((2, geo.rows) if geo.shared else geo.rows, dtype=torch.float32, device=dev)
+    _call(*geo.front('front_fwd', in_=xin, causal_filter=net.cf, x_out=xs[0]))
     for j, d in enumerate(net.dilations):
         v, last = net.layers[j], j == L - 1
-        _call(geo.entry('layer_fwd'), geo.layer_args(form=_lib.TRAIN_LAST if last else _lib.TRAIN_RESIDUAL, dilation=d, x=xs[j],
-                                                       filter=v['filter'], gate=v['gate'], dense=None if last else v['dense'],
-                                                       dense_bias=None if last else v.get('dense_bias'), x_out=None if last else xs[j + 1],
-                                                       skip=v['skip'], skip_bias=v.get('skip_bias'), skip_sum=S, skip_accumulate=int(j > 0),
-                                                       **geo.cond_fwd(net, j, v)))
-    h = net.head
-    if geo.shared:                          # two outputs: y = [scale plane, shift plane]
-        y = torch.empty((2, geo.rows), dtype=torch.float32, device=dev)
-        _call('pwv_train_shared_head_fwd_f32', geo.shared_head_args(
-            _lib.TRAIN_HEAD_IN_SKIPSUM, skip_sum=S, post1=h['postprocess1'], post1_bias=h.get('postprocess1_bias'), post2=h['postprocess2'],
-            post2_bias=h.get('postprocess2_bias'), y=y[0], y_shift=y[1]))
-        return xs, S, y
-    _call('pwv_train_skip_head_fwd_f32', geo.head_args(skip_sum=S, post1=h['postprocess1'], post1_bias=h.get('postprocess1_bias'),
-                                                       post2=h['postprocess2'], post2_bias=h.get('postprocess2_bias'), y=y))
-    return xs, S, y
+        dense = not (last and geo.skip)
+        x_out = (None if geo.skip else hin) if last else xs[j + 1]
+        skip = dict(skip=v['skip'], skip_bias=v.get('skip_bias'), skip_sum=hin, skip_accumulate=int(j > 0)) if geo.skip else {}
+        _call(*geo.layer('layer_fwd', form=_lib.TRAIN_LAST if last else _lib.TRAIN_RESIDUAL, dilation=d, x=xs[j], filter=v['filter'],
+                         gate=v['gate'], dense=v['dense'] if dense else None, dense_bias=v.get('dense_bias') if dense else None,
+                         x_out=x_out, **skip, **geo.cond.fwd(net, j, v)))
+    h, lv = net.head, net.layers[-1]
+    front = dict(skip_sum=hin) if geo.skip else dict(x=hin, skip=lv['skip'], skip_bias=lv.get('skip_bias'))
+    out = dict(y=y[0], y_shift=y[1]) if geo.shared else dict(y=y)
+    _call(*geo.head('fwd', post1=h['postprocess1'], post1_bias=h.get('postprocess1_bias'), post2=h['postprocess2'],
+                    post2_bias=h.get('postprocess2_bias'), **front, **out))
+    return xs, hin, y
 
 
-def _net_backward_skip(net: _Net, geo: _Geometry, saved, xin, d_out, d_mul, scale, d_in, accumulate, dP, ws, grads):
-    """_net_backward for the skip-connection architecture: the head leaves dS and its column sums, which are every layer's
-    d skip_bias; every layer takes dS skip^T into its d o and leaves its d skip."""
-    xs, S, _ = saved
+def _net_backward(net: _Net, geo: _Geometry, saved, xin, d_out, d_mul, scale, d_in, accumulate, dP, ws, grads):
+    """The net's share of the gradients into `grads`, of dP and of d_in.  Under skip connections the head leaves dS and its column
+    sums, which are every layer's d skip_bias; every layer takes dS skip^T into its d o and leaves its d skip."""
+    xs, hin, _ = saved
     dev, L = xin.device, len(net.dilations)
     g = lambda name, like: grads.setdefault(name, torch.empty_like(like))
-    h = net.head
+    h, lv = net.head, net.layers[-1]
     hp_ = net.scope + '/postprocessing/'
     opt = lambda d, key, name: g(name, d[key]) if key in d else None
-    dS = _tile32w(geo.rows, dev)
-    biased = [j for j in range(L) if 'skip_bias' in net.layers[j]]
-    sums = torch.empty(128, dtype=torch.float32, device=dev) if biased else None
-    head_bwd, head_args = (('pwv_train_shared_head_bwd_f32', lambda **kw: geo.shared_head_args(_lib.TRAIN_HEAD_IN_SKIPSUM, **kw)) if geo.shared
-                           else ('pwv_train_skip_head_bwd_f32', geo.head_args))
-    _call(head_bwd, head_args(
-        skip_sum=S, d_out=d_out, d_mul=d_mul, post1=h['postprocess1'], post1_bias=h.get('postprocess1_bias'), post2=h['postprocess2'],
-        post2_bias=h.get('postprocess2_bias'), d_skip_sum_out=dS, d_skip_bias=sums,
+    d_hin = torch.empty_like(hin)           # d o, or dS
+    if geo.skip:
+        biased = [j for j in range(L) if 'skip_bias' in net.layers[j]]
+        sums = torch.empty(128, dtype=torch.float32, device=dev) if biased else None
+        front = dict(skip_sum=hin, d_skip_sum_out=d_hin, d_skip_bias=sums)
+    else:
+        front = dict(x=hin, skip=lv['skip'], skip_bias=lv.get('skip_bias'), d_o_out=d_hin, d_skip=g(net.name(L - 1, 'skip'), lv['skip']),
+                     d_skip_bias=opt(lv, 'skip_bias', net.name(L - 1, 'skip_bias')))
+    _call(*geo.head(
+        'bwd', d_out=d_out, d_mul=d_mul, post1=h['postprocess1'], post1_bias=h.get('postprocess1_bias'), post2=h['postprocess2'],
+        post2_bias=h.get('postprocess2_bias'), **front,
         d_post1=g(hp_ + 'postprocess1', h['postprocess1']), d_post1_bias=opt(h, 'postprocess1_bias', hp_ + 'postprocess1_bias'),
         d_post2=g(hp_ + 'postprocess2', h['postprocess2']), d_post2_bias=opt(h, 'postprocess2_bias', hp_ + 'postprocess2_bias'),
         workspace=ws, workspace_bytes=ws.numel() * 4))
-    if biased:
+    if geo.skip and biased:
         copies = sums.repeat(len(biased), 1)                                            # one launch: the same bits for every layer
         for k, j in enumerate(biased):
             grads[net.name(j, 'skip_bias')] = copies[k]
@@ -402,80 +414,22 @@ def _net_backward_skip(net: _Net, geo: _Geometry, saved, xin, d_out, d_mul, scal
     for j in range(L - 1, -1, -1):
         v, last = net.layers[j], j == L - 1
         u_next, v_next = (None, None) if last else uv[(j + 1) & 1]
-        _call(geo.entry('layer_bwd'), geo.layer_args(
-            form=_lib.TRAIN_LAST if last else _lib.TRAIN_RESIDUAL, dilation=net.dilations[j],
+        if geo.skip:
+            skip = dict(dense=None if last else v['dense'], skip=v['skip'], d_skip_sum=d_hin, d_skip=g(net.name(j, 'skip'), v['skip']))
+        else:
+            skip = dict(dense=v['dense'], d_o=d_hin if last else None)
+        _call(*geo.layer(
+            'layer_bwd', form=_lib.TRAIN_LAST if last else _lib.TRAIN_RESIDUAL, dilation=net.dilations[j],
             next_dilation=1 if last else net.dilations[j + 1], x=xs[j],
-            filter=v['filter'], gate=v['gate'], dense=None if last else v['dense'], u_next=u_next, v_next=v_next,
-            skip=v['skip'], d_skip_sum=dS, d_skip=g(net.name(j, 'skip'), v['skip']),
-            u=uv[j & 1][0], v=uv[j & 1][1], **geo.cond_bwd(net, j, v, dP, g, opt),
+            filter=v['filter'], gate=v['gate'], u_next=u_next, v_next=v_next, **skip,
+            u=uv[j & 1][0], v=uv[j & 1][1], **geo.cond.bwd(net, j, v, dP, g, opt),
             d_filter=g(net.name(j, 'filter'), v['filter']), d_gate=g(net.name(j, 'gate'), v['gate']),
             d_dense=None if last else g(net.name(j, 'dense'), v['dense']),
             d_dense_bias=None if last else opt(v, 'dense_bias', net.name(j, 'dense_bias')),
             workspace=ws, workspace_bytes=ws.numel() * 4))
-    _call(geo.entry('front_bwd'), geo.args(
-        in_=xin, causal_filter=net.cf, u_next=uv[0][0], v_next=uv[0][1], next_dilation=net.dilations[0], d_out=d_out, scale=scale,
-        d_in=d_in, accumulate=int(accumulate), d_causal_filter=g(net.scope + '/causal_layer/filter', net.cf),
-        workspace=ws, workspace_bytes=ws.numel() * 4))
-
-
-def _net_forward(net: _Net, geo: _Geometry, xin):
-    """x_j for every layer, the last layer's o and the net's output y [rows]."""
-    dev, L = xin.device, len(net.dilations)
-    xs = [_tile32(geo.rows, dev) for _ in range(L)]
-    o, y = _tile32(geo.rows, dev), torch.empty(geo.rows, dtype=torch.float32, device=dev)
-    _call(geo.entry('front_fwd'), geo.args(in_=xin, causal_filter=net.cf, x_out=xs[0]))
-    for j, d in enumerate(net.dilations):
-        v, last = net.layers[j], j == L - 1
-        _call(geo.entry('layer_fwd'), geo.layer_args(form=_lib.TRAIN_LAST if last else _lib.TRAIN_RESIDUAL, dilation=d, x=xs[j],
-                                                       filter=v['filter'], gate=v['gate'], dense=v['dense'], dense_bias=v.get('dense_bias'),
-                                                       x_out=o if last else xs[j + 1], **geo.cond_fwd(net, j, v)))
-    h, lv = net.head, net.layers[-1]
-    if geo.shared:                          # two outputs: y = [scale plane, shift plane]
-        y = torch.empty((2, geo.rows), dtype=torch.float32, device=dev)
-        _call('pwv_train_shared_head_fwd_f32', geo.shared_head_args(
-            _lib.TRAIN_HEAD_IN_GATED, x=o, skip=lv['skip'], skip_bias=lv.get('skip_bias'), post1=h['postprocess1'],
-            post1_bias=h.get('postprocess1_bias'), post2=h['postprocess2'], post2_bias=h.get('postprocess2_bias'), y=y[0], y_shift=y[1]))
-        return xs, o, y
-    _call('pwv_train_head_fwd_f32', geo.head_args(x=o, skip=lv['skip'], skip_bias=lv.get('skip_bias'), post1=h['postprocess1'],
-                                            post1_bias=h.get('postprocess1_bias'), post2=h['postprocess2'],
-                                            post2_bias=h.get('postprocess2_bias'), y=y))
-    return xs, o, y
-
-
-def _net_backward(net: _Net, geo: _Geometry, saved, xin, d_out, d_mul, scale, d_in, accumulate, dP, ws, grads):
-    """The net's share of the gradients into `grads`, of dP and of d_in."""
-    xs, o, _ = saved
-    dev, L = xin.device, len(net.dilations)
-    g = lambda name, like: grads.setdefault(name, torch.empty_like(like))
-    h, lv = net.head, net.layers[-1]
-    hp_ = net.scope + '/postprocessing/'
-    opt = lambda d, key, name: g(name, d[key]) if key in d else None
-    d_o = _tile32(geo.rows, dev)
-    head_bwd, head_args = (('pwv_train_shared_head_bwd_f32', lambda **kw: geo.shared_head_args(_lib.TRAIN_HEAD_IN_GATED, **kw)) if geo.shared
-                           else ('pwv_train_head_bwd_f32', geo.head_args))
-    _call(head_bwd, head_args(
-        x=o, d_out=d_out, d_mul=d_mul, skip=lv['skip'], skip_bias=lv.get('skip_bias'), post1=h['postprocess1'],
-        post1_bias=h.get('postprocess1_bias'), post2=h['postprocess2'], post2_bias=h.get('postprocess2_bias'), d_o_out=d_o,
-        d_skip=g(net.name(L - 1, 'skip'), lv['skip']), d_skip_bias=opt(lv, 'skip_bias', net.name(L - 1, 'skip_bias')),
-        d_post1=g(hp_ + 'postprocess1', h['postprocess1']), d_post1_bias=opt(h, 'postprocess1_bias', hp_ + 'postprocess1_bias'),
-        d_post2=g(hp_ + 'postprocess2', h['postprocess2']), d_post2_bias=opt(h, 'postprocess2_bias', hp_ + 'postprocess2_bias'),
-        workspace=ws, workspace_bytes=ws.numel() * 4))
-    uv = [(_tile32(geo.rows, dev), _tile32(geo.rows, dev)) for _ in range(2)]
-    for j in range(L - 1, -1, -1):
-        v, last = net.layers[j], j == L - 1
-        u_next, v_next = (None, None) if last else uv[(j + 1) & 1]
-        _call(geo.entry('layer_bwd'), geo.layer_args(
-            form=_lib.TRAIN_LAST if last else _lib.TRAIN_RESIDUAL, dilation=net.dilations[j],
-            next_dilation=1 if last else net.dilations[j + 1], x=xs[j],
-            filter=v['filter'], gate=v['gate'], dense=v['dense'], u_next=u_next, v_next=v_next, d_o=d_o if last else None,
-            u=uv[j & 1][0], v=uv[j & 1][1], **geo.cond_bwd(net, j, v, dP, g, opt),
-            d_filter=g(net.name(j, 'filter'), v['filter']), d_gate=g(net.name(j, 'gate'), v['gate']),
-            d_dense=None if last else g(net.name(j, 'dense'), v['dense']),
-            d_dense_bias=None if last else opt(v, 'dense_bias', net.name(j, 'dense_bias')),
-            workspace=ws, workspace_bytes=ws.numel() * 4))
-    _call(geo.entry('front_bwd'), geo.args(
-        in_=xin, causal_filter=net.cf, u_next=uv[0][0], v_next=uv[0][1], next_dilation=net.dilations[0], d_out=d_out, scale=scale,
-        d_in=d_in, accumulate=int(accumulate), d_causal_filter=g(net.scope + '/causal_layer/filter', net.cf),
+    _call(*geo.front(
+        'front_bwd', in_=xin, causal_filter=net.cf, u_next=uv[0][0], v_next=uv[0][1], next_dilation=net.dilations[0], d_out=d_out,
+        scale=scale, d_in=d_in, accumulate=int(accumulate), d_causal_filter=g(net.scope + '/causal_layer/filter', net.cf),
         workspace=ws, workspace_bytes=ws.numel() * 4))
 
 
@@ -565,11 +519,11 @@ def loss_and_grad(model, wav, melspec, z=None, seed=None, max_workgroups: int = 
             raise ValueError('z must be [%d, %d, 1], got %s' % (N, T, tuple(noise.shape)))
     flows = model_nets(model, store)
     cols = sum(128 * len(net.dilations) for pair in flows for net in pair)
-    if hp.model.cond_upsample_method == 'transposed_conv':
-        geo = _CondGeometry(N, T, int(hp.model.condition_channels), int(max_workgroups))
+    if hp.model.cond_upsample_method == 'transposed_conv':      # no frames, no P: nothing there is at frame rate
+        batch, cond, cols = _Uniform(N, T, 0), _PerSample(int(hp.model.condition_channels)), 0
     else:
-        geo = (_SkipGeometry if use_skip_connection else _Geometry)(N, T, t_mel, cols, int(max_workgroups))
-    geo.shared = bool(shared_nets)
+        batch, cond = _Uniform(N, T, t_mel), _Projected()
+    geo = _Geometry(batch, cond, cols, int(max_workgroups), skip=bool(use_skip_connection), shared=bool(shared_nets))
 
     loss, x, grads = _forward_backward(store, flows, geo, melspec.reshape(N * t_mel, n_mels), noise.reshape(N * T).contiguous(),
                                        wav.reshape(N * T), _head((N, T), N * T, power_weight, terms))
@@ -612,7 +566,7 @@ def _forward_backward(store, flows, geo, mel2, x, y, head):
     dev = mel2.device
     nets = [net for pair in flows for net in pair]
     cols = geo.cols
-    per_sample = isinstance(geo, _CondGeometry)
+    per_sample = geo.cond.per_sample
 
     # frame rate, forward: frames = relu(mel dense); P = frames [gc_filter | gc_gate] + [filter_bias | gate_bias] for every net-layer.
     # Both products run on the project's exact-fp32 GEMM (pwv_linear_f32), whose sum over K has one order whatever the number of rows:
@@ -622,30 +576,21 @@ def _forward_backward(store, flows, geo, mel2, x, y, head):
     zeros64 = torch.zeros(64, dtype=torch.float32, device=dev)
     mel2 = mel2.contiguous()
     if per_sample:
-        stages = _tconv_forward(store, mel2, geo.C)
-        geo.set_cond(stages[-1][2].reshape(geo.N, geo.T + geo.hop, geo.C))          # uncropped: the kernels skip hop / 2 rows themselves
+        stages = _tconv_forward(store, mel2, geo.cond.C)
+        geo.cond.set(stages[-1][2].reshape(geo.N, geo.T + geo.hop, geo.cond.C))          # uncropped: the kernels skip hop / 2 rows themselves
     else:
         dense = cond_dense(store)
         frames = engine.linear_op(mel2, dense[0].contiguous(), None, True, 'f32')
         bank_w = torch.cat([v[k][0] for net in nets for v in net.layers for k in ('gc_filter', 'gc_gate')], dim=1)          # [C, cols]
         bank_b = torch.cat([v.get(k, zeros64) for net in nets for v in net.layers for k in ('filter_bias', 'gate_bias')])
-        geo.P = engine.linear_op(frames, bank_w, bank_b, False, 'f32')                                                     # [M, cols]
+        geo.cond.P = engine.linear_op(frames, bank_w, bank_b, False, 'f32')                                                     # [M, cols]
 
     # sample rate, forward
-    ws_bytes, ws_name = geo.workspace_bytes()
-    if not ws_bytes:
-        _lib.check(-1, ws_name)
-    if geo.shared:                          # the two-output head's partial is the larger one
-        assert all(len(pair) == 1 for pair in flows)
-        more, more_name = geo.shared_workspace_bytes()
-        if not more:
-            _lib.check(-1, more_name)
-        ws_bytes = max(ws_bytes, more)
-    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=dev)
+    assert all(len(pair) == (1 if geo.shared else 2) for pair in flows)
+    ws = geo.workspace(dev)
     saved = []
-    net_forward, net_backward = (_net_forward_skip, _net_backward_skip) if getattr(geo, 'skip', False) else (_net_forward, _net_backward)
     for pair in flows:
-        s = [net_forward(net, geo, x) for net in pair]
+        s = [_net_forward(net, geo, x) for net in pair]
         saved.append((x, s))
         if geo.shared:
             x = x * s[0][2][0] + s[0][2][1]                                             # SharedIAFLayer: out = x y[..., 0] + y[..., 1]
@@ -656,21 +601,21 @@ def _forward_backward(store, flows, geo, mel2, x, y, head):
     # sample rate, backward
     grads: Dict[str, torch.Tensor] = {}
     M = mel2.shape[0]
-    # K slots per P row (include/pwv_hip_train.h); a per-sample condition has no P: its layers add to geo.d_cond instead
+    # K slots per P row (include/pwv_hip_train.h); a per-sample condition has no P: its layers add to geo.cond.d_cond instead
     dP = None if per_sample else torch.zeros((M * geo.kmax, cols), dtype=torch.float32, device=dev)
     for i in range(len(flows) - 1, -1, -1):
         xin, s = saved[i]
         d_in = torch.empty_like(xin) if i > 0 else None
         if geo.shared:                      # one net: the head forms ds = d out * in and db = d out itself
-            net_backward(flows[i][0], geo, s[0], xin, d_out, xin, s[0][2][0], d_in, False, dP, ws, grads)
+            _net_backward(flows[i][0], geo, s[0], xin, d_out, xin, s[0][2][0], d_in, False, dP, ws, grads)
             d_out = d_in
             continue
-        net_backward(flows[i][0], geo, s[0], xin, d_out, xin, s[0][2], d_in, False, dP, ws, grads)       # ds = d out * in
-        net_backward(flows[i][1], geo, s[1], xin, d_out, None, None, d_in, True, dP, ws, grads)          # db = d out
+        _net_backward(flows[i][0], geo, s[0], xin, d_out, xin, s[0][2], d_in, False, dP, ws, grads)       # ds = d out * in
+        _net_backward(flows[i][1], geo, s[1], xin, d_out, None, None, d_in, True, dP, ws, grads)          # db = d out
         d_out = d_in
 
     if per_sample:       # (the gradients of gc_* and of the biases came straight from the kernels)
-        _tconv_backward(stages, geo.d_cond, grads)
+        _tconv_backward(stages, geo.cond.d_cond, grads)
         return _fill_unread(store, grads, loss, x)
 
     # frame rate, backward
@@ -764,8 +709,7 @@ def loss_and_grad_varlen(model, wavs, mels, z=None, seeds=None, max_workgroups: 
         noise = torch.cat([engine._require_cuda_f32(v, 'z[%d]' % i).reshape(-1) for i, v in enumerate(z)])
     flows = model_nets(model, store)
     cols = sum(128 * len(net.dilations) for pair in flows for net in pair)
-    geo = (_SkipPackedGeometry if use_skip_connection else _PackedGeometry)(layout, cols, int(max_workgroups))
-    geo.shared = bool(shared_nets)
+    geo = _Geometry(_Packed(layout), _Projected(), cols, int(max_workgroups), skip=bool(use_skip_connection), shared=bool(shared_nets))
 
     loss, x, grads = _forward_backward(store, flows, geo, torch.cat(mels), noise.reshape(layout.rows).contiguous(),
                                        torch.cat([w.reshape(-1) for w in wavs]), _head(layout, layout.rows, power_weight, terms))

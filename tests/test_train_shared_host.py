@@ -140,8 +140,9 @@ def test_shared_kernel_resources():
     by = lambda k: next(r for n, r in res.items() if k in n)
     # the arrays of the existing heads + 32 floats for the second dy plane
     assert by('bwd_kernel<pwv::GatedIn>')['lds'] == 41472 + 128 and by('bwd_kernel<pwv::SumIn>')['lds'] == 33152 + 128
-    src = open(os.path.join(ROOT, 'parallel-wavenet-vocoder_amd', 'csrc', 'pwv_train_shared.hip')).read()
-    assert 'atomic' not in src.lower().replace('no floating-point atomics', '')
+    for source in ('pwv_train_shared.hip', 'pwv_train_head.h'):       # (the head's text is the header's)
+        src = open(os.path.join(ROOT, 'parallel-wavenet-vocoder_amd', 'csrc', source)).read()
+        assert 'atomic' not in src.lower().replace('no floating-point atomics', ''), source
 
 
 # (VGPRs, AGPRs, static LDS bytes) of every older training kernel: the tables of DESIGN.md section 9 ("Training", "Packed training",

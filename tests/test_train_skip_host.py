@@ -169,8 +169,9 @@ def test_skip_kernel_resources():
     by = lambda k: next(r for n, r in res.items() if k in n)
     assert by('bwd_kernel<pwv::UniformGeo, false>')['lds'] == 49792 + 16512
     assert by('bwd_kernel<pwv::PackedGeo, false>')['lds'] == 49792 + 16512 + 528
-    src = open(os.path.join(ROOT, 'parallel-wavenet-vocoder_amd', 'csrc', 'pwv_train_skip.hip')).read()
-    assert 'atomic' not in src.lower().replace('no floating-point atomics', '')
+    for source in ('pwv_train_skip.hip', 'pwv_train_head.h'):       # (the head's text is the header's)
+        src = open(os.path.join(ROOT, 'parallel-wavenet-vocoder_amd', 'csrc', source)).read()
+        assert 'atomic' not in src.lower().replace('no floating-point atomics', ''), source
 
 
 def _model(cfg, N=TO.N, T=TO.T, precision='f32'):

@@ -138,8 +138,8 @@ def main():
     def train_forward():
         flows = TR.model_nets(model, store)
         nets = [net for pair in flows for net in pair]
-        geo = TR._Geometry(n, length, mel.shape[1], sum(128 * len(net.dilations) for net in nets), 0)
-        geo.P = train_forward.P
+        geo = TR._Geometry(TR._Uniform(n, length, mel.shape[1]), TR._Projected(), sum(128 * len(net.dilations) for net in nets), 0)
+        geo.cond.P = train_forward.P
         x = z.reshape(-1)
         for pair in flows:
             s = [TR._net_forward(net, geo, x) for net in pair]
