@@ -20,7 +20,7 @@ LIB_PATH = os.environ.get('PWV_LIB') or os.path.join(_PKG_DIR, 'libpwv_hip.so') 
 CSRC = [os.path.join(_PKG_DIR, 'csrc', f) for f in ('pwv_layer.hip', 'pwv_layer_f16.hip', 'pwv_layer_h16.hip', 'pwv_misc.hip',
                                                     'pwv_stack_persist.hip', 'pwv_norm.hip', 'pwv_audio.hip', 'pwv_stream_tick.hip', 'pwv_score.hip', 'pwv_train.hip', 'pwv_train_loss.hip',
                                                     'pwv_train_varlen.hip', 'pwv_train_cond.hip', 'pwv_train_opt.hip', 'pwv_train_skip.hip',
-                                                    'pwv_train_shared.hip', 'pwv_layer_stream_cond.hip')]
+                                                    'pwv_train_shared.hip', 'pwv_layer_stream_cond.hip', 'pwv_layer_stream_skip.hip')]
 
 HEADER_VERSION = 301          # PWV_HIP_VERSION of include/pwv_hip.h these ctypes mirrors were written against
 FIRST_FOLD_FLOATS = 2048      # PWV_FIRST_FOLD_FLOATS
@@ -72,6 +72,8 @@ TRAIN_SKIP_SYMBOLS = ('pwv_train_skip_workspace_bytes', 'pwv_train_skip_layer_fw
 TRAIN_SHARED_SYMBOLS = ('pwv_train_shared_workspace_bytes', 'pwv_train_shared_head_fwd_f32', 'pwv_train_shared_head_bwd_f32')
 # ... and of include/pwv_hip_stream_cond.h: the streaming layer launch with a per-sample (transposed-conv) condition
 STREAM_COND_SYMBOLS = ('pwv_wavenet_layer_stream_cond_f32',)
+# ... and of include/pwv_hip_stream_skip.h: the streaming layer launch with skip accumulation and the streaming causal front in front of it
+STREAM_SKIP_SYMBOLS = ('pwv_wavenet_layer_stream_skip_f32', 'pwv_iaf_front_stream_f32')
 TRAIN_HEAD_IN_GATED, TRAIN_HEAD_IN_SKIPSUM = 0, 1      # PWV_TRAIN_HEAD_IN_GATED, PWV_TRAIN_HEAD_IN_SKIPSUM
 TRAIN_OPT_REC = 3             # PWV_TRAIN_OPT_REC: int64 per record of an arena table = {tensor address, arena offset, count}
 TRAIN_OPT_CHUNK = 1024        # PWV_TRAIN_OPT_CHUNK: floats per record of a block map
@@ -633,6 +635,8 @@ def _declare(lib):
     lib.pwv_wavenet_layer_f32.argtypes = [POINTER(LayerArgs), c_void_p]
     lib.pwv_wavenet_layer_stream_f32.argtypes = [POINTER(LayerArgs), POINTER(StreamArgs), c_void_p]
     lib.pwv_wavenet_layer_stream_cond_f32.argtypes = [POINTER(LayerArgs), POINTER(StreamArgs), c_void_p]
+    lib.pwv_wavenet_layer_stream_skip_f32.argtypes = [POINTER(LayerArgs), POINTER(StreamArgs), c_void_p]
+    lib.pwv_iaf_front_stream_f32.argtypes = [f32p, c_int, POINTER(c_void_p), POINTER(c_void_p), c_int, c_int, POINTER(StreamArgs), c_void_p]
     lib.pwv_stream_carry_f32.argtypes = [POINTER(StreamArgs), c_int, c_int, c_void_p]
     lib.pwv_stream_tick_begin.argtypes = [POINTER(StreamTickArgs), c_void_p]
     lib.pwv_stream_tick_commit.argtypes = [POINTER(StreamTickArgs), c_void_p]
@@ -701,7 +705,7 @@ def _declare(lib):
     lib.pwv_status_words_alloc.argtypes = [POINTER(c_void_p)]
     lib.pwv_status_words_free.argtypes = [c_void_p]
     lib.pwv_range_check_f32.argtypes = [f32p, c_int64, ctypes.c_float, c_void_p, c_void_p]
-    for name in EXPORTED_SYMBOLS + EXTENSION_SYMBOLS + LIVE_TICK_SYMBOLS + SCORE_SYMBOLS + TRAIN_SYMBOLS + TRAIN_LOSS_SYMBOLS + TRAIN_VARLEN_SYMBOLS + TRAIN_COND_SYMBOLS + TRAIN_OPT_SYMBOLS + TRAIN_SKIP_SYMBOLS + TRAIN_SHARED_SYMBOLS + STREAM_COND_SYMBOLS:      # fails loudly (AttributeError) if a symbol is missing
+    for name in EXPORTED_SYMBOLS + EXTENSION_SYMBOLS + LIVE_TICK_SYMBOLS + SCORE_SYMBOLS + TRAIN_SYMBOLS + TRAIN_LOSS_SYMBOLS + TRAIN_VARLEN_SYMBOLS + TRAIN_COND_SYMBOLS + TRAIN_OPT_SYMBOLS + TRAIN_SKIP_SYMBOLS + TRAIN_SHARED_SYMBOLS + STREAM_COND_SYMBOLS + STREAM_SKIP_SYMBOLS:      # fails loudly (AttributeError) if a symbol is missing
         getattr(lib, name)
     return lib
 

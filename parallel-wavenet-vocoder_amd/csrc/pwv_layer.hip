@@ -439,6 +439,7 @@ static int layer_call(const pwv_layer_args* a, const StreamParams* st, pwv_strea
     PWV_CHECK_ARG(a->out_mode == PWV_OUT_GATED || a->out_mode == PWV_OUT_RESIDUAL, "pwv_wavenet_layer_f32: bad out_mode");
     if (st) {      // (pwv_wavenet_layer_stream_f32 has checked that the layer is one of the three streaming forms)
         if (cond) return launch_layer_stream_cond(lp, *st, a->precision == PWV_PREC_F16X3, gated, g8, s);      // (pwv_wavenet_layer_stream_cond_f32 has)
+        if (any_skip) return launch_layer_stream_skip(lp, *st, a->precision == PWV_PREC_F16X3, gated, g8, s);      // (pwv_wavenet_layer_stream_skip_f32 has)
         if (a->precision == PWV_PREC_F16X3) return launch_layer_f16x3_stream(lp, *st, g8, s);
         const dim3 grid(g8 * lp.G);
         if (lp.packed_head[0]) hipLaunchKernelGGL((layer_f32_stream_kernel<false, true>), grid, dim3(512), 0, s, lp, *st);

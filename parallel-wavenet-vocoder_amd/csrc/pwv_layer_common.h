@@ -361,6 +361,9 @@ int launch_pack_head_f16x3(const float* skip, const float* skip_bias, const floa
 // the streaming forms with a per-sample condition, both arithmetics (pwv_layer_stream_cond.hip): layer 0 folded (lp.x_first), the last layer
 // with gated output (`gated`), else a plain residual layer
 int launch_layer_stream_cond(const LayerParams& lp, const StreamParams& st, bool f16x3, bool gated, int per_net, hipStream_t s);
+// the streaming forms with skip accumulation, both arithmetics (pwv_layer_stream_skip.hip): the last layer with gated output (`gated`), else a
+// residual layer
+int launch_layer_stream_skip(const LayerParams& lp, const StreamParams& st, bool f16x3, bool gated, int per_net, hipStream_t s);
 // ... and what their entry point shares with pwv_wavenet_layer_stream_f32 (pwv_layer.hip): the caller's pwv_stream_args as far as its
 // struct_size reaches and the kernels' view of it (returns why not, or NULL); the checks, parameters, grid and launch of a streaming layer
 const char* stream_args_view(const pwv_stream_args* sa, pwv_stream_args& out, StreamParams& st);

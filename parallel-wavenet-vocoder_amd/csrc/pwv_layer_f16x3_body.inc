@@ -5,8 +5,9 @@
 // includes too: the two are bit-identical because they are one text.
     static_assert(!HEAD || (GATED && !SKIP && !COND && !FIRST), "HEAD: plain last layer only");
     static_assert(!FOLD || FIRST, "FOLD: layer 0 of a scalar-input net only");
-    static_assert(!STREAM || (!SKIP && FOLD == FIRST && (COND ? !HEAD && !(FIRST && GATED) : GATED == HEAD)),
-                  "STREAM: folded layer 0, plain residual layer, last layer + head; COND: the last layer gated, its head a launch of its own");
+    static_assert(!STREAM || (SKIP ? !COND && !FIRST && !HEAD : FOLD == FIRST && (COND ? !HEAD && !(FIRST && GATED) : GATED == HEAD)),
+                  "STREAM: folded layer 0, plain residual layer, last layer + head; COND: the last layer gated, its head a launch of its own; "
+                  "SKIP: a residual or gated layer on row histories (layer 0 behind a streaming front), the head a launch of its own");
     constexpr int WAVES = 8;
     constexpr int kLds = HEAD ? kA1Size + kASSize + kHA1Size : layer_floats(SKIP, COND);
     constexpr int kCF = kLds + 4;           // FIRST: the causal filter [2][64] behind the unit counter

@@ -4,8 +4,9 @@
 // The fused head of the HEAD variants is text of its own, pwv_head_f32.inc and pwv_head_pp2.inc, which the persistent kernel's tail (pwv_persist_tail.inc)
 // includes too: the two are bit-identical because they are one text.
     static_assert(!FOLD || FIRST, "FOLD: layer 0 of a scalar-input net only");
-    static_assert(!STREAM || (!SKIP && FOLD == FIRST && (COND ? !HEAD && !(FIRST && GATED) : GATED == HEAD)),
-                  "STREAM: folded layer 0, plain residual layer, last layer + head; COND: the last layer gated, its head a launch of its own");
+    static_assert(!STREAM || (SKIP ? !COND && !FIRST && !HEAD : FOLD == FIRST && (COND ? !HEAD && !(FIRST && GATED) : GATED == HEAD)),
+                  "STREAM: folded layer 0, plain residual layer, last layer + head; COND: the last layer gated, its head a launch of its own; "
+                  "SKIP: a residual or gated layer on row histories (layer 0 behind a streaming front), the head a launch of its own");
     static_assert(!HEAD || (GATED && !SKIP && !COND && !FIRST), "HEAD: plain last layer only");
     static_assert(!FIRST || !SKIP, "FIRST: no skip accumulation");
     constexpr int WAVES = 8;

@@ -1,5 +1,6 @@
 // The register tile of one 32-row unit of the exact-fp32 layer kernels and its loads: shared by pwv_layer.hip and the streaming forms with a
-// per-sample condition (pwv_layer_stream_cond.hip), which include the same body text (pwv_layer_f32_body.inc).
+// per-sample condition (pwv_layer_stream_cond.hip) or with skip accumulation (pwv_layer_stream_skip.hip), which include the same body text
+// (pwv_layer_f32_body.inc).
 #pragma once
 
 #include "pwv_layer_common.h"

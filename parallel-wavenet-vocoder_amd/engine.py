@@ -1209,19 +1209,24 @@ def _instance_norm(nets) -> bool:
     return any(getattr(n, 'normalize', None) == 'in' for n in nets)
 
 
-def _flow_structure(nets, cond, precision: Optional[str] = None, per_sample: bool = False) -> Optional[str]:
+def _flow_structure(nets, cond, precision: Optional[str] = None, per_sample: bool = False, skip: bool = False) -> Optional[str]:
     """Which structural property keeps a flow (its nets) off the forms that run it whole inside the fused launches -- the packed batch's
     and the streaming ones -- as a key, or None: 'samples' (per-sample conditioning), 'skip' (skip accumulation), 'f16' (the fp16
     storage mode), 'shape' (not two scalar-in / scalar-out nets or one shared net of two outputs, all fused-capable, of one structure
     and one precision).  varlen_fallback_reason and stream_refusal word them.  per_sample=True asks about the per-layer streaming route
-    with a per-sample condition (run_flow_stream): 'samples' is then no obstacle, and a condition that is NOT per sample is 'frames'."""
+    with a per-sample condition (run_flow_stream): 'samples' is then no obstacle, and a condition that is NOT per sample is 'frames'.
+    skip=True asks about the per-layer streaming route with skip accumulation: 'skip' is then no obstacle, and nets WITHOUT
+    use_skip_connection are 'noskip'."""
     net0 = nets[0]
     if per_sample:
         if cond is None or isinstance(cond, RepeatedCondition):
             return 'frames'
     elif cond is not None and not isinstance(cond, RepeatedCondition):
         return 'samples'
-    if net0.use_skip_connection:
+    if skip:
+        if not net0.use_skip_connection:
+            return 'noskip'
+    elif net0.use_skip_connection:
         return 'skip'
     if (precision or net0.precision or DEFAULT_PRECISION) == 'f16':
         return 'f16'
@@ -1518,34 +1523,39 @@ def _run_stack_layers(path: _Path, nets, plans, projs, bufs, outs, x, x_limit, c
 # ---- streaming: a flow on one CHUNK of N sessions (include/pwv_hip.h "STREAMING"; stream.StreamingVocoder owns the sessions) ---------
 _STREAM_STRUCTURE_WHY = {'samples': 'per-sample (transposed-conv) conditioning',
                          'frames': 'per_sample=True without a per-sample condition (a [N, T, C] tensor at sample rate)', 'skip': 'skip accumulation (use_skip_connection)',
+                         'noskip': 'skip=True does not match these nets: they have no skip accumulation (use_skip_connection is False)',
                          'f16': "precision 'f16' (the fp16 storage mode)",
                          'shape': 'a net outside the fused shape (two scalar-input nets per flow, W = 2, R = D = 64, S = 128, no normaliser, at least 2 layers)'}
 
 
-def stream_refusal(nets, cond, precision: Optional[str] = None, per_sample: bool = False) -> Optional[str]:
+def stream_refusal(nets, cond, precision: Optional[str] = None, per_sample: bool = False, skip: bool = False) -> Optional[str]:
     """Why a flow (its nets) has no streaming form -- or None.  The per-layer kernels stream in three forms only: layer 0 folded onto
     its scalar input, a plain residual layer, the last layer with the head fused behind it.  Two flow shapes stream (_flow_structure):
     two nets of one output each, and one shared net of two outputs (its launches carry G = 1 and a head / tail of Q = 2).
     per_sample=True: the same question for the streaming forms with a per-sample condition (pwv_wavenet_layer_stream_cond_f32: layer 0
     folded, a plain residual layer, the last layer gated with the head launch behind it); `cond` is then the [N, T, C] tensor, or the
-    PackedSampleCondition of a ragged chunk."""
+    PackedSampleCondition of a ragged chunk.
+    skip=True: the same question for the streaming forms with skip accumulation (pwv_iaf_front_stream_f32, then
+    pwv_wavenet_layer_stream_skip_f32 per layer and the head launch on the skip sum); not together with per_sample."""
     net0 = nets[0]
+    if skip and per_sample:
+        return 'skip=True together with per_sample=True: skip accumulation with a per-sample condition has no streaming form'
     if _instance_norm(nets):
         return "instance normalisation ('in'): its statistics span the whole time axis"
-    key = _flow_structure(nets, cond, precision, per_sample)
+    key = _flow_structure(nets, cond, precision, per_sample, skip)
     if key is None and (net0.normalize or len(net0.dilations) < 2):       # (_flow_structure has settled the nets: two of one output or one of two)
         key = 'shape'
     if key is not None:
         return _STREAM_STRUCTURE_WHY[key]
-    if not (FOLD_FIRST and FUSE_FIRST and FUSE_HEAD):
+    if not skip and not (FOLD_FIRST and FUSE_FIRST and FUSE_HEAD):      # (a skip stream has its front and its head as launches of their own)
         return 'PWV_FOLD_FIRST=0 / FUSE_FIRST / FUSE_HEAD off: layer 0 streams folded and the head fused only'
     return None
 
 
-def _prepare_flow_stream(nets, x: torch.Tensor, cond, precision: Optional[str]) -> _FlowPrep:
-    """_prepare_flow for a streaming flow: layer 0 streams in its folded form only."""
+def _prepare_flow_stream(nets, x: torch.Tensor, cond, precision: Optional[str], skip: bool = False) -> _FlowPrep:
+    """_prepare_flow for a streaming flow: layer 0 streams in its folded form only (skip: behind the streaming front, not folded)."""
     prep = _prepare_flow(nets, x, cond, precision)
-    if any(p.first_fold is None for p in prep.plans):
+    if not skip and any(p.first_fold is None for p in prep.plans):
         raise _lib.PwvError('run_flow_stream: no streaming form: layer 0 has no folded form for these weights')
     return prep
 
@@ -1624,7 +1634,7 @@ def stream_groups(geom: 'VarlenGeometry', tab: torch.Tensor) -> List[_StreamGrou
     return groups
 
 
-def _run_flow_stream_ragged(nets, x, cond, precision, hist, scalar_off, row_off, geom, slot_tab, per_sample=False):
+def _run_flow_stream_ragged(nets, x, cond, precision, hist, scalar_off, row_off, geom, slot_tab, per_sample=False, skip=False):
     """run_flow_stream on a ragged chunk (geom: session i has geom.lengths[i] rows of the packed x [R, 1]; route 4 of DESIGN.md section 9
     "Routes").  The launches, chosen once per flow:
       * the PACKED streaming persistent launches (pwv_persist_args.cu_rows with hist->cu_rows, stack_persist_ragged_kernel) where a uniform
@@ -1635,11 +1645,14 @@ def _run_flow_stream_ragged(nets, x, cond, precision, hist, scalar_off, row_off,
     Same bits: a session's rows do not depend on which sessions were advanced with it.  EVENT_LOG gets ('stream_ragged', None, None,
     'packed' | 'grouped', why, groups) ahead of the route's own entries.
     per_sample (cond a PackedSampleCondition): the grouped route only -- the packed route is the persistent kernel, which cannot host a
-    per-sample condition."""
+    per-sample condition.  skip: the grouped route only, for the same reason (the persistent launch has no skip accumulators)."""
     x = _require_cuda_f32(x, 'input')
     if x.dim() != 2 or tuple(x.shape) != (geom.rows, 1):
         raise ValueError('input must be the packed chunk [%d, 1], got %s' % (geom.rows, tuple(x.shape)))
-    why = 'per-sample conditioning (the packed route is the persistent launch)' if per_sample else varlen_fallback_reason(nets, cond, geom, precision)
+    if skip:
+        why = 'skip accumulation (the packed route is the persistent launch)'
+    else:
+        why = 'per-sample conditioning (the packed route is the persistent launch)' if per_sample else varlen_fallback_reason(nets, cond, geom, precision)
     if why is None:
         x3 = x.reshape(1, geom.rows, 1)
         prep = _prepare_flow_stream(nets, x3, cond, precision)
@@ -1666,13 +1679,13 @@ def _run_flow_stream_ragged(nets, x, cond, precision, hist, scalar_off, row_off,
         ctypes.memmove(ctypes.addressof(hg), ctypes.addressof(hist), ctypes.sizeof(_lib.StreamArgs))
         hg.slot_tab, hg.cu_rows = grp.tab.data_ptr(), None
         yg = run_flow_stream(nets, x.index_select(0, grp.rows_idx).reshape(grp.n, grp.t, 1), grp.condition(cond, geom), precision, hg,
-                             scalar_off, row_off, per_sample=per_sample)
+                             scalar_off, row_off, per_sample=per_sample, skip=skip)
         out.index_copy_(0, grp.rows_idx, yg.reshape(grp.n * grp.t, 1))
     return out
 
 
 def run_flow_stream(nets: Sequence, x: torch.Tensor, cond, precision: Optional[str], hist: _lib.StreamArgs, scalar_off: int,
-                    row_off, geom=None, slot_tab: Optional[torch.Tensor] = None, per_sample: bool = False) -> torch.Tensor:
+                    row_off, geom=None, slot_tab: Optional[torch.Tensor] = None, per_sample: bool = False, skip: bool = False) -> torch.Tensor:
     """One IAF flow on a chunk: x [N, T, 1] = the T samples that follow what each of the N sessions has seen, `cond` the chunk's own
     frames (a RepeatedCondition of T / hop + 1 frames per session).  `hist` carries the history blocks and the slot table of the call
     (read / written block per session); `scalar_off` and `row_off[g][j]` (j >= 1) say where this flow's histories lie in a block.
@@ -1690,14 +1703,19 @@ def run_flow_stream(nets: Sequence, x: torch.Tensor, cond, precision: Optional[s
     (_run_flow_stream_ragged: packed persistent launches, else the sessions grouped by length on the routes above).
     per_sample=True (a transposed-conv model's stream): `cond` is the chunk's condition at sample rate, [N, T, C] -- a PackedSampleCondition
     for a ragged chunk -- and the flow is L calls of pwv_wavenet_layer_stream_cond_f32, the head launch and the affine
-    (_run_flow_stream_cond); the persistent launch cannot host a per-sample condition."""
-    why = stream_refusal(nets, cond, precision, per_sample=per_sample)
+    (_run_flow_stream_cond); the persistent launch cannot host a per-sample condition.
+    skip=True (a stream of a model with use_skip_connection): the flow is the streaming front, L calls of
+    pwv_wavenet_layer_stream_skip_f32 on a per-chunk skip accumulator, the head launch on the skip sum and the affine
+    (_run_flow_stream_skip); `scalar_off` is then the ONE scalar x[-1] of the front and row_off[g][0] layer 0's row history."""
+    why = stream_refusal(nets, cond, precision, per_sample=per_sample, skip=skip)
     if why is not None:
         raise _lib.PwvError('run_flow_stream: no streaming form: ' + why)
     if geom is not None:
-        return _run_flow_stream_ragged(nets, x, cond, precision, hist, scalar_off, row_off, geom, slot_tab, per_sample)
+        return _run_flow_stream_ragged(nets, x, cond, precision, hist, scalar_off, row_off, geom, slot_tab, per_sample, skip)
     x = _require_cuda_f32(x, 'input')
-    prep = _prepare_flow_stream(nets, x, cond, precision)
+    prep = _prepare_flow_stream(nets, x, cond, precision, skip)
+    if skip:
+        return _run_flow_stream_skip(prep, nets, x, cond, hist, scalar_off, row_off)
     if per_sample:
         return _run_flow_stream_cond(prep, nets, x, hist, scalar_off, row_off)
     if prep.path.whole_flow:
@@ -1762,5 +1780,46 @@ def _run_flow_stream_cond(prep: _FlowPrep, nets, x: torch.Tensor, hist: _lib.Str
     ha.in_mode, ha.precision = _lib.HEAD_IN_GATED, plans[0].precision
     for g, p in enumerate(plans):
         ha.in_[g], ha.packed[g], ha.out[g] = bufs[g][(L - 1) & 1].data_ptr(), p.packed_head.data_ptr(), outs[g].data_ptr()
+    check(lib.pwv_wavenet_head_f32(ctypes.byref(ha), s), 'pwv_wavenet_head_f32')
+    return _flow_affine(x, outs)
+
+
+def _run_flow_stream_skip(prep: _FlowPrep, nets, x: torch.Tensor, cond, hist: _lib.StreamArgs, scalar_off: int, row_off) -> torch.Tensor:
+    """run_flow_stream with skip accumulation ("Streaming the skip-connection architecture"): the launches of the
+    one-shot skip forward (_causal_front + pwv_wavenet_stack_f32) with the look-back of a stream.  The streaming front writes the causal
+    layer's rows of the chunk (x[-1] from the session's scalar at `scalar_off`); L streaming layer launches of all the flow's nets add
+    their skip contributions, in layer order, to the CHUNK's accumulators -- pwv_tile32_floats(n t, 128) floats per net: the skip sum is
+    row-local and has no history --, layer 0 on a row history like the others (row_off[g][0]), the last one with gated output; the head
+    launch reads the skip sum; the affine."""
+    lib, s = _lib.lib(), _stream()
+    net0, plans = nets[0], prep.plans
+    n, t, _ = x.shape
+    G, L = len(plans), plans[0].n_layers
+    assert prep.mode != 'samples' and all(p.with_skip for p in plans)
+    if EVENT_LOG is not None:
+        EVENT_LOG.append(('layer_stream_skip', None, None, G, L))      # the front + L calls of pwv_wavenet_layer_stream_skip_f32 + the head + the affine
+    if plans[0].precision == _lib.PREC_F16X3:
+        range_check_op(x, prep.x_limit, kind=None)      # (as _causal_front: no layer reads the scalar input itself)
+    projs = _projections(cond, prep.mode, plans, prep.precision, None)
+    outs = [torch.empty((n, t, net0.out_channels), dtype=torch.float32, device=x.device) for _ in plans]
+    bufs = [[torch.empty((lib.pwv_tile32_floats(n * t, 64),), dtype=torch.float32, device=x.device) for _ in range(2)] for _ in plans]
+    skips = [torch.empty((lib.pwv_tile32_floats(n * t, net0.skip_channels),), dtype=torch.float32, device=x.device) for _ in plans]
+    hist.scalar_off = scalar_off
+    filt = (c_void_p * G)(*[p.causal_filter.data_ptr() for p in plans])
+    hout = (c_void_p * G)(*[b[0].data_ptr() for b in bufs])
+    check(lib.pwv_iaf_front_stream_f32(_ptr(x), G, filt, hout, n, t, ctypes.byref(hist), s), 'pwv_iaf_front_stream_f32')
+    for j in range(L):
+        la = _layer_args(net0, plans, projs, projs[0].stride(0), prep.cond_geom, bufs, j, j & 1, (j + 1) & 1, x)
+        la.out_mode = _lib.OUT_GATED if j == L - 1 else _lib.OUT_RESIDUAL
+        la.skip_init = 1 if j == 0 else 0
+        for g in range(G):
+            la.skip[g] = skips[g].data_ptr()
+            hist.row_off[g] = row_off[g][j]
+        check(lib.pwv_wavenet_layer_stream_skip_f32(ctypes.byref(la), ctypes.byref(hist), s), 'pwv_wavenet_layer_stream_skip_f32')
+    ha = _lib.HeadArgs()
+    ha.G, ha.N, ha.T, ha.Q = G, n, t, net0.out_channels
+    ha.in_mode, ha.precision = _lib.HEAD_IN_SKIPSUM, plans[0].precision
+    for g, p in enumerate(plans):
+        ha.in_[g], ha.packed[g], ha.out[g] = skips[g].data_ptr(), p.packed_head.data_ptr(), outs[g].data_ptr()
     check(lib.pwv_wavenet_head_f32(ctypes.byref(ha), s), 'pwv_wavenet_head_f32')
     return _flow_affine(x, outs)

@@ -224,7 +224,7 @@ def generate(case='default', ckpt=None, debug=False, varlen=False, seed=None, st
         its mel and the seed -- not on the other files of the run or their order.
     :param stream: vocode every input at its own length as a STREAM (IAFVocoder.open_stream): one session per input, fed in pushes
         of `stream` mel frames; writes the files --varlen writes.  A case with cond_upsample_method 'transposed_conv' streams too (on
-        per-layer launches; --graph and --live=graph are refused for it by name).
+        per-layer launches; --graph and --live=graph are refused for it by name), and so does a case with use_skip_connection.
     :param graph: (with stream) every tick is one replay of a captured ragged tick (StreamingVocoder.graphed_varlen at a capacity of one
         slot per input and inputs x `stream` frames), the first one included: it starts the sessions (tick(starts=)); only an input too
         short for that starts with the eager one-frame push; same files.
@@ -251,6 +251,9 @@ def generate(case='default', ckpt=None, debug=False, varlen=False, seed=None, st
         if not 0 <= seed < (1 << 64):
             raise ValueError('--seed must be in [0, 2**64), got %d' % seed)
     hp.set_hparam_yaml(case)
+    if stream is not None and hp.model.use_skip_connection and (graph or live == 'graph'):
+        raise _lib.PwvError('--graph / --live=graph: skip accumulation (use_skip_connection) streams on per-layer launches only; a graphed '
+                            'tick needs the whole-flow persistent launch (use --stream=FRAMES or --stream=FRAMES --live)')
     if stream is not None and hp.model.cond_upsample_method == 'transposed_conv' and (graph or live == 'graph'):
         raise _lib.PwvError('--graph / --live=graph: per-sample (transposed-conv) conditioning streams on per-layer launches only; a graphed '
                             'tick needs the whole-flow persistent launch (use --stream=FRAMES or --stream=FRAMES --live)')
@@ -343,8 +346,10 @@ def generate(case='default', ckpt=None, debug=False, varlen=False, seed=None, st
 
 def _open_stream(model, slots):
     """The stream of --stream: a case with model.cond_upsample_method 'transposed_conv' makes the request for its streaming form
-    (IAFVocoder.open_stream(transposed_conv=True)), as the train command line asks for skip / shared."""
-    return model.open_stream(slots=slots, transposed_conv=hp.model.cond_upsample_method == 'transposed_conv')
+    (IAFVocoder.open_stream(transposed_conv=True)), a case with model.use_skip_connection for its own (use_skip_connection=True), as the
+    train command line asks for skip / shared."""
+    return model.open_stream(slots=slots, transposed_conv=hp.model.cond_upsample_method == 'transposed_conv',
+                             use_skip_connection=bool(hp.model.use_skip_connection))
 
 
 def _generate_stream(model, mels, frames):

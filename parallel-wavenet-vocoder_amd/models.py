@@ -246,7 +246,7 @@ class IAFVocoder(object):
         return self._forward(store, mel.unsqueeze(0), noise, False, 'iaf_vocoder', precision, length=geom.rows, geom=geom)
 
     # -- streaming ("Streaming") ---------------------------------------------------------------------
-    def open_stream(self, slots=1, hist_alloc=None, transposed_conv=False):
+    def open_stream(self, slots=1, hist_alloc=None, transposed_conv=False, use_skip_connection=False):
         """A stream.StreamingVocoder over this model's weights: `slots` independent sessions that take their mel frames in pushes
         and return each push's samples -- bit for bit the samples the one-shot forward gives for the whole utterance, at the cost
         of the pushed rows alone (every layer keeps the last `dilation` rows of its input per session).  The constructor's
@@ -263,9 +263,14 @@ class IAFVocoder(object):
         refuses such hparams, and the request under 'repeat' hparams is a PwvError): every sample of the condition depends on one mel
         frame, so the chunks still equal the one-shot forward bit for bit; a flow is then L per-layer launches with the condition GEMM
         inside, the head launch and the affine (no persistent launch, no graph replay).  DESIGN.md section 9, "Streaming transposed-conv
-        conditioning" has the routes and the measured ticks."""
+        conditioning" has the routes and the measured ticks.
+        ``use_skip_connection=True`` is the request to stream a model with model.use_skip_connection (the bare call refuses such
+        hparams, the request under hparams without the switch is a PwvError, and so is the request together with transposed_conv):
+        the skip sum is row-local, so the chunks equal the one-shot forward bit for bit; a flow is then a streaming causal front, L
+        per-layer launches that accumulate the chunk's skip sums, the head launch and the affine (no persistent launch, no graph
+        replay).  DESIGN.md section 9, "Streaming the skip-connection architecture"."""
         from .stream import StreamingVocoder
-        return StreamingVocoder(self, slots, hist_alloc=hist_alloc, transposed_conv=transposed_conv)
+        return StreamingVocoder(self, slots, hist_alloc=hist_alloc, transposed_conv=transposed_conv, use_skip_connection=use_skip_connection)
 
     def verify(self):
         """For callers of the enqueue-only form (verify=False / PWV_ASYNC=1): wait for the enqueued forwards and raise

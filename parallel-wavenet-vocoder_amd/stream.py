@@ -30,21 +30,26 @@ class HistoryLayout:
     """Where every history of the model lies inside a block (float offsets): per flow the d0 + 1 scalars of layer 0's input
     (padded to 64 floats), then per net and layer j >= 1 a tile32 buffer of round32(d_j) rows x 64 channels.  `carry` lists every
     history as (offset, rows, floats per row): the table of pwv_stream_carry_f32.  `nets_per_flow`: 2 for the default architecture,
-    1 for the shared-net one (one two-output net per flow: one row history per layer)."""
+    1 for the shared-net one (one two-output net per flow: one row history per layer).
+    skip=True (a stream of a model with use_skip_connection): layer 0 is a plain layer behind the streaming front
+    (pwv_iaf_front_stream_f32), so per flow ONE scalar, x[-1] (padded to 64 floats; carry entry (offset, 1, 1)), and per net a row
+    history for layer 0 too -- round32(d_0) rows of the causal layer's output -- at row_off[flow][net][0].  The skip sums themselves are
+    row-local and keep no history."""
 
-    def __init__(self, dilations: Sequence[Sequence[int]], nets_per_flow: int = 2):
+    def __init__(self, dilations: Sequence[Sequence[int]], nets_per_flow: int = 2, skip: bool = False):
         self.scalar_off: List[int] = []
-        self.row_off: List[List[List[int]]] = []       # [flow][net][layer] (layer 0: unused, -1)
+        self.row_off: List[List[List[int]]] = []       # [flow][net][layer] (layer 0: unused, -1, unless skip)
         self.carry: List[tuple] = []
         off = 0
         for dil in dilations:
+            scalars = 1 if skip else int(dil[0]) + 1
             self.scalar_off.append(off)
-            self.carry.append((off, int(dil[0]) + 1, 1))
-            off += (int(dil[0]) + 1 + 63) // 64 * 64
+            self.carry.append((off, scalars, 1))
+            off += (scalars + 63) // 64 * 64
             per_net = []
             for _ in range(nets_per_flow):
-                offs = [-1]
-                for d in dil[1:]:
+                offs = [] if skip else [-1]
+                for d in (dil if skip else dil[1:]):
                     offs.append(off)
                     self.carry.append((off, int(d), 64))
                     off += round32(d) * 64
@@ -279,14 +284,25 @@ class StreamingVocoder(object):
     (the grouped route), state / load_state, reset, verify and the noise contract are the same; graphed / graphed_varlen / graphed_live
     refuse by name (they capture the persistent launch).  The request under 'repeat' hparams is a PwvError, and so is hop_length != 80.
 
+    A fourth streams on request, ``open_stream(slots, use_skip_connection=True)`` under model.use_skip_connection (bench/skip; with or
+    without shared_nets): the skip sum of a sample is row-local, so it has no history -- a chunk accumulates it in a buffer of its own
+    and the head launch reads it.  Layer 0 runs, as in the one-shot skip forward, on the rows of the causal front (a streaming front
+    that keeps x[-1] per session) and has a row history like every other layer (HistoryLayout(..., skip=True)); a flow is the front, L
+    per-layer launches (pwv_wavenet_layer_stream_skip_f32), the head launch and the affine.  push, push_varlen (the grouped route),
+    state / load_state, reset, verify and the noise contract are the same; the graph wrappers refuse by name.  The request under
+    hparams without the switch is a PwvError; together with transposed_conv=True it is refused by name.
+
     Refused with a PwvError that names the reason (nothing is launched): per-sample (transposed-conv) conditioning without that
-    request, skip accumulation (a shared-net model with skip connections is refused as a skip model), precision 'f16', any normaliser -- instance
+    request, skip accumulation without that request (a shared-net model with skip connections is refused as a skip model), precision 'f16', any normaliser -- instance
     normalisation's statistics span the whole time axis --, nets outside the fused shape."""
 
-    def __init__(self, model, slots: int, hist_alloc=None, transposed_conv: bool = False):
+    def __init__(self, model, slots: int, hist_alloc=None, transposed_conv: bool = False, use_skip_connection: bool = False):
         m = hp.model
         why = None
-        per_sample = bool(transposed_conv)
+        per_sample, skip = bool(transposed_conv), bool(use_skip_connection)
+        if skip and not m.use_skip_connection:
+            raise _lib.PwvError("open_stream(use_skip_connection=True) does not match these hparams: model.use_skip_connection is %r"
+                                % (m.use_skip_connection,))
         if per_sample and m.cond_upsample_method != 'transposed_conv':
             raise _lib.PwvError("open_stream(transposed_conv=True) does not match these hparams: model.cond_upsample_method is %r"
                                 % (m.cond_upsample_method,))
@@ -298,8 +314,11 @@ class StreamingVocoder(object):
             why = 'hop_length %d: the transposed convolutions (strides 4, 4, 5) upsample by 80' % int(hp.signal.hop_length)
         elif per_sample and m.condition_channels != 80:
             why = 'condition_channels %r: the per-sample layer kernels take 80' % (m.condition_channels,)
-        elif m.use_skip_connection:
+        elif m.use_skip_connection and not skip:
             why = 'skip accumulation (use_skip_connection: True): the per-layer kernels stream without skip sums only'
+        elif skip and per_sample:
+            why = ('use_skip_connection=True together with transposed_conv=True: skip accumulation with a per-sample condition has no '
+                   'streaming kernels (one or the other)')
         elif (model.precision or engine.DEFAULT_PRECISION) == 'f16':
             why = "precision 'f16': the fp16 storage mode has no streaming kernels ('f16x3' and 'f32' have)"
         elif m.get('normalize') or m.get('normalize_cond') or m.get('normalize_wavenet'):
@@ -313,10 +332,12 @@ class StreamingVocoder(object):
             raise ValueError('slots must be >= 1, got %r' % (slots,))
         self.model = model
         self.per_sample = per_sample                # a transposed-conv model: the condition enters every layer per sample (_enqueue)
+        self.skip = skip                            # a skip-connection model: per-layer launches on per-chunk skip accumulators (_enqueue)
         self.n_slots = int(slots)
         self.hop = int(hp.signal.hop_length)
         self.n_mels = int(hp.signal.n_mels)
-        self.layout = HistoryLayout([list(d) for d in m.dilations[:m.n_iaf]], nets_per_flow=1 if m.get('shared_nets', False) else 2)
+        self.layout = HistoryLayout([list(d) for d in m.dilations[:m.n_iaf]], nets_per_flow=1 if m.get('shared_nets', False) else 2,
+                                    skip=skip)
         store = model.store or get_default_store()
         self.device = store.device
         # two blocks per slot and, behind them in the same allocation, the ZERO BLOCK: what a session that starts inside a graphed tick
@@ -406,7 +427,10 @@ class StreamingVocoder(object):
             commit()
 
     def _refuse_graph(self, what: str) -> None:
-        """The graph wrappers capture the whole-flow persistent launch, which cannot host a per-sample condition."""
+        """The graph wrappers capture the whole-flow persistent launch, which can host neither a per-sample condition nor skip sums."""
+        if self.skip:
+            raise _lib.PwvError('%s: skip accumulation (use_skip_connection) streams on per-layer launches only; a graphed tick needs the '
+                                'whole-flow persistent launch.  Nothing was captured: push / push_varlen go on as before' % what)
         if self.per_sample:
             raise _lib.PwvError('%s: per-sample (transposed-conv) conditioning streams on per-layer launches only; a graphed tick needs the '
                                 'whole-flow persistent launch.  Nothing was captured: push / push_varlen go on as before' % what)
@@ -570,7 +594,7 @@ class StreamingVocoder(object):
             x = z
             for i, iaf in enumerate(flows):
                 x = engine.run_flow_stream(iaf.nets(), x, cond, precision, sa, lay.scalar_off[i], lay.row_off[i], geom=geom, slot_tab=tab,
-                                           per_sample=self.per_sample)
+                                           per_sample=self.per_sample, skip=self.skip)
         return x
 
     # -- a ragged push ---------------------------------------------------------------------------------------------------

@@ -1,7 +1,9 @@
 """Streaming against overlap-and-discard ("Streaming"): what one TICK of a server costs that advances
 `sessions` sessions by `chunk` samples each, default model (or --case: 'bench/c2' = the shared-net architecture, one two-output net per
 flow, at the default dilations; 'bench/c5' = transposed-conv conditioning, whose stream is per-layer launches with the condition GEMM
-inside -- its `stream` leg is that route and there is no `stream_layers` leg; the graph modes refuse it), random weights, one GPU, steady state (every session has emitted more
+inside -- its `stream` leg is that route and there is no `stream_layers` leg; the graph modes refuse it; 'bench/skip' = the skip-connection
+architecture, whose stream is a streaming front, per-layer launches on per-chunk skip accumulators and the head launch -- one route, no
+`stream_layers` leg and no graph modes either), random weights, one GPU, steady state (every session has emitted more
 than timeshard.chain_halo samples).
 
 Legs of a cell (sessions x chunk):
@@ -101,7 +103,8 @@ def main():
                     help='the ragged-tick cells as graph replays (StreamingVocoder.graphed_varlen against the eager push_varlen) instead of the default legs')
     ap.add_argument('--live', action='store_true', help='the streaming mel front-end in front of push_varlen (audio_frontend.StreamingMel) instead of the default legs')
     ap.add_argument('--case', default='default', help="the hparams case whose model streams: 'default', 'bench/c2' for the shared-net "
-                    "architecture (one two-output net per flow), 'bench/c5' for transposed-conv conditioning; the result line names it")
+                    "architecture (one two-output net per flow), 'bench/c5' for transposed-conv conditioning, 'bench/skip' for the skip-connection "
+                    "architecture; the result line names it")
     args = ap.parse_args()
 
     import numpy as np
@@ -126,9 +129,11 @@ def main():
 
     # a transposed-conv case ('bench/c5') makes the request for its streaming form: per-layer launches with the condition GEMM inside
     per_sample = cfg.cond_upsample_method == 'transposed_conv'
+    # ... and a skip-connection case ('bench/skip') for its own: the front, per-layer launches on the chunk's skip accumulators, the head
+    skip = bool(cfg.use_skip_connection)
 
     def open_stream(model, slots):
-        return model.open_stream(slots=slots, transposed_conv=per_sample)
+        return model.open_stream(slots=slots, transposed_conv=per_sample, use_skip_connection=skip)
 
     def rand(*shape):
         return torch.from_numpy(rng.uniform(-1, 1, shape).astype(np.float32)).to(dev)
@@ -429,7 +434,7 @@ def main():
                 'overlap': (lambda: over(None, mel_o, z=z_o, verify=False)[:, halo:], lambda: engine.verify_enqueued('overlap')),
                 'rows': (lambda: model(None, mel_r, z=z_r, verify=False), lambda: engine.verify_enqueued('rows')),
             }
-            if per_sample:          # (one streaming route only: PERSIST plays no part)
+            if per_sample or skip:          # (one streaming route only: PERSIST plays no part)
                 del legs['stream_layers']
             stream_legs = [name for name in ('stream', 'stream_layers') if name in legs]
             cell = {'sessions': S, 'chunk': chunk, 'stream_rows': S * chunk, 'overlap_rows': S * (chunk + halo), 'launches': {}}
